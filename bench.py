@@ -107,6 +107,30 @@ WORKLOADS = {
     "small": ("s1", 480, 270, 4, 3, "480x270, 16 spp, 3 bounces, MandelBox (quick check)"),
 }
 
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs writes at most this much, .npy headers included
+NPY_HEADER_BYTES = 128  # per file (np.save of a small-rank array)
+
+
+def dump_outputs(out_dir, film):
+    """--dump-outputs: writes the film one timed step returned (the flat per-pixel channels rayn_hip_render_frame_device fills) as out_dir/<channel>.npy,
+    float32.  A film above DUMP_LIMIT_BYTES is written as one fixed, seeded sample of pixels, the same in every channel, and pixel_index.npy (float64)
+    names the sampled pixels.  Returns the record for the JSON line."""
+    import numpy as np
+    arrays = {k: v.detach().cpu().numpy().astype(np.float32, copy=False) for k, v in film.items()}
+    n = len(next(iter(arrays.values())))
+    total = sum(a.nbytes for a in arrays.values())
+    sampled = None
+    if total + NPY_HEADER_BYTES * len(arrays) > DUMP_LIMIT_BYTES:
+        m = (DUMP_LIMIT_BYTES - NPY_HEADER_BYTES * (len(arrays) + 1)) // (total // n + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+        sampled = int(m)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "arrays": {k: list(a.shape) for k, a in arrays.items()}, "pixels": n, "sampled_pixels": sampled}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -129,7 +153,11 @@ def main():
                     "xGMI, no process group) - the path a rayn host bound per bindings/ uses for src/film.rs:630-658; same JSON line with per-device render times")
     ap.add_argument("--force-dist", action="store_true", help="run the N>1 code path (process group, barrier, all-reduce, FilmGather incl. rank 0's own block) even at "
                     "world size 1: executes the RCCL path of the multi-GPU launch on a one-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, rank 0 writes the film of the last timed step as DIR/<channel>.npy "
+                    "(float32; a film above 64 MB as a fixed, seeded pixel sample named by DIR/pixel_index.npy) - inputs are identical from run to run, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.single_process:
         # `python bench.py --gpus N` without a launcher: become the driver's own launch line (one rank per GPU under torch.distributed.run).
         # exec, not spawn: same stdout (ONE JSON line from rank 0), same exit code, nothing of this process left behind.
@@ -298,6 +326,8 @@ def main():
         result = step(timed=True)
     fence()
     dt = time.perf_counter() - t0
+    # before anything else renders into the film (film check, rooflines, named workload)
+    dumped = dump_outputs(args.dump_outputs, result) if args.dump_outputs and rank == 0 else None
     stats = ctx.stats()
     segments_per_step = stats["segments"]
     per_rank = None
@@ -562,6 +592,8 @@ def main():
             out["imbalance"] = round(max(rms) / mean_r, 4) if mean_r > 0 else None
         if film_check is not None:
             out["film_check"] = film_check  # gathered film == single-rank film, bit for bit
+        if dumped is not None:
+            out["outputs"] = dumped
         if use_dist and args.backend != "nccl":
             out["config"]["parallelism"] += f" [TEST MODE: backend {args.backend}, gather staged through host memory" + (", all ranks on one GPU" if args.share_gpu else "") + "]"
         print(json.dumps(out), flush=True)

@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -96,12 +97,13 @@ def test_bench_rccl_code_path_world1():
 
 
 @pytest.mark.gpu
-def test_bench_line_contract_n1():
+def test_bench_line_contract_n1(tmp_path):
     """The default (N = 1) launch on a small workload: ONE JSON line with the driver's keys, a live `roofline` (dominant march kernel,
     HIP-event timed), `roofline_hbm`, `cpu_baseline` (kind "port", bounded sample), `cold_ms` (fresh context -> first frame through
-    the host-buffer entry) and the build variant "product"."""
+    the host-buffer entry) and the build variant "product"; --dump-outputs writes the last timed step's film whole."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "small", "--cpu-seconds", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "small", "--cpu-seconds", "1",
+           "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -125,6 +127,29 @@ def test_bench_line_contract_n1():
     assert abs(out["cold_detail"]["context_ms"] + out["cold_detail"]["first_frame_ms"] - out["cold_ms"]) < 0.2
     assert "per_rank" not in out  # single-process line: no process group
     assert all(0 <= v["frac"] < 1.5 for v in out["roofline_hbm"]["kernels"].values())
+    # the dumped film is the frame the timed path computed: every channel whole (480 x 270 x 40 B is far below the limit), float32, and bit for
+    # bit the film of a fresh single render of the same workload on a context of its own
+    import bench
+    import rayn_amd
+    import torch
+    from rayn_amd import setup as S
+    from common import bits_equal
+    scene, W, H, samples, bounces, _ = bench.WORKLOADS["small"]
+    assert out["outputs"]["sampled_pixels"] is None and out["outputs"]["pixels"] == W * H
+    cam, wld = S.SCENES[scene]((W, H))
+    p = rayn_amd.frame_params(W, H, samples, bounces)
+    tabs = rayn_amd.build_tables(4 * samples, bounces, p.volume_marches, p.frame, W, H)
+    ctx = rayn_amd.Context(0)
+    ctx.upload_world(wld.to_desc(cam))
+    ref = rayn_amd.film.alloc_device_film(W, H, "cuda:0")
+    ctx.render_device(p, [torch.from_numpy(t).cuda() for t in tabs], ref)
+    torch.cuda.synchronize()
+    ctx.close()
+    for k, v in ref.items():
+        a = np.load(tmp_path / "dump" / f"{k}.npy")
+        want = v.cpu().numpy()
+        assert a.dtype == np.float32 and a.shape == want.shape and bits_equal(a, want), k
+    assert np.load(tmp_path / "dump" / "color.npy").max() > 0
 
 
 @pytest.mark.gpu
