@@ -16,8 +16,13 @@ frame is partitioned by tiles (rotating round-robin) across ranks and gathered t
   python bench.py --gpus N --single-process ...   (ONE process, one rayn_hip_create_multi context over N GPUs, peer-copy gather:
                                                    what a rayn host bound per bindings/ runs for src/film.rs:630-658)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. "roofline" (dominant kernel
-class, HIP-event timed live) and "cpu_baseline" (the CPU oracle on a bounded tile sample, N=1 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the
+steps, writes --dump-outputs and prints the line; everything else is measured with --full only: "cold_ms"
+(a fresh context's first frame), "roofline" / "roofline_hbm" / "kernel_ms" (dominant kernel class and
+per-class times, HIP-event timed live), "cpu_baseline" (the CPU oracle on a bounded tile sample, N=1 only)
+and, for the default workload, "named_workload".  Without --full those keys are null (named_workload absent).
+
+  python bench.py --full --gpus 1 --steps 2 --warmup 1
 """
 import argparse
 import json
@@ -138,10 +143,14 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed frames (default 2; 20 for the sub-100-ms workloads shipped / c1 / small)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed frames before them (default 1; 3 for shipped / c1 / small)")
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target wall time of the CPU-oracle baseline sample (0 = skip)")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-named", action="store_true", help="default workload only: skip the secondary measurement of the metric's literally named workload (bulb3) reported as `named_workload`")
-    ap.add_argument("--no-cold", action="store_true", help="skip the cold first frame through the host-buffer entry (cold_ms)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need, each outside the timed region: the cold first frame (cold_ms), "
+                    "the rooflines and per-kernel-class times, the CPU-oracle baseline and, for the default workload, the named workload.  Without it a run sets up, "
+                    "warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: target wall time of the CPU-oracle baseline sample (0 = skip)")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the rooflines (and with them the named workload)")
+    ap.add_argument("--no-named", action="store_true", help="with --full, default workload only: skip the secondary measurement of the metric's literally named workload (bulb3) "
+                    "reported as `named_workload`")
+    ap.add_argument("--no-cold", action="store_true", help="with --full: skip the cold first frame through the host-buffer entry (cold_ms)")
     ap.add_argument("--fma-policy", type=int, default=0, choices=[0, 1], help="0: unfused mul_add = rayn's default build (default); 1: fused = rayn built with +fma")
     # test aids for the N>1 path on a box with fewer GPUs than ranks (never used by the driver's launch)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend (nccl = RCCL; gloo stages the gather through host memory)")
@@ -226,9 +235,9 @@ def main():
     ctx.set_fma_policy(args.fma_policy)
     cold_ms = None
     cold_detail = None
-    measure_cold = not use_dist and not args.no_cold and n_devices == 1
+    measure_cold = args.full and not use_dist and not args.no_cold and n_devices == 1
     if not measure_cold:
-        # no cold frame is measured (N > 1, --single-process, --no-cold): the context's FIRST frame is then the first warm-up frame, and the library's first-frame
+        # no cold frame is measured (no --full, N > 1, --single-process, --no-cold): the context's FIRST frame is then the first warm-up frame, and the library's first-frame
         # policy (small arenas for hosts that render one frame per process, rayn_hip_set_cold_bytes) would move the one-off growth of the arenas into the SECOND
         # frame - the first timed step at --warmup 1.  Full-size arenas at once: every one-off cost lands in the warm-up.
         ctx.set_cold_bytes(0)
@@ -468,11 +477,11 @@ def main():
     roofline = None
     roofline_hbm = None
     kernel_ms = None
-    if not args.no_roofline and n_devices == 1:
+    if args.full and not args.no_roofline and n_devices == 1:
         roofline, roofline_hbm, kernel_ms = measure_rooflines(scene, args.workload)
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and n_devices == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and n_devices == 1 and args.cpu_seconds > 0:
         from oracle import oracle_py as O
         threads = usable_cpus()  # what the container may use (cgroup quota), not the host's thread count
         # The oracle runs a tile serially on one thread (like the reference).  A 16x16 tile of this workload is about a minute
@@ -515,9 +524,9 @@ def main():
 
     # BASELINE.json words its metric "1920x1080 Mandelbulb @1024spp".  The reference has no Mandelbulb, so `value` is measured on the reference's own
     # fractal at that size (c3); the literally named workload - the Mandelbulb EXTENSION with the same volume, same size, same tables - is measured right after,
-    # on the same context, OUTSIDE the timed region, and reported beside it (one warm-up + two timed frames, ~30 s).  `--workload bulb3` gives it a full line.
+    # on the same context, OUTSIDE the timed region, and reported beside it (one warm-up + two timed frames, ~30 s).  `--full --workload bulb3` gives it a full line.
     named = None
-    if rank == 0 and world == 1 and n_devices == 1 and args.workload == "c3" and not args.no_named and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and n_devices == 1 and args.workload == "c3" and not args.no_named and not args.no_roofline:
         try:
             scene_b, Wb, Hb, samples_b, bounces_b, desc_b = WORKLOADS["bulb3"]
             assert (Wb, Hb, samples_b, bounces_b) == (W, H, samples, bounces)  # same frame parameters and sample tables
@@ -539,7 +548,7 @@ def main():
                                                        "flop_per_dist_eval", "whole_frame", "bulb_stage_occupancy", "zero_throughput_elision", "lanes_enabled", "valu_issue") if k in rf_b},
                      "kernel_ms": kms_b,
                      "note": "secondary measurement on the same context after the timed region of `value` (one warm-up + two timed frames, then one profiling and one counting frame); "
-                             "parity of this workload: tests/test_config_digests.py [bulb3]; cpu_baseline and queue-kernel rooflines: python bench.py --workload bulb3 (profiles/r06_bench_bulb3_*.json)"}
+                             "parity of this workload: tests/test_config_digests.py [bulb3]; cpu_baseline and queue-kernel rooflines: python bench.py --full --workload bulb3 (profiles/r06_bench_bulb3_*.json)"}
             ctx.upload_world(wd)
         except Exception as e:  # never lose the main line to the secondary measurement
             named = {"error": f"{type(e).__name__}: {e}"}

@@ -96,13 +96,62 @@ def test_bench_rccl_code_path_world1():
     _check_per_rank(out, 1)
 
 
+def _check_dump_is_a_fresh_render(out, dump_dir, workload):
+    """The dumped film is the frame the timed path computed: every channel whole (480 x 270 x 40 B is far below the limit), float32, and bit for
+    bit the film of a fresh single render of the same workload on a context of its own."""
+    import bench
+    import rayn_amd
+    import torch
+    from rayn_amd import setup as S
+    from common import bits_equal
+    scene, W, H, samples, bounces, _ = bench.WORKLOADS[workload]
+    assert out["outputs"]["sampled_pixels"] is None and out["outputs"]["pixels"] == W * H
+    cam, wld = S.SCENES[scene]((W, H))
+    p = rayn_amd.frame_params(W, H, samples, bounces)
+    tabs = rayn_amd.build_tables(4 * samples, bounces, p.volume_marches, p.frame, W, H)
+    ctx = rayn_amd.Context(0)
+    ctx.upload_world(wld.to_desc(cam))
+    ref = rayn_amd.film.alloc_device_film(W, H, "cuda:0")
+    ctx.render_device(p, [torch.from_numpy(t).cuda() for t in tabs], ref)
+    torch.cuda.synchronize()
+    ctx.close()
+    for k, v in ref.items():
+        a = np.load(dump_dir / f"{k}.npy")
+        want = v.cpu().numpy()
+        assert a.dtype == np.float32 and a.shape == want.shape and bits_equal(a, want), k
+    assert np.load(dump_dir / "color.npy").max() > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_is_lean(tmp_path):
+    """A plain (N = 1) run does only what its headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  The line has
+    the driver's keys with the headline figure; what --full measures (cold frame, rooflines, kernel times, CPU baseline) is null."""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "small", "--dump-outputs", str(tmp_path / "dump")]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in out, k
+    assert out["metric"] == "Mpath-samples/sec" and out["unit"] == "Mpath-samples/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 1
+    assert out["value"] > 0 and abs(out["value"] - out["config"]["paths_per_step"] / out["ms_per_step"] / 1e3) < 1e-2 * out["value"]
+    assert out["segments_per_step"] > out["config"]["paths_per_step"] and out["config"]["build_variant"] == "product"
+    for k in ("roofline", "roofline_hbm", "kernel_ms", "cpu_baseline", "cold_ms"):
+        assert out[k] is None, k
+    assert "cold_detail" not in out and "named_workload" not in out and "per_rank" not in out
+    _check_dump_is_a_fresh_render(out, tmp_path / "dump", "small")
+
+
 @pytest.mark.gpu
 def test_bench_line_contract_n1(tmp_path):
-    """The default (N = 1) launch on a small workload: ONE JSON line with the driver's keys, a live `roofline` (dominant march kernel,
+    """The default (N = 1) launch on a small workload with --full: ONE JSON line with the driver's keys, a live `roofline` (dominant march kernel,
     HIP-event timed), `roofline_hbm`, `cpu_baseline` (kind "port", bounded sample), `cold_ms` (fresh context -> first frame through
     the host-buffer entry) and the build variant "product"; --dump-outputs writes the last timed step's film whole."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "small", "--cpu-seconds", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--workload", "small", "--cpu-seconds", "1",
            "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
@@ -127,29 +176,7 @@ def test_bench_line_contract_n1(tmp_path):
     assert abs(out["cold_detail"]["context_ms"] + out["cold_detail"]["first_frame_ms"] - out["cold_ms"]) < 0.2
     assert "per_rank" not in out  # single-process line: no process group
     assert all(0 <= v["frac"] < 1.5 for v in out["roofline_hbm"]["kernels"].values())
-    # the dumped film is the frame the timed path computed: every channel whole (480 x 270 x 40 B is far below the limit), float32, and bit for
-    # bit the film of a fresh single render of the same workload on a context of its own
-    import bench
-    import rayn_amd
-    import torch
-    from rayn_amd import setup as S
-    from common import bits_equal
-    scene, W, H, samples, bounces, _ = bench.WORKLOADS["small"]
-    assert out["outputs"]["sampled_pixels"] is None and out["outputs"]["pixels"] == W * H
-    cam, wld = S.SCENES[scene]((W, H))
-    p = rayn_amd.frame_params(W, H, samples, bounces)
-    tabs = rayn_amd.build_tables(4 * samples, bounces, p.volume_marches, p.frame, W, H)
-    ctx = rayn_amd.Context(0)
-    ctx.upload_world(wld.to_desc(cam))
-    ref = rayn_amd.film.alloc_device_film(W, H, "cuda:0")
-    ctx.render_device(p, [torch.from_numpy(t).cuda() for t in tabs], ref)
-    torch.cuda.synchronize()
-    ctx.close()
-    for k, v in ref.items():
-        a = np.load(tmp_path / "dump" / f"{k}.npy")
-        want = v.cpu().numpy()
-        assert a.dtype == np.float32 and a.shape == want.shape and bits_equal(a, want), k
-    assert np.load(tmp_path / "dump" / "color.npy").max() > 0
+    _check_dump_is_a_fresh_render(out, tmp_path / "dump", "small")
 
 
 @pytest.mark.gpu
@@ -158,7 +185,7 @@ def test_bench_bulb_prices_the_mandelbulb_by_counted_iterations():
     below the 8 x 84 + 10 = 682 of eight full steps (orbits escape at |w|^2 > 256), above one step."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", RAYN_HIP_ENV_TUNING="1", RAYN_HIP_BATCH_PATHS=str(1 << 22))
     r = subprocess.run([sys.executable, "-c", "import bench, sys; bench.WORKLOADS['bulb'] = ('bulb', 240, 136, 4, 3, 'small Mandelbulb (test)'); "
-                        "sys.argv = ['bench.py', '--workload', 'bulb', '--steps', '1', '--warmup', '1', '--cpu-seconds', '0', '--no-cold']; bench.main()"],
+                        "sys.argv = ['bench.py', '--full', '--workload', 'bulb', '--steps', '1', '--warmup', '1', '--cpu-seconds', '0', '--no-cold']; bench.main()"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -219,11 +246,11 @@ def test_bench_single_process_multi_device(entries):
 
 @pytest.mark.gpu
 def test_bench_default_line_carries_the_named_workload():
-    """The default workload's line (c3: the reference's fractal at the metric's size) also reports the metric's LITERALLY named workload (bulb3: the
+    """With --full, the default workload's line (c3: the reference's fractal at the metric's size) also reports the metric's LITERALLY named workload (bulb3: the
     Mandelbulb extension, same size / volume / tables), measured on the same context after the timed region.  Both shrunk here to test size."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", RAYN_HIP_ENV_TUNING="1", RAYN_HIP_BATCH_PATHS=str(1 << 22))
     code = ("import bench, sys; bench.WORKLOADS['c3'] = ('s2', 160, 96, 4, 3, 'small c3 (test)'); bench.WORKLOADS['bulb3'] = ('bulbv', 160, 96, 4, 3, 'small bulb3 (test)'); "
-            "sys.argv = ['bench.py', '--steps', '1', '--warmup', '1', '--cpu-seconds', '0', '--no-cold']; bench.main()")
+            "sys.argv = ['bench.py', '--full', '--steps', '1', '--warmup', '1', '--cpu-seconds', '0', '--no-cold']; bench.main()")
     r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -242,3 +269,9 @@ def test_bench_default_line_carries_the_named_workload():
     code2 = code.replace("'--no-cold']", "'--no-cold', '--no-named']")
     r2 = subprocess.run([sys.executable, "-c", code2], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r2.returncode == 0 and "named_workload" not in json.loads([ln for ln in r2.stdout.splitlines() if ln.startswith("{")][0])
+    # nor in a plain run: without --full the default workload's line is the headline figure alone
+    code3 = code.replace("'--full', ", "")
+    r3 = subprocess.run([sys.executable, "-c", code3], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r3.returncode == 0, r3.stdout[-2000:] + r3.stderr[-2000:]
+    out3 = json.loads([ln for ln in r3.stdout.splitlines() if ln.startswith("{")][0])
+    assert "named_workload" not in out3 and out3["roofline"] is None and out3["config"]["workload"] == "small c3 (test)"

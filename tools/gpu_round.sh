@@ -30,11 +30,11 @@ for WL in $WLS; do
   cp gpurun_out/prof_${WL}_2workers_kernel_stats.csv gpurun_out/${R}_${WL}_${TAG}_kernel_stats_2workers.csv
   cp gpurun_out/pmc_fetch_$WL.csv gpurun_out/${R}_${WL}_${TAG}_pmc_fetch_size.csv
   cp gpurun_out/pmc_write_$WL.csv gpurun_out/${R}_${WL}_${TAG}_pmc_write_size.csv
-  timeout 1200 python bench.py --workload $WL 2>&1 | tail -1 > gpurun_out/${R}_bench_${WL}_$TAG.json
-  timeout 900 python bench.py --workload $WL --fma-policy 1 --cpu-seconds 0 2>&1 | tail -1 > gpurun_out/${R}_bench_${WL}_${TAG}_fma1.json
+  timeout 1200 python bench.py --full --workload $WL 2>&1 | tail -1 > profiles/${R}_bench_${WL}_$TAG.json
+  timeout 900 python bench.py --full --workload $WL --fma-policy 1 --cpu-seconds 0 2>&1 | tail -1 > profiles/${R}_bench_${WL}_${TAG}_fma1.json
   python -c "
 import json
-for f in ('gpurun_out/${R}_bench_${WL}_$TAG.json','gpurun_out/${R}_bench_${WL}_${TAG}_fma1.json'):
+for f in ('profiles/${R}_bench_${WL}_$TAG.json','profiles/${R}_bench_${WL}_${TAG}_fma1.json'):
     j=json.load(open(f)); print('VALUE', j['value'], j['ms_per_step']); print(j['kernel_ms']); print({k:j['roofline'][k] for k in ('kernel','achieved','frac','traffic')}); print(j['cpu_baseline'])
     for k, v in j['roofline_hbm']['kernels'].items(): print('   ', k[:40], v['ms'], v['frac'])"
   cat gpurun_out/pmc_hbm_$WL.txt
@@ -47,12 +47,12 @@ timeout 600 python tools/share_profile.py 5 64 c5 2>&1 | tail -1 | sed 's/^/c5 1
 timeout 600 python tools/share_profile.py 0 1 bulb 2>&1 | tail -1 | sed 's/^/bulb: /'
 timeout 600 python tools/host_rate.py c3 2>&1 | tail -1
 timeout 600 python tools/host_rate.py c2 2>&1 | tail -1
-timeout 600 python bench.py --workload c4 --steps 1 --warmup 1 --no-roofline --cpu-seconds 0 2>&1 | tail -1 > gpurun_out/${R}_bench_c4_$TAG.json; cat gpurun_out/${R}_bench_c4_$TAG.json | cut -c1-200
+timeout 600 python bench.py --full --workload c4 --steps 1 --warmup 1 --no-roofline --cpu-seconds 0 2>&1 | tail -1 > profiles/${R}_bench_c4_$TAG.json; cut -c1-200 profiles/${R}_bench_c4_$TAG.json
 if [ -n "$WHOLE_C5" ]; then  # 136 G paths, ~3 GPU-minutes: only on request (r3's number stands, the march kernels did not change in r4)
-timeout 900 python bench.py --workload c5 --steps 1 --warmup 0 --no-roofline --no-cold --cpu-seconds 0 2>&1 | tail -1 > gpurun_out/${R}_bench_c5_$TAG.json; cat gpurun_out/${R}_bench_c5_$TAG.json | cut -c1-200
+timeout 900 python bench.py --workload c5 --steps 1 --warmup 0 2>&1 | tail -1 > profiles/${R}_bench_c5_$TAG.json; cut -c1-200 profiles/${R}_bench_c5_$TAG.json
 fi
 # the reference's own workload (src/main.rs:47-82): bench line with cold_ms, whole-frame 16x16 CPU leg; what an 8-GPU launch waits for
-timeout 600 python bench.py --workload shipped 2>&1 | tail -1 > gpurun_out/${R}_bench_shipped_$TAG.json; cut -c1-400 gpurun_out/${R}_bench_shipped_$TAG.json
+timeout 600 python bench.py --full --workload shipped 2>&1 | tail -1 > profiles/${R}_bench_shipped_$TAG.json; cut -c1-400 profiles/${R}_bench_shipped_$TAG.json
 timeout 600 python tools/share_balance.py 8 c2 2>&1 | tail -1
 timeout 600 python tools/share_balance.py 8 c3 2>&1 | tail -1
 for i in 1 2 3; do timeout 120 python tools/cold_breakdown.py shipped 0 2>&1 | tail -1; done
