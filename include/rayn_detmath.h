@@ -209,7 +209,7 @@ RAYN_HD void dm_sincosf(float xf, float* sn, float* cs) {
     if (dm_isnan(xf) || ax == dm_inff()) { *sn = dm_nanf(); *cs = dm_nanf(); return; }
     double s, c;
     dm_sincos_core((double)xf, &s, &c);
-    *sn = (float)s;
+    *sn = xf == 0.0f ? xf : (float)s; /* sin(-0) = -0: the core's r + r * (z * ps) is +0 for r = -0 */
     *cs = (float)c;
 }
 
@@ -222,7 +222,7 @@ RAYN_HD float dm_tanf(float xf) {
     if (dm_isnan(xf) || ax == dm_inff()) return dm_nanf();
     double s, c;
     dm_sincos_core((double)xf, &s, &c);
-    return (float)(s / c);
+    return xf == 0.0f ? xf : (float)(s / c); /* tan(-0) = -0 (see dm_sincosf) */
 }
 
 /* atan of t in [0,1]. */

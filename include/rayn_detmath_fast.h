@@ -223,7 +223,7 @@ RAYN_HD void dmf_sincosf(float xf, float* sn, float* cs) {
         dmf_sincos_core((double)xf, &s, &c);
         float fs, fc;
         const bool ok_s = dmf_round_safe(s, DMF_EPS_SINCOS, &fs), ok_c = dmf_round_safe(c, DMF_EPS_SINCOS, &fc);
-        if (ok_s && ok_c) { *sn = fs; *cs = fc; return; }
+        if (ok_s && ok_c) { *sn = xf == 0.0f ? xf : fs; *cs = fc; return; } // sin(+-0) = +-0, as dm_sincosf
     }
     dmf_slow_sincos(xf, sn, cs);
 }
@@ -235,7 +235,7 @@ RAYN_HD float dmf_tanf(float xf) {
     if (xf > -1.0e4f && xf < 1.0e4f) {
         double s, c;
         dmf_sincos_core((double)xf, &s, &c);
-        if (dmf_round_safe(s / c, DMF_EPS_TAN, &out)) return out;
+        if (dmf_round_safe(s / c, DMF_EPS_TAN, &out)) return xf == 0.0f ? xf : out; // tan(+-0) = +-0, as dm_tanf
     }
     return dmf_slow_tan(xf);
 }

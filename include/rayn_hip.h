@@ -367,7 +367,28 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *   result: 6 Newton-Raphson a/b, 7 IEEE a/b, 8 sqrt(a), 9/10/11 component x/y/z of v/|v| and
  *   12 |v| (a holds n xyz triples), 13 exhaustive sqrt sweep (out[i] = mismatch count over the
  *   65536 float bit patterns starting at bits(a[i])), 14 ln(a) as the Mandelbulb estimator evaluates it (dmf_logf),
- *   15 exhaustive sweep of 1 / sqrt(a) as the kernels evaluate it (rcp_sqrt_rn) against the IEEE sqrt and division (mismatch count over 65536 patterns), 16 that value. */
+ *   15 exhaustive sweep of 1 / sqrt(a) as the kernels evaluate it (rcp_sqrt_rn) against the IEEE sqrt and division (mismatch count over 65536 patterns), 16 that value.
+ *   rayn_hip_probe_shading    the shading half of the path: the SAME per-lane device functions k_raygen / k_shade_setup / k_shade_finish call, on n lanes
+ *                             of caller records, under the ctx's mul_add policy.  Lane i reads in[i * IN .. +IN) and writes out[i * OUT .. +OUT):
+ *     op  function (reference)                                        IN  in record                                   OUT  out record
+ *      0  Camera::get_rays of the uploaded camera (src/camera.rs)      5  uvx, uvy, lens0, lens1, t0                   6  origin xyz, dir xyz
+ *      1  concentric_circle_map (src/math.rs:201-219)                  2  u0, u1                                       2  x, y
+ *      2  cosine_weighted_in_hemisphere (src/math.rs:99-103)           2  u0, u1                                       3  xyz
+ *      3  cosine_power_weighted (src/math.rs:106-113)                  3  u0, u1, power                                3  xyz
+ *      4  get_orthonormal_basis (src/math.rs:49-59)                    3  n xyz                                        9  columns c0, c1, c2
+ *      5  f_schlick (src/math.rs:122-124)                              2  cos, f0                                      1  value
+ *      6  BSDF::f of material `index`, as called: f(arg0, arg1, n)     9  arg0 xyz, arg1 xyz, n xyz                    3  rgb
+ *      7  BSDF::le of material `index`                                 3  wo xyz                                       3  rgb
+ *      8  BSDF::scatter of material `index` at a shading point whose   11 wo xyz, normal xyz, s1, u0, u1, u2, u3       7  wi xyz, f rgb, pdf
+ *         basis is get_orthonormal_basis(normal), as k_shade_setup builds it
+ *      9  SphereLight::sample of light `index` (src/light.rs:38-72)    5  u0, u1, p xyz                                4  point xyz, pdf
+ *     10  SphereLight::sample_volume_scattering of light `index` (:75-102)  8  sample, ro xyz, rd xyz, max_distance       2  dist, pdf
+ *     11  light index floor(s * nl) clamped to nl - 1, nl = `index`     1  s                                            1  index as float
+ *     12  FilterImportanceSampler::sample (src/filter.rs:222-235)      1  u                                            1  value
+ *         with aux = the RAYN_FIS_TABLE_SIZE-float inverse CDF (aux is ignored by the other ops)
+ *   Camera closures (rayn_camera.animated) are evaluated at t0, which the reference takes from LANE 0 of the ray-gen packet (a caller comparing
+ *   with a 4-wide packet passes one t0 per group of four lanes).  Op 6 rejects Sky (its f panics in the reference) and op 8 takes only Lambertian and
+ *   Dielectric: Sky and Emissive never scatter (receives_light is false), so those paths are never reached and are not probed. */
 int rayn_hip_probe_sdf_dist(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t hitable_index,
                             const float* pts_xyz, float* out, uint32_t n);
 int rayn_hip_probe_extend(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t depth,
@@ -377,6 +398,8 @@ int rayn_hip_probe_shadow(rayn_ctx* ctx, const rayn_frame_params* p, const float
                           const float* end_xyz, float* out, uint32_t n);
 int rayn_hip_probe_detmath(rayn_ctx* ctx, uint32_t op, const float* a, const float* b, float* out,
                            uint32_t n);
+int rayn_hip_probe_shading(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t op, uint32_t index,
+                           const float* in, float* out, const float* aux, uint32_t n);
 
 #ifdef __cplusplus
 }

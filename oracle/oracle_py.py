@@ -161,3 +161,24 @@ def detmath(op, a, b=None, fma=False):
     out = np.zeros_like(a)
     L.oracle_detmath(C.c_uint32(op), _fp(a), _fp(b), _fp(out), C.c_uint64(a.size))
     return out
+
+
+# floats per lane read / written by each op of oracle_probe_shading / rayn_hip_probe_shading (op table: include/rayn_hip.h)
+SHADING_IN = (5, 2, 2, 3, 3, 2, 9, 3, 11, 5, 8, 1, 1)
+SHADING_OUT = (6, 2, 3, 3, 9, 1, 3, 3, 7, 4, 2, 1, 1)
+
+
+def probe_shading(world_desc, op, index, inp, aux=None, fma=False):
+    """The oracle's own shading functions on n lanes of records (op table: include/rayn_hip.h): inp [n, SHADING_IN[op]] -> [n, SHADING_OUT[op]].
+    aux = the 512-float inverse CDF of op 12."""
+    L = lib(fma)
+    inp = np.ascontiguousarray(inp, np.float32).reshape(-1, SHADING_IN[op])
+    out = np.zeros((len(inp), SHADING_OUT[op]), np.float32)
+    a = None if aux is None else np.ascontiguousarray(aux, np.float32)
+    if a is not None:
+        assert a.size == 512, a.size
+    rc = L.oracle_probe_shading(C.byref(world_desc), C.c_uint32(op), C.c_uint32(index), _fp(inp), _fp(out),
+                                None if a is None else _fp(a), C.c_uint64(len(inp)))
+    if rc != 0:
+        raise ValueError(f"oracle_probe_shading rejected op {op} index {index}")
+    return out

@@ -1335,6 +1335,72 @@ void oracle_detmath(uint32_t op, const float* a, const float* b, float* out, uin
     }
 }
 int oracle_fma_policy() { return RAYN_FMA_POLICY; }
+/* Counterpart of rayn_hip_probe_shading (op table, record widths and semantics: include/rayn_hip.h) through this file's OWN
+ * functions, four lanes per call like the reference's packets: Camera::get_rays, the sampling maps, make_bsdf's BSDFs at a
+ * WShadingPoint::make shading point, World's SphereLights, light_index as Integrator::integrate calls it, fis_sample.  A lane
+ * count that is not a multiple of 4 pads the last packet with copies of its first lane.  Returns -1 for an op / index the device probe
+ * rejects too. */
+int oracle_probe_shading(const rayn_world_desc* wd, uint32_t op, uint32_t index, const float* in, float* out, const float* aux, uint64_t n) {
+    static const uint32_t IN[13] = {5, 2, 2, 3, 3, 2, 9, 3, 11, 5, 8, 1, 1}, OUT[13] = {6, 2, 3, 3, 9, 1, 3, 3, 7, 4, 2, 1, 1};
+    if (!wd || op > 12 || !in || !out) return -1;
+    World w(*wd, Config{256, 100, 0.5f});
+    if (op >= 6 && op <= 8) {
+        if (index >= w.materials.size()) return -1;
+        const uint32_t k = wd->materials[index].kind;
+        if (op == 6 && k == RAYN_MAT_SKY) return -1;
+        if (op == 8 && k != RAYN_MAT_LAMBERTIAN && k != RAYN_MAT_DIELECTRIC) return -1;
+    }
+    if ((op == 9 || op == 10) && index >= w.lights.size()) return -1;
+    if ((op == 11 && index == 0) || (op == 12 && !aux)) return -1;
+    const Camera cam(wd->camera);
+    const uint32_t ni = IN[op], no = OUT[op];
+    for (uint64_t base = 0; base < n; base += 4) {
+        F4 a[11];
+        for (uint32_t k = 0; k < ni; k++)
+            for (int l = 0; l < 4; l++) a[k].v[l] = in[(base + l < n ? base + l : base) * ni + k];
+        F4 r[9];
+        auto w3 = [&](int k) { return W3(a[k], a[k + 1], a[k + 2]); };
+        auto put3 = [&](int k, const W3& v) { r[k] = v.x; r[k + 1] = v.y; r[k + 2] = v.z; };
+        switch (op) {
+        case 0: {
+            const size_t nums[4] = {0, 1, 2, 3};
+            const WRay ray = cam.get_rays(0.0f, nums, 0, 0, W2{a[0], a[1]}, a[4], &a[2]);
+            put3(0, ray.origin); put3(3, ray.dir);
+            break;
+        }
+        case 1: { const W2 v = concentric_circle_map(a[0], a[1]); r[0] = v.x; r[1] = v.y; break; }
+        case 2: put3(0, cosine_weighted_in_hemisphere(a[0], a[1])); break;
+        case 3: put3(0, cosine_power_weighted(a[0], a[1], a[2])); break;
+        case 4: { const Wat3 m = get_orthonormal_basis(w3(0)); put3(0, m.cols[0]); put3(3, m.cols[1]); put3(6, m.cols[2]); break; }
+        case 5: r[0] = f_schlick(a[0], a[1]); break;
+        case 6: put3(0, w.materials[index]->f(w3(0), w3(3), w3(6))); break;
+        case 7: put3(0, w.materials[index]->le(w3(0), WShadingPoint())); break;
+        case 8: {
+            WHit hit; hit.ray = WRay(); hit.t = F4(0.0f);
+            const WShadingPoint sp = WShadingPoint::make(hit, W3(F4(0.0f), F4(0.0f), F4(0.0f)), F4(0.0f), w3(3));
+            const WScatteringEvent se = w.materials[index]->scatter(w3(0), sp, a[6], &a[7]);
+            put3(0, se.wi); put3(3, se.f); r[6] = se.pdf;
+            break;
+        }
+        case 9: {
+            W3 pt; WSrgb li; F4 pdf;
+            w.lights[index].sample(&a[0], w3(2), &pt, &li, &pdf);
+            put3(0, pt); r[3] = pdf;
+            break;
+        }
+        case 10: w.lights[index].sample_volume_scattering(a[0], w3(1), w3(4), a[7], &r[0], &r[1]); break;
+        case 11: {
+            const F4 lts = floor4(a[0] * F4((float)index));
+            for (int l = 0; l < 4; l++) r[0].v[l] = (float)light_index(lts.v[l], index);
+            break;
+        }
+        default: for (int l = 0; l < 4; l++) r[0].v[l] = fis_sample(aux, a[0].v[l]); break;
+        }
+        for (int l = 0; l < 4 && base + l < n; l++)
+            for (uint32_t k = 0; k < no; k++) out[(base + l) * no + k] = r[k].v[l];
+    }
+    return 0;
+}
 /* Host check of include/rayn_detmath_fast.h (what the KERNELS evaluate; the oracle itself keeps using rayn_detmath.h): out = the fast
  * wrapper's result for op 0 exp, 1 sin, 2 cos, 3 tan, 4 atan2(a,b), 5 pow(a,b), 6 log; stats[0] = number of calls that fell back to the
  * reference evaluation, stats[1] = largest |d_fast - d_ref| / |d_ref| between the two binary64 evaluations over the arguments inside

@@ -24,6 +24,15 @@ static_assert(resolve_keys_fit(MAX_TILE_PIXELS, MAX_SPP_RESOLVE_BLK), "k_resolve
 static_assert(!resolve_keys_fit(MAX_TILE_PIXELS, 8u * MAX_SPP_RESOLVE_BLK), "resolve_keys_fit must reject a segment beyond 2^25 slots");
 
 
+// rayn_hip_probe_shading: number of ops and the floats per lane each op reads / writes (the op table of rayn_hip.h)
+constexpr uint32_t PROBE_SHADING_OPS = 13;
+__host__ __device__ constexpr uint32_t probe_shading_in(uint32_t op) {
+    return op == 0 ? 5 : op == 3 ? 3 : op == 4 ? 3 : op == 6 ? 9 : op == 7 ? 3 : op == 8 ? 11 : op == 9 ? 5 : op == 10 ? 8 : op >= 11 ? 1 : 2;
+}
+__host__ __device__ constexpr uint32_t probe_shading_out(uint32_t op) {
+    return op == 0 ? 6 : op == 1 ? 2 : op == 4 ? 9 : op == 5 ? 1 : op == 8 ? 7 : op == 9 ? 4 : op == 10 ? 2 : op >= 11 ? 1 : 3;
+}
+
 // Path pool (device pointers): one slot per camera path, records of 16 bytes so that a scattered
 // access costs one 128-bit gather per record instead of four 32-bit ones (the shade kernels were
 // bound by the address path of the vector memory unit, not by bandwidth).
@@ -147,6 +156,7 @@ struct Tables {
     void launch_probe_dist(hipStream_t s, const DScene* sc, uint32_t hit_index, const float* pts, float* out, uint32_t n); \
     void launch_shadow_march(hipStream_t s, bool count, const DScene* sc, Nee nee, uint32_t max_jobs, int single_sdf, DCtl* ctl, unsigned long long* evals, const Tuning& tun); \
     void launch_probe_detmath(hipStream_t s, uint32_t op, const float* a, const float* b, float* out, uint32_t n); \
+    void launch_probe_shading(hipStream_t s, const DScene* sc, uint32_t op, uint32_t index, const float* in, float* out, const float* aux, uint32_t n); \
     void launch_verify_short_div(hipStream_t s, float n, uint32_t lo_bits, uint32_t count, uint32_t* bad); \
     }
 RAYN_DECLARE_LAUNCHERS(rayn_p0)
@@ -168,8 +178,9 @@ struct KernelSet {
     decltype(&rayn_p0::launch_probe_dist) probe_dist;
     decltype(&rayn_p0::launch_shadow_march) shadow_march;
     decltype(&rayn_p0::launch_probe_detmath) probe_detmath;
+    decltype(&rayn_p0::launch_probe_shading) probe_shading;
 };
-#define RAYN_KERNEL_SET(NS) KernelSet{&NS::launch_pack_tables, &NS::launch_raygen, &NS::launch_extend, &NS::launch_group_hist, &NS::launch_scan_tile, &NS::launch_tile_prefix, &NS::launch_bin_scatter, &NS::launch_shade, &NS::launch_compact_scatter, &NS::launch_batch_setup, &NS::launch_resolve, &NS::launch_probe_dist, &NS::launch_shadow_march, &NS::launch_probe_detmath}
+#define RAYN_KERNEL_SET(NS) KernelSet{&NS::launch_pack_tables, &NS::launch_raygen, &NS::launch_extend, &NS::launch_group_hist, &NS::launch_scan_tile, &NS::launch_tile_prefix, &NS::launch_bin_scatter, &NS::launch_shade, &NS::launch_compact_scatter, &NS::launch_batch_setup, &NS::launch_resolve, &NS::launch_probe_dist, &NS::launch_shadow_march, &NS::launch_probe_detmath, &NS::launch_probe_shading}
 inline KernelSet kernel_set(int fma_policy) {
     if (fma_policy) return RAYN_KERNEL_SET(rayn_p1);
     return RAYN_KERNEL_SET(rayn_p0);

@@ -1868,6 +1868,52 @@ __global__ void k_probe_detmath(uint32_t op, const float* __restrict__ a, const 
     }
     out[i] = r;
 }
+// The shading half of the path, one device function per op, on caller records of probe_shading_in(op) floats in / probe_shading_out(op)
+// floats out per lane (op table: rayn_hip.h).  Materials, lights and the camera are the uploaded scene's (DScene); the host has checked
+// op, index and the material kind of ops 6 / 8.
+__global__ void k_probe_shading(const DScene* __restrict__ scp, uint32_t op, uint32_t index, const float* __restrict__ in, float* __restrict__ out,
+                                const float* __restrict__ aux, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || op >= PROBE_SHADING_OPS) return;
+    const float* a = in + (size_t)i * probe_shading_in(op);
+    float* r = out + (size_t)i * probe_shading_out(op);
+    const DScene& sc = *scp;
+    switch (op) {
+    case 0: {
+        f3 o, d;
+        camera_ray(sc.cam, a[0], a[1], a[2], a[3], a[4], &o, &d);
+        r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
+        break;
+    }
+    case 1: concentric_circle_map(a[0], a[1], &r[0], &r[1]); break;
+    case 2: { const f3 v = cosine_weighted_in_hemisphere(a[0], a[1]); r[0] = v.x; r[1] = v.y; r[2] = v.z; break; }
+    case 3: { const f3 v = cosine_power_weighted(a[0], a[1], a[2]); r[0] = v.x; r[1] = v.y; r[2] = v.z; break; }
+    case 4: {
+        const Basis b = orthonormal_basis(f3{a[0], a[1], a[2]});
+        r[0] = b.c0.x; r[1] = b.c0.y; r[2] = b.c0.z; r[3] = b.c1.x; r[4] = b.c1.y; r[5] = b.c1.z; r[6] = b.c2.x; r[7] = b.c2.y; r[8] = b.c2.z;
+        break;
+    }
+    case 5: r[0] = f_schlick(a[0], a[1]); break;
+    case 6: { const f3 v = bsdf_f(sc.m[index], f3{a[0], a[1], a[2]}, f3{a[3], a[4], a[5]}, f3{a[6], a[7], a[8]}); r[0] = v.x; r[1] = v.y; r[2] = v.z; break; }
+    case 7: { const f3 v = bsdf_le(sc.m[index], f3{a[0], a[1], a[2]}); r[0] = v.x; r[1] = v.y; r[2] = v.z; break; }
+    case 8: {
+        const f3 normal = f3{a[3], a[4], a[5]};
+        const Basis basis = orthonormal_basis(normal); // as k_shade_setup builds it
+        const Scatter se = bsdf_scatter(sc.m[index], f3{a[0], a[1], a[2]}, normal, basis, a[6], a[7], a[8], a[9], a[10]);
+        r[0] = se.wi.x; r[1] = se.wi.y; r[2] = se.wi.z; r[3] = se.f.x; r[4] = se.f.y; r[5] = se.f.z; r[6] = se.pdf;
+        break;
+    }
+    case 9: {
+        f3 pt; float pdf;
+        light_sample(sc.l[index], a[0], a[1], f3{a[2], a[3], a[4]}, &pt, &pdf);
+        r[0] = pt.x; r[1] = pt.y; r[2] = pt.z; r[3] = pdf;
+        break;
+    }
+    case 10: light_sample_volume(sc.l[index], a[0], f3{a[1], a[2], a[3]}, f3{a[4], a[5], a[6]}, a[7], &r[0], &r[1]); break;
+    case 11: r[0] = (float)light_index(a[0], index); break;
+    default: r[0] = fis_sample(aux, a[0]); break;
+    }
+}
 
 // Scene-upload check behind DHitable::fast_div == 2: div_short(n, d) against the IEEE quotient for every float d with
 // bit pattern in [lo_bits, lo_bits + count).
@@ -2019,6 +2065,9 @@ void launch_verify_short_div(hipStream_t s, float n, uint32_t lo_bits, uint32_t 
 }
 void launch_probe_detmath(hipStream_t s, uint32_t op, const float* a, const float* b, float* out, uint32_t n) {
     hipLaunchKernelGGL(k_probe_detmath, grid_for(n, 256), dim3(256), 0, s, op, a, b, out, n);
+}
+void launch_probe_shading(hipStream_t s, const DScene* sc, uint32_t op, uint32_t index, const float* in, float* out, const float* aux, uint32_t n) {
+    hipLaunchKernelGGL(k_probe_shading, grid_for(n, 256), dim3(256), 0, s, sc, op, index, in, out, aux, n);
 }
 
 } // namespace RAYN_KNS

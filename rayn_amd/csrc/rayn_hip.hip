@@ -1348,6 +1348,34 @@ int rayn_hip_probe_detmath(rayn_ctx* ctx, uint32_t op, const float* a, const flo
     HIPCHK(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return RAYN_OK;
 }
+int rayn_hip_probe_shading(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t op, uint32_t index, const float* in, float* out, const float* aux, uint32_t n) {
+    int rc = probe_common(ctx, p);
+    if (rc) return rc;
+    if (!in || !out) return fail(ctx, RAYN_ERR_INVALID_ARG, "null buffer");
+    if (op >= PROBE_SHADING_OPS) return fail(ctx, RAYN_ERR_INVALID_ARG, "unknown shading probe op");
+    if (n == 0 || n > (1u << 26)) return fail(ctx, RAYN_ERR_INVALID_ARG, "probe size out of range");
+    const rayn_world_desc& w = ctx->world;
+    if (op >= 6 && op <= 8) {
+        if (index >= w.n_materials) return fail(ctx, RAYN_ERR_INVALID_ARG, "index does not name a material of the uploaded world");
+        const uint32_t k = w.materials[index].kind;
+        if (op == 6 && k == RAYN_MAT_SKY) return fail(ctx, RAYN_ERR_INVALID_ARG, "Sky's BSDF::f panics in the reference: not probed");
+        if (op == 8 && k != RAYN_MAT_LAMBERTIAN && k != RAYN_MAT_DIELECTRIC) return fail(ctx, RAYN_ERR_INVALID_ARG, "only Lambertian and Dielectric scatter");
+    }
+    if ((op == 9 || op == 10) && index >= w.n_lights) return fail(ctx, RAYN_ERR_INVALID_ARG, "index does not name a light of the uploaded world");
+    if (op == 11 && index == 0) return fail(ctx, RAYN_ERR_INVALID_ARG, "light_index needs at least one light");
+    if (op == 12 && !aux) return fail(ctx, RAYN_ERR_INVALID_ARG, "fis_sample needs the inverse-CDF table in aux");
+    const size_t nin = (size_t)n * probe_shading_in(op), nout = (size_t)n * probe_shading_out(op);
+    const KernelSet K = kernel_set(ctx->fma_policy);
+    DevBuf d_in, d_out, d_aux;
+    HIPCHK(d_in.alloc(nin * 4)); HIPCHK(d_out.alloc(nout * 4)); HIPCHK(d_aux.alloc(RAYN_FIS_TABLE_SIZE * 4));
+    HIPCHK(hipMemcpy(d_in.p, in, nin * 4, hipMemcpyHostToDevice));
+    if (op == 12) HIPCHK(hipMemcpy(d_aux.p, aux, RAYN_FIS_TABLE_SIZE * 4, hipMemcpyHostToDevice));
+    K.probe_shading(ctx->stream, ctx->d_scene, op, index, d_in.as<float>(), d_out.as<float>(), d_aux.as<float>(), n);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, d_out.p, nout * 4, hipMemcpyDeviceToHost));
+    return RAYN_OK;
+}
 int rayn_hip_set_workers(rayn_ctx* ctx, int n_workers, uint64_t min_paths) {
     if (!ctx || n_workers < 1 || n_workers > MAX_WORKERS) return RAYN_ERR_INVALID_ARG;
     ctx->n_workers = n_workers;

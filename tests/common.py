@@ -29,3 +29,36 @@ def bits_equal(x, y):
 
 def film_equal_bits(a, b):
     return all(bits_equal(a[k], b[k]) for k in ("color", "alpha", "background", "normal"))
+
+
+def randomise_materials(world, rng, seed):
+    """Random shading parameters for a scene of rayn_amd.setup.setup(): the SDF's material (Lambertian or Dielectric, roughness in [0, 1] with
+    the ends 0 and 1 forced on every third seed, albedo incl. 0 and > 1), the emission of the light proxies, the sky colours, and 1 to
+    RAYN_MAX_LIGHTS sphere lights of random radius and emission (the shipped ones first, further ones at random positions)."""
+    import rayn_amd as R
+    from rayn_amd import _abi
+    f = lambda lo, hi, k=3: rng.uniform(lo, hi, k).astype(np.float32)
+    srgb = lambda v: R.Srgb(*[float(x) for x in v])
+    albedo = np.zeros(3, np.float32) if rng.integers(0, 6) == 0 else f(0.0, 1.3)
+    if seed % 3 == 0:
+        mat = R.Dielectric.new_remap(srgb(albedo), float(seed % 2))
+    elif rng.integers(0, 3) == 0:
+        mat = R.Lambertian(srgb(albedo))
+    else:
+        mat = R.Dielectric.new_remap(srgb(albedo), float(np.float32(rng.uniform(0.0, 1.0))))
+    sdf_mats = {h.material for h in world.hitables if isinstance(h, R.TracedSDF)}
+    for i, m in enumerate(world.materials):
+        if i in sdf_mats:
+            world.materials[i] = mat
+        elif isinstance(m, R.Sky):
+            world.materials[i] = R.Sky(srgb(f(0.0, 1.5)), srgb(f(0.0, 0.4)))
+        elif isinstance(m, R.Emissive):
+            world.materials[i] = R.Emissive.new_splat(srgb(f(0.0, 8.0)))
+    nl = int(rng.integers(1, _abi.MAX_LIGHTS + 1))
+    lights = list(world.lights[:nl])
+    while len(lights) < nl:
+        lights.append(R.SphereLight(f(-2.5, 2.5), 0.15, srgb(f(0.0, 1.0))))
+    for L in lights:
+        L.rad = float(np.float32(np.exp(rng.uniform(np.log(0.01), np.log(0.8)))))
+        L.emission = srgb(f(0.0, 60.0))
+    world.lights = lights

@@ -40,6 +40,8 @@ def test_special_values(oracle):
     assert f(1, 0.0) == 0.0 and f(2, 0.0) == 1.0 and math.isnan(f(1, float("inf")))
     assert f(4, 0.0, -1.0) == np.float32(math.pi) and f(4, -0.0, -1.0) == -np.float32(math.pi) and f(4, 1.0, 0.0) == np.float32(math.pi / 2)
     assert f(5, 0.0, 2.0) == 0.0 and f(5, 1.0, 7.0) == 1.0 and f(5, 0.5, 0.0) == 1.0 and math.isnan(f(5, -1.0, 0.5))
+    bits = lambda op, a: int(oracle.detmath(op, np.array([a], np.float32)).view(np.uint32)[0])
+    assert [bits(op, z) for op in (1, 3) for z in (0.0, -0.0)] == [0, 0x80000000] * 2  # sin and tan keep the sign of a zero argument
 
 
 # ---- include/rayn_detmath_fast.h: what the KERNELS evaluate (host build of the same header, through oracle_detmath_fast) ----

@@ -825,3 +825,47 @@ def test_randomised_scene_parity(gpu_ctx, oracle, seed):
     st = gpu_ctx.stats()
     assert st["paths"] == ctr.paths and st["segments"] == ctr.segments
     assert film_equal_bits(out, ref), f"seed {seed}: L2 {film_l2(out, ref)}"
+
+
+@pytest.mark.parametrize("seed", list(range(12)))
+def test_randomised_material_parity(gpu_ctx, oracle, seed):
+    """test_randomised_scene_parity's generator plus random shading parameters (common.randomise_materials): the SDF's material kind,
+    roughness (the ends 0 and 1 on every third seed) and albedo, the proxies' emission, the sky colours, the number of lights (1 to 16),
+    their radii and emission.  Film bit-identical to the oracle, paths and segments equal."""
+    import rayn_amd as R
+    from rayn_amd import setup as S
+    from rayn_amd import params as P
+    from common import randomise_materials
+    rng = np.random.default_rng(2000 + seed)
+    w, h = int(rng.integers(17, 49)), int(rng.integers(9, 33))
+    volumes = bool(rng.integers(0, 2))
+    cam_h, world = S.setup((w, h), volumes=volumes, sdf="mandelbox")
+    box = world.hitables[1].sdf
+    box.iterations = int(rng.integers(5, 15))
+    box.scale = float(np.float32(rng.uniform(-2.6, -1.7) if rng.integers(0, 2) else rng.uniform(1.8, 2.8)))
+    box.box_fold.side_length = float(np.float32(rng.uniform(0.7, 1.3)))
+    box.sphere_fold.min_radius = float(np.float32(rng.uniform(0.005, 0.6)))
+    box.sphere_fold.fixed_radius = float(np.float32(rng.uniform(0.8, 2.2)))
+    if volumes:
+        world.volume_params = R.VolumeParams(float(np.float32(rng.uniform(0.05, 0.6))), float(np.float32(rng.uniform(0.01, 0.2))))
+    for L in world.lights:
+        L.pos = L.pos + rng.uniform(-0.3, 0.3, 3).astype(np.float32)
+    cam = world.cameras.get(cam_h)
+    cam.origin = (cam.origin * np.float32(rng.uniform(0.6, 1.4)) + rng.uniform(-0.5, 0.5, 3).astype(np.float32)).astype(np.float32)
+    if rng.integers(0, 3) == 0:
+        world.hitables[1].transform_seq = R.Linear(rng.uniform(-0.2, 0.2, 3).astype(np.float32), rng.uniform(-3, 3, 3).astype(np.float32))
+    if rng.integers(0, 3) == 0:
+        box.scale_vel = float(np.float32(rng.uniform(-3, 3)))
+    randomise_materials(world, rng, seed)
+    wd = world.to_desc(cam_h)
+    samples, bounces = int(rng.integers(1, 4)), int(rng.integers(1, 7))
+    t0 = float(np.float32(rng.uniform(0.0, 2.0)))
+    p = P.frame_params(w, h, samples, bounces, frame=int(rng.integers(1, 50)), time_range=(t0, float(np.float32(t0 + rng.uniform(0.01, 0.2)))),
+                       tile_size=(int(rng.choice([4, 8, 16])), int(rng.choice([4, 8, 16]))))
+    tabs = _tables(oracle, p)
+    ref, ctr = oracle.render(wd, p, tabs)
+    gpu_ctx.upload_world(wd)
+    out = gpu_ctx.render_host(p, tabs)
+    st = gpu_ctx.stats()
+    assert st["paths"] == ctr.paths and st["segments"] == ctr.segments
+    assert film_equal_bits(out, ref), f"seed {seed}: L2 {film_l2(out, ref)}"

@@ -2,7 +2,9 @@
 test_randomised_scene_parity, larger films, up to 1024 spp).  Every third scene goes through a two-entry multi-device context
 (rayn_hip_create_multi on GPU 0 twice); r5: every third OTHER scene is rendered share by share (2-5 ranks' shares) straight into the packed planar
 films of the multi-process gather and reassembled with rayn_hip_unpack_share_device.  r6: a third argument `bulb` makes every scene a Mandelbulb
-scene (k_shadow_bulb, march_bulb.h) with random march budgets.  usage: fuzz_parity.py [n=60] [first_seed=100] [bulb]"""
+scene (k_shadow_bulb, march_bulb.h) with random march budgets.  A third argument `materials` randomises the shading parameters on top (tests/common.py randomise_materials: the
+SDF's material, roughness and albedo, proxy emission, sky colours, 1 to 16 lights of random radius and emission).
+usage: fuzz_parity.py [n=60] [first_seed=100] [bulb|materials]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
@@ -10,9 +12,10 @@ import numpy as np, torch
 import rayn_amd as R
 from rayn_amd import setup as S, params as P
 from oracle import oracle_py as O
-from common import film_equal_bits, film_l2
+from common import film_equal_bits, film_l2, randomise_materials
 n, first = (int(sys.argv[1]) if len(sys.argv) > 1 else 60), (int(sys.argv[2]) if len(sys.argv) > 2 else 100)
 only_bulb = len(sys.argv) > 3 and sys.argv[3] == "bulb"
+materials = len(sys.argv) > 3 and sys.argv[3] == "materials"
 ctx1 = R.Context(0)
 ctx2 = R.Context([0, 0])
 bad = 0
@@ -46,6 +49,8 @@ for seed in range(first, first + n):
         cam.origin = R.Linear(cam.origin, rng.uniform(-3, 3, 3).astype(np.float32))
     if only_bulb:
         world.hitables[1].sdf.iterations = int(rng.integers(1, 13))
+    if materials:
+        randomise_materials(world, rng, seed)
     wd = world.to_desc(cam_h)
     samples, bounces = int(rng.choice([1, 2, 3, 4, 4, 8, 16, 33, 64, 150, 256])), int(rng.integers(0, 9))
     if samples >= 8:  # many samples per pixel (the resolve sorts 4*samples keys): keep the film small
