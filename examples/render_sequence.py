@@ -1,0 +1,102 @@
+"""rayn's main loop (src/main.rs:47-96) over a frame range on the GPU with Film.render_sequence: rayn's shipped scene
+(rayn_amd.setup, 1280x720, SAMPLES = 2 (8 spp), 3 bounces, the BlackmanHarris filter, 16x16 tiles) rendered frame by frame and
+written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints per-frame render times and frames/s.
+
+    python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop]
+
+--compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
+the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
+both loops wrote the same bytes."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import rayn_amd as R  # noqa: E402
+from rayn_amd import image  # noqa: E402
+from rayn_amd import setup as S  # noqa: E402
+
+SAMPLES, MAX_INDIRECT_BOUNCES = 2, 3  # src/setup.rs:16-25
+FRAME_RATE, SHUTTER_SPEED = 24, 1.0 / 24.0  # src/main.rs:47-49
+K = R.ChannelKind
+CHANNELS = [K.Color, K.Alpha, K.Background, K.WorldNormal]
+WRITE = [K.Alpha, K.WorldNormal, K.Color]  # src/main.rs:87-91
+
+
+def host_save_to(film, write_channels, output_folder, base_name):
+    """The host post-process of the plain loop (not transparent): every channel copied to the host, image.py's arms, PNG."""
+    os.makedirs(output_folder, exist_ok=True)
+    for kind in write_channels:
+        if kind == K.Color:
+            img = image.color_image(film.channel(K.Color), background=film.channel(K.Background))
+        elif kind == K.Alpha:
+            img = image.alpha_image(film.channel(K.Alpha))
+        elif kind == K.Background:
+            img = image.background_image(film.channel(K.Background))
+        else:
+            img = image.normal_image(film.channel(K.WorldNormal))
+        suffix = {K.Color: "color", K.Alpha: "alpha", K.Background: "background", K.WorldNormal: "normal"}[kind]
+        image.save(os.path.join(output_folder, f"{base_name}_{suffix}.png"), img)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--frames", default="1:25", help="frame range first:end (end exclusive, like rayn's frame_range)")
+    ap.add_argument("--out", default="renders_seq", help="output folder")
+    ap.add_argument("--width", type=int, default=1280)
+    ap.add_argument("--height", type=int, default=720)
+    ap.add_argument("--writers", type=int, default=None, help="PNG writer threads (at most 8; default 2 per written channel)")
+    ap.add_argument("--compare-loop", action="store_true", help="also time the plain render_frame_into + host post-process loop")
+    args = ap.parse_args()
+    first, end = (int(x) for x in args.frames.split(":"))
+    frames = list(range(first, end))
+    base = f"{SAMPLES * 4}_spp"
+    cam, world = S.setup((args.width, args.height))
+    integ = R.PathTracingIntegrator(max_bounces=MAX_INDIRECT_BOUNCES, volume_marches=S.VOLUME_MARCHES_PER_SAMPLE)
+    filt = R.BlackmanHarrisFilter(S.FILTER_RADIUS)
+
+    film = R.Film(CHANNELS, (args.width, args.height))
+    # warm-up: code objects, the context's first-frame arena and the writer path (not timed)
+    film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames[:1], FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
+                         os.path.join(args.out, "warmup"), base, writers=args.writers)
+    t0 = time.perf_counter()
+    stats = film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
+                                 os.path.join(args.out, "sequence"), base, writers=args.writers)
+    seq_s = time.perf_counter() - t0
+    for st in stats:
+        print(f"frame {st['frame']:4d}: render {st['ms_total']:8.2f} ms")
+    print(f"render_sequence: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s "
+          f"(render alone: {sum(st['ms_total'] for st in stats) / len(frames):.2f} ms/frame)")
+
+    if args.compare_loop:
+        plain = R.Film(CHANNELS, (args.width, args.height))
+        loop_dir = os.path.join(args.out, "loop")
+        f32 = np.float32
+        plain.render_frame_into(world, cam, integ, filt, S.TILE_SIZE, frames[0], None, SAMPLES)  # warm-up of the plain film's context (not timed)
+        t0 = time.perf_counter()
+        for frame in frames:
+            start = f32(frame) * (f32(1.0) / f32(FRAME_RATE))
+            t1 = time.perf_counter()
+            plain.render_frame_into(world, cam, integ, filt, S.TILE_SIZE, frame, (float(start), float(f32(start + f32(SHUTTER_SPEED)))), SAMPLES)
+            t2 = time.perf_counter()
+            host_save_to(plain, WRITE, loop_dir, f"{base}_{frame:04d}")
+            t3 = time.perf_counter()
+            print(f"plain loop frame {frame:4d}: render_frame_into {1e3 * (t2 - t1):8.2f} ms, host save_to {1e3 * (t3 - t2):8.2f} ms")
+        loop_s = time.perf_counter() - t0
+        print(f"plain loop: {len(frames)} frames in {loop_s:.3f} s = {len(frames) / loop_s:.2f} frames/s")
+        print(f"speed-up of render_sequence over the plain loop: {loop_s / seq_s:.2f}x")
+        same = all(open(os.path.join(loop_dir, n), "rb").read() == open(os.path.join(args.out, "sequence", n), "rb").read()
+                   for n in sorted(os.listdir(loop_dir)))
+        print(f"identical PNGs: {same} ({len(os.listdir(loop_dir))} files)")
+        if not same:
+            sys.exit(1)
+
+
+if __name__ == "__main__":
+    main()

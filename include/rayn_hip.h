@@ -263,6 +263,24 @@ int rayn_hip_unpack_share_device(rayn_ctx* ctx, const rayn_frame_params* p, cons
                                  float* d_out_color, float* d_out_alpha, float* d_out_background,
                                  float* d_out_normal, void* hip_stream);
 
+/* ---- Film::save_to's per-pixel post-process (src/film.rs:205-378) on the device ----------------------------------------
+ * kind: ChannelKind (0 Color, 1 Alpha, 2 Background, 3 WorldNormal, src/film.rs:103-120); bit k of have_mask = ChannelKind k is
+ * among the film's channels (bits above 3 are ignored).  The arms: Color + Alpha with transparent_background -> RGBA, the colour
+ * saturated and gamma-corrected (2.2), the alpha quantised; Color + Background, not transparent -> RGB of (color + background),
+ * saturated and gamma-corrected; Color without Background, not transparent -> RGB, gamma-corrected but NOT saturated; Background
+ * -> RGB, saturated and gamma-corrected; WorldNormal -> RGB of n * 0.5 + 0.5; Alpha -> grey.  Quantisation is
+ * `(v * 255.0).min(255.0).max(0.0) as u8` with Rust's f32::min / max; powf is the pinned dm_powf (rayn_detmath.h).
+ * Bytes per pixel of the image for that combination (4, 3 or 1), or -1 where the reference returns Err.  Host only; needs no GPU. */
+int rayn_save_to_bpp(uint32_t kind, uint32_t have_mask, int transparent_background);
+/* Enqueue the post-process of one channel on 'hip_stream' (NULL = the ctx's own stream; not waited for).  DEVICE pointers on the
+ * ctx's GPU (devices[0] of a multi-device ctx), the film in the layout rayn_hip_render_frame_device writes (bottom-up rows);
+ * the channels the arm does not read may be NULL.  d_out receives width * height * bpp bytes, rows top-down.  A combination
+ * the reference rejects returns RAYN_ERR_INVALID_ARG with the reference's Err text as the last error; so do a missing buffer
+ * the arm reads and a zero-sized image. */
+int rayn_hip_save_to_pixels_device(rayn_ctx* ctx, uint32_t kind, uint32_t have_mask, int transparent_background,
+                                   uint32_t width, uint32_t height, const float* d_color, const float* d_alpha,
+                                   const float* d_background, const float* d_normal, uint8_t* d_out, void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */

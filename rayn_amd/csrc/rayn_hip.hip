@@ -18,6 +18,7 @@
 #include "../../include/rayn_detmath.h"
 #include "../../include/rayn_hip.h"
 #include "kernels.h"
+#include "save_to.h"
 
 using namespace rayn;
 
@@ -1118,6 +1119,25 @@ int rayn_hip_unpack_share_device(rayn_ctx* ctx, const rayn_frame_params* p, cons
     }
     if (plan->n_tiles)
         rayn_p0::launch_unpack_tiles(s, plan->d_tiles, plan->n_tiles, p->width, d_out_color, d_out_alpha, d_out_background, d_out_normal, d_packed, plan->pixels);
+    HIPCHK(hipGetLastError());
+    return RAYN_OK; // enqueued on the stream, not waited for
+}
+
+int rayn_hip_save_to_pixels_device(rayn_ctx* ctx, uint32_t kind, uint32_t have_mask, int transparent_background, uint32_t width, uint32_t height,
+                                   const float* d_color, const float* d_alpha, const float* d_background, const float* d_normal, uint8_t* d_out,
+                                   void* hip_stream) {
+    if (!ctx) return RAYN_ERR_INVALID_ARG;
+    const char* why = nullptr;
+    const int arm = save_to_arm(kind, have_mask, transparent_background, &why);
+    if (arm < 0) return fail(ctx, RAYN_ERR_INVALID_ARG, why); // the reference's Err text
+    if (!width || !height) return fail(ctx, RAYN_ERR_INVALID_ARG, "zero-sized image");
+    if ((uint64_t)width * height >= ((uint64_t)1 << 31)) return fail(ctx, RAYN_ERR_INVALID_ARG, "image larger than 2^31 pixels unsupported (32-bit pixel indices)");
+    const uint32_t reads = save_to_arm_reads(arm);
+    if (!d_out || ((reads & 1u) && !d_color) || ((reads & 2u) && !d_alpha) || ((reads & 4u) && !d_background) || ((reads & 8u) && !d_normal))
+        return fail(ctx, RAYN_ERR_INVALID_ARG, "null buffer");
+    HIPCHK(hipSetDevice(ctx->device)); // a multi-device ctx is entry 0: its device is devices[0], where the film lives
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    launch_save_to(s, arm, width, height, d_color, d_alpha, d_background, d_normal, d_out);
     HIPCHK(hipGetLastError());
     return RAYN_OK; // enqueued on the stream, not waited for
 }

@@ -32,17 +32,32 @@ def _fp(a):
 def build_tables(spp, max_bounces, volume_marches, frame, width, height, filter=None):
     """Samples::new_rd (src/sampler.rs:18-37), per-pixel scramble (src/film.rs:460-461) and
     FilterImportanceSampler::new (src/filter.rs:196-220) through the product's host builders."""
+    s1, s2 = build_rd_tables(spp, max_bounces, volume_marches, frame)
+    scr, fis = build_film_tables(width, height, filter)
+    return s1, s2, scr, fis
+
+
+def build_rd_tables(spp, max_bounces, volume_marches, frame):
+    """Samples::new_rd (src/sampler.rs:18-37): the only tables that depend on the frame."""
+    L = lib()
+    n1, n2 = L.rayn_sets_1d(max_bounces, volume_marches), L.rayn_sets_2d(max_bounces, volume_marches)
+    s1, s2 = np.zeros(spp * n1, np.float32), np.zeros(spp * 2 * n2, np.float32)
+    rc = L.rayn_build_rd_tables(spp, n1, n2, frame, _fp(s1), _fp(s2))
+    if rc != 0:
+        raise RaynHipError(f"table builder failed: {rc}")
+    return s1, s2
+
+
+def build_film_tables(width, height, filter=None):
+    """The per-pixel scramble (src/film.rs:460-461) and FilterImportanceSampler::new (src/filter.rs:196-220)."""
     L = lib()
     kind, radius = (0, 1.5) if filter is None else (filter.kind, filter.radius)
     p0, p1 = getattr(filter, "params", (0.0, 0.0))
-    n1, n2 = L.rayn_sets_1d(max_bounces, volume_marches), L.rayn_sets_2d(max_bounces, volume_marches)
-    s1, s2 = np.zeros(spp * n1, np.float32), np.zeros(spp * 2 * n2, np.float32)
     scr, fis = np.zeros(width * height, np.float32), np.zeros(_abi.FIS_TABLE_SIZE, np.float32)
-    for rc in (L.rayn_build_rd_tables(spp, n1, n2, frame, _fp(s1), _fp(s2)), L.rayn_build_scramble(width, height, _fp(scr)),
-               L.rayn_build_fis_table_ex(kind, radius, p0, p1, _fp(fis))):
+    for rc in (L.rayn_build_scramble(width, height, _fp(scr)), L.rayn_build_fis_table_ex(kind, radius, p0, p1, _fp(fis))):
         if rc != 0:
             raise RaynHipError(f"table builder failed: {rc}")
-    return s1, s2, scr, fis
+    return scr, fis
 
 
 def share_pixels(params):
@@ -196,6 +211,29 @@ class Context:
         self._chk(self._L.rayn_hip_unpack_share_device(self.h, C.byref(params), ptr(d_packed), ptr(d_out["color"]), ptr(d_out["alpha"]),
                                                        ptr(d_out["background"]), ptr(d_out["normal"]), C.c_void_p(s)))
 
+    def save_to_pixels(self, kind, have_mask, transparent_background, width, height, d_film, d_out, stream=None):
+        """rayn_hip_save_to_pixels_device: Film::save_to's post-process of channel `kind` (ChannelKind or its value) from the device film
+        `d_film` (a dict of torch CUDA tensors as render_device fills them; channels the arm does not read may be absent) into the uint8
+        CUDA tensor `d_out` (width * height * bpp bytes, rows top-down).  Enqueued on the stream, not waited for."""
+        import torch
+        kind = getattr(kind, "value", kind)
+        bpp = save_to_bpp(kind, have_mask, transparent_background)
+        n = int(width) * int(height)
+        if not (d_out.dtype == torch.uint8 and d_out.is_contiguous() and d_out.numel() >= n * max(bpp, 0)):
+            raise ValueError(f"d_out must be a contiguous uint8 tensor of at least {n * max(bpp, 0)} bytes")
+        ptrs = []
+        for key, floats in (("color", 3), ("alpha", 1), ("background", 3), ("normal", 3)):
+            t = d_film.get(key)
+            if t is None:
+                ptrs.append(None)
+                continue
+            if not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= floats * n):
+                raise ValueError(f"d_film[{key!r}] must be a contiguous float32 tensor of at least {floats * n} floats")
+            ptrs.append(C.c_void_p(t.data_ptr()))
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._chk(self._L.rayn_hip_save_to_pixels_device(self.h, int(kind), int(have_mask), int(bool(transparent_background)), int(width), int(height),
+                                                         *ptrs, C.c_void_p(d_out.data_ptr()), C.c_void_p(s)))
+
     def close(self):
         if self.h:
             self._L.rayn_hip_destroy(self.h)
@@ -206,6 +244,12 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+def save_to_bpp(kind, have_mask, transparent_background=False):
+    """rayn_save_to_bpp: bytes per pixel of the image Film::save_to writes for channel `kind` given the film's channels (bit k of
+    have_mask = ChannelKind k), or -1 where the reference returns Err.  Host only."""
+    return int(lib().rayn_save_to_bpp(int(getattr(kind, "value", kind)), int(have_mask), int(bool(transparent_background))))
 
 
 def alloc_device_film(width, height, device="cuda"):
@@ -254,31 +298,133 @@ class Film:
         t = self.channels[key].cpu().numpy()
         return t.reshape(h, w, 3) if t.ndim == 2 else t.reshape(h, w)
 
-    def save_to(self, write_channels, output_folder, base_name, transparent_background=False):
-        """Film::save_to (src/film.rs:205-378) - the post-process after the hot path, arm by arm; the reference's
-        Err(String) cases raise ValueError with the same text."""
-        os.makedirs(output_folder, exist_ok=True)
-        have = lambda k: k in self.channel_kinds
+    def have_mask(self):
+        """bit k = ChannelKind k is among the film's channels (the have_mask of rayn_save_to_bpp)"""
+        return sum(1 << k.value for k in self.channel_kinds)
+
+    def _save_jobs(self, write_channels, transparent_background):
+        """[(kind, bytes per pixel, file suffix)] of a save_to call; raises the reference's Err text as ValueError before anything runs."""
+        jobs = []
         for kind in write_channels:
-            if kind == ChannelKind.Color:
-                if have(ChannelKind.Color) and have(ChannelKind.Alpha) and transparent_background:
-                    img = image.color_image(self.channel(ChannelKind.Color), alpha=self.channel(ChannelKind.Alpha), transparent_background=True)
-                elif have(ChannelKind.Color) and have(ChannelKind.Background) and not transparent_background:
-                    img = image.color_image(self.channel(ChannelKind.Color), background=self.channel(ChannelKind.Background))
-                elif have(ChannelKind.Color) and not have(ChannelKind.Background) and not transparent_background:
-                    img = image.color_image(self.channel(ChannelKind.Color))
-                else:
-                    raise ValueError("Attempted to write Color channel with insufficient channels")
-                image.save(os.path.join(output_folder, f"{base_name}_color.png"), img)
-            elif kind == ChannelKind.Background:
-                if not have(kind):
-                    raise ValueError("Attempted to write Background channel but it didn't exist")
-                image.save(os.path.join(output_folder, f"{base_name}_background.png"), image.background_image(self.channel(kind)))
-            elif kind == ChannelKind.WorldNormal:
-                if not have(kind):
-                    raise ValueError("Attempted to write WorldNormal channel but it didn't exist")
-                image.save(os.path.join(output_folder, f"{base_name}_normal.png"), image.normal_image(self.channel(kind)))
-            elif kind == ChannelKind.Alpha:
-                if not have(kind):
-                    raise ValueError("Attempted to write Alpha channel but it didn't exist")
-                image.save(os.path.join(output_folder, f"{base_name}_alpha.png"), image.alpha_image(self.channel(kind)))
+            bpp = save_to_bpp(kind, self.have_mask(), transparent_background)
+            if bpp < 0:
+                raise ValueError(_SAVE_TO_ERR[kind])
+            jobs.append((kind, bpp, _SAVE_TO_SUFFIX[kind]))
+        return jobs
+
+    def pixels(self, kind, transparent_background=False):
+        """The 8-bit image Film::save_to writes for channel `kind` (rows top-down; (h, w, 4 / 3 / 1) uint8), computed on the device
+        (rayn_hip_save_to_pixels_device); only the 8-bit image is copied back.  Channels the film lacks are not read."""
+        import torch
+        ((kind, bpp, _),) = self._save_jobs([kind], transparent_background)
+        w, h = self.res
+        with torch.cuda.device(self.device):
+            out = torch.empty(h * w * bpp, dtype=torch.uint8, device=self.device)
+            self.ctx.save_to_pixels(kind, self.have_mask(), transparent_background, w, h, self.channels, out)
+            return out.cpu().numpy().reshape(h, w, bpp)  # .cpu() waits for the current stream, where the kernel was enqueued
+
+    def save_to(self, write_channels, output_folder, base_name, transparent_background=False):
+        """Film::save_to (src/film.rs:205-378) - the post-process after the hot path, arm by arm (on the device: pixels); the
+        reference's Err(String) cases raise ValueError with the same text.  The PNGs are those of rayn_amd.image (host reference)."""
+        os.makedirs(output_folder, exist_ok=True)
+        for kind in write_channels:
+            ((kind, _, suffix),) = self._save_jobs([kind], transparent_background)  # the reference fails at the first bad channel, after writing the ones before
+            image.save(os.path.join(output_folder, f"{base_name}_{suffix}.png"), self.pixels(kind, transparent_background))
+
+    def render_sequence(self, world, camera, integrator, filter, tile_size, frames, frame_rate, shutter_speed, samples, write_channels,
+                        output_folder, base_name, transparent_background=False, writers=None):
+        """rayn's main loop (src/main.rs:58-96) on the GPU: for each frame of `frames`, render_frame_into at
+        frame_start = frame as f32 * (1.0 / frame_rate as f32), frame_end = frame_start + shutter_speed (f32, src/main.rs:61-62), then
+        save_to(write_channels, output_folder, f"{base_name}_{frame:04d}", transparent_background).  rayn writes every frame under
+        one base name (each frame overwrites the last); the per-frame names are an extension.  The images are byte-identical to
+        those of that plain loop.  Returns the render stats of every frame (Context.stats() plus "frame").
+
+        The world is uploaded once; the scramble and filter tables are built once; the device film, the device tables and the
+        8-bit images are allocated once.  The R_d tables (Samples::new_rd, the only frame-dependent ones) are built on a host
+        thread one frame ahead.  After frame k's render returns, its post-process kernels and the copies of its 8-bit images into
+        pinned host buffers (two sets, used in turn) are enqueued on the same stream, and a pool of at most 8 writer threads
+        encodes the PNGs of frame k while frame k + 1 renders.  A channel combination the reference rejects raises ValueError
+        before anything renders; a render or writer error stops the sequence and is raised after every thread has been joined.
+        Afterwards film.channels holds the last frame, as the plain loop leaves it."""
+        import concurrent.futures as cf
+        import torch
+        frames = [int(f) for f in frames]
+        jobs = self._save_jobs(write_channels, transparent_background)
+        os.makedirs(output_folder, exist_ok=True)
+        w, h = self.res
+        f32 = np.float32
+        inv_rate, shutter = f32(1.0) / f32(frame_rate), f32(shutter_speed)
+        spp, mb, vm = 4 * samples, integrator.max_bounces, integrator.volume_marches
+        n_writers = max(1, min(8, 2 * len(jobs) if writers is None else int(writers)))
+        mask = self.have_mask()
+        stats, pending = [], [[], []]  # pending[slot]: writer futures still reading that slot's pinned images
+        table_pool = cf.ThreadPoolExecutor(max_workers=1, thread_name_prefix="rayn-rd-tables")
+        write_pool = cf.ThreadPoolExecutor(max_workers=n_writers, thread_name_prefix="rayn-png")
+
+        def write(event, img, path):
+            event.synchronize()
+            image.save(path, img)
+
+        def wait_slot(slot):
+            for fut in pending[slot]:
+                fut.result()  # re-raises a writer's exception
+            pending[slot] = []
+
+        try:
+            if not frames:
+                return stats
+            with torch.cuda.device(self.device):
+                stream = torch.cuda.current_stream()
+                self.ctx.upload_world(world.to_desc(camera))
+                next_rd = table_pool.submit(build_rd_tables, spp, mb, vm, frames[0])
+                scr, fis = build_film_tables(w, h, filter)
+                s1, s2 = next_rd.result()
+                d_tables = [torch.from_numpy(t).to(self.device) for t in (s1, s2, scr, fis)]
+                d_film = alloc_device_film(w, h, self.device)
+                d_img = [torch.empty(h * w * bpp, dtype=torch.uint8, device=self.device) for _, bpp, _ in jobs]
+                h_img = [[torch.empty(h * w * bpp, dtype=torch.uint8, pin_memory=True) for _, bpp, _ in jobs] for _ in range(2)]
+                for i, frame in enumerate(frames):
+                    if i:
+                        s1, s2 = next_rd.result()
+                        d_tables[0].copy_(torch.from_numpy(s1))  # synchronous copies from pageable memory: the previous render has returned
+                        d_tables[1].copy_(torch.from_numpy(s2))
+                    if i + 1 < len(frames):
+                        next_rd = table_pool.submit(build_rd_tables, spp, mb, vm, frames[i + 1])
+                    for fut in pending[0] + pending[1]:
+                        if fut.done() and fut.exception() is not None:
+                            raise fut.exception()
+                    start = f32(frame) * inv_rate
+                    p = frame_params(w, h, samples, mb, vm, frame, (float(start), float(f32(start + shutter))), tile_size)
+                    self.ctx.render_device(p, d_tables, d_film, stream.cuda_stream)  # blocking: returns when the frame is complete
+                    st = self.ctx.stats()
+                    st["frame"] = frame
+                    stats.append(st)
+                    self.channels = d_film
+                    self.progressive_epoch += 1
+                    # Frame k's post-process and copies go on the render stream, so frame k + 1's render (enqueued on the same stream
+                    # after them) cannot overwrite d_film or d_img before they have been read; only the pinned slot needs a host-side
+                    # wait: its images from frame k - 2 must have been encoded.
+                    slot = i % 2
+                    wait_slot(slot)
+                    for (kind, _, suffix), d, hbuf in zip(jobs, d_img, h_img[slot]):
+                        self.ctx.save_to_pixels(kind, mask, transparent_background, w, h, d_film, d, stream.cuda_stream)
+                        hbuf.copy_(d, non_blocking=True)
+                    done = torch.cuda.Event()
+                    done.record(stream)
+                    for (kind, bpp, suffix), hbuf in zip(jobs, h_img[slot]):
+                        path = os.path.join(output_folder, f"{base_name}_{frame:04d}_{suffix}.png")
+                        pending[slot].append(write_pool.submit(write, done, hbuf.numpy().reshape(h, w, bpp), path))
+                wait_slot(0)
+                wait_slot(1)
+            return stats
+        finally:
+            # on success everything has been waited for already; on an error this joins the threads before it propagates
+            write_pool.shutdown(wait=True, cancel_futures=True)
+            table_pool.shutdown(wait=True, cancel_futures=True)
+
+
+_SAVE_TO_SUFFIX = {ChannelKind.Color: "color", ChannelKind.Alpha: "alpha", ChannelKind.Background: "background", ChannelKind.WorldNormal: "normal"}
+_SAVE_TO_ERR = {ChannelKind.Color: "Attempted to write Color channel with insufficient channels",  # src/film.rs:283-287
+                ChannelKind.Alpha: "Attempted to write Alpha channel but it didn't exist",  # :341-345
+                ChannelKind.Background: "Attempted to write Background channel but it didn't exist",  # :292-296
+                ChannelKind.WorldNormal: "Attempted to write WorldNormal channel but it didn't exist"}  # :316-320
