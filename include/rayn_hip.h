@@ -281,6 +281,28 @@ int rayn_hip_save_to_pixels_device(rayn_ctx* ctx, uint32_t kind, uint32_t have_m
                                    uint32_t width, uint32_t height, const float* d_color, const float* d_alpha,
                                    const float* d_background, const float* d_normal, uint8_t* d_out, void* hip_stream);
 
+/* ---- denoiser of the film's Color channel (an EXTENSION: rayn has no denoiser) -------------------------------------------------
+ * The edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010), guided by WorldNormal and Alpha, on the film's planar layout
+ * (pixel x + y * width).  `iterations` L in 1..8; iteration i = 0 .. L-1 uses step 2^i and reads the previous iteration's colour.
+ * kc = 1 / sigma_color^2, kn = 1 / sigma_normal^2, ka = 1 / sigma_alpha^2 (f32).  A pixel whose colour has a non-finite component
+ * passes through; otherwise W = 9/64, S = (9/64) c_p, and for the 24 other taps of the 5x5 stencil in raster order (ky = -2..2
+ * outer, kx = -2..2 inner), q = p + (kx, ky) 2^i, skipped outside the image or where c_q has a non-finite component:
+ *   e = (d_c * kc * 4^i + d_n * kn) + d_a * ka   (squared distances of colour, normal and alpha; a term whose sigma is 0 is left out)
+ *   w = (h[ky+2] * h[kx+2]) * expf(-e), h = {1/16, 1/4, 3/8, 1/4, 1/16}, expf = dm_expf (rayn_detmath.h); a NaN w skips the tap
+ *   W += w, S += w * c_q;   out_p = S / W.
+ * All f32, no contraction, IEEE division.  Only Color is filtered; Alpha, Background and WorldNormal stay as rendered.
+ * Bytes of device scratch rayn_hip_denoise_device needs for a width x height film (0 for a size it rejects).  Host only; needs no GPU. */
+size_t rayn_denoise_scratch_bytes(uint32_t width, uint32_t height);
+/* Enqueue the filter on 'hip_stream' (NULL = the ctx's own stream; not waited for), on the ctx's GPU (devices[0] of a multi-device
+ * ctx).  DEVICE pointers: d_color / d_normal 3 floats per pixel, d_alpha 1, d_out_color 3; d_scratch 16-byte aligned, at least
+ * rayn_denoise_scratch_bytes.  A sigma of 0 switches its term off (that guide may be NULL); any other sigma must be finite and in
+ * [2^-30, 2^30].  RAYN_ERR_INVALID_ARG with a last error text for: a zero-sized image or width * height >= 2^31, iterations outside
+ * 1..8, a bad sigma, a NULL colour, output or scratch, a NULL guide whose sigma is not 0, too little or misaligned scratch, and
+ * d_out_color == d_color.  The inputs are not modified. */
+int rayn_hip_denoise_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t iterations, float sigma_color, float sigma_normal,
+                            float sigma_alpha, const float* d_color, const float* d_alpha, const float* d_normal, float* d_out_color,
+                            void* d_scratch, size_t scratch_bytes, void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */

@@ -36,7 +36,7 @@ EXPORTS = [
     "rayn_hip_set_batch_paths", "rayn_hip_set_cold_bytes", "rayn_hip_set_workers", "rayn_hip_set_tile_subset", "rayn_hip_set_trace_tile", "rayn_hip_get_trace", "rayn_hip_fma_policy", "rayn_hip_set_fma_policy", "rayn_hip_sizeof", "rayn_hip_probe_sdf_dist",
     "rayn_hip_probe_extend", "rayn_hip_probe_shadow", "rayn_hip_probe_detmath", "rayn_hip_probe_shading", "rayn_hip_build_variant",
     "rayn_hip_get_entry_stats", "rayn_hip_get_sdf_iterations", "rayn_hip_get_elision_counts", "rayn_hip_get_stage_slots", "rayn_share_pixels", "rayn_hip_render_frame_packed_device", "rayn_hip_unpack_share_device",
-    "rayn_save_to_bpp", "rayn_hip_save_to_pixels_device",
+    "rayn_save_to_bpp", "rayn_hip_save_to_pixels_device", "rayn_denoise_scratch_bytes", "rayn_hip_denoise_device",
 ]
 
 
@@ -86,6 +86,9 @@ def lib():
         L.rayn_hip_unpack_share_device.argtypes = [vp, C.POINTER(_abi.FrameParams)] + [vp] * 6
         L.rayn_save_to_bpp.argtypes = [C.c_uint32, C.c_uint32, C.c_int]
         L.rayn_hip_save_to_pixels_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32] + [vp] * 6
+        L.rayn_denoise_scratch_bytes.restype = C.c_size_t
+        L.rayn_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        L.rayn_hip_denoise_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float] + [vp] * 5 + [C.c_size_t, vp]
         L.rayn_sets_1d.restype = C.c_uint32
         L.rayn_sets_1d.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_sets_2d.restype = C.c_uint32

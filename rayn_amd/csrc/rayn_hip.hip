@@ -19,6 +19,7 @@
 #include "../../include/rayn_hip.h"
 #include "kernels.h"
 #include "save_to.h"
+#include "denoise.h"
 
 using namespace rayn;
 
@@ -1138,6 +1139,20 @@ int rayn_hip_save_to_pixels_device(rayn_ctx* ctx, uint32_t kind, uint32_t have_m
     HIPCHK(hipSetDevice(ctx->device)); // a multi-device ctx is entry 0: its device is devices[0], where the film lives
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     launch_save_to(s, arm, width, height, d_color, d_alpha, d_background, d_normal, d_out);
+    HIPCHK(hipGetLastError());
+    return RAYN_OK; // enqueued on the stream, not waited for
+}
+
+int rayn_hip_denoise_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t iterations, float sigma_color, float sigma_normal,
+                            float sigma_alpha, const float* d_color, const float* d_alpha, const float* d_normal, float* d_out_color,
+                            void* d_scratch, size_t scratch_bytes, void* hip_stream) {
+    if (!ctx) return RAYN_ERR_INVALID_ARG;
+    const char* why = denoise_check_args(width, height, iterations, sigma_color, sigma_normal, sigma_alpha, d_color, d_alpha, d_normal,
+                                         d_out_color, d_scratch, scratch_bytes);
+    if (why) return fail(ctx, RAYN_ERR_INVALID_ARG, why);
+    HIPCHK(hipSetDevice(ctx->device)); // a multi-device ctx is entry 0: its device is devices[0], where the film lives
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    launch_denoise(s, width, height, iterations, sigma_color, sigma_normal, sigma_alpha, d_color, d_alpha, d_normal, d_out_color, d_scratch);
     HIPCHK(hipGetLastError());
     return RAYN_OK; // enqueued on the stream, not waited for
 }
