@@ -303,6 +303,76 @@ int rayn_hip_denoise_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint
                             float sigma_alpha, const float* d_color, const float* d_alpha, const float* d_normal, float* d_out_color,
                             void* d_scratch, size_t scratch_bytes, void* hip_stream);
 
+/* ---- progressive rendering (an EXTENSION: rayn carries only an unused progressive_epoch counter, src/film.rs:178-179) ------------
+ * A progressive render is a series of EPOCHS: ordinary renders of the same frame, each under its own sample tables, whose finished
+ * films are accumulated.  Everything here happens to finished films; the integrator and the film resolve are not involved.
+ *
+ * Epoch seed.  Samples::new_rd gives set i the sequence offset (offset + i) << 32 (src/sampler.rs:22-29), so consecutive offsets share
+ * all but one set, shifted by one dimension.  Epoch e of frame f therefore uses the tables of offset seed(f, e) = f + e * 65536;
+ * epoch 0 is the plain frame.  Valid only while the sets of one epoch (3 + (max_bounces + 1) (15 + 9 volume_marches)) number at most
+ * 65536 and seed < 2^32: otherwise RAYN_ERR_INVALID_ARG, never a wrap.  The epoch's render call carries the seed in
+ * rayn_frame_params.frame (the kernels do not read it; the table broadcast of a multi-device context keys on it).  Scramble and filter
+ * tables do not depend on the epoch.  Host only; needs no GPU. */
+int rayn_progressive_seed(uint32_t frame, uint32_t epoch, uint32_t max_bounces, uint32_t volume_marches, uint32_t* out_seed);
+/* State, per film, in device memory the caller owns: per pixel the ten film floats as running sums and mean_y, m2 (48 bytes: three
+ * float4 planes in film pixel order - (sum Color, sum Alpha), (sum Background, mean_y), (sum WorldNormal, m2)); per tile a record of 4 u32
+ * (epochs, retired, outliers, bits of max_e); then 4 u32 of totals (active tiles, bits of max e, outlier pixels lo / hi), the active
+ * list and the list of the accumulate in flight (one u32 per tile each), in that order.  Bytes of it for a width x height film cut into
+ * tile_w x tile_h tiles (0 for a geometry the entries reject).  Host only; needs no GPU. */
+size_t rayn_progressive_state_bytes(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h);
+typedef struct {
+    float target_error;        /* a pixel with e_p > target_error is an outlier; finite, >= 0 */
+    float noise_floor;         /* added to |mean_y| in e_p's denominator; finite, >= 0 */
+    uint32_t min_epochs;       /* no tile retires before it has this many epochs; >= 2 */
+    uint32_t max_epochs;       /* the loop's limit (the entries only validate it); min_epochs .. 65536 */
+    uint32_t outlier_permille; /* a tile retires while at most this many per thousand of its pixels are outliers; <= 1000 */
+    uint32_t adaptive;         /* 0: no tile ever retires */
+} rayn_progressive_params;
+typedef struct {
+    uint32_t active_tiles;   /* tiles not retired */
+    float max_e;             /* the largest max_e of all tiles */
+    uint64_t outlier_pixels; /* the sum of all tiles' outliers */
+} rayn_progressive_totals;
+/* All rayn_hip_progressive_* entries take p for the film's geometry (width, height, tile_w, tile_h; the tiles are the reference's,
+ * x-major, src/film.rs:399-427), DEVICE pointers on the ctx's GPU (devices[0] of a multi-device ctx) and 'hip_stream' (NULL = the ctx's
+ * own stream); d_state 16-byte aligned, at least rayn_progressive_state_bytes.  RAYN_ERR_INVALID_ARG with a last error text for every
+ * rejected argument.
+ * Reset: enqueue a fresh state (sums -0.0f - the identity of IEEE addition, so that one epoch's sums are the epoch film's bits - mean_y =
+ * m2 = 0, no epochs, nothing retired, every tile active).  Not waited for. */
+int rayn_hip_progressive_reset_device(rayn_ctx* ctx, const rayn_frame_params* p, void* d_state, size_t state_bytes, void* hip_stream);
+/* Accumulate the epoch film F (the four planes rayn_hip_render_frame_device writes) into the tiles of the list `tiles` (a HOST array of
+ * n_tiles strictly ascending tile indices; NULL = every tile) and write those tiles' mean film to d_out_*.  For every pixel of a listed
+ * tile, with n = the tile's epochs after increment, all f32, no contraction, IEEE '/' and sqrt:
+ *   sum[k] = sum[k] + F[k]                                   k = 0..9
+ *   c      = F.color + F.background                          per channel
+ *   y      = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b
+ *   d      = y - mean_y;  mean_y = mean_y + d / (float)n;  m2 = m2 + d * (y - mean_y)
+ *   mean film[k] = sum[k] / (float)n
+ *   n >= 2:  se = sqrtf(m2 / (float)(n * (n - 1)));  e_p = se / (fabsf(mean_y) + noise_floor)
+ * Pixels of tiles not in the list are neither read nor written (state and mean film).  The tile's record: outliers = its pixels with
+ * e_p > target_error (a NaN e_p compares false: a NaN pixel never holds a tile open), max_e = the largest e_p > 0 (0 for n < 2 or where
+ * there is none).  With adaptive != 0 the tile retires when n >= min_epochs and outliers * 1000 <= outlier_permille * tile pixels (64-bit
+ * integers); a retired tile stays retired.  Then the active (not retired) tiles are compacted into an ascending list and the totals are
+ * taken, all on the device.  Enqueued, not waited for.  Rejected: a zero-sized film or tile, width * height >= 2^31, a NULL plane or
+ * state, too little or misaligned state, a tile index beyond the tile count, a list not strictly ascending or empty, min_epochs < 2,
+ * max_epochs < min_epochs or > 65536, a non-finite or negative target_error / noise_floor, outlier_permille > 1000, and an output plane
+ * that is one of the epoch film's planes.  The epoch film is not modified. */
+int rayn_hip_progressive_accumulate_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_progressive_params* pp,
+                                           const uint32_t* tiles, uint32_t n_tiles, const float* d_color, const float* d_alpha,
+                                           const float* d_background, const float* d_normal, void* d_state, size_t state_bytes,
+                                           float* d_out_color, float* d_out_alpha, float* d_out_background, float* d_out_normal,
+                                           void* hip_stream);
+/* The active list and the totals of the state as the work queued on the stream leaves them.  BLOCKING: the one small read-back of a
+ * progressive epoch (16 bytes + 4 per tile), which the host needs for rayn_hip_set_tile_subset.  out_tiles: HOST array of `cap` entries
+ * (cap >= the film's tile count, or out_tiles NULL to fetch the totals alone); out_totals may be NULL.  Returns the number of active
+ * tiles (>= 0) or a negative rayn_status. */
+int64_t rayn_hip_progressive_fetch_active(rayn_ctx* ctx, const rayn_frame_params* p, const void* d_state, size_t state_bytes,
+                                          uint32_t* out_tiles, uint32_t cap, rayn_progressive_totals* out_totals, void* hip_stream);
+/* Diagnostics, BLOCKING: every tile's record into HOST arrays of rayn_tile_count entries (any may be NULL). */
+int rayn_hip_progressive_tile_report(rayn_ctx* ctx, const rayn_frame_params* p, const void* d_state, size_t state_bytes,
+                                     uint32_t* out_epochs, uint32_t* out_retired, uint32_t* out_outliers, float* out_max_e,
+                                     void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */

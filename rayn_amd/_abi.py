@@ -56,6 +56,15 @@ class FrameParams(C.Structure):
                 ("tile_first", C.c_uint32), ("tile_step", C.c_uint32)]
 
 
+class ProgressiveParams(C.Structure):  # rayn_progressive_params
+    _fields_ = [("target_error", C.c_float), ("noise_floor", C.c_float), ("min_epochs", C.c_uint32), ("max_epochs", C.c_uint32),
+                ("outlier_permille", C.c_uint32), ("adaptive", C.c_uint32)]
+
+
+class ProgressiveTotals(C.Structure):  # rayn_progressive_totals
+    _fields_ = [("active_tiles", C.c_uint32), ("max_e", C.c_float), ("outlier_pixels", C.c_uint64)]
+
+
 class Stats(C.Structure):
     _fields_ = [("paths", C.c_uint64), ("segments", C.c_uint64), ("shaded_slots", C.c_uint64),
                 ("tiles", C.c_uint64), ("batches", C.c_uint64), ("ms_total", C.c_double),

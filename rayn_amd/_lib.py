@@ -37,6 +37,8 @@ EXPORTS = [
     "rayn_hip_probe_extend", "rayn_hip_probe_shadow", "rayn_hip_probe_detmath", "rayn_hip_probe_shading", "rayn_hip_build_variant",
     "rayn_hip_get_entry_stats", "rayn_hip_get_sdf_iterations", "rayn_hip_get_elision_counts", "rayn_hip_get_stage_slots", "rayn_share_pixels", "rayn_hip_render_frame_packed_device", "rayn_hip_unpack_share_device",
     "rayn_save_to_bpp", "rayn_hip_save_to_pixels_device", "rayn_denoise_scratch_bytes", "rayn_hip_denoise_device",
+    "rayn_progressive_seed", "rayn_progressive_state_bytes", "rayn_hip_progressive_reset_device", "rayn_hip_progressive_accumulate_device",
+    "rayn_hip_progressive_fetch_active", "rayn_hip_progressive_tile_report",
 ]
 
 
@@ -89,6 +91,16 @@ def lib():
         L.rayn_denoise_scratch_bytes.restype = C.c_size_t
         L.rayn_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_hip_denoise_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float] + [vp] * 5 + [C.c_size_t, vp]
+        L.rayn_progressive_seed.argtypes = [C.c_uint32] * 4 + [up]
+        L.rayn_progressive_state_bytes.restype = C.c_size_t
+        L.rayn_progressive_state_bytes.argtypes = [C.c_uint32] * 4
+        L.rayn_hip_progressive_reset_device.argtypes = [vp, C.POINTER(_abi.FrameParams), vp, C.c_size_t, vp]
+        L.rayn_hip_progressive_accumulate_device.argtypes = ([vp, C.POINTER(_abi.FrameParams), C.POINTER(_abi.ProgressiveParams), up, C.c_uint32]
+                                                             + [vp] * 5 + [C.c_size_t] + [vp] * 5)
+        L.rayn_hip_progressive_fetch_active.restype = C.c_int64
+        L.rayn_hip_progressive_fetch_active.argtypes = [vp, C.POINTER(_abi.FrameParams), vp, C.c_size_t, up, C.c_uint32,
+                                                        C.POINTER(_abi.ProgressiveTotals), vp]
+        L.rayn_hip_progressive_tile_report.argtypes = [vp, C.POINTER(_abi.FrameParams), vp, C.c_size_t, up, up, up, fp, vp]
         L.rayn_sets_1d.restype = C.c_uint32
         L.rayn_sets_1d.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_sets_2d.restype = C.c_uint32

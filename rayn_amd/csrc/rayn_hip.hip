@@ -20,6 +20,7 @@
 #include "kernels.h"
 #include "save_to.h"
 #include "denoise.h"
+#include "progressive.h"
 
 using namespace rayn;
 
@@ -94,6 +95,7 @@ struct rayn_ctx {
     int n_workers = 2;
     Tuning tun;
     std::vector<uint32_t> tile_subset; // rayn_hip_set_tile_subset: render only these tiles (sorted)
+    std::vector<uint32_t> prog_host;   // rayn_hip_progressive_*: host side of the tile list upload and of the read-backs
     // ---- multi-device context (rayn_hip_create_multi): this ctx is entry 0 and owns the others; every peer is a complete
     // single-device ctx (own streams, workers, arenas) on its device.  A render deals the share's tiles to the entries, each
     // renders its list (only_tiles), packs its pixels and sends them to device 0 with one peer copy (render_multi).
@@ -1155,6 +1157,103 @@ int rayn_hip_denoise_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint
     launch_denoise(s, width, height, iterations, sigma_color, sigma_normal, sigma_alpha, d_color, d_alpha, d_normal, d_out_color, d_scratch);
     HIPCHK(hipGetLastError());
     return RAYN_OK; // enqueued on the stream, not waited for
+}
+
+// the checks every rayn_hip_progressive_* entry shares; on success *L is the state's layout
+static const char* progressive_geometry(const rayn_frame_params* p, const void* d_state, size_t state_bytes, ProgLayout* L) {
+    const char* why = progressive_check_geometry(p, d_state, state_bytes);
+    if (!why) *L = progressive_layout(p->width, p->height, p->tile_w, p->tile_h);
+    return why;
+}
+
+int rayn_hip_progressive_reset_device(rayn_ctx* ctx, const rayn_frame_params* p, void* d_state, size_t state_bytes, void* hip_stream) {
+    if (!ctx) return RAYN_ERR_INVALID_ARG;
+    ProgLayout L;
+    const char* why = progressive_geometry(p, d_state, state_bytes, &L);
+    if (why) return fail(ctx, RAYN_ERR_INVALID_ARG, why);
+    HIPCHK(hipSetDevice(ctx->device)); // a multi-device ctx is entry 0: its device is devices[0], where the film lives
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    launch_progressive_reset(s, L, d_state);
+    HIPCHK(hipGetLastError());
+    return RAYN_OK; // enqueued on the stream, not waited for
+}
+
+int rayn_hip_progressive_accumulate_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_progressive_params* pp, const uint32_t* tiles,
+                                           uint32_t n_tiles, const float* d_color, const float* d_alpha, const float* d_background,
+                                           const float* d_normal, void* d_state, size_t state_bytes, float* d_out_color, float* d_out_alpha,
+                                           float* d_out_background, float* d_out_normal, void* hip_stream) {
+    if (!ctx) return RAYN_ERR_INVALID_ARG;
+    ProgLayout L;
+    const char* why = progressive_geometry(p, d_state, state_bytes, &L);
+    if (!why) why = progressive_check_params(pp);
+    if (!why && (!d_color || !d_alpha || !d_background || !d_normal || !d_out_color || !d_out_alpha || !d_out_background || !d_out_normal)) why = "null buffer";
+    if (!why) {
+        const float* in[4] = {d_color, d_alpha, d_background, d_normal};
+        const float* out[4] = {d_out_color, d_out_alpha, d_out_background, d_out_normal};
+        for (int i = 0; i < 4; i++)
+            for (int j = 0; j < 4; j++)
+                if (out[i] == in[j]) why = "the output film must not alias the epoch film";
+    }
+    if (!why) why = progressive_check_tiles(L, tiles, n_tiles);
+    if (why) return fail(ctx, RAYN_ERR_INVALID_ARG, why);
+    HIPCHK(hipSetDevice(ctx->device)); // a multi-device ctx is entry 0: its device is devices[0], where the film lives
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    uint32_t* d_list = nullptr;
+    if (tiles) {
+        d_list = (uint32_t*)((char*)d_state + L.off_listed);
+        ctx->prog_host.assign(tiles, tiles + n_tiles); // the caller's array may go away once this returns
+        HIPCHK(hipMemcpyAsync(d_list, ctx->prog_host.data(), (size_t)n_tiles * 4u, hipMemcpyHostToDevice, s));
+    }
+    launch_progressive_accumulate(s, L, *pp, d_list, n_tiles, d_color, d_alpha, d_background, d_normal, d_state, d_out_color, d_out_alpha,
+                                  d_out_background, d_out_normal);
+    launch_progressive_compact(s, L, d_state);
+    HIPCHK(hipGetLastError());
+    return RAYN_OK; // enqueued on the stream, not waited for
+}
+
+int64_t rayn_hip_progressive_fetch_active(rayn_ctx* ctx, const rayn_frame_params* p, const void* d_state, size_t state_bytes, uint32_t* out_tiles,
+                                          uint32_t cap, rayn_progressive_totals* out_totals, void* hip_stream) {
+    if (!ctx) return RAYN_ERR_INVALID_ARG;
+    ProgLayout L;
+    const char* why = progressive_geometry(p, d_state, state_bytes, &L);
+    if (!why && out_tiles && cap < L.n_tiles) why = "out_tiles holds fewer entries than the film has tiles";
+    if (why) return fail(ctx, RAYN_ERR_INVALID_ARG, why);
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    const size_t words = 4u + (out_tiles ? (size_t)L.n_tiles : 0u); // totals, then the list: adjacent in the state, ONE copy
+    ctx->prog_host.resize(words);
+    HIPCHK(hipMemcpyAsync(ctx->prog_host.data(), (const char*)d_state + L.off_totals, words * 4u, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const uint32_t* h = ctx->prog_host.data();
+    if (h[0] > L.n_tiles) return fail(ctx, RAYN_ERR_INVALID_ARG, "the state holds more active tiles than the film has tiles (not a state of this film?)");
+    if (out_totals) {
+        out_totals->active_tiles = h[0];
+        memcpy(&out_totals->max_e, &h[1], 4);
+        out_totals->outlier_pixels = (uint64_t)h[2] | ((uint64_t)h[3] << 32);
+    }
+    if (out_tiles) memcpy(out_tiles, h + 4, (size_t)h[0] * 4u);
+    return (int64_t)h[0];
+}
+
+int rayn_hip_progressive_tile_report(rayn_ctx* ctx, const rayn_frame_params* p, const void* d_state, size_t state_bytes, uint32_t* out_epochs,
+                                     uint32_t* out_retired, uint32_t* out_outliers, float* out_max_e, void* hip_stream) {
+    if (!ctx) return RAYN_ERR_INVALID_ARG;
+    ProgLayout L;
+    const char* why = progressive_geometry(p, d_state, state_bytes, &L);
+    if (why) return fail(ctx, RAYN_ERR_INVALID_ARG, why);
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    ctx->prog_host.resize((size_t)L.n_tiles * 4u);
+    HIPCHK(hipMemcpyAsync(ctx->prog_host.data(), (const char*)d_state + L.off_records, (size_t)L.n_tiles * 16u, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t k = 0; k < L.n_tiles; k++) {
+        const uint32_t* r = ctx->prog_host.data() + (size_t)k * 4u;
+        if (out_epochs) out_epochs[k] = r[0];
+        if (out_retired) out_retired[k] = r[1];
+        if (out_outliers) out_outliers[k] = r[2];
+        if (out_max_e) memcpy(&out_max_e[k], &r[3], 4);
+    }
+    return RAYN_OK;
 }
 
 int rayn_hip_get_entry_stats(const rayn_ctx* ctx, int entry, rayn_stats* out) {

@@ -15,8 +15,10 @@ import os
 import numpy as np
 
 from . import _abi, image
+from . import progressive as _prog
 from ._lib import RaynHipError, lib
 from .params import frame_params
+from .progressive import Progressive, progressive_seed  # noqa: F401
 
 
 class ChannelKind(enum.Enum):  # src/film.rs:103-120
@@ -123,6 +125,7 @@ class Context:
             raise RaynHipError(f"rayn_hip_create(device={device}) failed with {rc} (no usable GPU?)")
         self.h = h
         self.device = first
+        self.fma_policy = int(self._L.rayn_hip_fma_policy())  # of this ctx: the library's default until set_fma_policy
 
     def device_count(self):
         return self._L.rayn_hip_device_count(self.h)
@@ -147,6 +150,7 @@ class Context:
     def set_fma_policy(self, policy):
         """0 = unfused mul_add (reference default build, the default), 1 = fused (rayn built with +fma)."""
         self._chk(self._L.rayn_hip_set_fma_policy(self.h, int(policy)))
+        self.fma_policy = int(policy)
 
     def set_workers(self, n_workers, min_paths=1 << 22):
         self._chk(self._L.rayn_hip_set_workers(self.h, int(n_workers), int(min_paths)))
@@ -301,6 +305,74 @@ class Context:
                                                   C.c_void_p(d_out_color.data_ptr()), C.c_void_p(d_scratch.data_ptr()),
                                                   d_scratch.numel() * d_scratch.element_size(), C.c_void_p(s)))
 
+    @staticmethod
+    def _prog_state(params, d_state):
+        import torch
+        need = _prog.state_bytes(params.width, params.height, (params.tile_w, params.tile_h))
+        if not (d_state.dtype == torch.uint8 and d_state.is_contiguous()):
+            raise ValueError("d_state must be a contiguous uint8 tensor")
+        if need and d_state.numel() < need:
+            raise ValueError(f"d_state must hold at least {need} bytes")
+        return C.c_void_p(d_state.data_ptr()), d_state.numel()
+
+    def progressive_reset(self, params, d_state, stream=None):
+        """rayn_hip_progressive_reset_device: a fresh progressive state for the film geometry of `params` in the uint8 CUDA tensor
+        `d_state` (at least rayn_amd.progressive.state_bytes).  Enqueued on the stream, not waited for."""
+        import torch
+        ptr, nbytes = self._prog_state(params, d_state)
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._chk(self._L.rayn_hip_progressive_reset_device(self.h, C.byref(params), ptr, nbytes, C.c_void_p(s)))
+
+    def progressive_accumulate(self, params, progressive, tiles, d_epoch, d_state, d_mean, stream=None):
+        """rayn_hip_progressive_accumulate_device: accumulate the epoch film `d_epoch` (a dict of torch CUDA tensors as render_device
+        fills them) into the tiles `tiles` (ascending indices; None = every tile) of `d_state`, write those tiles' mean film to `d_mean`,
+        retire tiles by the Progressive `progressive` and compact the active list.  Enqueued on the stream, not waited for."""
+        import torch
+        n = params.width * params.height
+        ptrs = []
+        for film in (d_epoch, d_mean):
+            for key, floats in (("color", 3), ("alpha", 1), ("background", 3), ("normal", 3)):
+                t = film.get(key)
+                if t is None or not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= floats * n):
+                    raise ValueError(f"film[{key!r}] must be a contiguous float32 tensor of at least {floats * n} floats")
+                ptrs.append(C.c_void_p(t.data_ptr()))
+        ptr, nbytes = self._prog_state(params, d_state)
+        arr, n_tiles = None, 0
+        if tiles is not None:
+            arr = np.ascontiguousarray(tiles, dtype=np.uint32)
+            n_tiles = len(arr)
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        pp = progressive.to_abi()
+        self._chk(self._L.rayn_hip_progressive_accumulate_device(self.h, C.byref(params), C.byref(pp),
+                                                                 None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_uint32)), n_tiles,
+                                                                 *ptrs[:4], ptr, nbytes, *ptrs[4:], C.c_void_p(s)))
+
+    def progressive_fetch_active(self, params, d_state, stream=None):
+        """rayn_hip_progressive_fetch_active (blocking): (the ascending list of the tiles not retired as a uint32 array, totals dict)."""
+        import torch
+        ptr, nbytes = self._prog_state(params, d_state)
+        cap = int(self._L.rayn_tile_count(params.width, params.height, params.tile_w, params.tile_h))
+        out = np.zeros(max(cap, 1), np.uint32)
+        tot = _abi.ProgressiveTotals()
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        n = self._L.rayn_hip_progressive_fetch_active(self.h, C.byref(params), ptr, nbytes, out.ctypes.data_as(C.POINTER(C.c_uint32)), cap,
+                                                      C.byref(tot), C.c_void_p(s))
+        if n < 0:
+            self._chk(int(n))
+        return out[:n].copy(), {"active_tiles": int(tot.active_tiles), "max_e": float(tot.max_e), "outlier_pixels": int(tot.outlier_pixels)}
+
+    def progressive_tile_report(self, params, d_state, stream=None):
+        """rayn_hip_progressive_tile_report (blocking): dict of per-tile arrays epochs, retired, outliers (uint32) and max_e (float32)."""
+        import torch
+        ptr, nbytes = self._prog_state(params, d_state)
+        t = max(int(self._L.rayn_tile_count(params.width, params.height, params.tile_w, params.tile_h)), 1)
+        rep = {"epochs": np.zeros(t, np.uint32), "retired": np.zeros(t, np.uint32), "outliers": np.zeros(t, np.uint32), "max_e": np.zeros(t, np.float32)}
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._chk(self._L.rayn_hip_progressive_tile_report(self.h, C.byref(params), ptr, nbytes, up(rep["epochs"]), up(rep["retired"]),
+                                                           up(rep["outliers"]), _fp(rep["max_e"]), C.c_void_p(s)))
+        return rep
+
     def close(self):
         if self.h:
             self._L.rayn_hip_destroy(self.h)
@@ -340,6 +412,7 @@ class Film:
         self.device = f"cuda:{device}"
         self.channels = None  # torch tensors after a render
         self.progressive_epoch = 0
+        self._progressive = None  # after render_progressive: its device state, geometry, checkpoint key and epoch count
 
     def render_frame_into(self, world, camera, integrator, filter, tile_size, frame, time_range, samples, tile_first=0, tile_step=1):
         """Film::render_frame_into (src/film.rs:382-628); the film is overwritten, not accumulated (:91)."""
@@ -422,6 +495,122 @@ class Film:
             if denoise is not None and kind == ChannelKind.Color:
                 suffix = "color_denoised"
             image.save(os.path.join(output_folder, f"{base_name}_{suffix}.png"), self.pixels(kind, transparent_background, denoise))
+
+    def render_progressive(self, world, camera, integrator, filter, tile_size, frame, time_range, samples, progressive=None, on_epoch=None,
+                           resume=None):
+        """Render frame `frame` progressively (an extension; include/rayn_hip.h has the definition): a series of epochs, each an ordinary
+        render of the frame (render_frame_into's arguments) under the sample tables of progressive_seed(frame, epoch), accumulated on the
+        device.  After every epoch film.channels holds the mean film of all epochs so far, so pixels / save_to / denoise= work on it
+        unchanged.  With progressive.adaptive, tiles whose error estimate has met the target retire and later epochs render only the
+        tiles still active (Context.set_tile_subset); the render ends when none is left or after progressive.max_epochs.
+
+        The world is uploaded once; scramble and filter tables are built once; epoch e + 1's R_d tables are built on a host thread while
+        epoch e renders; per epoch only the active list (16 bytes + 4 per tile) comes back to the host.  on_epoch(report), called after
+        every epoch with the report so far (report["epoch_film"]: the device film the epoch rendered; only the tiles
+        report["rendered_tiles"], None = all, are current), may return False to stop.  resume=path continues the render a checkpoint
+        (save_checkpoint) was made from; ValueError if it belongs to another render.  The tile subset is cleared on every exit path.
+
+        Returns the report (a dict): epochs (run in total, those before a resume included), seed and rendered_tiles of the last epoch,
+        active_tiles, totals, tile_epochs (per-tile epoch counts), paths traced by this call, paths_non_adaptive (what its epochs would
+        have traced over the whole frame), and stats (Context.stats() of every epoch of this call plus "epoch" and "seed")."""
+        import concurrent.futures as cf
+        import torch
+        progressive = Progressive() if progressive is None else progressive
+        w, h = self.res
+        spp, mb, vm = 4 * samples, integrator.max_bounces, integrator.volume_marches
+        p0 = frame_params(w, h, samples, mb, vm, frame, time_range, tile_size)
+        progressive_seed(frame, progressive.max_epochs - 1, mb, vm)  # every seed of the run is valid, or nothing renders
+        desc = world.to_desc(camera)
+        key = _prog.checkpoint_key((w, h), tile_size, samples, mb, vm, frame, (p0.time_start, p0.time_end), filter, desc, progressive,
+                                   self.ctx.fma_policy)
+        rects = _prog.tile_rects(w, h, tile_size)
+        covered = sum((x1 - x0) * (y1 - y0) for x0, y0, x1, y1 in rects)
+        first, restored = 0, None
+        if resume is not None:
+            saved, restored, first = _prog.read_checkpoint(resume)
+            _prog.check_key(saved, key)
+        report = {"epochs": first, "seed": None, "rendered_tiles": None, "active_tiles": None, "totals": None, "tile_epochs": None, "paths": 0,
+                  "paths_non_adaptive": 0, "stats": [], "epoch_film": None}
+        table_pool = cf.ThreadPoolExecutor(max_workers=1, thread_name_prefix="rayn-rd-tables")
+        try:
+            with torch.cuda.device(self.device):
+                stream = torch.cuda.current_stream()
+                self.ctx.upload_world(desc)
+                d_state = torch.empty(_prog.state_bytes(w, h, tile_size), dtype=torch.uint8, device=self.device)
+                d_mean = alloc_device_film(w, h, self.device)
+                if restored is None:
+                    self.ctx.progressive_reset(p0, d_state, stream.cuda_stream)
+                else:
+                    d_state.copy_(torch.from_numpy(_prog.join_state(restored, w, h, tile_size)))
+                    for k, v in _prog.mean_film(restored, w, h, tile_size).items():
+                        d_mean[k].copy_(torch.from_numpy(v).reshape(d_mean[k].shape))
+                self.channels = d_mean
+                self._progressive = {"state": d_state, "params": p0, "key": key, "epochs": first, "noise_floor": progressive.noise_floor}
+                active, totals = self.ctx.progressive_fetch_active(p0, d_state, stream.cuda_stream)
+                report.update(active_tiles=active, totals=totals)
+                if first < progressive.max_epochs and len(active):
+                    next_rd = table_pool.submit(build_rd_tables, spp, mb, vm, progressive_seed(frame, first, mb, vm))
+                    scr, fis = build_film_tables(w, h, filter)
+                    d_tables, d_epoch = None, alloc_device_film(w, h, self.device)
+                    report["epoch_film"] = d_epoch
+                epoch = first
+                while epoch < progressive.max_epochs and len(active):
+                    seed = progressive_seed(frame, epoch, mb, vm)
+                    s1, s2 = next_rd.result()
+                    if d_tables is None:
+                        d_tables = [torch.from_numpy(t).to(self.device) for t in (s1, s2, scr, fis)]
+                    else:
+                        d_tables[0].copy_(torch.from_numpy(s1))  # synchronous copies from pageable memory: the previous render has returned
+                        d_tables[1].copy_(torch.from_numpy(s2))
+                    if epoch + 1 < progressive.max_epochs:
+                        next_rd = table_pool.submit(build_rd_tables, spp, mb, vm, progressive_seed(frame, epoch + 1, mb, vm))
+                    subset = None if len(active) == len(rects) else active
+                    self.ctx.set_tile_subset(subset)
+                    # the epoch's render carries the seed as its frame: the table broadcast of a multi-device context keys on it
+                    p = frame_params(w, h, samples, mb, vm, seed, (p0.time_start, p0.time_end), tile_size)
+                    self.ctx.render_device(p, d_tables, d_epoch, stream.cuda_stream)  # blocking: returns when the epoch's film is complete
+                    st = self.ctx.stats()
+                    st.update(epoch=epoch, seed=seed)
+                    self.ctx.progressive_accumulate(p0, progressive, subset, d_epoch, d_state, d_mean, stream.cuda_stream)
+                    active, totals = self.ctx.progressive_fetch_active(p0, d_state, stream.cuda_stream)
+                    epoch += 1
+                    self.progressive_epoch += 1
+                    self._progressive["epochs"] = epoch
+                    report["stats"].append(st)
+                    report.update(epochs=epoch, seed=seed, rendered_tiles=subset, active_tiles=active, totals=totals,
+                                  paths=report["paths"] + st["paths"], paths_non_adaptive=report["paths_non_adaptive"] + covered * spp)
+                    if on_epoch is not None and on_epoch(report) is False:
+                        break
+                report["tile_epochs"] = self.ctx.progressive_tile_report(p0, d_state, stream.cuda_stream)["epochs"]
+            return report
+        finally:
+            self.ctx.set_tile_subset(None)
+            table_pool.shutdown(wait=True, cancel_futures=True)
+
+    def _progressive_arrays(self):
+        if self._progressive is None:
+            raise ValueError("the film holds no progressive render (render_progressive has not run)")
+        pr = self._progressive
+        w, h = self.res
+        return _prog.split_state(pr["state"].cpu().numpy(), w, h, (pr["params"].tile_w, pr["params"].tile_h)), pr
+
+    def save_checkpoint(self, path):
+        """Write the progressive render this film holds to `path` (one .npz: the state, the tile records and the key of the render);
+        render_progressive(..., resume=path) with the same arguments continues it, bit for bit as if it had not stopped."""
+        arrays, pr = self._progressive_arrays()
+        _prog.write_checkpoint(path, pr["key"], arrays, pr["epochs"])
+
+    def sample_count_image(self):
+        """u8 heat map ((h, w), rows top-down) of the per-tile epoch counts of the progressive render: 255 = the largest count."""
+        arrays, pr = self._progressive_arrays()
+        w, h = self.res
+        return _prog.sample_count_image(arrays["epochs"], w, h, (pr["params"].tile_w, pr["params"].tile_h))
+
+    def error_map(self):
+        """The error estimate e_p of every pixel of the progressive render, float32 (h, w), rows bottom-up like the film."""
+        arrays, pr = self._progressive_arrays()
+        w, h = self.res
+        return _prog.error_map(arrays, w, h, (pr["params"].tile_w, pr["params"].tile_h), pr["noise_floor"])
 
     def render_sequence(self, world, camera, integrator, filter, tile_size, frames, frame_rate, shutter_speed, samples, write_channels,
                         output_folder, base_name, transparent_background=False, writers=None, denoise=None):
