@@ -1811,7 +1811,7 @@ __global__ void __launch_bounds__(256) k_unpack_tiles(const DTile* __restrict__ 
 
 // ------------------------------------------------------------------------------------------------
 // test probes (called through the C ABI by tests only): per-lane primitives on arbitrary inputs.  (Closest hit and occlusion have no
-// probe kernel: rayn_hip_probe_extend / rayn_hip_probe_shadow launch the PRODUCT march kernels on a synthetic queue, rayn_hip.hip.)
+// probe kernel: rayn_hip_probe_extend / rayn_hip_probe_shadow launch the PRODUCT march kernels on a synthetic queue, probes.hip.)
 // ------------------------------------------------------------------------------------------------
 __global__ void k_probe_dist(const DScene* __restrict__ scp, uint32_t hit_index, const float* __restrict__ pts, float* __restrict__ out, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

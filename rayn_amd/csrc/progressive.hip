@@ -30,6 +30,7 @@
 
 #include "../../include/rayn_hip.h"
 #include "progressive.h"
+#include "tiles.h"
 
 namespace rayn {
 namespace {
@@ -205,11 +206,11 @@ ProgLayout progressive_layout(uint32_t width, uint32_t height, uint32_t tile_w, 
     memset(&L, 0, sizeof L);
     const uint64_t n = (uint64_t)width * height;
     if (!n || n >= ((uint64_t)1 << 31) || !tile_w || !tile_h) return L;
-    const uint32_t nx = (width + width % tile_w) / tile_w, ny = (height + height % tile_h) / tile_h; // src/film.rs:399-404
-    if (!nx || !ny) return L;
+    const TileGrid grid(width, height, tile_w, tile_h);
+    if (!grid.count()) return L;
     L.width = width; L.height = height; L.tile_w = tile_w; L.tile_h = tile_h;
-    L.tiles_y = ny;
-    L.n_tiles = nx * ny;
+    L.tiles_y = grid.ny;
+    L.n_tiles = grid.count();
     L.pixels = n;
     const size_t plane = (size_t)n * 16u, t = L.n_tiles;
     L.off_s0 = 0;

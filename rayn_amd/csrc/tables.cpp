@@ -11,6 +11,7 @@
 
 #include "../../include/rayn_detmath.h"
 #include "../../include/rayn_hip.h"
+#include "tiles.h"
 
 namespace {
 
@@ -142,8 +143,7 @@ int rayn_build_fis_table_ex(uint32_t filter_kind, float radius, float param0, fl
 }
 
 uint32_t rayn_tile_count(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h) {
-    if (!tile_w || !tile_h) return 0;
-    return ((width + width % tile_w) / tile_w) * ((height + height % tile_h) / tile_h); // src/film.rs:399-404
+    return rayn::TileGrid(width, height, tile_w, tile_h).count(); // 0 for a zero tile size
 }
 
 } // extern "C"

@@ -45,6 +45,22 @@ def test_tile_count_quirk(L):
     assert L.rayn_tile_count(256, 256, 16, 16) == 256
 
 
+def test_tile_count_and_progressive_state_follow_the_tile_list(L):
+    """rayn_tile_count and rayn_progressive_state_bytes count the tiles of the same grid as the Python mirror of the reference's tile
+    list (distributed.tile_rects), incl. under-covered resolutions and a tile larger than the film (no tiles: a count of 0 and a
+    rejected state geometry); a zero tile size gives 0 from both.  State layout as include/rayn_hip.h documents it: three float4
+    planes per pixel, 16 bytes per tile of records, 16 of totals, two u32 lists of one entry per tile, rounded up to 16."""
+    from rayn_amd.distributed import tile_rects
+    for (w, h, tw, th) in [(64, 48, 16, 16), (50, 37, 16, 16), (1920, 1080, 16, 16), (256, 256, 16, 16), (33, 20, 8, 4), (5, 3, 16, 16)]:
+        t = len(tile_rects(w, h, tw, th))
+        assert L.rayn_tile_count(w, h, tw, th) == t, (w, h, tw, th)
+        want = (48 * w * h + 16 * t + 16 + 8 * t + 15) // 16 * 16 if t else 0
+        assert L.rayn_progressive_state_bytes(w, h, tw, th) == want, (w, h, tw, th)
+    assert len(tile_rects(5, 3, 16, 16)) == 0
+    assert L.rayn_tile_count(64, 48, 0, 16) == 0 and L.rayn_tile_count(64, 48, 16, 0) == 0
+    assert L.rayn_progressive_state_bytes(64, 48, 0, 16) == 0 and L.rayn_progressive_state_bytes(64, 48, 16, 0) == 0
+
+
 def test_create_without_gpu_is_an_error_not_a_fallback(L):
     import torch
     if torch.cuda.is_available():

@@ -82,7 +82,7 @@ def test_packed_shares_reassemble_the_frame(gpu_ctx, oracle, name, w, h, samples
 
 
 @pytest.mark.gpu
-def test_packed_entry_argument_errors(gpu_ctx):
+def test_packed_entry_argument_errors(gpu_ctx, oracle):
     import torch
     import rayn_amd
     wd, p = case("s1", 64, 48, 1, 1)
@@ -90,6 +90,18 @@ def test_packed_entry_argument_errors(gpu_ctx):
     L = gpu_ctx._L
     buf = torch.zeros(64 * 48 * 10, device="cuda:0")
     assert L.rayn_hip_render_frame_packed_device(gpu_ctx.h, C.byref(p), None, None, None, None, None, None) == -1
+    # a valid packed film with NULL tables passes the entry's own checks and is rejected by the renderer before anything is launched:
+    # nothing of the refused packed call may stick to the context - the next plain frame is the oracle's, bit for bit
+    assert L.rayn_hip_render_frame_packed_device(gpu_ctx.h, C.byref(p), None, None, None, None, C.c_void_p(buf.data_ptr()), None) == -1
+    assert b"null buffer" in L.rayn_hip_last_error(gpu_ctx.h)
+    tabs = oracle.build_tables(4, 1, p.volume_marches, p.frame, 64, 48)
+    ref, _ = oracle.render(wd, p, tabs)
+    film = rayn_amd.film.alloc_device_film(64, 48, "cuda:0")
+    gpu_ctx.render_device(p, [torch.from_numpy(t).cuda() for t in tabs], film)
+    torch.cuda.synchronize()
+    assert film_equal_bits({"color": film["color"].cpu().numpy().reshape(48, 64, 3), "alpha": film["alpha"].cpu().numpy().reshape(48, 64),
+                            "background": film["background"].cpu().numpy().reshape(48, 64, 3),
+                            "normal": film["normal"].cpu().numpy().reshape(48, 64, 3)}, ref)
     gpu_ctx.set_tile_subset([0, 1])
     try:
         d = C.c_void_p(buf.data_ptr())
