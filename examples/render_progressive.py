@@ -3,10 +3,12 @@ filter, 16x16 tiles) with Film.render_progressive: epochs are accumulated on the
 and later epochs render only the tiles still active.  Prints one line per epoch and writes the final PNGs and the sample-count image.
 
     python examples/render_progressive.py [--out renders_progressive] [--max-epochs 64] [--target-error 0.05] [--non-adaptive]
-                                          [--checkpoint FILE] [--resume FILE] [--denoise]
+                                          [--checkpoint FILE] [--resume FILE] [--denoise {atrous,variance}]
 
 --checkpoint writes the state after the last epoch; --resume continues the render such a file was made from (same arguments otherwise).
---denoise also writes the Color image after the a-trous denoiser (rayn_amd.Denoise() defaults)."""
+--denoise also writes the Color image after a denoiser: `atrous` (also a bare --denoise) is the fixed-sigma a-trous filter
+(rayn_amd.Denoise() defaults), `variance` the one guided by the per-pixel variance this render measured (rayn_amd.VarianceDenoise()
+defaults; it needs at least two epochs)."""
 import argparse
 import dataclasses
 import os
@@ -42,7 +44,8 @@ def main():
     ap.add_argument("--non-adaptive", action="store_true", help="no tile retires: every epoch renders the whole frame")
     ap.add_argument("--checkpoint", default=None, help="write the state to this file after the last epoch")
     ap.add_argument("--resume", default=None, help="continue the render this checkpoint was made from")
-    ap.add_argument("--denoise", action="store_true", help="also write the denoised Color (rayn_amd.Denoise() defaults)")
+    ap.add_argument("--denoise", nargs="?", const="atrous", default=None, choices=("atrous", "variance"),
+                    help="also write the denoised Color: atrous = rayn_amd.Denoise(), variance = rayn_amd.VarianceDenoise()")
     args = ap.parse_args()
     given = {k: getattr(args, k) for k in ("max_epochs", "min_epochs", "target_error", "noise_floor", "outlier_permille") if getattr(args, k) is not None}
     prog = dataclasses.replace(R.Progressive(), adaptive=not args.non_adaptive, **given)
@@ -71,7 +74,7 @@ def main():
     base = f"{4 * args.samples}_spp_x{rep['epochs']}"
     film.save_to(WRITE, args.out, base)
     if args.denoise:
-        film.save_to([K.Color], args.out, base, denoise=R.Denoise())
+        film.save_to([K.Color], args.out, base, denoise=R.VarianceDenoise() if args.denoise == "variance" else R.Denoise())
     image.save(os.path.join(args.out, f"{base}_sample_count.png"), film.sample_count_image()[:, :, None])
     if args.checkpoint:
         film.save_checkpoint(args.checkpoint)

@@ -373,6 +373,50 @@ int rayn_hip_progressive_tile_report(rayn_ctx* ctx, const rayn_frame_params* p, 
                                      uint32_t* out_epochs, uint32_t* out_retired, uint32_t* out_outliers, float* out_max_e,
                                      void* hip_stream);
 
+/* ---- variance-guided denoiser of a progressive render's Color channel (an EXTENSION: rayn has neither a denoiser nor a progressive
+ * render) -- The spatial half of SVGF (Schied et al., HPG 2017): the a-trous filter above with its colour term replaced by a luminance
+ * edge-stop scaled by the local standard deviation the progressive state measured, and the variance filtered along with the colour.
+ * Film layout and pixel order as rayn_hip_denoise_device.  Inputs: the MEAN film's Color c, Alpha a, WorldNormal nrm (what
+ * rayn_hip_progressive_accumulate_device writes to d_out_*) and the state of that render with its geometry p (width, height, tile_w, tile_h).
+ * Initial variance.  Pixel p lies in tile k of the reference's grid (x-major; resolutions the grid under-covers have pixels in no tile).
+ * With n = that tile's epochs and m2 the state's value, v_p = m2 / (float)((uint64)n * (n - 1)): the variance of the mean, the expression
+ * the accumulate takes the square root of.  p is GUIDED when it lies in a tile, n >= 2, v_p is finite and >= 0, and c_p has three
+ * finite components.  A pixel that is not guided passes through all passes unchanged and is skipped as a tap (it contributes to no
+ * neighbour).  v is the variance of the luminance of Color + Background (that is what the state holds) while the filter acts on Color
+ * alone; the two differ only where depth-0 rays miss, i.e. at silhouettes, where the Alpha term guards.
+ * Pass i = 0 .. L-1 (L in 1..8), step s = 2^i, on the previous pass's (c, v); kn = 1 / sigma_normal^2, ka = 1 / sigma_alpha^2; for every
+ * guided p:
+ *   l_x = (0.2126f * c_x.r + 0.7152f * c_x.g) + 0.0722f * c_x.b
+ *   g_p = (sum k_j * v_j) / (sum k_j)   3x3 at UNIT spacing around p (not dilated), k = 1/4 centre, 1/8 edges, 1/16 corners, the centre
+ *                                       first, then raster order; taps outside the image or not guided are left out of both sums
+ *   inv = 1.0f / (sigma_luminance * sqrtf(g_p) + 1e-8f)
+ *   W = 9/64, S = W * c_p, V = (W * W) * v_p
+ *   the 24 other taps of the 5x5 stencil in raster order, q = p + (kx, ky) * s, skipped outside the image or when q is not guided:
+ *     e = (fabsf(l_p - l_q) * inv + d_n * kn) + d_a * ka   (d_n, d_a: squared distances of normal and alpha as in
+ *                                                          rayn_hip_denoise_device; a term whose sigma is 0 is left out)
+ *     w = (h[ky+2] * h[kx+2]) * expf(-e), h and expf as in rayn_hip_denoise_device; a NaN w skips the tap
+ *     W += w, S += w * c_q, V += (w * w) * v_q
+ *   c'_p = S / W, v'_p = V / (W * W)
+ *   p stays guided when c'_p has three finite components and v'_p is finite; else (an overflow) it keeps c'_p and is not guided from
+ *   the next pass on - the same predicate as at the start, so that "not guided" stays one value of the record (v = NaN).
+ * The last pass writes the planar 3-float colour and, when d_out_variance is given, v' (1 float per pixel; a pixel that is not guided
+ * gets a quiet NaN there: no estimate).  All f32, no contraction, IEEE division and square root.
+ * Bytes of device scratch the entry needs for a width x height film: 48 per pixel (two (colour, variance) record planes and one
+ * (normal, alpha) record plane); 0 for a size it rejects.  Host only; needs no GPU. */
+size_t rayn_denoise_variance_scratch_bytes(uint32_t width, uint32_t height);
+/* Enqueue the filter on 'hip_stream' (NULL = the ctx's own stream; not waited for), on the ctx's GPU (devices[0] of a multi-device
+ * ctx).  DEVICE pointers: d_color / d_normal 3 floats per pixel, d_alpha 1, d_out_color 3, d_out_variance 1 (may be NULL); d_state 16-byte
+ * aligned, at least rayn_progressive_state_bytes; d_scratch 16-byte aligned, at least rayn_denoise_variance_scratch_bytes.  A sigma of 0
+ * switches its term off (a guide whose sigma is 0 may be NULL); any other sigma must be finite and in [2^-30, 2^30].
+ * RAYN_ERR_INVALID_ARG with a last error text for: what the progressive entries reject in p and d_state (zero-sized film or tile,
+ * width * height >= 2^31, a tile size that leaves no tiles, a NULL, too small or misaligned state), iterations outside 1..8, a bad sigma,
+ * a NULL colour, output or scratch, a NULL guide whose sigma is not 0, too little or misaligned scratch, d_out_color == d_color, and a
+ * d_out_variance that is d_color, d_alpha, d_normal, d_state or d_out_color.  The inputs and the state are not modified. */
+int rayn_hip_denoise_variance_device(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t iterations, float sigma_luminance,
+                                     float sigma_normal, float sigma_alpha, const float* d_color, const float* d_alpha,
+                                     const float* d_normal, const void* d_state, size_t state_bytes, float* d_out_color,
+                                     float* d_out_variance, void* d_scratch, size_t scratch_bytes, void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */

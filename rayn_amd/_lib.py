@@ -39,6 +39,7 @@ EXPORTS = [
     "rayn_save_to_bpp", "rayn_hip_save_to_pixels_device", "rayn_denoise_scratch_bytes", "rayn_hip_denoise_device",
     "rayn_progressive_seed", "rayn_progressive_state_bytes", "rayn_hip_progressive_reset_device", "rayn_hip_progressive_accumulate_device",
     "rayn_hip_progressive_fetch_active", "rayn_hip_progressive_tile_report",
+    "rayn_denoise_variance_scratch_bytes", "rayn_hip_denoise_variance_device",
 ]
 
 
@@ -101,6 +102,10 @@ def lib():
         L.rayn_hip_progressive_fetch_active.argtypes = [vp, C.POINTER(_abi.FrameParams), vp, C.c_size_t, up, C.c_uint32,
                                                         C.POINTER(_abi.ProgressiveTotals), vp]
         L.rayn_hip_progressive_tile_report.argtypes = [vp, C.POINTER(_abi.FrameParams), vp, C.c_size_t, up, up, up, fp, vp]
+        L.rayn_denoise_variance_scratch_bytes.restype = C.c_size_t
+        L.rayn_denoise_variance_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        L.rayn_hip_denoise_variance_device.argtypes = ([vp, C.POINTER(_abi.FrameParams), C.c_uint32, C.c_float, C.c_float, C.c_float] + [vp] * 4
+                                                       + [C.c_size_t, vp, vp, vp, C.c_size_t, vp])
         L.rayn_sets_1d.restype = C.c_uint32
         L.rayn_sets_1d.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_sets_2d.restype = C.c_uint32

@@ -21,6 +21,7 @@
 #include "tiles.h"
 #include "save_to.h"
 #include "denoise.h"
+#include "denoise_variance.h"
 #include "progressive.h"
 
 using namespace rayn;
@@ -974,7 +975,7 @@ int rayn_hip_unpack_share_device(rayn_ctx* ctx, const rayn_frame_params* p, cons
     return RAYN_OK; // enqueued on the stream, not waited for
 }
 
-// What the post-process entries (save_to_pixels, denoise, progressive_*) share around their own argument checks.  post_enter: 'why' is
+// What the post-process entries (save_to_pixels, denoise, denoise_variance, progressive_*) share around their own argument checks.  post_enter: 'why' is
 // the entry's verdict on its arguments (nullptr = valid); on RAYN_OK the context's device is current - a multi-device ctx is entry 0: its
 // device is devices[0], where the film lives - and *s is the stream to enqueue on.
 static int post_enter(rayn_ctx* ctx, const char* why, void* hip_stream, hipStream_t* s) {
@@ -1014,6 +1015,18 @@ int rayn_hip_denoise_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint
     if (int rc = post_enter(ctx, denoise_check_args(width, height, iterations, sigma_color, sigma_normal, sigma_alpha, d_color, d_alpha, d_normal, d_out_color,
                                                     d_scratch, scratch_bytes), hip_stream, &s)) return rc;
     launch_denoise(s, width, height, iterations, sigma_color, sigma_normal, sigma_alpha, d_color, d_alpha, d_normal, d_out_color, d_scratch);
+    return post_enqueued(ctx);
+}
+
+int rayn_hip_denoise_variance_device(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t iterations, float sigma_luminance, float sigma_normal,
+                                     float sigma_alpha, const float* d_color, const float* d_alpha, const float* d_normal, const void* d_state,
+                                     size_t state_bytes, float* d_out_color, float* d_out_variance, void* d_scratch, size_t scratch_bytes,
+                                     void* hip_stream) {
+    hipStream_t s;
+    if (int rc = post_enter(ctx, denoise_variance_check_args(p, iterations, sigma_luminance, sigma_normal, sigma_alpha, d_color, d_alpha, d_normal, d_state,
+                                                             state_bytes, d_out_color, d_out_variance, d_scratch, scratch_bytes), hip_stream, &s)) return rc;
+    launch_denoise_variance(s, *p, iterations, sigma_luminance, sigma_normal, sigma_alpha, d_color, d_alpha, d_normal, d_state, d_out_color, d_out_variance,
+                            d_scratch);
     return post_enqueued(ctx);
 }
 

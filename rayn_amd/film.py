@@ -61,9 +61,52 @@ class Denoise:
                                    sigma_alpha=self.sigma_alpha if have_mask & 2 else 0.0)
 
 
+@dataclasses.dataclass(frozen=True)
+class VarianceDenoise:
+    """Parameters of the variance-guided a-trous denoiser of a progressive render's Color channel (rayn_hip_denoise_variance_device, an
+    extension: rayn has neither a denoiser nor a progressive render; the spatial half of SVGF, Schied et al., HPG 2017).  `iterations`
+    a-trous passes (1..8, steps 1, 2, 4, ...).  The luminance edge-stop of a tap is |l_p - l_q| / (sigma_luminance * sd_p), sd_p the
+    local standard deviation of the pixel's mean luminance as the progressive state measured it (3x3 pre-filtered), so a pixel the
+    render found noisy is smoothed widely and one it found converged is left alone; the variance is filtered along with the colour.
+    sigma_normal and sigma_alpha weigh the squared normal and alpha distances as Denoise's do.  A sigma of 0 switches its term off; any
+    other must be finite and in [2^-30, 2^30].
+
+    The defaults were chosen on the shipped scene (rayn_amd.setup at 160x96; the MSE of the saturated Color + Background against 1024
+    spp of a non-adaptive progressive render of 32 spp and of an adaptive one capped at 16 epochs) over a grid around SVGF's (5 passes,
+    sigma 4) and Denoise's (0.4, 0.3): one pass, luminance 2, normals 0.4, alpha 0.3 bring the MSE to 0.75x / 0.86x that of the mean
+    film where Denoise() raises it to 1.22x / 3.77x.  As for Denoise, the scene's fractal detail is pixel-sized at that size and every
+    further pass blurs it: SVGF's five passes at sigma 4 give 1.49x / 2.27x (DESIGN.md section 8 has the grid)."""
+    iterations: int = 1
+    sigma_luminance: float = 2.0
+    sigma_normal: float = 0.4
+    sigma_alpha: float = 0.3
+
+    def __post_init__(self):
+        if isinstance(self.iterations, bool) or not isinstance(self.iterations, (int, np.integer)) or not 1 <= self.iterations <= 8:
+            raise ValueError(f"VarianceDenoise.iterations must be an int in 1..8, got {self.iterations!r}")
+        for name in ("sigma_luminance", "sigma_normal", "sigma_alpha"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+                raise ValueError(f"VarianceDenoise.{name} must be a number, got {v!r}")
+            f = float(v)  # the C entry takes it as an f32: check that value too
+            if not (f == 0.0 or (2.0 ** -30 <= f <= 2.0 ** 30 and 2.0 ** -30 <= float(np.float32(f)) <= 2.0 ** 30)):
+                raise ValueError(f"VarianceDenoise.{name} must be 0 (off) or finite in [2^-30, 2^30], got {v!r}")
+
+    def without(self, have_mask):
+        """These parameters with the terms of the guides the film lacks (bit k of have_mask = ChannelKind k) switched off."""
+        return dataclasses.replace(self, sigma_normal=self.sigma_normal if have_mask & 8 else 0.0,
+                                   sigma_alpha=self.sigma_alpha if have_mask & 2 else 0.0)
+
+
 def denoise_scratch_bytes(width, height):
     """rayn_denoise_scratch_bytes: bytes of device scratch the denoiser needs for a width x height film (0 for a size it rejects)."""
     return int(lib().rayn_denoise_scratch_bytes(int(width), int(height)))
+
+
+def denoise_variance_scratch_bytes(width, height):
+    """rayn_denoise_variance_scratch_bytes: bytes of device scratch the variance-guided denoiser needs for a width x height film (0 for a
+    size it rejects)."""
+    return int(lib().rayn_denoise_variance_scratch_bytes(int(width), int(height)))
 
 
 def _fp(a):
@@ -305,6 +348,42 @@ class Context:
                                                   C.c_void_p(d_out_color.data_ptr()), C.c_void_p(d_scratch.data_ptr()),
                                                   d_scratch.numel() * d_scratch.element_size(), C.c_void_p(s)))
 
+    def denoise_variance(self, params, d_film, d_state, d_out_color, denoise, d_out_variance=None, d_scratch=None, stream=None):
+        """rayn_hip_denoise_variance_device: the variance-guided a-trous denoiser (VarianceDenoise `denoise`) of the mean film
+        d_film["color"] of a progressive render into the float32 CUDA tensor d_out_color (width * height * 3 floats), guided by
+        d_film["normal"] and d_film["alpha"] (a guide whose sigma is 0 may be absent) and by the render's state `d_state` with the film
+        geometry of `params` (as progressive_accumulate takes them).  d_out_variance: a float32 CUDA tensor of width * height floats for
+        the filtered variance, or None.  d_scratch: a CUDA tensor of at least denoise_variance_scratch_bytes(width, height) bytes,
+        allocated here when None.  Enqueued on the stream, not waited for."""
+        import torch
+        width, height = params.width, params.height
+        n = int(width) * int(height)
+        if not (d_out_color.dtype == torch.float32 and d_out_color.is_contiguous() and d_out_color.numel() >= 3 * n):
+            raise ValueError(f"d_out_color must be a contiguous float32 tensor of at least {3 * n} floats")
+        if d_out_variance is not None and not (d_out_variance.dtype == torch.float32 and d_out_variance.is_contiguous() and d_out_variance.numel() >= n):
+            raise ValueError(f"d_out_variance must be a contiguous float32 tensor of at least {n} floats")
+        ptrs = []
+        for key, floats in (("color", 3), ("alpha", 1), ("normal", 3)):
+            t = d_film.get(key)
+            if t is None:
+                ptrs.append(None)
+                continue
+            if not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= floats * n):
+                raise ValueError(f"d_film[{key!r}] must be a contiguous float32 tensor of at least {floats * n} floats")
+            ptrs.append(C.c_void_p(t.data_ptr()))
+        state_ptr, state_bytes = self._prog_state(params, d_state)
+        if d_scratch is None:
+            d_scratch = torch.empty(max(denoise_variance_scratch_bytes(width, height), 1), dtype=torch.uint8, device=d_out_color.device)
+        if not d_scratch.is_contiguous():
+            raise ValueError("d_scratch must be contiguous")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._chk(self._L.rayn_hip_denoise_variance_device(self.h, C.byref(params), int(denoise.iterations), float(denoise.sigma_luminance),
+                                                           float(denoise.sigma_normal), float(denoise.sigma_alpha), *ptrs, state_ptr, state_bytes,
+                                                           C.c_void_p(d_out_color.data_ptr()),
+                                                           None if d_out_variance is None else C.c_void_p(d_out_variance.data_ptr()),
+                                                           C.c_void_p(d_scratch.data_ptr()), d_scratch.numel() * d_scratch.element_size(),
+                                                           C.c_void_p(s)))
+
     @staticmethod
     def _prog_state(params, d_state):
         import torch
@@ -458,10 +537,37 @@ class Film:
             raise ValueError("Attempted to denoise the Color channel but it didn't exist")
         return denoise.without(self.have_mask())
 
-    def denoised_color(self, params):
-        """The film's Color after the a-trous denoiser (Denoise `params`, rayn_hip_denoise_device) as a float32 device tensor of shape
-        (n, 3), pixels in the film's order.  A guide the film lacks is switched off; the film itself is not changed."""
+    def _variance_state(self):
+        """The progressive render behind the film's channels, for a VarianceDenoise; ValueError when there is none or it is too short."""
+        pr = self._progressive
+        if pr is None or self.channels is not pr["film"]:
+            raise ValueError("VarianceDenoise needs the state of a progressive render, and the film holds none (render_progressive has not "
+                             "run, or another render has replaced its film)")
+        if pr["epochs"] < 2:
+            raise ValueError(f"VarianceDenoise needs a progressive render of at least two epochs (the variance of one sample is unknown), "
+                             f"this one has run {pr['epochs']}")
+        return pr
+
+    def _denoise_variance(self, params, want_variance):
         import torch
+        params = self._denoise_params(params)
+        pr = self._variance_state()
+        w, h = self.res
+        with torch.cuda.device(self.device):
+            out = torch.empty(w * h, 3, dtype=torch.float32, device=self.device)
+            var = torch.empty(w * h, dtype=torch.float32, device=self.device) if want_variance else None
+            self.ctx.denoise_variance(pr["params"], self.channels, pr["state"], out, params, var)
+            return out, var
+
+    def denoised_color(self, params):
+        """The film's Color after a denoiser as a float32 device tensor of shape (n, 3), pixels in the film's order: the a-trous filter
+        (Denoise `params`, rayn_hip_denoise_device) or the variance-guided one (VarianceDenoise `params`,
+        rayn_hip_denoise_variance_device), which uses the state of the progressive render the film holds and raises ValueError when it
+        holds none or that render has run fewer than two epochs.  A guide the film lacks is switched off; the film itself is not
+        changed."""
+        import torch
+        if isinstance(params, VarianceDenoise):
+            return self._denoise_variance(params, False)[0]
         params = self._denoise_params(params)
         w, h = self.res
         with torch.cuda.device(self.device):
@@ -469,10 +575,17 @@ class Film:
             self.ctx.denoise(w, h, self.channels, out, params)
             return out
 
+    def denoised_variance(self, params):
+        """The variance of the mean luminance after the variance-guided denoiser (VarianceDenoise `params`) - what is left of the
+        progressive render's estimate once the filter has averaged it with squared weights - as float32 (h, w), rows bottom-up like
+        error_map; NaN where the filter had no estimate to go by (the pixel passed through).  ValueError as denoised_color."""
+        w, h = self.res
+        return self._denoise_variance(params, True)[1].cpu().numpy().reshape(h, w)
+
     def pixels(self, kind, transparent_background=False, denoise=None):
         """The 8-bit image Film::save_to writes for channel `kind` (rows top-down; (h, w, 4 / 3 / 1) uint8), computed on the device
         (rayn_hip_save_to_pixels_device); only the 8-bit image is copied back.  Channels the film lacks are not read.  With `denoise`
-        (a Denoise), the Color image is made from denoised_color(denoise); the other channels are unchanged."""
+        (a Denoise or a VarianceDenoise), the Color image is made from denoised_color(denoise); the other channels are unchanged."""
         import torch
         ((kind, bpp, _),) = self._save_jobs([kind], transparent_background)
         w, h = self.res
@@ -487,7 +600,7 @@ class Film:
     def save_to(self, write_channels, output_folder, base_name, transparent_background=False, denoise=None):
         """Film::save_to (src/film.rs:205-378) - the post-process after the hot path, arm by arm (on the device: pixels); the
         reference's Err(String) cases raise ValueError with the same text.  The PNGs are those of rayn_amd.image (host reference).
-        With `denoise` (a Denoise, an extension), the Color image is made from the denoised Color and written as
+        With `denoise` (a Denoise or a VarianceDenoise, extensions), the Color image is made from the denoised Color and written as
         {base_name}_color_denoised.png instead of {base_name}_color.png; the other channels are unchanged."""
         os.makedirs(output_folder, exist_ok=True)
         for kind in write_channels:
@@ -501,7 +614,7 @@ class Film:
         """Render frame `frame` progressively (an extension; include/rayn_hip.h has the definition): a series of epochs, each an ordinary
         render of the frame (render_frame_into's arguments) under the sample tables of progressive_seed(frame, epoch), accumulated on the
         device.  After every epoch film.channels holds the mean film of all epochs so far, so pixels / save_to / denoise= work on it
-        unchanged.  With progressive.adaptive, tiles whose error estimate has met the target retire and later epochs render only the
+        unchanged; denoise=VarianceDenoise() also uses what the render measured (the per-pixel variance in its state).  With progressive.adaptive, tiles whose error estimate has met the target retire and later epochs render only the
         tiles still active (Context.set_tile_subset); the render ends when none is left or after progressive.max_epochs.
 
         The world is uploaded once; scramble and filter tables are built once; epoch e + 1's R_d tables are built on a host thread while
@@ -545,7 +658,8 @@ class Film:
                     for k, v in _prog.mean_film(restored, w, h, tile_size).items():
                         d_mean[k].copy_(torch.from_numpy(v).reshape(d_mean[k].shape))
                 self.channels = d_mean
-                self._progressive = {"state": d_state, "params": p0, "key": key, "epochs": first, "noise_floor": progressive.noise_floor}
+                self._progressive = {"state": d_state, "params": p0, "key": key, "epochs": first, "noise_floor": progressive.noise_floor,
+                                     "film": d_mean}
                 active, totals = self.ctx.progressive_fetch_active(p0, d_state, stream.cuda_stream)
                 report.update(active_tiles=active, totals=totals)
                 if first < progressive.max_epochs and len(active):
@@ -630,9 +744,12 @@ class Film:
 
         With `denoise` (a Denoise), every frame's Color image is made from the denoised Color and written as _color_denoised.png, as
         save_to(..., denoise=denoise) does: the denoiser's kernels go on the render stream ahead of that frame's post-process kernels,
-        and its scratch and denoised plane are allocated once."""
+        and its scratch and denoised plane are allocated once.  A VarianceDenoise raises ValueError: a sequence's frames are plain
+        renders and carry no variance."""
         import concurrent.futures as cf
         import torch
+        if isinstance(denoise, VarianceDenoise):
+            raise ValueError("render_sequence renders plain frames: VarianceDenoise needs the state of a progressive render")
         frames = [int(f) for f in frames]
         jobs = self._save_jobs(write_channels, transparent_background)
         if denoise is not None:
