@@ -27,6 +27,8 @@
 namespace RAYN_KNS {
 
 RD uint32_t lane_id() { return threadIdx.x & 63u; }
+// this lane's bit of a wave-uniform 64-bit mask as a predicate: the mask itself becomes the exec mask / the select's condition, no vector instruction
+RD bool lane_of(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
 // number of set bits of a 64-bit wave mask below this lane
 RD uint32_t mbcnt(uint64_t mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -243,26 +245,24 @@ __global__ void __launch_bounds__(256) k_extend1(const DScene* __restrict__ scp,
     uint32_t cur = 0, end = 0;
     bool exhausted = false, endgame = false;
     // current ray
-    bool c_has = false, first = false, nan = false;
-    uint32_t c_P = 0, c_ent = 0, c_ids = 0, m = 0;
+    uint64_t cm = 0, nm = 0, nanm = 0; // wave masks: the lanes that hold a current / a spare ray; the current ray's first distance was NaN
+    uint32_t c_P = 0, c_ent = 0, c_ids = 0, e = 0; // e: evaluations of the current ray so far (marches m = e - 1)
     EvalCtr evals;
     f3 o = f3{0, 0, 0}, d = f3{0, 0, 0};
-    f3 pt = f3{0, 0, 0}; // the current ray's next march point (unused under -DRAYN_MARCH_POINT_SELECT)
+    f3 pt = f3{0, 0, 0}; // the current ray's next march point
     float c_pre = 0.0f, c_post = 0.0f, t = 0.0f;
     float c_scale = h.scale, n_scale = h.scale; // MandelBox scale at the packet time (extension; h.scale itself in the reference's case)
     // prefetched next ray
-    bool n_has = false;
     uint32_t n_P = 0, n_ent = 0, n_ids = 0;
     f3 n_o = f3{0, 0, 0}, n_d = f3{0, 0, 0};
     float n_pre = 0.0f, n_post = 0.0f;
     for (;;) {
-        const uint64_t lack = __ballot(!n_has);
-        const uint64_t idle = __ballot(!c_has && !n_has);
+        const uint64_t lack = ~nm, idle = ~(cm | nm);
         // endgame: once the queue is nearly drained no more spare rays are hoarded (a spare held by a lane that is still
         // inside a long march would wait while other lanes idle) - idle lanes then fetch one ray at a time
         if (!exhausted && (endgame ? idle != 0 : ((uint32_t)__popcll(lack) >= PREFETCH_MIN || (uint32_t)__popcll(idle) >= 4u))) {
             for (;;) {
-                const uint64_t need = endgame ? __ballot(!n_has && !c_has) : __ballot(!n_has);
+                const uint64_t need = endgame ? ~(nm | cm) : ~nm;
                 if (need == 0) break;
                 if (cur == end) {
                     uint32_t base = 0;
@@ -274,7 +274,8 @@ __global__ void __launch_bounds__(256) k_extend1(const DScene* __restrict__ scp,
                     endgame = n_entries - base < ENDGAME_ENTRIES;
                 }
                 const uint32_t rank = mbcnt(need), avail = end - cur;
-                if ((need >> lane) & 1ull) if (rank < avail) {
+                const uint64_t take = need & __builtin_amdgcn_ballot_w64(rank < avail);
+                if (lane_of(take)) {
                     n_ent = cur + rank;
                     n_P = q[n_ent];
                     if (n_P == INVALID) ent_obj[n_ent] = (uint8_t)OBJ_NONE;
@@ -300,54 +301,56 @@ __global__ void __launch_bounds__(256) k_extend1(const DScene* __restrict__ scp,
                         n_ids = id | (idp << 8);
                         n_o = n_o - sphere_center(h, t0); // march in the SDF's frame (extension; zero origin in the reference)
                         n_scale = sdf_scale(h, t0);
-                        n_has = true;
                     }
                 }
+                nm |= take & __builtin_amdgcn_ballot_w64(n_P != INVALID); // (a taking lane's n_P is the entry it just read)
                 cur += min((uint32_t)__popcll(need), avail);
             }
         }
-        if (!c_has && n_has) { // start the spare ray
-            c_has = true; n_has = false;
-            o = n_o; d = n_d; c_pre = n_pre; c_post = n_post; c_ids = n_ids; c_P = n_P; c_ent = n_ent; c_scale = n_scale;
-            first = true;
-#ifndef RAYN_MARCH_POINT_SELECT
+        // start the spare ray; a ray's FIRST evaluation happens in the trip that promotes it, so the promotion mask is the 'first' flag (see k_shadow1)
+        const uint64_t fm = nm & ~cm;
+        if (lane_of(fm)) {
+            o = n_o; d = n_d; c_pre = n_pre; c_post = n_post; c_ids = n_ids; c_P = n_P; c_ent = n_ent; e = 0;
+            c_scale = n_scale;
             pt = n_o; // the first evaluation is at the origin
-#endif
         }
-        if (__ballot(c_has) == 0) {
+        cm |= fm; nm &= ~fm;
+        if (cm == 0) {
             if (exhausted) break;
             continue;
         }
-        if (c_has) { // TracedSDF::hit, src/sdf.rs:59-83, one evaluation per loop trip
-#ifdef RAYN_MARCH_POINT_SELECT
-            const f3 p = first ? o : muladd3(d, t, o);
-#else
-            const f3 p = pt; // r6: the march point is STATE - set at promotion (the origin) and at the end of a trip that goes on - instead of a per-trip select between the origin and o + d t
-#endif
-            const float dist = sdf_dist<COUNT, SDFK>(h, p, evals, c_scale);
-            bool done;
-            if (first) { t = dist; nan = dist != dist; first = false; m = 0; done = max_marches == 0; }
-            else {
-                const bool hit = __builtin_fabsf(dist) < fmaxs(c0, c1 * thr_at(th, t));
-                const bool gt = t > c_pre;
-                done = hit || nan || gt;
-                if (!done) { t = t + dist; m++; done = m == max_marches; }
-            }
-            if (done) {
-                float closest = c_pre;
-                uint32_t id = c_ids & 0xFFu;
-                if (t < closest) { closest = t; id = ks; }
-                const uint32_t idp = c_ids >> 8;
-                if (idp != OBJ_NONE && c_post < closest) { closest = c_post; id = idp; }
-                pool.geo1[c_P].z = closest;
-                ((uint8_t*)&pool.geo1[c_P].w)[0] = (uint8_t)id; // low byte of the bits word = hit object
-                ent_obj[c_ent] = (uint8_t)id;
-                c_has = false;
-            }
-#ifndef RAYN_MARCH_POINT_SELECT
-            else pt = muladd3(d, t, o); // the next trip's point (Ray::point_at: the same operations the select form ran at the top of that trip)
-#endif
+        // TracedSDF::hit, src/sdf.rs:59-83, one evaluation per loop trip, in every lane of the product kernels (see k_shadow1)
+        float dist = 0.0f;
+        if (!COUNT) dist = sdf_dist<COUNT, SDFK>(h, pt, evals, c_scale);
+        else if (lane_of(cm)) dist = sdf_dist<COUNT, SDFK>(h, pt, evals, c_scale);
+        // The hit test as straight-line code in which 'first' is data (the mask fm).  Equivalence with the two-region form
+        //     first:  t = dist; nan = isnan(dist); m = 0; done = max_marches == 0
+        //     later:  done = hit || nan || t > c_pre; if (!done) { t += dist; m++; done = m == max_marches }
+        //  * stop = (hit | nan | t > c_pre) & ~first: the compares run on a first lane's stale t and are masked; nan (a mask) is rewritten by the first lanes
+        //    only, AFTER stop has read the old value, and kept by the others - the flag's life in the two-region form.
+        //  * t' = stop ? t : (first ? dist : t + dist): selects, so a stopping lane hands the epilogue the t it stopped at and dist == -0 stays -0.
+        //  * e = evaluations so far including this one (reset at promotion, incremented every trip) = m + 1 for the incremented m of a lane that goes on, so
+        //    m == max_marches  <=>  e == max_marches + 1 (mod 2^32); in a first trip e == 1, and 1 == max_marches + 1 is the first region's max_marches == 0.
+        //    A stopping lane is done whatever e says.
+        const uint64_t stop = (__builtin_amdgcn_ballot_w64(__builtin_fabsf(dist) < fmaxs(c0, c1 * thr_at(th, t))) | __builtin_amdgcn_ballot_w64(t > c_pre) | nanm) & ~fm;
+        nanm = (nanm & ~fm) | (__builtin_amdgcn_ballot_w64(dist != dist) & fm);
+        const float ts = t + dist;
+        const float tg = lane_of(fm) ? dist : ts;
+        t = lane_of(stop) ? t : tg;
+        e++;
+        const uint64_t fin = (stop | __builtin_amdgcn_ballot_w64(e == max_marches + 1u)) & cm;
+        if (lane_of(fin)) {
+            float closest = c_pre;
+            uint32_t id = c_ids & 0xFFu;
+            if (t < closest) { closest = t; id = ks; }
+            const uint32_t idp = c_ids >> 8;
+            if (idp != OBJ_NONE && c_post < closest) { closest = c_post; id = idp; }
+            pool.geo1[c_P].z = closest;
+            ((uint8_t*)&pool.geo1[c_P].w)[0] = (uint8_t)id; // low byte of the bits word = hit object
+            ent_obj[c_ent] = (uint8_t)id;
         }
+        cm &= ~fin;
+        pt = muladd3(d, t, o); // the next trip's point (Ray::point_at); dead in a lane whose ray just ended (promotion rewrites it)
     }
     if (COUNT && evals.n) { atomicAdd(evals_out, (unsigned long long)evals.n); atomicAdd(evals_out + 4, (unsigned long long)evals.it); }
 }
@@ -1075,21 +1078,20 @@ __global__ void __launch_bounds__(256) k_shadow1(const DScene* __restrict__ scp,
     const float c0 = 0.0001f * sc.detail_scale, c1 = 0.00001f * sc.detail_scale;
     uint32_t cur = 0, end = 0;
     bool exhausted = false, endgame = false;
-    bool c_has = false, first = false, nan = false, n_has = false;
-    uint32_t ref = 0, n_ref = 0, m = 0;
+    uint64_t cm = 0, nm = 0; // wave masks: the lanes that hold a current / a spare segment
+    uint32_t ref = 0, n_ref = 0, e = 0; // e: evaluations of the current segment so far (marches m = e - 1)
     EvalCtr evals;
     f3 start = f3{0, 0, 0}, dir = f3{0, 0, 0}, n_start = f3{0, 0, 0}, n_dir = f3{0, 0, 0};
-    f3 pt = f3{0, 0, 0}; // the current segment's next march point (unused under -DRAYN_MARCH_POINT_SELECT)
+    f3 pt = f3{0, 0, 0}; // the current segment's next march point
     float max_dist = 0.0f, n_max = 0.0f, t = 0.0f;
     float c_scale = h.scale, n_scale = h.scale; // MandelBox scale at the packet time (extension)
     for (;;) {
-        const uint64_t lack = __ballot(!n_has);
-        const uint64_t idle = __ballot(!c_has && !n_has);
+        const uint64_t lack = ~nm, idle = ~(cm | nm);
         // endgame: once the queue is nearly drained no more spare rays are hoarded (a spare held by a lane that is still
         // inside a long march would wait while other lanes idle) - idle lanes then fetch one ray at a time
         if (!exhausted && (endgame ? idle != 0 : ((uint32_t)__popcll(lack) >= PREFETCH_MIN || (uint32_t)__popcll(idle) >= 4u))) {
             for (;;) {
-                const uint64_t need = endgame ? __ballot(!n_has && !c_has) : __ballot(!n_has);
+                const uint64_t need = endgame ? ~(nm | cm) : ~nm;
                 if (need == 0) break;
                 if (cur == end) {
                     uint32_t base = 0;
@@ -1101,58 +1103,68 @@ __global__ void __launch_bounds__(256) k_shadow1(const DScene* __restrict__ scp,
                     endgame = n_jobs - base < ENDGAME_ENTRIES;
                 }
                 const uint32_t rank = mbcnt(need), avail = end - cur;
-                if (((need >> lane) & 1ull) && rank < avail) {
+                const uint64_t take = need & __builtin_amdgcn_ballot_w64(rank < avail);
+                if (lane_of(take)) {
                     n_ref = nee.job_ref[cur + rank];
                     const float2 j0 = nee.job_geo[3 * (size_t)n_ref], j1 = nee.job_geo[3 * (size_t)n_ref + 1], j2 = nee.job_geo[3 * (size_t)n_ref + 2];
                     const float jt0 = sc.anim_spheres ? nee.t0[n_ref % (uint32_t)nee.cap] : 0.0f;
                     const f3 origin = sphere_center(h, jt0); // TracedSDF origin at the packet time (extension; zero in the reference)
                     n_scale = sdf_scale(h, jt0);
                     n_start = f3{j0.x, j0.y, j1.x} - origin;
-                    const f3 e = f3{j1.y, j2.x, j2.y} - origin;
-                    n_dir = e - n_start;
+                    const f3 e1 = f3{j1.y, j2.x, j2.y} - origin;
+                    n_dir = e1 - n_start;
                     n_max = mag(n_dir);
                     n_dir = div_by_mag(n_dir, n_max);
-                    n_has = true;
                 }
+                nm |= take;
                 cur += min((uint32_t)__popcll(need), avail);
             }
         }
-        if (!c_has && n_has) {
-            c_has = true; n_has = false;
-            start = n_start; dir = n_dir; max_dist = n_max; ref = n_ref; c_scale = n_scale;
-            first = true;
-#ifndef RAYN_MARCH_POINT_SELECT
+        // promotion of the spare segment; a segment's FIRST evaluation happens in the trip that promotes it (every lane with a
+        // current segment evaluates in every trip), so the promotion mask is the 'first' flag and needs no state of its own
+        const uint64_t fm = nm & ~cm;
+        if (lane_of(fm)) {
+            start = n_start; dir = n_dir; max_dist = n_max; ref = n_ref; e = 0;
+            c_scale = n_scale;
             pt = n_start; // the first evaluation is at the segment start
-#endif
         }
-        if (__ballot(c_has) == 0) {
+        cm |= fm; nm &= ~fm;
+        if (cm == 0) {
             if (exhausted) break;
             continue;
         }
-        if (c_has) { // TracedSDF::occluded, src/sdf.rs:25-57
-#ifdef RAYN_MARCH_POINT_SELECT
-            const f3 p = first ? start : muladd3(dir, t, start);
-#else
-            const f3 p = pt; // (see k_extend1)
-#endif
-            const float dist = sdf_dist<COUNT, SDFK>(h, p, evals, c_scale);
-            int res = -1; // -1 keep marching, 0 occluded, 1 visible
-            if (first) {
-                t = dist; nan = dist != dist; first = false; m = 0;
-                if (max_vis == 0) res = ((dist < 0.0001f) && !((dist > max_dist) || nan)) ? 0 : 1;
-                else if ((t > max_dist) || nan) res = 1;
-            } else {
-                if (__builtin_fabsf(dist) < fmaxs(c0, c1 * t)) res = 0;
-                else {
-                    t = t + dist; m++;
-                    if (m == max_vis || (t > max_dist) || nan) res = 1;
-                }
-            }
-            if (res >= 0) { if (res == 1) nee.vis[ref] = 1; c_has = false; } // only VISIBLE results are written (see Nee::vis)
-#ifndef RAYN_MARCH_POINT_SELECT
-            else pt = muladd3(dir, t, start);
-#endif
+        // TracedSDF::occluded, src/sdf.rs:25-57.  The product kernels evaluate in EVERY lane: a lane without a segment marches the stale point of its
+        // last one and its results are masked out below (cm) - no exec-mask bookkeeping around the evaluation.  The counting variants mask it.
+        float dist = 0.0f;
+        if (!COUNT) dist = sdf_dist<COUNT, SDFK>(h, pt, evals, c_scale);
+        else if (lane_of(cm)) dist = sdf_dist<COUNT, SDFK>(h, pt, evals, c_scale);
+        // The march test as straight-line code in which 'first' is data (the mask fm).  Equivalence with the two-region form
+        //     first:  t = dist; nan = isnan(dist); m = 0; visible if (t > max_dist || nan)            [max_vis == 0: its own test, below]
+        //     later:  occluded if (|dist| < max(c0, c1 t)); else { t += dist; m++; visible if (m == max_vis || t > max_dist || nan) }
+        //  * 'nan' is only ever true in a segment's first trip: a NaN first distance ends the segment (visible) in that very trip, so in every later
+        //    trip nan == false and its term vanishes.  What remains of it is (isnan(dist) & first).  A NaN LATER distance is not occluded
+        //    (|NaN| < x is false), makes t NaN, and NaN > max_dist is false: the segment marches on until m == max_vis - in both forms.
+        //  * occluded = (|dist| < max(c0, c1 t)) & ~first: the compare runs on the stale t of a first lane and is masked, which is what "a threshold that
+        //    can never fire" amounts to without a select.  max(c0, c1 t) keeps its compare-and-select form (a NaN t selects the NaN, as before).
+        //  * t' = first ? dist : t + dist is a SELECT: 0 + dist would turn dist == -0 into +0.  An occluded lane's t' is never read again.
+        //  * m == max_vis after the increment  <=>  e == max_vis + 1 (mod 2^32) for e = m + 1 = evaluations so far including this one; e is reset at promotion
+        //    and incremented every trip.  In a first trip e == 1 != max_vis + 1 because max_vis != 0 here, so the term needs no mask.
+        //  * visible = ~occluded & (e == max_vis + 1 | t' > max_dist | (isnan(dist) & first)): for a first lane t' == dist, which is the first region's test.
+        uint64_t occ, vis;
+        if (max_vis == 0) { // every evaluation is a first one
+            occ = __builtin_amdgcn_ballot_w64(dist < 0.0001f) & ~__builtin_amdgcn_ballot_w64(dist > max_dist); // (dist < 0.0001 && !(dist > max_dist || nan)): a NaN fails the first compare
+            vis = ~occ;
+        } else {
+            occ = __builtin_amdgcn_ballot_w64(__builtin_fabsf(dist) < fmaxs(c0, c1 * t)) & ~fm;
+            const float ts = t + dist;
+            t = lane_of(fm) ? dist : ts;
+            e++;
+            vis = (__builtin_amdgcn_ballot_w64(e == max_vis + 1u) | __builtin_amdgcn_ballot_w64(t > max_dist) | (__builtin_amdgcn_ballot_w64(dist != dist) & fm)) & ~occ;
         }
+        vis &= cm;
+        if (lane_of(vis)) nee.vis[ref] = 1; // only VISIBLE results are written (see Nee::vis)
+        cm &= ~(occ | vis);
+        pt = muladd3(dir, t, start); // the next trip's point; dead in a lane whose segment just ended (promotion rewrites it)
     }
     if (COUNT && evals.n) { atomicAdd(evals_out, (unsigned long long)evals.n); atomicAdd(evals_out + 4, (unsigned long long)evals.it); }
 }
