@@ -2,12 +2,14 @@
 (rayn_amd.setup, 1280x720, SAMPLES = 2 (8 spp), 3 bounces, the BlackmanHarris filter, 16x16 tiles) rendered frame by frame and
 written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints per-frame render times and frames/s.
 
-    python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise]
+    python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise] [--temporal]
 
 --compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
 the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
 both loops wrote the same bytes.  --denoise runs the a-trous denoiser (rayn_amd.Denoise() defaults, an extension) on every frame's
-Color before its post-process and writes _color_denoised.png instead of _color.png."""
+Color before its post-process and writes _color_denoised.png instead of _color.png.  --temporal accumulates every frame's Color over the
+frames before it (rayn_amd.Temporal() defaults, an extension: a primary-hit G-buffer pass and a reprojection per frame) under a camera whose
+origin drifts, and writes _color_temporal.png (_color_temporal_denoised.png with --denoise)."""
 import argparse
 import os
 import sys
@@ -22,6 +24,7 @@ if ROOT not in sys.path:
 import rayn_amd as R  # noqa: E402
 from rayn_amd import image  # noqa: E402
 from rayn_amd import setup as S  # noqa: E402
+from rayn_amd.scene import Linear  # noqa: E402
 
 SAMPLES, MAX_INDIRECT_BOUNCES = 2, 3  # src/setup.rs:16-25
 FRAME_RATE, SHUTTER_SPEED = 24, 1.0 / 24.0  # src/main.rs:47-49
@@ -55,28 +58,33 @@ def main():
     ap.add_argument("--writers", type=int, default=None, help="PNG writer threads (at most 8; default 2 per written channel)")
     ap.add_argument("--compare-loop", action="store_true", help="also time the plain render_frame_into + host post-process loop")
     ap.add_argument("--denoise", action="store_true", help="denoise every frame's Color (rayn_amd.Denoise() defaults)")
+    ap.add_argument("--temporal", action="store_true", help="accumulate every frame's Color over the frames before it (rayn_amd.Temporal() defaults); the camera's origin drifts")
     args = ap.parse_args()
-    if args.denoise and args.compare_loop:
-        ap.error("--compare-loop compares with the host post-process, which has no denoiser: use one or the other")
+    if (args.denoise or args.temporal) and args.compare_loop:
+        ap.error("--compare-loop compares with the host post-process, which has neither a denoiser nor a temporal accumulation: use one or the other")
     denoise = R.Denoise() if args.denoise else None
+    temporal = R.Temporal() if args.temporal else None
     first, end = (int(x) for x in args.frames.split(":"))
     frames = list(range(first, end))
     base = f"{SAMPLES * 4}_spp"
     cam, world = S.setup((args.width, args.height))
+    if temporal is not None:  # something to reproject: the camera of BASELINE config 5 (rayn_amd.setup.setup_s3)
+        c = world.cameras.get(cam)
+        c.origin = Linear(c.origin, R.vec3(0.9, -0.3, 0.15))
     integ = R.PathTracingIntegrator(max_bounces=MAX_INDIRECT_BOUNCES, volume_marches=S.VOLUME_MARCHES_PER_SAMPLE)
     filt = R.BlackmanHarrisFilter(S.FILTER_RADIUS)
 
     film = R.Film(CHANNELS, (args.width, args.height))
     # warm-up: code objects, the context's first-frame arena and the writer path (not timed)
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames[:1], FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
-                         os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise)
+                         os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal)
     t0 = time.perf_counter()
     stats = film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
-                                 os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise)
+                                 os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal)
     seq_s = time.perf_counter() - t0
     for st in stats:
         print(f"frame {st['frame']:4d}: render {st['ms_total']:8.2f} ms")
-    print(f"render_sequence{' --denoise ' + str(denoise) if denoise else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s "
+    print(f"render_sequence{' --denoise ' + str(denoise) if denoise else ''}{' --temporal ' + str(temporal) if temporal else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s "
           f"(render alone: {sum(st['ms_total'] for st in stats) / len(frames):.2f} ms/frame)")
 
     if args.compare_loop:

@@ -417,6 +417,77 @@ int rayn_hip_denoise_variance_device(rayn_ctx* ctx, const rayn_frame_params* p, 
                                      const float* d_normal, const void* d_state, size_t state_bytes, float* d_out_color,
                                      float* d_out_variance, void* d_scratch, size_t scratch_bytes, void* hip_stream);
 
+/* ---- temporal accumulation for frame sequences (an EXTENSION: rayn renders every frame on its own) -- The temporal half of SVGF (Schied
+ * et al., HPG 2017): the previous frame's accumulated Color is reprojected onto the current frame through the world position of every
+ * pixel's primary hit and blended with the new frame, so that a sequence at few samples per frame approaches the noise of `samples x history`
+ * wherever the surface stays visible.  Two passes, both downstream of the film: the film's four channels stay what the integrator wrote.
+ *
+ * Primary-hit G-buffer.  For every pixel (x, y) of the film (bottom-up rows, pixel x + y * width) ONE ray: uv = (ndc_x * (x + 0.5f),
+ * ndc_y * (y + 0.5f)) - the ray-gen kernel's expression with a filter offset of 0 - lens sample (0.5, 0.5), ray time and camera closure
+ * time both p->time_start, through the same Camera::get_rays code as a render, under the ctx's mul_add policy.  (0.5, 0.5) is the point
+ * concentric_circle_map moves off its singular centre (src/math.rs:205): a thin lens's G-buffer ray starts 0.0001 * aperture beside the
+ * lens centre.  The rays go through the scene's PRODUCT extend kernel at depth 0 (HitableStore::add_hits; the kernel rayn_hip_probe_extend
+ * runs) as one identity queue.  Per pixel the pass writes a 16-byte record (Px, Py, Pz, t) - t the kernel's hit distance, P = o + t * d as
+ * a separate f32 multiply and add under either policy - and the u32 index of the hit object; a miss writes (0, 0, 0, +inf) and 0xFFFFFFFF.
+ * Closure-sequenced hitables are evaluated at p->time_start.
+ * Bytes of device scratch the pass needs for a width x height film: 53 per pixel of the film rounded up to a multiple of 64 pixels, + 384
+ * (0 for a size it rejects).  Host only; needs no GPU. */
+size_t rayn_gbuffer_scratch_bytes(uint32_t width, uint32_t height);
+/* Enqueue the pass on 'hip_stream' (NULL = the ctx's own stream; not waited for) for the uploaded world and p (its resolution, time_start,
+ * max_marches, sdf_detail_scale, world_radius), on the ctx's GPU (devices[0] of a multi-device ctx).  DEVICE pointers: d_out_records 16
+ * bytes per pixel and 16-byte aligned, d_out_object one u32 per pixel, d_scratch 16-byte aligned and at least rayn_gbuffer_scratch_bytes.
+ * Like a render it replaces the context's device scene.  RAYN_ERR_INVALID_ARG with a last error text for: NULL p, a zero-sized image or
+ * width * height >= 2^31, a NULL or misaligned buffer, too little scratch, buffers that overlap, and no uploaded world. */
+int rayn_hip_gbuffer_device(rayn_ctx* ctx, const rayn_frame_params* p, void* d_out_records, uint32_t* d_out_object, void* d_scratch,
+                            size_t scratch_bytes, void* hip_stream);
+
+/* Temporal accumulate.  A HISTORY of a width x height film is one block of 52 bytes per pixel: plane A (r, g, b, n) - the accumulated Color
+ * and the history length n as a float, n = 0: no history - plane B (Px, Py, Pz, t) - that frame's G-buffer record - the WorldNormal as
+ * (nx, ny, nz, 0), 16 bytes each, and the object index (u32), in that order, each in film pixel order.  The caller ping-pongs two of them. */
+typedef struct {
+    uint32_t max_history;  /* the history length stops growing here (the blend weight never falls below 1 / max_history); 1..65536 */
+    float depth_tolerance; /* a tap's recorded hit distance may differ from the reprojected one by this fraction of it; finite, >= 0 */
+    float normal_min;      /* a tap's normal must have at least this dot product with the pixel's; in [-1, 1], -1 switches the test off */
+} rayn_temporal_params;
+/* Bytes of one history (0 for a size the entry rejects).  Host only; needs no GPU. */
+size_t rayn_temporal_history_bytes(uint32_t width, uint32_t height);
+/* Inputs: the current frame's Color c and WorldNormal nrm (3 floats per pixel), its G-buffer (records (P, t), objects obj), the previous
+ * frame's history (NULL: none - the first frame) with that frame's camera and time_start, and p for the resolution and the current
+ * time_start.  Outputs: the accumulated Color (3 floats per pixel) and the new history.  Hitable motion comes from the uploaded world.
+ * All arithmetic f32, no contraction under either mul_add policy, IEEE '/' and sqrtf.  dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z;
+ * cross(a, b) = (a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); nz(a) = a * (1.0f / sqrtf(dot(a, a))); vector +, -
+ * and * scalar act per component, and "a - b * s" is a multiply, then a subtraction.  Per pixel:
+ *   1. Reset: out = c, n' = 1 - and n' = 0 when c has a non-finite component, so that it never becomes a tap - when obj = 0xFFFFFFFF (a
+ *      miss), c has a non-finite component, or there is no previous history.
+ *   2. Object motion: Pp = P - center_vel * (time_start_cur - time_start_prev) when hitable obj has animated != 0, else Pp = P.  scale_vel
+ *      morphing is not reprojected; the depth test catches it.
+ *   3. The previous camera at ts = its time_start: o = origin + origin_vel * ts when bit 0 of animated is set, else origin; at and up
+ *      likewise (bits 1, 2).
+ *        pinhole, thin lens (a pinhole at o):  w = nz(o - at), u = nz(cross(up, w)), v = cross(w, u);  q = Pp - o;  zc = -dot(q, w),
+ *          rejected unless zc > 0;  uvx = (dot(q, u) / (zc * half_w) + 1.0f) * 0.5f, uvy = (dot(q, v) / (zc * half_h) + 1.0f) * 0.5f;
+ *          te = sqrtf(dot(q, q))
+ *        orthographic:  w = nz(at - o), u = nz(cross(w, up)), v = cross(u, w);  ll = (o - u * half_w) - v * half_h;  q = Pp - ll;
+ *          uvx = dot(q, u) / full_w, uvy = dot(q, v) / full_h;  te = dot(q, w), rejected unless te > 0
+ *      (half_w .. full_h: the constants the camera's ::new derives, src/camera.rs:53-72,134-157,228-240.)
+ *      fx = uvx * (float)width - 0.5f, fy = uvy * (float)height - 0.5f, rejected unless both are finite.
+ *   4. x0f = floorf(fx), wx1 = fx - x0f, wx0 = 1.0f - wx1, and y likewise; x0, y0 = x0f, y0f as integers (clamped to [-2, 2^31] first,
+ *      which changes no result).  Taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) with w = wx0 * wy0, wx1 * wy0, wx0 * wy1,
+ *      wx1 * wy1.  A tap counts when it is inside the image, n_tap >= 1, obj_tap == obj, fabsf(t_tap - te) <= depth_tolerance * te and,
+ *      with normal_min > -1, dot(nrm, nrm_tap) >= normal_min (a NaN fails every one):  W += w, S += w * c_tap, N += w * n_tap.
+ *   5. W > 0:  h = S / W, nh = N / W, n' = fminf(nh + 1.0f, (float)max_history), a = 1.0f / n', out = h + a * (c - h) as separate
+ *      operations.  A rejected projection, W <= 0 and an out with a non-finite component reset the pixel as in 1.
+ *   New history: A' = (out, n'), B' = (P, t), (nrm, 0) and obj.
+ * Enqueued on 'hip_stream' (NULL = the ctx's own stream; not waited for), on the ctx's GPU (devices[0] of a multi-device ctx); DEVICE
+ * pointers, records and histories 16-byte aligned.  RAYN_ERR_INVALID_ARG with a last error text for: NULL p or tp, a zero-sized image or
+ * width * height >= 2^31, max_history outside 1..65536, a non-finite or negative depth_tolerance, normal_min outside [-1, 1], a NULL
+ * buffer (d_prev_history alone may be NULL; prev_camera may be NULL with it), an unknown camera kind, a history_bytes (the size of EACH
+ * history) below rayn_temporal_history_bytes, a misaligned record plane or history, an output that overlaps an input, the new history
+ * overlapping the previous one or d_out_color, and no uploaded world.  The inputs and the previous history are not modified. */
+int rayn_hip_temporal_accumulate_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp, const rayn_camera* prev_camera,
+                                        float prev_time_start, const float* d_color, const float* d_normal, const void* d_gbuffer_records,
+                                        const uint32_t* d_gbuffer_object, const void* d_prev_history, void* d_new_history, size_t history_bytes,
+                                        float* d_out_color, void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */

@@ -65,6 +65,10 @@ class ProgressiveTotals(C.Structure):  # rayn_progressive_totals
     _fields_ = [("active_tiles", C.c_uint32), ("max_e", C.c_float), ("outlier_pixels", C.c_uint64)]
 
 
+class TemporalParams(C.Structure):  # rayn_temporal_params
+    _fields_ = [("max_history", C.c_uint32), ("depth_tolerance", C.c_float), ("normal_min", C.c_float)]
+
+
 class Stats(C.Structure):
     _fields_ = [("paths", C.c_uint64), ("segments", C.c_uint64), ("shaded_slots", C.c_uint64),
                 ("tiles", C.c_uint64), ("batches", C.c_uint64), ("ms_total", C.c_double),

@@ -23,6 +23,7 @@
 #include "denoise.h"
 #include "denoise_variance.h"
 #include "progressive.h"
+#include "temporal.h"
 
 using namespace rayn;
 
@@ -66,6 +67,29 @@ bool short_div_is_exact(rayn_ctx* ctx, float mrs, float frs) {
 } // namespace
 
 namespace rayn { // shared with probes.hip (driver.h)
+
+// rayn_camera -> DCamera: the constants the cameras' ::new derive from resolution and field of view; false for an unknown kind
+bool build_camera(const rayn_camera& c, DCamera* out) {
+    memset(out, 0, sizeof *out);
+    DCamera& dc = *out;
+    dc.kind = c.kind; dc.origin = to3(c.origin); dc.at = to3(c.at); dc.up = to3(c.up); dc.focus = to3(c.focus); dc.aperture = c.aperture;
+    dc.animated = c.animated & 15u; dc.origin_vel = to3(c.origin_vel); dc.at_vel = to3(c.at_vel); dc.up_vel = to3(c.up_vel); dc.focus_vel = to3(c.focus_vel);
+    if (c.kind == RAYN_CAM_ORTHOGRAPHIC) { // OrthographicCamera::new, src/camera.rs:228-240
+        float aspect = c.res_w / c.res_h;
+        float sx = c.vfov_or_size * aspect, sy = c.vfov_or_size;
+        float pixel_size = c.vfov_or_size / c.res_h;
+        dc.half_w = sx / 2.0f; dc.half_h = sy / 2.0f; dc.full_w = sx; dc.full_h = sy;
+        dc.half_pixel_size = pixel_size / 2.0f;
+    } else if (c.kind == RAYN_CAM_PINHOLE || c.kind == RAYN_CAM_THIN_LENS) { // ::new, src/camera.rs:53-72,134-157
+        float theta = c.vfov_or_size * 3.14159265358979323846f / 180.0f;
+        float half_height = dm_tanf(theta / 2.0f);
+        float aspect = c.res_w / c.res_h;
+        float half_width = aspect * half_height;
+        dc.half_pixel_size = half_height / c.res_h;
+        dc.half_w = half_width; dc.half_h = half_height; dc.full_w = half_width; dc.full_h = half_height;
+    } else return false;
+    return true;
+}
 
 int build_scene(rayn_ctx* ctx, const rayn_world_desc& w, const rayn_frame_params& p, DScene* out) {
     DScene& s = *out;
@@ -112,24 +136,7 @@ int build_scene(rayn_ctx* ctx, const rayn_world_desc& w, const rayn_frame_params
     for (uint32_t i = 0; i < w.n_lights; i++) {
         s.l[i].pos = to3(w.lights[i].pos); s.l[i].rad = w.lights[i].rad; s.l[i].emission = to3(w.lights[i].emission);
     }
-    const rayn_camera& c = w.camera;
-    DCamera& dc = s.cam;
-    dc.kind = c.kind; dc.origin = to3(c.origin); dc.at = to3(c.at); dc.up = to3(c.up); dc.focus = to3(c.focus); dc.aperture = c.aperture;
-    dc.animated = c.animated & 15u; dc.origin_vel = to3(c.origin_vel); dc.at_vel = to3(c.at_vel); dc.up_vel = to3(c.up_vel); dc.focus_vel = to3(c.focus_vel);
-    if (c.kind == RAYN_CAM_ORTHOGRAPHIC) { // OrthographicCamera::new, src/camera.rs:228-240
-        float aspect = c.res_w / c.res_h;
-        float sx = c.vfov_or_size * aspect, sy = c.vfov_or_size;
-        float pixel_size = c.vfov_or_size / c.res_h;
-        dc.half_w = sx / 2.0f; dc.half_h = sy / 2.0f; dc.full_w = sx; dc.full_h = sy;
-        dc.half_pixel_size = pixel_size / 2.0f;
-    } else if (c.kind == RAYN_CAM_PINHOLE || c.kind == RAYN_CAM_THIN_LENS) { // ::new, src/camera.rs:53-72,134-157
-        float theta = c.vfov_or_size * 3.14159265358979323846f / 180.0f;
-        float half_height = dm_tanf(theta / 2.0f);
-        float aspect = c.res_w / c.res_h;
-        float half_width = aspect * half_height;
-        dc.half_pixel_size = half_height / c.res_h;
-        dc.half_w = half_width; dc.half_h = half_height; dc.full_w = half_width; dc.full_h = half_height;
-    } else return fail(ctx, RAYN_ERR_INVALID_ARG, "unknown camera kind");
+    if (!build_camera(w.camera, &s.cam)) return fail(ctx, RAYN_ERR_INVALID_ARG, "unknown camera kind");
     s.has_scatter = w.has_scattering; s.has_extinct = w.has_extinction; s.rho_s = w.coeff_scattering; s.rho_t = w.coeff_extinction;
     s.width = p.width; s.height = p.height; s.spp = p.samples * 4; s.max_bounces = p.max_bounces; s.vm = p.volume_marches;
     s.max_marches = p.max_marches; s.max_vis_marches = p.max_vis_marches;
@@ -1027,6 +1034,51 @@ int rayn_hip_denoise_variance_device(rayn_ctx* ctx, const rayn_frame_params* p, 
                                                              state_bytes, d_out_color, d_out_variance, d_scratch, scratch_bytes), hip_stream, &s)) return rc;
     launch_denoise_variance(s, *p, iterations, sigma_luminance, sigma_normal, sigma_alpha, d_color, d_alpha, d_normal, d_state, d_out_color, d_out_variance,
                             d_scratch);
+    return post_enqueued(ctx);
+}
+
+// The primary-hit G-buffer (temporal.hip): one centre ray per pixel through the scene's PRODUCT extend kernel at depth 0, selected as
+// rayn_hip_probe_extend selects it.  The scene of (uploaded world, p) goes to ctx->d_scene on the stream, as a render's does (a pageable
+// source is staged before hipMemcpyAsync returns, so the stack copy may go away).
+int rayn_hip_gbuffer_device(rayn_ctx* ctx, const rayn_frame_params* p, void* d_out_records, uint32_t* d_out_object, void* d_scratch,
+                            size_t scratch_bytes, void* hip_stream) {
+    const char* why = gbuffer_check_args(p, d_out_records, d_out_object, d_scratch, scratch_bytes);
+    if (!why && ctx && !ctx->cfg->have_world) why = "rayn_hip_upload_world has not been called";
+    hipStream_t s;
+    if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
+    DScene hs;
+    if (int rc = build_scene(ctx, ctx->cfg->world, *p, &hs)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_scene, &hs, sizeof hs, hipMemcpyHostToDevice, s));
+    Tuning tun;
+    const int single_sdf = scene_march_kernels(ctx, hs, *p, &tun);
+    const KernelSet K = kernel_set(ctx->cfg->fma_policy);
+    const GbufScratch g = gbuffer_scratch(p->width, p->height, d_scratch);
+    if (ctx->cfg->fma_policy) rayn_p1::launch_gbuffer_rays(s, ctx->d_scene, g);
+    else rayn_p0::launch_gbuffer_rays(s, ctx->d_scene, g);
+    K.extend(s, false, ctx->d_scene, 0, g.q, g.npad, g.pool, g.ent_obj, single_sdf, g.ctl, g.evals, tun);
+    launch_gbuffer_finish(s, g, d_out_records, d_out_object);
+    return post_enqueued(ctx);
+}
+
+int rayn_hip_temporal_accumulate_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp, const rayn_camera* prev_camera,
+                                        float prev_time_start, const float* d_color, const float* d_normal, const void* d_gbuffer_records,
+                                        const uint32_t* d_gbuffer_object, const void* d_prev_history, void* d_new_history, size_t history_bytes,
+                                        float* d_out_color, void* hip_stream) {
+    const char* why = temporal_check_args(p, tp, prev_camera, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history, d_new_history,
+                                          history_bytes, d_out_color);
+    if (!why && ctx && !ctx->cfg->have_world) why = "rayn_hip_upload_world has not been called";
+    TemporalScene ts;
+    memset(&ts, 0, sizeof ts);
+    if (!why && prev_camera && !build_camera(*prev_camera, &ts.cam)) why = "unknown camera kind";
+    hipStream_t s;
+    if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
+    const rayn_world_desc& w = ctx->cfg->world;
+    ts.prev_time = prev_time_start; ts.cur_time = p->time_start;
+    ts.n_hitables = w.n_hitables < RAYN_MAX_HITABLES ? w.n_hitables : RAYN_MAX_HITABLES;
+    for (uint32_t i = 0; i < ts.n_hitables; i++)
+        ts.hvel[i] = make_float4(w.hitables[i].center_vel.x, w.hitables[i].center_vel.y, w.hitables[i].center_vel.z, w.hitables[i].animated ? 1.0f : 0.0f);
+    launch_temporal_accumulate(s, p->width, p->height, *tp, ts, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history, d_new_history,
+                               d_out_color);
     return post_enqueued(ctx);
 }
 

@@ -1,0 +1,310 @@
+// temporal.hip — temporal accumulation for frame sequences, the temporal half of SVGF (Schied et al., HPG 2017): a primary-hit G-buffer
+// pass (rayn_hip_gbuffer_device) and the reprojection + blend of the film's Color channel (rayn_hip_temporal_accumulate_device).
+// Extensions: rayn has neither.  Both run downstream of the film; the film and the integrator are not touched.
+//
+// G-buffer.  k_gbuffer_rays writes one ray per pixel p = x + y * width (bottom-up rows) into a pool-shaped scratch: uv = (ndc_x (x + 0.5f),
+// ndc_y (y + 0.5f)) - k_raygen's expression with a filter offset of 0 - lens sample (0.5, 0.5), ray time = closure time = time_start,
+// through camera_ray (device_core.h) under the build's mul_add policy; and the identity queue padded to whole 64-slot groups.  (0.5, 0.5)
+// is the point concentric_circle_map nudges off its singular centre (b = 0.0001, src/math.rs:205): a thin lens's G-buffer ray leaves the
+// lens 0.0001 * aperture beside the centre, far below a pixel.  The scene's PRODUCT extend kernel then runs at depth 0 (launch glue in
+// rayn_hip.hip, as rayn_hip_probe_extend selects it), and k_gbuffer_finish writes (P, t) with P = o + t d as a separate multiply and add,
+// and the object index; a miss writes (0, 0, 0, +inf) and 0xFFFFFFFF.  This file is built once per mul_add policy for k_gbuffer_rays;
+// everything else is policy-free and built with the RAYN_FMA_POLICY=0 object only.
+//
+// Accumulate (include/rayn_hip.h has the same text; tests/temporal_np.py restates it in numpy and the tests compare bit for bit).  All f32,
+// -ffp-contract=off, IEEE '/' and sqrtf.  dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z; cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z,
+// a.x b.y - a.y b.x); nz(a) = a * (1.0f / sqrtf(dot(a, a))); a vector +, -, * scalar acts per component; "a - b * s" is a multiply, then
+// a subtraction.  Per pixel p with colour c, normal nrm, G-buffer record (P, t) and object obj:
+//   reset (out = c, n' = 1; n' = 0 when c has a non-finite component) when obj = 0xFFFFFFFF, c is not finite, or there is no previous history
+//   Pp = P - center_vel[obj] * (time_start_cur - time_start_prev) when hitable obj is animated, else P
+//   camera at ts = time_start_prev: o = origin + origin_vel * ts (bit 0 of animated; else origin), at and up likewise
+//   pinhole, thin lens:  w = nz(o - at), u = nz(cross(up, w)), v = cross(w, u);  q = Pp - o;  zc = -dot(q, w), rejected unless zc > 0;
+//                        uvx = (dot(q, u) / (zc * half_w) + 1.0f) * 0.5f, uvy = (dot(q, v) / (zc * half_h) + 1.0f) * 0.5f;  te = sqrtf(dot(q, q))
+//   orthographic:        w = nz(at - o), u = nz(cross(w, up)), v = cross(u, w);  ll = (o - u * half_w) - v * half_h;  q = Pp - ll;
+//                        uvx = dot(q, u) / full_w, uvy = dot(q, v) / full_h;  te = dot(q, w), rejected unless te > 0
+//   fx = uvx * (float)width - 0.5f, fy = uvy * (float)height - 0.5f, rejected unless both are finite
+//   x0f = floorf(fx), y0f = floorf(fy); wx1 = fx - x0f, wx0 = 1.0f - wx1, wy1 = fy - y0f, wy0 = 1.0f - wy1;
+//   x0 = (integer) min(max(x0f, -2), 2^31), y0 likewise (the clamp only keeps the conversion defined: such taps are outside anyway)
+//   taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) with w = wx0 wy0, wx1 wy0, wx0 wy1, wx1 wy1; a tap counts when it is inside
+//   the image, n_tap >= 1, obj_tap = obj, fabsf(t_tap - te) <= depth_tolerance * te and, with normal_min > -1, dot(nrm, nrm_tap) >= normal_min
+//   (every comparison false for a NaN):   W += w, S += w * c_tap, N += w * n_tap
+//   W > 0:  h = S / W, nh = N / W, n' = fminf(nh + 1.0f, (float)max_history), a = 1.0f / n', out = h + a * (c - h); out is taken when its
+//   three components are finite.  A rejected projection, W <= 0 and a non-finite out reset the pixel.
+//   History out: A' = (out, n'), B' = (P, t), the object and (nrm, 0).
+// One thread per pixel in 16x16 blocks, 16-byte record loads, as denoise.hip; at most 4 x 3 record loads per pixel: bandwidth-trivial.
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "device_core.h"
+#include "temporal.h"
+
+namespace RAYN_KNS {
+
+// One thread per padded slot.  n = width * height < 2^31, npad = n rounded up to 64.
+__global__ void __launch_bounds__(256) k_gbuffer_rays(const DScene* __restrict__ scp, uint32_t n, uint32_t npad, float4* __restrict__ geo0,
+                                                       float4* __restrict__ geo1, float4* __restrict__ col1, uint32_t* __restrict__ q,
+                                                       DCtl* __restrict__ ctl) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= npad) return;
+    if (i == 0) {
+        DCtl c = {};
+        c.q_groups = npad >> 6; c.q_valid = n;
+        *ctl = c;
+    }
+    if (i >= n) { q[i] = INVALID; return; }
+    const DScene& sc = *scp;
+    const uint32_t y = i / sc.width, x = i - y * sc.width;
+    const float uvx = sc.ndc_x * ((float)x + 0.5f), uvy = sc.ndc_y * ((float)y + 0.5f);
+    f3 o, d;
+    camera_ray(sc.cam, uvx, uvy, 0.5f, 0.5f, sc.time_start, &o, &d);
+    geo0[i] = make_float4(o.x, o.y, o.z, d.x);
+    geo1[i] = make_float4(d.y, d.z, 0.0f, __uint_as_float(OBJ_NONE));
+    col1[i] = make_float4(0.0f, 0.0f, __uint_as_float(i), sc.time_start);
+    q[i] = i;
+}
+
+void launch_gbuffer_rays(hipStream_t s, const DScene* sc, const GbufScratch& g) {
+    hipLaunchKernelGGL(k_gbuffer_rays, dim3((g.npad + 255u) / 256u), dim3(256), 0, s, sc, g.n, g.npad, g.pool.geo0, g.pool.geo1, g.pool.col1, g.q, g.ctl);
+}
+
+} // namespace RAYN_KNS
+
+#if RAYN_FMA_POLICY == 0
+namespace rayn {
+namespace {
+
+constexpr size_t GBUF_CTL_BYTES = 256, GBUF_EVALS_BYTES = 128;
+static_assert(sizeof(DCtl) <= GBUF_CTL_BYTES, "the G-buffer scratch reserves 256 bytes for the control block");
+
+__device__ inline bool fin(float v) { return __builtin_isfinite(v); }
+
+// One thread per pixel: the pool's ray + the hit the extend kernel left in geo1 -> record and object index.
+__global__ void __launch_bounds__(256) k_gbuffer_finish(uint32_t n, const float4* __restrict__ geo0, const float4* __restrict__ geo1,
+                                                         float4* __restrict__ out, uint32_t* __restrict__ out_obj) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 g0 = geo0[i], g1 = geo1[i];
+    const uint32_t id = __float_as_uint(g1.w) & 0xFFu;
+    if (id == OBJ_NONE) {
+        out[i] = make_float4(0.0f, 0.0f, 0.0f, __builtin_inff());
+        out_obj[i] = INVALID;
+        return;
+    }
+    const float t = g1.z;
+    const float mx = t * g0.w, my = t * g1.x, mz = t * g1.y;
+    out[i] = make_float4(g0.x + mx, g0.y + my, g0.z + mz, t);
+    out_obj[i] = id;
+}
+
+struct v3 { float x, y, z; };
+__device__ inline v3 sub3(v3 a, v3 b) { return v3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ inline v3 scale3(v3 a, float s) { return v3{a.x * s, a.y * s, a.z * s}; }
+__device__ inline float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ inline v3 cross3(v3 a, v3 b) { return v3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ inline v3 nz3(v3 a) { return scale3(a, 1.0f / __builtin_sqrtf(dot3(a, a))); }
+__device__ inline v3 closure3(f3 base, f3 vel, bool on, float t) {
+    return on ? v3{base.x + vel.x * t, base.y + vel.y * t, base.z + vel.z * t} : v3{base.x, base.y, base.z};
+}
+
+__global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uint32_t height, uint32_t tiles_x, float max_history, float depth_tolerance,
+                                                              float normal_min, TemporalScene ts, const float* __restrict__ color,
+                                                              const float* __restrict__ normal, const float4* __restrict__ grec,
+                                                              const uint32_t* __restrict__ gobj, const float4* __restrict__ pA,
+                                                              const float4* __restrict__ pB, const float4* __restrict__ pN,
+                                                              const uint32_t* __restrict__ pO, float4* __restrict__ nA, float4* __restrict__ nB,
+                                                              float4* __restrict__ nN, uint32_t* __restrict__ nO, float* __restrict__ out_color) {
+    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const uint32_t x = tx * 16u + threadIdx.x, y = ty * 16u + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const uint32_t p = x + y * width; // < 2^31
+    const size_t f = (size_t)p * 3u;
+    const v3 c = v3{color[f], color[f + 1], color[f + 2]};
+    const v3 nrm = v3{normal[f], normal[f + 1], normal[f + 2]};
+    const float4 g = grec[p];
+    const uint32_t obj = gobj[p];
+    const bool cfin = fin(c.x) && fin(c.y) && fin(c.z);
+    v3 out = c;
+    float nn = cfin ? 1.0f : 0.0f;
+    if (cfin && obj != INVALID && pA) {
+        v3 Pp = v3{g.x, g.y, g.z};
+        const float dt = ts.cur_time - ts.prev_time;
+#pragma unroll
+        for (uint32_t k = 0; k < RAYN_MAX_HITABLES; k++)
+            if (k < ts.n_hitables && obj == k && ts.hvel[k].w != 0.0f) Pp = v3{g.x - ts.hvel[k].x * dt, g.y - ts.hvel[k].y * dt, g.z - ts.hvel[k].z * dt};
+        const DCamera& cam = ts.cam;
+        const v3 o = closure3(cam.origin, cam.origin_vel, cam.animated & 1u, ts.prev_time);
+        const v3 at = closure3(cam.at, cam.at_vel, cam.animated & 2u, ts.prev_time);
+        const v3 up = closure3(cam.up, cam.up_vel, cam.animated & 4u, ts.prev_time);
+        float uvx, uvy, te;
+        bool ok;
+        if (cam.kind == RAYN_CAM_ORTHOGRAPHIC) {
+            const v3 w = nz3(sub3(at, o)), u = nz3(cross3(w, up)), v = cross3(u, w);
+            const v3 ll = sub3(sub3(o, scale3(u, cam.half_w)), scale3(v, cam.half_h));
+            const v3 q = sub3(Pp, ll);
+            uvx = dot3(q, u) / cam.full_w;
+            uvy = dot3(q, v) / cam.full_h;
+            te = dot3(q, w);
+            ok = te > 0.0f;
+        } else {
+            const v3 w = nz3(sub3(o, at)), u = nz3(cross3(up, w)), v = cross3(w, u);
+            const v3 q = sub3(Pp, o);
+            const float zc = -dot3(q, w);
+            ok = zc > 0.0f;
+            uvx = (dot3(q, u) / (zc * cam.half_w) + 1.0f) * 0.5f;
+            uvy = (dot3(q, v) / (zc * cam.half_h) + 1.0f) * 0.5f;
+            te = __builtin_sqrtf(dot3(q, q));
+        }
+        const float fx = uvx * (float)width - 0.5f, fy = uvy * (float)height - 0.5f;
+        if (ok && fin(fx) && fin(fy)) {
+            const float x0f = __builtin_floorf(fx), y0f = __builtin_floorf(fy);
+            const float wx1 = fx - x0f, wx0 = 1.0f - wx1, wy1 = fy - y0f, wy0 = 1.0f - wy1;
+            const long long x0 = (long long)__builtin_fminf(__builtin_fmaxf(x0f, -2.0f), 2147483648.0f);
+            const long long y0 = (long long)__builtin_fminf(__builtin_fmaxf(y0f, -2.0f), 2147483648.0f);
+            const float tol = depth_tolerance * te;
+            float W = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f, N = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const long long qx = x0 + (k & 1), qy = y0 + (k >> 1);
+                if (qx < 0 || qx >= (long long)width || qy < 0 || qy >= (long long)height) continue;
+                const uint32_t q = (uint32_t)qx + (uint32_t)qy * width;
+                const float4 a = pA[q];
+                if (!(a.w >= 1.0f)) continue;
+                if (pO[q] != obj) continue;
+                if (!(__builtin_fabsf(pB[q].w - te) <= tol)) continue;
+                if (normal_min > -1.0f) {
+                    const float4 nq = pN[q];
+                    if (!(dot3(nrm, v3{nq.x, nq.y, nq.z}) >= normal_min)) continue;
+                }
+                const float w = ((k & 1) ? wx1 : wx0) * ((k >> 1) ? wy1 : wy0);
+                W += w;
+                Sr += w * a.x;
+                Sg += w * a.y;
+                Sb += w * a.z;
+                N += w * a.w;
+            }
+            if (W > 0.0f) {
+                const float hr = Sr / W, hg = Sg / W, hb = Sb / W, nh = N / W;
+                const float n1 = __builtin_fminf(nh + 1.0f, max_history);
+                const float al = 1.0f / n1;
+                const float dr = c.x - hr, dg = c.y - hg, db = c.z - hb;
+                const v3 b = v3{hr + al * dr, hg + al * dg, hb + al * db};
+                if (fin(b.x) && fin(b.y) && fin(b.z)) { out = b; nn = n1; }
+            }
+        }
+    }
+    out_color[f] = out.x;
+    out_color[f + 1] = out.y;
+    out_color[f + 2] = out.z;
+    nA[p] = make_float4(out.x, out.y, out.z, nn);
+    nB[p] = g;
+    nN[p] = make_float4(nrm.x, nrm.y, nrm.z, 0.0f);
+    nO[p] = obj;
+}
+
+bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + nb && y < x + na;
+}
+
+const char* check_size(uint32_t width, uint32_t height) {
+    if (!width || !height) return "zero-sized image";
+    if ((uint64_t)width * height >= ((uint64_t)1 << 31)) return "image larger than 2^31 pixels unsupported (32-bit pixel indices)";
+    return nullptr;
+}
+
+} // namespace
+
+size_t gbuffer_scratch_bytes(uint32_t width, uint32_t height) {
+    if (check_size(width, height)) return 0;
+    const uint64_t npad = ((uint64_t)width * height + 63u) & ~(uint64_t)63u;
+    return (size_t)(53u * npad + GBUF_CTL_BYTES + GBUF_EVALS_BYTES);
+}
+
+GbufScratch gbuffer_scratch(uint32_t width, uint32_t height, void* scratch) {
+    GbufScratch g;
+    memset(&g, 0, sizeof g);
+    g.n = width * height;
+    g.npad = (g.n + 63u) & ~63u;
+    char* b = (char*)scratch;
+    const size_t np = g.npad;
+    g.pool.geo0 = (float4*)b;
+    g.pool.geo1 = (float4*)(b + 16u * np);
+    g.pool.col1 = (float4*)(b + 32u * np);
+    g.q = (uint32_t*)(b + 48u * np);
+    g.ent_obj = (uint8_t*)(b + 52u * np);
+    g.ctl = (DCtl*)(b + 53u * np);
+    g.evals = (unsigned long long*)(b + 53u * np + GBUF_CTL_BYTES);
+    return g;
+}
+
+const char* gbuffer_check_args(const rayn_frame_params* p, const void* out_records, const uint32_t* out_object, const void* scratch, size_t scratch_bytes) {
+    if (!p) return "null frame params";
+    if (const char* why = check_size(p->width, p->height)) return why;
+    if (!out_records || !out_object || !scratch) return "null buffer";
+    if (scratch_bytes < gbuffer_scratch_bytes(p->width, p->height)) return "scratch smaller than rayn_gbuffer_scratch_bytes(width, height)";
+    if ((uintptr_t)scratch % 16u) return "scratch not 16-byte aligned";
+    if ((uintptr_t)out_records % 16u) return "d_out_records not 16-byte aligned";
+    if ((uintptr_t)out_object % 4u) return "d_out_object not 4-byte aligned";
+    const size_t n = (size_t)p->width * p->height;
+    if (overlap(out_records, 16u * n, scratch, scratch_bytes) || overlap(out_object, 4u * n, scratch, scratch_bytes) || overlap(out_records, 16u * n, out_object, 4u * n))
+        return "the outputs must not overlap each other or the scratch";
+    return nullptr;
+}
+
+void launch_gbuffer_finish(hipStream_t s, const GbufScratch& g, void* out_records, uint32_t* out_object) {
+    hipLaunchKernelGGL(k_gbuffer_finish, dim3((g.n + 255u) / 256u), dim3(256), 0, s, g.n, g.pool.geo0, g.pool.geo1, (float4*)out_records, out_object);
+}
+
+size_t temporal_history_bytes(uint32_t width, uint32_t height) {
+    if (check_size(width, height)) return 0;
+    return (size_t)(52u * (uint64_t)width * height);
+}
+
+const char* temporal_check_args(const rayn_frame_params* p, const rayn_temporal_params* tp, const rayn_camera* prev_camera, const float* color,
+                                const float* normal, const void* g_records, const uint32_t* g_object, const void* prev_history,
+                                const void* new_history, size_t history_bytes, const float* out_color) {
+    if (!p) return "null frame params";
+    if (const char* why = check_size(p->width, p->height)) return why;
+    if (!tp) return "null temporal params";
+    if (tp->max_history < 1 || tp->max_history > 65536) return "max_history must be in 1..65536";
+    if (!(tp->depth_tolerance >= 0.0f) || !(tp->depth_tolerance <= 3.40282347e+38f)) return "depth_tolerance must be finite and >= 0";
+    if (!(tp->normal_min >= -1.0f && tp->normal_min <= 1.0f)) return "normal_min must be in [-1, 1]";
+    if (!color || !normal || !g_records || !g_object || !new_history || !out_color) return "null buffer";
+    if (prev_history && !prev_camera) return "a previous history needs the previous camera";
+    if (prev_camera && prev_camera->kind > RAYN_CAM_ORTHOGRAPHIC) return "unknown camera kind";
+    const size_t need = temporal_history_bytes(p->width, p->height);
+    if (history_bytes < need) return "history smaller than rayn_temporal_history_bytes(width, height)";
+    if ((uintptr_t)new_history % 16u || (uintptr_t)prev_history % 16u) return "history not 16-byte aligned";
+    if ((uintptr_t)g_records % 16u) return "d_gbuffer_records not 16-byte aligned";
+    if ((uintptr_t)g_object % 4u) return "d_gbuffer_object not 4-byte aligned";
+    const size_t n = (size_t)p->width * p->height;
+    if (overlap(new_history, need, prev_history, need)) return "the new history must not alias the previous one";
+    const void* in[4] = {color, normal, g_records, g_object};
+    const size_t in_bytes[4] = {12u * n, 12u * n, 16u * n, 4u * n};
+    for (int i = 0; i < 4; i++)
+        if (overlap(out_color, 12u * n, in[i], in_bytes[i]) || overlap(new_history, need, in[i], in_bytes[i])) return "an output must not alias an input";
+    if (overlap(out_color, 12u * n, prev_history, need)) return "an output must not alias an input";
+    if (overlap(out_color, 12u * n, new_history, need)) return "d_out_color must not alias the new history";
+    return nullptr;
+}
+
+void launch_temporal_accumulate(hipStream_t s, uint32_t width, uint32_t height, const rayn_temporal_params& tp, const TemporalScene& ts,
+                                const float* color, const float* normal, const void* g_records, const uint32_t* g_object,
+                                const void* prev_history, void* new_history, float* out_color) {
+    const size_t n = (size_t)width * height;
+    const float4* pA = (const float4*)prev_history; // null: no previous history
+    float4* nA = (float4*)new_history;
+    const uint32_t tiles_x = (width + 15u) / 16u, tiles_y = (height + 15u) / 16u;
+    hipLaunchKernelGGL(k_temporal_accumulate, dim3(tiles_x * tiles_y), dim3(16, 16), 0, s, width, height, tiles_x, (float)tp.max_history,
+                       tp.depth_tolerance, tp.normal_min, ts, color, normal, (const float4*)g_records, g_object, pA, pA ? pA + n : nullptr,
+                       pA ? pA + 2u * n : nullptr, pA ? (const uint32_t*)(pA + 3u * n) : nullptr, nA, nA + n, nA + 2u * n, (uint32_t*)(nA + 3u * n),
+                       out_color);
+}
+
+} // namespace rayn
+
+extern "C" size_t rayn_gbuffer_scratch_bytes(uint32_t width, uint32_t height) { return rayn::gbuffer_scratch_bytes(width, height); }
+extern "C" size_t rayn_temporal_history_bytes(uint32_t width, uint32_t height) { return rayn::temporal_history_bytes(width, height); }
+#endif // RAYN_FMA_POLICY == 0

@@ -98,6 +98,60 @@ class VarianceDenoise:
                                    sigma_alpha=self.sigma_alpha if have_mask & 2 else 0.0)
 
 
+@dataclasses.dataclass(frozen=True)
+class Temporal:
+    """Parameters of the temporal accumulation of a sequence's Color channel (rayn_hip_temporal_accumulate_device, an extension: rayn
+    renders every frame on its own; the temporal half of SVGF, Schied et al., HPG 2017).  Every frame's accumulated Color is reprojected
+    onto the next frame through the world position of each pixel's primary hit (rayn_hip_gbuffer_device) and blended with it, out = h +
+    (c - h) / n, n the history length + 1 capped at `max_history` (1..65536; 1 = no accumulation).  A bilinear tap of the history counts
+    when it shows the same object, its recorded hit distance is within `depth_tolerance` (relative; finite, >= 0) of the reprojected one
+    and its normal has at least the dot product `normal_min` (in [-1, 1]; -1 switches the test off) with the pixel's.
+
+    The defaults were chosen on the shipped scene (rayn_amd.setup at 160x96 under a camera whose origin moves, 8 frames of 8 spp; the MSE
+    of the saturated Color + Background of the last frame against 1024 spp) over a grid of the three (tools/temporal_defaults.py; DESIGN.md
+    section 8 has it): a history of 4, a depth tolerance of 5 % and the normal test off bring the MSE to 0.49x that of the raw frame.  The
+    film's WorldNormal is the mean of a pixel's sample normals, far from unit length on the fractal, and a floor on its dot product throws
+    away most of the history (0.81x at 0.5, 0.94x at 0.9); a longer history gains nothing over 8 frames (0.51x) and blurs more."""
+    max_history: int = 4
+    depth_tolerance: float = 0.05
+    normal_min: float = -1.0
+
+    def __post_init__(self):
+        if isinstance(self.max_history, bool) or not isinstance(self.max_history, (int, np.integer)) or not 1 <= self.max_history <= 65536:
+            raise ValueError(f"Temporal.max_history must be an int in 1..65536, got {self.max_history!r}")
+        for name in ("depth_tolerance", "normal_min"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+                raise ValueError(f"Temporal.{name} must be a number, got {v!r}")
+        with np.errstate(over="ignore"):
+            d = float(np.float32(self.depth_tolerance))  # the C entry takes it as an f32: check that value too
+        if not (np.isfinite(d) and d >= 0.0 and float(self.depth_tolerance) >= 0.0):
+            raise ValueError(f"Temporal.depth_tolerance must be finite and >= 0, got {self.depth_tolerance!r}")
+        if not -1.0 <= float(self.normal_min) <= 1.0:
+            raise ValueError(f"Temporal.normal_min must be in [-1, 1], got {self.normal_min!r}")
+
+    def to_abi(self):
+        return _abi.TemporalParams(int(self.max_history), float(self.depth_tolerance), float(self.normal_min))
+
+
+def gbuffer_scratch_bytes(width, height):
+    """rayn_gbuffer_scratch_bytes: bytes of device scratch the G-buffer pass needs for a width x height film (0 for a size it rejects)."""
+    return int(lib().rayn_gbuffer_scratch_bytes(int(width), int(height)))
+
+
+def temporal_history_bytes(width, height):
+    """rayn_temporal_history_bytes: bytes of one history of the temporal accumulation for a width x height film (0 for a size it rejects)."""
+    return int(lib().rayn_temporal_history_bytes(int(width), int(height)))
+
+
+def alloc_gbuffer(width, height, device="cuda"):
+    """The two planes of a G-buffer as Context.gbuffer fills them: records (n, 4) float32 (Px, Py, Pz, t) and object (n,) int32 (the u32
+    object index; a miss is -1 = 0xFFFFFFFF)."""
+    import torch
+    n = width * height
+    return {"records": torch.zeros(n, 4, dtype=torch.float32, device=device), "object": torch.zeros(n, dtype=torch.int32, device=device)}
+
+
 def denoise_scratch_bytes(width, height):
     """rayn_denoise_scratch_bytes: bytes of device scratch the denoiser needs for a width x height film (0 for a size it rejects)."""
     return int(lib().rayn_denoise_scratch_bytes(int(width), int(height)))
@@ -384,6 +438,55 @@ class Context:
                                                            C.c_void_p(d_scratch.data_ptr()), d_scratch.numel() * d_scratch.element_size(),
                                                            C.c_void_p(s)))
 
+    def gbuffer(self, params, d_gbuffer, d_scratch=None, stream=None):
+        """rayn_hip_gbuffer_device: the primary-hit G-buffer of the uploaded world under `params` (resolution, time_start, march constants)
+        into d_gbuffer (alloc_gbuffer's dict: "records" (n, 4) float32 = (Px, Py, Pz, t), "object" (n,) int32).  d_scratch: a CUDA tensor
+        of at least gbuffer_scratch_bytes(width, height) bytes, allocated here when None.  Enqueued on the stream, not waited for."""
+        import torch
+        n = int(params.width) * int(params.height)
+        rec, obj = d_gbuffer["records"], d_gbuffer["object"]
+        if not (rec.dtype == torch.float32 and rec.is_contiguous() and rec.numel() >= 4 * n):
+            raise ValueError(f"d_gbuffer['records'] must be a contiguous float32 tensor of at least {4 * n} floats")
+        if not (obj.dtype == torch.int32 and obj.is_contiguous() and obj.numel() >= n):
+            raise ValueError(f"d_gbuffer['object'] must be a contiguous int32 tensor of at least {n} elements")
+        if d_scratch is None:
+            d_scratch = torch.empty(max(gbuffer_scratch_bytes(params.width, params.height), 1), dtype=torch.uint8, device=rec.device)
+        if not d_scratch.is_contiguous():
+            raise ValueError("d_scratch must be contiguous")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._chk(self._L.rayn_hip_gbuffer_device(self.h, C.byref(params), C.c_void_p(rec.data_ptr()), C.c_void_p(obj.data_ptr()),
+                                                  C.c_void_p(d_scratch.data_ptr()), d_scratch.numel() * d_scratch.element_size(), C.c_void_p(s)))
+
+    def temporal_accumulate(self, params, temporal, d_film, d_gbuffer, d_prev_history, prev_camera, prev_time_start, d_new_history, d_out_color,
+                            stream=None):
+        """rayn_hip_temporal_accumulate_device: blend d_film["color"] (guides: d_film["normal"], the G-buffer d_gbuffer of the same frame)
+        with the previous frame's history d_prev_history (a uint8 CUDA tensor of temporal_history_bytes, or None: no history) reprojected
+        through prev_camera (an _abi.Camera) at prev_time_start, by the Temporal `temporal`.  Writes the accumulated colour to the float32
+        CUDA tensor d_out_color (width * height * 3 floats) and the new history to d_new_history.  Enqueued on the stream, not waited for."""
+        import torch
+        n = int(params.width) * int(params.height)
+        for key, t, floats in (("color", d_film.get("color"), 3), ("normal", d_film.get("normal"), 3), ("records", d_gbuffer.get("records"), 4)):
+            if t is None or not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= floats * n):
+                raise ValueError(f"{key!r} must be a contiguous float32 tensor of at least {floats * n} floats")
+        obj = d_gbuffer.get("object")
+        if obj is None or not (obj.dtype == torch.int32 and obj.is_contiguous() and obj.numel() >= n):
+            raise ValueError(f"d_gbuffer['object'] must be a contiguous int32 tensor of at least {n} elements")
+        if not (d_out_color.dtype == torch.float32 and d_out_color.is_contiguous() and d_out_color.numel() >= 3 * n):
+            raise ValueError(f"d_out_color must be a contiguous float32 tensor of at least {3 * n} floats")
+        for name, t in (("d_prev_history", d_prev_history), ("d_new_history", d_new_history)):
+            if t is not None and not (t.dtype == torch.uint8 and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous uint8 tensor")
+        if d_new_history is None:
+            raise ValueError("d_new_history must be a contiguous uint8 tensor")
+        nbytes = d_new_history.numel() if d_prev_history is None else min(d_new_history.numel(), d_prev_history.numel())
+        tp = temporal.to_abi()
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._chk(self._L.rayn_hip_temporal_accumulate_device(
+            self.h, C.byref(params), C.byref(tp), None if prev_camera is None else C.byref(prev_camera), float(prev_time_start),
+            C.c_void_p(d_film["color"].data_ptr()), C.c_void_p(d_film["normal"].data_ptr()), C.c_void_p(d_gbuffer["records"].data_ptr()),
+            C.c_void_p(obj.data_ptr()), None if d_prev_history is None else C.c_void_p(d_prev_history.data_ptr()),
+            C.c_void_p(d_new_history.data_ptr()), nbytes, C.c_void_p(d_out_color.data_ptr()), C.c_void_p(s)))
+
     @staticmethod
     def _prog_state(params, d_state):
         import torch
@@ -492,6 +595,7 @@ class Film:
         self.channels = None  # torch tensors after a render
         self.progressive_epoch = 0
         self._progressive = None  # after render_progressive: its device state, geometry, checkpoint key and epoch count
+        self._last_params = None  # the frame parameters of the last render (gbuffer)
 
     def render_frame_into(self, world, camera, integrator, filter, tile_size, frame, time_range, samples, tile_first=0, tile_step=1):
         """Film::render_frame_into (src/film.rs:382-628); the film is overwritten, not accumulated (:91)."""
@@ -506,6 +610,7 @@ class Film:
             self.ctx.render_device(p, d_tables, out)
             torch.cuda.synchronize()
         self.channels = out
+        self._last_params = p
         self.progressive_epoch += 1
         return self.ctx.stats()
 
@@ -516,6 +621,21 @@ class Film:
         w, h = self.res
         t = self.channels[key].cpu().numpy()
         return t.reshape(h, w, 3) if t.ndim == 2 else t.reshape(h, w)
+
+    def gbuffer(self):
+        """The primary-hit G-buffer of the last rendered frame (rayn_hip_gbuffer_device, an extension): one centre ray per pixel at the
+        frame's time_start through the product closest-hit kernel.  Returns {"position": float32 (h, w, 3), "t": float32 (h, w; +inf for
+        a miss), "object": uint32 (h, w; 0xFFFFFFFF for a miss)}, rows bottom-up like the film."""
+        import torch
+        if self._last_params is None:
+            raise ValueError("the film holds no rendered frame (render_frame_into, render_sequence or render_progressive has not run)")
+        w, h = self.res
+        with torch.cuda.device(self.device):
+            g = alloc_gbuffer(w, h, self.device)
+            self.ctx.gbuffer(self._last_params, g)
+            rec = g["records"].cpu().numpy().reshape(h, w, 4)
+            obj = g["object"].cpu().numpy().view(np.uint32).reshape(h, w)
+        return {"position": rec[..., :3].copy(), "t": rec[..., 3].copy(), "object": obj}
 
     def have_mask(self):
         """bit k = ChannelKind k is among the film's channels (the have_mask of rayn_save_to_bpp)"""
@@ -660,6 +780,7 @@ class Film:
                 self.channels = d_mean
                 self._progressive = {"state": d_state, "params": p0, "key": key, "epochs": first, "noise_floor": progressive.noise_floor,
                                      "film": d_mean}
+                self._last_params = p0
                 active, totals = self.ctx.progressive_fetch_active(p0, d_state, stream.cuda_stream)
                 report.update(active_tiles=active, totals=totals)
                 if first < progressive.max_epochs and len(active):
@@ -727,7 +848,7 @@ class Film:
         return _prog.error_map(arrays, w, h, (pr["params"].tile_w, pr["params"].tile_h), pr["noise_floor"])
 
     def render_sequence(self, world, camera, integrator, filter, tile_size, frames, frame_rate, shutter_speed, samples, write_channels,
-                        output_folder, base_name, transparent_background=False, writers=None, denoise=None):
+                        output_folder, base_name, transparent_background=False, writers=None, denoise=None, temporal=None):
         """rayn's main loop (src/main.rs:58-96) on the GPU: for each frame of `frames`, render_frame_into at
         frame_start = frame as f32 * (1.0 / frame_rate as f32), frame_end = frame_start + shutter_speed (f32, src/main.rs:61-62), then
         save_to(write_channels, output_folder, f"{base_name}_{frame:04d}", transparent_background).  rayn writes every frame under
@@ -745,7 +866,14 @@ class Film:
         With `denoise` (a Denoise), every frame's Color image is made from the denoised Color and written as _color_denoised.png, as
         save_to(..., denoise=denoise) does: the denoiser's kernels go on the render stream ahead of that frame's post-process kernels,
         and its scratch and denoised plane are allocated once.  A VarianceDenoise raises ValueError: a sequence's frames are plain
-        renders and carry no variance."""
+        renders and carry no variance.
+
+        With `temporal` (a Temporal, an extension), every frame's Color is accumulated over the frames before it: after the render, the
+        frame's G-buffer pass and the temporal accumulate go on the render stream, the Color image is made from the accumulated colour and
+        written as _color_temporal.png; with `denoise` as well the a-trous filter runs on the accumulated colour and the file is
+        _color_temporal_denoised.png.  The two histories, the G-buffer and the scratch are allocated once.  The first frame of a call has
+        no history; frames that are not consecutive still reproject, over whatever time lies between their starts.  The film's channels
+        stay what the integrator wrote.  temporal=None is the path described above, unchanged."""
         import concurrent.futures as cf
         import torch
         if isinstance(denoise, VarianceDenoise):
@@ -755,6 +883,16 @@ class Film:
         if denoise is not None:
             denoise = self._denoise_params(denoise) if ChannelKind.Color in write_channels else None
             jobs = [(kind, bpp, "color_denoised" if denoise is not None and kind == ChannelKind.Color else suffix) for kind, bpp, suffix in jobs]
+        if temporal is not None:
+            if not isinstance(temporal, Temporal):
+                raise ValueError(f"temporal must be a Temporal, got {temporal!r}")
+            if ChannelKind.Color not in self.channel_kinds or ChannelKind.WorldNormal not in self.channel_kinds:
+                raise ValueError("temporal accumulation needs the film's Color and WorldNormal channels")
+            if ChannelKind.Color not in write_channels:
+                temporal = None
+            else:
+                jobs = [(kind, bpp, ("color_temporal" if denoise is None else "color_temporal_denoised") if kind == ChannelKind.Color else suffix)
+                        for kind, bpp, suffix in jobs]
         os.makedirs(output_folder, exist_ok=True)
         w, h = self.res
         f32 = np.float32
@@ -780,7 +918,8 @@ class Film:
                 return stats
             with torch.cuda.device(self.device):
                 stream = torch.cuda.current_stream()
-                self.ctx.upload_world(world.to_desc(camera))
+                desc = world.to_desc(camera)
+                self.ctx.upload_world(desc)
                 next_rd = table_pool.submit(build_rd_tables, spp, mb, vm, frames[0])
                 scr, fis = build_film_tables(w, h, filter)
                 s1, s2 = next_rd.result()
@@ -790,6 +929,12 @@ class Film:
                 if denoise is not None:
                     d_denoised = torch.empty(w * h, 3, dtype=torch.float32, device=self.device)
                     d_scratch = torch.empty(denoise_scratch_bytes(w, h), dtype=torch.uint8, device=self.device)
+                if temporal is not None:
+                    d_gbuf = alloc_gbuffer(w, h, self.device)
+                    d_gscratch = torch.empty(gbuffer_scratch_bytes(w, h), dtype=torch.uint8, device=self.device)
+                    d_hist = [torch.empty(temporal_history_bytes(w, h), dtype=torch.uint8, device=self.device) for _ in range(2)]
+                    d_accum = torch.empty(w * h, 3, dtype=torch.float32, device=self.device)
+                    prev_start = None
                 h_img = [[torch.empty(h * w * bpp, dtype=torch.uint8, pin_memory=True) for _, bpp, _ in jobs] for _ in range(2)]
                 for i, frame in enumerate(frames):
                     if i:
@@ -808,16 +953,26 @@ class Film:
                     st["frame"] = frame
                     stats.append(st)
                     self.channels = d_film
+                    self._last_params = p
                     self.progressive_epoch += 1
                     # Frame k's post-process and copies go on the render stream, so frame k + 1's render (enqueued on the same stream
                     # after them) cannot overwrite d_film or d_img before they have been read; only the pinned slot needs a host-side
                     # wait: its images from frame k - 2 must have been encoded.
                     slot = i % 2
                     wait_slot(slot)
+                    d_shown = d_film  # what the Color image is made from
+                    if temporal is not None:
+                        self.ctx.gbuffer(p, d_gbuf, d_gscratch, stream.cuda_stream)
+                        self.ctx.temporal_accumulate(p, temporal, d_film, d_gbuf, None if prev_start is None else d_hist[(i + 1) % 2],
+                                                     None if prev_start is None else desc.camera, 0.0 if prev_start is None else prev_start,
+                                                     d_hist[i % 2], d_accum, stream.cuda_stream)
+                        prev_start = p.time_start
+                        d_shown = dict(d_film, color=d_accum)
                     if denoise is not None:
-                        self.ctx.denoise(w, h, d_film, d_denoised, denoise, d_scratch, stream.cuda_stream)
+                        self.ctx.denoise(w, h, d_shown, d_denoised, denoise, d_scratch, stream.cuda_stream)
+                        d_shown = dict(d_film, color=d_denoised)
                     for (kind, _, suffix), d, hbuf in zip(jobs, d_img, h_img[slot]):
-                        src = dict(d_film, color=d_denoised) if denoise is not None and kind == ChannelKind.Color else d_film
+                        src = d_shown if kind == ChannelKind.Color else d_film
                         self.ctx.save_to_pixels(kind, mask, transparent_background, w, h, src, d, stream.cuda_stream)
                         hbuf.copy_(d, non_blocking=True)
                     done = torch.cuda.Event()
