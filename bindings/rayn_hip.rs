@@ -9,7 +9,7 @@
 //!
 //! Reference seam: `Film::render_frame_into` (src/film.rs:382-395); the flattened `World` (src/world.rs:7-13).
 #![allow(dead_code)]
-use std::os::raw::c_char;
+use std::os::raw::{c_char, c_void};
 
 pub const RAYN_MAX_HITABLES: usize = 16;
 pub const RAYN_MAX_MATERIALS: usize = 16;
@@ -189,6 +189,31 @@ extern "C" {
     pub fn rayn_hip_get_entry_stats(ctx: *const RaynCtx, entry: i32, out: *mut RaynStats) -> i32;
     pub fn rayn_hip_set_fma_policy(ctx: *mut RaynCtx, policy: i32) -> i32;
     pub fn rayn_hip_sizeof(which: i32) -> usize;
+    /// bytes of the luminance moments beside one temporal history (a float2 per pixel; 0 for a size the entries reject); host only
+    pub fn rayn_temporal_moments_bytes(width: u32, height: u32) -> usize;
+    /// the variance-guided a-trous filter of a temporally accumulated Color (device pointers; include/rayn_hip.h has the definition)
+    pub fn rayn_hip_denoise_temporal_variance_device(
+        ctx: *mut RaynCtx,
+        width: u32,
+        height: u32,
+        iterations: u32,
+        sigma_luminance: f32,
+        sigma_normal: f32,
+        sigma_alpha: f32,
+        d_color: *const f32,
+        d_alpha: *const f32,
+        d_normal: *const f32,
+        d_gbuffer_object: *const u32,
+        d_history: *const c_void,
+        history_bytes: usize,
+        d_moments: *const c_void,
+        moments_bytes: usize,
+        d_out_color: *mut f32,
+        d_out_variance: *mut f32,
+        d_scratch: *mut c_void,
+        scratch_bytes: usize,
+        hip_stream: *mut c_void,
+    ) -> i32;
 }
 
 /// Start-up layout check against the library as compiled (indices: include/rayn_hip.h, rayn_hip_sizeof).

@@ -2,14 +2,16 @@
 (rayn_amd.setup, 1280x720, SAMPLES = 2 (8 spp), 3 bounces, the BlackmanHarris filter, 16x16 tiles) rendered frame by frame and
 written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints per-frame render times and frames/s.
 
-    python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise] [--temporal]
+    python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise [atrous|variance]] [--temporal]
 
 --compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
 the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
 both loops wrote the same bytes.  --denoise runs the a-trous denoiser (rayn_amd.Denoise() defaults, an extension) on every frame's
 Color before its post-process and writes _color_denoised.png instead of _color.png.  --temporal accumulates every frame's Color over the
 frames before it (rayn_amd.Temporal() defaults, an extension: a primary-hit G-buffer pass and a reprojection per frame) under a camera whose
-origin drifts, and writes _color_temporal.png (_color_temporal_denoised.png with --denoise)."""
+origin drifts, and writes _color_temporal.png (_color_temporal_denoised.png with --denoise).  --temporal --denoise variance filters the
+accumulated colour with the variance-guided denoiser instead, its variance estimated from luminance moments the accumulate carries along
+(rayn_amd.VarianceDenoise(1, 4.0, 0.4, 0.3), the setting recommended for sequences); it needs --temporal."""
 import argparse
 import os
 import sys
@@ -57,12 +59,16 @@ def main():
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--writers", type=int, default=None, help="PNG writer threads (at most 8; default 2 per written channel)")
     ap.add_argument("--compare-loop", action="store_true", help="also time the plain render_frame_into + host post-process loop")
-    ap.add_argument("--denoise", action="store_true", help="denoise every frame's Color (rayn_amd.Denoise() defaults)")
+    ap.add_argument("--denoise", nargs="?", const="atrous", default=None, choices=["atrous", "variance"],
+                    help="denoise every frame's Color: atrous (rayn_amd.Denoise() defaults; what a bare --denoise means) or variance "
+                         "(rayn_amd.VarianceDenoise(1, 4.0, 0.4, 0.3) on the temporally accumulated colour; needs --temporal)")
     ap.add_argument("--temporal", action="store_true", help="accumulate every frame's Color over the frames before it (rayn_amd.Temporal() defaults); the camera's origin drifts")
     args = ap.parse_args()
     if (args.denoise or args.temporal) and args.compare_loop:
         ap.error("--compare-loop compares with the host post-process, which has neither a denoiser nor a temporal accumulation: use one or the other")
-    denoise = R.Denoise() if args.denoise else None
+    if args.denoise == "variance" and not args.temporal:
+        ap.error("--denoise variance estimates its variance from the temporal accumulation: add --temporal")
+    denoise = {None: None, "atrous": R.Denoise(), "variance": R.VarianceDenoise(1, 4.0, 0.4, 0.3)}[args.denoise]
     temporal = R.Temporal() if args.temporal else None
     first, end = (int(x) for x in args.frames.split(":"))
     frames = list(range(first, end))

@@ -488,6 +488,55 @@ int rayn_hip_temporal_accumulate_device(rayn_ctx* ctx, const rayn_frame_params* 
                                         const uint32_t* d_gbuffer_object, const void* d_prev_history, void* d_new_history, size_t history_bytes,
                                         float* d_out_color, void* hip_stream);
 
+/* Temporal accumulate with luminance moments: SVGF's noise estimate for sequences.  The MOMENTS of a width x height film are one float2
+ * (m1, m2) per pixel in film pixel order, 8 bytes per pixel, beside a history (whose 52-byte layout does not change); the caller ping-pongs
+ * two of them with the histories.  Bytes of one (0 for a size rayn_temporal_history_bytes rejects).  Host only; needs no GPU. */
+size_t rayn_temporal_moments_bytes(uint32_t width, uint32_t height);
+/* rayn_hip_temporal_accumulate_device with the moments carried through the same reprojection: d_out_color and the new history are, bit
+ * for bit, what that entry writes for the same inputs.  On top of its definition, f32, no contraction, IEEE '/':
+ *   y = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b, y2 = y * y, for the frame's Color c.
+ *   A pixel that resets (steps 1 and 5) writes (m1, m2) = (y, y2), and (0, 0) when c is not finite (n' = 0: it is never a tap).
+ *   Otherwise, over the taps that count for the colour, with the same w and in the same order: S1 += w * m1_tap, S2 += w * m2_tap;
+ *   h1 = S1 / W, h2 = S2 / W; m1' = h1 + a * (y - h1), m2' = h2 + a * (y2 - h2) with the colour's a = 1.0f / n'.
+ *   If m1' or m2' is not finite the pixel writes (y, y2); the colour keeps its blended value (an overflow heals on the next frame).
+ * d_prev_moments is required exactly when d_prev_history is given; d_new_moments always; moments_bytes is the size of EACH.
+ * RAYN_ERR_INVALID_ARG with a last error text for everything rayn_hip_temporal_accumulate_device rejects, and for: a NULL d_new_moments,
+ * previous moments without a previous history or a previous history without previous moments, a moments_bytes below
+ * rayn_temporal_moments_bytes, moments that are not 16-byte aligned, the new moments overlapping the previous ones, an input or another
+ * output, and the previous moments overlapping an output.  The inputs, the previous history and the previous moments are not modified. */
+int rayn_hip_temporal_accumulate_moments_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp,
+                                                const rayn_camera* prev_camera, float prev_time_start, const float* d_color, const float* d_normal,
+                                                const void* d_gbuffer_records, const uint32_t* d_gbuffer_object, const void* d_prev_history,
+                                                void* d_new_history, size_t history_bytes, const void* d_prev_moments, void* d_new_moments,
+                                                size_t moments_bytes, float* d_out_color, void* hip_stream);
+
+/* Variance-guided denoiser of a temporally accumulated Color: the passes of rayn_hip_denoise_variance_device on a variance estimated
+ * from the moments above (SVGF, section 4.2).  Inputs: the accumulated colour c (3 floats per pixel, what the accumulate wrote to
+ * d_out_color), the film's Alpha and WorldNormal, the frame's G-buffer objects obj, the NEW history (for the history length n' in plane A's
+ * fourth component) and the NEW moments (m1, m2).  l_x = (0.2126f * c_x.r + 0.7152f * c_x.g) + 0.0722f * c_x.b.  Initial variance of pixel p:
+ *   NOT GUIDED (it passes through all passes unchanged and is never a tap) when obj_p = 0xFFFFFFFF, c_p has a non-finite component, or
+ *   n'_p >= 1 does not hold.
+ *   Temporal estimate, when n'_p >= 4.0f (SVGF's threshold, fixed):  d = m2 - m1 * m1,  v = (d > 0 ? d : 0.0f) / n'_p - the variance of the
+ *   accumulated mean, the meaning v has after a progressive render.  With a max_history below 4 this arm is never taken.
+ *   Spatial estimate, when 1 <= n'_p < 4:  the 7x7 window at unit spacing around p in raster order, the centre included; a tap q counts
+ *   when it is inside the image, obj_q == obj_p, n'_q >= 1 and c_q has three finite components:  k += 1.0f, s1 += l_q, s2 += l_q * l_q;
+ *   mu = s1 / k, d = s2 / k - mu * mu, v = d > 0 ? d : 0.0f.
+ *   A v that is not finite makes p not guided.
+ * Then the passes, the outputs and the parameter ranges of rayn_hip_denoise_variance_device, unchanged.  The filtered colour is NOT fed
+ * back into the history (SVGF feeds its first pass back; left out here).  All f32, no contraction, IEEE division.
+ * Enqueued on 'hip_stream' (NULL = the ctx's own stream; not waited for), on the ctx's GPU (devices[0] of a multi-device ctx).  DEVICE
+ * pointers: d_color / d_normal 3 floats per pixel, d_alpha 1, d_gbuffer_object one u32, d_out_color 3, d_out_variance 1 (may be NULL);
+ * d_history and d_moments 16-byte aligned, at least rayn_temporal_history_bytes / rayn_temporal_moments_bytes; d_scratch 16-byte aligned, at
+ * least rayn_denoise_variance_scratch_bytes.  RAYN_ERR_INVALID_ARG with a last error text for: a zero-sized image or width * height >= 2^31,
+ * iterations outside 1..8, a bad sigma, a NULL colour, object plane, history, moments, output or scratch, a NULL guide whose sigma is not 0,
+ * too small a history, moments or scratch, a misaligned history, moments, object plane or scratch, and an output or the scratch overlapping
+ * an input or each other.  The inputs are not modified. */
+int rayn_hip_denoise_temporal_variance_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance,
+                                              float sigma_normal, float sigma_alpha, const float* d_color, const float* d_alpha,
+                                              const float* d_normal, const uint32_t* d_gbuffer_object, const void* d_history, size_t history_bytes,
+                                              const void* d_moments, size_t moments_bytes, float* d_out_color, float* d_out_variance,
+                                              void* d_scratch, size_t scratch_bytes, void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */

@@ -309,6 +309,10 @@ class Film {
     rayn_ctx* ctx_ = nullptr;
 };
 
+// Extension (include/rayn_hip.h: temporal accumulate with luminance moments): bytes of the moments beside one temporal history of a film
+// of this size, 8 per pixel; 0 for a size the entries reject.  Host only.
+inline size_t temporal_moments_bytes(Extent2u res) { return rayn_temporal_moments_bytes(res.w, res.h); }
+
 // ---- setup::setup() (src/setup.rs:46-170) with the resolution as an argument ---------------------
 namespace setup {
 constexpr float WORLD_RADIUS = 100.0f;

@@ -69,6 +69,16 @@ class TemporalParams(C.Structure):  # rayn_temporal_params
     _fields_ = [("max_history", C.c_uint32), ("depth_tolerance", C.c_float), ("normal_min", C.c_float)]
 
 
+MOMENTS_BYTES_PER_PIXEL = 8  # one float2 (m1, m2) per pixel beside a temporal history
+
+
+def temporal_moments_bytes(width, height):
+    """rayn_temporal_moments_bytes without the library: 8 bytes per pixel, 0 for a size the temporal entries reject (zero, or
+    width * height >= 2^31)."""
+    n = int(width) * int(height)
+    return MOMENTS_BYTES_PER_PIXEL * n if 0 < n < 1 << 31 and width > 0 and height > 0 else 0
+
+
 class Stats(C.Structure):
     _fields_ = [("paths", C.c_uint64), ("segments", C.c_uint64), ("shaded_slots", C.c_uint64),
                 ("tiles", C.c_uint64), ("batches", C.c_uint64), ("ms_total", C.c_double),

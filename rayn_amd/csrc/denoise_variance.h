@@ -23,4 +23,31 @@ void launch_denoise_variance(hipStream_t s, const rayn_frame_params& p, uint32_t
                              float sigma_alpha, const float* color, const float* alpha, const float* normal, const void* state, float* out_color,
                              float* out_variance, void* scratch);
 
+
+// ---- what the entries that pack a variance of their own share (denoise_temporal.hip) ----------------------------------------------------
+// which of k_vatrous's terms are on: a sigma of 0 switches its term off
+constexpr uint32_t VATROUS_LUMINANCE = 1u, VATROUS_NORMAL = 2u, VATROUS_ALPHA = 4u;
+inline uint32_t vatrous_terms(float sigma_luminance, float sigma_normal, float sigma_alpha) {
+    return (sigma_luminance != 0.0f ? VATROUS_LUMINANCE : 0u) | (sigma_normal != 0.0f ? VATROUS_NORMAL : 0u) | (sigma_alpha != 0.0f ? VATROUS_ALPHA : 0u);
+}
+// the (normal, alpha) record plane of the scratch, nullptr when both guides are off (it is then neither written nor read)
+inline float4* vatrous_guides(uint32_t terms, uint32_t width, uint32_t height, void* scratch) {
+    return (terms & (VATROUS_NORMAL | VATROUS_ALPHA)) ? (float4*)scratch + 2u * ((size_t)width * height) : nullptr;
+}
+bool vatrous_sigma_ok(float sigma);
+// Enqueue the `iterations` passes on records a pack kernel has written: A = (r, g, b, v or NaN) in plane 0 of the scratch, B = (nx, ny,
+// nz, alpha) in vatrous_guides.  The last pass writes out_color and, when given, out_variance.
+void launch_vatrous_passes(hipStream_t s, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance, float sigma_normal,
+                           float sigma_alpha, float* out_color, float* out_variance, void* scratch);
+
+// ---- the same filter on a temporally accumulated colour (denoise_temporal.hip; rayn_hip_denoise_temporal_variance_device) -----------------
+const char* denoise_temporal_check_args(uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance, float sigma_normal,
+                                        float sigma_alpha, const float* color, const float* alpha, const float* normal, const uint32_t* g_object,
+                                        const void* history, size_t history_bytes, const void* moments, size_t moments_bytes,
+                                        const float* out_color, const float* out_variance, const void* scratch, size_t scratch_bytes);
+void launch_denoise_temporal_variance(hipStream_t s, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance,
+                                      float sigma_normal, float sigma_alpha, const float* color, const float* alpha, const float* normal,
+                                      const uint32_t* g_object, const void* history, const void* moments, float* out_color, float* out_variance,
+                                      void* scratch);
+
 } // namespace rayn

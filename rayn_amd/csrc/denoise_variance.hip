@@ -39,7 +39,7 @@
 namespace rayn {
 namespace {
 
-constexpr uint32_t TERM_LUMINANCE = 1u, TERM_NORMAL = 2u, TERM_ALPHA = 4u;
+constexpr uint32_t TERM_LUMINANCE = VATROUS_LUMINANCE, TERM_NORMAL = VATROUS_NORMAL, TERM_ALPHA = VATROUS_ALPHA;
 
 struct VarGeom { uint32_t width, height, tile_w, tile_h, tiles_x, tiles_y; };
 
@@ -181,10 +181,10 @@ void launch_pass(hipStream_t s, bool last, dim3 grid, uint32_t width, uint32_t h
         hipLaunchKernelGGL((k_vatrous<TERMS, false>), grid, block, 0, s, width, height, blocks_x, step, sl, sn, sa, a, b, a_out, out_color, out_variance);
 }
 
-// 0 = off; else finite and in [2^-30, 2^30]
-bool sigma_ok(float sigma) { return sigma == 0.0f || (sigma >= 0x1p-30f && sigma <= 0x1p30f); }
-
 } // namespace
+
+// 0 = off; else finite and in [2^-30, 2^30]
+bool vatrous_sigma_ok(float sigma) { return sigma == 0.0f || (sigma >= 0x1p-30f && sigma <= 0x1p30f); }
 
 size_t denoise_variance_scratch_bytes(uint32_t width, uint32_t height) {
     const uint64_t n = (uint64_t)width * height;
@@ -198,9 +198,9 @@ const char* denoise_variance_check_args(const rayn_frame_params* p, uint32_t ite
                                         size_t scratch_bytes) {
     if (const char* why = progressive_check_geometry(p, state, state_bytes)) return why;
     if (iterations < 1 || iterations > 8) return "iterations must be in 1..8";
-    if (!sigma_ok(sigma_luminance)) return "sigma_luminance must be 0 (off) or in [2^-30, 2^30]";
-    if (!sigma_ok(sigma_normal)) return "sigma_normal must be 0 (off) or in [2^-30, 2^30]";
-    if (!sigma_ok(sigma_alpha)) return "sigma_alpha must be 0 (off) or in [2^-30, 2^30]";
+    if (!vatrous_sigma_ok(sigma_luminance)) return "sigma_luminance must be 0 (off) or in [2^-30, 2^30]";
+    if (!vatrous_sigma_ok(sigma_normal)) return "sigma_normal must be 0 (off) or in [2^-30, 2^30]";
+    if (!vatrous_sigma_ok(sigma_alpha)) return "sigma_alpha must be 0 (off) or in [2^-30, 2^30]";
     if (!color || !out_color || !scratch) return "null buffer";
     if (!normal && sigma_normal != 0.0f) return "null normal guide with sigma_normal != 0";
     if (!alpha && sigma_alpha != 0.0f) return "null alpha guide with sigma_alpha != 0";
@@ -213,19 +213,14 @@ const char* denoise_variance_check_args(const rayn_frame_params* p, uint32_t ite
     return nullptr;
 }
 
-void launch_denoise_variance(hipStream_t s, const rayn_frame_params& p, uint32_t iterations, float sigma_luminance, float sigma_normal,
-                             float sigma_alpha, const float* color, const float* alpha, const float* normal, const void* state, float* out_color,
-                             float* out_variance, void* scratch) {
-    const ProgLayout L = progressive_layout(p.width, p.height, p.tile_w, p.tile_h);
-    const uint32_t width = p.width, height = p.height, n = width * height;
-    const uint32_t terms = (sigma_luminance != 0.0f ? TERM_LUMINANCE : 0u) | (sigma_normal != 0.0f ? TERM_NORMAL : 0u) | (sigma_alpha != 0.0f ? TERM_ALPHA : 0u);
+// The passes of k_vatrous on packed records: plane 0 of the scratch holds A = (r, g, b, v or NaN), plane 2 B = (nx, ny, nz, alpha) when a
+// guide is on; plane 1 is the other half of the ping-pong.  Shared by every entry that packs a variance (this file, denoise_temporal.hip).
+void launch_vatrous_passes(hipStream_t s, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance, float sigma_normal,
+                           float sigma_alpha, float* out_color, float* out_variance, void* scratch) {
+    const uint32_t n = width * height;
+    const uint32_t terms = vatrous_terms(sigma_luminance, sigma_normal, sigma_alpha);
     float4* plane[2] = {(float4*)scratch, (float4*)scratch + n};
-    float4* guides = (terms & (TERM_NORMAL | TERM_ALPHA)) ? (float4*)scratch + 2u * (size_t)n : nullptr;
-    const char* base = (const char*)state;
-    const VarGeom g{width, height, p.tile_w, p.tile_h, L.n_tiles / L.tiles_y, L.tiles_y};
-    hipLaunchKernelGGL(k_vdenoise_pack, dim3((n + 255u) / 256u), dim3(256), 0, s, g, color, (terms & TERM_ALPHA) ? alpha : nullptr,
-                       (terms & TERM_NORMAL) ? normal : nullptr, (const float4*)(base + L.off_s2), (const uint4*)(base + L.off_records), plane[0],
-                       guides);
+    float4* guides = vatrous_guides(terms, width, height, scratch);
     const uint32_t blocks_x = (width + 15u) / 16u, blocks_y = (height + 15u) / 16u;
     const dim3 grid(blocks_x * blocks_y); // < 2^27 blocks
     for (uint32_t i = 0; i < iterations; i++) {
@@ -246,6 +241,20 @@ void launch_denoise_variance(hipStream_t s, const rayn_frame_params& p, uint32_t
         }
 #undef RAYN_VPASS
     }
+}
+
+void launch_denoise_variance(hipStream_t s, const rayn_frame_params& p, uint32_t iterations, float sigma_luminance, float sigma_normal,
+                             float sigma_alpha, const float* color, const float* alpha, const float* normal, const void* state, float* out_color,
+                             float* out_variance, void* scratch) {
+    const ProgLayout L = progressive_layout(p.width, p.height, p.tile_w, p.tile_h);
+    const uint32_t width = p.width, height = p.height, n = width * height;
+    const uint32_t terms = vatrous_terms(sigma_luminance, sigma_normal, sigma_alpha);
+    const char* base = (const char*)state;
+    const VarGeom g{width, height, p.tile_w, p.tile_h, L.n_tiles / L.tiles_y, L.tiles_y};
+    hipLaunchKernelGGL(k_vdenoise_pack, dim3((n + 255u) / 256u), dim3(256), 0, s, g, color, (terms & VATROUS_ALPHA) ? alpha : nullptr,
+                       (terms & VATROUS_NORMAL) ? normal : nullptr, (const float4*)(base + L.off_s2), (const uint4*)(base + L.off_records),
+                       (float4*)scratch, vatrous_guides(terms, width, height, scratch));
+    launch_vatrous_passes(s, width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, out_color, out_variance, scratch);
 }
 
 } // namespace rayn

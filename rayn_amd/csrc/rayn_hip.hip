@@ -1060,12 +1060,17 @@ int rayn_hip_gbuffer_device(rayn_ctx* ctx, const rayn_frame_params* p, void* d_o
     return post_enqueued(ctx);
 }
 
-int rayn_hip_temporal_accumulate_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp, const rayn_camera* prev_camera,
-                                        float prev_time_start, const float* d_color, const float* d_normal, const void* d_gbuffer_records,
-                                        const uint32_t* d_gbuffer_object, const void* d_prev_history, void* d_new_history, size_t history_bytes,
-                                        float* d_out_color, void* hip_stream) {
+// Both temporal accumulate entries: new_moments == nullptr is the plain one (the moments arguments are then not looked at).
+static int temporal_accumulate(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp, const rayn_camera* prev_camera,
+                               float prev_time_start, const float* d_color, const float* d_normal, const void* d_gbuffer_records,
+                               const uint32_t* d_gbuffer_object, const void* d_prev_history, void* d_new_history, size_t history_bytes,
+                               bool moments, const void* d_prev_moments, void* d_new_moments, size_t moments_bytes, float* d_out_color,
+                               void* hip_stream) {
     const char* why = temporal_check_args(p, tp, prev_camera, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history, d_new_history,
                                           history_bytes, d_out_color);
+    if (!why && moments)
+        why = temporal_moments_check_args(p, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history, d_new_history, d_prev_moments,
+                                          d_new_moments, moments_bytes, d_out_color);
     if (!why && ctx && !ctx->cfg->have_world) why = "rayn_hip_upload_world has not been called";
     TemporalScene ts;
     memset(&ts, 0, sizeof ts);
@@ -1078,7 +1083,38 @@ int rayn_hip_temporal_accumulate_device(rayn_ctx* ctx, const rayn_frame_params* 
     for (uint32_t i = 0; i < ts.n_hitables; i++)
         ts.hvel[i] = make_float4(w.hitables[i].center_vel.x, w.hitables[i].center_vel.y, w.hitables[i].center_vel.z, w.hitables[i].animated ? 1.0f : 0.0f);
     launch_temporal_accumulate(s, p->width, p->height, *tp, ts, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history, d_new_history,
-                               d_out_color);
+                               d_out_color, moments ? d_prev_moments : nullptr, moments ? d_new_moments : nullptr);
+    return post_enqueued(ctx);
+}
+
+int rayn_hip_temporal_accumulate_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp, const rayn_camera* prev_camera,
+                                        float prev_time_start, const float* d_color, const float* d_normal, const void* d_gbuffer_records,
+                                        const uint32_t* d_gbuffer_object, const void* d_prev_history, void* d_new_history, size_t history_bytes,
+                                        float* d_out_color, void* hip_stream) {
+    return temporal_accumulate(ctx, p, tp, prev_camera, prev_time_start, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history,
+                               d_new_history, history_bytes, false, nullptr, nullptr, 0, d_out_color, hip_stream);
+}
+
+int rayn_hip_temporal_accumulate_moments_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp,
+                                                const rayn_camera* prev_camera, float prev_time_start, const float* d_color, const float* d_normal,
+                                                const void* d_gbuffer_records, const uint32_t* d_gbuffer_object, const void* d_prev_history,
+                                                void* d_new_history, size_t history_bytes, const void* d_prev_moments, void* d_new_moments,
+                                                size_t moments_bytes, float* d_out_color, void* hip_stream) {
+    return temporal_accumulate(ctx, p, tp, prev_camera, prev_time_start, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history,
+                               d_new_history, history_bytes, true, d_prev_moments, d_new_moments, moments_bytes, d_out_color, hip_stream);
+}
+
+int rayn_hip_denoise_temporal_variance_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance,
+                                              float sigma_normal, float sigma_alpha, const float* d_color, const float* d_alpha, const float* d_normal,
+                                              const uint32_t* d_gbuffer_object, const void* d_history, size_t history_bytes, const void* d_moments,
+                                              size_t moments_bytes, float* d_out_color, float* d_out_variance, void* d_scratch, size_t scratch_bytes,
+                                              void* hip_stream) {
+    hipStream_t s;
+    if (int rc = post_enter(ctx, denoise_temporal_check_args(width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, d_color, d_alpha, d_normal,
+                                                             d_gbuffer_object, d_history, history_bytes, d_moments, moments_bytes, d_out_color, d_out_variance,
+                                                             d_scratch, scratch_bytes), hip_stream, &s)) return rc;
+    launch_denoise_temporal_variance(s, width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, d_color, d_alpha, d_normal, d_gbuffer_object,
+                                     d_history, d_moments, d_out_color, d_out_variance, d_scratch);
     return post_enqueued(ctx);
 }
 

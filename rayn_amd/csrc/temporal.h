@@ -44,9 +44,17 @@ struct TemporalScene {
 const char* temporal_check_args(const rayn_frame_params* p, const rayn_temporal_params* tp, const rayn_camera* prev_camera, const float* color,
                                 const float* normal, const void* g_records, const uint32_t* g_object, const void* prev_history,
                                 const void* new_history, size_t history_bytes, const float* out_color);
+// The luminance moments beside a history: a float2 (m1, m2) per pixel in film pixel order, 8 bytes per pixel; 0 for a size the entry rejects.
+size_t temporal_moments_bytes(uint32_t width, uint32_t height);
+// what rayn_hip_temporal_accumulate_moments_device checks on top of temporal_check_args (call that first: p is valid here)
+const char* temporal_moments_check_args(const rayn_frame_params* p, const float* color, const float* normal, const void* g_records,
+                                        const uint32_t* g_object, const void* prev_history, const void* new_history, const void* prev_moments,
+                                        const void* new_moments, size_t moments_bytes, const float* out_color);
+// new_moments == nullptr: the plain accumulate (k_temporal_accumulate<false>); else the moments are carried too
 void launch_temporal_accumulate(hipStream_t s, uint32_t width, uint32_t height, const rayn_temporal_params& tp, const TemporalScene& ts,
                                 const float* color, const float* normal, const void* g_records, const uint32_t* g_object,
-                                const void* prev_history, void* new_history, float* out_color);
+                                const void* prev_history, void* new_history, float* out_color, const void* prev_moments = nullptr,
+                                void* new_moments = nullptr);
 
 } // namespace rayn
 

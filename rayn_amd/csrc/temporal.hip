@@ -31,6 +31,11 @@
 //   W > 0:  h = S / W, nh = N / W, n' = fminf(nh + 1.0f, (float)max_history), a = 1.0f / n', out = h + a * (c - h); out is taken when its
 //   three components are finite.  A rejected projection, W <= 0 and a non-finite out reset the pixel.
 //   History out: A' = (out, n'), B' = (P, t), the object and (nrm, 0).
+// Moments (rayn_hip_temporal_accumulate_moments_device; k_temporal_accumulate<true>): 8 more bytes per pixel, a float2 (m1, m2) in film pixel
+// order beside the history, carried through the same taps.  y = (0.2126f c.r + 0.7152f c.g) + 0.0722f c.b, y2 = y * y.  A pixel that resets
+// writes (y, y2), and (0, 0) when c is not finite.  Otherwise S1 += w * m1_tap, S2 += w * m2_tap over the colour's taps in its loop order,
+// h1 = S1 / W, h2 = S2 / W, m1' = h1 + a * (y - h1), m2' = h2 + a * (y2 - h2) with the colour's a; a non-finite m1' or m2' writes (y, y2)
+// while the colour keeps its blend.  The colour and the 52 B history are the bits of the plain entry.
 // One thread per pixel in 16x16 blocks, 16-byte record loads, as denoise.hip; at most 4 x 3 record loads per pixel: bandwidth-trivial.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -108,13 +113,17 @@ __device__ inline v3 closure3(f3 base, f3 vel, bool on, float t) {
     return on ? v3{base.x + vel.x * t, base.y + vel.y * t, base.z + vel.z * t} : v3{base.x, base.y, base.z};
 }
 
+// MOMENTS: also carry the first and second moment of the luminance through the same taps (rayn_hip_temporal_accumulate_moments_device);
+// the false instantiation reads and writes exactly what the kernel did before the moments existed.
+template <bool MOMENTS>
 __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uint32_t height, uint32_t tiles_x, float max_history, float depth_tolerance,
                                                               float normal_min, TemporalScene ts, const float* __restrict__ color,
                                                               const float* __restrict__ normal, const float4* __restrict__ grec,
                                                               const uint32_t* __restrict__ gobj, const float4* __restrict__ pA,
                                                               const float4* __restrict__ pB, const float4* __restrict__ pN,
                                                               const uint32_t* __restrict__ pO, float4* __restrict__ nA, float4* __restrict__ nB,
-                                                              float4* __restrict__ nN, uint32_t* __restrict__ nO, float* __restrict__ out_color) {
+                                                              float4* __restrict__ nN, uint32_t* __restrict__ nO, float* __restrict__ out_color,
+                                                              const float2* __restrict__ pM, float2* __restrict__ nM) {
     const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
     const uint32_t x = tx * 16u + threadIdx.x, y = ty * 16u + threadIdx.y;
     if (x >= width || y >= height) return;
@@ -127,6 +136,8 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uin
     const bool cfin = fin(c.x) && fin(c.y) && fin(c.z);
     v3 out = c;
     float nn = cfin ? 1.0f : 0.0f;
+    const float lum = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z, lum2 = lum * lum; // the definition's y, y2
+    float m1 = cfin ? lum : 0.0f, m2 = cfin ? lum2 : 0.0f;
     if (cfin && obj != INVALID && pA) {
         v3 Pp = v3{g.x, g.y, g.z};
         const float dt = ts.cur_time - ts.prev_time;
@@ -163,7 +174,7 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uin
             const long long x0 = (long long)__builtin_fminf(__builtin_fmaxf(x0f, -2.0f), 2147483648.0f);
             const long long y0 = (long long)__builtin_fminf(__builtin_fmaxf(y0f, -2.0f), 2147483648.0f);
             const float tol = depth_tolerance * te;
-            float W = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f, N = 0.0f;
+            float W = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f, N = 0.0f, S1 = 0.0f, S2 = 0.0f;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const long long qx = x0 + (k & 1), qy = y0 + (k >> 1);
@@ -183,6 +194,11 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uin
                 Sg += w * a.y;
                 Sb += w * a.z;
                 N += w * a.w;
+                if (MOMENTS) {
+                    const float2 m = pM[q];
+                    S1 += w * m.x;
+                    S2 += w * m.y;
+                }
             }
             if (W > 0.0f) {
                 const float hr = Sr / W, hg = Sg / W, hb = Sb / W, nh = N / W;
@@ -190,7 +206,15 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uin
                 const float al = 1.0f / n1;
                 const float dr = c.x - hr, dg = c.y - hg, db = c.z - hb;
                 const v3 b = v3{hr + al * dr, hg + al * dg, hb + al * db};
-                if (fin(b.x) && fin(b.y) && fin(b.z)) { out = b; nn = n1; }
+                if (fin(b.x) && fin(b.y) && fin(b.z)) {
+                    out = b; nn = n1;
+                    if (MOMENTS) {
+                        const float h1 = S1 / W, h2 = S2 / W;
+                        const float d1 = lum - h1, d2 = lum2 - h2;
+                        const float b1 = h1 + al * d1, b2 = h2 + al * d2;
+                        if (fin(b1) && fin(b2)) { m1 = b1; m2 = b2; } // else (y, y2): an overflow heals on the next frame
+                    }
+                }
             }
         }
     }
@@ -201,6 +225,7 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uin
     nB[p] = g;
     nN[p] = make_float4(nrm.x, nrm.y, nrm.z, 0.0f);
     nO[p] = obj;
+    if (MOMENTS) nM[p] = make_float2(m1, m2);
 }
 
 bool overlap(const void* a, size_t na, const void* b, size_t nb) {
@@ -290,21 +315,50 @@ const char* temporal_check_args(const rayn_frame_params* p, const rayn_temporal_
     return nullptr;
 }
 
+size_t temporal_moments_bytes(uint32_t width, uint32_t height) {
+    if (check_size(width, height)) return 0;
+    return (size_t)(8u * (uint64_t)width * height);
+}
+
+const char* temporal_moments_check_args(const rayn_frame_params* p, const float* color, const float* normal, const void* g_records,
+                                        const uint32_t* g_object, const void* prev_history, const void* new_history, const void* prev_moments,
+                                        const void* new_moments, size_t moments_bytes, const float* out_color) {
+    if (!new_moments) return "null buffer";
+    if (prev_moments && !prev_history) return "previous moments without a previous history";
+    if (prev_history && !prev_moments) return "a previous history needs the previous moments";
+    const size_t need = temporal_moments_bytes(p->width, p->height), hist = temporal_history_bytes(p->width, p->height);
+    if (moments_bytes < need) return "moments smaller than rayn_temporal_moments_bytes(width, height)";
+    if ((uintptr_t)new_moments % 16u || (uintptr_t)prev_moments % 16u) return "moments not 16-byte aligned";
+    const size_t n = (size_t)p->width * p->height;
+    if (overlap(new_moments, need, prev_moments, need)) return "the new moments must not alias the previous ones";
+    const void* in[6] = {color, normal, g_records, g_object, prev_history, prev_moments};
+    const size_t in_bytes[6] = {12u * n, 12u * n, 16u * n, 4u * n, hist, need};
+    for (int i = 0; i < 6; i++)
+        if (overlap(new_moments, need, in[i], in_bytes[i])) return "an output must not alias an input";
+    if (overlap(out_color, 12u * n, prev_moments, need) || overlap(new_history, hist, prev_moments, need)) return "an output must not alias an input";
+    if (overlap(new_moments, need, new_history, hist) || overlap(new_moments, need, out_color, 12u * n)) return "the new moments must not alias another output";
+    return nullptr;
+}
+
 void launch_temporal_accumulate(hipStream_t s, uint32_t width, uint32_t height, const rayn_temporal_params& tp, const TemporalScene& ts,
                                 const float* color, const float* normal, const void* g_records, const uint32_t* g_object,
-                                const void* prev_history, void* new_history, float* out_color) {
+                                const void* prev_history, void* new_history, float* out_color, const void* prev_moments, void* new_moments) {
     const size_t n = (size_t)width * height;
     const float4* pA = (const float4*)prev_history; // null: no previous history
     float4* nA = (float4*)new_history;
     const uint32_t tiles_x = (width + 15u) / 16u, tiles_y = (height + 15u) / 16u;
-    hipLaunchKernelGGL(k_temporal_accumulate, dim3(tiles_x * tiles_y), dim3(16, 16), 0, s, width, height, tiles_x, (float)tp.max_history,
-                       tp.depth_tolerance, tp.normal_min, ts, color, normal, (const float4*)g_records, g_object, pA, pA ? pA + n : nullptr,
-                       pA ? pA + 2u * n : nullptr, pA ? (const uint32_t*)(pA + 3u * n) : nullptr, nA, nA + n, nA + 2u * n, (uint32_t*)(nA + 3u * n),
-                       out_color);
+#define RAYN_TACC(M) hipLaunchKernelGGL(k_temporal_accumulate<M>, dim3(tiles_x * tiles_y), dim3(16, 16), 0, s, width, height, tiles_x, (float)tp.max_history, \
+                       tp.depth_tolerance, tp.normal_min, ts, color, normal, (const float4*)g_records, g_object, pA, pA ? pA + n : nullptr,           \
+                       pA ? pA + 2u * n : nullptr, pA ? (const uint32_t*)(pA + 3u * n) : nullptr, nA, nA + n, nA + 2u * n, (uint32_t*)(nA + 3u * n), \
+                       out_color, (const float2*)prev_moments, (float2*)new_moments)
+    if (new_moments) RAYN_TACC(true); // the moments entry
+    else RAYN_TACC(false);
+#undef RAYN_TACC
 }
 
 } // namespace rayn
 
 extern "C" size_t rayn_gbuffer_scratch_bytes(uint32_t width, uint32_t height) { return rayn::gbuffer_scratch_bytes(width, height); }
 extern "C" size_t rayn_temporal_history_bytes(uint32_t width, uint32_t height) { return rayn::temporal_history_bytes(width, height); }
+extern "C" size_t rayn_temporal_moments_bytes(uint32_t width, uint32_t height) { return rayn::temporal_moments_bytes(width, height); }
 #endif // RAYN_FMA_POLICY == 0

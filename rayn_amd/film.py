@@ -144,6 +144,11 @@ def temporal_history_bytes(width, height):
     return int(lib().rayn_temporal_history_bytes(int(width), int(height)))
 
 
+def temporal_moments_bytes(width, height):
+    """rayn_temporal_moments_bytes: bytes of the luminance moments beside one history (a float2 per pixel; 0 for a size the entries reject)."""
+    return int(lib().rayn_temporal_moments_bytes(int(width), int(height)))
+
+
 def alloc_gbuffer(width, height, device="cuda"):
     """The two planes of a G-buffer as Context.gbuffer fills them: records (n, 4) float32 (Px, Py, Pz, t) and object (n,) int32 (the u32
     object index; a miss is -1 = 0xFFFFFFFF)."""
@@ -458,11 +463,15 @@ class Context:
                                                   C.c_void_p(d_scratch.data_ptr()), d_scratch.numel() * d_scratch.element_size(), C.c_void_p(s)))
 
     def temporal_accumulate(self, params, temporal, d_film, d_gbuffer, d_prev_history, prev_camera, prev_time_start, d_new_history, d_out_color,
-                            stream=None):
+                            stream=None, d_prev_moments=None, d_new_moments=None):
         """rayn_hip_temporal_accumulate_device: blend d_film["color"] (guides: d_film["normal"], the G-buffer d_gbuffer of the same frame)
         with the previous frame's history d_prev_history (a uint8 CUDA tensor of temporal_history_bytes, or None: no history) reprojected
         through prev_camera (an _abi.Camera) at prev_time_start, by the Temporal `temporal`.  Writes the accumulated colour to the float32
-        CUDA tensor d_out_color (width * height * 3 floats) and the new history to d_new_history.  Enqueued on the stream, not waited for."""
+        CUDA tensor d_out_color (width * height * 3 floats) and the new history to d_new_history.  Enqueued on the stream, not waited for.
+
+        With d_new_moments (a uint8 CUDA tensor of temporal_moments_bytes; d_prev_moments beside d_prev_history, None with it) the call
+        goes through rayn_hip_temporal_accumulate_moments_device, which also carries the first and second moment of the luminance through
+        the same reprojection - what denoise_temporal_variance reads; colour and history are the same bits.  Both None: the plain entry."""
         import torch
         n = int(params.width) * int(params.height)
         for key, t, floats in (("color", d_film.get("color"), 3), ("normal", d_film.get("normal"), 3), ("records", d_gbuffer.get("records"), 4)):
@@ -481,11 +490,69 @@ class Context:
         nbytes = d_new_history.numel() if d_prev_history is None else min(d_new_history.numel(), d_prev_history.numel())
         tp = temporal.to_abi()
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        if d_prev_moments is not None or d_new_moments is not None:
+            for name, t in (("d_prev_moments", d_prev_moments), ("d_new_moments", d_new_moments)):
+                if t is not None and not (t.dtype == torch.uint8 and t.is_contiguous()):
+                    raise ValueError(f"{name} must be a contiguous uint8 tensor")
+            if d_new_moments is None:
+                raise ValueError("d_new_moments must be a contiguous uint8 tensor")
+            mbytes = d_new_moments.numel() if d_prev_moments is None else min(d_new_moments.numel(), d_prev_moments.numel())
+            self._chk(self._L.rayn_hip_temporal_accumulate_moments_device(
+                self.h, C.byref(params), C.byref(tp), None if prev_camera is None else C.byref(prev_camera), float(prev_time_start),
+                C.c_void_p(d_film["color"].data_ptr()), C.c_void_p(d_film["normal"].data_ptr()), C.c_void_p(d_gbuffer["records"].data_ptr()),
+                C.c_void_p(obj.data_ptr()), None if d_prev_history is None else C.c_void_p(d_prev_history.data_ptr()),
+                C.c_void_p(d_new_history.data_ptr()), nbytes, None if d_prev_moments is None else C.c_void_p(d_prev_moments.data_ptr()),
+                C.c_void_p(d_new_moments.data_ptr()), mbytes, C.c_void_p(d_out_color.data_ptr()), C.c_void_p(s)))
+            return
         self._chk(self._L.rayn_hip_temporal_accumulate_device(
             self.h, C.byref(params), C.byref(tp), None if prev_camera is None else C.byref(prev_camera), float(prev_time_start),
             C.c_void_p(d_film["color"].data_ptr()), C.c_void_p(d_film["normal"].data_ptr()), C.c_void_p(d_gbuffer["records"].data_ptr()),
             C.c_void_p(obj.data_ptr()), None if d_prev_history is None else C.c_void_p(d_prev_history.data_ptr()),
             C.c_void_p(d_new_history.data_ptr()), nbytes, C.c_void_p(d_out_color.data_ptr()), C.c_void_p(s)))
+
+    def denoise_temporal_variance(self, width, height, d_film, d_gbuffer, d_history, d_moments, d_out_color, denoise, d_out_variance=None,
+                                  d_scratch=None, stream=None):
+        """rayn_hip_denoise_temporal_variance_device: the variance-guided a-trous denoiser (VarianceDenoise `denoise`) of a temporally
+        accumulated colour.  d_film["color"] is the ACCUMULATED colour (what temporal_accumulate wrote to d_out_color), d_film["normal"] /
+        d_film["alpha"] the film's guides (a guide whose sigma is 0 may be absent), d_gbuffer the frame's G-buffer (its "object" plane is
+        read), d_history / d_moments the NEW history and moments of that accumulate.  A pixel's variance comes from its moments once its
+        history is 4 frames long, (m2 - m1^2) / n, and from the 7x7 neighbourhood of the accumulated luminance on the same object before
+        that - so with Temporal(max_history < 4) only the spatial estimate is ever used.  Writes the float32 CUDA tensor d_out_color
+        (width * height * 3 floats) and, when given, d_out_variance (width * height floats; NaN where there was no estimate).  d_scratch: a
+        CUDA tensor of at least denoise_variance_scratch_bytes(width, height) bytes, allocated here when None.  Enqueued on the stream,
+        not waited for.  Recommended for sequences: VarianceDenoise(1, 4.0, 0.4, 0.3), 0.46x the raw frame where Temporal() alone gives 0.49x."""
+        import torch
+        n = int(width) * int(height)
+        if not (d_out_color.dtype == torch.float32 and d_out_color.is_contiguous() and d_out_color.numel() >= 3 * n):
+            raise ValueError(f"d_out_color must be a contiguous float32 tensor of at least {3 * n} floats")
+        if d_out_variance is not None and not (d_out_variance.dtype == torch.float32 and d_out_variance.is_contiguous() and d_out_variance.numel() >= n):
+            raise ValueError(f"d_out_variance must be a contiguous float32 tensor of at least {n} floats")
+        ptrs = []
+        for key, floats in (("color", 3), ("alpha", 1), ("normal", 3)):
+            t = d_film.get(key)
+            if t is None:
+                ptrs.append(None)
+                continue
+            if not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= floats * n):
+                raise ValueError(f"d_film[{key!r}] must be a contiguous float32 tensor of at least {floats * n} floats")
+            ptrs.append(C.c_void_p(t.data_ptr()))
+        obj = d_gbuffer.get("object")
+        if obj is None or not (obj.dtype == torch.int32 and obj.is_contiguous() and obj.numel() >= n):
+            raise ValueError(f"d_gbuffer['object'] must be a contiguous int32 tensor of at least {n} elements")
+        for name, t in (("d_history", d_history), ("d_moments", d_moments)):
+            if t is None or not (t.dtype == torch.uint8 and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous uint8 tensor")
+        if d_scratch is None:
+            d_scratch = torch.empty(max(denoise_variance_scratch_bytes(width, height), 1), dtype=torch.uint8, device=d_out_color.device)
+        if not d_scratch.is_contiguous():
+            raise ValueError("d_scratch must be contiguous")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._chk(self._L.rayn_hip_denoise_temporal_variance_device(
+            self.h, int(width), int(height), int(denoise.iterations), float(denoise.sigma_luminance), float(denoise.sigma_normal),
+            float(denoise.sigma_alpha), *ptrs, C.c_void_p(obj.data_ptr()), C.c_void_p(d_history.data_ptr()), d_history.numel(),
+            C.c_void_p(d_moments.data_ptr()), d_moments.numel(), C.c_void_p(d_out_color.data_ptr()),
+            None if d_out_variance is None else C.c_void_p(d_out_variance.data_ptr()), C.c_void_p(d_scratch.data_ptr()),
+            d_scratch.numel() * d_scratch.element_size(), C.c_void_p(s)))
 
     @staticmethod
     def _prog_state(params, d_state):
@@ -865,29 +932,42 @@ class Film:
 
         With `denoise` (a Denoise), every frame's Color image is made from the denoised Color and written as _color_denoised.png, as
         save_to(..., denoise=denoise) does: the denoiser's kernels go on the render stream ahead of that frame's post-process kernels,
-        and its scratch and denoised plane are allocated once.  A VarianceDenoise raises ValueError: a sequence's frames are plain
-        renders and carry no variance.
+        and its scratch and denoised plane are allocated once.  A VarianceDenoise without `temporal` raises ValueError: a sequence's
+        frames are plain renders and carry no variance.
 
         With `temporal` (a Temporal, an extension), every frame's Color is accumulated over the frames before it: after the render, the
         frame's G-buffer pass and the temporal accumulate go on the render stream, the Color image is made from the accumulated colour and
         written as _color_temporal.png; with `denoise` as well the a-trous filter runs on the accumulated colour and the file is
         _color_temporal_denoised.png.  The two histories, the G-buffer and the scratch are allocated once.  The first frame of a call has
         no history; frames that are not consecutive still reproject, over whatever time lies between their starts.  The film's channels
-        stay what the integrator wrote.  temporal=None is the path described above, unchanged."""
+        stay what the integrator wrote.  temporal=None is the path described above, unchanged.
+
+        With `temporal` and a VarianceDenoise as `denoise`, the accumulate also carries the luminance moments (two more buffers, allocated
+        once), and the variance-guided filter runs on the accumulated colour with a variance estimated from them
+        (Context.denoise_temporal_variance); the file is _color_temporal_denoised.png.  The filtered colour is not fed back into the
+        history.  The film needs its Alpha channel when sigma_alpha != 0 (WorldNormal it needs anyway).  Recommended for sequences
+        (DESIGN.md section 8): VarianceDenoise(1, 4.0, 0.4, 0.3), 0.46x the raw frame where Temporal() alone gives 0.49x."""
         import concurrent.futures as cf
         import torch
-        if isinstance(denoise, VarianceDenoise):
+        variance = isinstance(denoise, VarianceDenoise)
+        if variance and temporal is None:
             raise ValueError("render_sequence renders plain frames: VarianceDenoise needs the state of a progressive render")
         frames = [int(f) for f in frames]
         jobs = self._save_jobs(write_channels, transparent_background)
         if denoise is not None:
-            denoise = self._denoise_params(denoise) if ChannelKind.Color in write_channels else None
+            if variance:  # its guides are required, not switched off: checked with the temporal arguments below
+                self._denoise_params(denoise)
+                denoise = denoise if ChannelKind.Color in write_channels else None
+            else:
+                denoise = self._denoise_params(denoise) if ChannelKind.Color in write_channels else None
             jobs = [(kind, bpp, "color_denoised" if denoise is not None and kind == ChannelKind.Color else suffix) for kind, bpp, suffix in jobs]
         if temporal is not None:
             if not isinstance(temporal, Temporal):
                 raise ValueError(f"temporal must be a Temporal, got {temporal!r}")
             if ChannelKind.Color not in self.channel_kinds or ChannelKind.WorldNormal not in self.channel_kinds:
                 raise ValueError("temporal accumulation needs the film's Color and WorldNormal channels")
+            if variance and denoise is not None and float(denoise.sigma_alpha) != 0.0 and ChannelKind.Alpha not in self.channel_kinds:
+                raise ValueError("variance-guided denoising of a temporal sequence needs the film's Alpha channel when sigma_alpha != 0")
             if ChannelKind.Color not in write_channels:
                 temporal = None
             else:
@@ -928,7 +1008,10 @@ class Film:
                 d_img = [torch.empty(h * w * bpp, dtype=torch.uint8, device=self.device) for _, bpp, _ in jobs]
                 if denoise is not None:
                     d_denoised = torch.empty(w * h, 3, dtype=torch.float32, device=self.device)
-                    d_scratch = torch.empty(denoise_scratch_bytes(w, h), dtype=torch.uint8, device=self.device)
+                    d_scratch = torch.empty((denoise_variance_scratch_bytes if variance else denoise_scratch_bytes)(w, h), dtype=torch.uint8, device=self.device)
+                d_mom = [None, None]
+                if temporal is not None and variance and denoise is not None:
+                    d_mom = [torch.empty(temporal_moments_bytes(w, h), dtype=torch.uint8, device=self.device) for _ in range(2)]
                 if temporal is not None:
                     d_gbuf = alloc_gbuffer(w, h, self.device)
                     d_gscratch = torch.empty(gbuffer_scratch_bytes(w, h), dtype=torch.uint8, device=self.device)
@@ -965,11 +1048,16 @@ class Film:
                         self.ctx.gbuffer(p, d_gbuf, d_gscratch, stream.cuda_stream)
                         self.ctx.temporal_accumulate(p, temporal, d_film, d_gbuf, None if prev_start is None else d_hist[(i + 1) % 2],
                                                      None if prev_start is None else desc.camera, 0.0 if prev_start is None else prev_start,
-                                                     d_hist[i % 2], d_accum, stream.cuda_stream)
+                                                     d_hist[i % 2], d_accum, stream.cuda_stream,
+                                                     None if prev_start is None else d_mom[(i + 1) % 2], d_mom[i % 2])
                         prev_start = p.time_start
                         d_shown = dict(d_film, color=d_accum)
                     if denoise is not None:
-                        self.ctx.denoise(w, h, d_shown, d_denoised, denoise, d_scratch, stream.cuda_stream)
+                        if variance:
+                            self.ctx.denoise_temporal_variance(w, h, d_shown, d_gbuf, d_hist[i % 2], d_mom[i % 2], d_denoised, denoise, None, d_scratch,
+                                                               stream.cuda_stream)
+                        else:
+                            self.ctx.denoise(w, h, d_shown, d_denoised, denoise, d_scratch, stream.cuda_stream)
                         d_shown = dict(d_film, color=d_denoised)
                     for (kind, _, suffix), d, hbuf in zip(jobs, d_img, h_img[slot]):
                         src = d_shown if kind == ChannelKind.Color else d_film
