@@ -214,6 +214,30 @@ extern "C" {
         scratch_bytes: usize,
         hip_stream: *mut c_void,
     ) -> i32;
+    /// the same filter with SVGF's feedback edge: pass 0 is blended into the history's colour with strength `feedback` (0 = the entry above)
+    pub fn rayn_hip_denoise_temporal_variance_feedback_device(
+        ctx: *mut RaynCtx,
+        width: u32,
+        height: u32,
+        iterations: u32,
+        sigma_luminance: f32,
+        sigma_normal: f32,
+        sigma_alpha: f32,
+        d_color: *const f32,
+        d_alpha: *const f32,
+        d_normal: *const f32,
+        d_gbuffer_object: *const u32,
+        d_history: *mut c_void,
+        history_bytes: usize,
+        d_moments: *const c_void,
+        moments_bytes: usize,
+        d_out_color: *mut f32,
+        d_out_variance: *mut f32,
+        d_scratch: *mut c_void,
+        scratch_bytes: usize,
+        feedback: f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
 }
 
 /// Start-up layout check against the library as compiled (indices: include/rayn_hip.h, rayn_hip_sizeof).

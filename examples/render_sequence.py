@@ -2,7 +2,7 @@
 (rayn_amd.setup, 1280x720, SAMPLES = 2 (8 spp), 3 bounces, the BlackmanHarris filter, 16x16 tiles) rendered frame by frame and
 written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints per-frame render times and frames/s.
 
-    python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise [atrous|variance]] [--temporal]
+    python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise [atrous|variance]] [--temporal] [--feedback B]
 
 --compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
 the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
@@ -11,7 +11,9 @@ Color before its post-process and writes _color_denoised.png instead of _color.p
 frames before it (rayn_amd.Temporal() defaults, an extension: a primary-hit G-buffer pass and a reprojection per frame) under a camera whose
 origin drifts, and writes _color_temporal.png (_color_temporal_denoised.png with --denoise).  --temporal --denoise variance filters the
 accumulated colour with the variance-guided denoiser instead, its variance estimated from luminance moments the accumulate carries along
-(rayn_amd.VarianceDenoise(1, 4.0, 0.4, 0.3), the setting recommended for sequences); it needs --temporal."""
+(rayn_amd.VarianceDenoise(1, 4.0, 0.4, 0.3), the setting recommended for sequences); it needs --temporal.  --feedback B (in [0, 1],
+default 0 = off) also blends the output of every frame's first a-trous pass into the history the next frame reprojects, with strength B
+(rayn_amd.Temporal(feedback=B)); it needs --temporal --denoise variance."""
 import argparse
 import os
 import sys
@@ -63,13 +65,20 @@ def main():
                     help="denoise every frame's Color: atrous (rayn_amd.Denoise() defaults; what a bare --denoise means) or variance "
                          "(rayn_amd.VarianceDenoise(1, 4.0, 0.4, 0.3) on the temporally accumulated colour; needs --temporal)")
     ap.add_argument("--temporal", action="store_true", help="accumulate every frame's Color over the frames before it (rayn_amd.Temporal() defaults); the camera's origin drifts")
+    ap.add_argument("--feedback", type=float, default=0.0, metavar="B",
+                    help="strength in [0, 1] with which every frame's first a-trous pass is fed back into the temporal history (0 = off); "
+                         "needs --temporal --denoise variance")
     args = ap.parse_args()
     if (args.denoise or args.temporal) and args.compare_loop:
         ap.error("--compare-loop compares with the host post-process, which has neither a denoiser nor a temporal accumulation: use one or the other")
     if args.denoise == "variance" and not args.temporal:
         ap.error("--denoise variance estimates its variance from the temporal accumulation: add --temporal")
+    if args.feedback != 0.0 and not (args.temporal and args.denoise == "variance"):
+        ap.error("--feedback feeds the variance-guided filter's first pass back into the temporal history: add --temporal --denoise variance")
+    if not 0.0 <= args.feedback <= 1.0:
+        ap.error("--feedback must be in [0, 1]")
     denoise = {None: None, "atrous": R.Denoise(), "variance": R.VarianceDenoise(1, 4.0, 0.4, 0.3)}[args.denoise]
-    temporal = R.Temporal() if args.temporal else None
+    temporal = R.Temporal(feedback=args.feedback) if args.temporal else None
     first, end = (int(x) for x in args.frames.split(":"))
     frames = list(range(first, end))
     base = f"{SAMPLES * 4}_spp"

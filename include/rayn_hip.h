@@ -522,8 +522,9 @@ int rayn_hip_temporal_accumulate_moments_device(rayn_ctx* ctx, const rayn_frame_
  *   when it is inside the image, obj_q == obj_p, n'_q >= 1 and c_q has three finite components:  k += 1.0f, s1 += l_q, s2 += l_q * l_q;
  *   mu = s1 / k, d = s2 / k - mu * mu, v = d > 0 ? d : 0.0f.
  *   A v that is not finite makes p not guided.
- * Then the passes, the outputs and the parameter ranges of rayn_hip_denoise_variance_device, unchanged.  The filtered colour is NOT fed
- * back into the history (SVGF feeds its first pass back; left out here).  All f32, no contraction, IEEE division.
+ * Then the passes, the outputs and the parameter ranges of rayn_hip_denoise_variance_device, unchanged.  This entry does NOT feed the
+ * filtered colour back into the history (SVGF feeds its first pass back; rayn_hip_denoise_temporal_variance_feedback_device below does).
+ * All f32, no contraction, IEEE division.
  * Enqueued on 'hip_stream' (NULL = the ctx's own stream; not waited for), on the ctx's GPU (devices[0] of a multi-device ctx).  DEVICE
  * pointers: d_color / d_normal 3 floats per pixel, d_alpha 1, d_gbuffer_object one u32, d_out_color 3, d_out_variance 1 (may be NULL);
  * d_history and d_moments 16-byte aligned, at least rayn_temporal_history_bytes / rayn_temporal_moments_bytes; d_scratch 16-byte aligned, at
@@ -536,6 +537,27 @@ int rayn_hip_denoise_temporal_variance_device(rayn_ctx* ctx, uint32_t width, uin
                                               const float* d_normal, const uint32_t* d_gbuffer_object, const void* d_history, size_t history_bytes,
                                               const void* d_moments, size_t moments_bytes, float* d_out_color, float* d_out_variance,
                                               void* d_scratch, size_t scratch_bytes, void* hip_stream);
+
+/* rayn_hip_denoise_temporal_variance_device with SVGF's feedback edge: the output of the FIRST a-trous pass is blended into the colour of
+ * the history, so that the next frame's accumulate reprojects what this frame's filter cleaned.  The arguments of that entry, except that
+ * d_history is in/out and that 'feedback' (beta) is the strength.  The records are packed and the 'iterations' passes run exactly as there:
+ * for every beta, d_out_color and d_out_variance are bit for bit what that entry writes from the same inputs; the history write is a side
+ * effect only.  All f32, no contraction, under either mul_add policy.
+ *   beta == 0 writes nothing to the history: it is that entry (no c + 0 * x is evaluated, which would turn -0.0 into +0.0).
+ *   beta > 0: take pass 0 - step 1, the pass that reads the packed records.  For every pixel p of the image, with c = p's colour in pass 0's
+ *   input record (the accumulated colour d_color) and (c', v') what pass 0 computes for p:
+ *     v' is NaN (p not guided on entry, or dropped by pass 0's overflow rule): the history is untouched.
+ *     Otherwise, per component, d = c' - c, m = beta * d, fb = c + m.  If fb has three finite components, plane A of the history gets
+ *     (fb.r, fb.g, fb.b) and its fourth component n' keeps its bits; if not, the history is untouched.
+ *   Planes B, normal and object of the history are never written, nor are the moments (SVGF keeps raw moments too).  A history pixel with
+ *   n' >= 1 keeps a finite colour.  With iterations == 1 pass 0 is also the last pass: it writes the planar outputs and the history.
+ * RAYN_ERR_INVALID_ARG with a last error text for everything rayn_hip_denoise_temporal_variance_device rejects, for a beta that is not
+ * finite or outside [0, 1], and for a history that overlaps anything else: it is an output here.  Nothing is written then. */
+int rayn_hip_denoise_temporal_variance_feedback_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance,
+                                                       float sigma_normal, float sigma_alpha, const float* d_color, const float* d_alpha,
+                                                       const float* d_normal, const uint32_t* d_gbuffer_object, void* d_history, size_t history_bytes,
+                                                       const void* d_moments, size_t moments_bytes, float* d_out_color, float* d_out_variance,
+                                                       void* d_scratch, size_t scratch_bytes, float feedback, void* hip_stream);
 
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,

@@ -42,6 +42,7 @@ EXPORTS = [
     "rayn_denoise_variance_scratch_bytes", "rayn_hip_denoise_variance_device",
     "rayn_gbuffer_scratch_bytes", "rayn_hip_gbuffer_device", "rayn_temporal_history_bytes", "rayn_hip_temporal_accumulate_device",
     "rayn_temporal_moments_bytes", "rayn_hip_temporal_accumulate_moments_device", "rayn_hip_denoise_temporal_variance_device",
+    "rayn_hip_denoise_temporal_variance_feedback_device",
 ]
 
 
@@ -121,6 +122,8 @@ def lib():
                                                                   + [vp] * 6 + [C.c_size_t, vp, vp, C.c_size_t, vp, vp])
         L.rayn_hip_denoise_temporal_variance_device.argtypes = ([vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float] + [vp] * 5
                                                                 + [C.c_size_t, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp])
+        L.rayn_hip_denoise_temporal_variance_feedback_device.argtypes = ([vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float] + [vp] * 5
+                                                                         + [C.c_size_t, vp, C.c_size_t, vp, vp, vp, C.c_size_t, C.c_float, vp])
         L.rayn_sets_1d.restype = C.c_uint32
         L.rayn_sets_1d.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_sets_2d.restype = C.c_uint32

@@ -2,7 +2,9 @@
 // SVGF's variance estimate for sequences (Schied et al., HPG 2017, section 4.2) in front of the passes of denoise_variance.hip.  An
 // extension: rayn has neither.  It runs downstream of the temporal accumulate: it reads the accumulated colour, the film's Alpha and
 // WorldNormal, the frame's G-buffer objects, the new history (for the history length n' in A.w) and the new luminance moments, and
-// writes a new Color plane and, optionally, the filtered variance.  The history is not touched: the filtered colour is not fed back.
+// writes a new Color plane and, optionally, the filtered variance.  That entry does not touch the history: the filtered colour is not fed
+// back.  rayn_hip_denoise_temporal_variance_feedback_device is the same filter with SVGF's feedback edge: pass 0 (k_vatrous<.., true>,
+// denoise_variance.hip) also blends its colour into plane A of the history, which the next frame's accumulate reprojects.
 //
 // The definition (include/rayn_hip.h; tests/temporal_variance_np.py restates it in numpy and the tests compare bit
 // for bit).  l_x = (0.2126f c_x.r + 0.7152f c_x.g) + 0.0722f c_x.b of the accumulated colour.  Pixel p is NOT GUIDED (v = NaN: it passes
@@ -152,16 +154,50 @@ const char* denoise_temporal_check_args(uint32_t width, uint32_t height, uint32_
     return nullptr;
 }
 
-void launch_denoise_temporal_variance(hipStream_t s, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance,
-                                      float sigma_normal, float sigma_alpha, const float* color, const float* alpha, const float* normal,
-                                      const uint32_t* g_object, const void* history, const void* moments, float* out_color, float* out_variance,
-                                      void* scratch) {
+// history: read by the pack kernel (n'), written by pass 0 when feedback != 0 - kernels of one stream, in that order
+static void launch_tvdenoise(hipStream_t s, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance, float sigma_normal, float sigma_alpha,
+                             const float* color, const float* alpha, const float* normal, const uint32_t* g_object, const void* history,
+                             void* history_out, const void* moments, float* out_color, float* out_variance, void* scratch, float feedback) {
     const uint32_t terms = vatrous_terms(sigma_luminance, sigma_normal, sigma_alpha);
     const uint32_t blocks_x = (width + 15u) / 16u, blocks_y = (height + 15u) / 16u;
     hipLaunchKernelGGL(k_tvdenoise_pack, dim3(blocks_x * blocks_y), dim3(TILE, TILE), 0, s, width, height, blocks_x, color,
                        (terms & VATROUS_ALPHA) ? alpha : nullptr, (terms & VATROUS_NORMAL) ? normal : nullptr, g_object, (const float4*)history,
                        (const float2*)moments, (float4*)scratch, vatrous_guides(terms, width, height, scratch));
-    launch_vatrous_passes(s, width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, out_color, out_variance, scratch);
+    launch_vatrous_passes(s, width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, out_color, out_variance, scratch, history_out, feedback);
+}
+
+void launch_denoise_temporal_variance(hipStream_t s, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance,
+                                      float sigma_normal, float sigma_alpha, const float* color, const float* alpha, const float* normal,
+                                      const uint32_t* g_object, const void* history, const void* moments, float* out_color, float* out_variance,
+                                      void* scratch) {
+    launch_tvdenoise(s, width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, color, alpha, normal, g_object, history, nullptr, moments,
+                     out_color, out_variance, scratch, 0.0f);
+}
+
+const char* denoise_temporal_feedback_check_args(uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance, float sigma_normal,
+                                                 float sigma_alpha, const float* color, const float* alpha, const float* normal,
+                                                 const uint32_t* g_object, const void* history, size_t history_bytes, const void* moments,
+                                                 size_t moments_bytes, const float* out_color, const float* out_variance, const void* scratch,
+                                                 size_t scratch_bytes, float feedback) {
+    if (const char* why = denoise_temporal_check_args(width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, color, alpha, normal, g_object,
+                                                      history, history_bytes, moments, moments_bytes, out_color, out_variance, scratch, scratch_bytes))
+        return why;
+    if (!(feedback >= 0.0f && feedback <= 1.0f)) return "feedback must be finite and in [0, 1]";
+    // the history is an output here: the checks above keep it off the outputs and the scratch; these keep it off the other inputs
+    const size_t n = (size_t)width * height, hist = temporal_history_bytes(width, height);
+    const void* in[5] = {color, alpha, normal, g_object, moments};
+    const size_t in_bytes[5] = {12u * n, 4u * n, 12u * n, 4u * n, temporal_moments_bytes(width, height)};
+    for (int i = 0; i < 5; i++)
+        if (overlap(history, hist, in[i], in_bytes[i])) return "the history must not alias an input";
+    return nullptr;
+}
+
+void launch_denoise_temporal_variance_feedback(hipStream_t s, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance,
+                                               float sigma_normal, float sigma_alpha, const float* color, const float* alpha, const float* normal,
+                                               const uint32_t* g_object, void* history, const void* moments, float* out_color, float* out_variance,
+                                               void* scratch, float feedback) {
+    launch_tvdenoise(s, width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, color, alpha, normal, g_object, history, history, moments,
+                     out_color, out_variance, scratch, feedback);
 }
 
 } // namespace rayn

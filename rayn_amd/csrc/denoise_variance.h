@@ -36,9 +36,10 @@ inline float4* vatrous_guides(uint32_t terms, uint32_t width, uint32_t height, v
 }
 bool vatrous_sigma_ok(float sigma);
 // Enqueue the `iterations` passes on records a pack kernel has written: A = (r, g, b, v or NaN) in plane 0 of the scratch, B = (nx, ny,
-// nz, alpha) in vatrous_guides.  The last pass writes out_color and, when given, out_variance.
+// nz, alpha) in vatrous_guides.  The last pass writes out_color and, when given, out_variance.  With `history` (a temporal history, plane A
+// first) and feedback != 0, pass 0 also blends its colour into plane A's (r, g, b) with that strength; the outputs do not depend on it.
 void launch_vatrous_passes(hipStream_t s, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance, float sigma_normal,
-                           float sigma_alpha, float* out_color, float* out_variance, void* scratch);
+                           float sigma_alpha, float* out_color, float* out_variance, void* scratch, void* history = nullptr, float feedback = 0.0f);
 
 // ---- the same filter on a temporally accumulated colour (denoise_temporal.hip; rayn_hip_denoise_temporal_variance_device) -----------------
 const char* denoise_temporal_check_args(uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance, float sigma_normal,
@@ -49,5 +50,16 @@ void launch_denoise_temporal_variance(hipStream_t s, uint32_t width, uint32_t he
                                       float sigma_normal, float sigma_alpha, const float* color, const float* alpha, const float* normal,
                                       const uint32_t* g_object, const void* history, const void* moments, float* out_color, float* out_variance,
                                       void* scratch);
+// rayn_hip_denoise_temporal_variance_feedback_device: the checks above, the strength, and the history as an output that overlaps nothing
+const char* denoise_temporal_feedback_check_args(uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance, float sigma_normal,
+                                                 float sigma_alpha, const float* color, const float* alpha, const float* normal,
+                                                 const uint32_t* g_object, const void* history, size_t history_bytes, const void* moments,
+                                                 size_t moments_bytes, const float* out_color, const float* out_variance, const void* scratch,
+                                                 size_t scratch_bytes, float feedback);
+// the same kernels; with feedback != 0 pass 0 writes plane A's colour of `history` (feedback == 0: nothing writes it)
+void launch_denoise_temporal_variance_feedback(hipStream_t s, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance,
+                                               float sigma_normal, float sigma_alpha, const float* color, const float* alpha, const float* normal,
+                                               const uint32_t* g_object, void* history, const void* moments, float* out_color, float* out_variance,
+                                               void* scratch, float feedback);
 
 } // namespace rayn

@@ -76,14 +76,22 @@ __global__ void __launch_bounds__(256) k_vdenoise_pack(VarGeom g, const float* _
     }
 }
 
+// What pass 0 of rayn_hip_denoise_temporal_variance_feedback_device gets on top of a pass's arguments: plane A of the temporal history and
+// the strength.  The plain pass carries nothing, so its arguments and its code are what they were before there was a feedback.
+template <bool FEEDBACK> struct VatrousFeedback {};
+template <> struct VatrousFeedback<true> { float4* hist; float beta; };
+
 // One pass with step `step` (a power of two <= 128).  Blocks of 16x16 threads, one per 16x16 block of the image, in a 1-D grid
 // (row-major, blocks_x per row).  TERMS: which of the luminance / normal / alpha terms are on.  LAST: write the planar colour (and the
-// variance plane, when there is one) instead of the next record plane.
-template <uint32_t TERMS, bool LAST>
+// variance plane, when there is one) instead of the next record plane.  FEEDBACK (launched for pass 0, step 1, only): also blend the
+// pass's colour into the history, fb = c + beta * (c' - c) per component, where v' is not NaN and fb is finite; n' in .w keeps its bits:
+// three dword stores, which compile to one global_store_dwordx3, and no read of the history.  The taps come from `a`, never from the
+// history, so the write races with no neighbour's read.
+template <uint32_t TERMS, bool LAST, bool FEEDBACK = false>
 __global__ void __launch_bounds__(256) k_vatrous(uint32_t width, uint32_t height, uint32_t blocks_x, uint32_t step, float sigma_luminance,
                                                  float sigma_normal, float sigma_alpha, const float4* __restrict__ a,
                                                  const float4* __restrict__ b, float4* __restrict__ a_out, float* __restrict__ out_color,
-                                                 float* __restrict__ out_variance) {
+                                                 float* __restrict__ out_variance, VatrousFeedback<FEEDBACK> fb = {}) {
     const uint32_t by = blockIdx.x / blocks_x, bx = blockIdx.x - by * blocks_x;
     const uint32_t x = bx * 16u + threadIdx.x, y = by * 16u + threadIdx.y;
     if (x >= width || y >= height) return;
@@ -160,6 +168,19 @@ __global__ void __launch_bounds__(256) k_vatrous(uint32_t width, uint32_t height
         v = V / (W * W);
         if (!(finite3(r, g, bl) && __builtin_isfinite(v))) v = quiet_nan(); // an overflow: not guided from here on
     }
+    if constexpr (FEEDBACK) {
+        if (v == v) { // not guided on entry, or dropped by the overflow rule: the history keeps its colour
+            const float dr = r - ap.x, dg = g - ap.y, db = bl - ap.z;
+            const float mr = fb.beta * dr, mg = fb.beta * dg, mb = fb.beta * db;
+            const float fr = ap.x + mr, fg = ap.y + mg, fbl = ap.z + mb;
+            if (finite3(fr, fg, fbl)) {
+                float* hp = (float*)(fb.hist + p); // 16-byte aligned; .w = n' is not written
+                hp[0] = fr;
+                hp[1] = fg;
+                hp[2] = fbl;
+            }
+        }
+    }
     if (LAST) {
         const size_t f = (size_t)p * 3u;
         out_color[f] = r;
@@ -171,14 +192,21 @@ __global__ void __launch_bounds__(256) k_vatrous(uint32_t width, uint32_t height
     }
 }
 
+// hist != nullptr: the feedback variant (the caller passes it for pass 0 only)
 template <uint32_t TERMS>
 void launch_pass(hipStream_t s, bool last, dim3 grid, uint32_t width, uint32_t height, uint32_t blocks_x, uint32_t step, float sl, float sn,
-                 float sa, const float4* a, const float4* b, float4* a_out, float* out_color, float* out_variance) {
+                 float sa, const float4* a, const float4* b, float4* a_out, float* out_color, float* out_variance, float4* hist, float beta) {
     const dim3 block(16, 16);
-    if (last)
-        hipLaunchKernelGGL((k_vatrous<TERMS, true>), grid, block, 0, s, width, height, blocks_x, step, sl, sn, sa, a, b, a_out, out_color, out_variance);
+    if (hist) {
+        const VatrousFeedback<true> fb{hist, beta};
+        if (last)
+            hipLaunchKernelGGL((k_vatrous<TERMS, true, true>), grid, block, 0, s, width, height, blocks_x, step, sl, sn, sa, a, b, a_out, out_color, out_variance, fb);
+        else
+            hipLaunchKernelGGL((k_vatrous<TERMS, false, true>), grid, block, 0, s, width, height, blocks_x, step, sl, sn, sa, a, b, a_out, out_color, out_variance, fb);
+    } else if (last)
+        hipLaunchKernelGGL((k_vatrous<TERMS, true>), grid, block, 0, s, width, height, blocks_x, step, sl, sn, sa, a, b, a_out, out_color, out_variance, VatrousFeedback<false>{});
     else
-        hipLaunchKernelGGL((k_vatrous<TERMS, false>), grid, block, 0, s, width, height, blocks_x, step, sl, sn, sa, a, b, a_out, out_color, out_variance);
+        hipLaunchKernelGGL((k_vatrous<TERMS, false>), grid, block, 0, s, width, height, blocks_x, step, sl, sn, sa, a, b, a_out, out_color, out_variance, VatrousFeedback<false>{});
 }
 
 } // namespace
@@ -215,8 +243,9 @@ const char* denoise_variance_check_args(const rayn_frame_params* p, uint32_t ite
 
 // The passes of k_vatrous on packed records: plane 0 of the scratch holds A = (r, g, b, v or NaN), plane 2 B = (nx, ny, nz, alpha) when a
 // guide is on; plane 1 is the other half of the ping-pong.  Shared by every entry that packs a variance (this file, denoise_temporal.hip).
+// With a history and feedback != 0, pass 0 is the feedback variant; every other pass, and every pass without them, is the plain kernel.
 void launch_vatrous_passes(hipStream_t s, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance, float sigma_normal,
-                           float sigma_alpha, float* out_color, float* out_variance, void* scratch) {
+                           float sigma_alpha, float* out_color, float* out_variance, void* scratch, void* history, float feedback) {
     const uint32_t n = width * height;
     const uint32_t terms = vatrous_terms(sigma_luminance, sigma_normal, sigma_alpha);
     float4* plane[2] = {(float4*)scratch, (float4*)scratch + n};
@@ -228,7 +257,8 @@ void launch_vatrous_passes(hipStream_t s, uint32_t width, uint32_t height, uint3
         const float4* in = plane[i & 1u];
         float4* out = plane[(i + 1u) & 1u];
         const uint32_t step = 1u << i;
-#define RAYN_VPASS(T) launch_pass<T>(s, last, grid, width, height, blocks_x, step, sigma_luminance, sigma_normal, sigma_alpha, in, guides, out, out_color, out_variance)
+        float4* hist = (i == 0 && feedback != 0.0f) ? (float4*)history : nullptr;
+#define RAYN_VPASS(T) launch_pass<T>(s, last, grid, width, height, blocks_x, step, sigma_luminance, sigma_normal, sigma_alpha, in, guides, out, out_color, out_variance, hist, feedback)
         switch (terms) {
         case 0: RAYN_VPASS(0); break;
         case 1: RAYN_VPASS(1); break;

@@ -1118,6 +1118,20 @@ int rayn_hip_denoise_temporal_variance_device(rayn_ctx* ctx, uint32_t width, uin
     return post_enqueued(ctx);
 }
 
+int rayn_hip_denoise_temporal_variance_feedback_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance,
+                                                       float sigma_normal, float sigma_alpha, const float* d_color, const float* d_alpha,
+                                                       const float* d_normal, const uint32_t* d_gbuffer_object, void* d_history, size_t history_bytes,
+                                                       const void* d_moments, size_t moments_bytes, float* d_out_color, float* d_out_variance,
+                                                       void* d_scratch, size_t scratch_bytes, float feedback, void* hip_stream) {
+    hipStream_t s;
+    if (int rc = post_enter(ctx, denoise_temporal_feedback_check_args(width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, d_color, d_alpha,
+                                                                      d_normal, d_gbuffer_object, d_history, history_bytes, d_moments, moments_bytes, d_out_color,
+                                                                      d_out_variance, d_scratch, scratch_bytes, feedback), hip_stream, &s)) return rc;
+    launch_denoise_temporal_variance_feedback(s, width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, d_color, d_alpha, d_normal,
+                                              d_gbuffer_object, d_history, d_moments, d_out_color, d_out_variance, d_scratch, feedback);
+    return post_enqueued(ctx);
+}
+
 // the checks every rayn_hip_progressive_* entry shares; on success *L is the state's layout
 static const char* progressive_geometry(const rayn_frame_params* p, const void* d_state, size_t state_bytes, ProgLayout* L) {
     const char* why = progressive_check_geometry(p, d_state, state_bytes);

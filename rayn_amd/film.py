@@ -111,15 +111,22 @@ class Temporal:
     of the saturated Color + Background of the last frame against 1024 spp) over a grid of the three (tools/temporal_defaults.py; DESIGN.md
     section 8 has it): a history of 4, a depth tolerance of 5 % and the normal test off bring the MSE to 0.49x that of the raw frame.  The
     film's WorldNormal is the mean of a pixel's sample normals, far from unit length on the fractal, and a floor on its dot product throws
-    away most of the history (0.81x at 0.5, 0.94x at 0.9); a longer history gains nothing over 8 frames (0.51x) and blurs more."""
+    away most of the history (0.81x at 0.5, 0.94x at 0.9); a longer history gains nothing over 8 frames (0.51x) and blurs more.
+
+    `feedback` (finite, in [0, 1]; 0 = off, the default) is the strength of SVGF's feedback edge and needs a VarianceDenoise beside it in
+    render_sequence: the output of the filter's first a-trous pass c' is blended into the history the next frame reprojects, c + feedback *
+    (c' - c) (rayn_hip_denoise_temporal_variance_feedback_device).  It is not part of rayn_temporal_params: the strength travels as that
+    entry's argument.  On the sequence above no strength above 0 lowered the error - 0.4675x at the best point (0.25, with
+    VarianceDenoise(1, 2.0, 0.4, 0.3)) against 0.4571x without feedback (DESIGN.md section 8 has the grid) - so nothing is recommended."""
     max_history: int = 4
     depth_tolerance: float = 0.05
     normal_min: float = -1.0
+    feedback: float = 0.0
 
     def __post_init__(self):
         if isinstance(self.max_history, bool) or not isinstance(self.max_history, (int, np.integer)) or not 1 <= self.max_history <= 65536:
             raise ValueError(f"Temporal.max_history must be an int in 1..65536, got {self.max_history!r}")
-        for name in ("depth_tolerance", "normal_min"):
+        for name in ("depth_tolerance", "normal_min", "feedback"):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
                 raise ValueError(f"Temporal.{name} must be a number, got {v!r}")
@@ -129,6 +136,8 @@ class Temporal:
             raise ValueError(f"Temporal.depth_tolerance must be finite and >= 0, got {self.depth_tolerance!r}")
         if not -1.0 <= float(self.normal_min) <= 1.0:
             raise ValueError(f"Temporal.normal_min must be in [-1, 1], got {self.normal_min!r}")
+        if not 0.0 <= float(self.feedback) <= 1.0:  # a NaN fails both
+            raise ValueError(f"Temporal.feedback must be finite and in [0, 1], got {self.feedback!r}")
 
     def to_abi(self):
         return _abi.TemporalParams(int(self.max_history), float(self.depth_tolerance), float(self.normal_min))
@@ -511,7 +520,7 @@ class Context:
             C.c_void_p(d_new_history.data_ptr()), nbytes, C.c_void_p(d_out_color.data_ptr()), C.c_void_p(s)))
 
     def denoise_temporal_variance(self, width, height, d_film, d_gbuffer, d_history, d_moments, d_out_color, denoise, d_out_variance=None,
-                                  d_scratch=None, stream=None):
+                                  d_scratch=None, stream=None, feedback=0.0):
         """rayn_hip_denoise_temporal_variance_device: the variance-guided a-trous denoiser (VarianceDenoise `denoise`) of a temporally
         accumulated colour.  d_film["color"] is the ACCUMULATED colour (what temporal_accumulate wrote to d_out_color), d_film["normal"] /
         d_film["alpha"] the film's guides (a guide whose sigma is 0 may be absent), d_gbuffer the frame's G-buffer (its "object" plane is
@@ -520,8 +529,16 @@ class Context:
         that - so with Temporal(max_history < 4) only the spatial estimate is ever used.  Writes the float32 CUDA tensor d_out_color
         (width * height * 3 floats) and, when given, d_out_variance (width * height floats; NaN where there was no estimate).  d_scratch: a
         CUDA tensor of at least denoise_variance_scratch_bytes(width, height) bytes, allocated here when None.  Enqueued on the stream,
-        not waited for.  Recommended for sequences: VarianceDenoise(1, 4.0, 0.4, 0.3), 0.46x the raw frame where Temporal() alone gives 0.49x."""
+        not waited for.  Recommended for sequences: VarianceDenoise(1, 4.0, 0.4, 0.3), 0.46x the raw frame where Temporal() alone gives 0.49x.
+
+        feedback (finite, in [0, 1]): 0 takes the entry above and leaves d_history alone.  Anything else goes through
+        rayn_hip_denoise_temporal_variance_feedback_device: d_out_color and d_out_variance are the same bits, and the colour of d_history
+        becomes c + feedback * (c' - c), c' the output of the first a-trous pass, wherever that pass had an estimate; the history lengths,
+        the other planes of the history and the moments are not written."""
         import torch
+        feedback = float(feedback)
+        if not 0.0 <= feedback <= 1.0:
+            raise ValueError(f"feedback must be finite and in [0, 1], got {feedback!r}")
         n = int(width) * int(height)
         if not (d_out_color.dtype == torch.float32 and d_out_color.is_contiguous() and d_out_color.numel() >= 3 * n):
             raise ValueError(f"d_out_color must be a contiguous float32 tensor of at least {3 * n} floats")
@@ -547,12 +564,15 @@ class Context:
         if not d_scratch.is_contiguous():
             raise ValueError("d_scratch must be contiguous")
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        self._chk(self._L.rayn_hip_denoise_temporal_variance_device(
-            self.h, int(width), int(height), int(denoise.iterations), float(denoise.sigma_luminance), float(denoise.sigma_normal),
-            float(denoise.sigma_alpha), *ptrs, C.c_void_p(obj.data_ptr()), C.c_void_p(d_history.data_ptr()), d_history.numel(),
-            C.c_void_p(d_moments.data_ptr()), d_moments.numel(), C.c_void_p(d_out_color.data_ptr()),
-            None if d_out_variance is None else C.c_void_p(d_out_variance.data_ptr()), C.c_void_p(d_scratch.data_ptr()),
-            d_scratch.numel() * d_scratch.element_size(), C.c_void_p(s)))
+        args = (self.h, int(width), int(height), int(denoise.iterations), float(denoise.sigma_luminance), float(denoise.sigma_normal),
+                float(denoise.sigma_alpha), *ptrs, C.c_void_p(obj.data_ptr()), C.c_void_p(d_history.data_ptr()), d_history.numel(),
+                C.c_void_p(d_moments.data_ptr()), d_moments.numel(), C.c_void_p(d_out_color.data_ptr()),
+                None if d_out_variance is None else C.c_void_p(d_out_variance.data_ptr()), C.c_void_p(d_scratch.data_ptr()),
+                d_scratch.numel() * d_scratch.element_size())
+        if feedback == 0.0:
+            self._chk(self._L.rayn_hip_denoise_temporal_variance_device(*args, C.c_void_p(s)))
+        else:
+            self._chk(self._L.rayn_hip_denoise_temporal_variance_feedback_device(*args, feedback, C.c_void_p(s)))
 
     @staticmethod
     def _prog_state(params, d_state):
@@ -944,14 +964,23 @@ class Film:
 
         With `temporal` and a VarianceDenoise as `denoise`, the accumulate also carries the luminance moments (two more buffers, allocated
         once), and the variance-guided filter runs on the accumulated colour with a variance estimated from them
-        (Context.denoise_temporal_variance); the file is _color_temporal_denoised.png.  The filtered colour is not fed back into the
-        history.  The film needs its Alpha channel when sigma_alpha != 0 (WorldNormal it needs anyway).  Recommended for sequences
-        (DESIGN.md section 8): VarianceDenoise(1, 4.0, 0.4, 0.3), 0.46x the raw frame where Temporal() alone gives 0.49x."""
+        (Context.denoise_temporal_variance); the file is _color_temporal_denoised.png.  The film needs its Alpha channel when sigma_alpha
+        != 0 (WorldNormal it needs anyway).  Recommended for sequences: VarianceDenoise(1, 4.0, 0.4, 0.3), 0.46x the
+        raw frame where Temporal() alone gives 0.49x.
+
+        With temporal.feedback == 0 (the default) the filtered colour is not fed back into the history: every frame's filter is a function
+        of that frame's buffers.  With temporal.feedback > 0 the filter of frame i also blends the output of its first pass into frame
+        i's history with that strength (rayn_hip_denoise_temporal_variance_feedback_device), so frame i + 1 reprojects what frame i's filter
+        left; the file names do not change.  It needs a VarianceDenoise as `denoise` - there is nothing to feed back otherwise - and raises
+        ValueError before anything renders without one.  Measured on the sequence of DESIGN.md section 8, no strength above 0 lowered the
+        error (0.4675x at best, against 0.4571x): the option is there to be measured on other scenes and sizes, not recommended."""
         import concurrent.futures as cf
         import torch
         variance = isinstance(denoise, VarianceDenoise)
         if variance and temporal is None:
             raise ValueError("render_sequence renders plain frames: VarianceDenoise needs the state of a progressive render")
+        if isinstance(temporal, Temporal) and float(temporal.feedback) > 0.0 and not variance:
+            raise ValueError("Temporal.feedback > 0 feeds a VarianceDenoise's first pass back into the history: pass one as `denoise`")
         frames = [int(f) for f in frames]
         jobs = self._save_jobs(write_channels, transparent_background)
         if denoise is not None:
@@ -1055,7 +1084,7 @@ class Film:
                     if denoise is not None:
                         if variance:
                             self.ctx.denoise_temporal_variance(w, h, d_shown, d_gbuf, d_hist[i % 2], d_mom[i % 2], d_denoised, denoise, None, d_scratch,
-                                                               stream.cuda_stream)
+                                                               stream.cuda_stream, float(temporal.feedback))
                         else:
                             self.ctx.denoise(w, h, d_shown, d_denoised, denoise, d_scratch, stream.cuda_stream)
                         d_shown = dict(d_film, color=d_denoised)
