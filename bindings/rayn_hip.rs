@@ -164,6 +164,23 @@ pub struct RaynStats {
 
 pub enum RaynCtx {}
 
+// The two parameter blocks of the temporal accumulate (extensions; include/rayn_hip.h: rayn_temporal_params,
+// rayn_temporal_resample_params).  Plain scalars: 12 and 4 bytes; rayn_hip_sizeof(7) reports the second.
+#[repr(C)]
+/// `max_history` 1..65536, `depth_tolerance` finite and >= 0, `normal_min` in [-1, 1] (-1: the test is off)
+#[derive(Clone, Copy, Debug)]
+pub struct RaynTemporalParams {
+    pub max_history: u32,
+    pub depth_tolerance: f32,
+    pub normal_min: f32,
+}
+#[repr(C)]
+/// `resample`: 0 bilinear, 1 Catmull-Rom
+#[derive(Clone, Copy, Debug)]
+pub struct RaynTemporalResampleParams {
+    pub resample: u32,
+}
+
 #[link(name = "rayn_hip")]
 extern "C" {
     pub fn rayn_hip_create(device: i32, out: *mut *mut RaynCtx) -> i32;
@@ -212,6 +229,28 @@ extern "C" {
         d_out_variance: *mut f32,
         d_scratch: *mut c_void,
         scratch_bytes: usize,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    /// the temporal accumulate with a choice of the history resampling filter (`rp.resample`: 0 bilinear, 1 Catmull-Rom); both moments
+    /// pointers null: no moments (include/rayn_hip.h has the definition)
+    pub fn rayn_hip_temporal_accumulate_resample_device(
+        ctx: *mut RaynCtx,
+        p: *const RaynFrameParams,
+        tp: *const RaynTemporalParams,
+        rp: *const RaynTemporalResampleParams,
+        prev_camera: *const RaynCamera,
+        prev_time_start: f32,
+        d_color: *const f32,
+        d_normal: *const f32,
+        d_gbuffer_records: *const c_void,
+        d_gbuffer_object: *const u32,
+        d_prev_history: *const c_void,
+        d_new_history: *mut c_void,
+        history_bytes: usize,
+        d_prev_moments: *const c_void,
+        d_new_moments: *mut c_void,
+        moments_bytes: usize,
+        d_out_color: *mut f32,
         hip_stream: *mut c_void,
     ) -> i32;
     /// the same filter with SVGF's feedback edge: pass 0 is blended into the history's colour with strength `feedback` (0 = the entry above)

@@ -3,6 +3,7 @@
 written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints per-frame render times and frames/s.
 
     python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise [atrous|variance]] [--temporal] [--feedback B]
+                                      [--resample {bilinear,catmull_rom}]
 
 --compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
 the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
@@ -13,7 +14,8 @@ origin drifts, and writes _color_temporal.png (_color_temporal_denoised.png with
 accumulated colour with the variance-guided denoiser instead, its variance estimated from luminance moments the accumulate carries along
 (rayn_amd.VarianceDenoise(1, 4.0, 0.4, 0.3), the setting recommended for sequences); it needs --temporal.  --feedback B (in [0, 1],
 default 0 = off) also blends the output of every frame's first a-trous pass into the history the next frame reprojects, with strength B
-(rayn_amd.Temporal(feedback=B)); it needs --temporal --denoise variance."""
+(rayn_amd.Temporal(feedback=B)); it needs --temporal --denoise variance.  --resample catmull_rom resamples the history with the 4x4
+Catmull-Rom filter instead of the bilinear one wherever the whole footprint is valid (rayn_amd.Temporal(resample=...)); it needs --temporal."""
 import argparse
 import os
 import sys
@@ -68,7 +70,11 @@ def main():
     ap.add_argument("--feedback", type=float, default=0.0, metavar="B",
                     help="strength in [0, 1] with which every frame's first a-trous pass is fed back into the temporal history (0 = off); "
                          "needs --temporal --denoise variance")
+    ap.add_argument("--resample", choices=("bilinear", "catmull_rom"), default="bilinear",
+                    help="the filter that resamples the temporal history at the reprojected position (default bilinear); needs --temporal")
     args = ap.parse_args()
+    if args.resample != "bilinear" and not args.temporal:
+        ap.error("--resample chooses the resampling filter of the temporal accumulation: add --temporal")
     if (args.denoise or args.temporal) and args.compare_loop:
         ap.error("--compare-loop compares with the host post-process, which has neither a denoiser nor a temporal accumulation: use one or the other")
     if args.denoise == "variance" and not args.temporal:
@@ -78,7 +84,7 @@ def main():
     if not 0.0 <= args.feedback <= 1.0:
         ap.error("--feedback must be in [0, 1]")
     denoise = {None: None, "atrous": R.Denoise(), "variance": R.VarianceDenoise(1, 4.0, 0.4, 0.3)}[args.denoise]
-    temporal = R.Temporal(feedback=args.feedback) if args.temporal else None
+    temporal = R.Temporal(feedback=args.feedback, resample=args.resample) if args.temporal else None
     first, end = (int(x) for x in args.frames.split(":"))
     frames = list(range(first, end))
     base = f"{SAMPLES * 4}_spp"

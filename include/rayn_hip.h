@@ -510,6 +510,32 @@ int rayn_hip_temporal_accumulate_moments_device(rayn_ctx* ctx, const rayn_frame_
                                                 void* d_new_history, size_t history_bytes, const void* d_prev_moments, void* d_new_moments,
                                                 size_t moments_bytes, float* d_out_color, void* hip_stream);
 
+/* Temporal accumulate with a choice of the history resampling filter of step 4.  The arguments of the two entries above plus rp. */
+typedef struct { uint32_t resample; /* 0 bilinear (the existing step 4), 1 Catmull-Rom */ } rayn_temporal_resample_params;
+/* d_prev_moments and d_new_moments both NULL: no moments, the outputs of rayn_hip_temporal_accumulate_device (moments_bytes is ignored).
+ * Otherwise the rules of rayn_hip_temporal_accumulate_moments_device apply.  resample == 0: the outputs are bit for bit those of these
+ * two entries.  resample == 1: steps 1, 2, 3 and 5 (the moments' blend and both non-finite fallbacks included) do not change; all f32, no
+ * contraction under either mul_add policy, "a * b + c" a multiply and then an add.  Step 4 becomes:
+ *   x0f = floorf(fx), t = fx - x0f, x0 the integer as before; y likewise.  Per axis the weights of the offsets -1, 0, 1, 2:
+ *     k_-1 = ((-0.5f * t + 1.0f) * t - 0.5f) * t        k_0 = ((1.5f * t - 2.5f) * t) * t + 1.0f
+ *     k_1  = ((-1.5f * t + 2.0f) * t + 0.5f) * t        k_2 = ((0.5f * t - 0.5f) * t) * t
+ *   The 16 taps (x0 + i, y0 + j), i, j in -1..2, in raster order (j outer, i inner); a tap counts by step 4's predicate: inside the image,
+ *   n_tap >= 1, obj_tap == obj, the depth test and, with normal_min > -1, the normal test.
+ *   FULL SUPPORT - all 16 count:  w = kx_i * ky_j;  W += w, S += w * c_tap, N += w * n_tap, and with moments S1 += w * m1_tap,
+ *     S2 += w * m2_tap;  h = S / W, nh = N / W, h1 = S1 / W, h2 = S2 / W.  Anti-ringing: every component of h, and h1 and h2, becomes
+ *     fminf(fmaxf(v, lo), hi) with lo / hi the minimum / maximum of that quantity over the four inner taps (i, j in 0..1; fminf and fmaxf
+ *     return the other operand for a NaN and order -0 below +0; the colours and moments of taps with n >= 1 are finite in a history these
+ *     entries wrote).  nh = fmaxf(nh, 1.0f).  Then step 5 from n' = fminf(nh + 1.0f, (float)max_history) on.
+ *   ANYTHING LESS - a tap outside the image or rejected: the bilinear step 4 on the four inner taps, exactly (Catmull-Rom weights
+ *     renormalised over a partial footprint ring).  An image narrower or lower than 4 pixels therefore never takes the cubic arm.
+ * RAYN_ERR_INVALID_ARG with the same last error texts for everything the two entries above reject, and for a NULL rp and resample > 1. */
+int rayn_hip_temporal_accumulate_resample_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp,
+                                                 const rayn_temporal_resample_params* rp, const rayn_camera* prev_camera, float prev_time_start,
+                                                 const float* d_color, const float* d_normal, const void* d_gbuffer_records,
+                                                 const uint32_t* d_gbuffer_object, const void* d_prev_history, void* d_new_history,
+                                                 size_t history_bytes, const void* d_prev_moments, void* d_new_moments, size_t moments_bytes,
+                                                 float* d_out_color, void* hip_stream);
+
 /* Variance-guided denoiser of a temporally accumulated Color: the passes of rayn_hip_denoise_variance_device on a variance estimated
  * from the moments above (SVGF, section 4.2).  Inputs: the accumulated colour c (3 floats per pixel, what the accumulate wrote to
  * d_out_color), the film's Alpha and WorldNormal, the frame's G-buffer objects obj, the NEW history (for the history length n' in plane A's
@@ -631,7 +657,7 @@ int rayn_hip_set_cold_bytes(rayn_ctx* ctx, uint64_t bytes);
 int rayn_hip_fma_policy(void);
 int rayn_hip_set_fma_policy(rayn_ctx* ctx, int policy);
 /* sizeof() of the ABI structs as compiled: 0 world_desc, 1 frame_params, 2 stats, 3 hitable,
- * 4 material, 5 light, 6 camera — lets a binding verify its layout. */
+ * 4 material, 5 light, 6 camera, 7 temporal_resample_params — lets a binding verify its layout. */
 size_t rayn_hip_sizeof(int which);
 /* "" for the product build of the library; the VARIANT name of a `make variant` build (timing experiments: such a build is
  * only ever loaded through RAYN_HIP_LIB + RAYN_HIP_ALLOW_VARIANT=1, and bench.py prints the name in its result line). */

@@ -313,6 +313,20 @@ class Film {
 // of this size, 8 per pixel; 0 for a size the entries reject.  Host only.
 inline size_t temporal_moments_bytes(Extent2u res) { return rayn_temporal_moments_bytes(res.w, res.h); }
 
+// Extension (include/rayn_hip.h: rayn_hip_temporal_accumulate_resample_device): the temporal accumulate with a choice of the history
+// resampling filter.  Device pointers; the moments pointers may both be null (no moments).  Returns the entry's code.
+enum class TemporalResample : uint32_t { Bilinear = 0, CatmullRom = 1 };
+inline int temporal_accumulate_resample(rayn_ctx* ctx, const rayn_frame_params& p, const rayn_temporal_params& tp, TemporalResample resample,
+                                        const rayn_camera* prev_camera, float prev_time_start, const float* d_color, const float* d_normal,
+                                        const void* d_gbuffer_records, const uint32_t* d_gbuffer_object, const void* d_prev_history,
+                                        void* d_new_history, size_t history_bytes, const void* d_prev_moments, void* d_new_moments,
+                                        size_t moments_bytes, float* d_out_color, void* hip_stream = nullptr) {
+    const rayn_temporal_resample_params rp = {static_cast<uint32_t>(resample)};
+    return rayn_hip_temporal_accumulate_resample_device(ctx, &p, &tp, &rp, prev_camera, prev_time_start, d_color, d_normal, d_gbuffer_records,
+                                                        d_gbuffer_object, d_prev_history, d_new_history, history_bytes, d_prev_moments,
+                                                        d_new_moments, moments_bytes, d_out_color, hip_stream);
+}
+
 // ---- setup::setup() (src/setup.rs:46-170) with the resolution as an argument ---------------------
 namespace setup {
 constexpr float WORLD_RADIUS = 100.0f;

@@ -69,6 +69,12 @@ class TemporalParams(C.Structure):  # rayn_temporal_params
     _fields_ = [("max_history", C.c_uint32), ("depth_tolerance", C.c_float), ("normal_min", C.c_float)]
 
 
+class TemporalResampleParams(C.Structure):  # rayn_temporal_resample_params
+    _fields_ = [("resample", C.c_uint32)]
+
+
+TEMPORAL_RESAMPLE = {"bilinear": 0, "catmull_rom": 1}  # rayn_temporal_resample_params.resample by the name rayn_amd.Temporal takes
+
 MOMENTS_BYTES_PER_PIXEL = 8  # one float2 (m1, m2) per pixel beside a temporal history
 
 

@@ -42,7 +42,7 @@ EXPORTS = [
     "rayn_denoise_variance_scratch_bytes", "rayn_hip_denoise_variance_device",
     "rayn_gbuffer_scratch_bytes", "rayn_hip_gbuffer_device", "rayn_temporal_history_bytes", "rayn_hip_temporal_accumulate_device",
     "rayn_temporal_moments_bytes", "rayn_hip_temporal_accumulate_moments_device", "rayn_hip_denoise_temporal_variance_device",
-    "rayn_hip_denoise_temporal_variance_feedback_device",
+    "rayn_hip_denoise_temporal_variance_feedback_device", "rayn_hip_temporal_accumulate_resample_device",
 ]
 
 
@@ -120,6 +120,9 @@ def lib():
         L.rayn_temporal_moments_bytes.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_hip_temporal_accumulate_moments_device.argtypes = ([vp, C.POINTER(_abi.FrameParams), C.POINTER(_abi.TemporalParams), C.POINTER(_abi.Camera), C.c_float]
                                                                   + [vp] * 6 + [C.c_size_t, vp, vp, C.c_size_t, vp, vp])
+        L.rayn_hip_temporal_accumulate_resample_device.argtypes = ([vp, C.POINTER(_abi.FrameParams), C.POINTER(_abi.TemporalParams),
+                                                                    C.POINTER(_abi.TemporalResampleParams), C.POINTER(_abi.Camera), C.c_float]
+                                                                   + [vp] * 6 + [C.c_size_t, vp, vp, C.c_size_t, vp, vp])
         L.rayn_hip_denoise_temporal_variance_device.argtypes = ([vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float] + [vp] * 5
                                                                 + [C.c_size_t, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp])
         L.rayn_hip_denoise_temporal_variance_feedback_device.argtypes = ([vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float] + [vp] * 5

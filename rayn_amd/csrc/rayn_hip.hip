@@ -1060,17 +1060,19 @@ int rayn_hip_gbuffer_device(rayn_ctx* ctx, const rayn_frame_params* p, void* d_o
     return post_enqueued(ctx);
 }
 
-// Both temporal accumulate entries: new_moments == nullptr is the plain one (the moments arguments are then not looked at).
+// The temporal accumulate entries: moments == false is the plain one (the moments arguments are then not looked at); resample is step 4's
+// filter (0: the two older entries), bad_resample the resample entry's own complaint about its rp, reported after the shared checks.
 static int temporal_accumulate(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp, const rayn_camera* prev_camera,
                                float prev_time_start, const float* d_color, const float* d_normal, const void* d_gbuffer_records,
                                const uint32_t* d_gbuffer_object, const void* d_prev_history, void* d_new_history, size_t history_bytes,
                                bool moments, const void* d_prev_moments, void* d_new_moments, size_t moments_bytes, float* d_out_color,
-                               void* hip_stream) {
+                               void* hip_stream, uint32_t resample, const char* bad_resample) {
     const char* why = temporal_check_args(p, tp, prev_camera, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history, d_new_history,
                                           history_bytes, d_out_color);
     if (!why && moments)
         why = temporal_moments_check_args(p, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history, d_new_history, d_prev_moments,
                                           d_new_moments, moments_bytes, d_out_color);
+    if (!why) why = bad_resample;
     if (!why && ctx && !ctx->cfg->have_world) why = "rayn_hip_upload_world has not been called";
     TemporalScene ts;
     memset(&ts, 0, sizeof ts);
@@ -1083,7 +1085,7 @@ static int temporal_accumulate(rayn_ctx* ctx, const rayn_frame_params* p, const 
     for (uint32_t i = 0; i < ts.n_hitables; i++)
         ts.hvel[i] = make_float4(w.hitables[i].center_vel.x, w.hitables[i].center_vel.y, w.hitables[i].center_vel.z, w.hitables[i].animated ? 1.0f : 0.0f);
     launch_temporal_accumulate(s, p->width, p->height, *tp, ts, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history, d_new_history,
-                               d_out_color, moments ? d_prev_moments : nullptr, moments ? d_new_moments : nullptr);
+                               d_out_color, moments ? d_prev_moments : nullptr, moments ? d_new_moments : nullptr, resample);
     return post_enqueued(ctx);
 }
 
@@ -1092,7 +1094,7 @@ int rayn_hip_temporal_accumulate_device(rayn_ctx* ctx, const rayn_frame_params* 
                                         const uint32_t* d_gbuffer_object, const void* d_prev_history, void* d_new_history, size_t history_bytes,
                                         float* d_out_color, void* hip_stream) {
     return temporal_accumulate(ctx, p, tp, prev_camera, prev_time_start, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history,
-                               d_new_history, history_bytes, false, nullptr, nullptr, 0, d_out_color, hip_stream);
+                               d_new_history, history_bytes, false, nullptr, nullptr, 0, d_out_color, hip_stream, 0, nullptr);
 }
 
 int rayn_hip_temporal_accumulate_moments_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp,
@@ -1101,7 +1103,20 @@ int rayn_hip_temporal_accumulate_moments_device(rayn_ctx* ctx, const rayn_frame_
                                                 void* d_new_history, size_t history_bytes, const void* d_prev_moments, void* d_new_moments,
                                                 size_t moments_bytes, float* d_out_color, void* hip_stream) {
     return temporal_accumulate(ctx, p, tp, prev_camera, prev_time_start, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history,
-                               d_new_history, history_bytes, true, d_prev_moments, d_new_moments, moments_bytes, d_out_color, hip_stream);
+                               d_new_history, history_bytes, true, d_prev_moments, d_new_moments, moments_bytes, d_out_color, hip_stream, 0, nullptr);
+}
+
+int rayn_hip_temporal_accumulate_resample_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp,
+                                                 const rayn_temporal_resample_params* rp, const rayn_camera* prev_camera, float prev_time_start,
+                                                 const float* d_color, const float* d_normal, const void* d_gbuffer_records,
+                                                 const uint32_t* d_gbuffer_object, const void* d_prev_history, void* d_new_history,
+                                                 size_t history_bytes, const void* d_prev_moments, void* d_new_moments, size_t moments_bytes,
+                                                 float* d_out_color, void* hip_stream) {
+    const bool moments = d_prev_moments || d_new_moments; // both NULL: no moments; one alone: the moments entry's error
+    const char* bad = temporal_resample_check_args(rp);
+    return temporal_accumulate(ctx, p, tp, prev_camera, prev_time_start, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history,
+                               d_new_history, history_bytes, moments, d_prev_moments, d_new_moments, moments_bytes, d_out_color, hip_stream,
+                               bad ? 0u : rp->resample, bad);
 }
 
 int rayn_hip_denoise_temporal_variance_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance,
@@ -1337,6 +1352,7 @@ size_t rayn_hip_sizeof(int which) {
     case 4: return sizeof(rayn_material);
     case 5: return sizeof(rayn_light);
     case 6: return sizeof(rayn_camera);
+    case 7: return sizeof(rayn_temporal_resample_params);
     default: return 0;
     }
 }

@@ -50,11 +50,14 @@ size_t temporal_moments_bytes(uint32_t width, uint32_t height);
 const char* temporal_moments_check_args(const rayn_frame_params* p, const float* color, const float* normal, const void* g_records,
                                         const uint32_t* g_object, const void* prev_history, const void* new_history, const void* prev_moments,
                                         const void* new_moments, size_t moments_bytes, const float* out_color);
-// new_moments == nullptr: the plain accumulate (k_temporal_accumulate<false>); else the moments are carried too
+// what rayn_hip_temporal_accumulate_resample_device checks on top of the two above
+const char* temporal_resample_check_args(const rayn_temporal_resample_params* rp);
+// new_moments == nullptr: the plain accumulate (k_temporal_accumulate<false, *>); else the moments are carried too.  resample: 0 the
+// bilinear step 4 (<*, 0>, the kernels of the two older entries), 1 Catmull-Rom over a full 4x4 footprint (<*, 1>).
 void launch_temporal_accumulate(hipStream_t s, uint32_t width, uint32_t height, const rayn_temporal_params& tp, const TemporalScene& ts,
                                 const float* color, const float* normal, const void* g_records, const uint32_t* g_object,
                                 const void* prev_history, void* new_history, float* out_color, const void* prev_moments = nullptr,
-                                void* new_moments = nullptr);
+                                void* new_moments = nullptr, uint32_t resample = 0);
 
 } // namespace rayn
 

@@ -36,6 +36,14 @@
 // writes (y, y2), and (0, 0) when c is not finite.  Otherwise S1 += w * m1_tap, S2 += w * m2_tap over the colour's taps in its loop order,
 // h1 = S1 / W, h2 = S2 / W, m1' = h1 + a * (y - h1), m2' = h2 + a * (y2 - h2) with the colour's a; a non-finite m1' or m2' writes (y, y2)
 // while the colour keeps its blend.  The colour and the 52 B history are the bits of the plain entry.
+// Catmull-Rom (rayn_hip_temporal_accumulate_resample_device with resample = 1; k_temporal_accumulate<*, 1>): step 4 reads the 4x4 footprint
+// (x0 - 1 .. x0 + 2) x (y0 - 1 .. y0 + 2).  With t = wx1 (and wy1) the weights of the offsets -1, 0, 1, 2 are ((-0.5f t + 1.0f) t - 0.5f) t,
+// ((1.5f t - 2.5f) t) t + 1.0f, ((-1.5f t + 2.0f) t + 0.5f) t, ((0.5f t - 0.5f) t) t.  When all 16 taps count (the predicate above), in
+// raster order with w = kx_i * ky_j: W += w, S += w * c_tap, N += w * n_tap (S1, S2 likewise); h = S / W, nh = N / W, h1, h2; every
+// component of h, and h1 and h2, is clamped with fminf(fmaxf(v, lo), hi) to the range of the four inner taps (anti-ringing; fminf / fmaxf
+// drop a NaN operand and order -0 below +0, as v_min_f32 / v_max_f32 do), nh = fmaxf(nh, 1.0f), then step 5.  Any tap outside the image or
+// rejected: the bilinear step 4 above, exactly.  The kernel checks the 16 taps first (4 + 4 + 4 [+ 16] bytes each) and re-reads the colours
+// (and moments) of a full footprint in a second loop: no 16 live float4.
 // One thread per pixel in 16x16 blocks, 16-byte record loads, as denoise.hip; at most 4 x 3 record loads per pixel: bandwidth-trivial.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -113,9 +121,86 @@ __device__ inline v3 closure3(f3 base, f3 vel, bool on, float t) {
     return on ? v3{base.x + vel.x * t, base.y + vel.y * t, base.z + vel.z * t} : v3{base.x, base.y, base.z};
 }
 
+// One Catmull-Rom weight set: the offsets -1, 0, 1, 2 at the fraction t in [0, 1)
+__device__ inline void cubic_weights(float t, float k[4]) {
+    k[0] = ((-0.5f * t + 1.0f) * t - 0.5f) * t;
+    k[1] = ((1.5f * t - 2.5f) * t) * t + 1.0f;
+    k[2] = ((-1.5f * t + 2.0f) * t + 0.5f) * t;
+    k[3] = ((0.5f * t - 0.5f) * t) * t;
+}
+__device__ inline float clampf(float v, float lo, float hi) { return __builtin_fminf(__builtin_fmaxf(v, lo), hi); }
+
+// Step 4's result: the resampled history colour, length and moments
+struct Resampled { float r, g, b, n, m1, m2; };
+
+// The Catmull-Rom arm of step 4.  False - nothing written - unless all 16 taps of the footprint count; the caller then takes the bilinear
+// arm.  The first loop reads what the predicate needs (the length, object and depth dwords, the normal when its test is on), the second
+// re-reads the colours (and moments) of a full footprint from L2: at most one float4 (+ float2) is live per tap.
+template <bool MOMENTS>
+__device__ inline bool cubic_history(long long x0, long long y0, uint32_t width, uint32_t height, float tx, float ty, uint32_t obj, float te, float tol,
+                                     float normal_min, v3 nrm, const float4* __restrict__ pA, const float4* __restrict__ pB,
+                                     const float4* __restrict__ pN, const uint32_t* __restrict__ pO, const float2* __restrict__ pM, Resampled* out) {
+    if (x0 < 1 || x0 + 2 >= (long long)width || y0 < 1 || y0 + 2 >= (long long)height) return false;
+    const uint32_t q0 = (uint32_t)(x0 - 1) + (uint32_t)(y0 - 1) * width; // every tap is a pixel of the image: its index is < 2^31
+    // one row of the footprint per trip, not unrolled, in both loops: four taps in flight instead of sixteen
+#pragma unroll 1
+    for (int j = 0; j < 4; j++) {
+        bool row = true;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t q = q0 + (uint32_t)i + (uint32_t)j * width;
+            bool counts = pA[q].w >= 1.0f;
+            counts &= pO[q] == obj;
+            counts &= __builtin_fabsf(pB[q].w - te) <= tol;
+            if (normal_min > -1.0f) {
+                const float4 nq = pN[q];
+                counts &= dot3(nrm, v3{nq.x, nq.y, nq.z}) >= normal_min;
+            }
+            row &= counts;
+        }
+        if (!row) return false;
+    }
+    float kx[4], ky[4];
+    cubic_weights(tx, kx);
+    cubic_weights(ty, ky);
+    float W = 0.0f, S[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, lo[6], hi[6]; // r, g, b, n, m1, m2
+#pragma unroll 1
+    for (int j = 0; j < 4; j++) {
+        const float kyj = j == 0 ? ky[0] : j == 1 ? ky[1] : j == 2 ? ky[2] : ky[3];
+        const bool inner_row = j == 1 || j == 2;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t q = q0 + (uint32_t)i + (uint32_t)j * width;
+            const float4 a = pA[q];
+            const float2 m = MOMENTS ? pM[q] : make_float2(0.0f, 0.0f);
+            const float v[6] = {a.x, a.y, a.z, a.w, m.x, m.y};
+            const float w = kx[i] * kyj;
+            W += w;
+#pragma unroll
+            for (int c = 0; c < (MOMENTS ? 6 : 4); c++) {
+                S[c] += w * v[c];
+                // the four inner taps, raster order: the range of the anti-ringing clamp
+                if (i == 1 && j == 1) lo[c] = hi[c] = v[c];
+                else if ((i == 1 || i == 2) && inner_row) { lo[c] = __builtin_fminf(lo[c], v[c]); hi[c] = __builtin_fmaxf(hi[c], v[c]); }
+            }
+        }
+    }
+    out->r = clampf(S[0] / W, lo[0], hi[0]);
+    out->g = clampf(S[1] / W, lo[1], hi[1]);
+    out->b = clampf(S[2] / W, lo[2], hi[2]);
+    out->n = __builtin_fmaxf(S[3] / W, 1.0f);
+    if (MOMENTS) {
+        out->m1 = clampf(S[4] / W, lo[4], hi[4]);
+        out->m2 = clampf(S[5] / W, lo[5], hi[5]);
+    }
+    return true;
+}
+
 // MOMENTS: also carry the first and second moment of the luminance through the same taps (rayn_hip_temporal_accumulate_moments_device);
 // the false instantiation reads and writes exactly what the kernel did before the moments existed.
-template <bool MOMENTS>
+// RESAMPLE: 0 the bilinear step 4, the instruction streams of the kernel before the option existed; 1 Catmull-Rom over a full 4x4
+// footprint, bilinear otherwise (rayn_hip_temporal_accumulate_resample_device).
+template <bool MOMENTS, int RESAMPLE>
 __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uint32_t height, uint32_t tiles_x, float max_history, float depth_tolerance,
                                                               float normal_min, TemporalScene ts, const float* __restrict__ color,
                                                               const float* __restrict__ normal, const float4* __restrict__ grec,
@@ -175,33 +260,43 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uin
             const long long y0 = (long long)__builtin_fminf(__builtin_fmaxf(y0f, -2.0f), 2147483648.0f);
             const float tol = depth_tolerance * te;
             float W = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f, N = 0.0f, S1 = 0.0f, S2 = 0.0f;
+            Resampled hs = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            bool have = false;
+            if (RESAMPLE == 1) have = cubic_history<MOMENTS>(x0, y0, width, height, wx1, wy1, obj, te, tol, normal_min, nrm, pA, pB, pN, pO, pM, &hs);
+            if (!have) {
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const long long qx = x0 + (k & 1), qy = y0 + (k >> 1);
-                if (qx < 0 || qx >= (long long)width || qy < 0 || qy >= (long long)height) continue;
-                const uint32_t q = (uint32_t)qx + (uint32_t)qy * width;
-                const float4 a = pA[q];
-                if (!(a.w >= 1.0f)) continue;
-                if (pO[q] != obj) continue;
-                if (!(__builtin_fabsf(pB[q].w - te) <= tol)) continue;
-                if (normal_min > -1.0f) {
-                    const float4 nq = pN[q];
-                    if (!(dot3(nrm, v3{nq.x, nq.y, nq.z}) >= normal_min)) continue;
+                for (int k = 0; k < 4; k++) {
+                    const long long qx = x0 + (k & 1), qy = y0 + (k >> 1);
+                    if (qx < 0 || qx >= (long long)width || qy < 0 || qy >= (long long)height) continue;
+                    const uint32_t q = (uint32_t)qx + (uint32_t)qy * width;
+                    const float4 a = pA[q];
+                    if (!(a.w >= 1.0f)) continue;
+                    if (pO[q] != obj) continue;
+                    if (!(__builtin_fabsf(pB[q].w - te) <= tol)) continue;
+                    if (normal_min > -1.0f) {
+                        const float4 nq = pN[q];
+                        if (!(dot3(nrm, v3{nq.x, nq.y, nq.z}) >= normal_min)) continue;
+                    }
+                    const float w = ((k & 1) ? wx1 : wx0) * ((k >> 1) ? wy1 : wy0);
+                    W += w;
+                    Sr += w * a.x;
+                    Sg += w * a.y;
+                    Sb += w * a.z;
+                    N += w * a.w;
+                    if (MOMENTS) {
+                        const float2 m = pM[q];
+                        S1 += w * m.x;
+                        S2 += w * m.y;
+                    }
                 }
-                const float w = ((k & 1) ? wx1 : wx0) * ((k >> 1) ? wy1 : wy0);
-                W += w;
-                Sr += w * a.x;
-                Sg += w * a.y;
-                Sb += w * a.z;
-                N += w * a.w;
-                if (MOMENTS) {
-                    const float2 m = pM[q];
-                    S1 += w * m.x;
-                    S2 += w * m.y;
+                if (W > 0.0f) {
+                    hs = Resampled{Sr / W, Sg / W, Sb / W, N / W, 0.0f, 0.0f};
+                    if (MOMENTS) { hs.m1 = S1 / W; hs.m2 = S2 / W; }
+                    have = true;
                 }
             }
-            if (W > 0.0f) {
-                const float hr = Sr / W, hg = Sg / W, hb = Sb / W, nh = N / W;
+            if (have) {
+                const float hr = hs.r, hg = hs.g, hb = hs.b, nh = hs.n;
                 const float n1 = __builtin_fminf(nh + 1.0f, max_history);
                 const float al = 1.0f / n1;
                 const float dr = c.x - hr, dg = c.y - hg, db = c.z - hb;
@@ -209,7 +304,7 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uin
                 if (fin(b.x) && fin(b.y) && fin(b.z)) {
                     out = b; nn = n1;
                     if (MOMENTS) {
-                        const float h1 = S1 / W, h2 = S2 / W;
+                        const float h1 = hs.m1, h2 = hs.m2;
                         const float d1 = lum - h1, d2 = lum2 - h2;
                         const float b1 = h1 + al * d1, b2 = h2 + al * d2;
                         if (fin(b1) && fin(b2)) { m1 = b1; m2 = b2; } // else (y, y2): an overflow heals on the next frame
@@ -340,19 +435,28 @@ const char* temporal_moments_check_args(const rayn_frame_params* p, const float*
     return nullptr;
 }
 
+const char* temporal_resample_check_args(const rayn_temporal_resample_params* rp) {
+    if (!rp) return "null resample params";
+    if (rp->resample > 1u) return "resample must be 0 (bilinear) or 1 (Catmull-Rom)";
+    return nullptr;
+}
+
 void launch_temporal_accumulate(hipStream_t s, uint32_t width, uint32_t height, const rayn_temporal_params& tp, const TemporalScene& ts,
                                 const float* color, const float* normal, const void* g_records, const uint32_t* g_object,
-                                const void* prev_history, void* new_history, float* out_color, const void* prev_moments, void* new_moments) {
+                                const void* prev_history, void* new_history, float* out_color, const void* prev_moments, void* new_moments, uint32_t resample) {
     const size_t n = (size_t)width * height;
     const float4* pA = (const float4*)prev_history; // null: no previous history
     float4* nA = (float4*)new_history;
     const uint32_t tiles_x = (width + 15u) / 16u, tiles_y = (height + 15u) / 16u;
-#define RAYN_TACC(M) hipLaunchKernelGGL(k_temporal_accumulate<M>, dim3(tiles_x * tiles_y), dim3(16, 16), 0, s, width, height, tiles_x, (float)tp.max_history, \
+#define RAYN_TACC(M, R) hipLaunchKernelGGL((k_temporal_accumulate<M, R>), dim3(tiles_x * tiles_y), dim3(16, 16), 0, s, width, height, tiles_x, (float)tp.max_history, \
                        tp.depth_tolerance, tp.normal_min, ts, color, normal, (const float4*)g_records, g_object, pA, pA ? pA + n : nullptr,           \
                        pA ? pA + 2u * n : nullptr, pA ? (const uint32_t*)(pA + 3u * n) : nullptr, nA, nA + n, nA + 2u * n, (uint32_t*)(nA + 3u * n), \
                        out_color, (const float2*)prev_moments, (float2*)new_moments)
-    if (new_moments) RAYN_TACC(true); // the moments entry
-    else RAYN_TACC(false);
+    if (resample == 1) {
+        if (new_moments) RAYN_TACC(true, 1);
+        else RAYN_TACC(false, 1);
+    } else if (new_moments) RAYN_TACC(true, 0); // the moments entry
+    else RAYN_TACC(false, 0);
 #undef RAYN_TACC
 }
 

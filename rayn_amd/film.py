@@ -117,11 +117,19 @@ class Temporal:
     render_sequence: the output of the filter's first a-trous pass c' is blended into the history the next frame reprojects, c + feedback *
     (c' - c) (rayn_hip_denoise_temporal_variance_feedback_device).  It is not part of rayn_temporal_params: the strength travels as that
     entry's argument.  On the sequence above no strength above 0 lowered the error - 0.4675x at the best point (0.25, with
-    VarianceDenoise(1, 2.0, 0.4, 0.3)) against 0.4571x without feedback (DESIGN.md section 8 has the grid) - so nothing is recommended."""
+    VarianceDenoise(1, 2.0, 0.4, 0.3)) against 0.4571x without feedback (DESIGN.md section 8 has the grid) - so nothing is recommended.
+
+    `resample` ("bilinear", the default, or "catmull_rom") is the filter that resamples the history at the reprojected position.
+    "catmull_rom" (rayn_hip_temporal_accumulate_resample_device) reads the 4x4 footprint with Catmull-Rom weights wherever all 16 taps
+    count, clamps the result to the range of the four inner taps, and is the bilinear filter everywhere else; it blurs less per
+    reprojection.  Like feedback it is not part of rayn_temporal_params.  On the sequence above it did not lower the error - 0.4583x against
+    0.4571x with VarianceDenoise(1, 4.0, 0.4, 0.3), 0.4994x against 0.4940x alone - and a max_history above 4 stayed worse under both filters
+    (DESIGN.md section 8 has the grids), so nothing is recommended."""
     max_history: int = 4
     depth_tolerance: float = 0.05
     normal_min: float = -1.0
     feedback: float = 0.0
+    resample: str = "bilinear"
 
     def __post_init__(self):
         if isinstance(self.max_history, bool) or not isinstance(self.max_history, (int, np.integer)) or not 1 <= self.max_history <= 65536:
@@ -138,9 +146,14 @@ class Temporal:
             raise ValueError(f"Temporal.normal_min must be in [-1, 1], got {self.normal_min!r}")
         if not 0.0 <= float(self.feedback) <= 1.0:  # a NaN fails both
             raise ValueError(f"Temporal.feedback must be finite and in [0, 1], got {self.feedback!r}")
+        if not isinstance(self.resample, str) or self.resample not in _abi.TEMPORAL_RESAMPLE:
+            raise ValueError(f"Temporal.resample must be one of {sorted(_abi.TEMPORAL_RESAMPLE)}, got {self.resample!r}")
 
     def to_abi(self):
         return _abi.TemporalParams(int(self.max_history), float(self.depth_tolerance), float(self.normal_min))
+
+    def resample_to_abi(self):
+        return _abi.TemporalResampleParams(_abi.TEMPORAL_RESAMPLE[self.resample])
 
 
 def gbuffer_scratch_bytes(width, height):
@@ -480,7 +493,10 @@ class Context:
 
         With d_new_moments (a uint8 CUDA tensor of temporal_moments_bytes; d_prev_moments beside d_prev_history, None with it) the call
         goes through rayn_hip_temporal_accumulate_moments_device, which also carries the first and second moment of the luminance through
-        the same reprojection - what denoise_temporal_variance reads; colour and history are the same bits.  Both None: the plain entry."""
+        the same reprojection - what denoise_temporal_variance reads; colour and history are the same bits.  Both None: the plain entry.
+
+        temporal.resample == "bilinear" calls these two entries; "catmull_rom" goes through rayn_hip_temporal_accumulate_resample_device
+        instead, with or without moments, under the same rules."""
         import torch
         n = int(params.width) * int(params.height)
         for key, t, floats in (("color", d_film.get("color"), 3), ("normal", d_film.get("normal"), 3), ("records", d_gbuffer.get("records"), 4)):
@@ -499,6 +515,7 @@ class Context:
         nbytes = d_new_history.numel() if d_prev_history is None else min(d_new_history.numel(), d_prev_history.numel())
         tp = temporal.to_abi()
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        mbytes = 0
         if d_prev_moments is not None or d_new_moments is not None:
             for name, t in (("d_prev_moments", d_prev_moments), ("d_new_moments", d_new_moments)):
                 if t is not None and not (t.dtype == torch.uint8 and t.is_contiguous()):
@@ -506,6 +523,16 @@ class Context:
             if d_new_moments is None:
                 raise ValueError("d_new_moments must be a contiguous uint8 tensor")
             mbytes = d_new_moments.numel() if d_prev_moments is None else min(d_new_moments.numel(), d_prev_moments.numel())
+        if temporal.resample != "bilinear":
+            rp = temporal.resample_to_abi()
+            self._chk(self._L.rayn_hip_temporal_accumulate_resample_device(
+                self.h, C.byref(params), C.byref(tp), C.byref(rp), None if prev_camera is None else C.byref(prev_camera), float(prev_time_start),
+                C.c_void_p(d_film["color"].data_ptr()), C.c_void_p(d_film["normal"].data_ptr()), C.c_void_p(d_gbuffer["records"].data_ptr()),
+                C.c_void_p(obj.data_ptr()), None if d_prev_history is None else C.c_void_p(d_prev_history.data_ptr()),
+                C.c_void_p(d_new_history.data_ptr()), nbytes, None if d_prev_moments is None else C.c_void_p(d_prev_moments.data_ptr()),
+                None if d_new_moments is None else C.c_void_p(d_new_moments.data_ptr()), mbytes, C.c_void_p(d_out_color.data_ptr()), C.c_void_p(s)))
+            return
+        if d_prev_moments is not None or d_new_moments is not None:
             self._chk(self._L.rayn_hip_temporal_accumulate_moments_device(
                 self.h, C.byref(params), C.byref(tp), None if prev_camera is None else C.byref(prev_camera), float(prev_time_start),
                 C.c_void_p(d_film["color"].data_ptr()), C.c_void_p(d_film["normal"].data_ptr()), C.c_void_p(d_gbuffer["records"].data_ptr()),
