@@ -689,7 +689,8 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *   result: 6 Newton-Raphson a/b, 7 IEEE a/b, 8 sqrt(a), 9/10/11 component x/y/z of v/|v| and
  *   12 |v| (a holds n xyz triples), 13 exhaustive sqrt sweep (out[i] = mismatch count over the
  *   65536 float bit patterns starting at bits(a[i])), 14 ln(a) as the Mandelbulb estimator evaluates it (dmf_logf),
- *   15 exhaustive sweep of 1 / sqrt(a) as the kernels evaluate it (rcp_sqrt_rn) against the IEEE sqrt and division (mismatch count over 65536 patterns), 16 that value.
+ *   15 exhaustive sweep of 1 / sqrt(a) as the kernels evaluate it (rcp_sqrt_rn) against the IEEE sqrt and division (mismatch count over 65536 patterns), 16 that value,
+ *   17/18/19 component x/y/z of v/b through the shared-reciprocal division div3_by (a holds n xyz triples, b the n denominators).
  *   rayn_hip_probe_shading    the shading half of the path: the SAME per-lane device functions k_raygen / k_shade_setup / k_shade_finish call, on n lanes
  *                             of caller records, under the ctx's mul_add policy.  Lane i reads in[i * IN .. +IN) and writes out[i * OUT .. +OUT):
  *     op  function (reference)                                        IN  in record                                   OUT  out record

@@ -94,22 +94,48 @@ RD f3 normalized(f3 a) { float r = rcp_sqrt_rn(mag_sq(a)); return f3{a.x * r, a.
 // so min|a_i| >= 2^-60 and m <= 2^60 put every operand and quotient inside the window where the Newton-Raphson
 // steps of an IEEE '/' need neither v_div_scale nor v_div_fixup (see div_nr); the reciprocal is refined once
 // and shared.  Anything else (zero components, NaN, extreme exponents) takes the IEEE divisions.
+// The three quotients of div_nr for ONE denominator: v_rcp_f32 and its Newton-Raphson step once, then per component the product and div_nr's
+// two residual corrections (3 + 3 x 5 instructions, one transcendental).  No guard: the callers below own the window test.
+RD f3 div3_core(f3 a, float m) {
+    float r = __builtin_amdgcn_rcpf(m);
+    const float e0 = __builtin_fmaf(-m, r, 1.0f);
+    r = __builtin_fmaf(e0, r, r);
+    f3 q = f3{a.x * r, a.y * r, a.z * r};
+    q.x = __builtin_fmaf(__builtin_fmaf(-m, q.x, a.x), r, q.x);
+    q.y = __builtin_fmaf(__builtin_fmaf(-m, q.y, a.y), r, q.y);
+    q.z = __builtin_fmaf(__builtin_fmaf(-m, q.z, a.z), r, q.z);
+    q.x = __builtin_fmaf(__builtin_fmaf(-m, q.x, a.x), r, q.x);
+    q.y = __builtin_fmaf(__builtin_fmaf(-m, q.y, a.y), r, q.y);
+    q.z = __builtin_fmaf(__builtin_fmaf(-m, q.z, a.z), r, q.z);
+    return q;
+}
 RD f3 div_by_mag(f3 a, float m) {
     const float mn = __builtin_fminf(__builtin_fminf(__builtin_fabsf(a.x), __builtin_fabsf(a.y)), __builtin_fabsf(a.z));
-    if (mn >= 8.6736174e-19f && m <= 1.1529215e18f) {
-        float r = __builtin_amdgcn_rcpf(m);
-        const float e0 = __builtin_fmaf(-m, r, 1.0f);
-        r = __builtin_fmaf(e0, r, r);
-        f3 q = f3{a.x * r, a.y * r, a.z * r};
-        q.x = __builtin_fmaf(__builtin_fmaf(-m, q.x, a.x), r, q.x);
-        q.y = __builtin_fmaf(__builtin_fmaf(-m, q.y, a.y), r, q.y);
-        q.z = __builtin_fmaf(__builtin_fmaf(-m, q.z, a.z), r, q.z);
-        q.x = __builtin_fmaf(__builtin_fmaf(-m, q.x, a.x), r, q.x);
-        q.y = __builtin_fmaf(__builtin_fmaf(-m, q.y, a.y), r, q.y);
-        q.z = __builtin_fmaf(__builtin_fmaf(-m, q.z, a.z), r, q.z);
-        return q;
-    }
+    if (mn >= 8.6736174e-19f && m <= 1.1529215e18f) return div3_core(a, m);
     return f3{a.x / m, a.y / m, a.z / m};
+}
+// v / m for ANY denominator (not only m = mag(v)): the three IEEE quotients, bit for bit.
+// Window (one test per lane): m in [2^-60, 2^60) - positive - and every |v_i| in [2^-60, 2^60).  Then
+//  * r = rcp(m) and its refinement are normal numbers in (2^-60, 2^60], e0 = 1 - m r is exact in the fma and |e0| <= 2^-22;
+//  * every quotient lies in (2^-120, 2^120): a normal number, 6 binades from either exponent limit, so neither the product v_i r nor a
+//    residual v_i - m q (>= 2^-60 2^-25, exact in the fma) nor the corrected quotient can underflow or overflow - the two things
+//    v_div_scale / v_div_fixup exist for.  What remains of hipcc's IEEE '/' is div_nr's sequence, which is what div3_core runs.
+//  The ratio condition |v_i| / m in [2^-126, 2^128) is implied by the window and needs no test of its own.
+// Everything else takes the literal divisions: a zero component (the corrections lose the sign of -0 / m: fma(-m, -0, -0) is +0),
+// denormals, |v_i| or m >= 2^60, m <= 0, infinities, NaN.  The bit patterns of [2^-60, 2^60) are the contiguous integers
+// [0x21800000, 0x5D800000), so a window test is one subtract and one unsigned compare; a negative or NaN m fails it by its sign bit.
+// The general test costs 11 instructions where div_by_mag's costs 5 (it may assume m >= |v_i|), which is why the normalisations keep
+// div_by_mag; this form is for a denominator that is not the vector's own length.
+// One denominator significand per binade is left out as well: all ones (m = 2^k (2 - 2^-23)).  1 / m then lies 2^-48 above a rounding tie of the
+// reciprocal and a power-of-two numerator's quotient is only returned when v_rcp_f32 happens to deliver the correctly rounded value; with the
+// 1-ulp error its specification allows, the corrections stop one ulp short (Markstein's exception, as in rcp_sqrt_rn; tests/test_div3.py).
+RD bool in_div_window(uint32_t bits) { return bits - 0x21800000u < 0x3C000000u && (bits & 0x7FFFFFu) != 0x7FFFFFu; }
+RD f3 div3_by(f3 v, float m) {
+    const uint32_t ax = __float_as_uint(v.x) & 0x7FFFFFFFu, ay = __float_as_uint(v.y) & 0x7FFFFFFFu, az = __float_as_uint(v.z) & 0x7FFFFFFFu;
+    const uint32_t lo = ax < ay ? (ax < az ? ax : az) : (ay < az ? ay : az);
+    const uint32_t hi = ax > ay ? (ax > az ? ax : az) : (ay > az ? ay : az);
+    if (lo >= 0x21800000u && hi < 0x5D800000u && in_div_window(__float_as_uint(m))) return div3_core(v, m);
+    return f3{v.x / m, v.y / m, v.z / m};
 }
 RD f3 cross(f3 a, f3 b) {
     return f3{muladd(a.y, b.z, -a.z * b.y), muladd(a.z, b.x, -a.x * b.z), muladd(a.x, b.y, -a.y * b.x)};

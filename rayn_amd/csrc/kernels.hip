@@ -718,8 +718,8 @@ __global__ void __launch_bounds__(256, SETUP_WAVES) k_shade_setup(const DScene* 
         f3 dir = b - a;
         const float dist = mag(dir);
         dir = div_by_mag(dir, dist);
-        for (uint32_t k = 0; k < sc.n_hitables; k++)
-            if (sc.h[k].kind == RAYN_HITABLE_SPHERE && sphere_occluded_dir(sc.h[k], a, dir, dist, t0) == 0.0f) return false;
+        for (uint32_t m = sc.sphere_mask; m; m &= m - 1u) // the analytic spheres, in index order (build_scene): scalar bit scan, no kind test per hitable
+            if (sphere_occluded_dir(sc.h[__builtin_ctz(m)], a, dir, dist, t0) == 0.0f) return false;
         return true;
     };
     f3 o = f3{0, 0, 0}, d = f3{0, 0, 0}, rad = f3{0, 0, 0}, thr = f3{0, 0, 0}, point = f3{0, 0, 0}, normal = f3{0, 0, 1};
@@ -1876,6 +1876,11 @@ __global__ void k_probe_detmath(uint32_t op, const float* __restrict__ a, const 
         break;
     }
     case 16: r = rcp_sqrt_rn(a[i]); break;
+    case 17: case 18: case 19: { // div3_by: a holds n xyz triples, b the n denominators
+        const f3 q = div3_by(f3{a[3 * i], a[3 * i + 1], a[3 * i + 2]}, b[i]);
+        r = op == 17 ? q.x : (op == 18 ? q.y : q.z);
+        break;
+    }
     default: r = a[i] / b[i]; break;
     }
     out[i] = r;

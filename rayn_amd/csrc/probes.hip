@@ -145,7 +145,7 @@ int rayn_hip_probe_detmath(rayn_ctx* ctx, uint32_t op, const float* a, const flo
     const KernelSet K = kernel_set(ctx->cfg->fma_policy);
     HIPCHK(hipSetDevice(ctx->device));
     DevBuf d_a, d_b, d_out;
-    const size_t na = (op >= 9 && op <= 12) ? (size_t)n * 3 : (size_t)n; // ops 9..12 read xyz triples from a
+    const size_t na = ((op >= 9 && op <= 12) || (op >= 17 && op <= 19)) ? (size_t)n * 3 : (size_t)n; // ops 9..12 and 17..19 read xyz triples from a
     HIPCHK(d_a.alloc(na * 4)); HIPCHK(d_b.alloc((size_t)n * 4)); HIPCHK(d_out.alloc((size_t)n * 4));
     HIPCHK(hipMemcpy(d_a.p, a, na * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_b.p, b, (size_t)n * 4, hipMemcpyHostToDevice));
     K.probe_detmath(ctx->stream, op, d_a.as<float>(), d_b.as<float>(), d_out.as<float>(), n);
