@@ -711,7 +711,22 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *         with aux = the RAYN_FIS_TABLE_SIZE-float inverse CDF (aux is ignored by the other ops)
  *   Camera closures (rayn_camera.animated) are evaluated at t0, which the reference takes from LANE 0 of the ray-gen packet (a caller comparing
  *   with a 4-wide packet passes one t0 per group of four lanes).  Op 6 rejects Sky (its f panics in the reference) and op 8 takes only Lambertian and
- *   Dielectric: Sky and Emissive never scatter (receives_light is false), so those paths are never reached and are not probed. */
+ *   Dielectric: Sky and Emissive never scatter (receives_light is false), so those paths are never reached and are not probed.
+ *   rayn_hip_probe_queue      the queue stages of ONE depth through the PRODUCT kernels, launched as the depth loop launches them, on a caller-built ray queue
+ *                             (no scene, no world needed): stage 0 = bin (k_group_hist, k_scan_tile, k_tile_prefix, k_bin_scatter: object-major, insertion-ordered,
+ *                             x4-padded packets per tile), stage 1 = repack (k_scan_tile, k_tile_prefix, k_compact_scatter: the stable repack of the survivors).
+ *     in   nclass 1..16; tile_groups[n_tiles] = 64-entry groups each tile owns in the ray queue (tiles back to back, 0 allowed); q[e] / ent_obj[e] for the
+ *          64 * sum(tile_groups) entries: the queue reference (< n_refs, or 0xFFFFFFFF for a padding entry) and the object byte (a class < nclass, or 0xFF for
+ *          a miss; a padding entry carries 0xFF); survive[n_refs] = what the shading kernel would decide for each reference (the probe builds the per-group
+ *          survivor ballots and counts from it on the host, from the binned queue as the device left it: invalid slots are dead); cap_groups_bin /
+ *          cap_groups_repack = the queue capacities the two k_tile_prefix launches guard; max_entries / max_slots = the upper bounds the grids are sized by
+ *          (the kernels take the actual counts from the control block, so larger is allowed); sentinel = a word that is neither 0xFFFFFFFF nor a reference.
+ *     out  out_bq / out_qn [out_slots]: the binned queue and the next ray queue.  out_slots >= the slots the input's binned queue needs; every device
+ *          buffer is sized by it and not by the caps, and both queues start filled with the sentinel, so a refused stage writes nothing anywhere and a
+ *          stray write is visible.  out_tile[n_tiles][5] = output group begin, count of the bin stage; begin, count of the repack; the tile's base_hist
+ *          entry.  out_cls_cnt / out_cls_base [n_tiles][16] as the bin stage left them.
+ *     ctl_io[12], in and out: q_groups, q_valid, b_groups, b_valid, overflow, segments, shaded_slots, entries_sum, next_sum, job_count, head_shadow,
+ *          head_extend of the device control block.  On entry the start values (q_groups is taken from tile_groups instead); on return the final ones. */
 int rayn_hip_probe_sdf_dist(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t hitable_index,
                             const float* pts_xyz, float* out, uint32_t n);
 int rayn_hip_probe_extend(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t depth,
@@ -723,6 +738,12 @@ int rayn_hip_probe_detmath(rayn_ctx* ctx, uint32_t op, const float* a, const flo
                            uint32_t n);
 int rayn_hip_probe_shading(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t op, uint32_t index,
                            const float* in, float* out, const float* aux, uint32_t n);
+int rayn_hip_probe_queue(rayn_ctx* ctx, uint32_t nclass, uint32_t n_tiles, const uint32_t* tile_groups,
+                         const uint32_t* q, const uint8_t* ent_obj, const uint8_t* survive, uint32_t n_refs,
+                         uint32_t cap_groups_bin, uint32_t cap_groups_repack, uint32_t max_entries,
+                         uint32_t max_slots, uint32_t sentinel, uint32_t out_slots, uint32_t* out_bq,
+                         uint32_t* out_qn, uint32_t* out_tile, uint32_t* out_cls_cnt,
+                         uint32_t* out_cls_base, uint64_t* ctl_io);
 
 #ifdef __cplusplus
 }

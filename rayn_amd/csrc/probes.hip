@@ -1,4 +1,4 @@
-// probes.hip — the test probes of the C ABI (rayn_hip_probe_*): per-lane device primitives and the PRODUCT march kernels on caller data.
+// probes.hip — the test probes of the C ABI (rayn_hip_probe_*): per-lane device primitives, the PRODUCT march kernels and the PRODUCT queue stages on caller data.
 // Test infrastructure; defines no kernels (kernels.hip holds the probe kernels).
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -179,6 +179,120 @@ int rayn_hip_probe_shading(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t o
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out, d_out.p, nout * 4, hipMemcpyDeviceToHost));
+    return RAYN_OK;
+}
+// The two queue stages of one depth (bin: k_group_hist, k_scan_tile, k_tile_prefix, k_bin_scatter; repack: k_scan_tile, k_tile_prefix, k_compact_scatter) on a
+// caller-built ray queue, launched with the arguments of run_worker's depth loop.  The survivor ballots and counts k_shade_setup would write between the stages
+// are built here on the host from the binned queue as the device left it.  Both output queues hold out_slots slots (>= the input's full need, whatever the
+// cap_groups arguments say) and start filled with `sentinel`, so the overflow guard runs without an address leaving its buffer and a stray write shows.
+int rayn_hip_probe_queue(rayn_ctx* ctx, uint32_t nclass, uint32_t n_tiles, const uint32_t* tile_groups, const uint32_t* q, const uint8_t* ent_obj,
+                         const uint8_t* survive, uint32_t n_refs, uint32_t cap_groups_bin, uint32_t cap_groups_repack, uint32_t max_entries,
+                         uint32_t max_slots, uint32_t sentinel, uint32_t out_slots, uint32_t* out_bq, uint32_t* out_qn, uint32_t* out_tile,
+                         uint32_t* out_cls_cnt, uint32_t* out_cls_base, uint64_t* ctl_io) {
+    if (!ctx) return RAYN_ERR_INVALID_ARG;
+    if (!tile_groups || !q || !ent_obj || !survive || !out_bq || !out_qn || !out_tile || !out_cls_cnt || !out_cls_base || !ctl_io)
+        return fail(ctx, RAYN_ERR_INVALID_ARG, "null buffer");
+    if (nclass == 0 || nclass > SCAN_NC_BIN) return fail(ctx, RAYN_ERR_INVALID_ARG, "nclass outside 1..16");
+    if (n_tiles == 0 || n_tiles > (1u << 20)) return fail(ctx, RAYN_ERR_INVALID_ARG, "n_tiles outside 1..2^20");
+    if (max_entries > (1u << 27) || max_slots > (1u << 27) || out_slots > (1u << 27)) return fail(ctx, RAYN_ERR_INVALID_ARG, "probe size out of range");
+    if (sentinel == INVALID || sentinel < n_refs) return fail(ctx, RAYN_ERR_INVALID_ARG, "the sentinel must be neither INVALID nor a queue reference");
+    for (int k = 0; k < 12; k++) if (k != 5 && k != 6 && k != 7 && k != 8 && ctl_io[k] > 0xFFFFFFFFull) return fail(ctx, RAYN_ERR_INVALID_ARG, "a 32-bit field of ctl_io is out of range");
+    size_t groups = 0;
+    for (uint32_t k = 0; k < n_tiles; k++) {
+        groups += tile_groups[k];
+        if (groups > (1u << 20)) return fail(ctx, RAYN_ERR_INVALID_ARG, "more than 2^26 queue entries");
+    }
+    const size_t n_entries = groups * 64;
+    // the full need of the bin stage (the repack's is at most that: survivors of a tile's segment, unpadded) - and every entry must be binnable
+    size_t need_groups = 0;
+    {
+        size_t e = 0;
+        for (uint32_t k = 0; k < n_tiles; k++) {
+            uint32_t cnt[SCAN_NC_BIN] = {0};
+            for (size_t end = e + (size_t)tile_groups[k] * 64; e < end; e++) {
+                const uint32_t o = ent_obj[e];
+                if (o != OBJ_NONE && o >= nclass) return fail(ctx, RAYN_ERR_INVALID_ARG, "an object byte is neither a class below nclass nor OBJ_NONE");
+                if (q[e] == INVALID ? o != OBJ_NONE : q[e] >= n_refs) return fail(ctx, RAYN_ERR_INVALID_ARG, "a queue entry is a padding entry with an object, or a reference >= n_refs");
+                if (o != OBJ_NONE) cnt[o]++;
+            }
+            size_t total = 0;
+            for (uint32_t c = 0; c < nclass; c++) total += (cnt[c] + 3u) & ~3u;
+            need_groups += (total + 63) / 64;
+        }
+    }
+    if (out_slots < need_groups * 64) return fail(ctx, RAYN_ERR_INVALID_ARG, "out_slots is smaller than the binned queue the input needs");
+    const KernelSet K = kernel_set(ctx->cfg->fma_policy);
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t QG = groups + 1, BG = out_slots / 64 + 1, NT = n_tiles;
+    DevBuf d_q, d_obj, d_bq, d_qn, d_alive, d_grp_cnt, d_grp_base, d_grp_tile, d_bgrp_cnt, d_bgrp_base, d_bgrp_tile, d_tgbA, d_tgcA, d_tgbB, d_tgcB, d_total,
+        d_valid, d_out_base, d_cls_cnt, d_cls_base, d_hist, d_ctl;
+    HIPCHK(d_q.alloc(n_entries * 4)); HIPCHK(d_obj.alloc(n_entries)); HIPCHK(d_bq.alloc((size_t)out_slots * 4)); HIPCHK(d_qn.alloc((size_t)out_slots * 4));
+    HIPCHK(d_alive.alloc(BG * 8)); HIPCHK(d_grp_cnt.alloc(QG * SCAN_NC_BIN)); HIPCHK(d_grp_base.alloc(QG * SCAN_NC_BIN * 4)); HIPCHK(d_grp_tile.alloc(QG * 4));
+    HIPCHK(d_bgrp_cnt.alloc(BG)); HIPCHK(d_bgrp_base.alloc(BG * 4)); HIPCHK(d_bgrp_tile.alloc(BG * 4));
+    HIPCHK(d_tgbA.alloc(NT * 4)); HIPCHK(d_tgcA.alloc(NT * 4)); HIPCHK(d_tgbB.alloc(NT * 4)); HIPCHK(d_tgcB.alloc(NT * 4));
+    HIPCHK(d_total.alloc(NT * 4)); HIPCHK(d_valid.alloc(NT * 4)); HIPCHK(d_out_base.alloc(NT * 4));
+    HIPCHK(d_cls_cnt.alloc(NT * SCAN_NC_BIN * 4)); HIPCHK(d_cls_base.alloc(NT * SCAN_NC_BIN * 4)); HIPCHK(d_hist.alloc(NT * 4)); HIPCHK(d_ctl.alloc(sizeof(DCtl)));
+    std::vector<uint32_t> tgb(n_tiles), fill(out_slots, sentinel);
+    { uint32_t g = 0; for (uint32_t k = 0; k < n_tiles; k++) { tgb[k] = g; g += tile_groups[k]; } } // back to back, as k_batch_setup lays the tiles out
+    DCtl hc;
+    memset(&hc, 0, sizeof hc);
+    hc.q_groups = (uint32_t)groups; hc.q_valid = (uint32_t)ctl_io[1]; hc.b_groups = (uint32_t)ctl_io[2]; hc.b_valid = (uint32_t)ctl_io[3]; hc.overflow = (uint32_t)ctl_io[4];
+    hc.segments = ctl_io[5]; hc.shaded_slots = ctl_io[6]; hc.entries_sum = ctl_io[7]; hc.next_sum = ctl_io[8];
+    hc.job_count = (uint32_t)ctl_io[9]; hc.head_shadow = (uint32_t)ctl_io[10]; hc.head_extend = (uint32_t)ctl_io[11];
+    HIPCHK(hipMemcpy(d_q.p, q, n_entries * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_obj.p, ent_obj, n_entries, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_bq.p, fill.data(), (size_t)out_slots * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_qn.p, fill.data(), (size_t)out_slots * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_tgbA.p, tgb.data(), NT * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_tgcA.p, tile_groups, NT * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_tgbB.p, 0, NT * 4)); HIPCHK(hipMemset(d_tgcB.p, 0, NT * 4)); HIPCHK(hipMemset(d_total.p, 0, NT * 4)); HIPCHK(hipMemset(d_valid.p, 0, NT * 4));
+    HIPCHK(hipMemset(d_out_base.p, 0, NT * 4)); HIPCHK(hipMemset(d_cls_cnt.p, 0, NT * SCAN_NC_BIN * 4)); HIPCHK(hipMemset(d_cls_base.p, 0, NT * SCAN_NC_BIN * 4));
+    HIPCHK(hipMemset(d_hist.p, 0, NT * 4)); HIPCHK(hipMemcpy(d_ctl.p, &hc, sizeof hc, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize()); // the fills above ran on the null stream
+    hipStream_t s = ctx->stream;
+    DCtl* ctl = d_ctl.as<DCtl>();
+    uint32_t *tgbA = d_tgbA.as<uint32_t>(), *tgcA = d_tgcA.as<uint32_t>(), *tgbB = d_tgbB.as<uint32_t>(), *tgcB = d_tgcB.as<uint32_t>();
+    uint32_t *tile_total = d_total.as<uint32_t>(), *tile_valid = d_valid.as<uint32_t>(), *tile_out_base = d_out_base.as<uint32_t>();
+    uint32_t *tile_cls_cnt = d_cls_cnt.as<uint32_t>(), *tile_cls_base = d_cls_base.as<uint32_t>();
+    // stage 0: bin
+    K.group_hist(s, nclass, d_obj.as<uint8_t>(), max_entries, ctl, d_grp_cnt.as<uint8_t>());
+    K.scan_tile(s, n_tiles, nclass, SCAN_NC_BIN, 4, d_grp_cnt.as<uint8_t>(), tgbA, tgcA, d_grp_base.as<uint32_t>(), d_grp_tile.as<uint32_t>(), tile_total, tile_valid, tile_cls_cnt, ctl);
+    K.tile_prefix(s, n_tiles, tile_total, tile_valid, tile_out_base, tgbB, tgcB, ctl, 0, nclass, 4, tile_cls_cnt, tile_cls_base, cap_groups_bin, d_hist.as<uint32_t>());
+    K.bin_scatter(s, nclass, d_q.as<uint32_t>(), d_obj.as<uint8_t>(), d_grp_base.as<uint32_t>(), d_grp_tile.as<uint32_t>(), tile_out_base, max_entries, d_bq.as<uint32_t>(), n_tiles,
+                  tile_cls_cnt, tile_total, tile_cls_base, ctl);
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    std::vector<uint32_t> tmp(n_tiles);
+    HIPCHK(hipMemcpy(&hc, d_ctl.p, sizeof hc, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_bq, d_bq.p, (size_t)out_slots * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_cls_cnt, d_cls_cnt.p, NT * SCAN_NC_BIN * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_cls_base, d_cls_base.p, NT * SCAN_NC_BIN * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tmp.data(), d_tgbB.p, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k] = tmp[k];
+    HIPCHK(hipMemcpy(tmp.data(), d_tgcB.p, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k + 1] = tmp[k];
+    HIPCHK(hipMemcpy(tmp.data(), d_hist.p, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k + 4] = tmp[k];
+    if ((size_t)hc.b_groups * 64 > out_slots) return fail(ctx, RAYN_ERR_HIP, "internal: the bin stage reports a binned queue larger than the input's full need");
+    // what k_shade_setup would leave: one survivor ballot and one survivor count per binned group
+    std::vector<unsigned long long> alive(BG, 0ull);
+    std::vector<uint8_t> bcnt(BG, 0);
+    for (uint32_t g = 0; g < hc.b_groups; g++) {
+        unsigned long long m = 0;
+        for (uint32_t j = 0; j < 64; j++) {
+            const uint32_t r = out_bq[(size_t)g * 64 + j];
+            if (r < n_refs && survive[r]) m |= 1ull << j; // INVALID (and an unwritten slot's sentinel) are dead
+        }
+        alive[g] = m; bcnt[g] = (uint8_t)__builtin_popcountll(m);
+    }
+    HIPCHK(hipMemcpy(d_alive.p, alive.data(), BG * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_bgrp_cnt.p, bcnt.data(), BG, hipMemcpyHostToDevice));
+    // stage 1: repack
+    K.scan_tile(s, n_tiles, 1, 1, 1, d_bgrp_cnt.as<uint8_t>(), tgbB, tgcB, d_bgrp_base.as<uint32_t>(), d_bgrp_tile.as<uint32_t>(), tile_total, tile_valid, tile_cls_cnt, ctl);
+    K.tile_prefix(s, n_tiles, tile_total, tile_valid, tile_out_base, tgbA, tgcA, ctl, 1, 1, 1, tile_cls_cnt, tile_cls_base, cap_groups_repack, nullptr);
+    K.compact_scatter(s, d_bq.as<uint32_t>(), d_alive.as<unsigned long long>(), d_bgrp_base.as<uint32_t>(), d_bgrp_tile.as<uint32_t>(), tile_out_base, max_slots, d_qn.as<uint32_t>(),
+                      n_tiles, tile_total, ctl);
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(&hc, d_ctl.p, sizeof hc, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_qn, d_qn.p, (size_t)out_slots * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tmp.data(), d_tgbA.p, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k + 2] = tmp[k];
+    HIPCHK(hipMemcpy(tmp.data(), d_tgcA.p, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k + 3] = tmp[k];
+    const uint64_t fin[12] = {hc.q_groups, hc.q_valid, hc.b_groups, hc.b_valid, hc.overflow, hc.segments, hc.shaded_slots, hc.entries_sum, hc.next_sum,
+                              hc.job_count, hc.head_shadow, hc.head_extend};
+    memcpy(ctl_io, fin, sizeof fin);
     return RAYN_OK;
 }
 
