@@ -181,6 +181,23 @@ pub struct RaynTemporalResampleParams {
     pub resample: u32,
 }
 
+// The parameter block of the HDR display transform (an extension; include/rayn_hip.h: rayn_display_params).  Plain scalars, 36 bytes;
+// rayn_hip_sizeof(8) reports it.
+#[repr(C)]
+/// `tone`: 0 linear, 1 reinhard, 2 aces; `auto_exposure`: 0 manual (`exposure_scale`), 1 auto (`key`, `adapt`); `levels`: bloom levels, 0 = off
+#[derive(Clone, Copy, Debug)]
+pub struct RaynDisplayParams {
+    pub tone: u32,
+    pub auto_exposure: u32,
+    pub exposure_scale: f32,
+    pub key: f32,
+    pub adapt: f32,
+    pub iw2: f32,
+    pub levels: u32,
+    pub threshold: f32,
+    pub strength: f32,
+}
+
 #[link(name = "rayn_hip")]
 extern "C" {
     pub fn rayn_hip_create(device: i32, out: *mut *mut RaynCtx) -> i32;
@@ -275,6 +292,47 @@ extern "C" {
         d_scratch: *mut c_void,
         scratch_bytes: usize,
         feedback: f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    /// bytes of device scratch the display transform needs (0 for a size it rejects or levels > 8); host only
+    pub fn rayn_display_scratch_bytes(width: u32, height: u32, levels: u32) -> usize;
+    /// the HDR display transform of the Color kind into the 8-bit image (device pointers; `d_state`: two zeroed u32 words, auto exposure
+    /// only; `d_out_meter` / `d_out_bloom` may be null; include/rayn_hip.h has the definition)
+    pub fn rayn_hip_display_pixels_device(
+        ctx: *mut RaynCtx,
+        dp: *const RaynDisplayParams,
+        have_mask: u32,
+        transparent_background: i32,
+        width: u32,
+        height: u32,
+        d_color: *const f32,
+        d_alpha: *const f32,
+        d_background: *const f32,
+        d_state: *mut c_void,
+        d_scratch: *mut c_void,
+        scratch_bytes: usize,
+        d_out: *mut u8,
+        d_out_meter: *mut f32,
+        d_out_bloom: *mut f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    /// the same with the float plane before gamma and quantisation as the output (width * height * 3 floats, film order)
+    pub fn rayn_hip_display_color_device(
+        ctx: *mut RaynCtx,
+        dp: *const RaynDisplayParams,
+        have_mask: u32,
+        transparent_background: i32,
+        width: u32,
+        height: u32,
+        d_color: *const f32,
+        d_alpha: *const f32,
+        d_background: *const f32,
+        d_state: *mut c_void,
+        d_scratch: *mut c_void,
+        scratch_bytes: usize,
+        d_out_color: *mut f32,
+        d_out_meter: *mut f32,
+        d_out_bloom: *mut f32,
         hip_stream: *mut c_void,
     ) -> i32;
 }

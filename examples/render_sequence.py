@@ -3,7 +3,7 @@
 written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints per-frame render times and frames/s.
 
     python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise [atrous|variance]] [--temporal] [--feedback B]
-                                      [--resample {bilinear,catmull_rom}]
+                                      [--resample {bilinear,catmull_rom}] [--display [--exposure auto|EV] [--tone T] [--bloom LEVELS] [--adaptation S]]
 
 --compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
 the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
@@ -15,7 +15,10 @@ accumulated colour with the variance-guided denoiser instead, its variance estim
 (rayn_amd.VarianceDenoise(1, 4.0, 0.4, 0.3), the setting recommended for sequences); it needs --temporal.  --feedback B (in [0, 1],
 default 0 = off) also blends the output of every frame's first a-trous pass into the history the next frame reprojects, with strength B
 (rayn_amd.Temporal(feedback=B)); it needs --temporal --denoise variance.  --resample catmull_rom resamples the history with the 4x4
-Catmull-Rom filter instead of the bilinear one wherever the whole footprint is valid (rayn_amd.Temporal(resample=...)); it needs --temporal."""
+Catmull-Rom filter instead of the bilinear one wherever the whole footprint is valid (rayn_amd.Temporal(resample=...)); it needs --temporal.
+--display sends every frame's Color through the HDR display transform (rayn_amd.Display, an extension) after whatever else is on and writes
+_display after the Color file's suffix: --exposure auto (the default) or an EV, --tone aces|reinhard|linear, --bloom LEVELS (0 = off, the
+default; rayn_amd.Bloom() defaults otherwise) and --adaptation SECONDS (auto exposure follows the frames with this time constant)."""
 import argparse
 import os
 import sys
@@ -72,7 +75,16 @@ def main():
                          "needs --temporal --denoise variance")
     ap.add_argument("--resample", choices=("bilinear", "catmull_rom"), default="bilinear",
                     help="the filter that resamples the temporal history at the reprojected position (default bilinear); needs --temporal")
+    ap.add_argument("--display", action="store_true", help="send every frame's Color through the HDR display transform (rayn_amd.Display)")
+    ap.add_argument("--exposure", default="auto", help="auto (metered, the default) or an EV: the exposure scale is 2^EV; needs --display")
+    ap.add_argument("--tone", choices=("aces", "reinhard", "linear"), default="aces", help="the tone operator (default aces); needs --display")
+    ap.add_argument("--bloom", type=int, default=0, metavar="LEVELS", help="bloom over this many pyramid levels, 1..8 (0 = off, the default); needs --display")
+    ap.add_argument("--adaptation", type=float, default=None, metavar="S", help="time constant in seconds of the auto exposure's adaptation over the frames; needs --display")
     args = ap.parse_args()
+    if not args.display and (args.exposure != "auto" or args.tone != "aces" or args.bloom or args.adaptation is not None):
+        ap.error("--exposure, --tone, --bloom and --adaptation set up the display transform: add --display")
+    if args.display and args.compare_loop:
+        ap.error("--compare-loop compares with the host post-process, which has no display transform: use one or the other")
     if args.resample != "bilinear" and not args.temporal:
         ap.error("--resample chooses the resampling filter of the temporal accumulation: add --temporal")
     if (args.denoise or args.temporal) and args.compare_loop:
@@ -85,6 +97,10 @@ def main():
         ap.error("--feedback must be in [0, 1]")
     denoise = {None: None, "atrous": R.Denoise(), "variance": R.VarianceDenoise(1, 4.0, 0.4, 0.3)}[args.denoise]
     temporal = R.Temporal(feedback=args.feedback, resample=args.resample) if args.temporal else None
+    display = None
+    if args.display:
+        display = R.Display(exposure="auto" if args.exposure == "auto" else float(args.exposure), tone=args.tone,
+                            bloom=R.Bloom(levels=args.bloom) if args.bloom else None, adaptation=args.adaptation)
     first, end = (int(x) for x in args.frames.split(":"))
     frames = list(range(first, end))
     base = f"{SAMPLES * 4}_spp"
@@ -98,14 +114,14 @@ def main():
     film = R.Film(CHANNELS, (args.width, args.height))
     # warm-up: code objects, the context's first-frame arena and the writer path (not timed)
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames[:1], FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
-                         os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal)
+                         os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display)
     t0 = time.perf_counter()
     stats = film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
-                                 os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal)
+                                 os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display)
     seq_s = time.perf_counter() - t0
     for st in stats:
         print(f"frame {st['frame']:4d}: render {st['ms_total']:8.2f} ms")
-    print(f"render_sequence{' --denoise ' + str(denoise) if denoise else ''}{' --temporal ' + str(temporal) if temporal else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s "
+    print(f"render_sequence{' --denoise ' + str(denoise) if denoise else ''}{' --temporal ' + str(temporal) if temporal else ''}{' --display ' + str(display) if display else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s "
           f"(render alone: {sum(st['ms_total'] for st in stats) / len(frames):.2f} ms/frame)")
 
     if args.compare_loop:

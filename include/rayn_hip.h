@@ -303,6 +303,83 @@ int rayn_hip_denoise_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint
                             float sigma_alpha, const float* d_color, const float* d_alpha, const float* d_normal, float* d_out_color,
                             void* d_scratch, size_t scratch_bytes, void* hip_stream);
 
+/* ---- HDR display transform of the film's Color channel (an EXTENSION: rayn's save_to clamps the film to [0, 1]) ------------------
+ * Auto exposure, bloom and a tone operator between the float film and save_to's gamma 2.2 and 8-bit quantisation.  All arithmetic f32,
+ * no contraction, IEEE '/'; logf / expf / powf are dm_logf / dm_expf / dm_powf (rayn_detmath.h); rmin / rmax are Rust's f32::min / max
+ * (a NaN operand yields the other operand).  Film pixels in film order (bottom-up rows), n = width * height.  Only the Color kind is
+ * transformed, through the three arms of save_to that have_mask and transparent_background select.
+ *
+ * Input colour: c = color + background in the Color + Background arm, c = color in the other two.  A non-finite component of c counts
+ * as 0 in metering and in the bloom's bright pass and passes through unchanged in the final step.
+ * Luminance: lum(c) = (0.2126 c.r + 0.7152 c.g) + 0.0722 c.b.
+ *
+ * Metering (auto exposure only).  Pixel i contributes v_i = logf(rmax(lum(c_i), 1e-4f)), k_i = 1 when all three components of c_i are
+ * finite and lum(c_i) > 0, else v_i = 0, k_i = 0.  The order of the sum is fixed.  Stage 1: blocks of 256 consecutive film pixels
+ * (indices >= n contribute 0); in a block the halving tree a[j] += a[j + s] for s = 128, 64, ..., 1 (j < s); the block's partial is
+ * a[0]; the counts likewise in u32.  Stage 2: 256 accumulators, accumulator t adds the partials t, t + 256, t + 512, ... in ascending
+ * order starting from 0, then the same tree once more gives the sum S and the count N.
+ *   N == 0: the state is left as it is and the exposure scale is e = 1.
+ *   otherwise m_now = S / (float)N; m = m_now if the state's valid word is 0 or adapt == 1, else m = m_prev + (m_now - m_prev) * adapt;
+ *   the state becomes {m, 1}; e = key / expf(m).
+ * The STATE is two 32-bit words in device memory, {m (f32), valid (u32)}; all zeros = fresh.  It carries m from frame to frame.
+ * Manual exposure skips all of it: e = exposure_scale (a caller turning an EV into a scale uses 2^EV rounded to f32).
+ *
+ * Bloom (levels L in 1..8; 0 = off).  Bright pass D_0 = rmax(e * c - threshold, 0) per component, non-finite components of c read as 0.
+ * Level k has w_k = (w_k-1 + 1) / 2 by h_k = (h_k-1 + 1) / 2 pixels (a dimension that reaches 1 stays 1).  Downsample, k = 1..L:
+ *   D_k(x, y) = ((A + B) + (C + D)) * 0.25f, the taps at (2x, 2y), (2x + 1, 2y), (2x, 2y + 1), (2x + 1, 2y + 1) of level k - 1, each
+ *   coordinate clamped to the edge.
+ * Upsample: U_L = D_L, U_k = D_k + up(U_k+1) for k = L - 1 .. 0.  up is the bilinear 2x filter: along x, an even x reads the taps x / 2
+ * - 1 with weight 0.25 and x / 2 with 0.75, an odd x reads x / 2 with 0.75 and x / 2 + 1 with 0.25 (integer division, each tap clamped to
+ * the edge); the same along y; with a, b the taps of the first row and c, d those of the second,
+ *   up = wy0 * (wx0 * a + wx1 * b) + wy1 * (wx0 * c + wx1 * d).
+ * The bloom is B = U_0 * (strength / (float)(L + 1)), the scalar computed once in f32.
+ *
+ * Tone.  x = e * c + B (x = e * c without bloom), then per `tone`:
+ *   0 linear:   d = x
+ *   1 reinhard: extended Reinhard on luminance: lx = lum(x); where lx is finite and > 0, d = x * ((1 + lx * iw2) / (1 + lx)), else d = x;
+ *               iw2 = 1 / (white * white) is the caller's
+ *   2 aces:     Narkowicz's fit per component: y = rmax(x, 0), d = (y * (2.51f * y + 0.03f)) / (y * (2.43f * y + 0.59f) + 0.14f)
+ * Output: the arm's own chain of save_to on d - Color + Alpha: quant8(gamma22(saturate1(d))) with the alpha beside it; Color +
+ * Background: quant8(gamma22(saturate1(d))), the background being in c already; Color only: quant8(gamma22(d)) - rows flipped top-down.
+ * With manual exposure_scale 1, linear and no bloom, d has the bits of c and the image is that of rayn_hip_save_to_pixels_device. */
+typedef struct {
+    uint32_t tone;
+    uint32_t auto_exposure;
+    float exposure_scale;
+    float key;
+    float adapt;
+    float iw2;
+    uint32_t levels;
+    float threshold;
+    float strength;
+} rayn_display_params;
+/* tone: 0 linear, 1 reinhard, 2 aces.  auto_exposure: 0 manual (exposure_scale, finite and >= 0), 1 auto (key finite and > 0; adapt in
+ * [0, 1]: 1 = no adaptation).  iw2: finite and >= 0, read by reinhard.  levels: bloom levels, 0 = off, at most 8; threshold finite,
+ * strength finite and >= 0.
+ * Bytes of device scratch the two display entries need for a width x height film with `levels` bloom levels: a 256-byte header, the
+ * metering partials and levels 1 .. L as 16-byte records (0 for a size they reject or levels > 8).  Host only; needs no GPU. */
+size_t rayn_display_scratch_bytes(uint32_t width, uint32_t height, uint32_t levels);
+/* Enqueue the transform and the Color arm's post-process on 'hip_stream' (NULL = the ctx's own stream; not waited for), on the ctx's GPU
+ * (devices[0] of a multi-device ctx).  have_mask, transparent_background, width, height and the DEVICE film pointers as
+ * rayn_hip_save_to_pixels_device takes them for the Color kind (a channel the arm does not read may be NULL).  d_state: the two-word
+ * state, needed with auto exposure only.  d_scratch: 16-byte aligned, at least rayn_display_scratch_bytes; needed with auto exposure or
+ * bloom only.  d_out receives width * height * bpp bytes, rows top-down.  Optional outputs, NULL to skip: d_out_meter, 2 floats {m, e}
+ * (m as the state holds it after the call, 0 with manual exposure); d_out_bloom, the plane B as width * height * 3 floats in film
+ * order (written with bloom on only).  The exposure scale never leaves the device and the call does not synchronise.  The inputs are
+ * not modified.  RAYN_ERR_INVALID_ARG with a last error text for: a channel combination the reference rejects (its Err text), a
+ * zero-sized image or width * height >= 2^31, an unknown tone, levels > 8, parameters outside the ranges above, a NULL state with auto
+ * exposure, a NULL buffer, and a NULL, misaligned or too small scratch where one is needed. */
+int rayn_hip_display_pixels_device(rayn_ctx* ctx, const rayn_display_params* dp, uint32_t have_mask, int transparent_background,
+                                   uint32_t width, uint32_t height, const float* d_color, const float* d_alpha, const float* d_background,
+                                   void* d_state, void* d_scratch, size_t scratch_bytes, uint8_t* d_out, float* d_out_meter,
+                                   float* d_out_bloom, void* hip_stream);
+/* The same with the float plane d as the output: d_out_color receives width * height * 3 floats in film order, before the arm's
+ * saturate / gamma / quantise (so that a test is not blinded by the 8-bit quantisation).  It must not be d_color or d_background. */
+int rayn_hip_display_color_device(rayn_ctx* ctx, const rayn_display_params* dp, uint32_t have_mask, int transparent_background,
+                                  uint32_t width, uint32_t height, const float* d_color, const float* d_alpha, const float* d_background,
+                                  void* d_state, void* d_scratch, size_t scratch_bytes, float* d_out_color, float* d_out_meter,
+                                  float* d_out_bloom, void* hip_stream);
+
 /* ---- progressive rendering (an EXTENSION: rayn carries only an unused progressive_epoch counter, src/film.rs:178-179) ------------
  * A progressive render is a series of EPOCHS: ordinary renders of the same frame, each under its own sample tables, whose finished
  * films are accumulated.  Everything here happens to finished films; the integrator and the film resolve are not involved.
@@ -657,7 +734,7 @@ int rayn_hip_set_cold_bytes(rayn_ctx* ctx, uint64_t bytes);
 int rayn_hip_fma_policy(void);
 int rayn_hip_set_fma_policy(rayn_ctx* ctx, int policy);
 /* sizeof() of the ABI structs as compiled: 0 world_desc, 1 frame_params, 2 stats, 3 hitable,
- * 4 material, 5 light, 6 camera, 7 temporal_resample_params — lets a binding verify its layout. */
+ * 4 material, 5 light, 6 camera, 7 temporal_resample_params, 8 display_params — lets a binding verify its layout. */
 size_t rayn_hip_sizeof(int which);
 /* "" for the product build of the library; the VARIANT name of a `make variant` build (timing experiments: such a build is
  * only ever loaded through RAYN_HIP_LIB + RAYN_HIP_ALLOW_VARIANT=1, and bench.py prints the name in its result line). */

@@ -327,6 +327,25 @@ inline int temporal_accumulate_resample(rayn_ctx* ctx, const rayn_frame_params& 
                                                         d_new_moments, moments_bytes, d_out_color, hip_stream);
 }
 
+// Extension (include/rayn_hip.h: the HDR display transform): auto exposure, bloom and tone mapping of the Color kind in front of save_to's
+// gamma and quantisation.  display_params() fills the block from the terms a user thinks in - an EV (NaN = auto exposure), the Reinhard
+// white point, bloom levels (0 = off); display_pixels() is the 8-bit entry.  Device pointers; d_state (two zeroed 32-bit words) is needed
+// with auto exposure only, d_scratch (display_scratch_bytes) with auto exposure or bloom.  Returns the entry's code.
+enum class Tone : uint32_t { Linear = 0, Reinhard = 1, Aces = 2 };
+inline size_t display_scratch_bytes(Extent2u res, uint32_t levels) { return rayn_display_scratch_bytes(res.w, res.h, levels); }
+inline rayn_display_params display_params(Tone tone, float ev, float key = 0.18f, float white = 4.0f, uint32_t levels = 0,
+                                          float threshold = 1.0f, float strength = 0.5f, float adapt = 1.0f) {
+    const bool automatic = ev != ev;
+    return rayn_display_params{static_cast<uint32_t>(tone), automatic ? 1u : 0u, automatic ? 1.0f : static_cast<float>(std::exp2(static_cast<double>(ev))),
+                               key, adapt, 1.0f / (white * white), levels, threshold, strength};
+}
+inline int display_pixels(rayn_ctx* ctx, const rayn_display_params& dp, uint32_t have_mask, bool transparent_background, Extent2u res,
+                          const float* d_color, const float* d_alpha, const float* d_background, void* d_state, void* d_scratch,
+                          size_t scratch_bytes, uint8_t* d_out, void* hip_stream = nullptr) {
+    return rayn_hip_display_pixels_device(ctx, &dp, have_mask, transparent_background ? 1 : 0, res.w, res.h, d_color, d_alpha, d_background, d_state,
+                                          d_scratch, scratch_bytes, d_out, nullptr, nullptr, hip_stream);
+}
+
 // ---- setup::setup() (src/setup.rs:46-170) with the resolution as an argument ---------------------
 namespace setup {
 constexpr float WORLD_RADIUS = 100.0f;

@@ -73,6 +73,13 @@ class TemporalResampleParams(C.Structure):  # rayn_temporal_resample_params
     _fields_ = [("resample", C.c_uint32)]
 
 
+class DisplayParams(C.Structure):  # rayn_display_params
+    _fields_ = [("tone", C.c_uint32), ("auto_exposure", C.c_uint32), ("exposure_scale", C.c_float), ("key", C.c_float), ("adapt", C.c_float),
+                ("iw2", C.c_float), ("levels", C.c_uint32), ("threshold", C.c_float), ("strength", C.c_float)]
+
+
+DISPLAY_TONE = {"linear": 0, "reinhard": 1, "aces": 2}  # rayn_display_params.tone by the name rayn_amd.Display takes
+
 TEMPORAL_RESAMPLE = {"bilinear": 0, "catmull_rom": 1}  # rayn_temporal_resample_params.resample by the name rayn_amd.Temporal takes
 
 MOMENTS_BYTES_PER_PIXEL = 8  # one float2 (m1, m2) per pixel beside a temporal history

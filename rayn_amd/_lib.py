@@ -43,6 +43,7 @@ EXPORTS = [
     "rayn_gbuffer_scratch_bytes", "rayn_hip_gbuffer_device", "rayn_temporal_history_bytes", "rayn_hip_temporal_accumulate_device",
     "rayn_temporal_moments_bytes", "rayn_hip_temporal_accumulate_moments_device", "rayn_hip_denoise_temporal_variance_device",
     "rayn_hip_denoise_temporal_variance_feedback_device", "rayn_hip_temporal_accumulate_resample_device",
+    "rayn_display_scratch_bytes", "rayn_hip_display_pixels_device", "rayn_hip_display_color_device",
 ]
 
 
@@ -127,6 +128,10 @@ def lib():
                                                                 + [C.c_size_t, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp])
         L.rayn_hip_denoise_temporal_variance_feedback_device.argtypes = ([vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float] + [vp] * 5
                                                                          + [C.c_size_t, vp, C.c_size_t, vp, vp, vp, C.c_size_t, C.c_float, vp])
+        L.rayn_display_scratch_bytes.restype = C.c_size_t
+        L.rayn_display_scratch_bytes.argtypes = [C.c_uint32] * 3
+        for fn in (L.rayn_hip_display_pixels_device, L.rayn_hip_display_color_device):
+            fn.argtypes = [vp, C.POINTER(_abi.DisplayParams), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32] + [vp] * 5 + [C.c_size_t] + [vp] * 4
         L.rayn_sets_1d.restype = C.c_uint32
         L.rayn_sets_1d.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_sets_2d.restype = C.c_uint32

@@ -20,6 +20,7 @@
 #include "driver.h"
 #include "tiles.h"
 #include "save_to.h"
+#include "display.h"
 #include "denoise.h"
 #include "denoise_variance.h"
 #include "progressive.h"
@@ -1016,6 +1017,35 @@ int rayn_hip_save_to_pixels_device(rayn_ctx* ctx, uint32_t kind, uint32_t have_m
     return post_enqueued(ctx);
 }
 
+// The HDR display transform (display.hip): both entries differ only in which output the final kernel writes.
+static int display_entry(rayn_ctx* ctx, const rayn_display_params* dp, uint32_t have_mask, int transparent_background, uint32_t width, uint32_t height,
+                         const float* d_color, const float* d_alpha, const float* d_background, void* d_state, void* d_scratch, size_t scratch_bytes,
+                         uint8_t* d_out8, float* d_out_color, bool want_color, float* d_out_meter, float* d_out_bloom, void* hip_stream) {
+    int arm = -1;
+    const char* why = display_check_args(dp, have_mask, transparent_background, width, height, d_color, d_alpha, d_background, d_state, d_scratch,
+                                         scratch_bytes, &arm);
+    if (!why && !(want_color ? (const void*)d_out_color : (const void*)d_out8)) why = "null buffer";
+    if (!why && want_color && (d_out_color == d_color || d_out_color == d_background)) why = "d_out_color must not be d_color or d_background";
+    hipStream_t s;
+    if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
+    launch_display(s, arm, *dp, width, height, d_color, d_alpha, d_background, d_state, d_scratch, d_out8, d_out_color, d_out_meter, d_out_bloom);
+    return post_enqueued(ctx);
+}
+
+int rayn_hip_display_pixels_device(rayn_ctx* ctx, const rayn_display_params* dp, uint32_t have_mask, int transparent_background, uint32_t width,
+                                   uint32_t height, const float* d_color, const float* d_alpha, const float* d_background, void* d_state,
+                                   void* d_scratch, size_t scratch_bytes, uint8_t* d_out, float* d_out_meter, float* d_out_bloom, void* hip_stream) {
+    return display_entry(ctx, dp, have_mask, transparent_background, width, height, d_color, d_alpha, d_background, d_state, d_scratch, scratch_bytes,
+                         d_out, nullptr, false, d_out_meter, d_out_bloom, hip_stream);
+}
+
+int rayn_hip_display_color_device(rayn_ctx* ctx, const rayn_display_params* dp, uint32_t have_mask, int transparent_background, uint32_t width,
+                                  uint32_t height, const float* d_color, const float* d_alpha, const float* d_background, void* d_state,
+                                  void* d_scratch, size_t scratch_bytes, float* d_out_color, float* d_out_meter, float* d_out_bloom, void* hip_stream) {
+    return display_entry(ctx, dp, have_mask, transparent_background, width, height, d_color, d_alpha, d_background, d_state, d_scratch, scratch_bytes,
+                         nullptr, d_out_color, true, d_out_meter, d_out_bloom, hip_stream);
+}
+
 int rayn_hip_denoise_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t iterations, float sigma_color, float sigma_normal,
                             float sigma_alpha, const float* d_color, const float* d_alpha, const float* d_normal, float* d_out_color,
                             void* d_scratch, size_t scratch_bytes, void* hip_stream) {
@@ -1354,6 +1384,7 @@ size_t rayn_hip_sizeof(int which) {
     case 5: return sizeof(rayn_light);
     case 6: return sizeof(rayn_camera);
     case 7: return sizeof(rayn_temporal_resample_params);
+    case 8: return sizeof(rayn_display_params);
     default: return 0;
     }
 }

@@ -156,6 +156,102 @@ class Temporal:
         return _abi.TemporalResampleParams(_abi.TEMPORAL_RESAMPLE[self.resample])
 
 
+def _number(owner, name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+        raise ValueError(f"{owner}.{name} must be a number, got {v!r}")
+    return float(v)
+
+
+@dataclasses.dataclass(frozen=True)
+class Bloom:
+    """The bloom of a Display: the part of the exposed colour above `threshold` (finite, >= 0), blurred over a pyramid of `levels` (1..8)
+    halvings and added back with weight `strength` (finite, >= 0) over the levels' mean."""
+    threshold: float = 1.0
+    strength: float = 0.5
+    levels: int = 5
+
+    def __post_init__(self):
+        if isinstance(self.levels, bool) or not isinstance(self.levels, (int, np.integer)) or not 1 <= self.levels <= 8:
+            raise ValueError(f"Bloom.levels must be an int in 1..8, got {self.levels!r}")
+        for name in ("threshold", "strength"):
+            f = _number("Bloom", name, getattr(self, name))
+            with np.errstate(over="ignore"):
+                ok = np.isfinite(f) and f >= 0.0 and np.isfinite(np.float32(f))  # the C entry takes it as an f32: check that value too
+            if not ok:
+                raise ValueError(f"Bloom.{name} must be finite and >= 0, got {getattr(self, name)!r}")
+
+
+@dataclasses.dataclass(frozen=True)
+class Display:
+    """Parameters of the HDR display transform of the Color channel (rayn_hip_display_pixels_device, an extension: rayn's save_to clamps
+    the film to [0, 1]; include/rayn_hip.h has the definition): exposure, optional bloom, a tone operator, then save_to's own gamma and
+    8-bit quantisation.
+
+    `exposure`: "auto" meters the film - the exposure scale is `key` (finite, > 0) over the geometric mean of the luminance - or a
+    number, an EV: the scale is 2^EV (|EV| <= 100).  `tone`: "aces" (Narkowicz's fit), "reinhard" (extended Reinhard on luminance; a
+    luminance of `white`, in [2^-30, 2^30], maps to 1) or "linear".  `bloom`: None or a Bloom.  `adaptation`: None, or the time constant in
+    seconds (finite, > 0) with which render_sequence lets the metered value follow the frames, m += (m_now - m) * (1 - exp(-dt /
+    adaptation)); a single image always takes its own metered value.
+
+    Display(exposure=0.0, tone="linear") is the identity: the image is save_to's, byte for byte."""
+    exposure: object = "auto"
+    key: float = 0.18
+    tone: str = "aces"
+    white: float = 4.0
+    bloom: object = None
+    adaptation: object = None
+
+    def __post_init__(self):
+        if isinstance(self.exposure, str):
+            if self.exposure != "auto":
+                raise ValueError(f"Display.exposure must be 'auto' or an EV number, got {self.exposure!r}")
+        elif not abs(_number("Display", "exposure", self.exposure)) <= 100.0:  # a NaN fails
+            raise ValueError(f"Display.exposure must be 'auto' or a finite EV with |EV| <= 100, got {self.exposure!r}")
+        k = _number("Display", "key", self.key)
+        with np.errstate(over="ignore"):
+            if not (np.isfinite(k) and k > 0.0 and np.isfinite(np.float32(k)) and np.float32(k) > 0.0):
+                raise ValueError(f"Display.key must be finite and > 0, got {self.key!r}")
+        if not isinstance(self.tone, str) or self.tone not in _abi.DISPLAY_TONE:
+            raise ValueError(f"Display.tone must be one of {sorted(_abi.DISPLAY_TONE)}, got {self.tone!r}")
+        if not 2.0 ** -30 <= _number("Display", "white", self.white) <= 2.0 ** 30:
+            raise ValueError(f"Display.white must be finite in [2^-30, 2^30], got {self.white!r}")
+        if self.bloom is not None and not isinstance(self.bloom, Bloom):
+            raise ValueError(f"Display.bloom must be None or a Bloom, got {self.bloom!r}")
+        if self.adaptation is not None:
+            a = _number("Display", "adaptation", self.adaptation)
+            if not (np.isfinite(a) and a > 0.0):
+                raise ValueError(f"Display.adaptation must be None or finite and > 0 seconds, got {self.adaptation!r}")
+
+    @property
+    def auto(self):
+        return isinstance(self.exposure, str)
+
+    @property
+    def levels(self):
+        return 0 if self.bloom is None else int(self.bloom.levels)
+
+    def adapt(self, dt):
+        """The blend weight of a frame `dt` seconds after the one before it: 1 - exp(-|dt| / adaptation) rounded to f32; 1 without
+        adaptation."""
+        if self.adaptation is None:
+            return 1.0
+        return float(np.float32(1.0 - np.exp(-abs(float(dt)) / float(self.adaptation))))
+
+    def to_abi(self, adapt=1.0):
+        f32 = np.float32
+        w = f32(self.white)
+        b = self.bloom
+        return _abi.DisplayParams(_abi.DISPLAY_TONE[self.tone], int(self.auto), 1.0 if self.auto else float(f32(2.0 ** float(self.exposure))),
+                                  float(self.key), float(adapt), float(f32(1.0) / (w * w)), self.levels,
+                                  0.0 if b is None else float(b.threshold), 0.0 if b is None else float(b.strength))
+
+
+def display_scratch_bytes(width, height, levels):
+    """rayn_display_scratch_bytes: bytes of device scratch the display transform needs for a width x height film with `levels` bloom
+    levels (0 for a size it rejects or levels > 8).  A manual exposure without bloom needs none."""
+    return int(lib().rayn_display_scratch_bytes(int(width), int(height), int(levels)))
+
+
 def gbuffer_scratch_bytes(width, height):
     """rayn_gbuffer_scratch_bytes: bytes of device scratch the G-buffer pass needs for a width x height film (0 for a size it rejects)."""
     return int(lib().rayn_gbuffer_scratch_bytes(int(width), int(height)))
@@ -400,6 +496,58 @@ class Context:
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
         self._chk(self._L.rayn_hip_save_to_pixels_device(self.h, int(kind), int(have_mask), int(bool(transparent_background)), int(width), int(height),
                                                          *ptrs, C.c_void_p(d_out.data_ptr()), C.c_void_p(s)))
+
+    def display_state(self):
+        """A fresh state of the display transform's auto exposure: two zeroed 32-bit words {m, valid} on the context's GPU."""
+        import torch
+        return torch.zeros(2, dtype=torch.int32, device=f"cuda:{self.device}")
+
+    def display(self, display, have_mask, transparent_background, width, height, d_film, d_out, d_state=None, d_scratch=None, adapt=1.0,
+                d_out_meter=None, d_out_bloom=None, stream=None):
+        """rayn_hip_display_pixels_device / rayn_hip_display_color_device: the HDR display transform (Display `display`) of the Color kind
+        of the device film `d_film` (as save_to_pixels takes it).  A uint8 `d_out` (width * height * bpp bytes) receives the 8-bit image,
+        rows top-down; a float32 one (width * height * 3 floats) the float plane before gamma and quantisation, in film order.  d_state
+        (display_state(); auto exposure only) carries the metered value between calls, blended with weight `adapt`; None = a fresh one.
+        d_scratch: a CUDA tensor of at least display_scratch_bytes(width, height, display.levels) bytes, allocated here when None and
+        needed.  d_out_meter (2 floats: m, e) and d_out_bloom (width * height * 3 floats) are optional float32 outputs.  Enqueued on the
+        stream, not waited for; the exposure never comes to the host."""
+        import torch
+        n = int(width) * int(height)
+        bpp = save_to_bpp(0, have_mask, transparent_background)
+        if d_out.dtype == torch.uint8:
+            fn, need = self._L.rayn_hip_display_pixels_device, n * max(bpp, 0)
+        elif d_out.dtype == torch.float32:
+            fn, need = self._L.rayn_hip_display_color_device, 3 * n
+        else:
+            raise ValueError("d_out must be a uint8 tensor (the image) or a float32 tensor (the float plane)")
+        if not (d_out.is_contiguous() and d_out.numel() >= need):
+            raise ValueError(f"d_out must be contiguous and hold at least {need} elements")
+        for name, t, floats in (("d_out_meter", d_out_meter, 2), ("d_out_bloom", d_out_bloom, 3 * n)):
+            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= floats):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of at least {floats} floats")
+        ptrs = []
+        for key, floats in (("color", 3), ("alpha", 1), ("background", 3)):
+            t = d_film.get(key)
+            if t is None:
+                ptrs.append(None)
+                continue
+            if not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= floats * n):
+                raise ValueError(f"d_film[{key!r}] must be a contiguous float32 tensor of at least {floats * n} floats")
+            ptrs.append(C.c_void_p(t.data_ptr()))
+        if display.auto and d_state is None:
+            d_state = torch.zeros(2, dtype=torch.int32, device=d_out.device)
+        if d_state is not None and not (d_state.dtype == torch.int32 and d_state.is_contiguous() and d_state.numel() >= 2):
+            raise ValueError("d_state must be a contiguous int32 tensor of 2 elements (Context.display_state())")
+        if d_scratch is None and (display.auto or display.levels):
+            d_scratch = torch.empty(max(display_scratch_bytes(width, height, display.levels), 1), dtype=torch.uint8, device=d_out.device)
+        if d_scratch is not None and not d_scratch.is_contiguous():
+            raise ValueError("d_scratch must be contiguous")
+        opt = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        dp = display.to_abi(adapt)
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._chk(fn(self.h, C.byref(dp), int(have_mask), int(bool(transparent_background)), int(width), int(height), *ptrs, opt(d_state),
+                     opt(d_scratch), 0 if d_scratch is None else d_scratch.numel() * d_scratch.element_size(), C.c_void_p(d_out.data_ptr()),
+                     opt(d_out_meter), opt(d_out_bloom), C.c_void_p(s)))
 
     def denoise(self, width, height, d_film, d_out_color, params, d_scratch=None, stream=None):
         """rayn_hip_denoise_device: the a-trous denoiser (Denoise `params`) of d_film["color"] into the float32 CUDA tensor d_out_color
@@ -816,32 +964,70 @@ class Film:
         w, h = self.res
         return self._denoise_variance(params, True)[1].cpu().numpy().reshape(h, w)
 
-    def pixels(self, kind, transparent_background=False, denoise=None):
+    def display_color(self, display, denoise=None, transparent_background=False, display_state=None, adapt=1.0):
+        """The film's Color after the HDR display transform (Display `display`, rayn_hip_display_color_device) as a float32 device tensor
+        of shape (n, 3), pixels in the film's order: exposed, bloomed and tone-mapped, before gamma and quantisation.  The input is Color
+        + Background when the film has a Background and transparent_background is false, as in save_to; with `denoise`, the denoised
+        Color.  display_state (Context.display_state()) and adapt: as Context.display; None = this image's own metering."""
+        import torch
+        if not isinstance(display, Display):
+            raise ValueError(f"display must be a Display, got {display!r}")
+        self._save_jobs([ChannelKind.Color], transparent_background)
+        w, h = self.res
+        with torch.cuda.device(self.device):
+            film = self.channels
+            if denoise is not None:
+                film = dict(film, color=self.denoised_color(denoise))
+            out = torch.empty(w * h, 3, dtype=torch.float32, device=self.device)
+            self.ctx.display(display, self.have_mask(), transparent_background, w, h, film, out, display_state, None, adapt)
+            return out
+
+    def pixels(self, kind, transparent_background=False, denoise=None, display=None, display_state=None, adapt=1.0):
         """The 8-bit image Film::save_to writes for channel `kind` (rows top-down; (h, w, 4 / 3 / 1) uint8), computed on the device
         (rayn_hip_save_to_pixels_device); only the 8-bit image is copied back.  Channels the film lacks are not read.  With `denoise`
-        (a Denoise or a VarianceDenoise), the Color image is made from denoised_color(denoise); the other channels are unchanged."""
+        (a Denoise or a VarianceDenoise), the Color image is made from denoised_color(denoise); the other channels are unchanged.
+        With `display` (a Display, an extension), the Color image goes through the HDR display transform (after the denoiser, if any;
+        rayn_hip_display_pixels_device) with display_state and adapt as Context.display takes them; the other channels ignore it."""
         import torch
         ((kind, bpp, _),) = self._save_jobs([kind], transparent_background)
+        if display is not None and not isinstance(display, Display):
+            raise ValueError(f"display must be a Display, got {display!r}")
         w, h = self.res
         with torch.cuda.device(self.device):
             film = self.channels
             if denoise is not None and kind == ChannelKind.Color:
                 film = dict(film, color=self.denoised_color(denoise))
             out = torch.empty(h * w * bpp, dtype=torch.uint8, device=self.device)
-            self.ctx.save_to_pixels(kind, self.have_mask(), transparent_background, w, h, film, out)
+            if display is not None and kind == ChannelKind.Color:
+                self.ctx.display(display, self.have_mask(), transparent_background, w, h, film, out, display_state, None, adapt)
+            else:
+                self.ctx.save_to_pixels(kind, self.have_mask(), transparent_background, w, h, film, out)
             return out.cpu().numpy().reshape(h, w, bpp)  # .cpu() waits for the current stream, where the kernels were enqueued
 
-    def save_to(self, write_channels, output_folder, base_name, transparent_background=False, denoise=None):
+    def save_to(self, write_channels, output_folder, base_name, transparent_background=False, denoise=None, display=None):
         """Film::save_to (src/film.rs:205-378) - the post-process after the hot path, arm by arm (on the device: pixels); the
         reference's Err(String) cases raise ValueError with the same text.  The PNGs are those of rayn_amd.image (host reference).
         With `denoise` (a Denoise or a VarianceDenoise, extensions), the Color image is made from the denoised Color and written as
-        {base_name}_color_denoised.png instead of {base_name}_color.png; the other channels are unchanged."""
+        {base_name}_color_denoised.png instead of {base_name}_color.png; the other channels are unchanged.  With `display` (a Display, an
+        extension) the Color image goes through the HDR display transform and its file name gets _display appended:
+        {base_name}_color_display.png, {base_name}_color_denoised_display.png."""
         os.makedirs(output_folder, exist_ok=True)
         for kind in write_channels:
             ((kind, _, suffix),) = self._save_jobs([kind], transparent_background)  # the reference fails at the first bad channel, after writing the ones before
             if denoise is not None and kind == ChannelKind.Color:
                 suffix = "color_denoised"
-            image.save(os.path.join(output_folder, f"{base_name}_{suffix}.png"), self.pixels(kind, transparent_background, denoise))
+            if display is not None and kind == ChannelKind.Color:
+                suffix += "_display"
+            image.save(os.path.join(output_folder, f"{base_name}_{suffix}.png"), self.pixels(kind, transparent_background, denoise, display))
+
+    def save_hdr(self, path, transparent_background=False):
+        """Write the float Color channel to `path` as a little-endian PFM (image.save_pfm; rows bottom-up, like the film): Color +
+        Background when the film has a Background and transparent_background is false, as save_to composes them, else Color.  Host only."""
+        rgb = self.channel(ChannelKind.Color)
+        if ChannelKind.Background in self.channel_kinds and not transparent_background:
+            with np.errstate(invalid="ignore", over="ignore"):
+                rgb = (rgb + self.channel(ChannelKind.Background)).astype(np.float32)
+        image.save_pfm(path, rgb)
 
     def render_progressive(self, world, camera, integrator, filter, tile_size, frame, time_range, samples, progressive=None, on_epoch=None,
                            resume=None):
@@ -962,7 +1148,7 @@ class Film:
         return _prog.error_map(arrays, w, h, (pr["params"].tile_w, pr["params"].tile_h), pr["noise_floor"])
 
     def render_sequence(self, world, camera, integrator, filter, tile_size, frames, frame_rate, shutter_speed, samples, write_channels,
-                        output_folder, base_name, transparent_background=False, writers=None, denoise=None, temporal=None):
+                        output_folder, base_name, transparent_background=False, writers=None, denoise=None, display=None, temporal=None):
         """rayn's main loop (src/main.rs:58-96) on the GPU: for each frame of `frames`, render_frame_into at
         frame_start = frame as f32 * (1.0 / frame_rate as f32), frame_end = frame_start + shutter_speed (f32, src/main.rs:61-62), then
         save_to(write_channels, output_folder, f"{base_name}_{frame:04d}", transparent_background).  rayn writes every frame under
@@ -1000,7 +1186,14 @@ class Film:
         i's history with that strength (rayn_hip_denoise_temporal_variance_feedback_device), so frame i + 1 reprojects what frame i's filter
         left; the file names do not change.  It needs a VarianceDenoise as `denoise` - there is nothing to feed back otherwise - and raises
         ValueError before anything renders without one.  Measured on the sequence of DESIGN.md section 8, no strength above 0 lowered the
-        error (0.4675x at best, against 0.4571x): the option is there to be measured on other scenes and sizes, not recommended."""
+        error (0.4675x at best, against 0.4571x): the option is there to be measured on other scenes and sizes, not recommended.
+
+        With `display` (a Display, an extension), every frame's Color image goes through the HDR display transform, after the temporal and
+        denoise kernels and in place of the plain Color post-process kernel, on the render stream; the file name gets _display appended to
+        whatever suffix it would have had (_color_display.png, _color_temporal_denoised_display.png, ...).  One auto-exposure state serves
+        the call: the first frame takes its own metered value, every later one blends with adapt = 1 - exp(-dt / display.adaptation), dt
+        the difference of the f32 frame starts (1 without adaptation).  The exposure stays on the device, so nothing synchronises; the
+        state and the scratch are allocated once.  display=None is the path described above, unchanged."""
         import concurrent.futures as cf
         import torch
         variance = isinstance(denoise, VarianceDenoise)
@@ -1029,6 +1222,13 @@ class Film:
             else:
                 jobs = [(kind, bpp, ("color_temporal" if denoise is None else "color_temporal_denoised") if kind == ChannelKind.Color else suffix)
                         for kind, bpp, suffix in jobs]
+        if display is not None:
+            if not isinstance(display, Display):
+                raise ValueError(f"display must be a Display, got {display!r}")
+            if ChannelKind.Color not in write_channels:
+                display = None
+            else:
+                jobs = [(kind, bpp, suffix + "_display" if kind == ChannelKind.Color else suffix) for kind, bpp, suffix in jobs]
         os.makedirs(output_folder, exist_ok=True)
         w, h = self.res
         f32 = np.float32
@@ -1074,6 +1274,11 @@ class Film:
                     d_hist = [torch.empty(temporal_history_bytes(w, h), dtype=torch.uint8, device=self.device) for _ in range(2)]
                     d_accum = torch.empty(w * h, 3, dtype=torch.float32, device=self.device)
                     prev_start = None
+                if display is not None:
+                    d_dstate = self.ctx.display_state() if display.auto else None
+                    d_dscratch = (torch.empty(display_scratch_bytes(w, h, display.levels), dtype=torch.uint8, device=self.device)
+                                  if display.auto or display.levels else None)
+                    shown_start = None  # the start of the frame the state last metered
                 h_img = [[torch.empty(h * w * bpp, dtype=torch.uint8, pin_memory=True) for _, bpp, _ in jobs] for _ in range(2)]
                 for i, frame in enumerate(frames):
                     if i:
@@ -1117,7 +1322,12 @@ class Film:
                         d_shown = dict(d_film, color=d_denoised)
                     for (kind, _, suffix), d, hbuf in zip(jobs, d_img, h_img[slot]):
                         src = d_shown if kind == ChannelKind.Color else d_film
-                        self.ctx.save_to_pixels(kind, mask, transparent_background, w, h, src, d, stream.cuda_stream)
+                        if display is not None and kind == ChannelKind.Color:
+                            adapt = 1.0 if shown_start is None else display.adapt(float(start) - float(shown_start))
+                            self.ctx.display(display, mask, transparent_background, w, h, src, d, d_dstate, d_dscratch, adapt, stream=stream.cuda_stream)
+                            shown_start = start
+                        else:
+                            self.ctx.save_to_pixels(kind, mask, transparent_background, w, h, src, d, stream.cuda_stream)
                         hbuf.copy_(d, non_blocking=True)
                     done = torch.cuda.Event()
                     done.record(stream)

@@ -96,3 +96,23 @@ def alpha_image(alpha):
 
 def save(path, img8):
     _png(path, np.ascontiguousarray(img8))
+
+
+def save_pfm(path, rgb):
+    """Write a float image (h, w, 3), rows BOTTOM-UP like the film, as a colour PFM: the header "PF", "w h", "-1.0" (a negative scale =
+    little-endian), then the rows bottom-up as little-endian float32 - the film's own order, so the floats are written as they are."""
+    a = np.ascontiguousarray(rgb, dtype="<f4")
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"save_pfm takes an (h, w, 3) image, got shape {a.shape}")
+    with open(path, "wb") as f:
+        f.write(b"PF\n%d %d\n-1.0\n" % (a.shape[1], a.shape[0]) + a.tobytes())
+
+
+def load_pfm(path):
+    """Read a colour PFM written by save_pfm (either byte order): float32 (h, w, 3), rows bottom-up."""
+    with open(path, "rb") as f:
+        magic, dims, scale = f.readline().strip(), f.readline().split(), float(f.readline())
+        if magic != b"PF" or len(dims) != 2:
+            raise ValueError(f"{path} is not a colour PFM")
+        w, h = int(dims[0]), int(dims[1])
+        return np.frombuffer(f.read(12 * w * h), dtype="<f4" if scale < 0 else ">f4").astype(F32).reshape(h, w, 3)
