@@ -803,7 +803,13 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *          stray write is visible.  out_tile[n_tiles][5] = output group begin, count of the bin stage; begin, count of the repack; the tile's base_hist
  *          entry.  out_cls_cnt / out_cls_base [n_tiles][16] as the bin stage left them.
  *     ctl_io[12], in and out: q_groups, q_valid, b_groups, b_valid, overflow, segments, shaded_slots, entries_sum, next_sum, job_count, head_shadow,
- *          head_extend of the device control block.  On entry the start values (q_groups is taken from tile_groups instead); on return the final ones. */
+ *          head_extend of the device control block.  On entry the start values (q_groups is taken from tile_groups instead); on return the final ones.
+ *   rayn_hip_probe_march_limits  the sizes that decide the MODE of the persistent march kernels, as the library was built and the context tuned: the entries a
+ *                             wave takes from its queue per atomic (chunk); the remaining-entry count below which a fetched chunk puts its wave into the endgame
+ *                             (endgame_entries; k_shadow_bulb multiplies it by its rays per lane); the grid cap (persistent_blocks, blocks of 4 waves) and
+ *                             k_shadow_bulb's rays per lane (bulb_rays) of the ctx's launch tuning.  No GPU work.  Tests size their probe inputs from these. */
+int rayn_hip_probe_march_limits(const rayn_ctx* ctx, uint32_t* chunk, uint32_t* endgame_entries,
+                                uint32_t* persistent_blocks, uint32_t* bulb_rays);
 int rayn_hip_probe_sdf_dist(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t hitable_index,
                             const float* pts_xyz, float* out, uint32_t n);
 int rayn_hip_probe_extend(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t depth,

@@ -113,8 +113,7 @@ RD float packet_time(const DScene& sc, const uint32_t* __restrict__ q, const Poo
 // next queue entry (wave-local chunk of 256 entries, refilled with ONE atomic per chunk), so every
 // loop iteration evaluates the SDF on (almost) all 64 lanes.  Results are written by entry/pool
 // index, so the fetch order never influences the output.
-constexpr uint32_t CHUNK = 256;
-constexpr uint32_t ENDGAME_ENTRIES = 256 * 32 * 64; // about one ray per resident lane of the chip
+// (CHUNK and ENDGAME_ENTRIES: kernels.h, where rayn_hip_probe_march_limits reads them too)
 
 template <bool COUNT>
 __global__ void __launch_bounds__(256) k_extend(const DScene* __restrict__ scp, uint32_t depth, const uint32_t* __restrict__ q,

@@ -139,6 +139,13 @@ int rayn_hip_probe_shadow(rayn_ctx* ctx, const rayn_frame_params* p, const float
     for (uint32_t i = 0; i < n; i++) out[i] = vis[i] == 1 ? 1.0f : 0.0f;
     return RAYN_OK;
 }
+// the sizes that decide whether a launch of the march kernels reaches its steady state (kernels.h) + the two launch-tuning values of this context that enter them
+int rayn_hip_probe_march_limits(const rayn_ctx* ctx, uint32_t* chunk, uint32_t* endgame_entries, uint32_t* persistent_blocks, uint32_t* bulb_rays) {
+    if (!ctx || !chunk || !endgame_entries || !persistent_blocks || !bulb_rays) return RAYN_ERR_INVALID_ARG;
+    *chunk = CHUNK; *endgame_entries = ENDGAME_ENTRIES;
+    *persistent_blocks = ctx->tun.persistent_blocks; *bulb_rays = ctx->tun.bulb_rays;
+    return RAYN_OK;
+}
 int rayn_hip_probe_detmath(rayn_ctx* ctx, uint32_t op, const float* a, const float* b, float* out, uint32_t n) {
     if (!ctx) return RAYN_ERR_INVALID_ARG;
     if (!a || !b || !out) return fail(ctx, RAYN_ERR_INVALID_ARG, "null buffer");

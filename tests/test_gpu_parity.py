@@ -364,7 +364,9 @@ def test_two_workers_are_invisible(gpu_ctx, oracle):
 
 def test_tuning_variants_are_invisible(oracle, monkeypatch):
     """The code paths behind the tuning switches (generic multi-SDF march kernels instead of the single-SDF fast path, other
-    refill / prefetch thresholds of the persistent waves, one worker) give the same film bit for bit."""
+    refill / prefetch thresholds of the persistent waves, one worker) give the same film bit for bit.
+    At this film size (48x32, 8 spp: 12 288 paths) every launch of the march kernels is far below ENDGAME_ENTRIES and runs their endgame only: one ray per lane and no
+    spare rays, so the RAYN_HIP_PREFETCH_* settings change nothing this test can see.  The steady state under these switches: tests/test_march_steady_device.py."""
     import rayn_amd
     wd, p = case("s2", 48, 32, 2, 3)
     tabs = _tables(oracle, p)
@@ -389,9 +391,11 @@ def test_tuning_variants_are_invisible(oracle, monkeypatch):
 
 def test_bulb_march_kernel_variants_are_invisible(oracle, monkeypatch):
     """r6: a single-Mandelbulb scene marches its shadow segments with k_shadow_bulb (rayn_amd/csrc/march_bulb.h: K rays per lane, rounds of refill / orbits /
-    epilogues, orbits pulled from a per-wave job list in LDS and carried across rounds).  Every shape of it - 2 / 3 / 4 rays per lane, one or two orbit steps
-    per trip, drain-everything rounds (ORBIT_MIN 0), eager and lazy refill - and the generic k_shadow1 give the oracle's film bit for bit, with and without the
-    volume, with a moving bulb (packet times) and with exhausted march budgets."""
+    epilogues, orbits pulled from a per-wave job list in LDS and carried across rounds).  Every instantiation of it - built for 2 / 3 / 4 rays per lane, one or two
+    orbit steps per trip, drain-everything rounds (ORBIT_MIN 0), eager and lazy refill - and the generic k_shadow1 give the oracle's film bit for bit, with and without
+    the volume, with a moving bulb (packet times) and with exhausted march budgets.
+    At this film size (40x24, 8 spp: 7 680 paths) every launch is far below K x ENDGAME_ENTRIES, i.e. in the kernel's endgame, which refills ray slot 0 only: every
+    variant runs with ONE ray per lane here, whatever K it was built for.  K rays per lane at work: tests/test_march_steady_device.py."""
     import rayn_amd
     from rayn_amd import params as P
     cases = []

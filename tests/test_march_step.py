@@ -1,5 +1,9 @@
 """The per-step bookkeeping of the single-SDF march kernels (k_shadow1 / k_extend1): the straight-line march test in which 'first' is data (wave masks),
-on the corners of TracedSDF::occluded / TracedSDF::hit - NaN first and later distances, exhausted and zero march budgets, signed zeros."""
+on the corners of TracedSDF::occluded / TracedSDF::hit - NaN first and later distances, exhausted and zero march budgets, signed zeros.
+
+Mode: about 30 000 entries per launch, far below ENDGAME_ENTRIES (rayn_amd/csrc/kernels.h), so every launch here runs the kernels' ENDGAME - one ray per lane, fetched
+when the lane is idle, no spare rays - and k_shadow_bulb is not run at all.  The same corner classes in the STEADY STATE (spares, K rays per lane), spread
+through queues sized from the library's thresholds, are in tests/test_march_steady_device.py (inputs: tests/march_cases.py)."""
 import ctypes as C
 
 import numpy as np
