@@ -198,6 +198,17 @@ pub struct RaynDisplayParams {
     pub strength: f32,
 }
 
+// The parameter block of the guided upscaling (an extension; include/rayn_hip.h: rayn_upscale_params).  Plain scalars, 12 bytes;
+// rayn_hip_sizeof(9) reports it.
+#[repr(C)]
+/// `factor`: 1..8; `sigma_plane`, `sigma_position`: 0 = off, else in [2^-30, 2^30]
+#[derive(Clone, Copy, Debug)]
+pub struct RaynUpscaleParams {
+    pub factor: u32,
+    pub sigma_plane: f32,
+    pub sigma_position: f32,
+}
+
 #[link(name = "rayn_hip")]
 extern "C" {
     pub fn rayn_hip_create(device: i32, out: *mut *mut RaynCtx) -> i32;
@@ -333,6 +344,28 @@ extern "C" {
         d_out_color: *mut f32,
         d_out_meter: *mut f32,
         d_out_bloom: *mut f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    /// guided upscaling of the low film (`width` x `height`) to `factor` times its size with the G-buffers of both resolutions (device
+    /// pointers; a plane the film lacks is null in input and output together; `d_out_weight` may be null; include/rayn_hip.h has the definition)
+    pub fn rayn_hip_upscale_device(
+        ctx: *mut RaynCtx,
+        width: u32,
+        height: u32,
+        up: *const RaynUpscaleParams,
+        d_color: *const f32,
+        d_alpha: *const f32,
+        d_background: *const f32,
+        d_normal: *const f32,
+        d_low_records: *const c_void,
+        d_low_object: *const u32,
+        d_high_records: *const c_void,
+        d_high_object: *const u32,
+        d_out_color: *mut f32,
+        d_out_alpha: *mut f32,
+        d_out_background: *mut f32,
+        d_out_normal: *mut f32,
+        d_out_weight: *mut f32,
         hip_stream: *mut c_void,
     ) -> i32;
 }

@@ -4,6 +4,7 @@ written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints
 
     python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise [atrous|variance]] [--temporal] [--feedback B]
                                       [--resample {bilinear,catmull_rom}] [--display [--exposure auto|EV] [--tone T] [--bloom LEVELS] [--adaptation S]]
+                                      [--upscale S]
 
 --compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
 the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
@@ -18,7 +19,10 @@ default 0 = off) also blends the output of every frame's first a-trous pass into
 Catmull-Rom filter instead of the bilinear one wherever the whole footprint is valid (rayn_amd.Temporal(resample=...)); it needs --temporal.
 --display sends every frame's Color through the HDR display transform (rayn_amd.Display, an extension) after whatever else is on and writes
 _display after the Color file's suffix: --exposure auto (the default) or an EV, --tone aces|reinhard|linear, --bloom LEVELS (0 = off, the
-default; rayn_amd.Bloom() defaults otherwise) and --adaptation SECONDS (auto exposure follows the frames with this time constant)."""
+default; rayn_amd.Bloom() defaults otherwise) and --adaptation SECONDS (auto exposure follows the frames with this time constant).
+--upscale S (1..8) renders every frame at --width x --height and rebuilds it on the device at S times that size, guided by the primary-hit
+G-buffer traced at both resolutions (rayn_amd.Upscale(S) defaults, an extension); every written image is the high one and gets _xS after
+its suffix; --denoise atrous and --display then work on the upscaled film.  It does not combine with --temporal or --compare-loop."""
 import argparse
 import os
 import sys
@@ -80,7 +84,15 @@ def main():
     ap.add_argument("--tone", choices=("aces", "reinhard", "linear"), default="aces", help="the tone operator (default aces); needs --display")
     ap.add_argument("--bloom", type=int, default=0, metavar="LEVELS", help="bloom over this many pyramid levels, 1..8 (0 = off, the default); needs --display")
     ap.add_argument("--adaptation", type=float, default=None, metavar="S", help="time constant in seconds of the auto exposure's adaptation over the frames; needs --display")
+    ap.add_argument("--upscale", type=int, default=None, metavar="S",
+                    help="render at --width x --height and rebuild every frame at S times that size (1..8) with rayn_amd.Upscale(S)")
     args = ap.parse_args()
+    if args.upscale is not None and not 1 <= args.upscale <= 8:
+        ap.error("--upscale must be in 1..8")
+    if args.upscale is not None and args.temporal:
+        ap.error("--upscale with --temporal is not built: the temporal histories live at one resolution")
+    if args.upscale is not None and args.compare_loop:
+        ap.error("--compare-loop compares with the host post-process, which has no upscaling: use one or the other")
     if not args.display and (args.exposure != "auto" or args.tone != "aces" or args.bloom or args.adaptation is not None):
         ap.error("--exposure, --tone, --bloom and --adaptation set up the display transform: add --display")
     if args.display and args.compare_loop:
@@ -101,6 +113,7 @@ def main():
     if args.display:
         display = R.Display(exposure="auto" if args.exposure == "auto" else float(args.exposure), tone=args.tone,
                             bloom=R.Bloom(levels=args.bloom) if args.bloom else None, adaptation=args.adaptation)
+    upscale = R.Upscale(args.upscale) if args.upscale is not None else None
     first, end = (int(x) for x in args.frames.split(":"))
     frames = list(range(first, end))
     base = f"{SAMPLES * 4}_spp"
@@ -114,14 +127,14 @@ def main():
     film = R.Film(CHANNELS, (args.width, args.height))
     # warm-up: code objects, the context's first-frame arena and the writer path (not timed)
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames[:1], FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
-                         os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display)
+                         os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale)
     t0 = time.perf_counter()
     stats = film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
-                                 os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display)
+                                 os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale)
     seq_s = time.perf_counter() - t0
     for st in stats:
         print(f"frame {st['frame']:4d}: render {st['ms_total']:8.2f} ms")
-    print(f"render_sequence{' --denoise ' + str(denoise) if denoise else ''}{' --temporal ' + str(temporal) if temporal else ''}{' --display ' + str(display) if display else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s "
+    print(f"render_sequence{' --denoise ' + str(denoise) if denoise else ''}{' --temporal ' + str(temporal) if temporal else ''}{' --display ' + str(display) if display else ''}{' --upscale ' + str(upscale) if upscale else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s "
           f"(render alone: {sum(st['ms_total'] for st in stats) / len(frames):.2f} ms/frame)")
 
     if args.compare_loop:

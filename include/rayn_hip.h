@@ -662,6 +662,48 @@ int rayn_hip_denoise_temporal_variance_feedback_device(rayn_ctx* ctx, uint32_t w
                                                        const void* d_moments, size_t moments_bytes, float* d_out_color, float* d_out_variance,
                                                        void* d_scratch, size_t scratch_bytes, float feedback, void* hip_stream);
 
+/* ---- guided upscaling (an EXTENSION: rayn renders at one resolution) -- Joint bilateral upsampling (Kopf et al., SIGGRAPH 2007) of a film
+ * rendered at w x h to W x H = s * w x s * h, s = factor.  The guide is traced, not interpolated: the primary-hit G-buffer of the same
+ * camera and time_start at both resolutions, BOTH under the low film's uploaded world (rayn_hip_gbuffer_device with p.width, p.height = w, h
+ * and = W, H).  The factor keeps the aspect ratio, so the high pass shoots the pixel-centre rays of a camera built at W x H; its depth-0 hit
+ * threshold (half_pixel_size, which the camera's own resolution sets) stays the low frame's, so both G-buffers describe the surface the
+ * film's samples were shaded on and P - Pq below measures geometry, not the difference of two thresholds.  Geometry edges come out at the
+ * high resolution and every rendered sample goes into shading noise.  Downstream of the film: the low film's planes are read, new planes
+ * of the high size are written. */
+typedef struct {
+    uint32_t factor;      /* s, 1..8 */
+    float sigma_plane;    /* the distance of the pixel's hit point from the tap's tangent plane, relative to the hit distance; 0 = off */
+    float sigma_position; /* the distance between the two hit points, relative to the hit distance; 0 = off */
+} rayn_upscale_params;
+/* Inputs: the low film (planar Color 3 floats per pixel, Alpha 1, Background 3, WorldNormal 3, pixel x + y * w, rows bottom-up) with its
+ * G-buffer (records (Pq, tq), objects oq), and the high G-buffer (records (P, t), objects o).  All arithmetic f32, no contraction under
+ * either mul_add policy, IEEE '/', expf = dm_expf (rayn_detmath.h), dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z.  A sigma of 0 switches
+ * its term off; any other must be finite and in [2^-30, 2^30].  Per high pixel (X, Y):
+ *   1. Footprint: fx = ((float)X + 0.5f) / (float)s - 0.5f, x0f = floorf(fx), wx1 = fx - x0f, wx0 = 1.0f - wx1, and y likewise.  Taps
+ *      k = 0..3 at (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) with b_k = wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1.  A tap is
+ *      USABLE when it lies inside the low image, b_k > 0 and its Color has three finite components.
+ *   2. Guided weights over the usable taps with oq == o (a miss, 0xFFFFFFFF, matches a miss).  A miss pixel: g_k = b_k.  A hit pixel:
+ *      inv_t = 1.0f / (t + 1e-8f), d = P - Pq;  with sigma_plane != 0, dpl = fabsf(dot(nq, d)) * inv_t, nq the tap's WorldNormal as the
+ *      film holds it (not normalised);  with sigma_position != 0, dps = dot(d, d) * (inv_t * inv_t);  e = (dpl * dpl) * kp + dps * ks with
+ *      kp = 1.0f / (sigma_plane * sigma_plane), ks = 1.0f / (sigma_position * sigma_position), a term that is off left out (both off:
+ *      e = 0);  g_k = b_k * dm_expf(-e), and a NaN g_k skips the tap.  Wg += g_k and, per component of every present plane, Sg += g_k * v_k,
+ *      taps in the order above.  Every sum STARTS AT -0.0f, the identity of + for both zeros.
+ *   3. Wg > 0: every component is Sg / Wg.  Else the same sums with g_k = b_k over ALL usable taps (Wb, Sb), and Wb > 0 gives Sb / Wb.
+ *      Else the low pixel (min(X / s, w - 1), min(Y / s, h - 1)) (integer division) is copied verbatim, non-finite values included.
+ *      d_out_weight (optional, one float per high pixel) receives Wg, and 0 where a fallback was taken.
+ * The same weights serve all planes.  With factor == 1 a pixel with a finite Color comes out with the bits it went in with: fx = X, b_0 = 1,
+ * the other taps fail b_k > 0, e = 0 or d = 0, dm_expf(-0) = 1, -0.0f + 1 * v = v and v / 1 = v.
+ * 'width' and 'height' are the LOW film's.  A plane pointer (Alpha, Background, WorldNormal) may be NULL in input and output together: the
+ * film lacks that channel, and it is neither read nor written.  DEVICE pointers; records 16-byte aligned.  Enqueued on 'hip_stream' (NULL =
+ * the ctx's own stream; not waited for), on the ctx's GPU (devices[0] of a multi-device ctx); the inputs are not modified.
+ * RAYN_ERR_INVALID_ARG with a last error text for: NULL up, a factor outside 1..8, a zero-sized image, W * H >= 2^31 or W or H above 2^23
+ * (the pixel centres X + 0.5 must be exact in f32), a bad sigma, a NULL Color, a NULL G-buffer plane, a plane that is NULL on one side only,
+ * a NULL WorldNormal with sigma_plane != 0, misaligned records or objects, and an output that overlaps an input or another output. */
+int rayn_hip_upscale_device(rayn_ctx* ctx, uint32_t width, uint32_t height, const rayn_upscale_params* up, const float* d_color,
+                            const float* d_alpha, const float* d_background, const float* d_normal, const void* d_low_records,
+                            const uint32_t* d_low_object, const void* d_high_records, const uint32_t* d_high_object, float* d_out_color,
+                            float* d_out_alpha, float* d_out_background, float* d_out_normal, float* d_out_weight, void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */
@@ -734,7 +776,7 @@ int rayn_hip_set_cold_bytes(rayn_ctx* ctx, uint64_t bytes);
 int rayn_hip_fma_policy(void);
 int rayn_hip_set_fma_policy(rayn_ctx* ctx, int policy);
 /* sizeof() of the ABI structs as compiled: 0 world_desc, 1 frame_params, 2 stats, 3 hitable,
- * 4 material, 5 light, 6 camera, 7 temporal_resample_params, 8 display_params — lets a binding verify its layout. */
+ * 4 material, 5 light, 6 camera, 7 temporal_resample_params, 8 display_params, 9 upscale_params — lets a binding verify its layout. */
 size_t rayn_hip_sizeof(int which);
 /* "" for the product build of the library; the VARIANT name of a `make variant` build (timing experiments: such a build is
  * only ever loaded through RAYN_HIP_LIB + RAYN_HIP_ALLOW_VARIANT=1, and bench.py prints the name in its result line). */

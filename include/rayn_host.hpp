@@ -346,6 +346,18 @@ inline int display_pixels(rayn_ctx* ctx, const rayn_display_params& dp, uint32_t
                                           d_scratch, scratch_bytes, d_out, nullptr, nullptr, hip_stream);
 }
 
+// Extension (include/rayn_hip.h: guided upscaling): the low film of `res` and the primary-hit G-buffers of both resolutions -> the planes of
+// the film at factor * res.  Device pointers; a plane the film lacks is null in input and output together; d_out_weight may be null.
+// Returns the entry's code.
+inline int upscale(rayn_ctx* ctx, Extent2u res, uint32_t factor, float sigma_plane, float sigma_position, const float* d_color, const float* d_alpha,
+                   const float* d_background, const float* d_normal, const void* d_low_records, const uint32_t* d_low_object,
+                   const void* d_high_records, const uint32_t* d_high_object, float* d_out_color, float* d_out_alpha, float* d_out_background,
+                   float* d_out_normal, float* d_out_weight = nullptr, void* hip_stream = nullptr) {
+    const rayn_upscale_params up = {factor, sigma_plane, sigma_position};
+    return rayn_hip_upscale_device(ctx, res.w, res.h, &up, d_color, d_alpha, d_background, d_normal, d_low_records, d_low_object, d_high_records,
+                                   d_high_object, d_out_color, d_out_alpha, d_out_background, d_out_normal, d_out_weight, hip_stream);
+}
+
 // ---- setup::setup() (src/setup.rs:46-170) with the resolution as an argument ---------------------
 namespace setup {
 constexpr float WORLD_RADIUS = 100.0f;

@@ -21,6 +21,7 @@
 #include "tiles.h"
 #include "save_to.h"
 #include "display.h"
+#include "upscale.h"
 #include "denoise.h"
 #include "denoise_variance.h"
 #include "progressive.h"
@@ -1068,6 +1069,19 @@ int rayn_hip_denoise_variance_device(rayn_ctx* ctx, const rayn_frame_params* p, 
     return post_enqueued(ctx);
 }
 
+// Guided upscaling (upscale.hip): the low film and the G-buffers of both resolutions -> the planes of the high film.
+int rayn_hip_upscale_device(rayn_ctx* ctx, uint32_t width, uint32_t height, const rayn_upscale_params* up, const float* d_color,
+                            const float* d_alpha, const float* d_background, const float* d_normal, const void* d_low_records,
+                            const uint32_t* d_low_object, const void* d_high_records, const uint32_t* d_high_object, float* d_out_color,
+                            float* d_out_alpha, float* d_out_background, float* d_out_normal, float* d_out_weight, void* hip_stream) {
+    const UpscalePlanes pl = {d_color, d_alpha, d_background, d_normal, d_low_records, d_low_object, d_high_records, d_high_object,
+                              d_out_color, d_out_alpha, d_out_background, d_out_normal, d_out_weight};
+    hipStream_t s;
+    if (int rc = post_enter(ctx, upscale_check_args(width, height, up, pl), hip_stream, &s)) return rc;
+    launch_upscale(s, width, height, *up, pl);
+    return post_enqueued(ctx);
+}
+
 // The primary-hit G-buffer (temporal.hip): one centre ray per pixel through the scene's PRODUCT extend kernel at depth 0, selected as
 // rayn_hip_probe_extend selects it.  The scene of (uploaded world, p) goes to ctx->d_scene on the stream, as a render's does (a pageable
 // source is staged before hipMemcpyAsync returns, so the stack copy may go away).
@@ -1385,6 +1399,7 @@ size_t rayn_hip_sizeof(int which) {
     case 6: return sizeof(rayn_camera);
     case 7: return sizeof(rayn_temporal_resample_params);
     case 8: return sizeof(rayn_display_params);
+    case 9: return sizeof(rayn_upscale_params);
     default: return 0;
     }
 }

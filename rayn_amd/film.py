@@ -246,6 +246,44 @@ class Display:
                                   0.0 if b is None else float(b.threshold), 0.0 if b is None else float(b.strength))
 
 
+@dataclasses.dataclass(frozen=True)
+class Upscale:
+    """Parameters of the guided upscaling of a film (rayn_hip_upscale_device, an extension: rayn renders at one resolution; joint bilateral
+    upsampling, Kopf et al., SIGGRAPH 2007; include/rayn_hip.h has the definition).  A film rendered at w x h is rebuilt at `factor` (1..8)
+    times that size: every high pixel takes the four low pixels of its bilinear footprint that show the object its own primary hit shows
+    (the G-buffer is traced at both resolutions, rayn_hip_gbuffer_device), weighted by the bilinear weight times exp(-(dpl / sigma_plane)^2
+    - (dps / sigma_position)^2), dpl the distance of the pixel's hit point from the tap's tangent plane (the film's WorldNormal) and dps
+    the distance between the two hit points, both relative to the pixel's hit distance.  Where no tap shows the object the plain bilinear
+    weights are used.  The same weights serve every channel.  A sigma of 0 switches its term off; any other must be finite and in
+    [2^-30, 2^30].  factor=1 is the identity.
+
+    The defaults were chosen on the shipped scene (rayn_amd.setup at 160x96 and 32 spp upscaled to 320x192; the MSE of the saturated Color
+    + Background against a native 1024 spp render) over a grid of the two sigmas (tools/upscale_defaults.py; DESIGN.md section 8 has it):
+    the plane term off and a wide position term, 0.3.  That brings the MSE to 0.68x that of a native 320x192 render of the same number of
+    paths (8 spp), where plain bilinear gives 0.74x, the object test alone 0.70x and the native render through Denoise() 0.67x.  On the
+    fractal the film's WorldNormal is the mean of a pixel's sample normals and no tangent plane: every finite sigma_plane on the grid made
+    the result worse (0.69x at 0.1, 0.86x at 0.005).  On the sphere scene s0, whose noise is low, the lost resolution dominates: the
+    upscaled film has 4.4x the error of the native 8 spp render - 0.72x that of plain bilinear, whatever the sigmas."""
+    factor: int = 2
+    sigma_plane: float = 0.0
+    sigma_position: float = 0.3
+
+    def __post_init__(self):
+        if isinstance(self.factor, bool) or not isinstance(self.factor, (int, np.integer)) or not 1 <= self.factor <= 8:
+            raise ValueError(f"Upscale.factor must be an int in 1..8, got {self.factor!r}")
+        for name in ("sigma_plane", "sigma_position"):
+            f = _number("Upscale", name, getattr(self, name))  # the C entry takes it as an f32: check that value too
+            if not (f == 0.0 or (2.0 ** -30 <= f <= 2.0 ** 30 and 2.0 ** -30 <= float(np.float32(f)) <= 2.0 ** 30)):
+                raise ValueError(f"Upscale.{name} must be 0 (off) or finite in [2^-30, 2^30], got {getattr(self, name)!r}")
+
+    def without(self, have_mask):
+        """These parameters with the plane term switched off for a film without WorldNormal (bit k of have_mask = ChannelKind k)."""
+        return dataclasses.replace(self, sigma_plane=self.sigma_plane if have_mask & 8 else 0.0)
+
+    def to_abi(self):
+        return _abi.UpscaleParams(int(self.factor), float(self.sigma_plane), float(self.sigma_position))
+
+
 def display_scratch_bytes(width, height, levels):
     """rayn_display_scratch_bytes: bytes of device scratch the display transform needs for a width x height film with `levels` bloom
     levels (0 for a size it rejects or levels > 8).  A manual exposure without bloom needs none."""
@@ -549,6 +587,42 @@ class Context:
                      opt(d_scratch), 0 if d_scratch is None else d_scratch.numel() * d_scratch.element_size(), C.c_void_p(d_out.data_ptr()),
                      opt(d_out_meter), opt(d_out_bloom), C.c_void_p(s)))
 
+    def upscale(self, params, upscale, d_film, d_low_gbuffer, d_high_gbuffer, d_out_film, d_out_weight=None, stream=None):
+        """rayn_hip_upscale_device: the guided upscaling (Upscale `upscale`) of the device film `d_film` of the frame `params` (its width
+        and height are the LOW film's) into `d_out_film`, a film dict of upscale.factor times that size.  d_low_gbuffer / d_high_gbuffer:
+        the G-buffers (alloc_gbuffer's dicts, as Context.gbuffer fills them) of the frame at the low and at the high resolution.  A plane
+        (alpha, background, normal) the film lacks is absent from d_film and d_out_film together and is neither read nor written; "color"
+        is required.  d_out_weight: a float32 CUDA tensor of one float per high pixel for the summed guided weight (0 where a fallback
+        was taken), or None.  Enqueued on the stream, not waited for."""
+        import torch
+        s_ = int(upscale.factor)
+        n = int(params.width) * int(params.height)
+        N = n * s_ * s_
+        ptrs = []
+        for film, count, what in ((d_film, n, "d_film"), (d_out_film, N, "d_out_film")):
+            for key, floats in (("color", 3), ("alpha", 1), ("background", 3), ("normal", 3)):
+                t = film.get(key)
+                if t is None:
+                    ptrs.append(None)
+                    continue
+                if not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= floats * count):
+                    raise ValueError(f"{what}[{key!r}] must be a contiguous float32 tensor of at least {floats * count} floats")
+                ptrs.append(C.c_void_p(t.data_ptr()))
+        gp = []
+        for g, count, what in ((d_low_gbuffer, n, "d_low_gbuffer"), (d_high_gbuffer, N, "d_high_gbuffer")):
+            rec, obj = g.get("records"), g.get("object")
+            if rec is None or not (rec.dtype == torch.float32 and rec.is_contiguous() and rec.numel() >= 4 * count):
+                raise ValueError(f"{what}['records'] must be a contiguous float32 tensor of at least {4 * count} floats")
+            if obj is None or not (obj.dtype == torch.int32 and obj.is_contiguous() and obj.numel() >= count):
+                raise ValueError(f"{what}['object'] must be a contiguous int32 tensor of at least {count} elements")
+            gp += [C.c_void_p(rec.data_ptr()), C.c_void_p(obj.data_ptr())]
+        if d_out_weight is not None and not (d_out_weight.dtype == torch.float32 and d_out_weight.is_contiguous() and d_out_weight.numel() >= N):
+            raise ValueError(f"d_out_weight must be a contiguous float32 tensor of at least {N} floats")
+        up = upscale.to_abi()
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._chk(self._L.rayn_hip_upscale_device(self.h, int(params.width), int(params.height), C.byref(up), *ptrs[:4], *gp, *ptrs[4:],
+                                                  None if d_out_weight is None else C.c_void_p(d_out_weight.data_ptr()), C.c_void_p(s)))
+
     def denoise(self, width, height, d_film, d_out_color, params, d_scratch=None, stream=None):
         """rayn_hip_denoise_device: the a-trous denoiser (Denoise `params`) of d_film["color"] into the float32 CUDA tensor d_out_color
         (width * height * 3 floats), guided by d_film["normal"] and d_film["alpha"] (a guide whose sigma is 0 may be absent).
@@ -850,10 +924,14 @@ class Film:
         if len(set(kinds)) != len(kinds):
             dup = next(k for k in kinds if kinds.count(k) > 1)
             raise ValueError(f"Attempted to create multiple {dup.name} channels")  # src/film.rs:188
+        self._init_state(kinds, res, Context(device), f"cuda:{device}")
+
+    def _init_state(self, kinds, res, ctx, device):
+        """Every attribute of a film: __init__ with a context of its own, Film.upscaled with the source film's."""
         self.channel_kinds = kinds
         self.res = (int(res[0]), int(res[1]))
-        self.ctx = Context(device)
-        self.device = f"cuda:{device}"
+        self.ctx = ctx
+        self.device = device
         self.channels = None  # torch tensors after a render
         self.progressive_epoch = 0
         self._progressive = None  # after render_progressive: its device state, geometry, checkpoint key and epoch count
@@ -898,6 +976,50 @@ class Film:
             rec = g["records"].cpu().numpy().reshape(h, w, 4)
             obj = g["object"].cpu().numpy().view(np.uint32).reshape(h, w)
         return {"position": rec[..., :3].copy(), "t": rec[..., 3].copy(), "object": obj}
+
+    def _upscale_plan(self, upscale):
+        """(`upscale` with the plane term off for a film without WorldNormal, the keys of the planes this film holds); ValueError for
+        anything that is no Upscale and for a film without Color."""
+        if not isinstance(upscale, Upscale):
+            raise ValueError(f"upscale must be an Upscale, got {upscale!r}")
+        if ChannelKind.Color not in self.channel_kinds:
+            raise ValueError("Attempted to upscale a film without a Color channel")
+        return upscale.without(self.have_mask()), [_CHANNEL_KEY[k] for k in ChannelKind if k in self.channel_kinds]
+
+    def upscaled(self, upscale, want_weight=False):
+        """A NEW Film of upscale.factor times this film's resolution, rebuilt from the last rendered frame by the guided upscaling (Upscale
+        `upscale`, rayn_hip_upscale_device, an extension): the G-buffer of the frame is traced at both resolutions and every channel the
+        film holds is upsampled with the same guided weights; a film without WorldNormal loses the plane term.  The new film has the same
+        channel kinds and shares this film's Context and device; its channels are the upscaled planes, so channel, pixels, save_to,
+        save_hdr, denoised_color(Denoise(...)), display_color and display= work on it unchanged, and its gbuffer() is the high G-buffer.
+        It holds no progressive state (a VarianceDenoise raises its ValueError).  This film is not changed.  With want_weight, returns
+        (film, weight): the summed guided weight of every high pixel as float32 (H, W), rows bottom-up, 0 where a fallback was taken.
+        ValueError when this film holds no rendered frame."""
+        import torch
+        up, keys = self._upscale_plan(upscale)
+        if self._last_params is None or self.channels is None:
+            raise ValueError("the film holds no rendered frame (render_frame_into, render_sequence or render_progressive has not run)")
+        w, h = self.res
+        p = self._last_params
+        ph = _scaled_params(p, up.factor)
+        W, H = int(ph.width), int(ph.height)
+        with torch.cuda.device(self.device):
+            g_low, g_high = alloc_gbuffer(w, h, self.device), alloc_gbuffer(W, H, self.device)
+            d_scratch = torch.empty(max(gbuffer_scratch_bytes(W, H), 1), dtype=torch.uint8, device=self.device)
+            self.ctx.gbuffer(p, g_low, d_scratch)
+            self.ctx.gbuffer(ph, g_high, d_scratch)
+            full = alloc_device_film(W, H, self.device)
+            d_out = {k: full[k] for k in keys}
+            d_weight = torch.empty(W * H, dtype=torch.float32, device=self.device) if want_weight else None
+            self.ctx.upscale(p, up, {k: self.channels[k] for k in keys}, g_low, g_high, d_out, d_weight)
+            out = Film.__new__(Film)
+            out._init_state(list(self.channel_kinds), (W, H), self.ctx, self.device)
+            out.channels = d_out
+            out.progressive_epoch = self.progressive_epoch
+            out._last_params = ph
+            if want_weight:
+                return out, d_weight.cpu().numpy().reshape(H, W)
+            return out
 
     def have_mask(self):
         """bit k = ChannelKind k is among the film's channels (the have_mask of rayn_save_to_bpp)"""
@@ -1148,7 +1270,7 @@ class Film:
         return _prog.error_map(arrays, w, h, (pr["params"].tile_w, pr["params"].tile_h), pr["noise_floor"])
 
     def render_sequence(self, world, camera, integrator, filter, tile_size, frames, frame_rate, shutter_speed, samples, write_channels,
-                        output_folder, base_name, transparent_background=False, writers=None, denoise=None, display=None, temporal=None):
+                        output_folder, base_name, transparent_background=False, writers=None, denoise=None, display=None, upscale=None, temporal=None):
         """rayn's main loop (src/main.rs:58-96) on the GPU: for each frame of `frames`, render_frame_into at
         frame_start = frame as f32 * (1.0 / frame_rate as f32), frame_end = frame_start + shutter_speed (f32, src/main.rs:61-62), then
         save_to(write_channels, output_folder, f"{base_name}_{frame:04d}", transparent_background).  rayn writes every frame under
@@ -1193,7 +1315,15 @@ class Film:
         whatever suffix it would have had (_color_display.png, _color_temporal_denoised_display.png, ...).  One auto-exposure state serves
         the call: the first frame takes its own metered value, every later one blends with adapt = 1 - exp(-dt / display.adaptation), dt
         the difference of the f32 frame starts (1 without adaptation).  The exposure stays on the device, so nothing synchronises; the
-        state and the scratch are allocated once.  display=None is the path described above, unchanged."""
+        state and the scratch are allocated once.  display=None is the path described above, unchanged.
+
+        With `upscale` (an Upscale, an extension), every frame is rendered at the film's resolution and rebuilt on the device at
+        upscale.factor times that size, as Film.upscaled does: after the render, the frame's G-buffer passes at both resolutions and the
+        upscale kernel go on the render stream, every written image is made from the upscaled film and its file name gets _x{factor}
+        appended to whatever suffix it would have had (_color_x2.png, _alpha_x2.png, _color_denoised_display_x2.png, ...).  `denoise` (a
+        Denoise) and `display` then work on the upscaled film.  The G-buffers, the upscaled film and the scratch are allocated once and
+        nothing synchronises.  The film's channels stay the rendered, low frame.  `temporal` together with `upscale` raises ValueError:
+        histories at two resolutions are not built.  upscale=None is the path described above, unchanged."""
         import concurrent.futures as cf
         import torch
         variance = isinstance(denoise, VarianceDenoise)
@@ -1201,6 +1331,10 @@ class Film:
             raise ValueError("render_sequence renders plain frames: VarianceDenoise needs the state of a progressive render")
         if isinstance(temporal, Temporal) and float(temporal.feedback) > 0.0 and not variance:
             raise ValueError("Temporal.feedback > 0 feeds a VarianceDenoise's first pass back into the history: pass one as `denoise`")
+        if upscale is not None:
+            if temporal is not None:
+                raise ValueError("temporal= together with upscale= is not built: the temporal histories live at one resolution")
+            upscale, up_keys = self._upscale_plan(upscale)
         frames = [int(f) for f in frames]
         jobs = self._save_jobs(write_channels, transparent_background)
         if denoise is not None:
@@ -1229,8 +1363,11 @@ class Film:
                 display = None
             else:
                 jobs = [(kind, bpp, suffix + "_display" if kind == ChannelKind.Color else suffix) for kind, bpp, suffix in jobs]
+        if upscale is not None:
+            jobs = [(kind, bpp, f"{suffix}_x{upscale.factor}") for kind, bpp, suffix in jobs]
         os.makedirs(output_folder, exist_ok=True)
         w, h = self.res
+        ow, oh = (w, h) if upscale is None else (w * upscale.factor, h * upscale.factor)  # the size of the written images
         f32 = np.float32
         inv_rate, shutter = f32(1.0) / f32(frame_rate), f32(shutter_speed)
         spp, mb, vm = 4 * samples, integrator.max_bounces, integrator.volume_marches
@@ -1261,10 +1398,16 @@ class Film:
                 s1, s2 = next_rd.result()
                 d_tables = [torch.from_numpy(t).to(self.device) for t in (s1, s2, scr, fis)]
                 d_film = alloc_device_film(w, h, self.device)
-                d_img = [torch.empty(h * w * bpp, dtype=torch.uint8, device=self.device) for _, bpp, _ in jobs]
+                d_img = [torch.empty(oh * ow * bpp, dtype=torch.uint8, device=self.device) for _, bpp, _ in jobs]
                 if denoise is not None:
-                    d_denoised = torch.empty(w * h, 3, dtype=torch.float32, device=self.device)
-                    d_scratch = torch.empty((denoise_variance_scratch_bytes if variance else denoise_scratch_bytes)(w, h), dtype=torch.uint8, device=self.device)
+                    d_denoised = torch.empty(ow * oh, 3, dtype=torch.float32, device=self.device)
+                    d_scratch = torch.empty((denoise_variance_scratch_bytes if variance else denoise_scratch_bytes)(ow, oh), dtype=torch.uint8, device=self.device)
+                if upscale is not None:
+                    d_glow, d_ghigh = alloc_gbuffer(w, h, self.device), alloc_gbuffer(ow, oh, self.device)
+                    d_uscratch = torch.empty(gbuffer_scratch_bytes(ow, oh), dtype=torch.uint8, device=self.device)  # serves both passes
+                    d_up_full = alloc_device_film(ow, oh, self.device)
+                    d_up = {k: d_up_full[k] for k in up_keys}
+                    d_low = {k: d_film[k] for k in up_keys}
                 d_mom = [None, None]
                 if temporal is not None and variance and denoise is not None:
                     d_mom = [torch.empty(temporal_moments_bytes(w, h), dtype=torch.uint8, device=self.device) for _ in range(2)]
@@ -1276,10 +1419,10 @@ class Film:
                     prev_start = None
                 if display is not None:
                     d_dstate = self.ctx.display_state() if display.auto else None
-                    d_dscratch = (torch.empty(display_scratch_bytes(w, h, display.levels), dtype=torch.uint8, device=self.device)
+                    d_dscratch = (torch.empty(display_scratch_bytes(ow, oh, display.levels), dtype=torch.uint8, device=self.device)
                                   if display.auto or display.levels else None)
                     shown_start = None  # the start of the frame the state last metered
-                h_img = [[torch.empty(h * w * bpp, dtype=torch.uint8, pin_memory=True) for _, bpp, _ in jobs] for _ in range(2)]
+                h_img = [[torch.empty(oh * ow * bpp, dtype=torch.uint8, pin_memory=True) for _, bpp, _ in jobs] for _ in range(2)]
                 for i, frame in enumerate(frames):
                     if i:
                         s1, s2 = next_rd.result()
@@ -1304,7 +1447,13 @@ class Film:
                     # wait: its images from frame k - 2 must have been encoded.
                     slot = i % 2
                     wait_slot(slot)
-                    d_shown = d_film  # what the Color image is made from
+                    d_base = d_film  # what the images are made from
+                    if upscale is not None:
+                        self.ctx.gbuffer(p, d_glow, d_uscratch, stream.cuda_stream)
+                        self.ctx.gbuffer(_scaled_params(p, upscale.factor), d_ghigh, d_uscratch, stream.cuda_stream)
+                        self.ctx.upscale(p, upscale, d_low, d_glow, d_ghigh, d_up, None, stream.cuda_stream)
+                        d_base = d_up
+                    d_shown = d_base  # what the Color image is made from
                     if temporal is not None:
                         self.ctx.gbuffer(p, d_gbuf, d_gscratch, stream.cuda_stream)
                         self.ctx.temporal_accumulate(p, temporal, d_film, d_gbuf, None if prev_start is None else d_hist[(i + 1) % 2],
@@ -1318,22 +1467,22 @@ class Film:
                             self.ctx.denoise_temporal_variance(w, h, d_shown, d_gbuf, d_hist[i % 2], d_mom[i % 2], d_denoised, denoise, None, d_scratch,
                                                                stream.cuda_stream, float(temporal.feedback))
                         else:
-                            self.ctx.denoise(w, h, d_shown, d_denoised, denoise, d_scratch, stream.cuda_stream)
-                        d_shown = dict(d_film, color=d_denoised)
+                            self.ctx.denoise(ow, oh, d_shown, d_denoised, denoise, d_scratch, stream.cuda_stream)
+                        d_shown = dict(d_base, color=d_denoised)
                     for (kind, _, suffix), d, hbuf in zip(jobs, d_img, h_img[slot]):
-                        src = d_shown if kind == ChannelKind.Color else d_film
+                        src = d_shown if kind == ChannelKind.Color else d_base
                         if display is not None and kind == ChannelKind.Color:
                             adapt = 1.0 if shown_start is None else display.adapt(float(start) - float(shown_start))
-                            self.ctx.display(display, mask, transparent_background, w, h, src, d, d_dstate, d_dscratch, adapt, stream=stream.cuda_stream)
+                            self.ctx.display(display, mask, transparent_background, ow, oh, src, d, d_dstate, d_dscratch, adapt, stream=stream.cuda_stream)
                             shown_start = start
                         else:
-                            self.ctx.save_to_pixels(kind, mask, transparent_background, w, h, src, d, stream.cuda_stream)
+                            self.ctx.save_to_pixels(kind, mask, transparent_background, ow, oh, src, d, stream.cuda_stream)
                         hbuf.copy_(d, non_blocking=True)
                     done = torch.cuda.Event()
                     done.record(stream)
                     for (kind, bpp, suffix), hbuf in zip(jobs, h_img[slot]):
                         path = os.path.join(output_folder, f"{base_name}_{frame:04d}_{suffix}.png")
-                        pending[slot].append(write_pool.submit(write, done, hbuf.numpy().reshape(h, w, bpp), path))
+                        pending[slot].append(write_pool.submit(write, done, hbuf.numpy().reshape(oh, ow, bpp), path))
                 wait_slot(0)
                 wait_slot(1)
             return stats
@@ -1343,6 +1492,14 @@ class Film:
             table_pool.shutdown(wait=True, cancel_futures=True)
 
 
+def _scaled_params(p, factor):
+    """A copy of the frame parameters p with the resolution multiplied by factor: the frame of an upscaled film."""
+    ph = type(p).from_buffer_copy(p)
+    ph.width, ph.height = int(p.width) * int(factor), int(p.height) * int(factor)
+    return ph
+
+
+_CHANNEL_KEY = {ChannelKind.Color: "color", ChannelKind.Alpha: "alpha", ChannelKind.Background: "background", ChannelKind.WorldNormal: "normal"}
 _SAVE_TO_SUFFIX = {ChannelKind.Color: "color", ChannelKind.Alpha: "alpha", ChannelKind.Background: "background", ChannelKind.WorldNormal: "normal"}
 _SAVE_TO_ERR = {ChannelKind.Color: "Attempted to write Color channel with insufficient channels",  # src/film.rs:283-287
                 ChannelKind.Alpha: "Attempted to write Alpha channel but it didn't exist",  # :341-345
