@@ -209,6 +209,15 @@ pub struct RaynUpscaleParams {
     pub sigma_position: f32,
 }
 
+// The parameter block of the temporal supersampling (an extension; include/rayn_hip.h: rayn_temporal_upscale_params).  One scalar,
+// 4 bytes; rayn_hip_sizeof(10) reports it.
+#[repr(C)]
+/// `confidence`: 0 off, 1 on
+#[derive(Clone, Copy, Debug)]
+pub struct RaynTemporalUpscaleParams {
+    pub confidence: u32,
+}
+
 #[link(name = "rayn_hip")]
 extern "C" {
     pub fn rayn_hip_create(device: i32, out: *mut *mut RaynCtx) -> i32;
@@ -361,6 +370,36 @@ extern "C" {
         d_low_object: *const u32,
         d_high_records: *const c_void,
         d_high_object: *const u32,
+        d_out_color: *mut f32,
+        d_out_alpha: *mut f32,
+        d_out_background: *mut f32,
+        d_out_normal: *mut f32,
+        d_out_weight: *mut f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    /// temporal supersampling: the guided upscaling of the low film (`p.width` x `p.height`) fused with the temporal accumulate at
+    /// `up.factor` times that size (device pointers; `low_camera`, `d_prev_history` with `prev_camera`, the Alpha / Background pairs and
+    /// `d_out_weight` may be null; `d_out_color` receives the accumulated colour; include/rayn_hip.h has the definition)
+    pub fn rayn_hip_temporal_upscale_device(
+        ctx: *mut RaynCtx,
+        p: *const RaynFrameParams,
+        up: *const RaynUpscaleParams,
+        tp: *const RaynTemporalParams,
+        sp: *const RaynTemporalUpscaleParams,
+        low_camera: *const RaynCamera,
+        prev_camera: *const RaynCamera,
+        prev_time_start: f32,
+        d_color: *const f32,
+        d_alpha: *const f32,
+        d_background: *const f32,
+        d_normal: *const f32,
+        d_low_records: *const c_void,
+        d_low_object: *const u32,
+        d_high_records: *const c_void,
+        d_high_object: *const u32,
+        d_prev_history: *const c_void,
+        d_new_history: *mut c_void,
+        history_bytes: usize,
         d_out_color: *mut f32,
         d_out_alpha: *mut f32,
         d_out_background: *mut f32,

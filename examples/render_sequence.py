@@ -4,7 +4,7 @@ written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints
 
     python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise [atrous|variance]] [--temporal] [--feedback B]
                                       [--resample {bilinear,catmull_rom}] [--display [--exposure auto|EV] [--tone T] [--bloom LEVELS] [--adaptation S]]
-                                      [--upscale S]
+                                      [--upscale S [--temporal --supersample [--no-jitter] [--confidence | --no-confidence]]]
 
 --compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
 the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
@@ -22,7 +22,11 @@ _display after the Color file's suffix: --exposure auto (the default) or an EV, 
 default; rayn_amd.Bloom() defaults otherwise) and --adaptation SECONDS (auto exposure follows the frames with this time constant).
 --upscale S (1..8) renders every frame at --width x --height and rebuilds it on the device at S times that size, guided by the primary-hit
 G-buffer traced at both resolutions (rayn_amd.Upscale(S) defaults, an extension); every written image is the high one and gets _xS after
-its suffix; --denoise atrous and --display then work on the upscaled film.  It does not combine with --temporal or --compare-loop."""
+its suffix; --denoise atrous and --display then work on the upscaled film.  It does not combine with --compare-loop, and with --temporal
+only through --supersample: the temporal history then lives at the upscaled size and every low frame is rendered through a camera offset
+by a fraction of a low pixel, so that over S * S frames every high pixel has had a sample at its own centre (rayn_amd.Supersample()
+defaults, an extension: jitter on, confidence off); --no-jitter switches the jitter off, --confidence weighs every frame by its nearest low
+sample and --no-confidence says the default aloud.  The Color file is _color_temporal_xS.png."""
 import argparse
 import os
 import sys
@@ -86,11 +90,24 @@ def main():
     ap.add_argument("--adaptation", type=float, default=None, metavar="S", help="time constant in seconds of the auto exposure's adaptation over the frames; needs --display")
     ap.add_argument("--upscale", type=int, default=None, metavar="S",
                     help="render at --width x --height and rebuild every frame at S times that size (1..8) with rayn_amd.Upscale(S)")
+    ap.add_argument("--supersample", action="store_true",
+                    help="keep the temporal history at the upscaled size and jitter the low frames' camera (rayn_amd.Supersample()); needs --upscale and --temporal")
+    ap.add_argument("--no-jitter", action="store_true", help="every low frame samples the same lattice (Supersample(jitter=False)); needs --supersample")
+    ap.add_argument("--confidence", action="store_true", help="weigh every frame by its nearest low sample (Supersample(confidence=True)); needs --supersample")
+    ap.add_argument("--no-confidence", action="store_true", help="every frame counts fully in the history (Supersample(confidence=False), the default); needs --supersample")
     args = ap.parse_args()
     if args.upscale is not None and not 1 <= args.upscale <= 8:
         ap.error("--upscale must be in 1..8")
-    if args.upscale is not None and args.temporal:
-        ap.error("--upscale with --temporal is not built: the temporal histories live at one resolution")
+    if args.supersample and not (args.upscale is not None and args.temporal):
+        ap.error("--supersample joins --upscale and --temporal: add both")
+    if (args.no_jitter or args.no_confidence or args.confidence) and not args.supersample:
+        ap.error("--no-jitter, --confidence and --no-confidence set up --supersample: add --supersample")
+    if args.confidence and args.no_confidence:
+        ap.error("--confidence and --no-confidence contradict each other")
+    if args.supersample and (args.denoise == "variance" or args.feedback != 0.0 or args.resample != "bilinear"):
+        ap.error("--supersample does not combine with --denoise variance, --feedback or --resample catmull_rom")
+    if args.upscale is not None and args.temporal and not args.supersample:
+        ap.error("--upscale with --temporal is not built: the temporal histories live at one resolution (add --supersample)")
     if args.upscale is not None and args.compare_loop:
         ap.error("--compare-loop compares with the host post-process, which has no upscaling: use one or the other")
     if not args.display and (args.exposure != "auto" or args.tone != "aces" or args.bloom or args.adaptation is not None):
@@ -114,6 +131,9 @@ def main():
         display = R.Display(exposure="auto" if args.exposure == "auto" else float(args.exposure), tone=args.tone,
                             bloom=R.Bloom(levels=args.bloom) if args.bloom else None, adaptation=args.adaptation)
     upscale = R.Upscale(args.upscale) if args.upscale is not None else None
+    supersample = None
+    if args.supersample:
+        supersample = R.Supersample(jitter=not args.no_jitter, confidence=True if args.confidence else False if args.no_confidence else R.Supersample().confidence)
     first, end = (int(x) for x in args.frames.split(":"))
     frames = list(range(first, end))
     base = f"{SAMPLES * 4}_spp"
@@ -127,14 +147,14 @@ def main():
     film = R.Film(CHANNELS, (args.width, args.height))
     # warm-up: code objects, the context's first-frame arena and the writer path (not timed)
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames[:1], FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
-                         os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale)
+                         os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample)
     t0 = time.perf_counter()
     stats = film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
-                                 os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale)
+                                 os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample)
     seq_s = time.perf_counter() - t0
     for st in stats:
         print(f"frame {st['frame']:4d}: render {st['ms_total']:8.2f} ms")
-    print(f"render_sequence{' --denoise ' + str(denoise) if denoise else ''}{' --temporal ' + str(temporal) if temporal else ''}{' --display ' + str(display) if display else ''}{' --upscale ' + str(upscale) if upscale else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s "
+    print(f"render_sequence{' --denoise ' + str(denoise) if denoise else ''}{' --temporal ' + str(temporal) if temporal else ''}{' --display ' + str(display) if display else ''}{' --upscale ' + str(upscale) if upscale else ''}{' --supersample ' + str(supersample) if supersample else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s "
           f"(render alone: {sum(st['ms_total'] for st in stats) / len(frames):.2f} ms/frame)")
 
     if args.compare_loop:

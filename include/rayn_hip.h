@@ -704,6 +704,54 @@ int rayn_hip_upscale_device(rayn_ctx* ctx, uint32_t width, uint32_t height, cons
                             const uint32_t* d_low_object, const void* d_high_records, const uint32_t* d_high_object, float* d_out_color,
                             float* d_out_alpha, float* d_out_background, float* d_out_normal, float* d_out_weight, void* hip_stream);
 
+/* ---- temporal supersampling (an EXTENSION: rayn renders at one resolution and every frame on its own) -- The guided upscaling above and
+ * the temporal accumulate in ONE kernel whose history lives at the HIGH resolution W x H = s * w x s * h: temporal upsampling as in TAAU /
+ * FSR2.  When every low frame is rendered with a different sub-pixel camera offset, over s * s frames every high pixel has had a low sample
+ * at its own centre, and the history - the one place where samples of different frames meet - collects the detail no single-frame filter
+ * can recover.  The kernel does not assume any particular offset: it finds each high pixel's footprint in the low film by projecting the
+ * pixel's primary hit through the camera the low film was rendered with. */
+typedef struct { uint32_t confidence; /* 0 off, 1 on */ } rayn_temporal_upscale_params;
+/* Inputs: the low film and its G-buffer as rayn_hip_upscale_device takes them (p->width, p->height = w, h; WorldNormal is REQUIRED), the
+ * high G-buffer (records (P, t), objects o) traced through the frame's own, unjittered camera, the previous HIGH history (NULL: none) with
+ * that frame's camera and time_start, and low_camera: the camera the low film and the low G-buffer were traced through, or NULL.  All
+ * arithmetic f32, no contraction under either mul_add policy, IEEE '/' and sqrtf; dot, cross and nz as for
+ * rayn_hip_temporal_accumulate_device.  Per high pixel (X, Y):
+ *   A. Footprint in the low film.  Default: step 1 of rayn_hip_upscale_device, fx = ((float)X + 0.5f) / (float)s - 0.5f and y likewise.
+ *      With low_camera != NULL and o != 0xFFFFFFFF: P through low_camera at ts = p->time_start by exactly step 3 of
+ *      rayn_hip_temporal_accumulate_device with the LOW width and height (no object-motion shift: both G-buffers belong to one instant);
+ *      its fx, fy are taken unless the projection is rejected or not finite, which keeps the default.  A miss pixel always keeps the
+ *      default, so under a jittered low camera its Background is registered less than one low pixel off.  Then x0f = floorf(fx),
+ *      wx1 = fx - x0f, wx0 = 1.0f - wx1, y likewise, and x0, y0 by step 4's clamp to [-2, 2^31].  (Here and in C an implementation may
+ *      clamp at any bound from 2^23 up - the kernel takes 2^24, which fits an int: W and H are at most 2^23, so every such origin is
+ *      outside the image and no result changes.)
+ *   B. This frame's value: steps 2 and 3 of rayn_hip_upscale_device on the taps k = 0..3 of that footprint - the same tier order, sums
+ *      that start at -0.0f and tap order; tier 3 is the verbatim low pixel (min(X / s, w - 1), min(Y / s, h - 1)) - for every present
+ *      plane.  c = the Color, nrm = the WorldNormal; Alpha, Background and WorldNormal go to their outputs and d_out_weight gets Wg, or 0.
+ *      conf = 1.0f when confidence == 0 and in tier 3; otherwise conf = the largest b_k over the taps that were ADDED to the sums of the
+ *      tier that produced the value (fmaxf from 0.0f): a high pixel whose centre a low sample hit exactly has conf = 1, one in the middle
+ *      of four low samples 0.25.
+ *   C. Steps 1 to 5 of rayn_hip_temporal_accumulate_device at W x H with c and nrm from B, the high G-buffer, the previous history,
+ *      prev_camera at prev_time_start, p->time_start and the uploaded world's hitable velocities, where step 5 reads
+ *      n' = fminf(nh + conf, (float)max_history), a = conf / n', out = h + a * (c - h).  A reset keeps n' = 1 (0 for a non-finite c), so
+ *      that "n_tap >= 1" keeps its meaning.  New history: A' = (out, n'), B' = (P, t), (nrm, 0) and o.
+ * With low_camera == NULL and confidence == 0 every output and the new history are bit for bit those of rayn_hip_upscale_device followed
+ * by rayn_hip_temporal_accumulate_device at the high size.  Moments, Catmull-Rom resampling and feedback are not part of this entry.
+ * d_out_color: the ACCUMULATED colour, 3 floats per high pixel; d_out_alpha, d_out_background (NULL together with their inputs) and
+ * d_out_normal: this frame's upscaled planes; d_out_weight may be NULL.  history_bytes: the size of EACH history, at least
+ * rayn_temporal_history_bytes(W, H).  DEVICE pointers, records and histories 16-byte aligned; enqueued on 'hip_stream' (NULL = the ctx's
+ * own stream; not waited for), on the ctx's GPU (devices[0] of a multi-device ctx).  RAYN_ERR_INVALID_ARG with a last error text, and
+ * nothing written, for: everything rayn_hip_upscale_device and rayn_hip_temporal_accumulate_device reject for the same arguments (the
+ * latter at the high size), a NULL WorldNormal, a NULL sp, confidence > 1, an unknown kind of either camera, a history smaller than
+ * rayn_temporal_history_bytes(W, H) or misaligned, and a history that overlaps the other history, an input or an output plane.  The
+ * inputs and the previous history are not modified. */
+int rayn_hip_temporal_upscale_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_upscale_params* up, const rayn_temporal_params* tp,
+                                     const rayn_temporal_upscale_params* sp, const rayn_camera* low_camera, const rayn_camera* prev_camera,
+                                     float prev_time_start, const float* d_color, const float* d_alpha, const float* d_background,
+                                     const float* d_normal, const void* d_low_records, const uint32_t* d_low_object, const void* d_high_records,
+                                     const uint32_t* d_high_object, const void* d_prev_history, void* d_new_history, size_t history_bytes,
+                                     float* d_out_color, float* d_out_alpha, float* d_out_background, float* d_out_normal, float* d_out_weight,
+                                     void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */
@@ -776,7 +824,8 @@ int rayn_hip_set_cold_bytes(rayn_ctx* ctx, uint64_t bytes);
 int rayn_hip_fma_policy(void);
 int rayn_hip_set_fma_policy(rayn_ctx* ctx, int policy);
 /* sizeof() of the ABI structs as compiled: 0 world_desc, 1 frame_params, 2 stats, 3 hitable,
- * 4 material, 5 light, 6 camera, 7 temporal_resample_params, 8 display_params, 9 upscale_params — lets a binding verify its layout. */
+ * 4 material, 5 light, 6 camera, 7 temporal_resample_params, 8 display_params, 9 upscale_params,
+ * 10 temporal_upscale_params — lets a binding verify its layout. */
 size_t rayn_hip_sizeof(int which);
 /* "" for the product build of the library; the VARIANT name of a `make variant` build (timing experiments: such a build is
  * only ever loaded through RAYN_HIP_LIB + RAYN_HIP_ALLOW_VARIANT=1, and bench.py prints the name in its result line). */

@@ -358,6 +358,21 @@ inline int upscale(rayn_ctx* ctx, Extent2u res, uint32_t factor, float sigma_pla
                                    d_high_object, d_out_color, d_out_alpha, d_out_background, d_out_normal, d_out_weight, hip_stream);
 }
 
+// Extension (include/rayn_hip.h: temporal supersampling): the guided upscaling fused with the temporal accumulate at factor * res, the
+// history at the high size.  `res`, p.width and p.height are the LOW film's; low_camera is the (jittered) camera the low film and the low
+// G-buffer were traced through, or null.  Device pointers; d_out_color receives the accumulated colour.  Returns the entry's code.
+inline int temporal_upscale(rayn_ctx* ctx, const rayn_frame_params& p, const rayn_upscale_params& up, const rayn_temporal_params& tp, bool confidence,
+                            const rayn_camera* low_camera, const rayn_camera* prev_camera, float prev_time_start, const float* d_color,
+                            const float* d_alpha, const float* d_background, const float* d_normal, const void* d_low_records,
+                            const uint32_t* d_low_object, const void* d_high_records, const uint32_t* d_high_object, const void* d_prev_history,
+                            void* d_new_history, size_t history_bytes, float* d_out_color, float* d_out_alpha, float* d_out_background,
+                            float* d_out_normal, float* d_out_weight = nullptr, void* hip_stream = nullptr) {
+    const rayn_temporal_upscale_params sp = {confidence ? 1u : 0u};
+    return rayn_hip_temporal_upscale_device(ctx, &p, &up, &tp, &sp, low_camera, prev_camera, prev_time_start, d_color, d_alpha, d_background, d_normal,
+                                            d_low_records, d_low_object, d_high_records, d_high_object, d_prev_history, d_new_history, history_bytes,
+                                            d_out_color, d_out_alpha, d_out_background, d_out_normal, d_out_weight, hip_stream);
+}
+
 // ---- setup::setup() (src/setup.rs:46-170) with the resolution as an argument ---------------------
 namespace setup {
 constexpr float WORLD_RADIUS = 100.0f;

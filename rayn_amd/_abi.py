@@ -82,6 +82,10 @@ class UpscaleParams(C.Structure):  # rayn_upscale_params
     _fields_ = [("factor", C.c_uint32), ("sigma_plane", C.c_float), ("sigma_position", C.c_float)]
 
 
+class TemporalUpscaleParams(C.Structure):  # rayn_temporal_upscale_params
+    _fields_ = [("confidence", C.c_uint32)]
+
+
 DISPLAY_TONE = {"linear": 0, "reinhard": 1, "aces": 2}  # rayn_display_params.tone by the name rayn_amd.Display takes
 
 TEMPORAL_RESAMPLE = {"bilinear": 0, "catmull_rom": 1}  # rayn_temporal_resample_params.resample by the name rayn_amd.Temporal takes

@@ -44,7 +44,7 @@ EXPORTS = [
     "rayn_temporal_moments_bytes", "rayn_hip_temporal_accumulate_moments_device", "rayn_hip_denoise_temporal_variance_device",
     "rayn_hip_denoise_temporal_variance_feedback_device", "rayn_hip_temporal_accumulate_resample_device",
     "rayn_display_scratch_bytes", "rayn_hip_display_pixels_device", "rayn_hip_display_color_device",
-    "rayn_hip_upscale_device",
+    "rayn_hip_upscale_device", "rayn_hip_temporal_upscale_device",
 ]
 
 
@@ -134,6 +134,9 @@ def lib():
         for fn in (L.rayn_hip_display_pixels_device, L.rayn_hip_display_color_device):
             fn.argtypes = [vp, C.POINTER(_abi.DisplayParams), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32] + [vp] * 5 + [C.c_size_t] + [vp] * 4
         L.rayn_hip_upscale_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(_abi.UpscaleParams)] + [vp] * 14
+        L.rayn_hip_temporal_upscale_device.argtypes = ([vp, C.POINTER(_abi.FrameParams), C.POINTER(_abi.UpscaleParams), C.POINTER(_abi.TemporalParams),
+                                                        C.POINTER(_abi.TemporalUpscaleParams), C.POINTER(_abi.Camera), C.POINTER(_abi.Camera), C.c_float]
+                                                       + [vp] * 10 + [C.c_size_t] + [vp] * 6)
         L.rayn_sets_1d.restype = C.c_uint32
         L.rayn_sets_1d.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_sets_2d.restype = C.c_uint32

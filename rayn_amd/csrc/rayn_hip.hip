@@ -21,6 +21,7 @@
 #include "tiles.h"
 #include "save_to.h"
 #include "display.h"
+#include "temporal_upscale.h"
 #include "upscale.h"
 #include "denoise.h"
 #include "denoise_variance.h"
@@ -1164,6 +1165,36 @@ int rayn_hip_temporal_accumulate_resample_device(rayn_ctx* ctx, const rayn_frame
                                bad ? 0u : rp->resample, bad);
 }
 
+// Temporal supersampling (temporal_upscale.hip): the guided upscaling and the temporal accumulate at the high size in one kernel.  The
+// hitable velocities come from the world as uploaded at the time of the call, by value, as for the accumulate entries.
+int rayn_hip_temporal_upscale_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_upscale_params* up, const rayn_temporal_params* tp,
+                                     const rayn_temporal_upscale_params* sp, const rayn_camera* low_camera, const rayn_camera* prev_camera,
+                                     float prev_time_start, const float* d_color, const float* d_alpha, const float* d_background,
+                                     const float* d_normal, const void* d_low_records, const uint32_t* d_low_object, const void* d_high_records,
+                                     const uint32_t* d_high_object, const void* d_prev_history, void* d_new_history, size_t history_bytes,
+                                     float* d_out_color, float* d_out_alpha, float* d_out_background, float* d_out_normal, float* d_out_weight,
+                                     void* hip_stream) {
+    const TemporalUpscaleCall c = {{d_color, d_alpha, d_background, d_normal, d_low_records, d_low_object, d_high_records, d_high_object,
+                                    d_out_color, d_out_alpha, d_out_background, d_out_normal, d_out_weight},
+                                   d_prev_history, d_new_history, history_bytes};
+    const char* why = temporal_upscale_check_args(p, up, tp, sp, low_camera, prev_camera, c);
+    if (!why && ctx && !ctx->cfg->have_world) why = "rayn_hip_upload_world has not been called";
+    TemporalScene ts;
+    memset(&ts, 0, sizeof ts);
+    DCamera low;
+    if (!why && prev_camera && !build_camera(*prev_camera, &ts.cam)) why = "unknown camera kind";
+    if (!why && low_camera && !build_camera(*low_camera, &low)) why = "unknown camera kind";
+    hipStream_t s;
+    if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
+    const rayn_world_desc& w = ctx->cfg->world;
+    ts.prev_time = prev_time_start; ts.cur_time = p->time_start;
+    ts.n_hitables = w.n_hitables < RAYN_MAX_HITABLES ? w.n_hitables : RAYN_MAX_HITABLES;
+    for (uint32_t i = 0; i < ts.n_hitables; i++)
+        ts.hvel[i] = make_float4(w.hitables[i].center_vel.x, w.hitables[i].center_vel.y, w.hitables[i].center_vel.z, w.hitables[i].animated ? 1.0f : 0.0f);
+    launch_temporal_upscale(s, p->width, p->height, *up, *tp, sp->confidence, low_camera ? &low : nullptr, ts, c);
+    return post_enqueued(ctx);
+}
+
 int rayn_hip_denoise_temporal_variance_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t iterations, float sigma_luminance,
                                               float sigma_normal, float sigma_alpha, const float* d_color, const float* d_alpha, const float* d_normal,
                                               const uint32_t* d_gbuffer_object, const void* d_history, size_t history_bytes, const void* d_moments,
@@ -1400,6 +1431,7 @@ size_t rayn_hip_sizeof(int which) {
     case 7: return sizeof(rayn_temporal_resample_params);
     case 8: return sizeof(rayn_display_params);
     case 9: return sizeof(rayn_upscale_params);
+    case 10: return sizeof(rayn_temporal_upscale_params);
     default: return 0;
     }
 }

@@ -284,6 +284,103 @@ class Upscale:
         return _abi.UpscaleParams(int(self.factor), float(self.sigma_plane), float(self.sigma_position))
 
 
+@dataclasses.dataclass(frozen=True)
+class Supersample:
+    """Parameters of the temporal supersampling of a sequence (rayn_hip_temporal_upscale_device, an extension; temporal upsampling as in
+    TAAU / FSR2; include/rayn_hip.h has the definition): render_sequence with `upscale` AND `temporal` keeps the temporal history at the
+    upscaled resolution and feeds it, frame after frame, with low frames whose cameras are offset by a fraction of a low pixel.
+
+    `jitter`: frame i of a call renders through the frame's camera offset by offsets(factor)[i % factor^2] low pixels, so that over
+    factor^2 frames every high pixel has had a low sample at its own centre; the kernel then finds every high pixel's footprint in the
+    low film by projecting its primary hit through that offset camera.  False: every low frame samples the same lattice (offset (0, 0),
+    no projection): the composition of Upscale and Temporal at the high size, bit for bit.
+
+    `confidence`: a high pixel blends this frame's value into its history with the weight of the nearest low sample that gave it - 1
+    when a low sample hit the pixel's centre, 0.25 in the middle of four - instead of 1 (the entry's conf; the history length grows by
+    the same amount).  False: every frame counts fully, as in Temporal.
+
+    The defaults are the best row of the measurement in DESIGN.md section 8 (tools/supersample_defaults.py: 8 frames at 160x96 and 32 spp
+    rebuilt at 320x192, the last frame against 1024 spp, as ratios to a native 320x192 frame of the same number of paths): jitter on,
+    confidence off.  On the shipped scene jitter alone brings Upscale(2)'s 0.68x to 0.60x under the moving camera and 0.66x to 0.58x
+    under a static one (the composition without jitter: 0.66x and 0.61x).  Confidence did not lower the error overall - 0.62x and 0.58x
+    on the shipped scene, 3.43x and 3.26x against 3.43x and 3.25x on the sphere scene s0 - so it is off by default.  Native Temporal() at
+    320x192 with the same number of paths is better than every row (0.48x and 0.46x; on s0 0.72x and 0.77x against 3.25x - 3.43x): what
+    supersampling buys is the render time of the low resolution, not a lower error than the full resolution at equal cost."""
+    jitter: bool = True
+    confidence: bool = False
+
+    def __post_init__(self):
+        for name in ("jitter", "confidence"):
+            v = getattr(self, name)
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"Supersample.{name} must be a bool, got {v!r}")
+
+    @staticmethod
+    def offsets(factor):
+        """The factor^2 camera offsets (jx, jy) of one cycle, in LOW pixels: phase i visits the sub-cell (ix, iy) of a low pixel with
+        k = i * (factor + 1) mod factor^2, ix = k mod factor, iy = k div factor - a walk along the diagonals that visits every cell once
+        - and its offset is ((ix + 0.5) / factor - 0.5, (iy + 0.5) / factor - 0.5), the centre of that cell relative to the centre of
+        the low pixel.  For factor >= 3 no two consecutive phases (the wrap from the last to the first included) share a row or a
+        column; for factor 2 the walk is (0, 0), (1, 1), (0, 1), (1, 0): two of its steps are diagonal, which is all a 2 x 2 grid allows."""
+        if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)) or not 1 <= factor <= 8:
+            raise ValueError(f"Supersample.offsets: factor must be an int in 1..8, got {factor!r}")
+        s = int(factor)
+        out = []
+        for i in range(s * s):
+            k = i * (s + 1) % (s * s)
+            out.append(((k % s + 0.5) / s - 0.5, (k // s + 0.5) / s - 0.5))
+        return out
+
+    def offset(self, factor, i):
+        """The offset of frame i of a call: offsets(factor)[i mod factor^2], and (0, 0) without jitter."""
+        return self.offsets(factor)[int(i) % (int(factor) ** 2)] if self.jitter else (0.0, 0.0)
+
+    def to_abi(self):
+        return _abi.TemporalUpscaleParams(int(bool(self.confidence)))
+
+
+def jittered_camera(camera, jx, jy, time_start):
+    """A copy of the rayn_camera `camera` (an _abi.Camera) offset by (jx, jy) pixels of ITS resolution: the centre ray of its pixel
+    (x, y) goes through what `camera` sees at the pixel coordinates (x + 0.5 + jx, y + 0.5 + jy).  With the basis u, v, w the camera has
+    at time_start (closures evaluated there, the definition of rayn_hip_temporal_accumulate_device's step 3):
+      orthographic:        origin and at both move by u * jx * full_w / res_w + v * jy * full_h / res_h - exact for every pixel;
+      pinhole, thin lens:  at moves by (u * jx * 2 half_w / res_w + v * jy * 2 half_h / res_h) * |origin - at|, a small rotation about
+                           the origin - exact at the image centre, and off by the perspective's second-order term elsewhere.
+    The shift is added to the closures' base values, so a moving camera keeps its velocities.  Computed in float64 and rounded into the
+    f32 fields: the temporal supersampling does not assume the shift, it projects through the camera it is given."""
+    out = type(camera).from_buffer_copy(camera)
+    ts = float(np.float32(time_start))
+
+    def at_time(base, vel, bit):
+        b = np.array([base.x, base.y, base.z], np.float64)
+        return b + np.array([vel.x, vel.y, vel.z], np.float64) * ts if camera.animated & bit else b
+
+    def unit(a):
+        return a / np.sqrt(a @ a)
+
+    o, at, up = at_time(camera.origin, camera.origin_vel, 1), at_time(camera.at, camera.at_vel, 2), at_time(camera.up, camera.up_vel, 4)
+    aspect = float(camera.res_w) / float(camera.res_h)
+    if camera.kind == _abi.CAM_ORTHOGRAPHIC:
+        w = unit(at - o)
+        u = unit(np.cross(w, up))
+        v = np.cross(u, w)
+        full_h = float(camera.vfov_or_size)
+        shift = u * (jx * full_h * aspect / camera.res_w) + v * (jy * full_h / camera.res_h)
+        moved = (out.origin, out.at)
+    elif camera.kind in (_abi.CAM_PINHOLE, _abi.CAM_THIN_LENS):
+        w = unit(o - at)
+        u = unit(np.cross(up, w))
+        v = np.cross(w, u)
+        half_h = float(np.tan(np.radians(float(camera.vfov_or_size)) / 2.0))
+        shift = (u * (jx * 2.0 * half_h * aspect / camera.res_w) + v * (jy * 2.0 * half_h / camera.res_h)) * np.sqrt((o - at) @ (o - at))
+        moved = (out.at,)
+    else:
+        raise ValueError(f"unknown camera kind {camera.kind!r}")
+    for vec in moved:
+        vec.x, vec.y, vec.z = vec.x + shift[0], vec.y + shift[1], vec.z + shift[2]
+    return out
+
+
 def display_scratch_bytes(width, height, levels):
     """rayn_display_scratch_bytes: bytes of device scratch the display transform needs for a width x height film with `levels` bloom
     levels (0 for a size it rejects or levels > 8).  A manual exposure without bloom needs none."""
@@ -622,6 +719,56 @@ class Context:
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
         self._chk(self._L.rayn_hip_upscale_device(self.h, int(params.width), int(params.height), C.byref(up), *ptrs[:4], *gp, *ptrs[4:],
                                                   None if d_out_weight is None else C.c_void_p(d_out_weight.data_ptr()), C.c_void_p(s)))
+
+    def temporal_upscale(self, params, upscale, temporal, supersample, d_film, d_low_gbuffer, d_high_gbuffer, d_prev_history, prev_camera,
+                         prev_time_start, d_new_history, d_out_film, low_camera=None, d_out_weight=None, stream=None):
+        """rayn_hip_temporal_upscale_device: the guided upscaling (Upscale `upscale`) of the low device film `d_film` of the frame `params`
+        (its width and height are the LOW film's) fused with the temporal accumulation (Temporal `temporal`; its resample and feedback are
+        not part of this entry) at upscale.factor times that size, by the Supersample `supersample`.  d_low_gbuffer / d_high_gbuffer: the
+        frame's G-buffers at both resolutions, the low one traced through `low_camera` (an _abi.Camera: the camera the low film was
+        rendered with, or None for the frame's own - the default footprint), the high one through the frame's own camera.
+        d_prev_history / d_new_history: uint8 CUDA tensors of temporal_history_bytes at the HIGH size (d_prev_history None: no history),
+        reprojected through prev_camera at prev_time_start.  d_out_film: a film dict of the high size; "color" receives the ACCUMULATED
+        colour, "alpha" / "background" (absent together with d_film's) and "normal" this frame's upscaled planes.  "color" and "normal"
+        are required on both sides.  d_out_weight: a float32 CUDA tensor of one float per high pixel, or None.  Enqueued on the stream, not
+        waited for."""
+        import torch
+        s_ = int(upscale.factor)
+        n = int(params.width) * int(params.height)
+        N = n * s_ * s_
+        ptrs = []
+        for film, count, what in ((d_film, n, "d_film"), (d_out_film, N, "d_out_film")):
+            for key, floats in (("color", 3), ("alpha", 1), ("background", 3), ("normal", 3)):
+                t = film.get(key)
+                if t is None:
+                    ptrs.append(None)
+                    continue
+                if not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= floats * count):
+                    raise ValueError(f"{what}[{key!r}] must be a contiguous float32 tensor of at least {floats * count} floats")
+                ptrs.append(C.c_void_p(t.data_ptr()))
+        gp = []
+        for g, count, what in ((d_low_gbuffer, n, "d_low_gbuffer"), (d_high_gbuffer, N, "d_high_gbuffer")):
+            rec, obj = g.get("records"), g.get("object")
+            if rec is None or not (rec.dtype == torch.float32 and rec.is_contiguous() and rec.numel() >= 4 * count):
+                raise ValueError(f"{what}['records'] must be a contiguous float32 tensor of at least {4 * count} floats")
+            if obj is None or not (obj.dtype == torch.int32 and obj.is_contiguous() and obj.numel() >= count):
+                raise ValueError(f"{what}['object'] must be a contiguous int32 tensor of at least {count} elements")
+            gp += [C.c_void_p(rec.data_ptr()), C.c_void_p(obj.data_ptr())]
+        if d_out_weight is not None and not (d_out_weight.dtype == torch.float32 and d_out_weight.is_contiguous() and d_out_weight.numel() >= N):
+            raise ValueError(f"d_out_weight must be a contiguous float32 tensor of at least {N} floats")
+        for name, t in (("d_prev_history", d_prev_history), ("d_new_history", d_new_history)):
+            if t is not None and not (t.dtype == torch.uint8 and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous uint8 tensor")
+        if d_new_history is None:
+            raise ValueError("d_new_history must be a contiguous uint8 tensor")
+        nbytes = d_new_history.numel() if d_prev_history is None else min(d_new_history.numel(), d_prev_history.numel())
+        up, tp, sp = upscale.to_abi(), temporal.to_abi(), supersample.to_abi()
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._chk(self._L.rayn_hip_temporal_upscale_device(
+            self.h, C.byref(params), C.byref(up), C.byref(tp), C.byref(sp), None if low_camera is None else C.byref(low_camera),
+            None if prev_camera is None else C.byref(prev_camera), float(prev_time_start), *ptrs[:4], *gp,
+            None if d_prev_history is None else C.c_void_p(d_prev_history.data_ptr()), C.c_void_p(d_new_history.data_ptr()), nbytes,
+            *ptrs[4:], None if d_out_weight is None else C.c_void_p(d_out_weight.data_ptr()), C.c_void_p(s)))
 
     def denoise(self, width, height, d_film, d_out_color, params, d_scratch=None, stream=None):
         """rayn_hip_denoise_device: the a-trous denoiser (Denoise `params`) of d_film["color"] into the float32 CUDA tensor d_out_color
@@ -1270,7 +1417,7 @@ class Film:
         return _prog.error_map(arrays, w, h, (pr["params"].tile_w, pr["params"].tile_h), pr["noise_floor"])
 
     def render_sequence(self, world, camera, integrator, filter, tile_size, frames, frame_rate, shutter_speed, samples, write_channels,
-                        output_folder, base_name, transparent_background=False, writers=None, denoise=None, display=None, upscale=None, temporal=None):
+                        output_folder, base_name, transparent_background=False, writers=None, denoise=None, display=None, upscale=None, supersample=None, temporal=None):
         """rayn's main loop (src/main.rs:58-96) on the GPU: for each frame of `frames`, render_frame_into at
         frame_start = frame as f32 * (1.0 / frame_rate as f32), frame_end = frame_start + shutter_speed (f32, src/main.rs:61-62), then
         save_to(write_channels, output_folder, f"{base_name}_{frame:04d}", transparent_background).  rayn writes every frame under
@@ -1322,17 +1469,43 @@ class Film:
         upscale kernel go on the render stream, every written image is made from the upscaled film and its file name gets _x{factor}
         appended to whatever suffix it would have had (_color_x2.png, _alpha_x2.png, _color_denoised_display_x2.png, ...).  `denoise` (a
         Denoise) and `display` then work on the upscaled film.  The G-buffers, the upscaled film and the scratch are allocated once and
-        nothing synchronises.  The film's channels stay the rendered, low frame.  `temporal` together with `upscale` raises ValueError:
-        histories at two resolutions are not built.  upscale=None is the path described above, unchanged."""
+        nothing synchronises.  The film's channels stay the rendered, low frame.  `temporal` together with `upscale` raises ValueError
+        unless `supersample` says how the two meet.  upscale=None is the path described above, unchanged.
+
+        With `supersample` (a Supersample, an extension; it needs `upscale` and `temporal` both), the temporal history lives at the
+        upscaled resolution: per frame the world is uploaded with the frame's camera offset by supersample.offset(factor, i) low pixels
+        (jittered_camera), the frame is rendered and its low G-buffer traced through that camera, the world is uploaded with the frame's
+        own camera again, the high G-buffer is traced, and ONE kernel (Context.temporal_upscale) upscales the frame and blends it into
+        the full-size history in place of Context.upscale.  The Color image is made from the accumulated colour, every other image from
+        the kernel's upscaled planes; the names are those of upscale= with temporal= (_color_temporal_x2.png, ...).  `denoise` (a
+        Denoise) and `display` work on the high film as for upscale=.  A VarianceDenoise, temporal.resample != "bilinear" and
+        temporal.feedback > 0 raise ValueError before anything renders: moments, Catmull-Rom and feedback are not built at two
+        resolutions.  Uploading a world is a host-side copy and every pass stages its own device scene on the stream when it is
+        called, so the two uploads per frame need no synchronisation; without jitter there are none.  The histories, G-buffers and
+        scratch are allocated once.  Afterwards the uploaded world is the frame's own.  supersample=None is the path described above,
+        unchanged."""
         import concurrent.futures as cf
         import torch
         variance = isinstance(denoise, VarianceDenoise)
+        if supersample is not None:
+            if not isinstance(supersample, Supersample):
+                raise ValueError(f"supersample must be a Supersample, got {supersample!r}")
+            if upscale is None or temporal is None:
+                raise ValueError("supersample= joins upscale= and temporal=: pass both")
+            if not isinstance(temporal, Temporal):
+                raise ValueError(f"temporal must be a Temporal, got {temporal!r}")
+            if variance:
+                raise ValueError("supersample= with a VarianceDenoise is not built: the luminance moments live at one resolution")
+            if temporal.resample != "bilinear":
+                raise ValueError("supersample= with Temporal.resample != 'bilinear' is not built")
+            if float(temporal.feedback) > 0.0:
+                raise ValueError("supersample= with Temporal.feedback > 0 is not built")
         if variance and temporal is None:
             raise ValueError("render_sequence renders plain frames: VarianceDenoise needs the state of a progressive render")
         if isinstance(temporal, Temporal) and float(temporal.feedback) > 0.0 and not variance:
             raise ValueError("Temporal.feedback > 0 feeds a VarianceDenoise's first pass back into the history: pass one as `denoise`")
         if upscale is not None:
-            if temporal is not None:
+            if temporal is not None and supersample is None:
                 raise ValueError("temporal= together with upscale= is not built: the temporal histories live at one resolution")
             upscale, up_keys = self._upscale_plan(upscale)
         frames = [int(f) for f in frames]
@@ -1352,7 +1525,7 @@ class Film:
             if variance and denoise is not None and float(denoise.sigma_alpha) != 0.0 and ChannelKind.Alpha not in self.channel_kinds:
                 raise ValueError("variance-guided denoising of a temporal sequence needs the film's Alpha channel when sigma_alpha != 0")
             if ChannelKind.Color not in write_channels:
-                temporal = None
+                temporal = supersample = None  # nothing shows the accumulated colour: the plain path (upscale= alone with supersample=)
             else:
                 jobs = [(kind, bpp, ("color_temporal" if denoise is None else "color_temporal_denoised") if kind == ChannelKind.Color else suffix)
                         for kind, bpp, suffix in jobs]
@@ -1411,7 +1584,11 @@ class Film:
                 d_mom = [None, None]
                 if temporal is not None and variance and denoise is not None:
                     d_mom = [torch.empty(temporal_moments_bytes(w, h), dtype=torch.uint8, device=self.device) for _ in range(2)]
-                if temporal is not None:
+                if supersample is not None:  # the histories live at the high size; the G-buffers are the upscale's
+                    d_hist = [torch.empty(temporal_history_bytes(ow, oh), dtype=torch.uint8, device=self.device) for _ in range(2)]
+                    prev_start = None
+                    desc_low = type(desc).from_buffer_copy(desc)  # the world as the low frame is rendered: the camera is set per frame
+                elif temporal is not None:
                     d_gbuf = alloc_gbuffer(w, h, self.device)
                     d_gscratch = torch.empty(gbuffer_scratch_bytes(w, h), dtype=torch.uint8, device=self.device)
                     d_hist = [torch.empty(temporal_history_bytes(w, h), dtype=torch.uint8, device=self.device) for _ in range(2)]
@@ -1435,6 +1612,11 @@ class Film:
                             raise fut.exception()
                     start = f32(frame) * inv_rate
                     p = frame_params(w, h, samples, mb, vm, frame, (float(start), float(f32(start + shutter))), tile_size)
+                    low_cam = None
+                    if supersample is not None and supersample.jitter:
+                        low_cam = jittered_camera(desc.camera, *supersample.offset(upscale.factor, i), p.time_start)
+                        desc_low.camera = low_cam
+                        self.ctx.upload_world(desc_low)
                     self.ctx.render_device(p, d_tables, d_film, stream.cuda_stream)  # blocking: returns when the frame is complete
                     st = self.ctx.stats()
                     st["frame"] = frame
@@ -1450,11 +1632,19 @@ class Film:
                     d_base = d_film  # what the images are made from
                     if upscale is not None:
                         self.ctx.gbuffer(p, d_glow, d_uscratch, stream.cuda_stream)
+                        if low_cam is not None:
+                            self.ctx.upload_world(desc)  # the high G-buffer and the history belong to the frame's own camera
                         self.ctx.gbuffer(_scaled_params(p, upscale.factor), d_ghigh, d_uscratch, stream.cuda_stream)
-                        self.ctx.upscale(p, upscale, d_low, d_glow, d_ghigh, d_up, None, stream.cuda_stream)
+                        if supersample is not None:
+                            self.ctx.temporal_upscale(p, upscale, temporal, supersample, d_low, d_glow, d_ghigh,
+                                                      None if prev_start is None else d_hist[(i + 1) % 2], None if prev_start is None else desc.camera,
+                                                      0.0 if prev_start is None else prev_start, d_hist[i % 2], d_up, low_cam, None, stream.cuda_stream)
+                            prev_start = p.time_start
+                        else:
+                            self.ctx.upscale(p, upscale, d_low, d_glow, d_ghigh, d_up, None, stream.cuda_stream)
                         d_base = d_up
                     d_shown = d_base  # what the Color image is made from
-                    if temporal is not None:
+                    if temporal is not None and supersample is None:
                         self.ctx.gbuffer(p, d_gbuf, d_gscratch, stream.cuda_stream)
                         self.ctx.temporal_accumulate(p, temporal, d_film, d_gbuf, None if prev_start is None else d_hist[(i + 1) % 2],
                                                      None if prev_start is None else desc.camera, 0.0 if prev_start is None else prev_start,
