@@ -898,7 +898,22 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *   rayn_hip_probe_march_limits  the sizes that decide the MODE of the persistent march kernels, as the library was built and the context tuned: the entries a
  *                             wave takes from its queue per atomic (chunk); the remaining-entry count below which a fetched chunk puts its wave into the endgame
  *                             (endgame_entries; k_shadow_bulb multiplies it by its rays per lane); the grid cap (persistent_blocks, blocks of 4 waves) and
- *                             k_shadow_bulb's rays per lane (bulb_rays) of the ctx's launch tuning.  No GPU work.  Tests size their probe inputs from these. */
+ *                             k_shadow_bulb's rays per lane (bulb_rays) of the ctx's launch tuning.  No GPU work.  Tests size their probe inputs from these.
+ *   rayn_hip_probe_resolve    the film resolve (k_resolve_reg / k_resolve_blk / k_resolve_huge) through the PRODUCT launcher - so the variant is the one the product picks
+ *                             for `spp` - on caller-built tiles and termination records (no scene, no world needed; the device scene is zero but for spp and width).
+ *     in   width = film width of the unpacked tiles; spp = samples per pixel as the host produces them (a multiple of 4 in 4..16384); tiles[n_tiles][8] = the
+ *          device tile words x0, y0, ew, eh, pool_base, n_paths, film_base, film_packed (n_paths is not read by the resolve); max_tile_pixels = the x size of
+ *          the grid (>= every tile's ew * eh; larger is allowed, the surplus blocks exit); per path of the n_paths-slot pool: term_info (depth in bits 0..6 |
+ *          Background flag in bit 7, 0xFF = no sample), term_key (the termination slot), col0_rgb[3], aov_xyz[3] and aov_obj (the depth-0 object, < 0xFF, or
+ *          0xFF for none); base_hist[n_depths][hist_stride] = the slot at which tile t's binned segment of depth d began, at [d * hist_stride + t] (read by
+ *          k_resolve_blk only: 512 < spp <= 4096; may be null otherwise); sentinel = the word every output float starts as.
+ *     out  out_color[3 N], out_alpha[N], out_background[3 N], out_normal[3 N], N = out_pixels: film planes, or the packed planes of film_packed tiles.  A
+ *          pixel no tile owns keeps the sentinel in all ten words.
+ *     Rejected with RAYN_ERR_INVALID_ARG - what the kernels could not index, or what their stated preconditions exclude: spp out of range; a tile of no
+ *          pixel, of more than 1024 pixels or of more than max_tile_pixels; pool_base + ew * eh * spp beyond n_paths; a film index at or beyond out_pixels,
+ *          or one that two tiles own; a contributing sample deeper than 120; an object word that is neither below 0xFF nor 0xFF; for 512 < spp <= 4096 a
+ *          depth at or beyond n_depths, hist_stride < n_tiles, a slot below its base_hist entry or 2^25 or more above it; two contributing samples of one
+ *          pixel with equal (depth, slot) - a slot holds one path, and the order of such a pair would be undefined.  Only the paths tiles own are looked at. */
 int rayn_hip_probe_march_limits(const rayn_ctx* ctx, uint32_t* chunk, uint32_t* endgame_entries,
                                 uint32_t* persistent_blocks, uint32_t* bulb_rays);
 int rayn_hip_probe_sdf_dist(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t hitable_index,
@@ -918,6 +933,12 @@ int rayn_hip_probe_queue(rayn_ctx* ctx, uint32_t nclass, uint32_t n_tiles, const
                          uint32_t max_slots, uint32_t sentinel, uint32_t out_slots, uint32_t* out_bq,
                          uint32_t* out_qn, uint32_t* out_tile, uint32_t* out_cls_cnt,
                          uint32_t* out_cls_base, uint64_t* ctl_io);
+int rayn_hip_probe_resolve(rayn_ctx* ctx, uint32_t width, uint32_t spp, uint32_t n_tiles, const uint32_t* tiles,
+                           uint32_t max_tile_pixels, uint32_t n_paths, const uint8_t* term_info,
+                           const uint32_t* term_key, const float* col0_rgb, const float* aov_xyz,
+                           const uint32_t* aov_obj, const uint32_t* base_hist, uint32_t hist_stride,
+                           uint32_t n_depths, uint32_t sentinel, uint32_t out_pixels, float* out_color,
+                           float* out_alpha, float* out_background, float* out_normal);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,9 @@
-// probes.hip — the test probes of the C ABI (rayn_hip_probe_*): per-lane device primitives, the PRODUCT march kernels and the PRODUCT queue stages on caller data.
+// probes.hip — the test probes of the C ABI (rayn_hip_probe_*): per-lane device primitives, the PRODUCT march kernels, the PRODUCT queue stages and the PRODUCT film resolve on caller data.
 // Test infrastructure; defines no kernels (kernels.hip holds the probe kernels).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -300,6 +301,92 @@ int rayn_hip_probe_queue(rayn_ctx* ctx, uint32_t nclass, uint32_t n_tiles, const
     const uint64_t fin[12] = {hc.q_groups, hc.q_valid, hc.b_groups, hc.b_valid, hc.overflow, hc.segments, hc.shaded_slots, hc.entries_sum, hc.next_sum,
                               hc.job_count, hc.head_shadow, hc.head_extend};
     memcpy(ctl_io, fin, sizeof fin);
+    return RAYN_OK;
+}
+// The film resolve on caller-built tiles and termination records, through launch_resolve (so the variant is the product's choice for spp).  The resolve
+// reads spp and width of the scene and term_info / term_key / col0 / aov of the pool; everything else of both stays zero / null.  The four planes start
+// filled with `sentinel`.  Everything the kernels would index is checked here first, and so are their preconditions (rayn_hip.h lists them).
+int rayn_hip_probe_resolve(rayn_ctx* ctx, uint32_t width, uint32_t spp, uint32_t n_tiles, const uint32_t* tiles, uint32_t max_tile_pixels, uint32_t n_paths,
+                           const uint8_t* term_info, const uint32_t* term_key, const float* col0_rgb, const float* aov_xyz, const uint32_t* aov_obj,
+                           const uint32_t* base_hist, uint32_t hist_stride, uint32_t n_depths, uint32_t sentinel, uint32_t out_pixels, float* out_color,
+                           float* out_alpha, float* out_background, float* out_normal) {
+    if (!ctx) return RAYN_ERR_INVALID_ARG;
+    if (!tiles || !term_info || !term_key || !col0_rgb || !aov_xyz || !aov_obj || !out_color || !out_alpha || !out_background || !out_normal)
+        return fail(ctx, RAYN_ERR_INVALID_ARG, "null buffer");
+    if (spp < 4 || spp > 16384 || spp % 4) return fail(ctx, RAYN_ERR_INVALID_ARG, "spp is not a multiple of 4 in 4..16384");
+    if (n_tiles == 0 || n_tiles > 65535) return fail(ctx, RAYN_ERR_INVALID_ARG, "n_tiles outside 1..65535 (the grid's y size)");
+    if (max_tile_pixels == 0 || max_tile_pixels > (1u << 16)) return fail(ctx, RAYN_ERR_INVALID_ARG, "max_tile_pixels outside 1..2^16");
+    if (n_paths == 0 || n_paths > (1u << 27) || out_pixels == 0 || out_pixels > (1u << 24) || width == 0) return fail(ctx, RAYN_ERR_INVALID_ARG, "probe size out of range");
+    const bool blk = spp > 512 && spp <= MAX_SPP_RESOLVE_BLK; // k_resolve_blk: the only variant that reads base_hist
+    if (blk && (!base_hist || hist_stride < n_tiles || n_depths == 0 || n_depths > MAX_BOUNCES + 1))
+        return fail(ctx, RAYN_ERR_INVALID_ARG, "512 < spp <= 4096 needs base_hist[n_depths][hist_stride] with hist_stride >= n_tiles and n_depths in 1..121");
+    std::vector<DTile> ht(n_tiles);
+    std::vector<uint8_t> owned(out_pixels, 0);
+    std::vector<unsigned long long> keys(spp);
+    for (uint32_t t = 0; t < n_tiles; t++) {
+        const uint32_t* w = tiles + 8 * (size_t)t;
+        DTile& T = ht[t];
+        T.x0 = w[0]; T.y0 = w[1]; T.ew = w[2]; T.eh = w[3]; T.pool_base = w[4]; T.n_paths = w[5]; T.film_base = w[6]; T.film_packed = w[7];
+        const uint64_t npx = (uint64_t)T.ew * T.eh;
+        if (npx == 0 || npx > MAX_TILE_PIXELS || npx > max_tile_pixels) return fail(ctx, RAYN_ERR_INVALID_ARG, "a tile has no pixel, more than 1024 pixels or more than max_tile_pixels");
+        if ((uint64_t)T.pool_base + npx * spp > n_paths) return fail(ctx, RAYN_ERR_INVALID_ARG, "a tile's paths end beyond the path arrays");
+        for (uint32_t lpix = 0; lpix < (uint32_t)npx; lpix++) {
+            const uint64_t fi = T.film_packed ? (uint64_t)T.film_base + lpix : (uint64_t)T.x0 + lpix / T.eh + ((uint64_t)T.y0 + lpix % T.eh) * width;
+            if (fi >= out_pixels) return fail(ctx, RAYN_ERR_INVALID_ARG, "a film index at or beyond out_pixels");
+            if (owned[fi]) return fail(ctx, RAYN_ERR_INVALID_ARG, "two tile pixels share a film index");
+            owned[fi] = 1;
+            const size_t P0 = (size_t)T.pool_base + (size_t)lpix * spp;
+            uint32_t nk = 0;
+            for (uint32_t i = 0; i < spp; i++) {
+                const uint32_t ob = aov_obj[P0 + i], info = term_info[P0 + i];
+                if (ob > OBJ_NONE) return fail(ctx, RAYN_ERR_INVALID_ARG, "an object word is neither below 0xFF nor OBJ_NONE");
+                if (info == TERM_NONE) continue;
+                const uint32_t d = info & 0x7Fu, slot = term_key[P0 + i];
+                if (d > MAX_BOUNCES) return fail(ctx, RAYN_ERR_INVALID_ARG, "a contributing sample is deeper than max_bounces can be (120)");
+                if (blk) {
+                    if (d >= n_depths) return fail(ctx, RAYN_ERR_INVALID_ARG, "a depth at or beyond n_depths");
+                    const uint32_t base = base_hist[(size_t)d * hist_stride + t];
+                    if (slot < base || slot - base >= (1u << RESOLVE_KEY_SHIFT)) return fail(ctx, RAYN_ERR_INVALID_ARG, "a slot below its base_hist entry, or 2^25 or more above it");
+                }
+                keys[nk++] = ((unsigned long long)d << 32) | slot;
+            }
+            std::sort(keys.begin(), keys.begin() + nk);
+            if (std::adjacent_find(keys.begin(), keys.begin() + nk) != keys.begin() + nk)
+                return fail(ctx, RAYN_ERR_INVALID_ARG, "two contributing samples of one pixel have equal (depth, slot)");
+        }
+    }
+    const KernelSet K = kernel_set(ctx->cfg->fma_policy);
+    HIPCHK(hipSetDevice(ctx->device));
+    DScene hs;
+    memset(&hs, 0, sizeof hs);
+    hs.spp = spp; hs.width = width;
+    HIPCHK(hipMemcpy(ctx->d_scene, &hs, sizeof hs, hipMemcpyHostToDevice));
+    std::vector<float4> c0(n_paths), av(n_paths);
+    for (size_t i = 0; i < n_paths; i++) {
+        float obf; memcpy(&obf, &aov_obj[i], 4);
+        c0[i] = make_float4(col0_rgb[3 * i], col0_rgb[3 * i + 1], col0_rgb[3 * i + 2], 0.0f);
+        av[i] = make_float4(aov_xyz[3 * i], aov_xyz[3 * i + 1], aov_xyz[3 * i + 2], obf);
+    }
+    const size_t NP = out_pixels, hist_words = blk ? (size_t)n_depths * hist_stride : 0;
+    DevBuf d_tiles, d_info, d_key, d_c0, d_av, d_hist, d_out;
+    HIPCHK(d_tiles.alloc((size_t)n_tiles * sizeof(DTile))); HIPCHK(d_info.alloc(n_paths)); HIPCHK(d_key.alloc((size_t)n_paths * 4));
+    HIPCHK(d_c0.alloc((size_t)n_paths * 16)); HIPCHK(d_av.alloc((size_t)n_paths * 16)); HIPCHK(d_hist.alloc(hist_words * 4)); HIPCHK(d_out.alloc(NP * 40));
+    std::vector<uint32_t> fill(NP * 10, sentinel);
+    HIPCHK(hipMemcpy(d_tiles.p, ht.data(), (size_t)n_tiles * sizeof(DTile), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_info.p, term_info, n_paths, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_key.p, term_key, (size_t)n_paths * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_c0.p, c0.data(), (size_t)n_paths * 16, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_av.p, av.data(), (size_t)n_paths * 16, hipMemcpyHostToDevice));
+    if (hist_words) HIPCHK(hipMemcpy(d_hist.p, base_hist, hist_words * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_out.p, fill.data(), NP * 40, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize()); // the uploads above ran on the null stream
+    Pool pool;
+    memset(&pool, 0, sizeof pool);
+    pool.col0 = d_c0.as<float4>(); pool.aov = d_av.as<float4>(); pool.term_key = d_key.as<uint32_t>(); pool.term_info = d_info.as<uint8_t>();
+    float *o_color = d_out.as<float>(), *o_alpha = o_color + 3 * NP, *o_bg = o_alpha + NP, *o_normal = o_bg + 3 * NP;
+    K.resolve(ctx->stream, ctx->d_scene, d_tiles.as<DTile>(), n_tiles, max_tile_pixels, spp, pool, o_color, o_alpha, o_bg, o_normal, d_hist.as<uint32_t>(), hist_stride);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out_color, o_color, NP * 12, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_alpha, o_alpha, NP * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_background, o_bg, NP * 12, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_normal, o_normal, NP * 12, hipMemcpyDeviceToHost));
     return RAYN_OK;
 }
 
