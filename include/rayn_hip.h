@@ -913,7 +913,46 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *          pixel, of more than 1024 pixels or of more than max_tile_pixels; pool_base + ew * eh * spp beyond n_paths; a film index at or beyond out_pixels,
  *          or one that two tiles own; a contributing sample deeper than 120; an object word that is neither below 0xFF nor 0xFF; for 512 < spp <= 4096 a
  *          depth at or beyond n_depths, hist_stride < n_tiles, a slot below its base_hist entry or 2^25 or more above it; two contributing samples of one
- *          pixel with equal (depth, slot) - a slot holds one path, and the order of such a pair would be undefined.  Only the paths tiles own are looked at. */
+ *          pixel with equal (depth, slot) - a slot holds one path, and the order of such a pair would be undefined.  Only the paths tiles own are looked at.
+ *   rayn_hip_probe_shade_limits  the sizes that decide how many grid-stride trips the streaming kernels of the shade stage make, as the library was built: the block
+ *                             cap of their grids (stream_blocks; k_shadow_list, k_shade_finish), the [sample][slot] ids a block of k_shadow_list scans per trip
+ *                             (list_ids_per_block) and the block size of k_shade_setup (setup_threads; its grid has no cap).  No GPU work.  Tests size the case that
+ *                             reaches the second trip from these.
+ *   rayn_hip_probe_shade      the shade stage of ONE depth through the PRODUCT launcher (launch_shade: k_shade_setup, k_shadow_list, the shadow-march kernel the
+ *                             product picks for the uploaded scene and the ctx's tuning, k_shade_finish) under the ctx's mul_add policy, on a caller-built binned
+ *                             queue and path pool - PathTracingIntegrator::integrate (src/integrator.rs:47-204) for n_slots / 4 packets of four lanes.
+ *     in   p and the four tables as rayn_hip_render_frame takes them (the packed sample records are built by the product's own kernel); depth <= max_bounces;
+ *          n_slots = binned slots, a multiple of 64; slots 4k..4k+3 are one packet; max_slots >= n_slots = the upper bound the grids are sized by (the surplus
+ *          exits); nee_cap >= n_slots = the plane stride of the per-slot NEE records; ref[n_slots] = the binned queue: a pool index below n_pool, or 0xFFFFFFFF
+ *          for a padding lane; geo0 / geo1 / col0 / col1 [n_pool][4] = the pool records in the pool's own encoding: origin xyz, dir x | dir yz, hit t, bits
+ *          (hit object | sample index << 8) | radiance rgb, throughput r | throughput gb, bits (film pixel index), ray time; sentinel = the word that pre-fills what
+ *          the kernels may or may not write.
+ *          The probe owns every device buffer (the pool, the NEE records, the survivor ballots, the control block with b_groups = n_slots / 64) and pre-fills:
+ *          aov, term_key and every float plane of the NEE records with the sentinel; term_info with 0xFF (no sample); the visibility plane with 2 ("march
+ *          pending") over all ns * nee_cap entries - the worst stale value: a (sample, slot) the setup kernel forgets becomes a shadow job and an occluded sample;
+ *          the job segments with zeros.
+ *     out  the pool as the stage left it: out_geo0 / out_geo1 / out_col0 / out_col1 / out_aov [n_pool][4], out_term_key[n_pool], out_term_info[n_pool];
+ *          out_alive_mask / out_bgrp_cnt [n_slots / 64] = the survivor ballot and count of every group; out_jobs[3] = job_count and shadow_jobs of the control
+ *          block, and the shadow-march kernel launch_shadow_march picks (0 none: no TracedSDF, 1 k_shadow, 2 k_shadow1, 3 k_shadow_bulb).
+ *          A spawned lane has its new origin / dir / throughput and its radiance in the pool and its bit in the ballot; a terminated one has term_info = depth |
+ *          Background flag (bit 7), term_key = its SLOT and its radiance in col0; a depth-0 hit of a light-receiving object has its WorldNormal sample and object
+ *          in aov.  The layout of the NEE records is NOT part of this contract: the probe only checks, after the run, that no word of theirs at a slot index in
+ *          [n_slots, nee_cap) changed and that job_count <= ns * n_slots (RAYN_ERR_HIP with a last error text otherwise).
+ *     Rejected with RAYN_ERR_INVALID_ARG - what the kernels could not index, or what their stated preconditions exclude: a null buffer; n_slots 0 or not a
+ *          multiple of 64; n_pool 0, or n_pool or max_slots above 2^27 (the probe's own size limit); max_slots or nee_cap below n_slots; ns * nee_cap or ns * max_slots beyond 2^32 - 2^26 (32-bit [sample][slot] ids; ns = 4, + 4 *
+ *          volume_marches when the volume scatters); a ref that is neither 0xFFFFFFFF nor below n_pool; a pool slot referenced twice; a packet whose lane 0 is
+ *          a padding lane while a later lane is not (lane 0 of a bin packet is always a real hit; a packet of four padding lanes is the tail of a group); a
+ *          packet whose valid lanes name different objects; an object at or beyond n_hitables; a sample index at or beyond 4 * samples; a pixel index at or
+ *          beyond width * height; a depth above max_bounces.  Only the pool records ref names are looked at. */
+int rayn_hip_probe_shade_limits(const rayn_ctx* ctx, uint32_t* stream_blocks, uint32_t* list_ids_per_block,
+                                uint32_t* setup_threads);
+int rayn_hip_probe_shade(rayn_ctx* ctx, const rayn_frame_params* p, const float* samples_1d, const float* samples_2d,
+                         const float* scramble, const float* fis_table, uint32_t depth, uint32_t n_slots,
+                         uint32_t max_slots, uint32_t nee_cap, const uint32_t* ref, uint32_t n_pool,
+                         const float* geo0, const float* geo1, const float* col0, const float* col1,
+                         uint32_t sentinel, float* out_geo0, float* out_geo1, float* out_col0, float* out_col1,
+                         float* out_aov, uint32_t* out_term_key, uint8_t* out_term_info,
+                         uint64_t* out_alive_mask, uint8_t* out_bgrp_cnt, uint64_t* out_jobs);
 int rayn_hip_probe_march_limits(const rayn_ctx* ctx, uint32_t* chunk, uint32_t* endgame_entries,
                                 uint32_t* persistent_blocks, uint32_t* bulb_rays);
 int rayn_hip_probe_sdf_dist(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t hitable_index,

@@ -56,6 +56,10 @@ def lib(fma=False, variant=None):
         L.oracle_trace_tile.restype = C.c_int64
         L.oracle_trace_tile.argtypes = [C.c_void_p, C.c_void_p, fp, fp, fp, fp, C.c_uint32, C.c_uint64,
                                         up, up, up, up, up, up]
+        L.oracle_trace_shade.restype = C.c_int64
+        L.oracle_trace_shade.argtypes = [C.c_void_p, C.c_void_p, fp, fp, fp, fp, C.c_uint32, C.c_uint64, up, up, fp, up, fp]
+        L.oracle_shade_packets.restype = C.c_int
+        L.oracle_shade_packets.argtypes = [C.c_void_p, C.c_void_p, fp, fp, C.c_uint32, C.c_uint64, up, up, fp, up, fp]
         L.oracle_build_rd_tables.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, fp, fp]
         L.oracle_build_scramble.argtypes = [C.c_uint32, C.c_uint32, fp]
         L.oracle_build_fis_table.argtypes = [C.c_uint32, C.c_float, fp]
@@ -124,6 +128,59 @@ def trace_tile(world_desc, params, tables, tile_index, fma=False, variant=None):
         raise RuntimeError(f"oracle_trace_tile failed: {n}")
     keys = ["depth", "obj", "px", "py", "sample", "valid"]
     return {k: a[:n].copy() for k, a in zip(keys, arrs)}
+
+
+# lane status of shade_packets / trace_shade
+SH_INVALID, SH_SPAWNED, SH_COLOR, SH_BACKGROUND = 0, 1, 2, 3
+# the 15 floats of a lane: what goes in ...
+SHADE_IN = {"origin": slice(0, 3), "dir": slice(3, 6), "t": 6, "time": 7, "radiance": slice(8, 11), "throughput": slice(11, 14), "scramble": 14}
+# ... and what comes out (what the status does not define is 0: a terminated lane has only its radiance, the Color / Background sample)
+SHADE_OUT = {"radiance": slice(0, 3), "throughput": slice(3, 6), "origin": slice(6, 9), "dir": slice(9, 12), "normal": slice(12, 15)}
+
+
+def _shade_dict(pk, lane_u, lane_f, out_u, out_f):
+    return {"depth": pk[:, 0].copy(), "obj": pk[:, 1].copy(), "valid": lane_u[:, :, 0].copy(), "sample": lane_u[:, :, 1].copy(), "tcx": lane_u[:, :, 2].copy(),
+            "tcy": lane_u[:, :, 3].copy(), "lane_f": lane_f, "status": out_u[:, :, 0].copy(), "aov": out_u[:, :, 1].copy(), "out_f": out_f}
+
+
+def trace_shade(world_desc, params, tables, tile_index, fma=False):
+    """Every Integrator::integrate call of one tile, rendered single-threaded, per depth in process_hits order.  dict of arrays over the n packets:
+    depth, obj [n]; valid, sample, tcx, tcy [n, 4]; lane_f [n, 4, 15] (SHADE_IN); status, aov [n, 4]; out_f [n, 4, 15] (SHADE_OUT)."""
+    L = lib(fma)
+    s1, s2, scr, fis = tables
+    cap = (params.tile_w * params.tile_h * params.samples + 16) * (params.max_bounces + 2)
+    pk, lane_u, lane_f = np.zeros((cap, 2), np.uint32), np.zeros((cap, 4, 4), np.uint32), np.zeros((cap, 4, 15), np.float32)
+    out_u, out_f = np.zeros((cap, 4, 2), np.uint32), np.zeros((cap, 4, 15), np.float32)
+    n = L.oracle_trace_shade(C.byref(world_desc), C.byref(params), _fp(s1), _fp(s2), _fp(scr), _fp(fis), tile_index, cap,
+                             _up(pk), _up(lane_u), _fp(lane_f), _up(out_u), _fp(out_f))
+    if n < 0 or n > cap:
+        raise RuntimeError(f"oracle_trace_shade failed: {n}")
+    return _shade_dict(pk[:n], lane_u[:n], lane_f[:n].copy(), out_u[:n], out_f[:n].copy())
+
+
+def shade_packets(world_desc, params, tables, depth, obj, valid, sample, lane_f, fma=False):
+    """get_shading_info + Integrator::integrate on caller-built packets of one depth: obj [n], valid / sample [n, 4], lane_f [n, 4, 15] (SHADE_IN).
+    -> (status [n, 4], aov [n, 4], out_f [n, 4, 15])."""
+    L = lib(fma)
+    s1, s2 = tables[0], tables[1]
+    obj = np.ascontiguousarray(obj, np.uint32)
+    n = len(obj)
+    lane_u = np.zeros((n, 4, 4), np.uint32)
+    lane_u[:, :, 0] = np.asarray(valid).reshape(n, 4) != 0
+    lane_u[:, :, 1] = np.asarray(sample).reshape(n, 4)
+    lane_f = np.ascontiguousarray(lane_f, np.float32).reshape(n, 4, 15)
+    out_u, out_f = np.zeros((n, 4, 2), np.uint32), np.zeros((n, 4, 15), np.float32)
+    rc = L.oracle_shade_packets(C.byref(world_desc), C.byref(params), _fp(s1), _fp(s2), depth, n, _up(obj), _up(lane_u), _fp(lane_f), _up(out_u), _fp(out_f))
+    if rc != 0:
+        raise ValueError(f"oracle_shade_packets failed: {rc}")
+    return out_u[:, :, 0].copy(), out_u[:, :, 1].copy(), out_f
+
+
+def dump_scene(world_desc, params, path):
+    """The scene blob oracle/shade_selftest.cpp reads: the bytes of rayn_world_desc, then of rayn_frame_params."""
+    with open(path, "wb") as f:
+        f.write(bytes(world_desc))
+        f.write(bytes(params))
 
 
 def sdf_dist(hitable, pts, fma=False):

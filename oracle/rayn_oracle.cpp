@@ -919,7 +919,9 @@ struct Integrator {
                 isect.ray.radiance += li * isect.ray.throughput * correction_factor * volume_transmission;
             }
         }
-        if (world.has_scatter) {
+        /* nl > 0: without a light the reference indexes an empty Vec here (world.lights[0], :252) and panics; the closed set defines that scene as "no volume
+         * NEE", like the surface branch above (k_shade_setup: do_vol; tests/restatement_np.py) - without the guard this was an out-of-bounds read */
+        if (world.has_scatter && nl > 0) {
             F4 rho_s(world.rho_s);
             for (size_t march = 0; march < volume_marches; march++) {
                 F4 lts = floor4(samples_1d[march + 1] * F4((float)nl));
@@ -990,6 +992,67 @@ struct TraceSink { /* optional per-depth packet dump for the packet-order tests 
     std::vector<uint32_t> depth, obj, px, py, sample, valid;
 };
 
+/* Optional record of every Integrator::integrate call of a tile (oracle_trace_shade), and the output form of oracle_shade_packets.
+ * Per packet: depth, hit object.  Per lane in: valid, sample, tcx, tcy | origin, dir, hit t, time, radiance, throughput, scramble (15 floats).
+ * Per lane out: status, flags (bit 0: Alpha + WorldNormal emitted) | radiance, throughput, origin, dir, WorldNormal sample (15 floats; what the
+ * status does not define is 0: a terminated lane has only its radiance = the Color / Background sample). */
+enum ShadeStatus : uint32_t { SH_INVALID = 0, SH_SPAWNED = 1, SH_COLOR = 2, SH_BACKGROUND = 3 };
+constexpr size_t SHADE_LANE_FLOATS = 15;
+struct ShadeSink {
+    std::vector<uint32_t> pk, lane_u, out_u; std::vector<float> lane_f, out_f;
+    size_t depth_first = 0; /* first packet of the depth being integrated */
+};
+inline void put3(float* f, V3 v) { f[0] = v.x; f[1] = v.y; f[2] = v.z; }
+void shade_lanes_in(const Ray r[4], const float t[4], uint32_t* lu, float* lf) {
+    for (int i = 0; i < 4; i++) {
+        lu[4 * i] = r[i].valid ? 1 : 0; lu[4 * i + 1] = (uint32_t)r[i].sample; lu[4 * i + 2] = r[i].tcx; lu[4 * i + 3] = r[i].tcy;
+        float* f = lf + SHADE_LANE_FLOATS * i;
+        put3(f, r[i].origin); put3(f + 3, r[i].dir); f[6] = t[i]; f[7] = r[i].time; put3(f + 8, r[i].radiance); put3(f + 11, r[i].throughput); f[14] = r[i].scramble;
+    }
+}
+/* Maps what one integrate call appended (spawned rays, channel samples) back to the packet's lanes.  A path is (tcx, tcy, sample), unique in a tile, so a
+ * spawned ray names its lane; the samples come in lane order (src/integrator.rs:161-203): Alpha + WorldNormal per valid lane, then one Color / Background
+ * per valid lane that did not spawn.  false = the call's output does not have that shape. */
+bool shade_lanes_out(const Ray in[4], const Ray* sp, size_t nsp, const ChannelSample* cs, size_t ncs, uint32_t* ou, float* of) {
+    for (size_t k = 0; k < 8; k++) ou[k] = 0;
+    for (size_t k = 0; k < 4 * SHADE_LANE_FLOATS; k++) of[k] = 0.0f;
+    size_t used = 0;
+    for (int i = 0; i < 4; i++) {
+        if (!in[i].valid) continue;
+        for (size_t j = 0; j < nsp; j++)
+            if (sp[j].tcx == in[i].tcx && sp[j].tcy == in[i].tcy && sp[j].sample == in[i].sample) {
+                float* f = of + SHADE_LANE_FLOATS * i;
+                ou[2 * i] = SH_SPAWNED; put3(f, sp[j].radiance); put3(f + 3, sp[j].throughput); put3(f + 6, sp[j].origin); put3(f + 9, sp[j].dir);
+                used++;
+                break;
+            }
+    }
+    if (used != nsp) return false;
+    int aov_lane = 0, term_lane = 0;
+    auto next = [&](int from, bool want_spawned_too) {
+        int i = from;
+        while (i < 4 && (!in[i].valid || (!want_spawned_too && ou[2 * i] == SH_SPAWNED))) i++;
+        return i;
+    };
+    for (size_t k = 0; k < ncs; k++) {
+        const ChannelSample& s = cs[k];
+        if (s.kind == S_ALPHA) {
+            if (k + 1 >= ncs || cs[k + 1].kind != S_NORMAL) return false;
+            int i = next(aov_lane, true);
+            if (i >= 4 || s.tcx != in[i].tcx || s.tcy != in[i].tcy) return false;
+            ou[2 * i + 1] |= 1u; put3(of + SHADE_LANE_FLOATS * i + 12, cs[k + 1].v);
+            aov_lane = i + 1; k++;
+        } else if (s.kind == S_COLOR || s.kind == S_BACKGROUND) {
+            int i = next(term_lane, false);
+            if (i >= 4 || s.tcx != in[i].tcx || s.tcy != in[i].tcy) return false;
+            ou[2 * i] = s.kind == S_COLOR ? SH_COLOR : SH_BACKGROUND; put3(of + SHADE_LANE_FLOATS * i, s.v);
+            term_lane = i + 1;
+        } else return false;
+    }
+    for (int i = 0; i < 4; i++) if (in[i].valid && ou[2 * i] == SH_INVALID) return false;
+    return true;
+}
+
 struct Tile {
     TileBounds b; uint32_t ew, eh;
     std::vector<V3> color, background, normal; std::vector<float> alpha; /* ChannelTileStorage, src/film.rs:42-61 */
@@ -1007,10 +1070,21 @@ struct Tile {
     }
 };
 
+/* the sample fetch of the tile closure, src/film.rs:568-584: s1[3 + VM], s2[12 + 8 * VM] of a packet at `depth` */
+inline void fetch_packet_samples(const Samples& sample_sets, const WRay& ray, size_t depth, size_t VM, F4* s1, F4* s2) {
+    const size_t n1 = 3 + VM, n2 = 12 + 8 * VM;
+    for (size_t set = 0; set < n1; set++)
+        s1[set] = sample_sets.wide_sample_1d_array(ray.sample, ray.scramble, 1 + set + depth * n1);
+    for (size_t i = 0; i < n2; i++) {
+        size_t dim = i % 2, set = i / 2;
+        s2[i] = sample_sets.wide_sample_2d_array(dim, ray.sample, ray.scramble, 2 + set + depth * n2 / 2);
+    }
+}
+
 /* the tile closure of render_frame_into, src/film.rs:439-627 */
 void integrate_tile(Tile& tile, const World& world, const Camera& camera, const Integrator& integrator,
                     const Samples& sample_sets, const float* fis, const float* scramble_buf,
-                    const rayn_frame_params& p, Counters* ctr, TraceSink* trace) {
+                    const rayn_frame_params& p, Counters* ctr, TraceSink* trace, ShadeSink* shade = nullptr, bool* shade_ok = nullptr) {
     const size_t VM = p.volume_marches;
     const size_t samples = p.samples;
     const uint32_t width = p.width;
@@ -1061,6 +1135,13 @@ void integrate_tile(Tile& tile, const World& world, const Camera& camera, const 
                 WHit wh; Ray rr[4] = {hits[k].ray, hits[k + 1].ray, hits[k + 2].ray, hits[k + 3].ray};
                 wh.ray = wray_from(rr); wh.t = F4(hits[k].t, hits[k + 1].t, hits[k + 2].t, hits[k + 3].t);
                 wintersections.push_back(world.hitables[obj_id]->get_shading_info(wh, half_pixel_size_at));
+                if (shade) {
+                    const size_t rec = shade->pk.size() / 2; /* this packet's record */
+                    shade->pk.push_back((uint32_t)depth); shade->pk.push_back((uint32_t)obj_id);
+                    shade->lane_u.resize(16 * (rec + 1)); shade->lane_f.resize(4 * SHADE_LANE_FLOATS * (rec + 1));
+                    shade->out_u.resize(8 * (rec + 1)); shade->out_f.resize(4 * SHADE_LANE_FLOATS * (rec + 1));
+                    shade_lanes_in(rr, wh.t.v, &shade->lane_u[16 * rec], &shade->lane_f[4 * SHADE_LANE_FLOATS * rec]);
+                }
                 if (trace)
                     for (int i = 0; i < 4; i++) {
                         trace->depth.push_back((uint32_t)depth); trace->obj.push_back((uint32_t)obj_id);
@@ -1072,16 +1153,19 @@ void integrate_tile(Tile& tile, const World& world, const Camera& camera, const 
 
         for (const ShadingInfo& si : wintersections) {
             F4 s1[3 + 4], s2[12 + 8 * 4]; /* [f32x4; 3+VM], [f32x4; 12+8*VM], VM <= 4 */
-            const size_t n1 = 3 + VM, n2 = 12 + 8 * VM;
-            for (size_t set = 0; set < n1; set++)
-                s1[set] = sample_sets.wide_sample_1d_array(si.sp.ray.sample, si.sp.ray.scramble, 1 + set + depth * n1);
-            for (size_t i = 0; i < n2; i++) {
-                size_t dim = i % 2, set = i / 2;
-                s2[i] = sample_sets.wide_sample_2d_array(dim, si.sp.ray.sample, si.sp.ray.scramble, 2 + set + depth * n2 / 2);
-            }
+            fetch_packet_samples(sample_sets, si.sp.ray, depth, VM, s1, s2);
+            const size_t sp0 = spawned_rays.size(), cs0 = new_samples.size();
             integrator.integrate(world, s1, s2, depth, si.material, si.sp, spawned_rays, new_samples);
             if (ctr) ctr->packets++;
+            if (shade) {
+                const size_t rec = shade->depth_first + (size_t)(&si - wintersections.data());
+                Ray in[4]; wray_into(si.sp.ray, in);
+                bool ok = shade_lanes_out(in, spawned_rays.data() + sp0, spawned_rays.size() - sp0, new_samples.data() + cs0, new_samples.size() - cs0,
+                                          &shade->out_u[8 * rec], &shade->out_f[4 * SHADE_LANE_FLOATS * rec]);
+                if (!ok && shade_ok) *shade_ok = false;
+            }
         }
+        if (shade) shade->depth_first = shade->pk.size() / 2;
         wintersections.clear();
 
         for (const ChannelSample& s : new_samples) tile.add_sample(s);
@@ -1282,6 +1366,66 @@ int64_t oracle_trace_tile(const rayn_world_desc* wd, const rayn_frame_params* p,
         depth[i] = sink.depth[i]; obj[i] = sink.obj[i]; px[i] = sink.px[i]; py[i] = sink.py[i]; sample[i] = sink.sample[i]; valid[i] = sink.valid[i];
     }
     return (int64_t)n;
+}
+
+/* Every Integrator::integrate call of ONE tile, rendered on the calling thread: its inputs and outputs per lane (ShadeSink), per depth in
+ * HitStore::process_hits order.  Returns the number of packets (the arrays hold the first `cap` of them), -1 for a bad tile index, -2 when a call's
+ * output could not be mapped back to its lanes. */
+int64_t oracle_trace_shade(const rayn_world_desc* wd, const rayn_frame_params* p, const float* s1d, const float* s2d,
+                           const float* scramble, const float* fis, uint32_t tile_index, uint64_t cap,
+                           uint32_t* pk, uint32_t* lane_u, float* lane_f, uint32_t* out_u, float* out_f) {
+    World world(*wd, cfg_of(*p));
+    Camera camera(wd->camera);
+    Integrator integ{p->max_bounces, p->volume_marches};
+    Samples sets{(size_t)p->samples * 4, s1d, s2d};
+    std::vector<TileBounds> tiles = build_tiles(p->width, p->height, p->tile_w, p->tile_h);
+    if (tile_index >= tiles.size()) return -1;
+    Tile tile(tiles[tile_index]); ShadeSink sink; bool ok = true;
+    integrate_tile(tile, world, camera, integ, sets, fis, scramble, *p, nullptr, nullptr, &sink, &ok);
+    if (!ok) return -2;
+    const uint64_t n = sink.pk.size() / 2, m = n < cap ? n : cap;
+    std::copy(sink.pk.begin(), sink.pk.begin() + 2 * m, pk);
+    std::copy(sink.lane_u.begin(), sink.lane_u.begin() + 16 * m, lane_u);
+    std::copy(sink.lane_f.begin(), sink.lane_f.begin() + 4 * SHADE_LANE_FLOATS * m, lane_f);
+    std::copy(sink.out_u.begin(), sink.out_u.begin() + 8 * m, out_u);
+    std::copy(sink.out_f.begin(), sink.out_f.begin() + 4 * SHADE_LANE_FLOATS * m, out_f);
+    return (int64_t)n;
+}
+
+/* get_shading_info + Integrator::integrate, as integrate_tile calls them, on caller-built packets of one depth: obj[n_packets]; lane_u / lane_f / out_u /
+ * out_f in the ShadeSink layout (tcx / tcy of lane_u are not read: lane i of a packet gets tcx = i, which maps its outputs back).  An invalid lane is
+ * Ray::new_invalid with hit t 0, as process_hits pads.  Returns 0, -1 for bad parameters, -2 for an object or sample out of range, -3 when the outputs
+ * of a call could not be mapped back. */
+int oracle_shade_packets(const rayn_world_desc* wd, const rayn_frame_params* p, const float* s1d, const float* s2d, uint32_t depth, uint64_t n_packets,
+                         const uint32_t* obj, const uint32_t* lane_u, const float* lane_f, uint32_t* out_u, float* out_f) {
+    if (!wd || !p || p->volume_marches < 2 || p->volume_marches > 4 || p->samples == 0) return -1;
+    World world(*wd, cfg_of(*p));
+    Camera camera(wd->camera);
+    Integrator integ{p->max_bounces, p->volume_marches};
+    Samples sets{(size_t)p->samples * 4, s1d, s2d};
+    ThresholdFn half_pixel_size_at;
+    if (depth == 0) half_pixel_size_at = [&camera](F4 t) { return camera.half_pixel_size_at(t); };
+    else { float k = 0.0001f * 2.0f * (float)depth; half_pixel_size_at = [k](F4 t) { return F4(k) * t; }; }
+    std::vector<Ray> spawned; std::vector<ChannelSample> samples;
+    for (uint64_t k = 0; k < n_packets; k++) {
+        if (obj[k] >= world.hitables.size()) return -2;
+        Ray rr[4]; float t[4];
+        for (int i = 0; i < 4; i++) {
+            const uint32_t* u = lane_u + 16 * k + 4 * i; const float* f = lane_f + SHADE_LANE_FLOATS * (4 * k + i);
+            if (!u[0]) { rr[i] = ray_new_invalid(); t[i] = 0.0f; continue; }
+            if (u[1] >= sets.samples) return -2;
+            rr[i] = Ray{f[7], V3{f[0], f[1], f[2]}, V3{f[3], f[4], f[5]}, V3{f[8], f[9], f[10]}, V3{f[11], f[12], f[13]}, (uint32_t)i, 0, true, f[14], u[1]};
+            t[i] = f[6];
+        }
+        WHit wh; wh.ray = wray_from(rr); wh.t = F4(t[0], t[1], t[2], t[3]);
+        ShadingInfo si = world.hitables[obj[k]]->get_shading_info(wh, half_pixel_size_at);
+        F4 s1[3 + 4], s2[12 + 8 * 4];
+        fetch_packet_samples(sets, si.sp.ray, depth, p->volume_marches, s1, s2);
+        spawned.clear(); samples.clear();
+        integ.integrate(world, s1, s2, depth, si.material, si.sp, spawned, samples);
+        if (!shade_lanes_out(rr, spawned.data(), spawned.size(), samples.data(), samples.size(), out_u + 8 * k, out_f + 4 * SHADE_LANE_FLOATS * k)) return -3;
+    }
+    return 0;
 }
 
 /* ---- known-answer helpers (single lane = lane 0 of a splatted packet) ---- */

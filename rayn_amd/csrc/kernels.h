@@ -98,6 +98,13 @@ struct ShadeHooks {
 constexpr uint32_t CHUNK = 256;
 constexpr uint32_t ENDGAME_ENTRIES = 256 * 32 * 64; // about one ray per resident lane of the chip
 
+// The sizes that decide how many grid-stride trips the streaming kernels of the shade stage make: the block cap of the light streaming grids (8 blocks of 256
+// threads per CU; k_shadow_list, k_shade_finish and the queue stages), the ids one thread of k_shadow_list scans per trip (a block scans 256 * SCAN_ITEMS)
+// and the block size of k_shade_setup, whose grid has no cap.  One definition for the kernels and for rayn_hip_probe_shade_limits.
+constexpr uint32_t STREAM_BLOCKS = 256 * 8;
+constexpr uint32_t SCAN_ITEMS = 64;
+constexpr uint32_t SHADE_SETUP_THREADS = 256;
+
 // launch tuning of the persistent march kernels
 struct Tuning {
     uint32_t persistent_blocks = 256 * 8; // 256 CUs x 8 blocks of 4 waves = 32 waves per CU
@@ -117,6 +124,14 @@ struct Tuning {
     uint32_t bulb_orbit_min = 24;         // the orbit phase of a round ends when at most this many lanes are still inside an orbit
     uint32_t bulb_prefetch_min = 32;      // free ray slots of a wave before the bulk queue fetch
 };
+
+// which shadow-march kernel launch_shadow_march launches for a scene (single_sdf: scene_march_kernels) under a tuning: one decision for the launcher and for
+// rayn_hip_probe_shade, which reports it
+enum ShadowMarchKernel { SHADOW_MARCH_GENERIC = 1 /* k_shadow */, SHADOW_MARCH_SINGLE = 2 /* k_shadow1 */, SHADOW_MARCH_BULB = 3 /* k_shadow_bulb */ };
+inline ShadowMarchKernel shadow_march_kernel(int single_sdf, const Tuning& tun) {
+    if (single_sdf >= 0 && tun.fast_path) return tun.bulb ? SHADOW_MARCH_BULB : SHADOW_MARCH_SINGLE;
+    return SHADOW_MARCH_GENERIC;
+}
 
 // sample tables: the reference layout (src/sampler.rs:11-15) + a per-(depth, sample) packed copy built at
 // frame start: record = [3+VM 1-D sets | pad to 8 | 12+8*VM 2-D components] of that depth, 16-byte aligned,

@@ -926,7 +926,6 @@ __global__ void __launch_bounds__(256, SETUP_WAVES) k_shade_setup(const DScene* 
 // thread = 16 K ids per atomic; (2) a uniform branch around every visibility load serialised them (load - wait - ballot, once
 // per group) - all loads of a trip are now issued before the first ballot.  Together: 16.5 -> 7.7 ms per 1/8 share of config 3
 // (3.5 TB/s); either one alone: 16.5 -> 15.5-16.2 ms.
-constexpr uint32_t SCAN_ITEMS = 64;
 __global__ void __launch_bounds__(256) k_shadow_list(Nee nee, uint32_t ns, DCtl* __restrict__ ctl) {
     __shared__ uint32_t s_wave[4];
     __shared__ uint32_t s_base;
@@ -1954,7 +1953,6 @@ static inline dim3 stride_grid(uint32_t max_items, uint32_t per_block, uint32_t 
     const uint32_t need = (max_items + per_block - 1) / per_block;
     return dim3(std::max<uint32_t>(1u, std::min<uint32_t>(need, cap_blocks)));
 }
-constexpr uint32_t STREAM_BLOCKS = 256 * 8; // light streaming kernels: 8 blocks of 256 threads per CU
 
 void launch_batch_setup(hipStream_t s, const DTile* tiles, uint32_t n_tiles, uint32_t* pgrp_tile, uint32_t* tgb, uint32_t* tgc) {
     hipLaunchKernelGGL(k_batch_setup, dim3(n_tiles), dim3(256), 0, s, tiles, pgrp_tile, tgb, tgc);
@@ -2001,7 +1999,8 @@ void launch_bin_scatter(hipStream_t s, uint32_t nclass, const uint32_t* q, const
 // the shadow-march kernel of the scene over the job list in nee / ctl (at most max_jobs entries): k_shade's second stage, and rayn_hip_probe_shadow
 void launch_shadow_march(hipStream_t s, bool count, const DScene* sc, Nee nee, uint32_t max_jobs, int single_sdf, DCtl* ctl, unsigned long long* evals, const Tuning& tun) {
     const dim3 grid = stride_grid(max_jobs, 256, tun.persistent_blocks);
-    if (single_sdf >= 0 && tun.fast_path && tun.bulb) {
+    const ShadowMarchKernel which = shadow_march_kernel(single_sdf, tun);
+    if (which == SHADOW_MARCH_BULB) {
 #define RAYN_SHADOW_BULB(C, KK, SS) hipLaunchKernelGGL((k_shadow_bulb<C, KK, SS>), grid, dim3(256), 0, s, sc, (uint32_t)single_sdf, nee, ctl, tun.bulb_orbit_min, tun.bulb_prefetch_min, evals + 2)
         if (count) { // the instrumented kernels run the SAME shape as the product ones (their stage-occupancy counters are quoted for it)
             if (tun.bulb_rays == 2) { if (tun.bulb_steps == 2) RAYN_SHADOW_BULB(true, 2, 2); else RAYN_SHADOW_BULB(true, 2, 1); }
@@ -2012,7 +2011,7 @@ void launch_shadow_march(hipStream_t s, bool count, const DScene* sc, Nee nee, u
         else if (tun.bulb_rays == 3) { if (tun.bulb_steps == 2) RAYN_SHADOW_BULB(false, 3, 2); else RAYN_SHADOW_BULB(false, 3, 1); }
         else { if (tun.bulb_steps == 2) RAYN_SHADOW_BULB(false, 4, 2); else RAYN_SHADOW_BULB(false, 4, 1); }
 #undef RAYN_SHADOW_BULB
-    } else if (single_sdf >= 0 && tun.fast_path) {
+    } else if (which == SHADOW_MARCH_SINGLE) {
 #define RAYN_SHADOW1(C, KIND) hipLaunchKernelGGL((k_shadow1<C, KIND>), grid, dim3(256), 0, s, sc, (uint32_t)single_sdf, nee, ctl, tun.prefetch_min_shadow, evals + 2)
         if (count) RAYN_SHADOW1(true, -1);
         else if (tun.sdf_kind == SDFK_MANDELBOX_12S) RAYN_SHADOW1(false, SDFK_MANDELBOX_12S);
@@ -2026,10 +2025,11 @@ void launch_shade(hipStream_t s, bool count, const DScene* sc, Tables tab, const
                   uint32_t max_slots, Pool pool, Nee nee, uint32_t ns, bool has_sdf, int single_sdf, unsigned long long* alive_mask, uint8_t* bgrp_cnt, DCtl* ctl,
                   unsigned long long* evals, ShadeHooks hooks, const Tuning& tun) {
     hooks.before(0);
+    static_assert(SHADE_SETUP_THREADS == 256, "k_shade_setup's launch bounds and its LDS memo are laid out for 256 threads");
     const uint32_t shmem = ns > 4 ? VOL_MEMO_LIGHTS * 3 * 256 * 4 : 0; // ns > 4: the volume scatters (volume NEE samples exist)
-    const dim3 sgrid = grid_for(max_slots, 256);
-    if (count) hipLaunchKernelGGL(k_shade_setup<true>, sgrid, dim3(256), shmem, s, sc, tab, scramble, depth, bq, ctl, pool, nee, alive_mask, bgrp_cnt, evals + 1);
-    else hipLaunchKernelGGL(k_shade_setup<false>, sgrid, dim3(256), shmem, s, sc, tab, scramble, depth, bq, ctl, pool, nee, alive_mask, bgrp_cnt, evals + 1);
+    const dim3 sgrid = grid_for(max_slots, SHADE_SETUP_THREADS);
+    if (count) hipLaunchKernelGGL(k_shade_setup<true>, sgrid, dim3(SHADE_SETUP_THREADS), shmem, s, sc, tab, scramble, depth, bq, ctl, pool, nee, alive_mask, bgrp_cnt, evals + 1);
+    else hipLaunchKernelGGL(k_shade_setup<false>, sgrid, dim3(SHADE_SETUP_THREADS), shmem, s, sc, tab, scramble, depth, bq, ctl, pool, nee, alive_mask, bgrp_cnt, evals + 1);
     hooks.after(0);
     if (has_sdf) {
         hooks.before(1);

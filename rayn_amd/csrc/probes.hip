@@ -303,6 +303,149 @@ int rayn_hip_probe_queue(rayn_ctx* ctx, uint32_t nclass, uint32_t n_tiles, const
     memcpy(ctl_io, fin, sizeof fin);
     return RAYN_OK;
 }
+// the sizes that decide the grid-stride trips of the shade stage's streaming kernels (kernels.h)
+int rayn_hip_probe_shade_limits(const rayn_ctx* ctx, uint32_t* stream_blocks, uint32_t* list_ids_per_block, uint32_t* setup_threads) {
+    if (!ctx || !stream_blocks || !list_ids_per_block || !setup_threads) return RAYN_ERR_INVALID_ARG;
+    *stream_blocks = STREAM_BLOCKS; *list_ids_per_block = 256 * SCAN_ITEMS; *setup_threads = SHADE_SETUP_THREADS;
+    return RAYN_OK;
+}
+// The shade stage of ONE depth through launch_shade (k_shade_setup, k_shadow_list, the scene's shadow-march kernel, k_shade_finish), launched with the
+// arguments of run_worker's depth loop, on a caller-built binned queue and pool.  The probe owns every device buffer: the pool, the NEE records, the
+// survivor ballots and the control block; what the kernels must not read before they write it starts as the worst stale value (header: rayn_hip.h).
+// Everything the kernels would index is checked here first, and so are their preconditions.
+int rayn_hip_probe_shade(rayn_ctx* ctx, const rayn_frame_params* p, const float* samples_1d, const float* samples_2d, const float* scramble, const float* fis_table,
+                         uint32_t depth, uint32_t n_slots, uint32_t max_slots, uint32_t nee_cap, const uint32_t* ref, uint32_t n_pool, const float* geo0,
+                         const float* geo1, const float* col0, const float* col1, uint32_t sentinel, float* out_geo0, float* out_geo1, float* out_col0,
+                         float* out_col1, float* out_aov, uint32_t* out_term_key, uint8_t* out_term_info, uint64_t* out_alive_mask, uint8_t* out_bgrp_cnt,
+                         uint64_t* out_jobs) {
+    int rc = validate(ctx, p);
+    if (rc) return rc;
+    if (!samples_1d || !samples_2d || !scramble || !fis_table || !ref || !geo0 || !geo1 || !col0 || !col1 || !out_geo0 || !out_geo1 || !out_col0 || !out_col1 ||
+        !out_aov || !out_term_key || !out_term_info || !out_alive_mask || !out_bgrp_cnt || !out_jobs)
+        return fail(ctx, RAYN_ERR_INVALID_ARG, "null buffer");
+    if (n_slots == 0 || n_slots % 64) return fail(ctx, RAYN_ERR_INVALID_ARG, "n_slots is 0 or not a multiple of 64 (the kernels work on whole 64-slot groups)");
+    if (max_slots < n_slots || nee_cap < n_slots) return fail(ctx, RAYN_ERR_INVALID_ARG, "max_slots or nee_cap below n_slots");
+    if (depth > p->max_bounces) return fail(ctx, RAYN_ERR_INVALID_ARG, "depth above max_bounces (the packed sample records end there)");
+    if (n_pool == 0 || n_pool > (1u << 27) || max_slots > (1u << 27)) return fail(ctx, RAYN_ERR_INVALID_ARG, "probe size out of range");
+    const rayn_world_desc& w = ctx->cfg->world;
+    const uint32_t NS = 4 + (w.has_scattering ? 4 * p->volume_marches : 0); // NEE samples per shading point, as render_device counts them
+    // 32-bit [sample][slot] ids, and k_shadow_list's grid-stride counter must not wrap (run_worker's check, on the probe's strides)
+    const uint64_t id_limit = ((uint64_t)1 << 32) - ((uint64_t)1 << 26);
+    if ((uint64_t)NS * nee_cap > id_limit || (uint64_t)NS * max_slots > id_limit)
+        return fail(ctx, RAYN_ERR_INVALID_ARG, "ns * nee_cap or ns * max_slots does not fit the 32-bit [sample][slot] ids");
+    const uint32_t spp = p->samples * 4;
+    const uint64_t n_pixels = (uint64_t)p->width * p->height;
+    {
+        std::vector<uint8_t> named(n_pool, 0);
+        for (uint32_t k = 0; k < n_slots; k += 4) {
+            uint32_t obj0 = 0;
+            bool any = false;
+            for (uint32_t i = 0; i < 4; i++) {
+                const uint32_t P = ref[k + i];
+                if (P == INVALID) continue;
+                if (P >= n_pool) return fail(ctx, RAYN_ERR_INVALID_ARG, "a ref that is neither 0xFFFFFFFF nor below n_pool");
+                if (named[P]) return fail(ctx, RAYN_ERR_INVALID_ARG, "a pool slot is referenced twice");
+                named[P] = 1;
+                uint32_t ow, pix;
+                memcpy(&ow, &geo1[4 * (size_t)P + 3], 4); memcpy(&pix, &col1[4 * (size_t)P + 2], 4);
+                const uint32_t obj = ow & 0xFFu;
+                if (obj >= w.n_hitables) return fail(ctx, RAYN_ERR_INVALID_ARG, "an object at or beyond n_hitables");
+                if ((ow >> 8) >= spp) return fail(ctx, RAYN_ERR_INVALID_ARG, "a sample index at or beyond 4 * samples");
+                if (pix >= n_pixels) return fail(ctx, RAYN_ERR_INVALID_ARG, "a pixel index at or beyond width * height");
+                if (!any && i != 0) return fail(ctx, RAYN_ERR_INVALID_ARG, "lane 0 of a packet is invalid while a later lane is not (lane 0 of a bin packet is always a real hit)");
+                if (any && obj != obj0) return fail(ctx, RAYN_ERR_INVALID_ARG, "the valid lanes of a packet name different objects");
+                any = true; obj0 = obj;
+            }
+        }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    DScene hs;
+    rc = build_scene(ctx, w, *p, &hs);
+    if (rc) return rc;
+    Tuning tun;
+    const int single_sdf = scene_march_kernels(ctx, hs, *p, &tun);
+    const KernelSet K = kernel_set(ctx->cfg->fma_policy);
+    const size_t n1 = (size_t)spp * rayn_sets_1d(p->max_bounces, p->volume_marches), n2 = (size_t)spp * 2 * rayn_sets_2d(p->max_bounces, p->volume_marches);
+    const uint32_t rec_stride = (8 + hs.n2) / 4, rec_depths = p->max_bounces + 1;
+    const size_t rec_n = (size_t)rec_depths * spp * rec_stride;
+    const size_t CAP = nee_cap, JOBCAP = (size_t)NS * CAP, NV = NS - 4 + 1, G = n_slots / 64, NP = n_pool;
+    DevBuf d_s1, d_s2, d_scr, d_fis, d_rec, d_bq, d_g0, d_g1, d_c0, d_c1, d_aov, d_key, d_info, d_alive, d_cnt, d_ctl, d_ev;
+    DevBuf d_x, d_vtr, d_pdf, d_aux, d_vis, d_picks, d_T, d_t0, d_nthr, d_flags, d_jref, d_jgeo;
+#define OOMCHK(expr) do { if ((expr) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAYN_ERR_OOM, "hipMalloc of the shade probe's buffers failed"); } } while (0)
+    OOMCHK(d_s1.alloc(n1 * 4)); OOMCHK(d_s2.alloc(n2 * 4)); OOMCHK(d_scr.alloc(n_pixels * 4)); OOMCHK(d_fis.alloc(RAYN_FIS_TABLE_SIZE * 4)); OOMCHK(d_rec.alloc(rec_n * 16));
+    OOMCHK(d_bq.alloc((size_t)n_slots * 4)); OOMCHK(d_g0.alloc(NP * 16)); OOMCHK(d_g1.alloc(NP * 16)); OOMCHK(d_c0.alloc(NP * 16)); OOMCHK(d_c1.alloc(NP * 16));
+    OOMCHK(d_aov.alloc(NP * 16)); OOMCHK(d_key.alloc(NP * 4)); OOMCHK(d_info.alloc(NP)); OOMCHK(d_alive.alloc(G * 8)); OOMCHK(d_cnt.alloc(G));
+    OOMCHK(d_ctl.alloc(sizeof(DCtl))); OOMCHK(d_ev.alloc(128));
+    OOMCHK(d_x.alloc(12 * CAP * 4)); OOMCHK(d_vtr.alloc(NV * CAP * 4)); OOMCHK(d_pdf.alloc(NS * CAP * 4)); OOMCHK(d_aux.alloc(NV * CAP * 4)); OOMCHK(d_vis.alloc(NS * CAP));
+    OOMCHK(d_picks.alloc(CAP * 8)); OOMCHK(d_T.alloc(CAP * 4)); OOMCHK(d_t0.alloc(CAP * 4)); OOMCHK(d_nthr.alloc(3 * CAP * 4)); OOMCHK(d_flags.alloc(CAP));
+    OOMCHK(d_jref.alloc(JOBCAP * 4)); OOMCHK(d_jgeo.alloc(3 * JOBCAP * 8));
+#undef OOMCHK
+    // the float planes of the NEE records, in the order the guard below walks them
+    struct Plane { DevBuf* b; size_t planes; } fplanes[] = {{&d_x, 12}, {&d_vtr, NV}, {&d_pdf, NS}, {&d_aux, NV}, {&d_T, 1}, {&d_t0, 1}, {&d_nthr, 3}};
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpy(d_s1.p, samples_1d, n1 * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_s2.p, samples_2d, n2 * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_scr.p, scramble, n_pixels * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_fis.p, fis_table, RAYN_FIS_TABLE_SIZE * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_bq.p, ref, (size_t)n_slots * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_g0.p, geo0, NP * 16, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_g1.p, geo1, NP * 16, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_c0.p, col0, NP * 16, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_c1.p, col1, NP * 16, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetD32((hipDeviceptr_t)d_aov.p, (int)sentinel, NP * 4)); HIPCHK(hipMemsetD32((hipDeviceptr_t)d_key.p, (int)sentinel, NP));
+    HIPCHK(hipMemset(d_info.p, (int)TERM_NONE, NP));
+    for (const Plane& pl : fplanes) HIPCHK(hipMemsetD32((hipDeviceptr_t)pl.b->p, (int)sentinel, pl.planes * CAP));
+    HIPCHK(hipMemset(d_vis.p, 2, NS * CAP)); // "march pending" everywhere: a (sample, slot) the setup forgets becomes a job and an occluded sample
+    HIPCHK(hipMemset(d_picks.p, 0xFF, CAP * 8)); HIPCHK(hipMemset(d_flags.p, 0xFF, CAP));
+    HIPCHK(hipMemset(d_jref.p, 0xFF, JOBCAP * 4)); HIPCHK(hipMemset(d_jgeo.p, 0, 3 * JOBCAP * 8));
+    HIPCHK(hipMemset(d_alive.p, 0xA5, G * 8)); HIPCHK(hipMemset(d_cnt.p, 0xA5, G)); HIPCHK(hipMemset(d_ev.p, 0, 128));
+    DCtl hc;
+    memset(&hc, 0, sizeof hc);
+    hc.b_groups = (uint32_t)G;
+    for (uint32_t k = 0; k < n_slots; k++) hc.b_valid += ref[k] != INVALID;
+    HIPCHK(hipMemcpy(d_ctl.p, &hc, sizeof hc, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->d_scene, &hs, sizeof hs, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize()); // the fills above ran on the null stream
+    const Tables tab{d_s1.as<float>(), d_s2.as<float>(), d_fis.as<float>(), d_rec.as<float4>(), rec_stride};
+    K.pack_tables(s, tab, d_rec.as<float4>(), spp, rec_depths, hs.n1, hs.n2);
+    Pool pool;
+    pool.geo0 = d_g0.as<float4>(); pool.geo1 = d_g1.as<float4>(); pool.col0 = d_c0.as<float4>(); pool.col1 = d_c1.as<float4>(); pool.aov = d_aov.as<float4>();
+    pool.term_key = d_key.as<uint32_t>(); pool.term_info = d_info.as<uint8_t>();
+    Nee nee;
+    nee.x = d_x.as<float>(); nee.vtr = d_vtr.as<float>(); nee.pdf = d_pdf.as<float>(); nee.aux = d_aux.as<float>(); nee.vis = d_vis.as<uint8_t>();
+    nee.vpicks = d_picks.as<unsigned long long>(); nee.T = d_T.as<float>(); nee.t0 = d_t0.as<float>(); nee.nthr = d_nthr.as<float>(); nee.flags = d_flags.as<uint8_t>();
+    nee.cap = CAP; nee.job_ref = d_jref.as<uint32_t>(); nee.job_geo = d_jgeo.as<float2>(); nee.jobcap = JOBCAP;
+    K.shade(s, false, ctx->d_scene, tab, d_scr.as<float>(), depth, d_bq.as<uint32_t>(), max_slots, pool, nee, NS, hs.n_sdf > 0, single_sdf,
+            d_alive.as<unsigned long long>(), d_cnt.as<uint8_t>(), d_ctl.as<DCtl>(), d_ev.as<unsigned long long>(), ShadeHooks{nullptr, nullptr, nullptr}, tun);
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(&hc, d_ctl.p, sizeof hc, hipMemcpyDeviceToHost));
+    if ((uint64_t)hc.job_count > (uint64_t)NS * n_slots) return fail(ctx, RAYN_ERR_HIP, "internal: job_count exceeds ns * n_slots");
+    if (CAP > n_slots) { // the surplus of every NEE plane: no word at a slot index in [n_slots, nee_cap) may have changed
+        const size_t extra = CAP - n_slots;
+        std::vector<uint32_t> words(extra);
+        std::vector<uint8_t> bytes(extra);
+        for (const Plane& pl : fplanes)
+            for (size_t k = 0; k < pl.planes; k++) {
+                HIPCHK(hipMemcpy(words.data(), (const uint32_t*)pl.b->p + k * CAP + n_slots, extra * 4, hipMemcpyDeviceToHost));
+                for (uint32_t v : words) if (v != sentinel) return fail(ctx, RAYN_ERR_HIP, "internal: a float plane of the NEE records was written at a slot index in [n_slots, nee_cap)");
+            }
+        for (size_t k = 0; k < NS; k++) {
+            HIPCHK(hipMemcpy(bytes.data(), (const uint8_t*)d_vis.p + k * CAP + n_slots, extra, hipMemcpyDeviceToHost));
+            for (uint8_t v : bytes) if (v != 2) return fail(ctx, RAYN_ERR_HIP, "internal: the visibility plane was written at a slot index in [n_slots, nee_cap)");
+        }
+        HIPCHK(hipMemcpy(bytes.data(), (const uint8_t*)d_flags.p + n_slots, extra, hipMemcpyDeviceToHost));
+        for (uint8_t v : bytes) if (v != 0xFF) return fail(ctx, RAYN_ERR_HIP, "internal: the flag plane was written at a slot index in [n_slots, nee_cap)");
+        std::vector<unsigned long long> picks(extra);
+        HIPCHK(hipMemcpy(picks.data(), (const unsigned long long*)d_picks.p + n_slots, extra * 8, hipMemcpyDeviceToHost));
+        for (unsigned long long v : picks) if (v != ~0ull) return fail(ctx, RAYN_ERR_HIP, "internal: the volume picks were written at a slot index in [n_slots, nee_cap)");
+    }
+    HIPCHK(hipMemcpy(out_geo0, d_g0.p, NP * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_geo1, d_g1.p, NP * 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_col0, d_c0.p, NP * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_col1, d_c1.p, NP * 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_aov, d_aov.p, NP * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_term_key, d_key.p, NP * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_term_info, d_info.p, NP, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_alive_mask, d_alive.p, G * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_bgrp_cnt, d_cnt.p, G, hipMemcpyDeviceToHost));
+    out_jobs[0] = hc.job_count; out_jobs[1] = hc.shadow_jobs;
+    // the shadow-march kernel launch_shadow_march launched, by the decision it shares with this probe (kernels.h); 0: launch_shade skips the march without a TracedSDF
+    out_jobs[2] = hs.n_sdf == 0 ? 0 : (uint64_t)shadow_march_kernel(single_sdf, tun);
+    return RAYN_OK;
+}
 // The film resolve on caller-built tiles and termination records, through launch_resolve (so the variant is the product's choice for spp).  The resolve
 // reads spp and width of the scene and term_info / term_key / col0 / aov of the pool; everything else of both stays zero / null.  The four planes start
 // filled with `sentinel`.  Everything the kernels would index is checked here first, and so are their preconditions (rayn_hip.h lists them).

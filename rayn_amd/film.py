@@ -581,6 +581,36 @@ class Context:
         return {"color": out["color"].reshape(h, w, 3), "alpha": out["alpha"].reshape(h, w),
                 "background": out["background"].reshape(h, w, 3), "normal": out["normal"].reshape(h, w, 3)}
 
+    def probe_shade_limits(self):
+        """(stream_blocks, list_ids_per_block, setup_threads): rayn_hip_probe_shade_limits."""
+        v = [C.c_uint32() for _ in range(3)]
+        self._chk(self._L.rayn_hip_probe_shade_limits(self.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def probe_shade(self, params, tables, depth, ref, geo0, geo1, col0, col1, max_slots=None, nee_cap=None, sentinel=0xC0FFEE5A, check=True):
+        """rayn_hip_probe_shade (rayn_hip.h): the shade stage of one depth on a binned queue `ref` [n_slots] and the pool records geo0 / geo1 / col0 / col1
+        [n_pool, 4] float32 in the pool's own encoding.  -> (rc, dict): the pool as the stage left it (geo0, geo1, col0, col1, aov [n_pool, 4], term_key, term_info
+        [n_pool]), alive_mask / bgrp_cnt [n_slots / 64], job_count, shadow_jobs, shadow_kernel.  check=False returns a non-zero rc instead of raising."""
+        s1, s2, scr, fis = tables
+        ref = np.ascontiguousarray(ref, np.uint32)
+        recs = [np.ascontiguousarray(a, np.float32).reshape(-1, 4) for a in (geo0, geo1, col0, col1)]
+        n_slots, n_pool = ref.size, recs[0].shape[0]
+        assert all(a.shape[0] == n_pool for a in recs)
+        out = {k: np.zeros((n_pool, 4), np.float32) for k in ("geo0", "geo1", "col0", "col1", "aov")}
+        out["term_key"], out["term_info"] = np.zeros(n_pool, np.uint32), np.zeros(n_pool, np.uint8)
+        groups = max(n_slots // 64, 1)
+        out["alive_mask"], out["bgrp_cnt"] = np.zeros(groups, np.uint64), np.zeros(groups, np.uint8)
+        jobs = np.zeros(3, np.uint64)
+        up, bp, qp = (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64)))
+        rc = self._L.rayn_hip_probe_shade(self.h, C.byref(params), _fp(s1), _fp(s2), _fp(scr), _fp(fis), depth, n_slots, n_slots if max_slots is None else max_slots,
+                                          n_slots if nee_cap is None else nee_cap, up(ref), n_pool, *[_fp(a) for a in recs], sentinel,
+                                          *[_fp(out[k]) for k in ("geo0", "geo1", "col0", "col1", "aov")], up(out["term_key"]), bp(out["term_info"]),
+                                          qp(out["alive_mask"]), bp(out["bgrp_cnt"]), qp(jobs))
+        if check:
+            self._chk(rc)
+        out["job_count"], out["shadow_jobs"], out["shadow_kernel"] = int(jobs[0]), int(jobs[1]), ("none", "k_shadow", "k_shadow1", "k_shadow_bulb")[int(jobs[2])]
+        return rc, out
+
     def render_device(self, params, d_tables, d_out, stream=None):
         """rayn_hip_render_frame_device: d_tables/d_out are torch CUDA tensors (kept resident in HBM)."""
         import torch
