@@ -22,16 +22,14 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "../../include/rayn_detmath_fast.h"
-#include "../../include/rayn_hip.h"
 #include "denoise.h"
+#include "post_checks.h"
+#include "post_device.h"
 
 namespace rayn {
 namespace {
 
 constexpr uint32_t TERM_COLOR = 1u, TERM_NORMAL = 2u, TERM_ALPHA = 4u;
-
-__device__ inline bool finite3(float4 v) { return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z); }
 
 // One thread per pixel: planar colour (3 floats), alpha (1) and normal (3) -> ca[p] = (r, g, b, alpha), nrm[p] = (nx, ny, nz, 0).
 // A guide that is switched off is not read (its pointer may be null): alpha 0, no normal record.  n < 2^31.
@@ -57,7 +55,7 @@ __global__ void __launch_bounds__(256) k_atrous(uint32_t width, uint32_t height,
     const uint32_t p = x + y * width; // < 2^31
     const float4 cp = ca[p];
     float r = cp.x, g = cp.y, b = cp.z;
-    if (finite3(cp)) {
+    if (finite3(cp.x, cp.y, cp.z)) {
         // kc 4^i: 4^i = step^2 <= 2^14 is exact in f32, and sigma in [2^-30, 2^30] keeps the product finite
         const float kc = (TERMS & TERM_COLOR) ? (1.0f / (sigma_color * sigma_color)) * (float)(step * step) : 0.0f;
         const float kn = (TERMS & TERM_NORMAL) ? 1.0f / (sigma_normal * sigma_normal) : 0.0f;
@@ -77,7 +75,7 @@ __global__ void __launch_bounds__(256) k_atrous(uint32_t width, uint32_t height,
                 if (qx >= width) continue;
                 const uint32_t q = qx + qy * width;
                 const float4 cq = ca[q];
-                if (!finite3(cq)) continue;
+                if (!finite3(cq.x, cq.y, cq.z)) continue;
                 float e = 0.0f; // 0 + t == t for every term t (t >= +0, inf or NaN): the same bits as the definition's sum
                 if (TERMS & TERM_COLOR) {
                     const float dr = r - cq.x, dg = g - cq.y, db = b - cq.z;
@@ -124,29 +122,19 @@ void launch_pass(hipStream_t s, bool last, dim3 grid, uint32_t width, uint32_t h
         hipLaunchKernelGGL((k_atrous<TERMS, false>), grid, block, 0, s, width, height, tiles_x, step, sc, sn, sa, ca, nrm, ca_out, out_color);
 }
 
-// 0 = off; else finite and in [2^-30, 2^30]
-bool sigma_ok(float sigma) { return sigma == 0.0f || (sigma >= 0x1p-30f && sigma <= 0x1p30f); }
-
 } // namespace
 
 size_t denoise_scratch_bytes(uint32_t width, uint32_t height) {
-    const uint64_t n = (uint64_t)width * height;
-    if (!n || n >= ((uint64_t)1 << 31)) return 0;
-    return (size_t)(3u * sizeof(float4) * n);
+    return atrous_scratch_bytes(width, height);
 }
 
 const char* denoise_check_args(uint32_t width, uint32_t height, uint32_t iterations, float sigma_color, float sigma_normal, float sigma_alpha,
                                const float* color, const float* alpha, const float* normal, const float* out_color, const void* scratch,
                                size_t scratch_bytes) {
-    if (!width || !height) return "zero-sized image";
-    if ((uint64_t)width * height >= ((uint64_t)1 << 31)) return "image larger than 2^31 pixels unsupported (32-bit pixel indices)";
-    if (iterations < 1 || iterations > 8) return "iterations must be in 1..8";
-    if (!sigma_ok(sigma_color)) return "sigma_color must be 0 (off) or in [2^-30, 2^30]";
-    if (!sigma_ok(sigma_normal)) return "sigma_normal must be 0 (off) or in [2^-30, 2^30]";
-    if (!sigma_ok(sigma_alpha)) return "sigma_alpha must be 0 (off) or in [2^-30, 2^30]";
-    if (!color || !out_color || !scratch) return "null buffer";
-    if (!normal && sigma_normal != 0.0f) return "null normal guide with sigma_normal != 0";
-    if (!alpha && sigma_alpha != 0.0f) return "null alpha guide with sigma_alpha != 0";
+    if (const char* why = check_size(width, height)) return why;
+    if (const char* why = check_atrous_params(iterations, sigma_color, "sigma_color must be 0 (off) or in [2^-30, 2^30]", sigma_normal, sigma_alpha,
+                                              color && out_color && scratch, normal, alpha))
+        return why;
     if (scratch_bytes < denoise_scratch_bytes(width, height)) return "scratch smaller than rayn_denoise_scratch_bytes(width, height)";
     if ((uintptr_t)scratch % 16u) return "scratch not 16-byte aligned";
     if (out_color == color) return "d_out_color must not be d_color";
@@ -168,16 +156,9 @@ void launch_denoise(hipStream_t s, uint32_t width, uint32_t height, uint32_t ite
         const float4* in = plane[i & 1u];
         float4* out = plane[(i + 1u) & 1u];
         const uint32_t step = 1u << i;
-        switch (terms) {
-        case 0: launch_pass<0>(s, last, grid, width, height, tiles_x, step, sigma_color, sigma_normal, sigma_alpha, in, nrm, out, out_color); break;
-        case 1: launch_pass<1>(s, last, grid, width, height, tiles_x, step, sigma_color, sigma_normal, sigma_alpha, in, nrm, out, out_color); break;
-        case 2: launch_pass<2>(s, last, grid, width, height, tiles_x, step, sigma_color, sigma_normal, sigma_alpha, in, nrm, out, out_color); break;
-        case 3: launch_pass<3>(s, last, grid, width, height, tiles_x, step, sigma_color, sigma_normal, sigma_alpha, in, nrm, out, out_color); break;
-        case 4: launch_pass<4>(s, last, grid, width, height, tiles_x, step, sigma_color, sigma_normal, sigma_alpha, in, nrm, out, out_color); break;
-        case 5: launch_pass<5>(s, last, grid, width, height, tiles_x, step, sigma_color, sigma_normal, sigma_alpha, in, nrm, out, out_color); break;
-        case 6: launch_pass<6>(s, last, grid, width, height, tiles_x, step, sigma_color, sigma_normal, sigma_alpha, in, nrm, out, out_color); break;
-        default: launch_pass<7>(s, last, grid, width, height, tiles_x, step, sigma_color, sigma_normal, sigma_alpha, in, nrm, out, out_color); break;
-        }
+        with_terms<3>(terms, [&](auto T) {
+            launch_pass<decltype(T)::value>(s, last, grid, width, height, tiles_x, step, sigma_color, sigma_normal, sigma_alpha, in, nrm, out, out_color);
+        });
     }
 }
 

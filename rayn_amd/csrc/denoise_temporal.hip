@@ -22,22 +22,18 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "../../include/rayn_hip.h"
 #include "denoise_variance.h"
+#include "post_checks.h"
+#include "post_device.h"
 #include "temporal.h"
 
 namespace rayn {
 namespace {
 
-constexpr uint32_t MISS_OBJECT = 0xFFFFFFFFu;
 constexpr int HALO = 3, TILE = 16, SPAN = TILE + 2 * HALO; // 22
 
-__device__ inline bool finite3(float r, float g, float b) { return __builtin_isfinite(r) && __builtin_isfinite(g) && __builtin_isfinite(b); }
-__device__ inline float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-__device__ inline float quiet_nan() { return __uint_as_float(0x7FC00000u); }
-
 // hA: plane A of the history, (r, g, b, n'); only n' is read - the colour is the caller's planar one.  a / b as k_vdenoise_pack writes
-// them; a guide that is switched off is not read (its pointer may be null), b is null when both are off.  width * height < 2^31.
+// them (b by the same write_guide_record); a guide that is switched off is not read (its pointer may be null), b is null when both are off.  width * height < 2^31.
 __global__ void __launch_bounds__(256) k_tvdenoise_pack(uint32_t width, uint32_t height, uint32_t blocks_x, const float* __restrict__ color,
                                                         const float* __restrict__ alpha, const float* __restrict__ normal,
                                                         const uint32_t* __restrict__ gobj, const float4* __restrict__ hA,
@@ -108,16 +104,7 @@ __global__ void __launch_bounds__(256) k_tvdenoise_pack(uint32_t width, uint32_t
     if (!inside) return;
     if (!__builtin_isfinite(v)) v = quiet_nan();
     a[p] = make_float4(cr, cg, cb, v);
-    if (b) {
-        float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-        if (normal) { nx = normal[f]; ny = normal[f + 1]; nz = normal[f + 2]; }
-        b[p] = make_float4(nx, ny, nz, alpha ? alpha[p] : 0.0f);
-    }
-}
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + nb && y < x + na;
+    write_guide_record(b, p, f, normal, alpha);
 }
 
 } // namespace
@@ -126,15 +113,10 @@ const char* denoise_temporal_check_args(uint32_t width, uint32_t height, uint32_
                                         float sigma_alpha, const float* color, const float* alpha, const float* normal, const uint32_t* g_object,
                                         const void* history, size_t history_bytes, const void* moments, size_t moments_bytes,
                                         const float* out_color, const float* out_variance, const void* scratch, size_t scratch_bytes) {
-    if (!width || !height) return "zero-sized image";
-    if ((uint64_t)width * height >= ((uint64_t)1 << 31)) return "image larger than 2^31 pixels unsupported (32-bit pixel indices)";
-    if (iterations < 1 || iterations > 8) return "iterations must be in 1..8";
-    if (!vatrous_sigma_ok(sigma_luminance)) return "sigma_luminance must be 0 (off) or in [2^-30, 2^30]";
-    if (!vatrous_sigma_ok(sigma_normal)) return "sigma_normal must be 0 (off) or in [2^-30, 2^30]";
-    if (!vatrous_sigma_ok(sigma_alpha)) return "sigma_alpha must be 0 (off) or in [2^-30, 2^30]";
-    if (!color || !g_object || !history || !moments || !out_color || !scratch) return "null buffer";
-    if (!normal && sigma_normal != 0.0f) return "null normal guide with sigma_normal != 0";
-    if (!alpha && sigma_alpha != 0.0f) return "null alpha guide with sigma_alpha != 0";
+    if (const char* why = check_size(width, height)) return why;
+    if (const char* why = check_atrous_params(iterations, sigma_luminance, "sigma_luminance must be 0 (off) or in [2^-30, 2^30]", sigma_normal, sigma_alpha,
+                                              color && g_object && history && moments && out_color && scratch, normal, alpha))
+        return why;
     const size_t n = (size_t)width * height, hist = temporal_history_bytes(width, height), mom = temporal_moments_bytes(width, height);
     if (history_bytes < hist) return "history smaller than rayn_temporal_history_bytes(width, height)";
     if (moments_bytes < mom) return "moments smaller than rayn_temporal_moments_bytes(width, height)";
@@ -143,12 +125,10 @@ const char* denoise_temporal_check_args(uint32_t width, uint32_t height, uint32_
     if ((uintptr_t)history % 16u) return "history not 16-byte aligned";
     if ((uintptr_t)moments % 16u) return "moments not 16-byte aligned";
     if ((uintptr_t)g_object % 4u) return "d_gbuffer_object not 4-byte aligned";
-    const void* in[6] = {color, alpha, normal, g_object, history, moments};
-    const size_t in_bytes[6] = {12u * n, 4u * n, 12u * n, 4u * n, hist, mom};
-    for (int i = 0; i < 6; i++) {
-        if (overlap(out_color, 12u * n, in[i], in_bytes[i]) || overlap(out_variance, 4u * n, in[i], in_bytes[i])) return "an output must not alias an input";
-        if (overlap(scratch, scratch_bytes, in[i], in_bytes[i])) return "the scratch must not alias an input";
-    }
+    const Span in[6] = {{color, 12u * n}, {alpha, 4u * n}, {normal, 12u * n}, {g_object, 4u * n}, {history, hist}, {moments, mom}};
+    const Span work[3] = {{out_color, 12u * n}, {out_variance, 4u * n}, {scratch, scratch_bytes}};
+    int j;
+    if (first_overlap(in, 6, work, 3, nullptr, &j)) return j < 2 ? "an output must not alias an input" : "the scratch must not alias an input";
     if (overlap(out_variance, 4u * n, out_color, 12u * n)) return "d_out_variance must not alias d_out_color";
     if (overlap(scratch, scratch_bytes, out_color, 12u * n) || overlap(scratch, scratch_bytes, out_variance, 4u * n)) return "the scratch must not alias an output";
     return nullptr;
@@ -185,10 +165,9 @@ const char* denoise_temporal_feedback_check_args(uint32_t width, uint32_t height
     if (!(feedback >= 0.0f && feedback <= 1.0f)) return "feedback must be finite and in [0, 1]";
     // the history is an output here: the checks above keep it off the outputs and the scratch; these keep it off the other inputs
     const size_t n = (size_t)width * height, hist = temporal_history_bytes(width, height);
-    const void* in[5] = {color, alpha, normal, g_object, moments};
-    const size_t in_bytes[5] = {12u * n, 4u * n, 12u * n, 4u * n, temporal_moments_bytes(width, height)};
-    for (int i = 0; i < 5; i++)
-        if (overlap(history, hist, in[i], in_bytes[i])) return "the history must not alias an input";
+    const Span in[5] = {{color, 12u * n}, {alpha, 4u * n}, {normal, 12u * n}, {g_object, 4u * n}, {moments, temporal_moments_bytes(width, height)}};
+    const Span hs = {history, hist};
+    if (first_overlap(&hs, 1, in, 5)) return "the history must not alias an input";
     return nullptr;
 }
 

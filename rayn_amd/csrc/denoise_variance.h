@@ -34,7 +34,6 @@ inline uint32_t vatrous_terms(float sigma_luminance, float sigma_normal, float s
 inline float4* vatrous_guides(uint32_t terms, uint32_t width, uint32_t height, void* scratch) {
     return (terms & (VATROUS_NORMAL | VATROUS_ALPHA)) ? (float4*)scratch + 2u * ((size_t)width * height) : nullptr;
 }
-bool vatrous_sigma_ok(float sigma);
 // Enqueue the `iterations` passes on records a pack kernel has written: A = (r, g, b, v or NaN) in plane 0 of the scratch, B = (nx, ny,
 // nz, alpha) in vatrous_guides.  The last pass writes out_color and, when given, out_variance.  With `history` (a temporal history, plane A
 // first) and feedback != 0, pass 0 also blends its colour into plane A's (r, g, b) with that strength; the outputs do not depend on it.

@@ -31,9 +31,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "../../include/rayn_detmath_fast.h"
-#include "../../include/rayn_hip.h"
 #include "denoise_variance.h"
+#include "post_checks.h"
+#include "post_device.h"
 #include "progressive.h"
 
 namespace rayn {
@@ -42,10 +42,6 @@ namespace {
 constexpr uint32_t TERM_LUMINANCE = VATROUS_LUMINANCE, TERM_NORMAL = VATROUS_NORMAL, TERM_ALPHA = VATROUS_ALPHA;
 
 struct VarGeom { uint32_t width, height, tile_w, tile_h, tiles_x, tiles_y; };
-
-__device__ inline bool finite3(float r, float g, float b) { return __builtin_isfinite(r) && __builtin_isfinite(g) && __builtin_isfinite(b); }
-__device__ inline float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-__device__ inline float quiet_nan() { return __uint_as_float(0x7FC00000u); }
 
 // One thread per pixel: planar colour, alpha and normal, the state's m2 (plane s2, .w) and the tile records -> a[p] = (r, g, b, v or
 // NaN), b[p] = (nx, ny, nz, alpha).  A guide that is switched off is not read (its pointer may be null) and reads as 0; b is null
@@ -69,11 +65,7 @@ __global__ void __launch_bounds__(256) k_vdenoise_pack(VarGeom g, const float* _
         }
     }
     a[p] = make_float4(cr, cg, cb, v);
-    if (b) {
-        float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-        if (normal) { nx = normal[f]; ny = normal[f + 1]; nz = normal[f + 2]; }
-        b[p] = make_float4(nx, ny, nz, alpha ? alpha[p] : 0.0f);
-    }
+    write_guide_record(b, p, f, normal, alpha);
 }
 
 // What pass 0 of rayn_hip_denoise_temporal_variance_feedback_device gets on top of a pass's arguments: plane A of the temporal history and
@@ -211,13 +203,8 @@ void launch_pass(hipStream_t s, bool last, dim3 grid, uint32_t width, uint32_t h
 
 } // namespace
 
-// 0 = off; else finite and in [2^-30, 2^30]
-bool vatrous_sigma_ok(float sigma) { return sigma == 0.0f || (sigma >= 0x1p-30f && sigma <= 0x1p30f); }
-
 size_t denoise_variance_scratch_bytes(uint32_t width, uint32_t height) {
-    const uint64_t n = (uint64_t)width * height;
-    if (!n || n >= ((uint64_t)1 << 31)) return 0;
-    return (size_t)(3u * sizeof(float4) * n);
+    return atrous_scratch_bytes(width, height);
 }
 
 const char* denoise_variance_check_args(const rayn_frame_params* p, uint32_t iterations, float sigma_luminance, float sigma_normal,
@@ -225,13 +212,9 @@ const char* denoise_variance_check_args(const rayn_frame_params* p, uint32_t ite
                                         size_t state_bytes, const float* out_color, const float* out_variance, const void* scratch,
                                         size_t scratch_bytes) {
     if (const char* why = progressive_check_geometry(p, state, state_bytes)) return why;
-    if (iterations < 1 || iterations > 8) return "iterations must be in 1..8";
-    if (!vatrous_sigma_ok(sigma_luminance)) return "sigma_luminance must be 0 (off) or in [2^-30, 2^30]";
-    if (!vatrous_sigma_ok(sigma_normal)) return "sigma_normal must be 0 (off) or in [2^-30, 2^30]";
-    if (!vatrous_sigma_ok(sigma_alpha)) return "sigma_alpha must be 0 (off) or in [2^-30, 2^30]";
-    if (!color || !out_color || !scratch) return "null buffer";
-    if (!normal && sigma_normal != 0.0f) return "null normal guide with sigma_normal != 0";
-    if (!alpha && sigma_alpha != 0.0f) return "null alpha guide with sigma_alpha != 0";
+    if (const char* why = check_atrous_params(iterations, sigma_luminance, "sigma_luminance must be 0 (off) or in [2^-30, 2^30]", sigma_normal, sigma_alpha,
+                                              color && out_color && scratch, normal, alpha))
+        return why;
     if (scratch_bytes < denoise_variance_scratch_bytes(p->width, p->height)) return "scratch smaller than rayn_denoise_variance_scratch_bytes(width, height)";
     if ((uintptr_t)scratch % 16u) return "scratch not 16-byte aligned";
     if (out_color == color) return "d_out_color must not be d_color";
@@ -258,18 +241,10 @@ void launch_vatrous_passes(hipStream_t s, uint32_t width, uint32_t height, uint3
         float4* out = plane[(i + 1u) & 1u];
         const uint32_t step = 1u << i;
         float4* hist = (i == 0 && feedback != 0.0f) ? (float4*)history : nullptr;
-#define RAYN_VPASS(T) launch_pass<T>(s, last, grid, width, height, blocks_x, step, sigma_luminance, sigma_normal, sigma_alpha, in, guides, out, out_color, out_variance, hist, feedback)
-        switch (terms) {
-        case 0: RAYN_VPASS(0); break;
-        case 1: RAYN_VPASS(1); break;
-        case 2: RAYN_VPASS(2); break;
-        case 3: RAYN_VPASS(3); break;
-        case 4: RAYN_VPASS(4); break;
-        case 5: RAYN_VPASS(5); break;
-        case 6: RAYN_VPASS(6); break;
-        default: RAYN_VPASS(7); break;
-        }
-#undef RAYN_VPASS
+        with_terms<3>(terms, [&](auto T) {
+            launch_pass<decltype(T)::value>(s, last, grid, width, height, blocks_x, step, sigma_luminance, sigma_normal, sigma_alpha, in, guides, out, out_color,
+                                            out_variance, hist, feedback);
+        });
     }
 }
 

@@ -24,8 +24,9 @@
 #include <stdint.h>
 
 #include "../../include/rayn_detmath.h"
-#include "../../include/rayn_hip.h"
 #include "display.h"
+#include "post_checks.h"
+#include "post_device.h"
 #include "save_to.h"
 
 namespace rayn {
@@ -42,7 +43,6 @@ __device__ inline float saturate1(float x) { return rmin(rmax(x, 0.0f), 1.0f); }
 __device__ inline float gamma22(float x) { return dm_powf(x, 1.0f / 2.2f); }
 
 __device__ inline float fin0(float v) { return __builtin_isfinite(v) ? v : 0.0f; }
-__device__ inline float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 __device__ inline float bright(float e, float c, float threshold) { return rmax(e * fin0(c) - threshold, 0.0f); }
 
 // the input colour of film pixel f: color, or color + background in the Color + Background arm
@@ -327,8 +327,7 @@ void launch_arm(hipStream_t s, const rayn_display_params& dp, uint32_t width, ui
 } // namespace
 
 size_t display_scratch_bytes(uint32_t width, uint32_t height, uint32_t levels) {
-    const uint64_t n = (uint64_t)width * height;
-    if (!n || n >= ((uint64_t)1 << 31) || levels > MAX_LEVELS) return 0;
+    if (check_size(width, height) || levels > MAX_LEVELS) return 0;
     return plan(width, height, levels).total;
 }
 
@@ -339,8 +338,7 @@ const char* display_check_args(const rayn_display_params* dp, uint32_t have_mask
     const char* why = nullptr;
     *arm = save_to_arm(0, have_mask, transparent_background, &why); // the Color kind; < 0: why = the reference's Err text
     if (*arm < 0) return why;
-    if (!width || !height) return "zero-sized image";
-    if ((uint64_t)width * height >= ((uint64_t)1 << 31)) return "image larger than 2^31 pixels unsupported (32-bit pixel indices)";
+    if (const char* size = check_size(width, height)) return size;
     if (dp->tone > TONE_ACES) return "unknown tone operator (0 linear, 1 reinhard, 2 aces)";
     if (dp->levels > MAX_LEVELS) return "bloom levels must be in 0..8 (0 = off)";
     if (dp->auto_exposure > 1u) return "auto_exposure must be 0 (manual) or 1 (auto)";

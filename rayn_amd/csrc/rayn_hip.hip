@@ -25,6 +25,7 @@
 #include "upscale.h"
 #include "denoise.h"
 #include "denoise_variance.h"
+#include "post_checks.h"
 #include "progressive.h"
 #include "temporal.h"
 
@@ -1008,9 +1009,8 @@ int rayn_hip_save_to_pixels_device(rayn_ctx* ctx, uint32_t kind, uint32_t have_m
     const int arm = save_to_arm(kind, have_mask, transparent_background, &why); // < 0: why = the reference's Err text
     if (arm >= 0) {
         const uint32_t reads = save_to_arm_reads(arm);
-        if (!width || !height) why = "zero-sized image";
-        else if ((uint64_t)width * height >= ((uint64_t)1 << 31)) why = "image larger than 2^31 pixels unsupported (32-bit pixel indices)";
-        else if (!d_out || ((reads & 1u) && !d_color) || ((reads & 2u) && !d_alpha) || ((reads & 4u) && !d_background) || ((reads & 8u) && !d_normal))
+        why = check_size(width, height);
+        if (!why && (!d_out || ((reads & 1u) && !d_color) || ((reads & 2u) && !d_alpha) || ((reads & 4u) && !d_background) || ((reads & 8u) && !d_normal)))
             why = "null buffer";
     }
     hipStream_t s;
@@ -1125,11 +1125,7 @@ static int temporal_accumulate(rayn_ctx* ctx, const rayn_frame_params* p, const 
     if (!why && prev_camera && !build_camera(*prev_camera, &ts.cam)) why = "unknown camera kind";
     hipStream_t s;
     if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
-    const rayn_world_desc& w = ctx->cfg->world;
-    ts.prev_time = prev_time_start; ts.cur_time = p->time_start;
-    ts.n_hitables = w.n_hitables < RAYN_MAX_HITABLES ? w.n_hitables : RAYN_MAX_HITABLES;
-    for (uint32_t i = 0; i < ts.n_hitables; i++)
-        ts.hvel[i] = make_float4(w.hitables[i].center_vel.x, w.hitables[i].center_vel.y, w.hitables[i].center_vel.z, w.hitables[i].animated ? 1.0f : 0.0f);
+    fill_temporal_scene(&ts, ctx->cfg->world, prev_time_start, p->time_start);
     launch_temporal_accumulate(s, p->width, p->height, *tp, ts, d_color, d_normal, d_gbuffer_records, d_gbuffer_object, d_prev_history, d_new_history,
                                d_out_color, moments ? d_prev_moments : nullptr, moments ? d_new_moments : nullptr, resample);
     return post_enqueued(ctx);
@@ -1186,11 +1182,7 @@ int rayn_hip_temporal_upscale_device(rayn_ctx* ctx, const rayn_frame_params* p, 
     if (!why && low_camera && !build_camera(*low_camera, &low)) why = "unknown camera kind";
     hipStream_t s;
     if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
-    const rayn_world_desc& w = ctx->cfg->world;
-    ts.prev_time = prev_time_start; ts.cur_time = p->time_start;
-    ts.n_hitables = w.n_hitables < RAYN_MAX_HITABLES ? w.n_hitables : RAYN_MAX_HITABLES;
-    for (uint32_t i = 0; i < ts.n_hitables; i++)
-        ts.hvel[i] = make_float4(w.hitables[i].center_vel.x, w.hitables[i].center_vel.y, w.hitables[i].center_vel.z, w.hitables[i].animated ? 1.0f : 0.0f);
+    fill_temporal_scene(&ts, ctx->cfg->world, prev_time_start, p->time_start);
     launch_temporal_upscale(s, p->width, p->height, *up, *tp, sp->confidence, low_camera ? &low : nullptr, ts, c);
     return post_enqueued(ctx);
 }

@@ -45,12 +45,16 @@
 // rejected: the bilinear step 4 above, exactly.  The kernel checks the 16 taps first (4 + 4 + 4 [+ 16] bytes each) and re-reads the colours
 // (and moments) of a full footprint in a second loop: no 16 live float4.
 // One thread per pixel in 16x16 blocks, 16-byte record loads, as denoise.hip; at most 4 x 3 record loads per pixel: bandwidth-trivial.
+// Step 3 (project), step 4's predicate (history_tap_counts) and step 5 (blend_history) are in post_device.h: k_temporal_upscale's phase C
+// calls the same functions.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
 #include "device_core.h"
+#include "post_checks.h"
+#include "post_device.h"
 #include "temporal.h"
 
 namespace RAYN_KNS {
@@ -91,8 +95,6 @@ namespace {
 constexpr size_t GBUF_CTL_BYTES = 256, GBUF_EVALS_BYTES = 128;
 static_assert(sizeof(DCtl) <= GBUF_CTL_BYTES, "the G-buffer scratch reserves 256 bytes for the control block");
 
-__device__ inline bool fin(float v) { return __builtin_isfinite(v); }
-
 // One thread per pixel: the pool's ray + the hit the extend kernel left in geo1 -> record and object index.
 __global__ void __launch_bounds__(256) k_gbuffer_finish(uint32_t n, const float4* __restrict__ geo0, const float4* __restrict__ geo1,
                                                          float4* __restrict__ out, uint32_t* __restrict__ out_obj) {
@@ -109,16 +111,6 @@ __global__ void __launch_bounds__(256) k_gbuffer_finish(uint32_t n, const float4
     const float mx = t * g0.w, my = t * g1.x, mz = t * g1.y;
     out[i] = make_float4(g0.x + mx, g0.y + my, g0.z + mz, t);
     out_obj[i] = id;
-}
-
-struct v3 { float x, y, z; };
-__device__ inline v3 sub3(v3 a, v3 b) { return v3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline v3 scale3(v3 a, float s) { return v3{a.x * s, a.y * s, a.z * s}; }
-__device__ inline float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ inline v3 cross3(v3 a, v3 b) { return v3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ inline v3 nz3(v3 a) { return scale3(a, 1.0f / __builtin_sqrtf(dot3(a, a))); }
-__device__ inline v3 closure3(f3 base, f3 vel, bool on, float t) {
-    return on ? v3{base.x + vel.x * t, base.y + vel.y * t, base.z + vel.z * t} : v3{base.x, base.y, base.z};
 }
 
 // One Catmull-Rom weight set: the offsets -1, 0, 1, 2 at the fraction t in [0, 1)
@@ -149,6 +141,7 @@ __device__ inline bool cubic_history(long long x0, long long y0, uint32_t width,
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const uint32_t q = q0 + (uint32_t)i + (uint32_t)j * width;
+            // history_tap_counts' four tests, but every plane read before any is looked at: a row's twelve loads are in flight together
             bool counts = pA[q].w >= 1.0f;
             counts &= pO[q] == obj;
             counts &= __builtin_fabsf(pB[q].w - te) <= tol;
@@ -221,39 +214,16 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uin
     const bool cfin = fin(c.x) && fin(c.y) && fin(c.z);
     v3 out = c;
     float nn = cfin ? 1.0f : 0.0f;
-    const float lum = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z, lum2 = lum * lum; // the definition's y, y2
+    const float lum = luminance(c.x, c.y, c.z), lum2 = lum * lum; // the definition's y, y2
     float m1 = cfin ? lum : 0.0f, m2 = cfin ? lum2 : 0.0f;
-    if (cfin && obj != INVALID && pA) {
+    if (cfin && obj != MISS_OBJECT && pA) {
         v3 Pp = v3{g.x, g.y, g.z};
         const float dt = ts.cur_time - ts.prev_time;
 #pragma unroll
         for (uint32_t k = 0; k < RAYN_MAX_HITABLES; k++)
             if (k < ts.n_hitables && obj == k && ts.hvel[k].w != 0.0f) Pp = v3{g.x - ts.hvel[k].x * dt, g.y - ts.hvel[k].y * dt, g.z - ts.hvel[k].z * dt};
-        const DCamera& cam = ts.cam;
-        const v3 o = closure3(cam.origin, cam.origin_vel, cam.animated & 1u, ts.prev_time);
-        const v3 at = closure3(cam.at, cam.at_vel, cam.animated & 2u, ts.prev_time);
-        const v3 up = closure3(cam.up, cam.up_vel, cam.animated & 4u, ts.prev_time);
-        float uvx, uvy, te;
-        bool ok;
-        if (cam.kind == RAYN_CAM_ORTHOGRAPHIC) {
-            const v3 w = nz3(sub3(at, o)), u = nz3(cross3(w, up)), v = cross3(u, w);
-            const v3 ll = sub3(sub3(o, scale3(u, cam.half_w)), scale3(v, cam.half_h));
-            const v3 q = sub3(Pp, ll);
-            uvx = dot3(q, u) / cam.full_w;
-            uvy = dot3(q, v) / cam.full_h;
-            te = dot3(q, w);
-            ok = te > 0.0f;
-        } else {
-            const v3 w = nz3(sub3(o, at)), u = nz3(cross3(up, w)), v = cross3(w, u);
-            const v3 q = sub3(Pp, o);
-            const float zc = -dot3(q, w);
-            ok = zc > 0.0f;
-            uvx = (dot3(q, u) / (zc * cam.half_w) + 1.0f) * 0.5f;
-            uvy = (dot3(q, v) / (zc * cam.half_h) + 1.0f) * 0.5f;
-            te = __builtin_sqrtf(dot3(q, q));
-        }
-        const float fx = uvx * (float)width - 0.5f, fy = uvy * (float)height - 0.5f;
-        if (ok && fin(fx) && fin(fy)) {
+        float fx, fy, te;
+        if (project(ts.cam, ts.prev_time, Pp, width, height, &fx, &fy, &te)) {
             const float x0f = __builtin_floorf(fx), y0f = __builtin_floorf(fy);
             const float wx1 = fx - x0f, wx0 = 1.0f - wx1, wy1 = fy - y0f, wy0 = 1.0f - wy1;
             const long long x0 = (long long)__builtin_fminf(__builtin_fmaxf(x0f, -2.0f), 2147483648.0f);
@@ -270,13 +240,7 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uin
                     if (qx < 0 || qx >= (long long)width || qy < 0 || qy >= (long long)height) continue;
                     const uint32_t q = (uint32_t)qx + (uint32_t)qy * width;
                     const float4 a = pA[q];
-                    if (!(a.w >= 1.0f)) continue;
-                    if (pO[q] != obj) continue;
-                    if (!(__builtin_fabsf(pB[q].w - te) <= tol)) continue;
-                    if (normal_min > -1.0f) {
-                        const float4 nq = pN[q];
-                        if (!(dot3(nrm, v3{nq.x, nq.y, nq.z}) >= normal_min)) continue;
-                    }
+                    if (!history_tap_counts(a.w, q, obj, te, tol, normal_min, nrm, pB, pN, pO)) continue;
                     const float w = ((k & 1) ? wx1 : wx0) * ((k >> 1) ? wy1 : wy0);
                     W += w;
                     Sr += w * a.x;
@@ -296,17 +260,13 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uin
                 }
             }
             if (have) {
-                const float hr = hs.r, hg = hs.g, hb = hs.b, nh = hs.n;
-                const float n1 = __builtin_fminf(nh + 1.0f, max_history);
-                const float al = 1.0f / n1;
-                const float dr = c.x - hr, dg = c.y - hg, db = c.z - hb;
-                const v3 b = v3{hr + al * dr, hg + al * dg, hb + al * db};
-                if (fin(b.x) && fin(b.y) && fin(b.z)) {
-                    out = b; nn = n1;
+                const Blend b = blend_history(c, v3{hs.r, hs.g, hs.b}, hs.n, 1.0f, max_history);
+                if (b.ok) {
+                    out = b.out; nn = b.n1;
                     if (MOMENTS) {
                         const float h1 = hs.m1, h2 = hs.m2;
                         const float d1 = lum - h1, d2 = lum2 - h2;
-                        const float b1 = h1 + al * d1, b2 = h2 + al * d2;
+                        const float b1 = h1 + b.a * d1, b2 = h2 + b.a * d2;
                         if (fin(b1) && fin(b2)) { m1 = b1; m2 = b2; } // else (y, y2): an overflow heals on the next frame
                     }
                 }
@@ -321,17 +281,6 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(uint32_t width, uin
     nN[p] = make_float4(nrm.x, nrm.y, nrm.z, 0.0f);
     nO[p] = obj;
     if (MOMENTS) nM[p] = make_float2(m1, m2);
-}
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + nb && y < x + na;
-}
-
-const char* check_size(uint32_t width, uint32_t height) {
-    if (!width || !height) return "zero-sized image";
-    if ((uint64_t)width * height >= ((uint64_t)1 << 31)) return "image larger than 2^31 pixels unsupported (32-bit pixel indices)";
-    return nullptr;
 }
 
 } // namespace
@@ -387,10 +336,7 @@ const char* temporal_check_args(const rayn_frame_params* p, const rayn_temporal_
                                 const void* new_history, size_t history_bytes, const float* out_color) {
     if (!p) return "null frame params";
     if (const char* why = check_size(p->width, p->height)) return why;
-    if (!tp) return "null temporal params";
-    if (tp->max_history < 1 || tp->max_history > 65536) return "max_history must be in 1..65536";
-    if (!(tp->depth_tolerance >= 0.0f) || !(tp->depth_tolerance <= 3.40282347e+38f)) return "depth_tolerance must be finite and >= 0";
-    if (!(tp->normal_min >= -1.0f && tp->normal_min <= 1.0f)) return "normal_min must be in [-1, 1]";
+    if (const char* why = check_temporal_params(tp)) return why;
     if (!color || !normal || !g_records || !g_object || !new_history || !out_color) return "null buffer";
     if (prev_history && !prev_camera) return "a previous history needs the previous camera";
     if (prev_camera && prev_camera->kind > RAYN_CAM_ORTHOGRAPHIC) return "unknown camera kind";
@@ -401,11 +347,9 @@ const char* temporal_check_args(const rayn_frame_params* p, const rayn_temporal_
     if ((uintptr_t)g_object % 4u) return "d_gbuffer_object not 4-byte aligned";
     const size_t n = (size_t)p->width * p->height;
     if (overlap(new_history, need, prev_history, need)) return "the new history must not alias the previous one";
-    const void* in[4] = {color, normal, g_records, g_object};
-    const size_t in_bytes[4] = {12u * n, 12u * n, 16u * n, 4u * n};
-    for (int i = 0; i < 4; i++)
-        if (overlap(out_color, 12u * n, in[i], in_bytes[i]) || overlap(new_history, need, in[i], in_bytes[i])) return "an output must not alias an input";
-    if (overlap(out_color, 12u * n, prev_history, need)) return "an output must not alias an input";
+    const Span in[5] = {{color, 12u * n}, {normal, 12u * n}, {g_records, 16u * n}, {g_object, 4u * n}, {prev_history, need}};
+    const Span out[2] = {{out_color, 12u * n}, {new_history, need}};
+    if (first_overlap(out, 2, in, 5)) return "an output must not alias an input";
     if (overlap(out_color, 12u * n, new_history, need)) return "d_out_color must not alias the new history";
     return nullptr;
 }
@@ -426,10 +370,9 @@ const char* temporal_moments_check_args(const rayn_frame_params* p, const float*
     if ((uintptr_t)new_moments % 16u || (uintptr_t)prev_moments % 16u) return "moments not 16-byte aligned";
     const size_t n = (size_t)p->width * p->height;
     if (overlap(new_moments, need, prev_moments, need)) return "the new moments must not alias the previous ones";
-    const void* in[6] = {color, normal, g_records, g_object, prev_history, prev_moments};
-    const size_t in_bytes[6] = {12u * n, 12u * n, 16u * n, 4u * n, hist, need};
-    for (int i = 0; i < 6; i++)
-        if (overlap(new_moments, need, in[i], in_bytes[i])) return "an output must not alias an input";
+    const Span in[6] = {{color, 12u * n}, {normal, 12u * n}, {g_records, 16u * n}, {g_object, 4u * n}, {prev_history, hist}, {prev_moments, need}};
+    const Span mom = {new_moments, need};
+    if (first_overlap(&mom, 1, in, 6)) return "an output must not alias an input";
     if (overlap(out_color, 12u * n, prev_moments, need) || overlap(new_history, hist, prev_moments, need)) return "an output must not alias an input";
     if (overlap(new_moments, need, new_history, hist) || overlap(new_moments, need, out_color, 12u * n)) return "the new moments must not alias another output";
     return nullptr;

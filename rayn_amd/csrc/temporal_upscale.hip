@@ -7,12 +7,13 @@
 // The definition (include/rayn_hip.h; tests/temporal_upscale_np.py restates it in numpy and the tests compare bit
 // for bit).  Per high pixel (X, Y) with the high G-buffer's (P, t) and o:
 //   A. footprint in the low film: fx = ((float)X + 0.5f) / s - 0.5f (upscale step 1), or - with a low camera and a hit pixel - P projected
-//      through that camera at the frame's time_start by the temporal entry's step 3 at the LOW size; a rejected projection and a miss
-//      pixel keep the default.  x0, y0 by the temporal entry's step 4.
-//   B. this frame's value: steps 2 and 3 of the upscale on that footprint (three tiers, sums from -0.0f, tap order), every plane;
-//      conf = 1, or with confidence on the largest bilinear weight b_k among the taps that were added in the tier that gave the value.
+//      through that camera at the frame's time_start by the temporal entry's step 3 (project(), post_device.h) at the LOW size; a
+//      rejected projection and a miss pixel keep the default.  x0, y0 by the temporal entry's step 4.
+//   B. this frame's value: steps 2 and 3 of the upscale on that footprint (three tiers, sums from -0.0f, tap order), every plane -
+//      upscale_gather() of post_device.h, the function k_upscale calls; conf = 1, or with confidence on the largest bilinear weight b_k
+//      among the taps that were added in the tier that gave the value (what upscale_gather returns).
 //   C. steps 1 to 5 of the temporal accumulate at the high size on B's Color and WorldNormal, with n' = fminf(nh + conf, max_history)
-//      and a = conf / n'.
+//      and a = conf / n': project(), history_tap_counts() and blend_history() of post_device.h, the functions k_temporal_accumulate calls.
 // With no low camera and confidence off the outputs are, bit for bit, those of k_upscale followed by k_temporal_accumulate - without the
 // 24 bytes per high pixel of Color and WorldNormal written by the one and read back by the other.  f32 throughout, built with
 // -ffp-contract=off and IEEE division; nothing depends on the mul_add policy: the file is built once.
@@ -26,15 +27,12 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "../../include/rayn_detmath_fast.h"
-#include "../../include/rayn_hip.h"
+#include "post_checks.h"
+#include "post_device.h"
 #include "temporal_upscale.h"
 
 namespace rayn {
 namespace {
-
-constexpr uint32_t TERM_PLANE = 1u, TERM_POSITION = 2u;
-constexpr uint32_t MISS = 0xFFFFFFFFu;
 
 struct TUArgs {
     uint32_t w, h, W, H, tiles_x, factor, confidence, have_low_cam; // the low size, the high size, 16x16 tiles per high row
@@ -48,69 +46,9 @@ struct TUArgs {
     TemporalScene ts;
 };
 
-struct v3 { float x, y, z; };
-__device__ inline v3 sub3(v3 a, v3 b) { return v3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline v3 scale3(v3 a, float s) { return v3{a.x * s, a.y * s, a.z * s}; }
-__device__ inline float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ inline v3 cross3(v3 a, v3 b) { return v3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ inline v3 nz3(v3 a) { return scale3(a, 1.0f / __builtin_sqrtf(dot3(a, a))); }
-__device__ inline v3 closure3(f3 base, f3 vel, bool on, float t) {
-    return on ? v3{base.x + vel.x * t, base.y + vel.y * t, base.z + vel.z * t} : v3{base.x, base.y, base.z};
-}
-__device__ inline bool fin(float v) { return __builtin_isfinite(v); }
-
-// Step 3 of the temporal accumulate: the point Pp through the camera at the closure time ts onto a width x height image.  False for a
-// rejected projection (behind the camera, or a position that is not finite).
-__device__ inline bool project(const DCamera& cam, float ts, v3 Pp, uint32_t width, uint32_t height, float* fx, float* fy, float* te) {
-    const v3 o = closure3(cam.origin, cam.origin_vel, cam.animated & 1u, ts);
-    const v3 at = closure3(cam.at, cam.at_vel, cam.animated & 2u, ts);
-    const v3 up = closure3(cam.up, cam.up_vel, cam.animated & 4u, ts);
-    float uvx, uvy;
-    bool ok;
-    if (cam.kind == RAYN_CAM_ORTHOGRAPHIC) {
-        const v3 w = nz3(sub3(at, o)), u = nz3(cross3(w, up)), v = cross3(u, w);
-        const v3 ll = sub3(sub3(o, scale3(u, cam.half_w)), scale3(v, cam.half_h));
-        const v3 q = sub3(Pp, ll);
-        uvx = dot3(q, u) / cam.full_w;
-        uvy = dot3(q, v) / cam.full_h;
-        *te = dot3(q, w);
-        ok = *te > 0.0f;
-    } else {
-        const v3 w = nz3(sub3(o, at)), u = nz3(cross3(up, w)), v = cross3(w, u);
-        const v3 q = sub3(Pp, o);
-        const float zc = -dot3(q, w);
-        ok = zc > 0.0f;
-        uvx = (dot3(q, u) / (zc * cam.half_w) + 1.0f) * 0.5f;
-        uvy = (dot3(q, v) / (zc * cam.half_h) + 1.0f) * 0.5f;
-        *te = __builtin_sqrtf(dot3(q, q));
-    }
-    *fx = uvx * (float)width - 0.5f;
-    *fy = uvy * (float)height - 0.5f;
-    return ok && fin(*fx) && fin(*fy);
-}
-
 // Step 4's integer tap origin.  The definition clamps to [-2, 2^31]; images are at most 2^23 wide and high here (the upscale's limit), so
 // every origin above 2^24 is as far outside as one at 2^31 and the narrower clamp, which fits an int, changes no result.
 __device__ inline int tap_origin(float x0f) { return (int)__builtin_fminf(__builtin_fmaxf(x0f, -2.0f), 16777216.0f); }
-
-// the sums of one weight set of B: every one starts at -0.0f, the identity of + for both zeros (upscale.hip)
-struct Sums {
-    float W = -0.0f, c[3] = {-0.0f, -0.0f, -0.0f}, a = -0.0f, b[3] = {-0.0f, -0.0f, -0.0f}, n[3] = {-0.0f, -0.0f, -0.0f};
-};
-
-__device__ inline void add_tap(Sums& S, float g, size_t q, float cr, float cg, float cb, const UpscalePlanes& pl) {
-    S.W += g;
-    S.c[0] += g * cr;
-    S.c[1] += g * cg;
-    S.c[2] += g * cb;
-    if (pl.alpha) S.a += g * pl.alpha[q];
-    if (pl.background) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) S.b[i] += g * pl.background[3u * q + i];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; i++) S.n[i] += g * pl.normal[3u * q + i];
-}
 
 // TERMS: which of the plane / position terms of B are on.  Every index is bounded by its plane: a low tap is used only with qx < w and
 // qy < h, the tier-3 source is clamped to the low image, a history tap only with qx < W and qy < H, and P < W * H by the guards on X, Y.
@@ -127,7 +65,7 @@ __global__ void __launch_bounds__(256) k_temporal_upscale(const TUArgs A) {
     // ---- A: the footprint in the low film
     const float sf = (float)A.factor;
     float fx = ((float)X + 0.5f) / sf - 0.5f, fy = ((float)Y + 0.5f) / sf - 0.5f; // exact pixel centres (W, H <= 2^23)
-    if (A.have_low_cam && o != MISS) {
+    if (A.have_low_cam && o != MISS_OBJECT) {
         float pfx, pfy, pte;
         if (project(A.low_cam, A.ts.cur_time, v3{G.x, G.y, G.z}, A.w, A.h, &pfx, &pfy, &pte)) { fx = pfx; fy = pfy; }
     }
@@ -139,62 +77,16 @@ __global__ void __launch_bounds__(256) k_temporal_upscale(const TUArgs A) {
         const float wx0 = 1.0f - wx1, wy0 = 1.0f - wy1;
         const int x0 = tap_origin(x0f), y0 = tap_origin(y0f);
 
-        // ---- B: this frame's value (upscale.hip steps 2 and 3)
-        const bool guided = TERMS != 0u && o != MISS;
-        const float inv_t = 1.0f / (G.w + 1e-8f);
-        const float kp = (TERMS & TERM_PLANE) ? 1.0f / (A.sigma_plane * A.sigma_plane) : 0.0f;
-        const float ks = (TERMS & TERM_POSITION) ? 1.0f / (A.sigma_position * A.sigma_position) : 0.0f;
+        // ---- B: this frame's value (steps 2 and 3 of the upscale)
+        const UpscaleGuide u = upscale_guide<TERMS>(o, TERMS != 0u && o != MISS_OBJECT, G, A.sigma_plane, A.sigma_position);
         Sums S;
-        float bmax = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            // unsigned wrap: a negative coordinate becomes >= w (w < 2^31)
-            const uint32_t qx = (uint32_t)(x0 + (k & 1)), qy = (uint32_t)(y0 + (k >> 1));
-            if (qx >= A.w || qy >= A.h) continue;
-            const float b = ((k & 1) ? wx1 : wx0) * ((k >> 1) ? wy1 : wy0);
-            if (!(b > 0.0f)) continue;
-            const size_t q = (size_t)qx + (size_t)qy * A.w;
-            if (pl.low_object[q] != o) continue;
-            const float cr = pl.color[3u * q], cg = pl.color[3u * q + 1], cb = pl.color[3u * q + 2];
-            if (!(fin(cr) && fin(cg) && fin(cb))) continue;
-            float g = b; // a miss pixel; and a hit pixel with both terms off
-            if (guided) {
-                const float4 Q = ((const float4*)pl.low_records)[q];
-                const float dx = G.x - Q.x, dy = G.y - Q.y, dz = G.z - Q.z;
-                float e = 0.0f;
-                if (TERMS & TERM_PLANE) {
-                    const float nx = pl.normal[3u * q], ny = pl.normal[3u * q + 1], nzq = pl.normal[3u * q + 2];
-                    const float dpl = fabsf((nx * dx + ny * dy) + nzq * dz) * inv_t;
-                    e = (dpl * dpl) * kp;
-                }
-                if (TERMS & TERM_POSITION) {
-                    const float dps = ((dx * dx + dy * dy) + dz * dz) * (inv_t * inv_t);
-                    e = (TERMS & TERM_PLANE) ? e + dps * ks : dps * ks;
-                }
-                g = b * dmf_expf(-e);
-                if (g != g) continue;
-            }
-            add_tap(S, g, q, cr, cg, cb, pl);
-            bmax = __builtin_fmaxf(bmax, b);
-        }
+        float bmax = upscale_gather<TERMS, true, true>(S, x0, y0, wx0, wx1, wy0, wy1, A.w, A.h, u, pl);
         weight = S.W;
         if (!(S.W > 0.0f)) {
             // tier 2: the plain bilinear weights over the usable taps, whatever they show
             weight = 0.0f;
             S = Sums();
-            bmax = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint32_t qx = (uint32_t)(x0 + (k & 1)), qy = (uint32_t)(y0 + (k >> 1));
-                if (qx >= A.w || qy >= A.h) continue;
-                const float b = ((k & 1) ? wx1 : wx0) * ((k >> 1) ? wy1 : wy0);
-                if (!(b > 0.0f)) continue;
-                const size_t q = (size_t)qx + (size_t)qy * A.w;
-                const float cr = pl.color[3u * q], cg = pl.color[3u * q + 1], cb = pl.color[3u * q + 2];
-                if (!(fin(cr) && fin(cg) && fin(cb))) continue;
-                add_tap(S, b, q, cr, cg, cb, pl);
-                bmax = __builtin_fmaxf(bmax, b);
-            }
+            bmax = upscale_gather<TERMS, false, true>(S, x0, y0, wx0, wx1, wy0, wy1, A.w, A.h, u, pl);
         }
         const size_t F = (size_t)P * 3u;
         if (S.W > 0.0f) {
@@ -224,11 +116,11 @@ __global__ void __launch_bounds__(256) k_temporal_upscale(const TUArgs A) {
         if (pl.out_weight) pl.out_weight[P] = weight;
     }
 
-    // ---- C: accumulate at the high size (temporal.hip steps 1 to 5, with conf in step 5)
+    // ---- C: accumulate at the high size (steps 1 to 5 of the temporal accumulate, with conf in step 5)
     const bool cfin = fin(c.x) && fin(c.y) && fin(c.z);
     v3 out = c;
     float nn = cfin ? 1.0f : 0.0f;
-    if (cfin && o != MISS && A.pA) {
+    if (cfin && o != MISS_OBJECT && A.pA) {
         const TemporalScene& ts = A.ts;
         v3 Pp = v3{G.x, G.y, G.z};
         const float dt = ts.cur_time - ts.prev_time;
@@ -248,13 +140,7 @@ __global__ void __launch_bounds__(256) k_temporal_upscale(const TUArgs A) {
                 if (qx >= A.W || qy >= A.H) continue;
                 const uint32_t q = qx + qy * A.W;
                 const float4 a = A.pA[q];
-                if (!(a.w >= 1.0f)) continue;
-                if (A.pO[q] != o) continue;
-                if (!(__builtin_fabsf(A.pB[q].w - te) <= tol)) continue;
-                if (A.normal_min > -1.0f) {
-                    const float4 nq = A.pN[q];
-                    if (!(dot3(nrm, v3{nq.x, nq.y, nq.z}) >= A.normal_min)) continue;
-                }
+                if (!history_tap_counts(a.w, q, o, te, tol, A.normal_min, nrm, A.pB, A.pN, A.pO)) continue;
                 const float w = ((k & 1) ? wx1 : wx0) * ((k >> 1) ? wy1 : wy0);
                 Wh += w;
                 Sr += w * a.x;
@@ -263,12 +149,8 @@ __global__ void __launch_bounds__(256) k_temporal_upscale(const TUArgs A) {
                 N += w * a.w;
             }
             if (Wh > 0.0f) {
-                const float hr = Sr / Wh, hg = Sg / Wh, hb = Sb / Wh, nh = N / Wh;
-                const float n1 = __builtin_fminf(nh + conf, A.max_history);
-                const float al = conf / n1;
-                const float dr = c.x - hr, dg = c.y - hg, db = c.z - hb;
-                const v3 b = v3{hr + al * dr, hg + al * dg, hb + al * db};
-                if (fin(b.x) && fin(b.y) && fin(b.z)) { out = b; nn = n1; }
+                const Blend b = blend_history(c, v3{Sr / Wh, Sg / Wh, Sb / Wh}, N / Wh, conf, A.max_history);
+                if (b.ok) { out = b.out; nn = b.n1; }
             }
         }
     }
@@ -282,11 +164,6 @@ __global__ void __launch_bounds__(256) k_temporal_upscale(const TUArgs A) {
     A.nO[P] = o;
 }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + nb && y < x + na;
-}
-
 } // namespace
 
 const char* temporal_upscale_check_args(const rayn_frame_params* p, const rayn_upscale_params* up, const rayn_temporal_params* tp,
@@ -297,10 +174,7 @@ const char* temporal_upscale_check_args(const rayn_frame_params* p, const rayn_u
     // the upscale's own rules: the factor, both sizes, the sigmas, the planes, the G-buffers and every overlap among them
     if (const char* why = upscale_check_args(p->width, p->height, up, pl)) return why;
     // the temporal accumulate's, at the high size
-    if (!tp) return "null temporal params";
-    if (tp->max_history < 1 || tp->max_history > 65536) return "max_history must be in 1..65536";
-    if (!(tp->depth_tolerance >= 0.0f) || !(tp->depth_tolerance <= 3.40282347e+38f)) return "depth_tolerance must be finite and >= 0";
-    if (!(tp->normal_min >= -1.0f && tp->normal_min <= 1.0f)) return "normal_min must be in [-1, 1]";
+    if (const char* why = check_temporal_params(tp)) return why;
     if (!sp) return "null temporal upscale params";
     if (sp->confidence > 1u) return "confidence must be 0 (off) or 1 (on)";
     if (!pl.normal || !c.new_history) return "null buffer"; // the accumulate needs the WorldNormal
@@ -312,15 +186,12 @@ const char* temporal_upscale_check_args(const rayn_frame_params* p, const rayn_u
     if ((uintptr_t)c.new_history % 16u || (uintptr_t)c.prev_history % 16u) return "history not 16-byte aligned";
     if (overlap(c.new_history, need, c.prev_history, need)) return "the new history must not alias the previous one";
     const size_t n = (size_t)p->width * p->height, N = (size_t)W * H;
-    const void* in[8] = {pl.color, pl.alpha, pl.background, pl.normal, pl.low_records, pl.low_object, pl.high_records, pl.high_object};
-    const size_t in_bytes[8] = {12u * n, 4u * n, 12u * n, 12u * n, 16u * n, 4u * n, 16u * N, 4u * N};
-    for (int i = 0; i < 8; i++)
-        if (overlap(c.new_history, need, in[i], in_bytes[i])) return "an output must not alias an input";
-    const void* out[5] = {pl.out_color, pl.out_alpha, pl.out_background, pl.out_normal, pl.out_weight};
-    const size_t out_bytes[5] = {12u * N, 4u * N, 12u * N, 12u * N, 4u * N};
+    const UpscaleSpans us = upscale_spans(pl, n, N);
+    const Span prev = {c.prev_history, need}, next = {c.new_history, need};
+    if (first_overlap(&next, 1, us.in, 8)) return "an output must not alias an input";
     for (int i = 0; i < 5; i++) {
-        if (overlap(out[i], out_bytes[i], c.prev_history, need)) return "an output must not alias an input";
-        if (overlap(out[i], out_bytes[i], c.new_history, need)) return i == 0 ? "d_out_color must not alias the new history" : "the outputs must not alias each other";
+        if (first_overlap(us.out + i, 1, &prev, 1)) return "an output must not alias an input";
+        if (first_overlap(us.out + i, 1, &next, 1)) return i == 0 ? "d_out_color must not alias the new history" : "the outputs must not alias each other";
     }
     return nullptr;
 }
@@ -355,14 +226,9 @@ void launch_temporal_upscale(hipStream_t s, uint32_t width, uint32_t height, con
     A.nO = (uint32_t*)(nA + 3u * N);
     A.low_cam = low_cam ? *low_cam : ts.cam;
     A.ts = ts;
-    const uint32_t terms = (up.sigma_plane != 0.0f ? TERM_PLANE : 0u) | (up.sigma_position != 0.0f ? TERM_POSITION : 0u);
+    const uint32_t terms = (up.sigma_plane != 0.0f ? UPSCALE_PLANE : 0u) | (up.sigma_position != 0.0f ? UPSCALE_POSITION : 0u);
     const dim3 grid(A.tiles_x * ((A.H + 15u) / 16u)), block(16, 16);
-    switch (terms) {
-    case 0: hipLaunchKernelGGL((k_temporal_upscale<0>), grid, block, 0, s, A); break;
-    case 1: hipLaunchKernelGGL((k_temporal_upscale<1>), grid, block, 0, s, A); break;
-    case 2: hipLaunchKernelGGL((k_temporal_upscale<2>), grid, block, 0, s, A); break;
-    default: hipLaunchKernelGGL((k_temporal_upscale<3>), grid, block, 0, s, A); break;
-    }
+    with_terms<2>(terms, [&](auto T) { hipLaunchKernelGGL((k_temporal_upscale<decltype(T)::value>), grid, block, 0, s, A); });
 }
 
 } // namespace rayn

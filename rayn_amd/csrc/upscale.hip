@@ -14,20 +14,19 @@
 // Layout: one thread per high pixel, blocks of 128 threads over contiguous runs of a row, rows x runs in a 1-D grid.  A pixel reads 20
 // bytes of its own guide (one 128-bit record load and the object index) and writes up to 44; its taps are shared with the s x s pixels
 // around it and come from L2.  The guided pass keeps eleven sums; the two fallback tiers re-read the taps in a branch few pixels take,
-// which keeps their sums out of the common path's registers.
+// which keeps their sums out of the common path's registers.  The sums and the gather of one tier (Sums, add_tap, upscale_gather) are in
+// post_device.h: k_temporal_upscale runs the same function on its own footprint.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
-#include "../../include/rayn_detmath_fast.h"
-#include "../../include/rayn_hip.h"
+#include "post_checks.h"
+#include "post_device.h"
 #include "upscale.h"
 
 namespace rayn {
 namespace {
 
-constexpr uint32_t TERM_PLANE = 1u, TERM_POSITION = 2u;
-constexpr uint32_t MISS = 0xFFFFFFFFu;
 constexpr uint32_t BLOCK = 128u;
 
 struct UpscaleArgs {
@@ -35,28 +34,6 @@ struct UpscaleArgs {
     float sigma_plane, sigma_position;
     UpscalePlanes pl;
 };
-
-// the sums of one weight set: every one starts at -0.0f, the identity of + for both zeros, so that a single tap of weight 1 gives the
-// tap's own bits back (0.0f + -0.0f would be +0.0f)
-struct Sums {
-    float W = -0.0f, c[3] = {-0.0f, -0.0f, -0.0f}, a = -0.0f, b[3] = {-0.0f, -0.0f, -0.0f}, n[3] = {-0.0f, -0.0f, -0.0f};
-};
-
-__device__ inline void add_tap(Sums& S, float g, size_t q, float cr, float cg, float cb, const UpscalePlanes& pl) {
-    S.W += g;
-    S.c[0] += g * cr;
-    S.c[1] += g * cg;
-    S.c[2] += g * cb;
-    if (pl.alpha) S.a += g * pl.alpha[q];
-    if (pl.background) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) S.b[i] += g * pl.background[3u * q + i];
-    }
-    if (pl.normal) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) S.n[i] += g * pl.normal[3u * q + i];
-    }
-}
 
 __device__ inline void write_mean(const Sums& S, size_t P, const UpscalePlanes& pl) {
 #pragma unroll
@@ -71,8 +48,6 @@ __device__ inline void write_mean(const Sums& S, size_t P, const UpscalePlanes& 
         for (int i = 0; i < 3; i++) pl.out_normal[3u * P + i] = S.n[i] / S.W;
     }
 }
-
-__device__ inline bool finite3(float x, float y, float z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
 
 // TERMS: which of the plane / position terms are on.  Every index is bounded by its plane: a tap is used only with qx < w and qy < h
 // (q < w * h), the tier-3 source is clamped to the low image, and P < W * H by the two guards on X and the grid (blocks_x * H blocks).
@@ -90,60 +65,19 @@ __global__ void __launch_bounds__(BLOCK) k_upscale(const UpscaleArgs A) {
     const float wx0 = 1.0f - wx1, wy0 = 1.0f - wy1;
     const int x0 = (int)x0f, y0 = (int)y0f; // -1 .. w - 1
     const uint32_t o = pl.high_object[P];
-    const bool guided = TERMS != 0u && o != MISS;
+    const bool guided = TERMS != 0u && o != MISS_OBJECT;
     float4 G = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (guided) G = ((const float4*)pl.high_records)[P];
-    const float inv_t = 1.0f / (G.w + 1e-8f);
-    const float kp = (TERMS & TERM_PLANE) ? 1.0f / (A.sigma_plane * A.sigma_plane) : 0.0f;
-    const float ks = (TERMS & TERM_POSITION) ? 1.0f / (A.sigma_position * A.sigma_position) : 0.0f;
+    const UpscaleGuide u = upscale_guide<TERMS>(o, guided, G, A.sigma_plane, A.sigma_position);
 
     Sums S;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        // unsigned wrap: x0 = -1 becomes >= w (w < 2^31)
-        const uint32_t qx = (uint32_t)(x0 + (k & 1)), qy = (uint32_t)(y0 + (k >> 1));
-        if (qx >= A.w || qy >= A.h) continue;
-        const float b = ((k & 1) ? wx1 : wx0) * ((k >> 1) ? wy1 : wy0);
-        if (!(b > 0.0f)) continue;
-        const size_t q = (size_t)qx + (size_t)qy * A.w;
-        if (pl.low_object[q] != o) continue;
-        const float cr = pl.color[3u * q], cg = pl.color[3u * q + 1], cb = pl.color[3u * q + 2];
-        if (!finite3(cr, cg, cb)) continue;
-        float g = b; // a miss pixel; and a hit pixel with both terms off: e = 0 and dm_expf(-0) = 1
-        if (guided) {
-            const float4 Q = ((const float4*)pl.low_records)[q];
-            const float dx = G.x - Q.x, dy = G.y - Q.y, dz = G.z - Q.z;
-            float e = 0.0f;
-            if (TERMS & TERM_PLANE) {
-                const float nx = pl.normal[3u * q], ny = pl.normal[3u * q + 1], nz = pl.normal[3u * q + 2];
-                const float dpl = fabsf((nx * dx + ny * dy) + nz * dz) * inv_t;
-                e = (dpl * dpl) * kp;
-            }
-            if (TERMS & TERM_POSITION) {
-                const float dps = ((dx * dx + dy * dy) + dz * dz) * (inv_t * inv_t);
-                e = (TERMS & TERM_PLANE) ? e + dps * ks : dps * ks;
-            }
-            g = b * dmf_expf(-e);
-            if (g != g) continue;
-        }
-        add_tap(S, g, q, cr, cg, cb, pl);
-    }
+    upscale_gather<TERMS, true, false>(S, x0, y0, wx0, wx1, wy0, wy1, A.w, A.h, u, pl);
     float weight = S.W;
     if (!(S.W > 0.0f)) {
         // tier 2: the plain bilinear weights over the usable taps, whatever they show
         weight = 0.0f;
         S = Sums();
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t qx = (uint32_t)(x0 + (k & 1)), qy = (uint32_t)(y0 + (k >> 1));
-            if (qx >= A.w || qy >= A.h) continue;
-            const float b = ((k & 1) ? wx1 : wx0) * ((k >> 1) ? wy1 : wy0);
-            if (!(b > 0.0f)) continue;
-            const size_t q = (size_t)qx + (size_t)qy * A.w;
-            const float cr = pl.color[3u * q], cg = pl.color[3u * q + 1], cb = pl.color[3u * q + 2];
-            if (!finite3(cr, cg, cb)) continue;
-            add_tap(S, b, q, cr, cg, cb, pl);
-        }
+        upscale_gather<TERMS, false, false>(S, x0, y0, wx0, wx1, wy0, wy1, A.w, A.h, u, pl);
     }
     if (S.W > 0.0f) {
         write_mean(S, P, pl);
@@ -166,14 +100,6 @@ __global__ void __launch_bounds__(BLOCK) k_upscale(const UpscaleArgs A) {
     if (pl.out_weight) pl.out_weight[P] = weight;
 }
 
-// 0 = off; else finite and in [2^-30, 2^30]
-bool sigma_ok(float sigma) { return sigma == 0.0f || (sigma >= 0x1p-30f && sigma <= 0x1p30f); }
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + nb && y < x + na;
-}
-
 } // namespace
 
 const char* upscale_check_args(uint32_t width, uint32_t height, const rayn_upscale_params* up, const UpscalePlanes& pl) {
@@ -193,15 +119,10 @@ const char* upscale_check_args(uint32_t width, uint32_t height, const rayn_upsca
     if ((uintptr_t)pl.low_records % 16u || (uintptr_t)pl.high_records % 16u) return "G-buffer records not 16-byte aligned";
     if ((uintptr_t)pl.low_object % 4u || (uintptr_t)pl.high_object % 4u) return "G-buffer objects not 4-byte aligned";
     const size_t n = (size_t)width * height, N = (size_t)(W * H);
-    const void* in[8] = {pl.color, pl.alpha, pl.background, pl.normal, pl.low_records, pl.low_object, pl.high_records, pl.high_object};
-    const size_t in_bytes[8] = {12u * n, 4u * n, 12u * n, 12u * n, 16u * n, 4u * n, 16u * N, 4u * N};
-    const void* out[5] = {pl.out_color, pl.out_alpha, pl.out_background, pl.out_normal, pl.out_weight};
-    const size_t out_bytes[5] = {12u * N, 4u * N, 12u * N, 12u * N, 4u * N};
+    const UpscaleSpans sp = upscale_spans(pl, n, N);
     for (int i = 0; i < 5; i++) {
-        for (int j = 0; j < 8; j++)
-            if (overlap(out[i], out_bytes[i], in[j], in_bytes[j])) return "an output must not alias an input";
-        for (int j = i + 1; j < 5; j++)
-            if (overlap(out[i], out_bytes[i], out[j], out_bytes[j])) return "the outputs must not alias each other";
+        if (first_overlap(sp.out + i, 1, sp.in, 8)) return "an output must not alias an input";
+        if (first_overlap(sp.out + i, 1, sp.out + i + 1, 4 - i)) return "the outputs must not alias each other";
     }
     return nullptr;
 }
@@ -216,14 +137,9 @@ void launch_upscale(hipStream_t s, uint32_t width, uint32_t height, const rayn_u
     A.sigma_plane = up.sigma_plane;
     A.sigma_position = up.sigma_position;
     A.pl = pl;
-    const uint32_t terms = (up.sigma_plane != 0.0f ? TERM_PLANE : 0u) | (up.sigma_position != 0.0f ? TERM_POSITION : 0u);
+    const uint32_t terms = (up.sigma_plane != 0.0f ? UPSCALE_PLANE : 0u) | (up.sigma_position != 0.0f ? UPSCALE_POSITION : 0u);
     const dim3 grid(A.blocks_x * (height * up.factor)), block(BLOCK); // blocks_x * H <= W * H < 2^31
-    switch (terms) {
-    case 0: hipLaunchKernelGGL((k_upscale<0>), grid, block, 0, s, A); break;
-    case 1: hipLaunchKernelGGL((k_upscale<1>), grid, block, 0, s, A); break;
-    case 2: hipLaunchKernelGGL((k_upscale<2>), grid, block, 0, s, A); break;
-    default: hipLaunchKernelGGL((k_upscale<3>), grid, block, 0, s, A); break;
-    }
+    with_terms<2>(terms, [&](auto T) { hipLaunchKernelGGL((k_upscale<decltype(T)::value>), grid, block, 0, s, A); });
 }
 
 } // namespace rayn
