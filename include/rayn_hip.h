@@ -914,6 +914,31 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *          or one that two tiles own; a contributing sample deeper than 120; an object word that is neither below 0xFF nor 0xFF; for 512 < spp <= 4096 a
  *          depth at or beyond n_depths, hist_stride < n_tiles, a slot below its base_hist entry or 2^25 or more above it; two contributing samples of one
  *          pixel with equal (depth, slot) - a slot holds one path, and the order of such a pair would be undefined.  Only the paths tiles own are looked at.
+ *   rayn_hip_probe_raygen     the ray-generation stage through the PRODUCT launchers under the ctx's mul_add policy, as the frame set-up and the batch loop launch them:
+ *                             k_pack_tables (the per-(depth, sample) packed sample records), k_batch_setup (the tile of every 64-slot pool group and every tile's group
+ *                             range) and k_raygen (the tile ray-gen loop, src/film.rs:456-529, one thread per pool slot) - with the uploaded world's camera, on
+ *                             caller-built tables and a caller-built tile list that need not be the reference grid's.
+ *     in   p as rayn_hip_render_frame takes it (tile_w / tile_h / tile_first / tile_step are not read: the tiles are given); samples_1d[n_samples_1d],
+ *          samples_2d[n_samples_2d], scramble[n_scramble], fis_table[512] with the counts in floats; tiles[n_tiles][8] = the device tile words x0, y0, ew, eh,
+ *          pool_base, n_paths, film_base, film_packed (the last two are not read by this stage); n_pool = pool slots, a multiple of 64; surplus = slots of
+ *          sentinel every per-slot output holds after the pool, a multiple of 64, at least 128; sentinel = the word every output starts as (term_info: its
+ *          low byte): neither 0xFFFFFFFF nor below n_pool, low byte not 0xFF.
+ *     out  per slot of the n_pool + surplus: out_geo0 / out_geo1 / out_col0 / out_col1 / out_aov [.][4] in the pool's own encoding (rayn_hip_probe_shade),
+ *          out_term_key, out_term_info, out_q (the ray queue); out_pgrp_tile[(n_pool + surplus) / 64]; out_tgb / out_tgc [n_tiles + 2]; out_ctl[8] = the
+ *          32-bit words of the control block: q_groups, q_valid, b_groups, b_valid, head_extend, job_count, head_shadow, overflow (k_raygen writes q_groups,
+ *          q_valid and head_extend; the others keep the sentinel); out_records[(max_bounces + 1) * 4 * samples * rec_stride * 4 + 64] floats, rec_stride =
+ *          (8 + 12 + 8 * volume_marches) / 4: record depth * spp + s = the 3 + VM 1-D sets 1 + k + depth * (3 + VM) of sample s, zeros up to 8 floats, then the
+ *          12 + 8 * VM components c of the 2-D sets 2 + c / 2 + depth * (6 + 4 * VM), as the tables hold them (no scramble).
+ *          A path slot has origin / dir, hit t 0, OBJ_NONE | sample << 8, radiance 0, throughput 1, its film pixel and time, aov (0, 0, 0, OBJ_NONE), term_info
+ *          0xFF and q = its own index; a padding slot (the tail of a tile's last group) has aov and term_info alike, q = 0xFFFFFFFF and nothing else written;
+ *          term_key is not written by this stage.
+ *     Rejected with RAYN_ERR_INVALID_ARG before anything is launched or written - what the kernels could not index: what rayn_hip_render_frame rejects in p
+ *          (volume_marches outside 2..4, max_bounces above 120, samples outside 1..4096 - so spp is a multiple of 4 in 4..16384); a null buffer;
+ *          n_samples_1d != spp * rayn_sets_1d or n_samples_2d != spp * 2 * rayn_sets_2d for p's bounces and volume marches; n_scramble != width * height;
+ *          n_tiles outside 1..2^20; n_pool 0, not a multiple of 64 or above 2^27; a bad surplus or sentinel; a tile of no pixel or of more than 1024; a tile
+ *          that does not lie inside width x height; n_paths != ew * eh * spp; a pool_base that is not a multiple of 64; tiles whose 64-padded segments
+ *          [pool_base, pool_base + ceil64(n_paths)) overlap, end beyond n_pool or leave a gap in [0, n_pool) (k_raygen reads pgrp_tile[P / 64] for every
+ *          P < n_pool, so a gap would read an unwritten word).  The segments may come in any order.
  *   rayn_hip_probe_shade_limits  the sizes that decide how many grid-stride trips the streaming kernels of the shade stage make, as the library was built: the block
  *                             cap of their grids (stream_blocks; k_shadow_list, k_shade_finish), the [sample][slot] ids a block of k_shadow_list scans per trip
  *                             (list_ids_per_block) and the block size of k_shade_setup (setup_threads; its grid has no cap).  No GPU work.  Tests size the case that
@@ -953,6 +978,13 @@ int rayn_hip_probe_shade(rayn_ctx* ctx, const rayn_frame_params* p, const float*
                          uint32_t sentinel, float* out_geo0, float* out_geo1, float* out_col0, float* out_col1,
                          float* out_aov, uint32_t* out_term_key, uint8_t* out_term_info,
                          uint64_t* out_alive_mask, uint8_t* out_bgrp_cnt, uint64_t* out_jobs);
+int rayn_hip_probe_raygen(rayn_ctx* ctx, const rayn_frame_params* p, const float* samples_1d, uint64_t n_samples_1d,
+                          const float* samples_2d, uint64_t n_samples_2d, const float* scramble, uint64_t n_scramble,
+                          const float* fis_table, uint32_t n_tiles, const uint32_t* tiles, uint32_t n_pool,
+                          uint32_t surplus, uint32_t sentinel, float* out_geo0, float* out_geo1, float* out_col0,
+                          float* out_col1, float* out_aov, uint32_t* out_term_key, uint8_t* out_term_info,
+                          uint32_t* out_q, uint32_t* out_pgrp_tile, uint32_t* out_tgb, uint32_t* out_tgc,
+                          uint32_t* out_ctl, float* out_records);
 int rayn_hip_probe_march_limits(const rayn_ctx* ctx, uint32_t* chunk, uint32_t* endgame_entries,
                                 uint32_t* persistent_blocks, uint32_t* bulb_rays);
 int rayn_hip_probe_sdf_dist(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t hitable_index,

@@ -58,6 +58,8 @@ def lib(fma=False, variant=None):
                                         up, up, up, up, up, up]
         L.oracle_trace_shade.restype = C.c_int64
         L.oracle_trace_shade.argtypes = [C.c_void_p, C.c_void_p, fp, fp, fp, fp, C.c_uint32, C.c_uint64, up, up, fp, up, fp]
+        L.oracle_raygen_tile.restype = C.c_int64
+        L.oracle_raygen_tile.argtypes = [C.c_void_p, C.c_void_p, fp, fp, fp, fp] + [C.c_uint32] * 4 + [C.c_uint64, fp, up]
         L.oracle_shade_packets.restype = C.c_int
         L.oracle_shade_packets.argtypes = [C.c_void_p, C.c_void_p, fp, fp, C.c_uint32, C.c_uint64, up, up, fp, up, fp]
         L.oracle_build_rd_tables.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, fp, fp]
@@ -128,6 +130,20 @@ def trace_tile(world_desc, params, tables, tile_index, fma=False, variant=None):
         raise RuntimeError(f"oracle_trace_tile failed: {n}")
     keys = ["depth", "obj", "px", "py", "sample", "valid"]
     return {k: a[:n].copy() for k, a in zip(keys, arrs)}
+
+
+def raygen_tile(world_desc, params, tables, x0, y0, x1, y1, fma=False):
+    """The ray-gen loop of the tile [x0, x1) x [y0, y1) (any rectangle inside the film), through the function the film's tile closure calls.  dict over the
+    paths in the reference's order (x outer, y inner, packet, lane): origin, dir [n, 3], time [n] float32; pixel (x + y * width), sample [n] uint32."""
+    L = lib(fma)
+    s1, s2, scr, fis = [np.ascontiguousarray(t, np.float32) for t in tables]
+    assert scr.size == params.width * params.height and fis.size == 512
+    cap = max(int(x1) - int(x0), 0) * max(int(y1) - int(y0), 0) * params.samples * 4
+    f, u = np.zeros((max(cap, 1), 7), np.float32), np.zeros((max(cap, 1), 2), np.uint32)
+    n = L.oracle_raygen_tile(C.byref(world_desc), C.byref(params), _fp(s1), _fp(s2), _fp(scr), _fp(fis), x0, y0, x1, y1, cap, _fp(f), _up(u))
+    if n != cap or n <= 0:
+        raise ValueError(f"oracle_raygen_tile failed: {n}")
+    return {"origin": f[:, 0:3].copy(), "dir": f[:, 3:6].copy(), "time": f[:, 6].copy(), "pixel": u[:, 0].copy(), "sample": u[:, 1].copy()}
 
 
 # lane status of shade_packets / trace_shade

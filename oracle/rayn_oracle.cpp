@@ -1081,22 +1081,20 @@ inline void fetch_packet_samples(const Samples& sample_sets, const WRay& ray, si
     }
 }
 
-/* the tile closure of render_frame_into, src/film.rs:439-627 */
-void integrate_tile(Tile& tile, const World& world, const Camera& camera, const Integrator& integrator,
-                    const Samples& sample_sets, const float* fis, const float* scramble_buf,
-                    const rayn_frame_params& p, Counters* ctr, TraceSink* trace, ShadeSink* shade = nullptr, bool* shade_ok = nullptr) {
-    const size_t VM = p.volume_marches;
+/* Optional record of the ray-gen loop (oracle_raygen_tile), per path in the loop's order (x outer, y inner, packet, lane):
+ * origin, dir, time (7 floats) | film pixel x + y * width, sample number (2 words). */
+struct RaygenSink { std::vector<float> f; std::vector<uint32_t> u; };
+
+/* the ray-gen loop of the tile closure, src/film.rs:456-529: one WRay per (pixel, packet of 4 samples) appended to `out` */
+void raygen_tile(const TileBounds& b, const Camera& camera, const Samples& sample_sets, const float* fis, const float* scramble_buf,
+                 const rayn_frame_params& p, std::vector<WRay>& out, Counters* ctr, RaygenSink* sink = nullptr) {
     const size_t samples = p.samples;
     const uint32_t width = p.width;
-    std::vector<Ray> spawned_rays; std::vector<WRay> spawned_wrays;
-    std::vector<ShadingInfo> wintersections; std::vector<ChannelSample> new_samples;
-    HitStore hit_store(world.hitables.size());
     F4 time_range_range(p.time_end - p.time_start);
     float ndc_x = 1.0f / (float)p.width, ndc_y = 1.0f / (float)p.height; /* Tile::new, src/film.rs:152 */
-
-    for (uint32_t x = tile.b.x0; x < tile.b.x1; x++)
-        for (uint32_t y = tile.b.y0; y < tile.b.y1; y++) {
-            uint32_t tcx = x - tile.b.x0, tcy = y - tile.b.y0;
+    for (uint32_t x = b.x0; x < b.x1; x++)
+        for (uint32_t y = b.y0; y < b.y1; y++) {
+            uint32_t tcx = x - b.x0, tcy = y - b.y0;
             float scramble = scramble_buf[x + y * width]; /* src/film.rs:460-461, precomputed */
             for (size_t samp = 0; samp < samples; samp++) {
                 size_t nums[4] = {4 * samp, 4 * samp + 1, 4 * samp + 2, 4 * samp + 3};
@@ -1110,10 +1108,31 @@ void integrate_tile(Tile& tile, const World& world, const Camera& camera, const 
                 }
                 F4 times = F4(p.time_start) + time_range_range * sample_sets.wide_sample_1d(nums[0], scramble, 0);
                 F4 lens[2] = {sample_sets.wide_sample_2d(0, nums[0], scramble, 1), sample_sets.wide_sample_2d(1, nums[0], scramble, 1)};
-                spawned_wrays.push_back(camera.get_rays(scramble, nums, tcx, tcy, ndcs, times, lens));
+                out.push_back(camera.get_rays(scramble, nums, tcx, tcy, ndcs, times, lens));
                 if (ctr) ctr->paths += 4;
+                if (sink) {
+                    const WRay& w = out.back();
+                    for (int i = 0; i < 4; i++) {
+                        const V3 o = lane(w.origin, i), d = lane(w.dir, i);
+                        const float rec[7] = {o.x, o.y, o.z, d.x, d.y, d.z, w.time.v[i]};
+                        sink->f.insert(sink->f.end(), rec, rec + 7);
+                        sink->u.push_back(x + y * width); sink->u.push_back((uint32_t)w.sample[i]);
+                    }
+                }
             }
         }
+}
+
+/* the tile closure of render_frame_into, src/film.rs:439-627 */
+void integrate_tile(Tile& tile, const World& world, const Camera& camera, const Integrator& integrator,
+                    const Samples& sample_sets, const float* fis, const float* scramble_buf,
+                    const rayn_frame_params& p, Counters* ctr, TraceSink* trace, ShadeSink* shade = nullptr, bool* shade_ok = nullptr) {
+    const size_t VM = p.volume_marches;
+    std::vector<Ray> spawned_rays; std::vector<WRay> spawned_wrays;
+    std::vector<ShadingInfo> wintersections; std::vector<ChannelSample> new_samples;
+    HitStore hit_store(world.hitables.size());
+
+    raygen_tile(tile.b, camera, sample_sets, fis, scramble_buf, p, spawned_wrays, ctr);
 
     for (size_t depth = 0;; depth++) {
         if (spawned_wrays.empty()) break;
@@ -1365,6 +1384,23 @@ int64_t oracle_trace_tile(const rayn_world_desc* wd, const rayn_frame_params* p,
     for (uint64_t i = 0; i < n && i < cap; i++) {
         depth[i] = sink.depth[i]; obj[i] = sink.obj[i]; px[i] = sink.px[i]; py[i] = sink.py[i]; sample[i] = sink.sample[i]; valid[i] = sink.valid[i];
     }
+    return (int64_t)n;
+}
+
+/* The ray-gen loop of ONE tile given by its rectangle [x0, x1) x [y0, y1) (any rectangle inside the film, not only a tile of the reference grid),
+ * through the function integrate_tile calls: per path, in the loop's order (x outer, y inner, packet, lane), out_f = origin, dir, time (7 floats),
+ * out_u = film pixel x + y * width, sample number.  Returns the number of paths (the arrays hold the first `cap` of them), -1 for bad parameters. */
+int64_t oracle_raygen_tile(const rayn_world_desc* wd, const rayn_frame_params* p, const float* s1d, const float* s2d, const float* scramble, const float* fis,
+                           uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint64_t cap, float* out_f, uint32_t* out_u) {
+    if (!wd || !p || !s1d || !s2d || !scramble || !fis || !out_f || !out_u || p->samples == 0) return -1;
+    if (x0 >= x1 || y0 >= y1 || x1 > p->width || y1 > p->height) return -1;
+    Camera camera(wd->camera);
+    Samples sets{(size_t)p->samples * 4, s1d, s2d};
+    std::vector<WRay> rays; RaygenSink sink;
+    raygen_tile(TileBounds{x0, y0, x1, y1}, camera, sets, fis, scramble, *p, rays, nullptr, &sink);
+    const uint64_t n = sink.u.size() / 2, m = n < cap ? n : cap;
+    std::copy(sink.f.begin(), sink.f.begin() + 7 * m, out_f);
+    std::copy(sink.u.begin(), sink.u.begin() + 2 * m, out_u);
     return (int64_t)n;
 }
 

@@ -1,6 +1,8 @@
-/* Stand-alone check of the oracle's shade entries for sanitizer builds (make -C oracle shade_selftest_asan): no Python, no GPU.
+/* Stand-alone check of the oracle's shade and ray-gen entries for sanitizer builds (make -C oracle shade_selftest_asan): no Python, no GPU.
  * Reads a scene blob (rayn_world_desc followed by rayn_frame_params, as oracle_py.dump_scene writes them), builds the tables, records every
  * integrate call of one tile with oracle_trace_shade, runs every depth again through oracle_shade_packets and compares the outputs bit for bit.
+ * Then records the tile's ray-gen loop with oracle_raygen_tile - and a rectangle that is no tile of the grid - and compares every depth-0 lane the
+ * integrator was handed (origin, direction, time) with the recorded ray of its (pixel, sample), bit for bit.
  * Exit status 0 = equal (and, in a sanitizer build, clean). */
 #include "rayn_oracle.cpp"
 
@@ -37,5 +39,44 @@ int main(int argc, char** argv) {
         a = b;
     }
     printf("%lld packets, %zu lanes, %zu differing words\n", (long long)n, lanes, bad);
-    return bad ? 1 : 0;
+    /* the ray-gen export: the rays of this tile, then of an off-grid rectangle that shares the tile's first pixel */
+    const std::vector<TileBounds> grid = build_tiles(p.width, p.height, p.tile_w, p.tile_h);
+    if (tile >= grid.size()) { fprintf(stderr, "tile index out of range\n"); return 1; }
+    const TileBounds b = grid[tile];
+    const uint32_t ew = b.x1 - b.x0, eh = b.y1 - b.y0;
+    const uint64_t np = (uint64_t)ew * eh * spp;
+    std::vector<float> rf(7 * np); std::vector<uint32_t> ru(2 * np);
+    const int64_t nr = oracle_raygen_tile(&wd, &p, s1.data(), s2.data(), scr.data(), fis.data(), b.x0, b.y0, b.x1, b.y1, np, rf.data(), ru.data());
+    if (nr < 0 || (uint64_t)nr != np) { fprintf(stderr, "oracle_raygen_tile: %lld, expected %llu\n", (long long)nr, (unsigned long long)np); return 1; }
+    size_t rbad = 0, rlanes = 0;
+    for (uint64_t j = 0; j < np; j++) { /* x outer, y inner, sample innermost */
+        const uint32_t s = (uint32_t)(j % spp), lp = (uint32_t)(j / spp), x = b.x0 + lp / eh, y = b.y0 + lp % eh;
+        rbad += ru[2 * j] != x + y * p.width; rbad += ru[2 * j + 1] != s;
+    }
+    for (int64_t k = 0; k < n && pk[2 * k] == 0; k++)
+        for (int i = 0; i < 4; i++) {
+            const uint32_t* u = &lane_u[16 * k + 4 * i];
+            if (!u[0]) continue;
+            const uint64_t j = ((uint64_t)u[2] * eh + u[3]) * spp + u[1];
+            if (j >= np) { rbad++; continue; }
+            const float* f = &lane_f[60 * k + 15 * i];
+            const float got[7] = {f[0], f[1], f[2], f[3], f[4], f[5], f[7]};
+            rbad += memcmp(got, &rf[7 * j], sizeof got) != 0;
+            rlanes++;
+        }
+    if (ew > 1 && eh > 1) { /* the same pixels through a smaller rectangle: a ray depends on its pixel and sample, not on the tile it is asked through */
+        const uint64_t ns = (uint64_t)(ew - 1) * (eh - 1) * spp;
+        std::vector<float> sf(7 * ns); std::vector<uint32_t> su(2 * ns);
+        const int64_t m = oracle_raygen_tile(&wd, &p, s1.data(), s2.data(), scr.data(), fis.data(), b.x0, b.y0, b.x1 - 1, b.y1 - 1, ns, sf.data(), su.data());
+        if (m < 0 || (uint64_t)m != ns) { fprintf(stderr, "oracle_raygen_tile (sub-rectangle): %lld\n", (long long)m); return 1; }
+        for (uint64_t j = 0; j < ns; j++) {
+            const uint32_t s = (uint32_t)(j % spp), lp = (uint32_t)(j / spp), lx = lp / (eh - 1), ly = lp % (eh - 1);
+            const uint64_t full = ((uint64_t)lx * eh + ly) * spp + s;
+            rbad += memcmp(&sf[7 * j], &rf[7 * full], 28) != 0; rbad += su[2 * j] != ru[2 * full]; rbad += su[2 * j + 1] != ru[2 * full + 1];
+        }
+    }
+    if (oracle_raygen_tile(&wd, &p, s1.data(), s2.data(), scr.data(), fis.data(), b.x0, b.y0, p.width + 1, b.y1, np, rf.data(), ru.data()) != -1) rbad++; /* outside the film */
+    printf("%llu ray-gen paths, %zu depth-0 lanes compared, %zu differing\n", (unsigned long long)np, rlanes, rbad);
+    if (rlanes == 0) { fprintf(stderr, "no depth-0 lane to compare\n"); return 1; }
+    return bad || rbad ? 1 : 0;
 }

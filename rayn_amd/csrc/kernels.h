@@ -71,7 +71,9 @@ struct Nee {
 // kernel takes its element count from here, grids are sized for the batch's upper bound and loop (grid-stride) or exit.
 struct DCtl {
     uint32_t q_groups;     // ray queue size in 64-slot groups   (k_raygen, then k_tile_prefix of the repack)
-    uint32_t q_valid;      // valid entries in it
+    uint32_t q_valid;      // entries of it that are not known to be padding: k_raygen writes the pool size, which counts the padding slots at the end
+                           // of every tile's segment (an upper bound of the paths); k_tile_prefix of the repack writes the exact survivor count.
+                           // A statistic: no kernel and no host code reads it
     uint32_t b_groups;     // binned queue size in groups        (k_tile_prefix of the bin stage)
     uint32_t b_valid;      // hits = valid binned entries
     uint32_t head_extend;  // persistent-kernel queue heads, reset on device between uses

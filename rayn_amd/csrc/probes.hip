@@ -1,4 +1,4 @@
-// probes.hip — the test probes of the C ABI (rayn_hip_probe_*): per-lane device primitives, the PRODUCT march kernels, the PRODUCT queue stages and the PRODUCT film resolve on caller data.
+// probes.hip — the test probes of the C ABI (rayn_hip_probe_*): per-lane device primitives, the PRODUCT march kernels, the PRODUCT queue stages, the PRODUCT shade and ray-generation stages and the PRODUCT film resolve on caller data.
 // Test infrastructure; defines no kernels (kernels.hip holds the probe kernels).
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -530,6 +530,99 @@ int rayn_hip_probe_resolve(rayn_ctx* ctx, uint32_t width, uint32_t spp, uint32_t
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out_color, o_color, NP * 12, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_alpha, o_alpha, NP * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out_background, o_bg, NP * 12, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_normal, o_normal, NP * 12, hipMemcpyDeviceToHost));
+    return RAYN_OK;
+}
+
+// The ray-generation stage (k_pack_tables, k_batch_setup, k_raygen) through the product launchers, as run_worker and prepare_frame launch them, on caller-built
+// tables and a caller-built tile list.  The probe owns every device buffer; every output buffer starts filled with `sentinel` (term_info with its low byte)
+// and is `surplus` slots longer than the pool (the group tables surplus / 64 words, the tile tables 2 words, the records 64 floats), so a write beyond the
+// pool, into a padding slot or into term_key shows.  Everything the kernels would index is checked here first (rayn_hip.h lists it).
+int rayn_hip_probe_raygen(rayn_ctx* ctx, const rayn_frame_params* p, const float* samples_1d, uint64_t n_samples_1d, const float* samples_2d, uint64_t n_samples_2d,
+                          const float* scramble, uint64_t n_scramble, const float* fis_table, uint32_t n_tiles, const uint32_t* tiles, uint32_t n_pool,
+                          uint32_t surplus, uint32_t sentinel, float* out_geo0, float* out_geo1, float* out_col0, float* out_col1, float* out_aov,
+                          uint32_t* out_term_key, uint8_t* out_term_info, uint32_t* out_q, uint32_t* out_pgrp_tile, uint32_t* out_tgb, uint32_t* out_tgc,
+                          uint32_t* out_ctl, float* out_records) {
+    int rc = validate(ctx, p);
+    if (rc) return rc;
+    if (!samples_1d || !samples_2d || !scramble || !fis_table || !tiles || !out_geo0 || !out_geo1 || !out_col0 || !out_col1 || !out_aov || !out_term_key ||
+        !out_term_info || !out_q || !out_pgrp_tile || !out_tgb || !out_tgc || !out_ctl || !out_records)
+        return fail(ctx, RAYN_ERR_INVALID_ARG, "null buffer");
+    const uint32_t spp = p->samples * 4; // validate: samples in 1..4096, so spp is a multiple of 4 in 4..16384
+    const uint64_t n_pixels = (uint64_t)p->width * p->height;
+    const size_t n1 = (size_t)spp * rayn_sets_1d(p->max_bounces, p->volume_marches), n2 = (size_t)spp * 2 * rayn_sets_2d(p->max_bounces, p->volume_marches);
+    if (n_samples_1d != n1 || n_samples_2d != n2) return fail(ctx, RAYN_ERR_INVALID_ARG, "a sample table is not sized by rayn_sets_1d / rayn_sets_2d for the frame's bounces and volume marches");
+    if (n_scramble != n_pixels) return fail(ctx, RAYN_ERR_INVALID_ARG, "the scramble does not hold width * height entries");
+    if (n_tiles == 0 || n_tiles > (1u << 20)) return fail(ctx, RAYN_ERR_INVALID_ARG, "n_tiles outside 1..2^20");
+    if (n_pool == 0 || n_pool % 64 || n_pool > (1u << 27)) return fail(ctx, RAYN_ERR_INVALID_ARG, "n_pool is 0, not a multiple of 64 or above 2^27");
+    if (surplus < 128 || surplus % 64 || surplus > (1u << 20)) return fail(ctx, RAYN_ERR_INVALID_ARG, "surplus is not a multiple of 64 in 128..2^20");
+    if (sentinel == INVALID || sentinel < n_pool || (sentinel & 0xFFu) == TERM_NONE)
+        return fail(ctx, RAYN_ERR_INVALID_ARG, "the sentinel must be neither INVALID nor a pool index, and its low byte not TERM_NONE");
+    std::vector<DTile> ht(n_tiles);
+    {
+        std::vector<uint8_t> owned(n_pool / 64, 0);
+        size_t covered = 0;
+        for (uint32_t t = 0; t < n_tiles; t++) {
+            const uint32_t* w = tiles + 8 * (size_t)t;
+            DTile& T = ht[t];
+            T.x0 = w[0]; T.y0 = w[1]; T.ew = w[2]; T.eh = w[3]; T.pool_base = w[4]; T.n_paths = w[5]; T.film_base = w[6]; T.film_packed = w[7];
+            const uint64_t npx = (uint64_t)T.ew * T.eh;
+            if (npx == 0 || npx > MAX_TILE_PIXELS) return fail(ctx, RAYN_ERR_INVALID_ARG, "a tile has no pixel or more than 1024 pixels");
+            if ((uint64_t)T.x0 + T.ew > p->width || (uint64_t)T.y0 + T.eh > p->height) return fail(ctx, RAYN_ERR_INVALID_ARG, "a tile does not lie inside width x height");
+            if (T.n_paths != npx * spp) return fail(ctx, RAYN_ERR_INVALID_ARG, "a tile's n_paths is not ew * eh * spp");
+            if (T.pool_base % 64) return fail(ctx, RAYN_ERR_INVALID_ARG, "a tile's pool_base is not a multiple of 64");
+            const uint64_t g0 = T.pool_base / 64, groups = ((uint64_t)T.n_paths + 63) / 64;
+            if (g0 + groups > n_pool / 64) return fail(ctx, RAYN_ERR_INVALID_ARG, "a tile's 64-padded segment ends beyond n_pool");
+            for (uint64_t g = g0; g < g0 + groups; g++) {
+                if (owned[g]) return fail(ctx, RAYN_ERR_INVALID_ARG, "the 64-padded segments of two tiles overlap");
+                owned[g] = 1;
+            }
+            covered += groups;
+        }
+        if (covered != n_pool / 64) return fail(ctx, RAYN_ERR_INVALID_ARG, "the tiles' 64-padded segments do not cover [0, n_pool): k_raygen would read an unwritten pgrp_tile word");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    DScene hs;
+    rc = build_scene(ctx, ctx->cfg->world, *p, &hs);
+    if (rc) return rc;
+    const KernelSet K = kernel_set(ctx->cfg->fma_policy);
+    const uint32_t rec_stride = (8 + hs.n2) / 4, rec_depths = p->max_bounces + 1;
+    const size_t rec_words = (size_t)rec_depths * spp * rec_stride * 4 + 64;
+    const size_t NP = (size_t)n_pool + surplus, NG = NP / 64, NT = (size_t)n_tiles + 2;
+    DevBuf d_s1, d_s2, d_scr, d_fis, d_rec, d_tiles, d_g0, d_g1, d_c0, d_c1, d_aov, d_key, d_info, d_q, d_pgrp, d_tgb, d_tgc, d_ctl;
+#define OOMCHK(expr) do { if ((expr) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAYN_ERR_OOM, "hipMalloc of the ray-gen probe's buffers failed"); } } while (0)
+    OOMCHK(d_s1.alloc(n1 * 4)); OOMCHK(d_s2.alloc(n2 * 4)); OOMCHK(d_scr.alloc(n_pixels * 4)); OOMCHK(d_fis.alloc(RAYN_FIS_TABLE_SIZE * 4)); OOMCHK(d_rec.alloc(rec_words * 4));
+    OOMCHK(d_tiles.alloc((size_t)n_tiles * sizeof(DTile))); OOMCHK(d_g0.alloc(NP * 16)); OOMCHK(d_g1.alloc(NP * 16)); OOMCHK(d_c0.alloc(NP * 16)); OOMCHK(d_c1.alloc(NP * 16));
+    OOMCHK(d_aov.alloc(NP * 16)); OOMCHK(d_key.alloc(NP * 4)); OOMCHK(d_info.alloc(NP)); OOMCHK(d_q.alloc(NP * 4)); OOMCHK(d_pgrp.alloc(NG * 4));
+    OOMCHK(d_tgb.alloc(NT * 4)); OOMCHK(d_tgc.alloc(NT * 4)); OOMCHK(d_ctl.alloc(sizeof(DCtl)));
+#undef OOMCHK
+    HIPCHK(hipMemcpy(d_s1.p, samples_1d, n1 * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_s2.p, samples_2d, n2 * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_scr.p, scramble, n_pixels * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_fis.p, fis_table, RAYN_FIS_TABLE_SIZE * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_tiles.p, ht.data(), (size_t)n_tiles * sizeof(DTile), hipMemcpyHostToDevice));
+    struct Fill { DevBuf* b; size_t words; } fills[] = {{&d_rec, rec_words}, {&d_g0, NP * 4}, {&d_g1, NP * 4}, {&d_c0, NP * 4}, {&d_c1, NP * 4}, {&d_aov, NP * 4}, {&d_key, NP},
+                                                        {&d_q, NP}, {&d_pgrp, NG}, {&d_tgb, NT}, {&d_tgc, NT}, {&d_ctl, sizeof(DCtl) / 4}};
+    for (const Fill& f : fills) HIPCHK(hipMemsetD32((hipDeviceptr_t)f.b->p, (int)sentinel, f.words));
+    HIPCHK(hipMemset(d_info.p, (int)(sentinel & 0xFFu), NP));
+    HIPCHK(hipMemcpy(ctx->d_scene, &hs, sizeof hs, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize()); // the fills above ran on the null stream
+    hipStream_t s = ctx->stream;
+    const Tables tab{d_s1.as<float>(), d_s2.as<float>(), d_fis.as<float>(), d_rec.as<float4>(), rec_stride};
+    K.pack_tables(s, tab, d_rec.as<float4>(), spp, rec_depths, hs.n1, hs.n2);
+    Pool pool;
+    pool.geo0 = d_g0.as<float4>(); pool.geo1 = d_g1.as<float4>(); pool.col0 = d_c0.as<float4>(); pool.col1 = d_c1.as<float4>(); pool.aov = d_aov.as<float4>();
+    pool.term_key = d_key.as<uint32_t>(); pool.term_info = d_info.as<uint8_t>();
+    K.batch_setup(s, d_tiles.as<DTile>(), n_tiles, d_pgrp.as<uint32_t>(), d_tgb.as<uint32_t>(), d_tgc.as<uint32_t>());
+    K.raygen(s, ctx->d_scene, tab, d_scr.as<float>(), d_tiles.as<DTile>(), d_pgrp.as<uint32_t>(), pool, d_q.as<uint32_t>(), n_pool, d_ctl.as<DCtl>());
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out_geo0, d_g0.p, NP * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_geo1, d_g1.p, NP * 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_col0, d_c0.p, NP * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_col1, d_c1.p, NP * 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_aov, d_aov.p, NP * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_term_key, d_key.p, NP * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_term_info, d_info.p, NP, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_q, d_q.p, NP * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_pgrp_tile, d_pgrp.p, NG * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_tgb, d_tgb.p, NT * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_tgc, d_tgc.p, NT * 4, hipMemcpyDeviceToHost));
+    static_assert(sizeof(DCtl) >= 32, "the eight 32-bit words of DCtl");
+    HIPCHK(hipMemcpy(out_ctl, d_ctl.p, 32, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_records, d_rec.p, rec_words * 4, hipMemcpyDeviceToHost));
     return RAYN_OK;
 }
 

@@ -587,6 +587,32 @@ class Context:
         self._chk(self._L.rayn_hip_probe_shade_limits(self.h, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
+    RAYGEN_CTL = ("q_groups", "q_valid", "b_groups", "b_valid", "head_extend", "job_count", "head_shadow", "overflow")
+
+    def probe_raygen(self, params, tables, tiles, n_pool, surplus=128, sentinel=0xC0FFEE5A, check=True):
+        """rayn_hip_probe_raygen (rayn_hip.h): k_pack_tables, k_batch_setup and k_raygen on the caller's tables and the tile list `tiles` [n_tiles, 8] uint32.
+        -> (rc, dict): geo0, geo1, col0, col1, aov [n_pool + surplus, 4] float32, term_key, term_info, q [n_pool + surplus], pgrp_tile [(n_pool + surplus) / 64],
+        tgb, tgc [n_tiles + 2], ctl (dict of the eight words, RAYGEN_CTL), records [(max_bounces + 1) * spp, rec_stride * 4] float32 and records_surplus [64].
+        Every array is handed over zeroed, so a refused call leaves zeros.  check=False returns a non-zero rc instead of raising."""
+        s1, s2, scr, fis = [np.ascontiguousarray(t, np.float32) for t in tables]
+        tiles = np.ascontiguousarray(tiles, np.uint32).reshape(-1, 8)
+        n_tiles, NP = tiles.shape[0], n_pool + surplus
+        out = {k: np.zeros((NP, 4), np.float32) for k in ("geo0", "geo1", "col0", "col1", "aov")}
+        out["term_key"], out["term_info"], out["q"] = np.zeros(NP, np.uint32), np.zeros(NP, np.uint8), np.zeros(NP, np.uint32)
+        out["pgrp_tile"], out["tgb"], out["tgc"] = np.zeros(max(NP // 64, 1), np.uint32), np.zeros(n_tiles + 2, np.uint32), np.zeros(n_tiles + 2, np.uint32)
+        ctl = np.zeros(8, np.uint32)
+        spp, stride = 4 * params.samples, 8 + 12 + 8 * params.volume_marches
+        recs = np.zeros((params.max_bounces + 1) * spp * stride + 64, np.float32)
+        up, bp = (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8)))
+        rc = self._L.rayn_hip_probe_raygen(self.h, C.byref(params), _fp(s1), s1.size, _fp(s2), s2.size, _fp(scr), scr.size, _fp(fis), n_tiles, up(tiles), n_pool, surplus,
+                                           sentinel, *[_fp(out[k]) for k in ("geo0", "geo1", "col0", "col1", "aov")], up(out["term_key"]), bp(out["term_info"]),
+                                           up(out["q"]), up(out["pgrp_tile"]), up(out["tgb"]), up(out["tgc"]), up(ctl), _fp(recs))
+        if check:
+            self._chk(rc)
+        out["ctl"] = dict(zip(self.RAYGEN_CTL, ctl.tolist()))
+        out["records"], out["records_surplus"] = recs[:-64].reshape(-1, stride), recs[-64:]
+        return rc, out
+
     def probe_shade(self, params, tables, depth, ref, geo0, geo1, col0, col1, max_slots=None, nee_cap=None, sentinel=0xC0FFEE5A, check=True):
         """rayn_hip_probe_shade (rayn_hip.h): the shade stage of one depth on a binned queue `ref` [n_slots] and the pool records geo0 / geo1 / col0 / col1
         [n_pool, 4] float32 in the pool's own encoding.  -> (rc, dict): the pool as the stage left it (geo0, geo1, col0, col1, aov [n_pool, 4], term_key, term_info

@@ -30,7 +30,40 @@ def smin(a, b):
     return np.where(a < b, a, b).astype(f32)
 
 
-def mul_add(a, b, c):  # A1: unfused
+FUSED = [False]  # A1: unfused unless a caller states the +fma build (fused_policy)
+
+
+class fused_policy:
+    """`with fused_policy(True):` states f32::mul_add as ONE rounding (rayn built with +fma) inside the block; the default is the x86-64 build's two"""
+    def __init__(self, on):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.was, FUSED[0] = FUSED[0], self.on
+
+    def __exit__(self, *exc):
+        FUSED[0] = self.was
+
+
+def fma32(a, b, c):
+    """a * b + c rounded once to binary32: the product of two binary32 is exact in binary64; the binary64 sum is made sticky (round to odd, from the exact
+    error of the addition) before the final rounding, so the two roundings equal one (binary64 carries more than 2 * 24 + 2 bits)"""
+    a, b, c = np.broadcast_arrays(np.asarray(a, f32), np.asarray(b, f32), np.asarray(c, f32))
+    with np.errstate(all="ignore"):
+        pr = a.astype(np.float64) * b.astype(np.float64)
+        c64 = c.astype(np.float64)
+        sm = pr + c64
+        bb = sm - pr
+        err = (pr - (sm - bb)) + (c64 - bb)  # TwoSum: pr + c64 = sm + err exactly
+        even = (sm.view(np.int64) & 1) == 0
+        fix = np.isfinite(sm) & (err != 0) & even
+        odd = np.nextafter(sm, np.where(err > 0, np.inf, -np.inf))
+        return np.where(fix, odd, sm).astype(f32)
+
+
+def mul_add(a, b, c):
+    if FUSED[0]:
+        return fma32(a, b, c)
     return (a * b + c).astype(f32)
 
 
@@ -402,6 +435,106 @@ def fis_sample(inv, u):  # FilterImportanceSampler::sample, src/filter.rs:222-23
     return f32(mult * f32(f32(inv[idx] * f32(f32(1.0) - t)) + f32(inv[idx + 1] * t)))
 
 
+def fis_sample_v(inv, u, mutant=None):
+    """fis_sample over an array of lanes (the same operations per lane)"""
+    inv = np.asarray(inv, f32)
+    with np.errstate(all="ignore"):
+        u = (f32(2.0) * (u - f32(0.5)).astype(f32)).astype(f32)
+        mult = np.where((u <= 0) if mutant == "mult_le0" else (u < 0), f32(-1.0), f32(1.0)).astype(f32)
+        u = np.abs(u)
+        u = np.where(u > 0, u, f32(0.0)).astype(f32)       # .max(0.0): a NaN becomes 0
+        cap = f32(1.0) if mutant == "clamp_one" else f32(0.99999)
+        u = np.where(u < cap, u, cap).astype(f32)           # .min(0.99999)
+        idx_full = (u * f32(511.0)).astype(f32)
+        idx = np.floor(idx_full).astype(np.int64)
+        t = fract(idx_full)
+        if mutant == "clamp_one":
+            inv = np.concatenate([inv, np.zeros(1, f32)])   # the wrong clamp reads one entry past the table
+        lo, hi = (inv[idx + 1], inv[idx]) if mutant == "lerp_swapped" else (inv[idx], inv[idx + 1])
+        return (mult * ((lo * (f32(1.0) - t).astype(f32)).astype(f32) + (hi * t).astype(f32)).astype(f32)).astype(f32)
+
+
+def camera_constants(cam):
+    """PinholeCamera::new / ThinLensCamera::new / OrthographicCamera::new -> (half_w, half_h, full_w, full_h, half_pixel)"""
+    res_w, res_h = f32(cam.res_w), f32(cam.res_h)
+    if cam.kind in (0, 1):  # src/camera.rs:53-72,134-157
+        theta = f32(f32(f32(cam.vfov_or_size) * PI) / f32(180.0))
+        half_h = f32(math.tan(float(f32(theta / f32(2.0)))))
+        half_w = f32(f32(res_w / res_h) * half_h)
+        return half_w, half_h, half_w, half_h, f32(half_h / res_h)
+    vsz = f32(cam.vfov_or_size)  # src/camera.rs:228-240
+    full_w, full_h = f32(vsz * f32(res_w / res_h)), vsz
+    return f32(full_w / f32(2.0)), f32(full_h / f32(2.0)), full_w, full_h, f32(f32(vsz / res_h) / f32(2.0))
+
+
+def raygen(cam, W, H, nspp, time_start, time_end, tabs, xs, ys, sn, mutant=None):
+    """The ray-gen loop of the tile closure, src/film.rs:456-529 (+ sample_uv :695-709, Samples::sample_*, src/sampler.rs:62-110, FilterImportanceSampler::sample,
+    src/filter.rs:222-235, Camera::get_rays), for the paths (pixel xs, ys; sample sn) given as arrays - the loop visits x outer, y inner, sample innermost, and four
+    consecutive samples of a pixel are one packet whose lane 0 dates the camera's closures.  -> dict: scr, time, o, d (lists of three arrays).
+    `mutant` names ONE wrong reading (tests/raygen_np.py MUTANTS); None is the statement."""
+    s1d, s2d, scramble, fis = [np.asarray(t, f32) for t in tabs]
+    half_w, half_h, full_w, full_h, _ = camera_constants(cam)
+    xs, ys, sn = np.asarray(xs, np.int64), np.asarray(ys, np.int64), np.asarray(sn, np.int64)
+    n = len(xs)
+
+    def cam_param(base, vel, bit, t0):  # WSequenced for a camera parameter: constant, or the closure |t| base + vel * t at lane 0's time
+        if not (cam.animated & bit):
+            return splat((base.x, base.y, base.z), n)
+        return [(f32((base.x, base.y, base.z)[c]) + (f32((vel.x, vel.y, vel.z)[c]) * t0).astype(f32)).astype(f32) for c in range(3)]
+
+    def samp1(set_, sample, scr):
+        return fract((s1d[sample + nspp * set_] + scr).astype(f32))
+
+    def samp2(dim, set_, sample, scr):
+        return fract((s2d[dim + sample * 2 + nspp * 2 * set_] + scr).astype(f32))
+
+    ndc = (f32(f32(1.0) / f32(W)), f32(f32(1.0) / f32(H)))
+    with np.errstate(all="ignore"):
+        pix = (ys + xs * H) % (W * H) if mutant == "pix_transposed" else xs + ys * W
+        scr = scramble[pix].astype(f32)
+        u0, u1 = samp2(0, 0, sn, scr), samp2(1, 0, sn, scr)
+        fx, fy = fis_sample_v(fis, u0, mutant), fis_sample_v(fis, u1, mutant)
+        half = f32(0.0) if mutant == "no_half" else f32(0.5)
+        uvx = (ndc[0] * ((xs.astype(f32) + half).astype(f32) + fx).astype(f32)).astype(f32)
+        uvy = (ndc[1] * ((ys.astype(f32) + half).astype(f32) + fy).astype(f32)).astype(f32)
+        trange = f32(f32(time_end) - f32(time_start))
+        time = (f32(time_start) + (trange * samp1(0, sn, scr)).astype(f32)).astype(f32)
+        # lane 0 of the ray-gen packet (4 consecutive samples of one pixel)
+        t0 = time if mutant == "own_lane_time" else (f32(time_start) + (trange * samp1(0, (sn // 4) * 4, scr)).astype(f32)).astype(f32)
+        org = cam_param(cam.origin, cam.origin_vel, 1, t0)
+        at, up = cam_param(cam.at, cam.at_vel, 2, t0), cam_param(cam.up, cam.up_vel, 4, t0)
+        if cam.kind == 0:  # PinholeCamera::get_rays, src/camera.rs:81-114
+            bw = normalized(vsub(org, at))
+            bu = normalized(cross(up, bw))
+            bv = cross(bw, bu)
+            ll = vsub(vsub(vsub(org, vscale(bu, half_w)), vscale(bv, half_h)), bw)
+            horiz = vscale(vscale(vscale(bu, half_w), f32(2.0)), uvx)
+            verti = vscale(vscale(vscale(bv, half_h), f32(2.0)), uvy)
+            ray_o, ray_d = org, normalized(vsub(vadd(vadd(ll, horiz), verti), org))
+        elif cam.kind == 1:  # ThinLensCamera::get_rays, src/camera.rs:168-208; lens sample = 2-D set 1 (src/film.rs:520-523)
+            focus = cam_param(cam.focus, cam.focus_vel, 8, t0)
+            fd = mag(vsub(focus, org))
+            bw = normalized(vsub(org, at))
+            bu = normalized(cross(up, bw))
+            bv = cross(bw, bu)
+            ll = vsub(vsub(vsub(org, vscale(vscale(bu, half_w), fd)), vscale(vscale(bv, half_h), fd)), vscale(bw, fd))
+            horiz = vscale(vscale(vscale(vscale(bu, half_w), fd), f32(2.0)), uvx)
+            verti = vscale(vscale(vscale(vscale(bv, half_h), fd), f32(2.0)), uvy)
+            lens_set = 0 if mutant == "lens_set0" else 1
+            rdx, rdy = concentric_circle_map(samp2(0, lens_set, sn, scr), samp2(1, lens_set, sn, scr))
+            rdx, rdy = (rdx * f32(cam.aperture)).astype(f32), (rdy * f32(cam.aperture)).astype(f32)
+            ray_o = vadd(org, vadd(vscale(bu, rdx), vscale(bv, rdy)))
+            ray_d = normalized(vsub(vadd(vadd(ll, horiz), verti), ray_o))
+        else:  # OrthographicCamera::get_rays, src/camera.rs:249-280
+            bw = normalized(vsub(at, org))
+            bu = normalized(cross(bw, up))
+            bv = cross(bu, bw)
+            ll = vsub(vsub(org, vscale(bu, half_w)), vscale(bv, half_h))
+            ray_o = vadd(ll, vadd(vscale(vscale(bu, uvx), full_w), vscale(vscale(bv, uvy), full_h)))
+            ray_d = bw
+    return {"scr": scr, "time": time, "o": ray_o, "d": ray_d, "pix": pix}
+
+
 def render(wd, p, tabs):
     """-> (film dict of float32 arrays like the oracle's, counters dict)"""
     s1d, s2d, scramble, fis = [np.asarray(t, f32) for t in tabs]
@@ -409,27 +542,10 @@ def render(wd, p, tabs):
     nspp, B, VM = 4 * samples, int(p.max_bounces), int(p.volume_marches)
     nl = int(wd.n_lights)
     cam = wd.camera
-    res_w, res_h = f32(cam.res_w), f32(cam.res_h)
-    if cam.kind in (0, 1):  # PinholeCamera::new / ThinLensCamera::new, src/camera.rs:53-72,134-157
-        theta = f32(f32(f32(cam.vfov_or_size) * PI) / f32(180.0))
-        half_h = f32(math.tan(float(f32(theta / f32(2.0)))))
-        half_w = f32(f32(res_w / res_h) * half_h)
-        half_pixel = f32(half_h / res_h)
-    else:  # OrthographicCamera::new, src/camera.rs:228-240
-        vsz = f32(cam.vfov_or_size)
-        full_w, full_h = f32(vsz * f32(res_w / res_h)), vsz
-        half_w, half_h = f32(full_w / f32(2.0)), f32(full_h / f32(2.0))
-        half_pixel = f32(f32(vsz / res_h) / f32(2.0))
-
-    def cam_param(base, vel, bit, t0):  # WSequenced for a camera parameter: constant, or the closure |t| base + vel * t at lane 0's time
-        n = len(t0)
-        if not (cam.animated & bit):
-            return splat((base.x, base.y, base.z), n)
-        return [(f32((base.x, base.y, base.z)[c]) + (f32((vel.x, vel.y, vel.z)[c]) * t0).astype(f32)).astype(f32) for c in range(3)]
+    half_pixel = camera_constants(cam)[4]
 
     film = {"color": np.zeros((H, W, 3), f32), "alpha": np.zeros((H, W), f32), "background": np.zeros((H, W, 3), f32), "normal": np.zeros((H, W, 3), f32)}
     ctr = {"paths": 0, "segments": 0}
-    ndc = (f32(f32(1.0) / f32(W)), f32(f32(1.0) / f32(H)))
     rho_t = f32(wd.coeff_extinction) if wd.has_extinction else None
     rho_s = f32(wd.coeff_scattering) if wd.has_scattering else None
     n1, n2 = 3 + VM, 12 + 8 * VM
@@ -452,44 +568,8 @@ def render(wd, p, tabs):
             xs, ys, sn = xs.reshape(-1), ys.reshape(-1), sn.reshape(-1)
             n = len(xs)
             ctr["paths"] += n
-            scr = scramble[xs + ys * W].astype(f32)
-            u0, u1 = samp2(0, 0, sn, scr), samp2(1, 0, sn, scr)
-            fx = np.array([fis_sample(fis, v) for v in u0], f32)
-            fy = np.array([fis_sample(fis, v) for v in u1], f32)
-            uvx = (ndc[0] * ((xs.astype(f32) + f32(0.5)).astype(f32) + fx).astype(f32)).astype(f32)
-            uvy = (ndc[1] * ((ys.astype(f32) + f32(0.5)).astype(f32) + fy).astype(f32)).astype(f32)
-            time = (f32(p.time_start) + (f32(f32(p.time_end) - f32(p.time_start)) * samp1(0, sn, scr)).astype(f32)).astype(f32)
-            t0 = time[(np.arange(n) // 4) * 4]  # lane 0 of the ray-gen packet (4 consecutive samples of one pixel)
-            org = cam_param(cam.origin, cam.origin_vel, 1, t0)
-            at, up = cam_param(cam.at, cam.at_vel, 2, t0), cam_param(cam.up, cam.up_vel, 4, t0)
-            if cam.kind == 0:  # PinholeCamera::get_rays, src/camera.rs:81-114
-                bw = normalized(vsub(org, at))
-                bu = normalized(cross(up, bw))
-                bv = cross(bw, bu)
-                ll = vsub(vsub(vsub(org, vscale(bu, half_w)), vscale(bv, half_h)), bw)
-                horiz = vscale(vscale(vscale(bu, half_w), f32(2.0)), uvx)
-                verti = vscale(vscale(vscale(bv, half_h), f32(2.0)), uvy)
-                ray_o, ray_d = org, normalized(vsub(vadd(vadd(ll, horiz), verti), org))
-            elif cam.kind == 1:  # ThinLensCamera::get_rays, src/camera.rs:168-208; lens sample = 2-D set 1 (src/film.rs:520-523)
-                focus = cam_param(cam.focus, cam.focus_vel, 8, t0)
-                fd = mag(vsub(focus, org))
-                bw = normalized(vsub(org, at))
-                bu = normalized(cross(up, bw))
-                bv = cross(bw, bu)
-                ll = vsub(vsub(vsub(org, vscale(vscale(bu, half_w), fd)), vscale(vscale(bv, half_h), fd)), vscale(bw, fd))
-                horiz = vscale(vscale(vscale(vscale(bu, half_w), fd), f32(2.0)), uvx)
-                verti = vscale(vscale(vscale(vscale(bv, half_h), fd), f32(2.0)), uvy)
-                rdx, rdy = concentric_circle_map(samp2(0, 1, sn, scr), samp2(1, 1, sn, scr))
-                rdx, rdy = (rdx * f32(cam.aperture)).astype(f32), (rdy * f32(cam.aperture)).astype(f32)
-                ray_o = vadd(org, vadd(vscale(bu, rdx), vscale(bv, rdy)))
-                ray_d = normalized(vsub(vadd(vadd(ll, horiz), verti), ray_o))
-            else:  # OrthographicCamera::get_rays, src/camera.rs:249-280
-                bw = normalized(vsub(at, org))
-                bu = normalized(cross(bw, up))
-                bv = cross(bu, bw)
-                ll = vsub(vsub(org, vscale(bu, half_w)), vscale(bv, half_h))
-                ray_o = vadd(ll, vadd(vscale(vscale(bu, uvx), full_w), vscale(vscale(bv, uvy), full_h)))
-                ray_d = bw
+            rg = raygen(cam, W, H, nspp, p.time_start, p.time_end, (s1d, s2d, scramble, fis), xs, ys, sn)
+            scr, time, ray_o, ray_d = rg["scr"], rg["time"], rg["o"], rg["d"]
             rays = {"time": time, "o": ray_o, "d": ray_d, "rad": splat((0, 0, 0), n), "thr": splat((1, 1, 1), n),
                     "tx": (xs - x0).astype(np.int64), "ty": (ys - y0).astype(np.int64), "valid": np.ones(n, bool), "scr": scr, "samp": sn.astype(np.int64)}
             sums = {"color": np.zeros((ew, eh, 3), f32), "alpha": np.zeros((ew, eh), f32), "background": np.zeros((ew, eh, 3), f32), "normal": np.zeros((ew, eh, 3), f32)}
