@@ -67,7 +67,7 @@ typedef struct {
     /* RAYN_HITABLE_TRACED_SDF: TracedSDF::new(sdf, material), src/sdf.rs:17-21 */
     uint32_t sdf_kind;   /* rayn_sdf_kind */
     uint32_t iterations; /* MandelBox::new(iterations, ..), src/sdf.rs:114 */
-    float box_side;      /* BoxFold::new(side_length), src/sdf.rs:151 */
+    float box_side;      /* BoxFold::new(side_length), src/sdf.rs:151.  Any value: a negative, -0 or NaN side folds as the reference's min(max(p, -l), l) does (the general arm) */
     float min_radius;    /* SphereFold::new(min_radius, fixed_radius), src/sdf.rs:172 */
     float fixed_radius;
     float scale;         /* MandelBox scale, src/sdf.rs:114 */
@@ -846,6 +846,19 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
 
 /* ---- test probes on caller data (HOST pointers), so that the parity tests can compare single functions with the CPU oracle lane for lane:
  *   rayn_hip_probe_sdf_dist   SDF::dist (src/sdf.rs:125-140) of one TracedSDF, a per-lane device function;
+ *   rayn_hip_probe_sdf_dist_as  the same function in ONE named instantiation and division arm: sdf_dist<false, sdfk> of hitable hitable_index with the scale the march
+ *                             kernels hand it for a packet of lane-0 time t0 (sdf_scale: scale + scale_vel * t0 when scale_vel != 0).  sdfk = -1 (the kind is read
+ *                             from the object), the object's own RAYN_SDF_* kind, or 100 (the 12-iteration MandelBox with the short division, both known at compile
+ *                             time).  fast_div = the division arm (0 IEEE '/' and the reference's clamp, 1 div_nr, 2 div_short); it may only LOWER the value the
+ *                             upload gave the object (rayn_hip_probe_scene_dispatch): the lower arms are the more general ones.  RAYN_ERR_INVALID_ARG with a text,
+ *                             nothing launched and out untouched, for: an sdfk outside {-1, 0, 1, 2, 100}; an sdfk >= 0 that is not the object's kind; sdfk = 100 on
+ *                             an object that is not a 12-iteration MandelBox with fast_div 2, or with a fast_div argument other than 2 (that instantiation has no
+ *                             other arm); a fast_div above the object's own; what rayn_hip_probe_sdf_dist rejects.
+ *   rayn_hip_probe_scene_dispatch  what the VALUES of the uploaded world and p decide, through the build_scene and scene_march_kernels a render calls (the upload-time
+ *                             verdict kernel behind fast_div 2 is the only launch): out[0] = the index of the scene's single TracedSDF or -1 (the single-SDF march
+ *                             kernels or the generic ones), out[1] = Tuning::sdf_kind (-1, 0, 1, 2 or 100: the instantiation), out[2] = Tuning::bulb (k_shadow_bulb),
+ *                             out[3] = DScene::anim_spheres (the kernels carry the packet's lane-0 time), out[4 + i] = DHitable::fast_div of hitable i for i <
+ *                             n_hitables and -1 beyond, RAYN_MAX_HITABLES entries.  out holds 4 + RAYN_MAX_HITABLES words.
  *   rayn_hip_probe_extend     HitableStore::add_hits' closest hit (src/hitable.rs:177-198 over Sphere::hit and TracedSDF::hit, src/sdf.rs:59-83) through the
  *                             PRODUCT extend kernel of the uploaded scene (k_extend1, or the generic k_extend of a multi-SDF scene) on a synthetic ray queue of
  *                             the n rays, ray time 0; out_obj 0xFFFFFFFF = none;
@@ -989,6 +1002,9 @@ int rayn_hip_probe_march_limits(const rayn_ctx* ctx, uint32_t* chunk, uint32_t* 
                                 uint32_t* persistent_blocks, uint32_t* bulb_rays);
 int rayn_hip_probe_sdf_dist(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t hitable_index,
                             const float* pts_xyz, float* out, uint32_t n);
+int rayn_hip_probe_sdf_dist_as(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t hitable_index, int32_t sdfk,
+                               uint32_t fast_div, float t0, const float* pts_xyz, float* out, uint32_t n);
+int rayn_hip_probe_scene_dispatch(rayn_ctx* ctx, const rayn_frame_params* p, int32_t* out);
 int rayn_hip_probe_extend(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t depth,
                           const float* org_xyz, const float* dir_xyz, float* out_t,
                           uint32_t* out_obj, uint32_t n);

@@ -199,11 +199,15 @@ def dump_scene(world_desc, params, path):
         f.write(bytes(params))
 
 
-def sdf_dist(hitable, pts, fma=False):
+def sdf_dist(hitable, pts, fma=False, t0=None):
+    """SDF::dist of one TracedSDF per point; t0 = lane 0's time of the calling packet, which only the MandelBox scale extension (scale_vel != 0) reads."""
     L = lib(fma)
     pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
     out = np.zeros(len(pts), np.float32)
-    L.oracle_sdf_dist(C.byref(hitable), _fp(pts), _fp(out), C.c_uint64(len(pts)))
+    if t0 is None:
+        L.oracle_sdf_dist(C.byref(hitable), _fp(pts), _fp(out), C.c_uint64(len(pts)))
+    else:
+        L.oracle_sdf_dist_at(C.byref(hitable), C.c_float(t0), _fp(pts), _fp(out), C.c_uint64(len(pts)))
     return out
 
 

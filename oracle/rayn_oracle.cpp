@@ -1474,6 +1474,16 @@ void oracle_sdf_dist(const rayn_hitable* h, const float* pts, float* out, uint64
         out[i] = t->sdf->dist(W3(F4(pts[3 * i]), F4(pts[3 * i + 1]), F4(pts[3 * i + 2]))).v[0];
     }
 }
+/* the same with the SDF's closure-sequenced parameters evaluated at t0, lane 0's time of the calling packet (SDF::dist_at: the MandelBox scale extension) */
+void oracle_sdf_dist_at(const rayn_hitable* h, float t0, const float* pts, float* out, uint64_t n) {
+    rayn_world_desc wd; memset(&wd, 0, sizeof wd); wd.n_hitables = 1; wd.hitables[0] = *h;
+    World w(wd, Config{256, 100, 0.5f});
+    const TracedSDF* t = dynamic_cast<const TracedSDF*>(w.hitables[0].get());
+    for (uint64_t i = 0; i < n; i++) {
+        if (!t) { out[i] = dm_nanf(); continue; }
+        out[i] = t->sdf->dist_at(W3(F4(pts[3 * i]), F4(pts[3 * i + 1]), F4(pts[3 * i + 2])), t0).v[0];
+    }
+}
 /* closest hit of the whole world for n rays at 'depth' (threshold closure of src/film.rs:540-551):
  * out_t, out_obj (0xFFFFFFFF = none) — HitableStore::add_hits without the bins. */
 void oracle_closest_hit(const rayn_world_desc* wd, const rayn_frame_params* p, uint32_t depth, const float* org,

@@ -330,6 +330,26 @@ class Context:
         self._chk(self._L.rayn_hip_probe_shade_limits(self.h, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
+    def probe_scene_dispatch(self, params):
+        """rayn_hip_probe_scene_dispatch (rayn_hip.h): what the values of the uploaded world and `params` decide, from the build_scene and scene_march_kernels
+        a render calls.  -> dict: single_sdf (index or -1), sdf_kind (-1, 0, 1, 2, 100), bulb, anim_spheres, fast_div (list, one entry per hitable)."""
+        out = (C.c_int32 * (4 + _abi.MAX_HITABLES))()
+        self._chk(self._L.rayn_hip_probe_scene_dispatch(self.h, C.byref(params), out))
+        v = list(out)
+        return {"single_sdf": v[0], "sdf_kind": v[1], "bulb": v[2], "anim_spheres": v[3], "fast_div": [x for x in v[4:] if x >= 0]}
+
+    def probe_sdf_dist_as(self, params, hitable_index, sdfk, fast_div, pts, t0=0.0, out=None, check=True):
+        """rayn_hip_probe_sdf_dist_as (rayn_hip.h): sdf_dist<false, sdfk> of one TracedSDF in the division arm `fast_div` at the packet time t0, per point of
+        pts [n, 3].  -> (rc, out [n] float32); `out` may be handed in to see that a refused call leaves it alone.  check=False returns a non-zero rc instead of raising."""
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        if out is None:
+            out = np.zeros(len(pts), np.float32)
+        assert out.dtype == np.float32 and out.size == len(pts) and out.flags.c_contiguous
+        rc = self._L.rayn_hip_probe_sdf_dist_as(self.h, C.byref(params), int(hitable_index), int(sdfk), int(fast_div), float(t0), _fp(pts), _fp(out), len(pts))
+        if check:
+            self._chk(rc)
+        return rc, out
+
     RAYGEN_CTL = ("q_groups", "q_valid", "b_groups", "b_valid", "head_extend", "job_count", "head_shadow", "overflow")
 
     def probe_raygen(self, params, tables, tiles, n_pool, surplus=128, sentinel=0xC0FFEE5A, check=True):

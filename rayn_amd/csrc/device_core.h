@@ -294,6 +294,13 @@ RD float div_short(float n, float d) {
     return __builtin_fmaf(__builtin_fmaf(-d, q, n), rc, q);
 }
 
+// clamped(lo, hi) = min(max(q, lo), hi) as the reference's SSE lanes compute it (src/sdf.rs:160-162): maxps(q, lo) = q > lo ? q : lo, minps(t, hi) = t < hi ? t : hi -
+// the second operand whenever the comparison is false, an unordered one included.  Equal to the median of the three only for lo <= hi.
+RD float clamp_ref(float q, float lo, float hi) {
+    const float t = q > lo ? q : lo;
+    return t < hi ? t : hi;
+}
+
 // MandelBox scale at the packet time t0 (EXTENSION, rayn_hip.h: the closure |t| scale + scale_vel * t); constants ignore t0
 RD float sdf_scale(const DHitable& h, float t0) { return h.scale_vel != 0.0f ? h.scale + h.scale_vel * t0 : h.scale; }
 
@@ -311,11 +318,11 @@ RD float sdf_scale(const DHitable& h, float t0) { return h.scale_vel != 0.0f ? h
 //   scale+offset p = p.mul_add(s, p0);  dr = (-dr).mul_add(s, 1)
 // DIV is the quotient R2 / max(r2min, r2) (IEEE '/', div_nr or div_short, chosen by the host per object: DHitable::fast_div),
 // BOX the 2c - p of the box fold (mul_add per policy, or one fma where the product 2c is exact).
-#define RAYN_FOLD_ITER(DIV, BOX)                                          \
+#define RAYN_FOLD_ITER(DIV, BOX, CLAMP)                                   \
     {                                                                     \
-        p.x = BOX(__builtin_amdgcn_fmed3f(p.x, nl, l), p.x);              \
-        p.y = BOX(__builtin_amdgcn_fmed3f(p.y, nl, l), p.y);              \
-        p.z = BOX(__builtin_amdgcn_fmed3f(p.z, nl, l), p.z);              \
+        p.x = BOX(CLAMP(p.x, nl, l), p.x);                                \
+        p.y = BOX(CLAMP(p.y, nl, l), p.y);                                \
+        p.z = BOX(CLAMP(p.z, nl, l), p.z);                                \
         const float r2 = mag_sq(p);                                       \
         if (r2 < frs_eff) { /* not NaN on a folding lane: ONE raw v_max_f32 */ \
             const float m = DIV(frs, vmax_raw(r2, mrs_v));                \
@@ -331,7 +338,13 @@ RD float sdf_scale(const DHitable& h, float t0) { return h.scale_vel != 0.0f ? h
 #define RAYN_BOX_REF(c, q) muladd(c, 2.0f, -(q))
 // |c| <= |l| <= 2^60: the product 2c is exact, so ONE rounding (fma) == the reference's two (mul, add)
 #define RAYN_BOX_FMA(c, q) __builtin_fmaf(c, 2.0f, -(q))
-#define RAYN_FOLD_X4(DIV, BOX) RAYN_FOLD_ITER(DIV, BOX) RAYN_FOLD_ITER(DIV, BOX) RAYN_FOLD_ITER(DIV, BOX) RAYN_FOLD_ITER(DIV, BOX)
+// CLAMP is the clamped(-l, l) of the box fold.  For 0 <= l (finite or not) the median of (p, -l, l) IS min(max(p, -l), l) for every non-NaN p: one v_med3_f32.
+// For l < 0 the reference's form returns l for every p and the median does not, and for a NaN l the reference returns NaN where the hardware's med3 drops
+// it - the host sends such an object (and every other one outside the window) through the fast_div == 0 arm, which states the reference's own order and
+// operand semantics (maxps / minps: the SECOND operand when the comparison is false or unordered) in plain comparisons.
+#define RAYN_CLAMP_MED3(q, lo, hi) __builtin_amdgcn_fmed3f(q, lo, hi)
+#define RAYN_CLAMP_REF(q, lo, hi) clamp_ref(q, lo, hi)
+#define RAYN_FOLD_X4(DIV, BOX) RAYN_FOLD_ITER(DIV, BOX, RAYN_CLAMP_MED3) RAYN_FOLD_ITER(DIV, BOX, RAYN_CLAMP_MED3) RAYN_FOLD_ITER(DIV, BOX, RAYN_CLAMP_MED3) RAYN_FOLD_ITER(DIV, BOX, RAYN_CLAMP_MED3)
 // SDFK >= 0: the SDF kind is known at compile time (the single-SDF march kernels are instantiated per kind: no per-evaluation branch, and the registers
 // / scalar constants of the other SDFs are not carried through the march loop); -1: the kind is read from the object
 // SDFK == SDFK_MANDELBOX_12S: the MandelBox in the shape the reference ships (12 fold iterations, src/setup.rs:44) with the short division verified for its fold
@@ -354,7 +367,8 @@ RD float sdf_dist(const DHitable& h, f3 p, EvalCtr& evals, float scale) {
         float mrs_v = mrs;
         asm("" : "+v"(mrs_v));
         // NaN-free inputs stay NaN-free here and a NaN point yields NaN through '-p', so the hardware
-        // med3/max (IEEE maxNum) forms are bit-identical to the reference's SSE max/min semantics.
+        // med3/max (IEEE maxNum) forms are bit-identical to the reference's SSE max/min semantics - for a box side l >= 0, which is what
+        // the host lets into the fast_div != 0 arms (build_scene); the fast_div == 0 arm clamps in the reference's own form.
         if (BOX12S) {
             RAYN_FOLD_X4(div_short, RAYN_BOX_FMA) RAYN_FOLD_X4(div_short, RAYN_BOX_FMA) RAYN_FOLD_X4(div_short, RAYN_BOX_FMA)
         } else if (h.fast_div == 2) {
@@ -364,11 +378,11 @@ RD float sdf_dist(const DHitable& h, f3 p, EvalCtr& evals, float scale) {
                 i = 12;
             }
             for (; i + 4 <= h.iterations; i += 4) { RAYN_FOLD_X4(div_short, RAYN_BOX_FMA) }
-            for (; i < h.iterations; i++) RAYN_FOLD_ITER(div_short, RAYN_BOX_FMA)
+            for (; i < h.iterations; i++) RAYN_FOLD_ITER(div_short, RAYN_BOX_FMA, RAYN_CLAMP_MED3)
         } else if (h.fast_div) {
-            for (uint32_t i = 0; i < h.iterations; i++) RAYN_FOLD_ITER(div_nr, RAYN_BOX_FMA)
+            for (uint32_t i = 0; i < h.iterations; i++) RAYN_FOLD_ITER(div_nr, RAYN_BOX_FMA, RAYN_CLAMP_MED3)
         } else {
-            for (uint32_t i = 0; i < h.iterations; i++) RAYN_FOLD_ITER(RAYN_DIV_IEEE, RAYN_BOX_REF)
+            for (uint32_t i = 0; i < h.iterations; i++) RAYN_FOLD_ITER(RAYN_DIV_IEEE, RAYN_BOX_REF, RAYN_CLAMP_REF)
         }
         return mag(p) / __builtin_fabsf(dr);
     }
@@ -376,6 +390,8 @@ RD float sdf_dist(const DHitable& h, f3 p, EvalCtr& evals, float scale) {
     return mag(p) - h.sdf_radius;
 }
 #undef RAYN_FOLD_X4
+#undef RAYN_CLAMP_MED3
+#undef RAYN_CLAMP_REF
 #undef RAYN_FOLD_ITER
 #undef RAYN_DIV_IEEE
 #undef RAYN_BOX_REF

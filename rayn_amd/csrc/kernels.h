@@ -177,6 +177,7 @@ struct Tables {
     void launch_resolve(hipStream_t s, const DScene* sc, const DTile* tiles, uint32_t n_tiles, uint32_t max_tile_pixels, uint32_t spp, Pool pool, \
                         float* out_color, float* out_alpha, float* out_background, float* out_normal, const uint32_t* base_hist, uint32_t hist_stride); \
     void launch_probe_dist(hipStream_t s, const DScene* sc, uint32_t hit_index, const float* pts, float* out, uint32_t n); \
+    void launch_probe_dist_as(hipStream_t s, const DScene* sc, uint32_t hit_index, int sdfk, float t0, const float* pts, float* out, uint32_t n); \
     void launch_shadow_march(hipStream_t s, bool count, const DScene* sc, Nee nee, uint32_t max_jobs, int single_sdf, DCtl* ctl, unsigned long long* evals, const Tuning& tun); \
     void launch_probe_detmath(hipStream_t s, uint32_t op, const float* a, const float* b, float* out, uint32_t n); \
     void launch_probe_shading(hipStream_t s, const DScene* sc, uint32_t op, uint32_t index, const float* in, float* out, const float* aux, uint32_t n); \
@@ -202,8 +203,9 @@ struct KernelSet {
     decltype(&rayn_p0::launch_shadow_march) shadow_march;
     decltype(&rayn_p0::launch_probe_detmath) probe_detmath;
     decltype(&rayn_p0::launch_probe_shading) probe_shading;
+    decltype(&rayn_p0::launch_probe_dist_as) probe_dist_as;
 };
-#define RAYN_KERNEL_SET(NS) KernelSet{&NS::launch_pack_tables, &NS::launch_raygen, &NS::launch_extend, &NS::launch_group_hist, &NS::launch_scan_tile, &NS::launch_tile_prefix, &NS::launch_bin_scatter, &NS::launch_shade, &NS::launch_compact_scatter, &NS::launch_batch_setup, &NS::launch_resolve, &NS::launch_probe_dist, &NS::launch_shadow_march, &NS::launch_probe_detmath, &NS::launch_probe_shading}
+#define RAYN_KERNEL_SET(NS) KernelSet{&NS::launch_pack_tables, &NS::launch_raygen, &NS::launch_extend, &NS::launch_group_hist, &NS::launch_scan_tile, &NS::launch_tile_prefix, &NS::launch_bin_scatter, &NS::launch_shade, &NS::launch_compact_scatter, &NS::launch_batch_setup, &NS::launch_resolve, &NS::launch_probe_dist, &NS::launch_shadow_march, &NS::launch_probe_detmath, &NS::launch_probe_shading, &NS::launch_probe_dist_as}
 inline KernelSet kernel_set(int fma_policy) {
     if (fma_policy) return RAYN_KERNEL_SET(rayn_p1);
     return RAYN_KERNEL_SET(rayn_p0);

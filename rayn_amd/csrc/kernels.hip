@@ -653,10 +653,14 @@ __global__ void __launch_bounds__(256, SETUP_WAVES) k_shade_setup(const DScene* 
                                                       unsigned long long* __restrict__ alive_mask, uint8_t* __restrict__ bgrp_cnt,
                                                       unsigned long long* __restrict__ evals_out) {
     const DScene& sc = *scp;
-    const uint32_t lane = lane_id();
     const uint32_t n_slots = ctl->b_groups << 6;
     EvalCtr evals;
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    // Thread and lane number from j (blocks of SHADE_SETUP_THREADS = 256), NOT from threadIdx.x: the kernel needs them at its very end, and threadIdx.x
+    // lives in v0, which the out-of-line bulb_logf calls of sdf_normal clobber.  hipcc (ROCm 7) keeps it across such a call by a copy it places BEFORE the
+    // s_or that restores exec after mandelbulb_dist's orbit loop; when no lane of the wave runs that loop (0 iterations) the copy runs under exec == 0,
+    // v0 comes back stale and the group's alive mask below is stored by no lane or a wrong one.  j is an ordinary value that no call touches.
+    const uint32_t tid = j & (SHADE_SETUP_THREADS - 1u), lane = j & 63u;
     if (j >= n_slots) return; // whole waves: n_slots % 64 == 0
     const uint32_t P = bq[j];
     const bool valid = P != INVALID;
@@ -822,9 +826,9 @@ __global__ void __launch_bounds__(256, SETUP_WAVES) k_shade_setup(const DScene* 
                     light_sample_volume(sc.l[li], vsample, o, d, t, &vd, &vp);
                     va = sc.has_extinct ? dmf_expf(-sc.rho_t * vd) : 1.0f;
                 }
-                s_vol[(li * 3 + 0) * 256 + threadIdx.x] = vd;
-                s_vol[(li * 3 + 1) * 256 + threadIdx.x] = vp;
-                s_vol[(li * 3 + 2) * 256 + threadIdx.x] = va;
+                s_vol[(li * 3 + 0) * 256 + tid] = vd;
+                s_vol[(li * 3 + 1) * 256 + tid] = vp;
+                s_vol[(li * 3 + 2) * 256 + tid] = va;
             }
         for (uint32_t march = 0; march < VM; march++) {
             for (uint32_t i = 0; i < 4; i++) {
@@ -837,9 +841,9 @@ __global__ void __launch_bounds__(256, SETUP_WAVES) k_shade_setup(const DScene* 
                     float u0 = dm_fractf(((i & 1) ? rs.z : rs.x) + scr), u1 = dm_fractf(((i & 1) ? rs.w : rs.y) + scr);
                     float vdist, vpdf, vaux;
                     if (memo) {
-                        vdist = s_vol[(li * 3 + 0) * 256 + threadIdx.x];
-                        vpdf = s_vol[(li * 3 + 1) * 256 + threadIdx.x];
-                        vaux = s_vol[(li * 3 + 2) * 256 + threadIdx.x];
+                        vdist = s_vol[(li * 3 + 0) * 256 + tid];
+                        vpdf = s_vol[(li * 3 + 1) * 256 + tid];
+                        vaux = s_vol[(li * 3 + 2) * 256 + tid];
                     } else {
                         light_sample_volume(L, vsample, o, d, t, &vdist, &vpdf);
                         vaux = sc.has_extinct ? dmf_expf(-sc.rho_t * vdist) : 1.0f;
@@ -1829,6 +1833,15 @@ __global__ void k_probe_dist(const DScene* __restrict__ scp, uint32_t hit_index,
     EvalCtr ev;
     out[i] = sdf_dist<false>(scp->h[hit_index], f3{pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]}, ev, scp->h[hit_index].scale);
 }
+// sdf_dist in the instantiation SDFK, with the scale of a packet of lane-0 time t0 (rayn_hip_probe_sdf_dist_as; the division arm is the object's fast_div in *scp)
+template <int SDFK>
+__global__ void k_probe_dist_as(const DScene* __restrict__ scp, uint32_t hit_index, float t0, const float* __restrict__ pts, float* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    EvalCtr ev;
+    const DHitable& h = scp->h[hit_index];
+    out[i] = sdf_dist<false, SDFK>(h, f3{pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]}, ev, sdf_scale(h, t0));
+}
 __global__ void k_probe_detmath(uint32_t op, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -2075,6 +2088,15 @@ void launch_resolve(hipStream_t s, const DScene* sc, const DTile* tiles, uint32_
 }
 void launch_probe_dist(hipStream_t s, const DScene* sc, uint32_t hit_index, const float* pts, float* out, uint32_t n) {
     hipLaunchKernelGGL(k_probe_dist, grid_for(n, 256), dim3(256), 0, s, sc, hit_index, pts, out, n);
+}
+void launch_probe_dist_as(hipStream_t s, const DScene* sc, uint32_t hit_index, int sdfk, float t0, const float* pts, float* out, uint32_t n) {
+#define RAYN_PROBE_DIST_AS(KIND) hipLaunchKernelGGL((k_probe_dist_as<KIND>), grid_for(n, 256), dim3(256), 0, s, sc, hit_index, t0, pts, out, n)
+    if (sdfk == SDFK_MANDELBOX_12S) RAYN_PROBE_DIST_AS(SDFK_MANDELBOX_12S);
+    else if (sdfk == (int)RAYN_SDF_SPHERE) RAYN_PROBE_DIST_AS(RAYN_SDF_SPHERE);
+    else if (sdfk == (int)RAYN_SDF_MANDELBOX) RAYN_PROBE_DIST_AS(RAYN_SDF_MANDELBOX);
+    else if (sdfk == (int)RAYN_SDF_MANDELBULB) RAYN_PROBE_DIST_AS(RAYN_SDF_MANDELBULB);
+    else RAYN_PROBE_DIST_AS(-1);
+#undef RAYN_PROBE_DIST_AS
 }
 void launch_verify_short_div(hipStream_t s, float n, uint32_t lo_bits, uint32_t count, uint32_t* bad) {
     hipLaunchKernelGGL(k_verify_short_div, dim3(4096), dim3(256), 0, s, n, lo_bits, count, bad);

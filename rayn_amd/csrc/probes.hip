@@ -51,6 +51,56 @@ int rayn_hip_probe_sdf_dist(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t 
     HIPCHK(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return RAYN_OK;
 }
+// sdf_dist<false, sdfk> of one TracedSDF in the division arm fast_div (at most the object's own) with the scale of a packet whose lane-0 time is t0.  The scene
+// copy that carries the lowered fast_div lives in a buffer of this call: ctx->d_scene keeps what the upload decided.
+int rayn_hip_probe_sdf_dist_as(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t hitable_index, int32_t sdfk, uint32_t fast_div, float t0, const float* pts,
+                               float* out, uint32_t n) {
+    int rc = validate(ctx, p);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    DScene hs;
+    rc = build_scene(ctx, ctx->cfg->world, *p, &hs);
+    if (rc) return rc;
+    if (hitable_index >= ctx->cfg->world.n_hitables || ctx->cfg->world.hitables[hitable_index].kind != RAYN_HITABLE_TRACED_SDF)
+        return fail(ctx, RAYN_ERR_INVALID_ARG, "hitable_index does not name a TracedSDF of the uploaded world");
+    if (!pts || !out) return fail(ctx, RAYN_ERR_INVALID_ARG, "null buffer");
+    if (n == 0 || n > (1u << 26)) return fail(ctx, RAYN_ERR_INVALID_ARG, "probe size out of range");
+    DHitable& h = hs.h[hitable_index];
+    if (sdfk != -1 && sdfk != (int32_t)RAYN_SDF_SPHERE && sdfk != (int32_t)RAYN_SDF_MANDELBOX && sdfk != (int32_t)RAYN_SDF_MANDELBULB && sdfk != 100)
+        return fail(ctx, RAYN_ERR_INVALID_ARG, "sdfk names no instantiation of sdf_dist (-1, a RAYN_SDF_* kind or 100)");
+    if (sdfk >= 0 && sdfk != 100 && (uint32_t)sdfk != h.sdf_kind) return fail(ctx, RAYN_ERR_INVALID_ARG, "sdfk is not the SDF kind of the object");
+    if (sdfk == 100 && (h.sdf_kind != RAYN_SDF_MANDELBOX || h.fast_div != 2u || h.iterations != 12u))
+        return fail(ctx, RAYN_ERR_INVALID_ARG, "sdfk 100 needs a 12-iteration MandelBox whose short division the upload verified (fast_div 2)");
+    if (fast_div > h.fast_div) return fail(ctx, RAYN_ERR_INVALID_ARG, "fast_div may only lower the object's own division arm");
+    if (sdfk == 100 && fast_div != 2u) return fail(ctx, RAYN_ERR_INVALID_ARG, "sdfk 100 has the short division compiled in: fast_div must be 2");
+    h.fast_div = fast_div;
+    const KernelSet K = kernel_set(ctx->cfg->fma_policy);
+    DevBuf d_sc, d_in, d_out;
+    HIPCHK(d_sc.alloc(sizeof hs)); HIPCHK(d_in.alloc((size_t)n * 12)); HIPCHK(d_out.alloc((size_t)n * 4));
+    HIPCHK(hipMemcpy(d_sc.p, &hs, sizeof hs, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_in.p, pts, (size_t)n * 12, hipMemcpyHostToDevice));
+    K.probe_dist_as(ctx->stream, d_sc.as<DScene>(), hitable_index, sdfk, t0, d_in.as<float>(), d_out.as<float>(), n);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return RAYN_OK;
+}
+// what the values of (uploaded world, p) decide: the same build_scene and scene_march_kernels a render calls, nothing uploaded and nothing launched
+// beyond build_scene's own verdict kernel (short_div_is_exact)
+int rayn_hip_probe_scene_dispatch(rayn_ctx* ctx, const rayn_frame_params* p, int32_t* out) {
+    int rc = validate(ctx, p);
+    if (rc) return rc;
+    if (!out) return fail(ctx, RAYN_ERR_INVALID_ARG, "null buffer");
+    HIPCHK(hipSetDevice(ctx->device));
+    DScene hs;
+    rc = build_scene(ctx, ctx->cfg->world, *p, &hs);
+    if (rc) return rc;
+    Tuning tun;
+    out[0] = scene_march_kernels(ctx, hs, *p, &tun);
+    out[1] = tun.sdf_kind; out[2] = tun.bulb ? 1 : 0; out[3] = (int32_t)hs.anim_spheres;
+    for (uint32_t i = 0; i < RAYN_MAX_HITABLES; i++) out[4 + i] = i < hs.n_hitables ? (int32_t)hs.h[i].fast_div : -1;
+    return RAYN_OK;
+}
 // HitableStore::add_hits for caller-supplied rays through the PRODUCT extend kernel of the uploaded scene (k_extend1, or the generic k_extend of a
 // multi-SDF scene): one synthetic ray queue - pool slot i = ray i, queue entry i = i, padded to whole 64-slot groups - one launch, then hit_t / object read back.
 int rayn_hip_probe_extend(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t depth, const float* org, const float* dir, float* out_t,

@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <thread>
 #include <vector>
@@ -121,6 +122,10 @@ int build_scene(rayn_ctx* ctx, const rayn_world_desc& w, const rayn_frame_params
             // ... and the box fold's 2*clamp(p) is an exact product while |box_side| <= 2^60 (fma == mul, add)
             const float bs = h.box_side < 0.0f ? -h.box_side : h.box_side;
             d.fast_div = (d.min_rad_sq >= lo && d.min_rad_sq <= hi && d.fixed_rad_sq >= lo && d.fixed_rad_sq <= hi && bs <= hi) ? 1u : 0u;
+            // ... and the fast arms' box fold is the median of (p, -l, l), which is the reference's min(max(p, -l), l) only for 0 <= l: a negative box side
+            // (the reference then returns l for every p, -0 included) and a NaN one (it returns NaN; med3 drops a NaN operand) take the fast_div == 0 arm, which clamps
+            // in the reference's own order (device_core.h: clamp_ref)
+            if (!(h.box_side >= 0.0f) || std::signbit(h.box_side)) d.fast_div = 0u;
             // ... and the 4-instruction division when the device has verified it for every reachable denominator
             if (d.fast_div && h.kind == RAYN_HITABLE_TRACED_SDF && h.sdf_kind == RAYN_SDF_MANDELBOX && short_div_is_exact(ctx, d.min_rad_sq, d.fixed_rad_sq))
                 d.fast_div = 2u;
