@@ -218,6 +218,17 @@ pub struct RaynTemporalUpscaleParams {
     pub confidence: u32,
 }
 
+// The parameter block of the preview integrator (an extension; include/rayn_hip.h: rayn_preview_params).  Plain scalars, 12 bytes;
+// rayn_hip_sizeof(11) reports it.
+#[repr(C)]
+/// `samples`: AO rays per pixel, 1..64; `radius`: their length, finite and > 0; `ambient`: in [0, 1]
+#[derive(Clone, Copy, Debug)]
+pub struct RaynPreviewParams {
+    pub samples: u32,
+    pub radius: f32,
+    pub ambient: f32,
+}
+
 #[link(name = "rayn_hip")]
 extern "C" {
     pub fn rayn_hip_create(device: i32, out: *mut *mut RaynCtx) -> i32;
@@ -405,6 +416,26 @@ extern "C" {
         d_out_background: *mut f32,
         d_out_normal: *mut f32,
         d_out_weight: *mut f32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    /// bytes of device scratch the preview integrator needs (0 for a size it rejects and for `samples` outside 1..64); host only
+    pub fn rayn_preview_scratch_bytes(width: u32, height: u32, samples: u32) -> usize;
+    /// the preview integrator: primary hit, viewer-facing normal and ambient occlusion of the uploaded world (device pointers;
+    /// `d_scramble`, `d_out_ao`, `d_out_records` and `d_out_object` may be null; include/rayn_hip.h has the definition)
+    pub fn rayn_hip_preview_device(
+        ctx: *mut RaynCtx,
+        p: *const RaynFrameParams,
+        pp: *const RaynPreviewParams,
+        d_samples: *const f32,
+        d_scramble: *const f32,
+        d_out_color: *mut f32,
+        d_out_alpha: *mut f32,
+        d_out_normal: *mut f32,
+        d_out_ao: *mut f32,
+        d_out_records: *mut c_void,
+        d_out_object: *mut u32,
+        d_scratch: *mut c_void,
+        scratch_bytes: usize,
         hip_stream: *mut c_void,
     ) -> i32;
 }

@@ -5,6 +5,7 @@ written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints
     python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise [atrous|variance]] [--temporal] [--feedback B]
                                       [--resample {bilinear,catmull_rom}] [--display [--exposure auto|EV] [--tone T] [--bloom LEVELS] [--adaptation S]]
                                       [--upscale S [--temporal --supersample [--no-jitter] [--confidence | --no-confidence]]]
+                                      [--preview [K] [--ao-radius R]]
 
 --compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
 the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
@@ -26,7 +27,11 @@ its suffix; --denoise atrous and --display then work on the upscaled film.  It d
 only through --supersample: the temporal history then lives at the upscaled size and every low frame is rendered through a camera offset
 by a fraction of a low pixel, so that over S * S frames every high pixel has had a sample at its own centre (rayn_amd.Supersample()
 defaults, an extension: jitter on, confidence off); --no-jitter switches the jitter off, --confidence weighs every frame by its nearest low
-sample and --no-confidence says the default aloud.  The Color file is _color_temporal_xS.png."""
+sample and --no-confidence says the default aloud.  The Color file is _color_temporal_xS.png.
+--preview [K] runs the preview integrator in place of the render (rayn_amd.Preview, an extension): every frame is the geometry alone -
+primary hit, viewer-facing normal and the ambient occlusion of K rays per pixel (default rayn_amd.Preview().samples) of length --ao-radius R
+(default rayn_amd.Preview().radius) - and the Color file gets _preview right after _color.  --temporal, --denoise atrous and --display work
+on it; --upscale, --denoise variance and --compare-loop do not combine with it."""
 import argparse
 import os
 import sys
@@ -95,7 +100,14 @@ def main():
     ap.add_argument("--no-jitter", action="store_true", help="every low frame samples the same lattice (Supersample(jitter=False)); needs --supersample")
     ap.add_argument("--confidence", action="store_true", help="weigh every frame by its nearest low sample (Supersample(confidence=True)); needs --supersample")
     ap.add_argument("--no-confidence", action="store_true", help="every frame counts fully in the history (Supersample(confidence=False), the default); needs --supersample")
+    ap.add_argument("--preview", nargs="?", type=int, const=R.Preview().samples, default=None, metavar="K",
+                    help="run the preview integrator in place of the render: primary hit, normal and the ambient occlusion of K rays per pixel (1..64)")
+    ap.add_argument("--ao-radius", type=float, default=None, metavar="R", help="length of the preview's ambient-occlusion rays in world units; needs --preview")
     args = ap.parse_args()
+    if args.ao_radius is not None and args.preview is None:
+        ap.error("--ao-radius sets up the preview integrator: add --preview")
+    if args.preview is not None and (args.upscale is not None or args.denoise == "variance" or args.compare_loop):
+        ap.error("--preview does not combine with --upscale, --denoise variance or --compare-loop")
     if args.upscale is not None and not 1 <= args.upscale <= 8:
         ap.error("--upscale must be in 1..8")
     if args.supersample and not (args.upscale is not None and args.temporal):
@@ -134,6 +146,9 @@ def main():
     supersample = None
     if args.supersample:
         supersample = R.Supersample(jitter=not args.no_jitter, confidence=True if args.confidence else False if args.no_confidence else R.Supersample().confidence)
+    preview = None
+    if args.preview is not None:
+        preview = R.Preview(samples=args.preview, radius=R.Preview().radius if args.ao_radius is None else args.ao_radius)
     first, end = (int(x) for x in args.frames.split(":"))
     frames = list(range(first, end))
     base = f"{SAMPLES * 4}_spp"
@@ -147,11 +162,15 @@ def main():
     film = R.Film(CHANNELS, (args.width, args.height))
     # warm-up: code objects, the context's first-frame arena and the writer path (not timed)
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames[:1], FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
-                         os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample)
+                         os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample, preview=preview)
     t0 = time.perf_counter()
     stats = film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
-                                 os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample)
+                                 os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample, preview=preview)
     seq_s = time.perf_counter() - t0
+    if preview is not None:  # the preview is enqueued, not waited for: there is no per-frame render time to report
+        print(f"render_sequence --preview {preview}{' --temporal ' + str(temporal) if temporal else ''}{' --denoise ' + str(denoise) if denoise else ''}"
+              f"{' --display ' + str(display) if display else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s")
+        return
     for st in stats:
         print(f"frame {st['frame']:4d}: render {st['ms_total']:8.2f} ms")
     print(f"render_sequence{' --denoise ' + str(denoise) if denoise else ''}{' --temporal ' + str(temporal) if temporal else ''}{' --display ' + str(display) if display else ''}{' --upscale ' + str(upscale) if upscale else ''}{' --supersample ' + str(supersample) if supersample else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s "

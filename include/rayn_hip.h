@@ -752,6 +752,55 @@ int rayn_hip_temporal_upscale_device(rayn_ctx* ctx, const rayn_frame_params* p, 
                                      float* d_out_color, float* d_out_alpha, float* d_out_background, float* d_out_normal, float* d_out_weight,
                                      void* hip_stream);
 
+/* ---- preview integrator (an EXTENSION: rayn has one integrator, the path tracer) -- An image of the geometry alone - primary hit,
+ * viewer-facing normal and ambient occlusion, a "clay" render - at a small fraction of the film's cost: for placing a camera inside a
+ * fractal, for checking an animation's motion before paying for the render, and as an AO AOV.  It runs beside the film path and shares none
+ * of its state: the primary hit is the G-buffer pass above, the occlusion of the TracedSDFs goes through the scene's PRODUCT shadow-march
+ * kernel (the kernel rayn_hip_probe_shadow runs).
+ *
+ * Definition.  All arithmetic f32 under the ctx's mul_add policy where the film's own functions honour it (dot, mag_sq, cross,
+ * concentric_circle_map, the MandelBox fold); a product and a sum written out below are a separate multiply and add.  For pixel
+ * p = x + y * width, bottom-up rows:
+ *   1. Primary hit: exactly the G-buffer pass - same ray (direction d), same product extend kernel at depth 0, same record (P, t) and object
+ *      index: the records and objects are bit for bit those of rayn_hip_gbuffer_device for the same p.  Every closure time is p->time_start (ts).
+ *   2. Background: a miss, or a hit object whose material kind is Sky: colour (0, 0, 0), alpha 0, normal (0, 0, 0), ao 1.  Every other pixel is
+ *      a surface with alpha 1.
+ *   3. Surface normal at depth 0 as the shade stage takes it (src/sphere.rs:73-86, src/sdf.rs:85-101), h the hit object: a Sphere has
+ *      n = normalized(P - center(h, ts)) and offset = 0; a TracedSDF has hps = max(0.0001f, sdf_detail_scale * half_pixel_size_at(t)) - the
+ *      depth-0 threshold closure of src/film.rs:540-551 - n = the tetrahedron normal (sdfu normals_fast) of the SDF at P - center(h, ts) with
+ *      epsilon hps, four distance evaluations with the MandelBox scale taken at ts, and offset = hps.
+ *   4. Viewer side: wo = -d, nf = n * signum(dot(n, wo)).
+ *   5. AO rays, k = 0..K-1 with K = samples: u = fract(s[k].x + r_p), v = fract(s[k].y + r_p), s the caller's table of K float pairs
+ *      (d_samples) and r_p the pixel's entry of the caller's scramble table (d_scramble: one float per pixel in the layout of the scramble
+ *      builder below; NULL: r_p = 0); l = cosine_weighted_in_hemisphere(u, v) (src/math.rs:99-103); w = c0 * l.x + c1 * l.y + c2 * l.z with
+ *      (c0, c1, c2) = get_orthonormal_basis(nf) (src/math.rs:49-59); a = P + nf * offset, b = a + w * radius;
+ *      vis_k = HitableStore::test_occluded(a, b) (src/hitable.rs:164-168) at ts: the analytic spheres in index order, the TracedSDFs through
+ *      the product shadow-march kernel.  A segment a sphere occludes is not marched; a scene without a TracedSDF launches no march.
+ *   6. Resolve: ao = (float)(number of k with vis_k == 1) / (float)K - an integer count, independent of order;
+ *      hl = ambient + (1.0f - ambient) * max(0.0f, dot(nf, wo)); colour = ao * hl in all three channels; the normal output is nf.
+ * The AO rays are parked, marched and counted in rounds of 8, which bounds the scratch and changes no result. */
+typedef struct {
+    uint32_t samples; /* K: AO rays per pixel, 1..64 */
+    float radius;     /* length of an AO ray in world units; finite, > 0 */
+    float ambient;    /* the part of the headlight term that does not depend on the view angle; in [0, 1] */
+} rayn_preview_params;
+/* Bytes of device scratch the entry needs for a width x height image with `samples` AO rays per pixel: the G-buffer pass's scratch, 32 bytes
+ * and 29 * min(samples, 8) bytes per pixel of the image rounded up to a multiple of 64 pixels (0 for a size it rejects and for samples
+ * outside 1..64).  Host only; needs no GPU. */
+size_t rayn_preview_scratch_bytes(uint32_t width, uint32_t height, uint32_t samples);
+/* Enqueue the preview on 'hip_stream' (NULL = the ctx's own stream; not waited for) for the uploaded world and p (its resolution, time_start,
+ * max_marches, max_vis_marches, sdf_detail_scale, world_radius), on the ctx's GPU (devices[0] of a multi-device ctx).  DEVICE pointers.
+ * Outputs in the film's and the G-buffer's layouts, so that the save_to, display, denoise and temporal entries take them unchanged:
+ * d_out_color and d_out_normal 3 floats per pixel, d_out_alpha 1; d_out_ao (1 float per pixel), d_out_records (16 bytes per pixel, 16-byte
+ * aligned) and d_out_object (one u32 per pixel) may each be NULL.  d_samples: 2 * samples floats, 8-byte aligned.  d_scratch: 16-byte
+ * aligned, at least the byte count above.  Like a render it replaces the context's device scene.  RAYN_ERR_INVALID_ARG with a last error text,
+ * and nothing written, for: a NULL p or pp, a zero-sized image or width * height >= 2^31, samples outside 1..64, a radius that is not finite
+ * and > 0, an ambient outside [0, 1], a NULL d_samples, colour, alpha, normal or scratch, a misaligned buffer, too little scratch, buffers
+ * that overlap, and no uploaded world. */
+int rayn_hip_preview_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_preview_params* pp, const float* d_samples,
+                            const float* d_scramble, float* d_out_color, float* d_out_alpha, float* d_out_normal, float* d_out_ao,
+                            void* d_out_records, uint32_t* d_out_object, void* d_scratch, size_t scratch_bytes, void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */
@@ -825,7 +874,7 @@ int rayn_hip_fma_policy(void);
 int rayn_hip_set_fma_policy(rayn_ctx* ctx, int policy);
 /* sizeof() of the ABI structs as compiled: 0 world_desc, 1 frame_params, 2 stats, 3 hitable,
  * 4 material, 5 light, 6 camera, 7 temporal_resample_params, 8 display_params, 9 upscale_params,
- * 10 temporal_upscale_params — lets a binding verify its layout. */
+ * 10 temporal_upscale_params, 11 preview_params — lets a binding verify its layout. */
 size_t rayn_hip_sizeof(int which);
 /* "" for the product build of the library; the VARIANT name of a `make variant` build (timing experiments: such a build is
  * only ever loaded through RAYN_HIP_LIB + RAYN_HIP_ALLOW_VARIANT=1, and bench.py prints the name in its result line). */

@@ -373,6 +373,18 @@ inline int temporal_upscale(rayn_ctx* ctx, const rayn_frame_params& p, const ray
                                             d_out_color, d_out_alpha, d_out_background, d_out_normal, d_out_weight, hip_stream);
 }
 
+// Extension (include/rayn_hip.h: the preview integrator): primary hit, viewer-facing normal and ambient occlusion of the uploaded world under
+// p - the geometry alone.  Device pointers; d_samples holds `samples` float pairs; d_scramble (one float per pixel), d_out_ao, d_out_records
+// and d_out_object may be null; d_scratch holds at least preview_scratch_bytes.  Returns the entry's code.
+inline size_t preview_scratch_bytes(Extent2u res, uint32_t samples) { return rayn_preview_scratch_bytes(res.w, res.h, samples); }
+inline int preview(rayn_ctx* ctx, const rayn_frame_params& p, uint32_t samples, float radius, float ambient, const float* d_samples,
+                   const float* d_scramble, float* d_out_color, float* d_out_alpha, float* d_out_normal, float* d_out_ao, void* d_out_records,
+                   uint32_t* d_out_object, void* d_scratch, size_t scratch_bytes, void* hip_stream = nullptr) {
+    const rayn_preview_params pp = {samples, radius, ambient};
+    return rayn_hip_preview_device(ctx, &p, &pp, d_samples, d_scramble, d_out_color, d_out_alpha, d_out_normal, d_out_ao, d_out_records, d_out_object,
+                                   d_scratch, scratch_bytes, hip_stream);
+}
+
 // ---- setup::setup() (src/setup.rs:46-170) with the resolution as an argument ---------------------
 namespace setup {
 constexpr float WORLD_RADIUS = 100.0f;

@@ -86,6 +86,10 @@ class TemporalUpscaleParams(C.Structure):  # rayn_temporal_upscale_params
     _fields_ = [("confidence", C.c_uint32)]
 
 
+class PreviewParams(C.Structure):  # rayn_preview_params
+    _fields_ = [("samples", C.c_uint32), ("radius", C.c_float), ("ambient", C.c_float)]
+
+
 DISPLAY_TONE = {"linear": 0, "reinhard": 1, "aces": 2}  # rayn_display_params.tone by the name rayn_amd.Display takes
 
 TEMPORAL_RESAMPLE = {"bilinear": 0, "catmull_rom": 1}  # rayn_temporal_resample_params.resample by the name rayn_amd.Temporal takes

@@ -45,6 +45,7 @@ EXPORTS = [
     "rayn_hip_denoise_temporal_variance_feedback_device", "rayn_hip_temporal_accumulate_resample_device",
     "rayn_display_scratch_bytes", "rayn_hip_display_pixels_device", "rayn_hip_display_color_device",
     "rayn_hip_upscale_device", "rayn_hip_temporal_upscale_device",
+    "rayn_preview_scratch_bytes", "rayn_hip_preview_device",
 ]
 
 
@@ -137,6 +138,9 @@ def lib():
         L.rayn_hip_temporal_upscale_device.argtypes = ([vp, C.POINTER(_abi.FrameParams), C.POINTER(_abi.UpscaleParams), C.POINTER(_abi.TemporalParams),
                                                         C.POINTER(_abi.TemporalUpscaleParams), C.POINTER(_abi.Camera), C.POINTER(_abi.Camera), C.c_float]
                                                        + [vp] * 10 + [C.c_size_t] + [vp] * 6)
+        L.rayn_preview_scratch_bytes.restype = C.c_size_t
+        L.rayn_preview_scratch_bytes.argtypes = [C.c_uint32] * 3
+        L.rayn_hip_preview_device.argtypes = [vp, C.POINTER(_abi.FrameParams), C.POINTER(_abi.PreviewParams)] + [vp] * 9 + [C.c_size_t, vp]
         L.rayn_sets_1d.restype = C.c_uint32
         L.rayn_sets_1d.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_sets_2d.restype = C.c_uint32

@@ -30,6 +30,20 @@ def temporal_moments_bytes(width, height):
     return int(lib().rayn_temporal_moments_bytes(int(width), int(height)))
 
 
+def preview_scratch_bytes(width, height, samples):
+    """rayn_preview_scratch_bytes: bytes of device scratch the preview integrator needs for a width x height image with `samples` AO rays
+    per pixel (0 for a size it rejects and for samples outside 1..64)."""
+    return int(lib().rayn_preview_scratch_bytes(int(width), int(height), int(samples)))
+
+
+def preview_tables(samples, frame, width, height):
+    """The default tables of a preview of `samples` AO rays for frame `frame`: (the sample table (samples, 2) float32 - 2-D set 0 of
+    build_rd_tables(samples, 0, 2, frame), so successive frames get different directions - and the per-pixel scramble of
+    build_film_tables)."""
+    s2 = build_rd_tables(int(samples), 0, 2, int(frame))[1]
+    return np.ascontiguousarray(s2[: 2 * int(samples)].reshape(int(samples), 2)), build_film_tables(int(width), int(height))[0]
+
+
 def alloc_gbuffer(width, height, device="cuda"):
     """The two planes of a G-buffer as Context.gbuffer fills them: records (n, 4) float32 (Px, Py, Pz, t) and object (n,) int32 (the u32
     object index; a miss is -1 = 0xFFFFFFFF)."""
@@ -541,6 +555,25 @@ class Context:
         rec, obj = gbuffer_ptrs(d_gbuffer, int(params.width) * int(params.height), "d_gbuffer")
         d_scratch, scratch_ptr, scratch_bytes = scratch(d_scratch, gbuffer_scratch_bytes(params.width, params.height), d_gbuffer["records"].device)
         self._chk(self._L.rayn_hip_gbuffer_device(self.h, C.byref(params), rec, obj, scratch_ptr, scratch_bytes, stream_ptr(stream)))
+
+    def preview(self, params, preview, d_samples, d_out_film, d_scramble=None, d_out_ao=None, d_out_gbuffer=None, d_scratch=None, stream=None):
+        """rayn_hip_preview_device: the preview integrator (Preview `preview`) of the uploaded world under `params` (resolution, time_start,
+        march constants): primary hit, viewer-facing normal and ambient occlusion.  d_samples: a float32 CUDA tensor of 2 * preview.samples
+        floats, the AO sample pairs; d_scramble: one float per pixel, or None for none (preview_tables builds the defaults of both).
+        d_out_film: a film dict whose "color", "alpha" and "normal" planes are written (a "background" plane is not touched: the preview
+        has none).  d_out_ao: a float32 CUDA tensor of one float per pixel, or None.  d_out_gbuffer: alloc_gbuffer's dict for the primary
+        hits - bit for bit what Context.gbuffer writes - or None.  d_scratch: a CUDA tensor of at least preview_scratch_bytes(width,
+        height, preview.samples) bytes, allocated here when None.  Enqueued on the stream, not waited for."""
+        n = int(params.width) * int(params.height)
+        smp = f32_ptr(d_samples, "d_samples", 2 * int(preview.samples))
+        scr, ao = opt_f32_ptr(d_scramble, "d_scramble", n), opt_f32_ptr(d_out_ao, "d_out_ao", n)
+        out = [f32_ptr(d_out_film.get(k), f"d_out_film[{k!r}]", _PLANE_FLOATS[k] * n) for k in ("color", "alpha", "normal")]
+        rec, obj = (None, None) if d_out_gbuffer is None else gbuffer_ptrs(d_out_gbuffer, n, "d_out_gbuffer")
+        d_scratch, scratch_ptr, scratch_bytes = scratch(d_scratch, preview_scratch_bytes(params.width, params.height, preview.samples),
+                                                        d_out_film["color"].device)
+        pp = preview.to_abi()
+        self._chk(self._L.rayn_hip_preview_device(self.h, C.byref(params), C.byref(pp), smp, scr, *out, ao, rec, obj, scratch_ptr, scratch_bytes,
+                                                  stream_ptr(stream)))
 
     def temporal_accumulate(self, params, temporal, d_film, d_gbuffer, d_prev_history, prev_camera, prev_time_start, d_new_history, d_out_color,
                             stream=None, d_prev_moments=None, d_new_moments=None):

@@ -27,6 +27,7 @@
 #include "denoise.h"
 #include "denoise_variance.h"
 #include "post_checks.h"
+#include "preview.h"
 #include "progressive.h"
 #include "temporal.h"
 
@@ -1111,6 +1112,38 @@ int rayn_hip_gbuffer_device(rayn_ctx* ctx, const rayn_frame_params* p, void* d_o
     return post_enqueued(ctx);
 }
 
+// The preview integrator (preview.hip): the G-buffer pass above into the entry's scratch, then per round of AO rays the job-generating kernel, the
+// scene's PRODUCT shadow-march kernel over the jobs it parked (none without a TracedSDF, as launch_shade decides) and the resolve.
+int rayn_hip_preview_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_preview_params* pp, const float* d_samples, const float* d_scramble,
+                            float* d_out_color, float* d_out_alpha, float* d_out_normal, float* d_out_ao, void* d_out_records, uint32_t* d_out_object,
+                            void* d_scratch, size_t scratch_bytes, void* hip_stream) {
+    const char* why = preview_check_args(p, pp, d_samples, d_scramble, d_out_color, d_out_alpha, d_out_normal, d_out_ao, d_out_records, d_out_object,
+                                         d_scratch, scratch_bytes);
+    if (!why && ctx && !ctx->cfg->have_world) why = "rayn_hip_upload_world has not been called";
+    hipStream_t s;
+    if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
+    DScene hs;
+    if (int rc = build_scene(ctx, ctx->cfg->world, *p, &hs)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_scene, &hs, sizeof hs, hipMemcpyHostToDevice, s));
+    Tuning tun;
+    const int single_sdf = scene_march_kernels(ctx, hs, *p, &tun);
+    const KernelSet K = kernel_set(ctx->cfg->fma_policy);
+    const PreviewScratch ps = preview_scratch(p->width, p->height, pp->samples, d_scratch, d_out_records, d_out_object);
+    if (ctx->cfg->fma_policy) rayn_p1::launch_gbuffer_rays(s, ctx->d_scene, ps.g);
+    else rayn_p0::launch_gbuffer_rays(s, ctx->d_scene, ps.g);
+    K.extend(s, false, ctx->d_scene, 0, ps.g.q, ps.g.npad, ps.g.pool, ps.g.ent_obj, single_sdf, ps.g.ctl, ps.g.evals, tun);
+    launch_gbuffer_finish(s, ps.g, ps.records, ps.object);
+    const Nee nee = preview_nee(ps);
+    for (uint32_t k0 = 0; k0 < pp->samples; k0 += ps.round) {
+        const uint32_t kn = std::min(ps.round, pp->samples - k0);
+        if (ctx->cfg->fma_policy) rayn_p1::launch_preview_jobs(s, ctx->d_scene, ps, k0, kn, pp->radius, pp->ambient, d_samples, d_scramble, d_out_normal);
+        else rayn_p0::launch_preview_jobs(s, ctx->d_scene, ps, k0, kn, pp->radius, pp->ambient, d_samples, d_scramble, d_out_normal);
+        if (hs.n_sdf > 0) K.shadow_march(s, false, ctx->d_scene, nee, kn * ps.g.npad, single_sdf, ps.g.ctl, ps.g.evals, tun);
+        launch_preview_resolve(s, ps, kn, pp->samples, k0 + kn >= pp->samples, d_out_color, d_out_alpha, d_out_ao);
+    }
+    return post_enqueued(ctx);
+}
+
 // The temporal accumulate entries: moments == false is the plain one (the moments arguments are then not looked at); resample is step 4's
 // filter (0: the two older entries), bad_resample the resample entry's own complaint about its rp, reported after the shared checks.
 static int temporal_accumulate(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp, const rayn_camera* prev_camera,
@@ -1429,6 +1462,7 @@ size_t rayn_hip_sizeof(int which) {
     case 8: return sizeof(rayn_display_params);
     case 9: return sizeof(rayn_upscale_params);
     case 10: return sizeof(rayn_temporal_upscale_params);
+    case 11: return sizeof(rayn_preview_params);
     default: return 0;
     }
 }

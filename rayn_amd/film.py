@@ -79,7 +79,7 @@ class SequencePlan:
     options as the loop uses them - a denoiser without the terms of the guides the film lacks, the upscale without its plane term on
     a film without WorldNormal, and None for whatever switched itself off.  variance: `denoise` was given as a VarianceDenoise.
     up_keys: the keys of the planes the upscale rebuilds (None without one).  jobs: [(kind, bytes per pixel, file suffix)] of
-    every written image, the suffixes final."""
+    every written image, the suffixes final.  preview: the Preview that takes the render's place, or None."""
     denoise: object
     display: object
     upscale: object
@@ -89,6 +89,7 @@ class SequencePlan:
     up_keys: object
     jobs: list
     transparent_background: bool = False
+    preview: object = None
 
     def out_res(self, res):
         """The size of the written images of a film of resolution `res`."""
@@ -97,12 +98,21 @@ class SequencePlan:
 
 
 def plan_sequence(channel_kinds, write_channels, transparent_background=False, denoise=None, display=None, upscale=None, supersample=None,
-                  temporal=None):
+                  temporal=None, preview=None):
     """The SequencePlan of render_sequence's arguments for a film of `channel_kinds`: every rule of its docstring that decides what
     runs and what the files are called, and every ValueError it raises before anything renders, in the order it raises them.  Host
     only: no context, no torch, no directory."""
     color = ChannelKind.Color
     variance = isinstance(denoise, VarianceDenoise)
+    if preview is not None:
+        if not isinstance(preview, Preview):
+            raise ValueError(f"preview must be a Preview, got {preview!r}")
+        if upscale is not None or supersample is not None:
+            raise ValueError("preview= with upscale= or supersample= is not built: a preview is cheap at the full resolution")
+        if variance:
+            raise ValueError("preview= with a VarianceDenoise is not built: the preview's ambient occlusion carries no variance estimate")
+        if color not in channel_kinds:
+            raise ValueError("Attempted to preview into a film without a Color channel")
     if supersample is not None:
         if not isinstance(supersample, Supersample):
             raise ValueError(f"supersample must be a Supersample, got {supersample!r}")
@@ -145,11 +155,11 @@ def plan_sequence(channel_kinds, write_channels, transparent_background=False, d
     if display is not None:
         _check_display(display)
         display = display if shown else None
-    shown_suffix = ("color" + ("_temporal" if temporal is not None else "") + ("_denoised" if denoise is not None else "")
+    shown_suffix = ("color" + ("_preview" if preview is not None else "") + ("_temporal" if temporal is not None else "") + ("_denoised" if denoise is not None else "")
                     + ("_display" if display is not None else ""))
     scale = "" if upscale is None else f"_x{upscale.factor}"
     jobs = [(kind, bpp, (shown_suffix if kind == color else suffix) + scale) for kind, bpp, suffix in jobs]
-    return SequencePlan(denoise, display, upscale, supersample, temporal, variance, up_keys, jobs, bool(transparent_background))
+    return SequencePlan(denoise, display, upscale, supersample, temporal, variance, up_keys, jobs, bool(transparent_background), preview)
 
 
 class _SequencePost:
@@ -179,7 +189,7 @@ class _SequencePost:
             self.desc_low = type(desc).from_buffer_copy(desc)  # the world as the low frame is rendered: the camera is set per frame
         elif plan.temporal is not None:
             self.d_gbuf = alloc_gbuffer(w, h, dev)
-            self.d_gscratch = nbytes(gbuffer_scratch_bytes(w, h))
+            self.d_gscratch = nbytes(gbuffer_scratch_bytes(w, h)) if plan.preview is None else None
             self.d_hist = [nbytes(temporal_history_bytes(w, h)) for _ in range(2)]
             self.d_accum = torch.empty(w * h, 3, dtype=torch.float32, device=dev)
         self.prev_start = None  # time_start of the frame the newest history belongs to
@@ -189,6 +199,19 @@ class _SequencePost:
             self.d_dstate = self.ctx.display_state() if d.auto else None
             self.d_dscratch = nbytes(display_scratch_bytes(ow, oh, d.levels)) if d.auto or d.levels else None
         self.shown_start = None  # the start of the frame the display state last metered
+        if plan.preview is not None:
+            k = int(plan.preview.samples)
+            self.d_psamples = torch.empty(k, 2, dtype=torch.float32, device=dev)
+            self.d_pscramble = torch.from_numpy(preview_tables(k, 0, w, h)[1]).to(dev)
+            self.d_pscratch = nbytes(preview_scratch_bytes(w, h, k))
+
+    def preview(self, p, stream):
+        """In place of frame p's render: upload the frame's AO sample table and enqueue the preview into the film, and into the temporal
+        stage's G-buffer when there is one."""
+        import torch
+        plan = self.plan
+        self.d_psamples.copy_(torch.from_numpy(preview_tables(plan.preview.samples, p.frame, 1, 1)[0]))
+        self.ctx.preview(p, plan.preview, self.d_psamples, self.d_film, self.d_pscramble, None, getattr(self, "d_gbuf", None), self.d_pscratch, stream)
 
     def jitter(self, i, p):
         """Before frame i's render: with a jittering Supersample, upload the world under the frame's offset camera."""
@@ -221,7 +244,8 @@ class _SequencePost:
             d_base = self.d_up
         d_shown = d_base
         if plan.temporal is not None and plan.supersample is None:
-            ctx.gbuffer(p, self.d_gbuf, self.d_gscratch, stream)
+            if plan.preview is None:  # a preview has written its own primary hits into d_gbuf
+                ctx.gbuffer(p, self.d_gbuf, self.d_gscratch, stream)
             ctx.temporal_accumulate(p, plan.temporal, self.d_film, self.d_gbuf, prev_hist, prev_cam, prev_start, self.d_hist[i % 2], self.d_accum,
                                     stream, prev_mom, self.d_mom[i % 2])
             self.prev_start = p.time_start
@@ -268,6 +292,8 @@ class Film:
         self.progressive_epoch = 0
         self._progressive = None  # after render_progressive: its device state, geometry, checkpoint key and epoch count
         self._last_params = None  # the frame parameters of the last render (gbuffer)
+        self._gbuffer = None  # (frame parameters, device G-buffer) of a render that traced its own primary hits (render_preview)
+        self.ao = None  # render_preview: the ambient-occlusion plane, a float32 device tensor of one float per pixel
 
     def render_frame_into(self, world, camera, integrator, filter, tile_size, frame, time_range, samples, tile_first=0, tile_step=1):
         """Film::render_frame_into (src/film.rs:382-628); the film is overwritten, not accumulated (:91)."""
@@ -302,8 +328,11 @@ class Film:
             raise ValueError("the film holds no rendered frame (render_frame_into, render_sequence or render_progressive has not run)")
         w, h = self.res
         with torch.cuda.device(self.device):
-            g = alloc_gbuffer(w, h, self.device)
-            self.ctx.gbuffer(self._last_params, g)
+            if self._gbuffer is not None and self._gbuffer[0] is self._last_params:
+                g = self._gbuffer[1]
+            else:
+                g = alloc_gbuffer(w, h, self.device)
+                self.ctx.gbuffer(self._last_params, g)
             rec = g["records"].cpu().numpy().reshape(h, w, 4)
             obj = g["object"].cpu().numpy().view(np.uint32).reshape(h, w)
         return {"position": rec[..., :3].copy(), "t": rec[..., 3].copy(), "object": obj}
@@ -346,6 +375,50 @@ class Film:
             out._last_params = ph
             if want_weight:
                 return out, d_weight.cpu().numpy().reshape(H, W)
+            return out
+
+    def render_preview(self, preview=None, frame=None, world=None, camera=None, time_range=None):
+        """A NEW Film of this film's size that holds the preview integrator's image (Preview `preview`, rayn_hip_preview_device, an
+        extension): the primary hit of every pixel's centre ray, its viewer-facing normal and its ambient occlusion - the geometry alone, in
+        milliseconds.  Without `world`, the preview is of the last rendered frame: its uploaded world and frame parameters (ValueError
+        when the film holds none), with `frame` (default: that frame's number) choosing the AO directions.  With `world` and `camera`, that
+        world is uploaded first and the frame is `frame` (default 1) over `time_range` (default: the frame's own, as render_frame_into
+        takes it); nothing needs to have been rendered.  The sample table is 2-D set 0 of build_rd_tables(samples, 0, 2, frame), the scramble
+        build_film_tables' (preview_tables), so successive frames get different directions.
+
+        The new film has the channels Color, Alpha and WorldNormal (the preview has no Background), shares this film's Context and device,
+        and channel, pixels, save_to, save_hdr, denoise=Denoise(...) and display= work on it unchanged; its gbuffer() returns the preview's
+        own primary hits without tracing again, and its `ao` attribute is the ambient-occlusion plane (a float32 device tensor of one float
+        per pixel, film order).  This film is not changed."""
+        import torch
+        preview = Preview() if preview is None else preview
+        if not isinstance(preview, Preview):
+            raise ValueError(f"preview must be a Preview, got {preview!r}")
+        w, h = self.res
+        if world is not None:
+            frame = 1 if frame is None else int(frame)
+            p = frame_params(w, h, 1, 0, 2, frame, time_range)
+            self.ctx.upload_world(world.to_desc(camera))
+        else:
+            if self._last_params is None:
+                raise ValueError("the film holds no rendered frame (render_frame_into, render_sequence or render_progressive has not run): pass world= and camera=")
+            p = type(self._last_params).from_buffer_copy(self._last_params)
+            if frame is not None:
+                p.frame = int(frame)
+        samples, scramble = preview_tables(preview.samples, int(p.frame), w, h)
+        with torch.cuda.device(self.device):
+            full = alloc_device_film(w, h, self.device)
+            d_out = {k: full[k] for k in ("color", "alpha", "normal")}
+            g = alloc_gbuffer(w, h, self.device)
+            d_ao = torch.empty(w * h, dtype=torch.float32, device=self.device)
+            self.ctx.preview(p, preview, torch.from_numpy(samples).to(self.device), d_out, torch.from_numpy(scramble).to(self.device), d_ao, g)
+            out = Film.__new__(Film)
+            out._init_state([ChannelKind.Color, ChannelKind.Alpha, ChannelKind.WorldNormal], (w, h), self.ctx, self.device)
+            out.channels = d_out
+            out.progressive_epoch = self.progressive_epoch
+            out._last_params = p
+            out._gbuffer = (p, g)
+            out.ao = d_ao
             return out
 
     def have_mask(self):
@@ -581,7 +654,8 @@ class Film:
         return _prog.error_map(arrays, w, h, (pr["params"].tile_w, pr["params"].tile_h), pr["noise_floor"])
 
     def render_sequence(self, world, camera, integrator, filter, tile_size, frames, frame_rate, shutter_speed, samples, write_channels,
-                        output_folder, base_name, transparent_background=False, writers=None, denoise=None, display=None, upscale=None, supersample=None, temporal=None):
+                        output_folder, base_name, transparent_background=False, writers=None, denoise=None, display=None, upscale=None, supersample=None, preview=None,
+                        temporal=None):
         """rayn's main loop (src/main.rs:58-96) on the GPU: for each frame of `frames`, render_frame_into at
         frame_start = frame as f32 * (1.0 / frame_rate as f32), frame_end = frame_start + shutter_speed (f32, src/main.rs:61-62), then
         save_to(write_channels, output_folder, f"{base_name}_{frame:04d}", transparent_background).  rayn writes every frame under
@@ -647,19 +721,32 @@ class Film:
         resolutions.  Uploading a world is a host-side copy and every pass stages its own device scene on the stream when it is
         called, so the two uploads per frame need no synchronisation; without jitter there are none.  The histories, G-buffers and
         scratch are allocated once.  Afterwards the uploaded world is the frame's own.  supersample=None is the path described above,
-        unchanged."""
+        unchanged.
+
+        With `preview` (a Preview, an extension), every frame is the preview integrator's image in place of the render - primary hit,
+        viewer-facing normal, ambient occlusion; Context.preview with the frame's preview_tables - and everything after it is the path
+        described above: the film's Color, Alpha and WorldNormal planes are the preview's (a Background plane stays zero), the Color file
+        name gets _preview right after _color (_color_preview.png, _color_preview_temporal_denoised_display.png, ...), the other images
+        keep their names.  `display`, `denoise` (a Denoise) and `temporal` compose with it; `temporal` reprojects through the preview's own
+        primary hits instead of tracing a G-buffer.  `integrator` and `filter` are not looked at (None will do), `samples` neither, and the
+        returned stats hold only "frame".  `upscale`, `supersample` and a VarianceDenoise raise ValueError before anything renders.  The
+        preview's tables and scratch are allocated once; the preview does not wait for the GPU, so the host runs ahead until a pinned
+        image slot is needed again.  preview=None is the path described above, unchanged."""
         import concurrent.futures as cf
         import torch
         # the rules about the options alone come first and need nothing of the film, not even its channels (a bare Film.__new__ gets them)
         kinds = getattr(self, "channel_kinds", ())
-        plan = plan_sequence(kinds, write_channels, transparent_background, denoise, display, upscale, supersample, temporal)
+        plan = plan_sequence(kinds, write_channels, transparent_background, denoise, display, upscale, supersample, temporal, preview)
         frames = [int(f) for f in frames]
         os.makedirs(output_folder, exist_ok=True)
         w, h = self.res
         ow, oh = plan.out_res(self.res)
         f32 = np.float32
         inv_rate, shutter = f32(1.0) / f32(frame_rate), f32(shutter_speed)
-        spp, mb, vm = 4 * samples, integrator.max_bounces, integrator.volume_marches
+        if plan.preview is not None and integrator is None:
+            spp, mb, vm = 4 * samples, 0, 2
+        else:
+            spp, mb, vm = 4 * samples, integrator.max_bounces, integrator.volume_marches
         n_writers = max(1, min(8, 2 * len(plan.jobs) if writers is None else int(writers)))
         stats, pending = [], [[], []]  # pending[slot]: writer futures still reading that slot's pinned images
         table_pool = cf.ThreadPoolExecutor(max_workers=1, thread_name_prefix="rayn-rd-tables")
@@ -681,21 +768,25 @@ class Film:
                 stream = torch.cuda.current_stream()
                 desc = world.to_desc(camera)
                 self.ctx.upload_world(desc)
-                tables = RdTablePrefetch(table_pool, frames, spp, mb, vm, w, h, filter, self.device)
+                tables = None if plan.preview is not None else RdTablePrefetch(table_pool, frames, spp, mb, vm, w, h, filter, self.device)
                 d_film = alloc_device_film(w, h, self.device)
                 d_img = [torch.empty(oh * ow * bpp, dtype=torch.uint8, device=self.device) for _, bpp, _ in plan.jobs]
                 post = _SequencePost(self, plan, desc, d_film)
                 h_img = [[torch.empty(oh * ow * bpp, dtype=torch.uint8, pin_memory=True) for _, bpp, _ in plan.jobs] for _ in range(2)]
                 for i, frame in enumerate(frames):
-                    d_tables = tables.next()
+                    d_tables = None if tables is None else tables.next()
                     for fut in pending[0] + pending[1]:
                         if fut.done() and fut.exception() is not None:
                             raise fut.exception()
                     start = f32(frame) * inv_rate
                     p = frame_params(w, h, samples, mb, vm, frame, (float(start), float(f32(start + shutter))), tile_size)
                     post.jitter(i, p)
-                    self.ctx.render_device(p, d_tables, d_film, stream.cuda_stream)  # blocking: returns when the frame is complete
-                    st = self.ctx.stats()
+                    if plan.preview is not None:
+                        post.preview(p, stream.cuda_stream)
+                        st = {}
+                    else:
+                        self.ctx.render_device(p, d_tables, d_film, stream.cuda_stream)  # blocking: returns when the frame is complete
+                        st = self.ctx.stats()
                     st["frame"] = frame
                     stats.append(st)
                     self.channels = d_film

@@ -1,4 +1,4 @@
-"""The option dataclasses of the extensions (denoisers, temporal accumulation, display transform, upscaling, supersampling), ChannelKind
+"""The option dataclasses of the extensions (denoisers, temporal accumulation, display transform, upscaling, supersampling, preview), ChannelKind
 and the camera jitter: host-side values only, validated where they are made.  rayn_amd.film re-exports every name."""
 import dataclasses
 import enum
@@ -316,6 +316,38 @@ class Supersample:
 
     def to_abi(self):
         return _abi.TemporalUpscaleParams(int(bool(self.confidence)))
+
+
+@dataclasses.dataclass(frozen=True)
+class Preview:
+    """Parameters of the preview integrator (rayn_hip_preview_device, an extension: rayn has one integrator, the path tracer;
+    include/rayn_hip.h has the definition): an image of the geometry alone - the primary hit of every pixel's centre ray, its normal turned
+    towards the viewer and the ambient occlusion of `samples` (1..64) cosine-weighted rays of length `radius` (world units; finite, > 0),
+    ao = the visible fraction.  The colour is ao * (ambient + (1 - ambient) * max(0, n . wo)) in all three channels - a headlight whose
+    view-independent part is `ambient` (in [0, 1]; 1 leaves the AO alone) - alpha is 1 on a surface and 0 on the sky or a miss.  No
+    material, light or volume is looked at.
+
+    The default radius was chosen on the shipped scene (rayn_amd.setup at 160x96, 16 rays per pixel, the numpy restatement on the CPU:
+    tools/preview_defaults.py) among the radii 0.025 * 2^k: the variance of the ao over the fractal's pixels - the contrast between its
+    cavities and its open faces - grows with the radius up to 0.8 and is flat from 0.4 on (0.1113 at 0.2, 0.1161 at 0.4, 0.1173 at 0.8,
+    0.1099 at 1.6), and a longer ray costs more march steps, so the default is the smallest radius within 2 % of the largest variance:
+    0.4 (DESIGN.md section 8 has the table).  It is a look, not a tolerance."""
+    samples: int = 8
+    radius: float = 0.4
+    ambient: float = 0.3
+
+    def __post_init__(self):
+        _int_in("Preview", "samples", self.samples, 1, 64)
+        r, a = _number("Preview", "radius", self.radius), _number("Preview", "ambient", self.ambient)
+        with np.errstate(over="ignore"):
+            r32 = float(np.float32(r))  # the C entry takes it as an f32: check that value too
+        if not (np.isfinite(r) and r > 0.0 and np.isfinite(r32) and r32 > 0.0):
+            raise ValueError(f"Preview.radius must be finite and > 0, got {self.radius!r}")
+        if not 0.0 <= a <= 1.0:  # a NaN fails both
+            raise ValueError(f"Preview.ambient must be in [0, 1], got {self.ambient!r}")
+
+    def to_abi(self):
+        return _abi.PreviewParams(int(self.samples), float(self.radius), float(self.ambient))
 
 
 def jittered_camera(camera, jx, jy, time_start):
