@@ -939,9 +939,15 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *     11  light index floor(s * nl) clamped to nl - 1, nl = `index`     1  s                                            1  index as float
  *     12  FilterImportanceSampler::sample (src/filter.rs:222-235)      1  u                                            1  value
  *         with aux = the RAYN_FIS_TABLE_SIZE-float inverse CDF (aux is ignored by the other ops)
+ *     13  Sphere::hit of hitable `index` (src/sphere.rs:48-72)         8  o xyz, d xyz, t_max, t0                      1  t (FLT_MAX = miss)
+ *     14  Sphere::occluded of hitable `index` (src/sphere.rs:24-46)    7  a xyz, b xyz, t0                             1  0 occluded, 1 not
+ *         the device runs the prologue of k_shade_setup's spheres_visible (dir = b - a, dist = |dir|, dir / dist) and then
+ *         sphere_occluded_dir, the same functions the shade, extend and preview kernels call
  *   Camera closures (rayn_camera.animated) are evaluated at t0, which the reference takes from LANE 0 of the ray-gen packet (a caller comparing
  *   with a 4-wide packet passes one t0 per group of four lanes).  Op 6 rejects Sky (its f panics in the reference) and op 8 takes only Lambertian and
- *   Dielectric: Sky and Emissive never scatter (receives_light is false), so those paths are never reached and are not probed.
+ *   Dielectric: Sky and Emissive never scatter (receives_light is false), so those paths are never reached and are not probed.  Ops 13 and 14
+ *   take t0 per lane - the packet's lane-0 time at which a closure centre (rayn_hitable.animated) is sampled; NaN is the time of a packet whose
+ *   lane 0 is empty - and return RAYN_ERR_INVALID_ARG with a text when `index` is out of range or names a TracedSDF.
  *   rayn_hip_probe_queue      the queue stages of ONE depth through the PRODUCT kernels, launched as the depth loop launches them, on a caller-built ray queue
  *                             (no scene, no world needed): stage 0 = bin (k_group_hist, k_scan_tile, k_tile_prefix, k_bin_scatter: object-major, insertion-ordered,
  *                             x4-padded packets per tile), stage 1 = repack (k_scan_tile, k_tile_prefix, k_compact_scatter: the stable repack of the survivors).

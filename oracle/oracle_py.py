@@ -241,8 +241,8 @@ def detmath(op, a, b=None, fma=False):
 
 
 # floats per lane read / written by each op of oracle_probe_shading / rayn_hip_probe_shading (op table: include/rayn_hip.h)
-SHADING_IN = (5, 2, 2, 3, 3, 2, 9, 3, 11, 5, 8, 1, 1)
-SHADING_OUT = (6, 2, 3, 3, 9, 1, 3, 3, 7, 4, 2, 1, 1)
+SHADING_IN = (5, 2, 2, 3, 3, 2, 9, 3, 11, 5, 8, 1, 1, 8, 7)
+SHADING_OUT = (6, 2, 3, 3, 9, 1, 3, 3, 7, 4, 2, 1, 1, 1, 1)
 
 
 def probe_shading(world_desc, op, index, inp, aux=None, fma=False):

@@ -1528,11 +1528,13 @@ int oracle_fma_policy() { return RAYN_FMA_POLICY; }
 /* Counterpart of rayn_hip_probe_shading (op table, record widths and semantics: include/rayn_hip.h) through this file's OWN
  * functions, four lanes per call like the reference's packets: Camera::get_rays, the sampling maps, make_bsdf's BSDFs at a
  * WShadingPoint::make shading point, World's SphereLights, light_index as Integrator::integrate calls it, fis_sample.  A lane
- * count that is not a multiple of 4 pads the last packet with copies of its first lane.  Returns -1 for an op / index the device probe
- * rejects too. */
+ * count that is not a multiple of 4 pads the last packet with copies of its first lane.  Ops 13 / 14 (Sphere::hit / Sphere::occluded of
+ * hitable `index`) run one packet PER LANE, the lane's record - its time t0 included - splatted over the four lanes and lane 0 returned:
+ * the closure centre is sampled at lane 0's time, so each record sees the sphere at its own t0.  Returns -1 for an op / index the device
+ * probe rejects too. */
 int oracle_probe_shading(const rayn_world_desc* wd, uint32_t op, uint32_t index, const float* in, float* out, const float* aux, uint64_t n) {
-    static const uint32_t IN[13] = {5, 2, 2, 3, 3, 2, 9, 3, 11, 5, 8, 1, 1}, OUT[13] = {6, 2, 3, 3, 9, 1, 3, 3, 7, 4, 2, 1, 1};
-    if (!wd || op > 12 || !in || !out) return -1;
+    static const uint32_t IN[15] = {5, 2, 2, 3, 3, 2, 9, 3, 11, 5, 8, 1, 1, 8, 7}, OUT[15] = {6, 2, 3, 3, 9, 1, 3, 3, 7, 4, 2, 1, 1, 1, 1};
+    if (!wd || op > 14 || !in || !out) return -1;
     World w(*wd, Config{256, 100, 0.5f});
     if (op >= 6 && op <= 8) {
         if (index >= w.materials.size()) return -1;
@@ -1544,6 +1546,22 @@ int oracle_probe_shading(const rayn_world_desc* wd, uint32_t op, uint32_t index,
     if ((op == 11 && index == 0) || (op == 12 && !aux)) return -1;
     const Camera cam(wd->camera);
     const uint32_t ni = IN[op], no = OUT[op];
+    if (op == 13 || op == 14) {
+        if (index >= w.hitables.size()) return -1;
+        const Sphere* sp = dynamic_cast<const Sphere*>(w.hitables[index].get());
+        if (!sp) return -1;
+        const ThresholdFn unused = [](F4 t) { return t; };
+        for (uint64_t i = 0; i < n; i++) {
+            const float* a = in + i * ni;
+            if (op == 13) {
+                WRay r; r.origin = W3(F4(a[0]), F4(a[1]), F4(a[2])); r.dir = W3(F4(a[3]), F4(a[4]), F4(a[5])); r.time = F4(a[7]);
+                out[i] = sp->hit(r, F4(a[6]), unused).v[0];
+            } else {
+                out[i] = sp->occluded(W3(F4(a[0]), F4(a[1]), F4(a[2])), W3(F4(a[3]), F4(a[4]), F4(a[5])), F4(a[6])).v[0];
+            }
+        }
+        return 0;
+    }
     for (uint64_t base = 0; base < n; base += 4) {
         F4 a[11];
         for (uint32_t k = 0; k < ni; k++)

@@ -25,9 +25,9 @@ static_assert(!resolve_keys_fit(MAX_TILE_PIXELS, 8u * MAX_SPP_RESOLVE_BLK), "res
 
 
 // rayn_hip_probe_shading: number of ops and the floats per lane each op reads / writes (the op table of rayn_hip.h)
-constexpr uint32_t PROBE_SHADING_OPS = 13;
+constexpr uint32_t PROBE_SHADING_OPS = 15;
 __host__ __device__ constexpr uint32_t probe_shading_in(uint32_t op) {
-    return op == 0 ? 5 : op == 3 ? 3 : op == 4 ? 3 : op == 6 ? 9 : op == 7 ? 3 : op == 8 ? 11 : op == 9 ? 5 : op == 10 ? 8 : op >= 11 ? 1 : 2;
+    return op == 0 ? 5 : op == 3 ? 3 : op == 4 ? 3 : op == 6 ? 9 : op == 7 ? 3 : op == 8 ? 11 : op == 9 ? 5 : op == 10 ? 8 : op == 13 ? 8 : op == 14 ? 7 : op >= 11 ? 1 : 2;
 }
 __host__ __device__ constexpr uint32_t probe_shading_out(uint32_t op) {
     return op == 0 ? 6 : op == 1 ? 2 : op == 4 ? 9 : op == 5 ? 1 : op == 8 ? 7 : op == 9 ? 4 : op == 10 ? 2 : op >= 11 ? 1 : 3;

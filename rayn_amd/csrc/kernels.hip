@@ -1897,8 +1897,8 @@ __global__ void k_probe_detmath(uint32_t op, const float* __restrict__ a, const 
     out[i] = r;
 }
 // The shading half of the path, one device function per op, on caller records of probe_shading_in(op) floats in / probe_shading_out(op)
-// floats out per lane (op table: rayn_hip.h).  Materials, lights and the camera are the uploaded scene's (DScene); the host has checked
-// op, index and the material kind of ops 6 / 8.
+// floats out per lane (op table: rayn_hip.h).  Materials, lights, the camera and the analytic spheres are the uploaded scene's (DScene);
+// the host has checked op, index, the material kind of ops 6 / 8 and the hitable kind of ops 13 / 14.
 __global__ void k_probe_shading(const DScene* __restrict__ scp, uint32_t op, uint32_t index, const float* __restrict__ in, float* __restrict__ out,
                                 const float* __restrict__ aux, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1939,6 +1939,15 @@ __global__ void k_probe_shading(const DScene* __restrict__ scp, uint32_t op, uin
     }
     case 10: light_sample_volume(sc.l[index], a[0], f3{a[1], a[2], a[3]}, f3{a[4], a[5], a[6]}, a[7], &r[0], &r[1]); break;
     case 11: r[0] = (float)light_index(a[0], index); break;
+    case 13: r[0] = sphere_hit(sc.h[index], f3{a[0], a[1], a[2]}, f3{a[3], a[4], a[5]}, a[6], a[7]); break;
+    case 14: { // the prologue of spheres_visible (k_shade_setup) and of k_preview_jobs, then one sphere's factor
+        const f3 s = f3{a[0], a[1], a[2]};
+        f3 dir = f3{a[3], a[4], a[5]} - s;
+        const float dist = mag(dir);
+        dir = div_by_mag(dir, dist);
+        r[0] = sphere_occluded_dir(sc.h[index], s, dir, dist, a[6]);
+        break;
+    }
     default: r[0] = fis_sample(aux, a[0]); break;
     }
 }

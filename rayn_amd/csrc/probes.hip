@@ -227,6 +227,8 @@ int rayn_hip_probe_shading(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t o
     if ((op == 9 || op == 10) && index >= w.n_lights) return fail(ctx, RAYN_ERR_INVALID_ARG, "index does not name a light of the uploaded world");
     if (op == 11 && index == 0) return fail(ctx, RAYN_ERR_INVALID_ARG, "light_index needs at least one light");
     if (op == 12 && !aux) return fail(ctx, RAYN_ERR_INVALID_ARG, "fis_sample needs the inverse-CDF table in aux");
+    if ((op == 13 || op == 14) && (index >= w.n_hitables || w.hitables[index].kind != RAYN_HITABLE_SPHERE))
+        return fail(ctx, RAYN_ERR_INVALID_ARG, "index does not name an analytic Sphere of the uploaded world");
     const size_t nin = (size_t)n * probe_shading_in(op), nout = (size_t)n * probe_shading_out(op);
     const KernelSet K = kernel_set(ctx->cfg->fma_policy);
     DevBuf d_in, d_out, d_aux;

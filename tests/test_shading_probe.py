@@ -292,15 +292,17 @@ def test_shading_probe_bit_exact(gpu_ctx, oracle, op, fma):
 
 @pytest.mark.gpu
 def test_shading_probe_rejects_unprobed_paths(gpu_ctx, oracle):
-    """Sky's f panics in the reference and Sky / Emissive never scatter: both sides refuse those ops instead of inventing a result."""
+    """Sky's f panics in the reference and Sky / Emissive never scatter: both sides refuse those ops instead of inventing a result.  The sphere ops 13 / 14
+    refuse an index that names no hitable (this world has one); that they refuse a TracedSDF is tests/test_sphere_device.py's part."""
     from rayn_amd._lib import lib
     wd, p = _probe_world()
     gpu_ctx.upload_world(wd)
     fp = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))
     buf = np.zeros(64, f32)
-    for op, index in ((6, MAT_SKY), (8, MAT_SKY), (8, MAT_EMISSIVE), (6, 16), (9, 16), (10, 16), (11, 0), (13, 0)):
+    for op, index in ((6, MAT_SKY), (8, MAT_SKY), (8, MAT_EMISSIVE), (6, 16), (9, 16), (10, 16), (11, 0), (13, 1), (14, 1), (13, 16), (14, 16), (15, 0)):
         assert lib().rayn_hip_probe_shading(gpu_ctx.h, C.byref(p), op, index, fp(buf), fp(buf), None, 1) != 0, (op, index)
-        if op < 13:
+        assert len(gpu_ctx.last_error()) > 10, (op, index)
+        if op < 15:
             with pytest.raises(ValueError):
                 oracle.probe_shading(wd, op, index, buf[:SHADING_IN[op]], None)
     assert lib().rayn_hip_probe_shading(gpu_ctx.h, C.byref(p), 12, 0, fp(buf), fp(buf), None, 1) != 0  # op 12 needs the table
