@@ -229,6 +229,31 @@ pub struct RaynPreviewParams {
     pub ambient: f32,
 }
 
+// The parameter block of the frame generation (an extension; include/rayn_hip.h: rayn_interpolate_params).  One scalar, 4 bytes;
+// rayn_hip_sizeof(12) reports it.
+#[repr(C)]
+/// `depth_tolerance`: finite, >= 0
+#[derive(Clone, Copy, Debug)]
+pub struct RaynInterpolateParams {
+    pub depth_tolerance: f32,
+}
+
+// One key frame of the frame generation (include/rayn_hip.h: rayn_interpolate_key): device pointers to its film planes and G-buffer, a
+// host pointer to its camera, and its time_start.  64 bytes; rayn_hip_sizeof(13) reports it.
+#[repr(C)]
+/// `d_alpha`, `d_background`, `d_normal`: null in both keys and the output together
+#[derive(Clone, Copy, Debug)]
+pub struct RaynInterpolateKey {
+    pub d_color: *const f32,
+    pub d_alpha: *const f32,
+    pub d_background: *const f32,
+    pub d_normal: *const f32,
+    pub d_records: *const c_void,
+    pub d_object: *const u32,
+    pub camera: *const RaynCamera,
+    pub time_start: f32,
+}
+
 #[link(name = "rayn_hip")]
 extern "C" {
     pub fn rayn_hip_create(device: i32, out: *mut *mut RaynCtx) -> i32;
@@ -436,6 +461,24 @@ extern "C" {
         d_out_object: *mut u32,
         d_scratch: *mut c_void,
         scratch_bytes: usize,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    /// frame generation: the planes of the frame `p` (resolution, time_start) between the rendered keys `key_a` and `key_b`, guided by
+    /// the frame's own G-buffer (device pointers; the Alpha / Background / WorldNormal outputs are null together with the keys' planes;
+    /// `d_out_source` may be null; include/rayn_hip.h has the definition)
+    pub fn rayn_hip_interpolate_device(
+        ctx: *mut RaynCtx,
+        p: *const RaynFrameParams,
+        ip: *const RaynInterpolateParams,
+        key_a: *const RaynInterpolateKey,
+        key_b: *const RaynInterpolateKey,
+        d_gbuffer_records: *const c_void,
+        d_gbuffer_object: *const u32,
+        d_out_color: *mut f32,
+        d_out_alpha: *mut f32,
+        d_out_background: *mut f32,
+        d_out_normal: *mut f32,
+        d_out_source: *mut u32,
         hip_stream: *mut c_void,
     ) -> i32;
 }

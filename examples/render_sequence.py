@@ -5,7 +5,7 @@ written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints
     python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise [atrous|variance]] [--temporal] [--feedback B]
                                       [--resample {bilinear,catmull_rom}] [--display [--exposure auto|EV] [--tone T] [--bloom LEVELS] [--adaptation S]]
                                       [--upscale S [--temporal --supersample [--no-jitter] [--confidence | --no-confidence]]]
-                                      [--preview [K] [--ao-radius R]]
+                                      [--preview [K] [--ao-radius R]] [--interpolate K [--interp-tolerance D]]
 
 --compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
 the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
@@ -31,7 +31,13 @@ sample and --no-confidence says the default aloud.  The Color file is _color_tem
 --preview [K] runs the preview integrator in place of the render (rayn_amd.Preview, an extension): every frame is the geometry alone -
 primary hit, viewer-facing normal and the ambient occlusion of K rays per pixel (default rayn_amd.Preview().samples) of length --ao-radius R
 (default rayn_amd.Preview().radius) - and the Color file gets _preview right after _color.  --temporal, --denoise atrous and --display work
-on it; --upscale, --denoise variance and --compare-loop do not combine with it."""
+on it; --upscale, --denoise variance and --compare-loop do not combine with it.
+--interpolate K (2..16) renders only every K-th frame of the range, and the last, and generates the frames between two rendered keys from
+them (rayn_amd.Interpolate(K), an extension): each generated frame traces its own primary-hit G-buffer, projects every pixel's hit into
+both keys and blends the taps that show the same surface by time; --interp-tolerance D is the relative depth tolerance of a tap (default
+rayn_amd.Interpolate().depth_tolerance).  The camera's origin drifts as for --temporal, every Color file gets _interp right after _color,
+and --denoise atrous and --display work on the generated frames too; --temporal, --upscale, --preview, --denoise variance and
+--compare-loop do not combine with it."""
 import argparse
 import os
 import sys
@@ -103,7 +109,17 @@ def main():
     ap.add_argument("--preview", nargs="?", type=int, const=R.Preview().samples, default=None, metavar="K",
                     help="run the preview integrator in place of the render: primary hit, normal and the ambient occlusion of K rays per pixel (1..64)")
     ap.add_argument("--ao-radius", type=float, default=None, metavar="R", help="length of the preview's ambient-occlusion rays in world units; needs --preview")
+    ap.add_argument("--interpolate", type=int, default=None, metavar="K",
+                    help="render every K-th frame (2..16) and the last, and generate the frames between two rendered keys (rayn_amd.Interpolate(K))")
+    ap.add_argument("--interp-tolerance", type=float, default=None, metavar="D",
+                    help="relative depth tolerance of a key's tap (default rayn_amd.Interpolate().depth_tolerance); needs --interpolate")
     args = ap.parse_args()
+    if args.interp_tolerance is not None and args.interpolate is None:
+        ap.error("--interp-tolerance sets up the frame generation: add --interpolate")
+    if args.interpolate is not None and not 2 <= args.interpolate <= 16:
+        ap.error("--interpolate must be in 2..16")
+    if args.interpolate is not None and (args.temporal or args.upscale is not None or args.preview is not None or args.denoise == "variance" or args.compare_loop):
+        ap.error("--interpolate does not combine with --temporal, --upscale, --preview, --denoise variance or --compare-loop")
     if args.ao_radius is not None and args.preview is None:
         ap.error("--ao-radius sets up the preview integrator: add --preview")
     if args.preview is not None and (args.upscale is not None or args.denoise == "variance" or args.compare_loop):
@@ -149,11 +165,14 @@ def main():
     preview = None
     if args.preview is not None:
         preview = R.Preview(samples=args.preview, radius=R.Preview().radius if args.ao_radius is None else args.ao_radius)
+    interpolate = None
+    if args.interpolate is not None:
+        interpolate = R.Interpolate(args.interpolate, R.Interpolate().depth_tolerance if args.interp_tolerance is None else args.interp_tolerance)
     first, end = (int(x) for x in args.frames.split(":"))
     frames = list(range(first, end))
     base = f"{SAMPLES * 4}_spp"
     cam, world = S.setup((args.width, args.height))
-    if temporal is not None:  # something to reproject: the camera of BASELINE config 5 (rayn_amd.setup.setup_s3)
+    if temporal is not None or interpolate is not None:  # something to reproject: the camera of BASELINE config 5 (rayn_amd.setup.setup_s3)
         c = world.cameras.get(cam)
         c.origin = Linear(c.origin, R.vec3(0.9, -0.3, 0.15))
     integ = R.PathTracingIntegrator(max_bounces=MAX_INDIRECT_BOUNCES, volume_marches=S.VOLUME_MARCHES_PER_SAMPLE)
@@ -162,17 +181,25 @@ def main():
     film = R.Film(CHANNELS, (args.width, args.height))
     # warm-up: code objects, the context's first-frame arena and the writer path (not timed)
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames[:1], FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
-                         os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample, preview=preview)
+                         os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample, preview=preview,
+                         interpolate=interpolate)
     t0 = time.perf_counter()
     stats = film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
-                                 os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample, preview=preview)
+                                 os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample, preview=preview,
+                         interpolate=interpolate)
     seq_s = time.perf_counter() - t0
     if preview is not None:  # the preview is enqueued, not waited for: there is no per-frame render time to report
         print(f"render_sequence --preview {preview}{' --temporal ' + str(temporal) if temporal else ''}{' --denoise ' + str(denoise) if denoise else ''}"
               f"{' --display ' + str(display) if display else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s")
         return
     for st in stats:
-        print(f"frame {st['frame']:4d}: render {st['ms_total']:8.2f} ms")
+        print(f"frame {st['frame']:4d}: generated" if st.get("generated") else f"frame {st['frame']:4d}: render {st['ms_total']:8.2f} ms")
+    if interpolate is not None:
+        keys = [st for st in stats if not st.get("generated")]
+        print(f"render_sequence --interpolate {interpolate}{' --denoise ' + str(denoise) if denoise else ''}{' --display ' + str(display) if display else ''}: "
+              f"{len(frames)} frames ({len(keys)} rendered, {len(frames) - len(keys)} generated) in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s "
+              f"(render alone: {sum(st['ms_total'] for st in keys) / len(keys):.2f} ms per rendered frame)")
+        return
     print(f"render_sequence{' --denoise ' + str(denoise) if denoise else ''}{' --temporal ' + str(temporal) if temporal else ''}{' --display ' + str(display) if display else ''}{' --upscale ' + str(upscale) if upscale else ''}{' --supersample ' + str(supersample) if supersample else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s "
           f"(render alone: {sum(st['ms_total'] for st in stats) / len(frames):.2f} ms/frame)")
 

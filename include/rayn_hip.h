@@ -801,6 +801,60 @@ int rayn_hip_preview_device(rayn_ctx* ctx, const rayn_frame_params* p, const ray
                             const float* d_scramble, float* d_out_color, float* d_out_alpha, float* d_out_normal, float* d_out_ao,
                             void* d_out_records, uint32_t* d_out_object, void* d_scratch, size_t scratch_bytes, void* hip_stream);
 
+/* ---- frame generation (an EXTENSION: rayn renders every frame) -- Motion-compensated interpolation of a frame T of a sequence from two
+ * RENDERED key frames A and B around it.  Unlike a 2-D optical-flow interpolator it knows the exact geometry of T - its own primary-hit
+ * G-buffer, which costs a fiftieth of the render - and therefore which of the two keys sees each point: a point visible in one key only is
+ * taken from that key alone, which a cross-fade cannot do.  Downstream of the film: the keys' planes are read, new planes are written. */
+typedef struct {
+    float depth_tolerance; /* a tap's recorded hit distance may differ from the projected one by this fraction of it; finite, >= 0 */
+} rayn_interpolate_params;
+/* One key frame: its film planes (planar, pixel x + y * width, rows bottom-up: Color 3 floats per pixel, Alpha 1, Background 3, WorldNormal
+ * 3), its G-buffer (16-byte records (P, t), u32 objects; rayn_hip_gbuffer_device at the key's time_start), the camera it was rendered
+ * through and its time_start.  DEVICE pointers, except `camera`. */
+typedef struct {
+    const float* d_color;
+    const float* d_alpha;
+    const float* d_background;
+    const float* d_normal;
+    const void* d_records;
+    const uint32_t* d_object;
+    const rayn_camera* camera;
+    float time_start;
+} rayn_interpolate_key;
+/* Inputs: the keys A (time_start ta) and B (tb), and T's G-buffer (records (P, t), objects o) traced with p->time_start = ts under the same
+ * uploaded world; p gives the resolution and ts.  ta < tb and ta <= ts <= tb, all finite.  All arithmetic f32, no contraction under either
+ * mul_add policy, IEEE '/' and sqrtf; dot, cross and nz as for rayn_hip_temporal_accumulate_device; every sum STARTS AT -0.0f as in
+ * rayn_hip_upscale_device.  s = (ts - ta) / (tb - ta), wB = s, wA = 1.0f - s.  Per pixel (X, Y) of T and for each key K in (A, B):
+ *   1. Position in the key.  A hit pixel (o != 0xFFFFFFFF): Pp = P - center_vel * (ts - tK) when hitable o has animated != 0, else P - step
+ *      2 of the accumulate with the sign as written, so that for B the point moves forward - then step 3 of the accumulate through K's
+ *      camera at tK gives fx, fy, te; a rejected or non-finite projection gives key K no taps.  A miss pixel: fx = (float)X, fy = (float)Y
+ *      and no depth: the key's own pixel is the only tap that can count.  scale_vel morphing is not reprojected; the depth test catches it.
+ *   2. Taps.  x0f = floorf(fx), wx1 = fx - x0f, wx0 = 1.0f - wx1, y likewise, x0, y0 by step 4's clamp; the taps (x0, y0), (x0 + 1, y0),
+ *      (x0, y0 + 1), (x0 + 1, y0 + 1) with b = wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1.  A tap counts when it lies inside the image,
+ *      b > 0, the key's object there equals o (a miss matches a miss), for a hit pixel fabsf(t_tap - te) <= depth_tolerance * te, and the
+ *      key's Color there has three finite components - tested in that order, a NaN fails every comparison:  W_K += b and, per component
+ *      of every present plane, S_K += b * v_tap.
+ *   3. Tier 1.  valid_K = W_K > 0, v_K = S_K / W_K.  Both valid: out = v_A * wA + v_B * wB per component, two multiplies and one add.
+ *      Only A valid: out = v_A; only B valid: out = v_B.  This is the arm that knows about occlusion.
+ *   4. Tier 2, neither key has a tap (the point is hidden or off screen in both).  A key's own pixel (X, Y) is usable when its Color is
+ *      finite.  Both usable: the same blend on the verbatim pixels.  One usable: that pixel verbatim.  Neither: key A's pixel verbatim
+ *      when wA >= wB, else key B's; non-finite values are copied as they are.
+ *   5. d_out_source (optional, one u32 per pixel): the arm that produced the pixel - 0 both keys in tier 1, 1 A only, 2 B only, 3 the
+ *      tier-2 blend, 4 a tier-2 single or verbatim pixel.
+ * With ts == ta a pixel that finds its taps in A (a static camera and object: its own pixel with b = 1) and taps in B comes out as
+ * v_A * 1 + v_B * 0: A's bits for finite values.
+ * Alpha, Background and WorldNormal may each be NULL in A, B and the output together: the film lacks that channel, and it is neither
+ * read nor written.  Color is required.  Records 16-byte aligned, objects and d_out_source 4-byte aligned.  Enqueued on 'hip_stream'
+ * (NULL = the ctx's own stream; not waited for), on the ctx's GPU (devices[0] of a multi-device ctx); hitable motion comes from the
+ * uploaded world at the time of the call; the inputs are not modified.  RAYN_ERR_INVALID_ARG with a last error text, and nothing written,
+ * for: a NULL p, ip or key, a NULL camera, Color, record or object plane, a plane that is NULL on one side only, an unknown camera kind, a
+ * zero-sized image or width * height >= 2^31, times that break the rule above, a non-finite or negative depth_tolerance, misaligned
+ * records or objects, an output that overlaps an input or another output, and no uploaded world. */
+int rayn_hip_interpolate_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_interpolate_params* ip, const rayn_interpolate_key* key_a,
+                                const rayn_interpolate_key* key_b, const void* d_gbuffer_records, const uint32_t* d_gbuffer_object,
+                                float* d_out_color, float* d_out_alpha, float* d_out_background, float* d_out_normal, uint32_t* d_out_source,
+                                void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */
@@ -874,7 +928,7 @@ int rayn_hip_fma_policy(void);
 int rayn_hip_set_fma_policy(rayn_ctx* ctx, int policy);
 /* sizeof() of the ABI structs as compiled: 0 world_desc, 1 frame_params, 2 stats, 3 hitable,
  * 4 material, 5 light, 6 camera, 7 temporal_resample_params, 8 display_params, 9 upscale_params,
- * 10 temporal_upscale_params, 11 preview_params — lets a binding verify its layout. */
+ * 10 temporal_upscale_params, 11 preview_params, 12 interpolate_params, 13 interpolate_key — lets a binding verify its layout. */
 size_t rayn_hip_sizeof(int which);
 /* "" for the product build of the library; the VARIANT name of a `make variant` build (timing experiments: such a build is
  * only ever loaded through RAYN_HIP_LIB + RAYN_HIP_ALLOW_VARIANT=1, and bench.py prints the name in its result line). */

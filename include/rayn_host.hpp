@@ -385,6 +385,17 @@ inline int preview(rayn_ctx* ctx, const rayn_frame_params& p, uint32_t samples, 
                                    d_scratch, scratch_bytes, hip_stream);
 }
 
+// Extension (include/rayn_hip.h: frame generation): the planes of the frame p (resolution, time_start) between the rendered keys a and b,
+// guided by the frame's own G-buffer.  Device pointers; the Alpha / Background / WorldNormal outputs are null together with the keys'
+// planes; d_out_source may be null.  Returns the entry's code.
+inline int interpolate(rayn_ctx* ctx, const rayn_frame_params& p, float depth_tolerance, const rayn_interpolate_key& a, const rayn_interpolate_key& b,
+                       const void* d_gbuffer_records, const uint32_t* d_gbuffer_object, float* d_out_color, float* d_out_alpha,
+                       float* d_out_background, float* d_out_normal, uint32_t* d_out_source = nullptr, void* hip_stream = nullptr) {
+    const rayn_interpolate_params ip = {depth_tolerance};
+    return rayn_hip_interpolate_device(ctx, &p, &ip, &a, &b, d_gbuffer_records, d_gbuffer_object, d_out_color, d_out_alpha, d_out_background,
+                                       d_out_normal, d_out_source, hip_stream);
+}
+
 // ---- setup::setup() (src/setup.rs:46-170) with the resolution as an argument ---------------------
 namespace setup {
 constexpr float WORLD_RADIUS = 100.0f;

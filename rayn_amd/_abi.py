@@ -90,6 +90,15 @@ class PreviewParams(C.Structure):  # rayn_preview_params
     _fields_ = [("samples", C.c_uint32), ("radius", C.c_float), ("ambient", C.c_float)]
 
 
+class InterpolateParams(C.Structure):  # rayn_interpolate_params
+    _fields_ = [("depth_tolerance", C.c_float)]
+
+
+class InterpolateKey(C.Structure):  # rayn_interpolate_key; `camera` points at a Camera the caller keeps alive
+    _fields_ = [("d_color", C.c_void_p), ("d_alpha", C.c_void_p), ("d_background", C.c_void_p), ("d_normal", C.c_void_p),
+                ("d_records", C.c_void_p), ("d_object", C.c_void_p), ("camera", C.c_void_p), ("time_start", C.c_float)]
+
+
 DISPLAY_TONE = {"linear": 0, "reinhard": 1, "aces": 2}  # rayn_display_params.tone by the name rayn_amd.Display takes
 
 TEMPORAL_RESAMPLE = {"bilinear": 0, "catmull_rom": 1}  # rayn_temporal_resample_params.resample by the name rayn_amd.Temporal takes

@@ -46,6 +46,7 @@ EXPORTS = [
     "rayn_display_scratch_bytes", "rayn_hip_display_pixels_device", "rayn_hip_display_color_device",
     "rayn_hip_upscale_device", "rayn_hip_temporal_upscale_device",
     "rayn_preview_scratch_bytes", "rayn_hip_preview_device",
+    "rayn_hip_interpolate_device",
 ]
 
 
@@ -141,6 +142,8 @@ def lib():
         L.rayn_preview_scratch_bytes.restype = C.c_size_t
         L.rayn_preview_scratch_bytes.argtypes = [C.c_uint32] * 3
         L.rayn_hip_preview_device.argtypes = [vp, C.POINTER(_abi.FrameParams), C.POINTER(_abi.PreviewParams)] + [vp] * 9 + [C.c_size_t, vp]
+        L.rayn_hip_interpolate_device.argtypes = ([vp, C.POINTER(_abi.FrameParams), C.POINTER(_abi.InterpolateParams), C.POINTER(_abi.InterpolateKey),
+                                                   C.POINTER(_abi.InterpolateKey)] + [vp] * 8)
         L.rayn_sets_1d.restype = C.c_uint32
         L.rayn_sets_1d.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_sets_2d.restype = C.c_uint32

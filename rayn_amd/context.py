@@ -575,6 +575,35 @@ class Context:
         self._chk(self._L.rayn_hip_preview_device(self.h, C.byref(params), C.byref(pp), smp, scr, *out, ao, rec, obj, scratch_ptr, scratch_bytes,
                                                   stream_ptr(stream)))
 
+    def interpolate(self, params, interpolate, key_a, key_b, d_gbuffer, d_out_film, d_out_source=None, stream=None):
+        """rayn_hip_interpolate_device: the film planes of the frame `params` (its width, height and time_start) generated from two rendered
+        key frames by the Interpolate `interpolate`.  A key is (film dict, G-buffer dict, _abi.Camera, time_start): the device film of the key,
+        its G-buffer (alloc_gbuffer's dict, as Context.gbuffer fills it at the key's time_start), the camera it was rendered through and
+        its time_start; key_a lies before key_b and params.time_start between them.  d_gbuffer: the frame's own G-buffer under the same
+        uploaded world.  d_out_film: a film dict of the same size.  A plane (alpha, background, normal) the films lack is absent from both
+        keys and d_out_film together and is neither read nor written; "color" is required.  d_out_source: an int32 CUDA tensor of one
+        element per pixel for the arm that produced the pixel (0 both keys, 1 A only, 2 B only, 3 cross-fade, 4 a single key's pixel), or
+        None.  Enqueued on the stream, not waited for."""
+        n = int(params.width) * int(params.height)
+        keys, cams = [], []
+        for label, key in (("key_a", key_a), ("key_b", key_b)):
+            film, gbuf, camera, time_start = key
+            if not isinstance(camera, _abi.Camera):
+                raise ValueError(f"{label}'s camera must be an _abi.Camera")
+            planes = film_ptrs(film, FILM_KEYS, n, f"{label}'s film")
+            if planes[0] is None:
+                raise ValueError(f"{label}'s film['color'] must be a contiguous float32 tensor of at least {3 * n} floats")
+            rec, obj = gbuffer_ptrs(gbuf, n, f"{label}'s G-buffer")
+            cams.append(camera)  # held until the call returns: the key points at it
+            keys.append(_abi.InterpolateKey(*[None if q is None else q.value for q in planes], rec.value, obj.value, C.addressof(camera),
+                                            float(time_start)))
+        rec, obj = gbuffer_ptrs(d_gbuffer, n, "d_gbuffer")
+        out = film_ptrs(d_out_film, FILM_KEYS, n, "d_out_film")
+        src = None if d_out_source is None else i32_ptr(d_out_source, "d_out_source", n)
+        ip = interpolate.to_abi()
+        self._chk(self._L.rayn_hip_interpolate_device(self.h, C.byref(params), C.byref(ip), C.byref(keys[0]), C.byref(keys[1]), rec, obj, *out, src,
+                                                      stream_ptr(stream)))
+
     def temporal_accumulate(self, params, temporal, d_film, d_gbuffer, d_prev_history, prev_camera, prev_time_start, d_new_history, d_out_color,
                             stream=None, d_prev_moments=None, d_new_moments=None):
         """rayn_hip_temporal_accumulate_device: blend d_film["color"] (guides: d_film["normal"], the G-buffer d_gbuffer of the same frame)

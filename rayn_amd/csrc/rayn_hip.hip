@@ -28,6 +28,7 @@
 #include "denoise_variance.h"
 #include "post_checks.h"
 #include "preview.h"
+#include "interpolate.h"
 #include "progressive.h"
 #include "temporal.h"
 
@@ -1144,6 +1145,50 @@ int rayn_hip_preview_device(rayn_ctx* ctx, const rayn_frame_params* p, const ray
     return post_enqueued(ctx);
 }
 
+// Frame generation (interpolate.hip): two rendered keys and the frame's own G-buffer -> the planes of the frame between them.  The hitable
+// velocities come from the world as uploaded at the time of the call, by value, as for the accumulate entries.
+int rayn_hip_interpolate_device(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_interpolate_params* ip, const rayn_interpolate_key* key_a,
+                                const rayn_interpolate_key* key_b, const void* d_gbuffer_records, const uint32_t* d_gbuffer_object,
+                                float* d_out_color, float* d_out_alpha, float* d_out_background, float* d_out_normal, uint32_t* d_out_source,
+                                void* hip_stream) {
+    const char* why = interpolate_check_args(p, ip, key_a, key_b, d_gbuffer_records, d_gbuffer_object, d_out_color, d_out_alpha, d_out_background,
+                                             d_out_normal, d_out_source);
+    if (!why && ctx && !ctx->cfg->have_world) why = "rayn_hip_upload_world has not been called";
+    InterpolateCall c;
+    memset(&c, 0, sizeof c);
+    if (!why && (!build_camera(*key_a->camera, &c.a.cam) || !build_camera(*key_b->camera, &c.b.cam))) why = "unknown camera kind";
+    hipStream_t s;
+    if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
+    c.width = p->width;
+    c.height = p->height;
+    c.depth_tolerance = ip->depth_tolerance;
+    c.time = p->time_start;
+    const rayn_interpolate_key* keys[2] = {key_a, key_b};
+    InterpolateKey* dst[2] = {&c.a, &c.b};
+    for (int k = 0; k < 2; k++) {
+        dst[k]->color = keys[k]->d_color;
+        dst[k]->alpha = keys[k]->d_alpha;
+        dst[k]->background = keys[k]->d_background;
+        dst[k]->normal = keys[k]->d_normal;
+        dst[k]->records = keys[k]->d_records;
+        dst[k]->object = keys[k]->d_object;
+        dst[k]->time = keys[k]->time_start;
+    }
+    c.records = d_gbuffer_records;
+    c.object = d_gbuffer_object;
+    c.out_color = d_out_color;
+    c.out_alpha = d_out_alpha;
+    c.out_background = d_out_background;
+    c.out_normal = d_out_normal;
+    c.out_source = d_out_source;
+    const rayn_world_desc& w = ctx->cfg->world;
+    c.n_hitables = w.n_hitables < RAYN_MAX_HITABLES ? w.n_hitables : RAYN_MAX_HITABLES;
+    for (uint32_t i = 0; i < c.n_hitables; i++)
+        c.hvel[i] = make_float4(w.hitables[i].center_vel.x, w.hitables[i].center_vel.y, w.hitables[i].center_vel.z, w.hitables[i].animated ? 1.0f : 0.0f);
+    launch_interpolate(s, c);
+    return post_enqueued(ctx);
+}
+
 // The temporal accumulate entries: moments == false is the plain one (the moments arguments are then not looked at); resample is step 4's
 // filter (0: the two older entries), bad_resample the resample entry's own complaint about its rp, reported after the shared checks.
 static int temporal_accumulate(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp, const rayn_camera* prev_camera,
@@ -1463,6 +1508,8 @@ size_t rayn_hip_sizeof(int which) {
     case 9: return sizeof(rayn_upscale_params);
     case 10: return sizeof(rayn_temporal_upscale_params);
     case 11: return sizeof(rayn_preview_params);
+    case 12: return sizeof(rayn_interpolate_params);
+    case 13: return sizeof(rayn_interpolate_key);
     default: return 0;
     }
 }

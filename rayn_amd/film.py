@@ -79,7 +79,8 @@ class SequencePlan:
     options as the loop uses them - a denoiser without the terms of the guides the film lacks, the upscale without its plane term on
     a film without WorldNormal, and None for whatever switched itself off.  variance: `denoise` was given as a VarianceDenoise.
     up_keys: the keys of the planes the upscale rebuilds (None without one).  jobs: [(kind, bytes per pixel, file suffix)] of
-    every written image, the suffixes final.  preview: the Preview that takes the render's place, or None."""
+    every written image, the suffixes final.  preview: the Preview that takes the render's place, or None.  interpolate: the Interpolate
+    that generates the frames between the rendered keys, or None; interp_keys: the keys of the planes it generates."""
     denoise: object
     display: object
     upscale: object
@@ -90,6 +91,8 @@ class SequencePlan:
     jobs: list
     transparent_background: bool = False
     preview: object = None
+    interpolate: object = None
+    interp_keys: object = None
 
     def out_res(self, res):
         """The size of the written images of a film of resolution `res`."""
@@ -98,12 +101,25 @@ class SequencePlan:
 
 
 def plan_sequence(channel_kinds, write_channels, transparent_background=False, denoise=None, display=None, upscale=None, supersample=None,
-                  temporal=None, preview=None):
+                  temporal=None, preview=None, interpolate=None):
     """The SequencePlan of render_sequence's arguments for a film of `channel_kinds`: every rule of its docstring that decides what
     runs and what the files are called, and every ValueError it raises before anything renders, in the order it raises them.  Host
-    only: no context, no torch, no directory."""
+    only: no context, no torch, no directory.  `interpolate` must be an Interpolate.  It raises ValueError together with `temporal`,
+    with `upscale`, with `supersample` and with `preview`: none of these compositions is built.  It raises ValueError with a
+    VarianceDenoise, as every sequence without `temporal` does.  It needs the film's Color channel.  It puts _interp right after
+    _color in the name of every Color image of the call, where _temporal would stand."""
     color = ChannelKind.Color
     variance = isinstance(denoise, VarianceDenoise)
+    interp_keys = None
+    if interpolate is not None:
+        if not isinstance(interpolate, Interpolate):
+            raise ValueError(f"interpolate must be an Interpolate, got {interpolate!r}")
+        for name, other in (("temporal", temporal), ("upscale", upscale), ("supersample", supersample), ("preview", preview)):
+            if other is not None:
+                raise ValueError(f"interpolate= with {name}= is not built: the generated frames are made from plain rendered keys at one resolution")
+        if color not in channel_kinds:
+            raise ValueError("Attempted to interpolate a film without a Color channel")
+        interp_keys = [_CHANNEL_KEY[k] for k in ChannelKind if k in channel_kinds]
     if preview is not None:
         if not isinstance(preview, Preview):
             raise ValueError(f"preview must be a Preview, got {preview!r}")
@@ -155,11 +171,13 @@ def plan_sequence(channel_kinds, write_channels, transparent_background=False, d
     if display is not None:
         _check_display(display)
         display = display if shown else None
-    shown_suffix = ("color" + ("_preview" if preview is not None else "") + ("_temporal" if temporal is not None else "") + ("_denoised" if denoise is not None else "")
+    shown_suffix = ("color" + ("_preview" if preview is not None else "") + ("_temporal" if temporal is not None else "")
+                    + ("_interp" if interpolate is not None else "") + ("_denoised" if denoise is not None else "")
                     + ("_display" if display is not None else ""))
     scale = "" if upscale is None else f"_x{upscale.factor}"
     jobs = [(kind, bpp, (shown_suffix if kind == color else suffix) + scale) for kind, bpp, suffix in jobs]
-    return SequencePlan(denoise, display, upscale, supersample, temporal, variance, up_keys, jobs, bool(transparent_background), preview)
+    return SequencePlan(denoise, display, upscale, supersample, temporal, variance, up_keys, jobs, bool(transparent_background), preview,
+                        interpolate, interp_keys)
 
 
 class _SequencePost:
@@ -199,6 +217,13 @@ class _SequencePost:
             self.d_dstate = self.ctx.display_state() if d.auto else None
             self.d_dscratch = nbytes(display_scratch_bytes(ow, oh, d.levels)) if d.auto or d.levels else None
         self.shown_start = None  # the start of the frame the display state last metered
+        if plan.interpolate is not None:  # two keys used in turn, one generated frame
+            self.d_keys = [d_film, alloc_device_film(w, h, dev)]
+            self.d_kgbuf = [alloc_gbuffer(w, h, dev) for _ in range(2)]
+            self.d_ggbuf = alloc_gbuffer(w, h, dev)
+            self.d_igscratch = nbytes(gbuffer_scratch_bytes(w, h))
+            d_gen_full = alloc_device_film(w, h, dev)
+            self.d_gen = {k: d_gen_full[k] for k in plan.interp_keys}
         if plan.preview is not None:
             k = int(plan.preview.samples)
             self.d_psamples = torch.empty(k, 2, dtype=torch.float32, device=dev)
@@ -221,15 +246,29 @@ class _SequencePost:
             self.desc_low.camera = self.low_cam
             self.ctx.upload_world(self.desc_low)
 
-    def enqueue(self, i, p, stream):
-        """After frame i's render (frame parameters p): enqueue its upscale, temporal and denoise stages on the raw `stream`.
+    def key_gbuffer(self, slot, p, stream):
+        """After the render of the key in `slot` (frame parameters p): trace its G-buffer."""
+        self.ctx.gbuffer(p, self.d_kgbuf[slot], self.d_igscratch, stream)
+
+    def generate(self, p, slot_a, p_a, slot_b, p_b, stream):
+        """The frame p between the keys in slot_a (frame parameters p_a) and slot_b (p_b): its own G-buffer and the interpolation, into
+        the generated film, which is returned."""
+        ctx, plan = self.ctx, self.plan
+        ctx.gbuffer(p, self.d_ggbuf, self.d_igscratch, stream)
+        keys = [({k: self.d_keys[s][k] for k in plan.interp_keys}, self.d_kgbuf[s], self.desc.camera, q.time_start) for s, q in ((slot_a, p_a), (slot_b, p_b))]
+        ctx.interpolate(p, plan.interpolate, keys[0], keys[1], self.d_ggbuf, self.d_gen, None, stream)
+        return self.d_gen
+
+    def enqueue(self, i, p, stream, d_film=None):
+        """After frame i's render (frame parameters p): enqueue its upscale, temporal and denoise stages on the raw `stream`.  d_film: the
+        film the frame is in, when it is not the sequence's own (a key's slot or the generated film of an interpolated sequence).
         -> (d_shown, d_base): the film dicts the Color image and the other images are made from."""
         ctx, plan = self.ctx, self.plan
         (w, h), (ow, oh) = self.res, self.out_res
         first = self.prev_start is None  # no history yet
         prev_hist, prev_mom = (None, None) if first else (self.d_hist[(i + 1) % 2], self.d_mom[(i + 1) % 2])
         prev_cam, prev_start = (None, 0.0) if first else (self.desc.camera, self.prev_start)
-        d_base = self.d_film
+        d_base = self.d_film if d_film is None else d_film
         if plan.upscale is not None:
             ctx.gbuffer(p, self.d_glow, self.d_uscratch, stream)
             if self.low_cam is not None:
@@ -294,13 +333,16 @@ class Film:
         self._last_params = None  # the frame parameters of the last render (gbuffer)
         self._gbuffer = None  # (frame parameters, device G-buffer) of a render that traced its own primary hits (render_preview)
         self.ao = None  # render_preview: the ambient-occlusion plane, a float32 device tensor of one float per pixel
+        self._last_camera = None  # the rayn_camera of the world the last render uploaded (interpolated)
 
     def render_frame_into(self, world, camera, integrator, filter, tile_size, frame, time_range, samples, tile_first=0, tile_step=1):
         """Film::render_frame_into (src/film.rs:382-628); the film is overwritten, not accumulated (:91)."""
         import torch
         w, h = self.res
         p = frame_params(w, h, samples, integrator.max_bounces, integrator.volume_marches, frame, time_range, tile_size, tile_first, tile_step)
-        self.ctx.upload_world(world.to_desc(camera))
+        desc = world.to_desc(camera)
+        self.ctx.upload_world(desc)
+        self._last_camera = desc.camera
         tables = build_tables(4 * samples, integrator.max_bounces, integrator.volume_marches, frame, w, h, filter)
         with torch.cuda.device(self.device):
             d_tables = [torch.from_numpy(t).to(self.device) for t in tables]
@@ -375,6 +417,55 @@ class Film:
             out._last_params = ph
             if want_weight:
                 return out, d_weight.cpu().numpy().reshape(H, W)
+            return out
+
+    def interpolated(self, other, time_start, interpolate=None):
+        """A NEW Film of this film's size that holds a frame GENERATED for the start time `time_start` between two rendered frames: this
+        film (key A) and `other` (key B), two films of the same size on the same device whose last renders were of the same world through
+        the same camera at two different start times, this film's first (Interpolate `interpolate`, rayn_hip_interpolate_device, an
+        extension).  The G-buffers of both keys and of the generated frame are traced under the world this film's render uploaded; every
+        channel the films hold is generated with the same weights.  The new film has the same channel kinds and shares this film's
+        Context and device, so channel, pixels, save_to, save_hdr, denoise=Denoise(...) and display= work on it unchanged, and its
+        gbuffer() is the generated frame's own.  It holds no progressive state.  Neither key is changed.  The counterpart of upscaled.
+        ValueError when either film holds no rendered frame, the films differ in size, channels or device, or the times are out of
+        order."""
+        import torch
+        interpolate = Interpolate() if interpolate is None else interpolate
+        if not isinstance(interpolate, Interpolate):
+            raise ValueError(f"interpolate must be an Interpolate, got {interpolate!r}")
+        if not isinstance(other, Film):
+            raise ValueError(f"other must be a Film, got {other!r}")
+        if ChannelKind.Color not in self.channel_kinds:
+            raise ValueError("Attempted to interpolate a film without a Color channel")
+        if other.res != self.res or set(other.channel_kinds) != set(self.channel_kinds) or other.device != self.device:
+            raise ValueError("the two key films must have the same size, channels and device")
+        for f in (self, other):
+            if f._last_params is None or f.channels is None or f._last_camera is None:
+                raise ValueError("a key film holds no rendered frame (render_frame_into, render_sequence or render_progressive has not run)")
+        pa, pb = self._last_params, other._last_params
+        ts = float(np.float32(time_start))
+        if not (pa.time_start < pb.time_start and pa.time_start <= ts <= pb.time_start):  # a NaN fails
+            raise ValueError(f"time_start must lie between the keys' start times {pa.time_start!r} < {pb.time_start!r}, got {time_start!r}")
+        w, h = self.res
+        pt = type(pa).from_buffer_copy(pa)
+        pt.time_start, pt.time_end = ts, float(np.float32(np.float32(ts) + (np.float32(pa.time_end) - np.float32(pa.time_start))))
+        keys = [_CHANNEL_KEY[k] for k in ChannelKind if k in self.channel_kinds]
+        with torch.cuda.device(self.device):
+            g_a, g_b, g_t = (alloc_gbuffer(w, h, self.device) for _ in range(3))
+            d_scratch = torch.empty(max(gbuffer_scratch_bytes(w, h), 1), dtype=torch.uint8, device=self.device)
+            for p, g in ((pa, g_a), (pb, g_b), (pt, g_t)):
+                self.ctx.gbuffer(p, g, d_scratch)
+            full = alloc_device_film(w, h, self.device)
+            d_out = {k: full[k] for k in keys}
+            self.ctx.interpolate(pt, interpolate, ({k: self.channels[k] for k in keys}, g_a, self._last_camera, pa.time_start),
+                                 ({k: other.channels[k] for k in keys}, g_b, other._last_camera, pb.time_start), g_t, d_out)
+            out = Film.__new__(Film)
+            out._init_state(list(self.channel_kinds), (w, h), self.ctx, self.device)
+            out.channels = d_out
+            out.progressive_epoch = self.progressive_epoch
+            out._last_params = pt
+            out._gbuffer = (pt, g_t)
+            out._last_camera = self._last_camera
             return out
 
     def render_preview(self, preview=None, frame=None, world=None, camera=None, time_range=None):
@@ -582,6 +673,7 @@ class Film:
             with torch.cuda.device(self.device):
                 stream = torch.cuda.current_stream()
                 self.ctx.upload_world(desc)
+                self._last_camera = desc.camera
                 d_state = torch.empty(_prog.state_bytes(w, h, tile_size), dtype=torch.uint8, device=self.device)
                 d_mean = alloc_device_film(w, h, self.device)
                 if restored is None:
@@ -655,7 +747,7 @@ class Film:
 
     def render_sequence(self, world, camera, integrator, filter, tile_size, frames, frame_rate, shutter_speed, samples, write_channels,
                         output_folder, base_name, transparent_background=False, writers=None, denoise=None, display=None, upscale=None, supersample=None, preview=None,
-                        temporal=None):
+                        interpolate=None, temporal=None):
         """rayn's main loop (src/main.rs:58-96) on the GPU: for each frame of `frames`, render_frame_into at
         frame_start = frame as f32 * (1.0 / frame_rate as f32), frame_end = frame_start + shutter_speed (f32, src/main.rs:61-62), then
         save_to(write_channels, output_folder, f"{base_name}_{frame:04d}", transparent_background).  rayn writes every frame under
@@ -731,12 +823,26 @@ class Film:
         primary hits instead of tracing a G-buffer.  `integrator` and `filter` are not looked at (None will do), `samples` neither, and the
         returned stats hold only "frame".  `upscale`, `supersample` and a VarianceDenoise raise ValueError before anything renders.  The
         preview's tables and scratch are allocated once; the preview does not wait for the GPU, so the host runs ahead until a pinned
-        image slot is needed again.  preview=None is the path described above, unchanged."""
+        image slot is needed again.  preview=None is the path described above, unchanged.
+
+        With `interpolate` (an Interpolate, an extension), only every interpolate.every-th entry of `frames` - and the last - is rendered,
+        exactly as above: a KEY.  Every other entry is GENERATED from the nearest key on each side (Context.interpolate): its own G-buffer
+        is traced at its own start time, f32(frame) * (1 / frame_rate) like any frame's, every pixel's primary hit is projected into both
+        keys, and the taps that show the same surface are blended by time.  `frames` must ascend.  The loop renders key B, then writes
+        the frames between A and B in ascending order, then B, so the display's auto-exposure state and the writers see the frames in
+        time order.  Two key films and two key G-buffers are used in turn; one G-buffer, one generated film, the scratch and the image
+        slots are allocated once, and nothing new synchronises.  `denoise` (a Denoise) and `display` run on a generated film as on a
+        rendered one.  Every Color image of the call - keys and generated frames alike, so that the files form one numbered sequence -
+        gets _interp right after _color (_color_interp.png, _color_interp_denoised_display.png); the keys' images are byte for byte
+        those of the plain loop.  The returned stats of a generated frame are {"frame": f, "generated": True}.  Together with
+        `temporal`, `upscale`, `supersample` or `preview` it raises ValueError before anything renders: not built.  View-dependent
+        shading and the shadows of moving objects are blended, not reprojected, and a generated frame averages two keys' noise
+        (DESIGN.md section 8).  interpolate=None is the path described above, unchanged."""
         import concurrent.futures as cf
         import torch
         # the rules about the options alone come first and need nothing of the film, not even its channels (a bare Film.__new__ gets them)
         kinds = getattr(self, "channel_kinds", ())
-        plan = plan_sequence(kinds, write_channels, transparent_background, denoise, display, upscale, supersample, temporal, preview)
+        plan = plan_sequence(kinds, write_channels, transparent_background, denoise, display, upscale, supersample, temporal, preview, interpolate)
         frames = [int(f) for f in frames]
         os.makedirs(output_folder, exist_ok=True)
         w, h = self.res
@@ -768,36 +874,48 @@ class Film:
                 stream = torch.cuda.current_stream()
                 desc = world.to_desc(camera)
                 self.ctx.upload_world(desc)
-                tables = None if plan.preview is not None else RdTablePrefetch(table_pool, frames, spp, mb, vm, w, h, filter, self.device)
+                self._last_camera = desc.camera
+                itp = plan.interpolate
+                rendered = frames if itp is None else [f for i, f in enumerate(frames) if itp.is_key(i, len(frames))]
+                tables = None if plan.preview is not None else RdTablePrefetch(table_pool, rendered, spp, mb, vm, w, h, filter, self.device)
                 d_film = alloc_device_film(w, h, self.device)
                 d_img = [torch.empty(oh * ow * bpp, dtype=torch.uint8, device=self.device) for _, bpp, _ in plan.jobs]
                 post = _SequencePost(self, plan, desc, d_film)
                 h_img = [[torch.empty(oh * ow * bpp, dtype=torch.uint8, pin_memory=True) for _, bpp, _ in plan.jobs] for _ in range(2)]
-                for i, frame in enumerate(frames):
+
+                def params_of(frame):
+                    start = f32(frame) * inv_rate
+                    return start, frame_params(w, h, samples, mb, vm, frame, (float(start), float(f32(start + shutter))), tile_size)
+
+                def render(i, frame, d_into):
+                    """Frame `frame`, entry i of the call, into the device film d_into -> (start, frame parameters, stats)."""
                     d_tables = None if tables is None else tables.next()
                     for fut in pending[0] + pending[1]:
                         if fut.done() and fut.exception() is not None:
                             raise fut.exception()
-                    start = f32(frame) * inv_rate
-                    p = frame_params(w, h, samples, mb, vm, frame, (float(start), float(f32(start + shutter))), tile_size)
+                    start, p = params_of(frame)
                     post.jitter(i, p)
                     if plan.preview is not None:
                         post.preview(p, stream.cuda_stream)
                         st = {}
                     else:
-                        self.ctx.render_device(p, d_tables, d_film, stream.cuda_stream)  # blocking: returns when the frame is complete
+                        self.ctx.render_device(p, d_tables, d_into, stream.cuda_stream)  # blocking: returns when the frame is complete
                         st = self.ctx.stats()
                     st["frame"] = frame
-                    stats.append(st)
-                    self.channels = d_film
+                    self.channels = d_into
                     self._last_params = p
                     self.progressive_epoch += 1
+                    return start, p, st
+
+                def emit(i, frame, start, p, st, d_src=None):
+                    """The images of entry i, whose film is d_src (None: the sequence's own d_film)."""
+                    stats.append(st)
                     # Frame k's post-process and copies go on the render stream, so frame k + 1's render (enqueued on the same stream
                     # after them) cannot overwrite d_film or d_img before they have been read; only the pinned slot needs a host-side
                     # wait: its images from frame k - 2 must have been encoded.
                     slot = i % 2
                     wait_slot(slot)
-                    d_shown, d_base = post.enqueue(i, p, stream.cuda_stream)
+                    d_shown, d_base = post.enqueue(i, p, stream.cuda_stream, d_src)
                     for (kind, _, _), d, hbuf in zip(plan.jobs, d_img, h_img[slot]):
                         post.pixels(kind, start, d_shown if kind == ChannelKind.Color else d_base, d, stream.cuda_stream)
                         hbuf.copy_(d, non_blocking=True)
@@ -806,6 +924,30 @@ class Film:
                     for (_, bpp, suffix), hbuf in zip(plan.jobs, h_img[slot]):
                         path = os.path.join(output_folder, f"{base_name}_{frame:04d}_{suffix}.png")
                         pending[slot].append(write_pool.submit(write, done, hbuf.numpy().reshape(oh, ow, bpp), path))
+
+                if itp is None:
+                    for i, frame in enumerate(frames):
+                        start, p, st = render(i, frame, d_film)
+                        emit(i, frame, start, p, st)
+                else:
+                    # key B is rendered, then the frames between A and B are generated and written in ascending order, then B: the
+                    # display state and every writer see the frames in time order.  Both keys' films and G-buffers are used in turn.
+                    keys = [i for i in range(len(frames)) if itp.is_key(i, len(frames))]
+                    slot_a, a = 0, None  # a: (entry, frame parameters) of key A
+                    for n_key, ib in enumerate(keys):
+                        slot_b = n_key % 2
+                        start_b, p_b, st_b = render(ib, frames[ib], post.d_keys[slot_b])
+                        post.key_gbuffer(slot_b, p_b, stream.cuda_stream)
+                        if a is not None:
+                            for ig in range(a[0] + 1, ib):
+                                start, p = params_of(frames[ig])
+                                if not (a[1].time_start <= p.time_start <= p_b.time_start):
+                                    raise ValueError(f"interpolate= needs ascending frames: frame {frames[ig]} does not lie between its keys "
+                                                     f"{frames[a[0]]} and {frames[ib]}")
+                                d_gen = post.generate(p, slot_a, a[1], slot_b, p_b, stream.cuda_stream)
+                                emit(ig, frames[ig], start, p, {"frame": frames[ig], "generated": True}, d_gen)
+                        emit(ib, frames[ib], start_b, p_b, st_b, post.d_keys[slot_b])
+                        slot_a, a = slot_b, (ib, p_b)
                 wait_slot(0)
                 wait_slot(1)
             return stats

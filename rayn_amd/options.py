@@ -350,6 +350,39 @@ class Preview:
         return _abi.PreviewParams(int(self.samples), float(self.radius), float(self.ambient))
 
 
+@dataclasses.dataclass(frozen=True)
+class Interpolate:
+    """Parameters of the frame generation of a sequence (rayn_hip_interpolate_device, an extension: rayn renders every frame;
+    include/rayn_hip.h has the definition): render_sequence renders every `every`-th frame (2..16) of its list - and the last - as a key
+    and generates the frames between two keys from them.  A generated frame traces its own primary-hit G-buffer, projects every pixel's
+    hit into both keys and blends, by time, the taps there that show the same object at the projected depth: a tap's recorded hit distance
+    may differ from the projected one by `depth_tolerance` (relative; finite, >= 0).  A point one key alone sees is taken from that key; one
+    that neither sees is a cross-fade of the keys' own pixels.
+
+    The tolerance was chosen on the shipped scene (rayn_amd.setup at 160x96 under a camera drift of 2 pixels a frame, keys at 8 spp, every
+    generated frame of every = 2 and 4 scored against 1024 spp; tools/interpolate_defaults.py, DESIGN.md section 8 has the grid): the error
+    falls as the tolerance grows, from 0.76x / 1.03x the rendered 8-spp frame's at Temporal's 5 % to 0.67x / 0.90x at 25 %, and only to 0.61x
+    / 0.88x with the depth test as good as off (100 %) - on the fractal, whose depth changes by more than 5 % from one pixel to the next, a
+    tight test throws away taps of the right surface.  25 % keeps the test that guards self-occlusion and scale_vel morphing."""
+    every: int = 2
+    depth_tolerance: float = 0.25
+
+    def __post_init__(self):
+        _int_in("Interpolate", "every", self.every, 2, 16)
+        _number("Interpolate", "depth_tolerance", self.depth_tolerance)
+        with np.errstate(over="ignore"):
+            d = float(np.float32(self.depth_tolerance))  # the C entry takes it as an f32: check that value too
+        if not (np.isfinite(d) and d >= 0.0 and float(self.depth_tolerance) >= 0.0):
+            raise ValueError(f"Interpolate.depth_tolerance must be finite and >= 0, got {self.depth_tolerance!r}")
+
+    def is_key(self, i, n):
+        """Is entry i of a list of n frames a key: i a multiple of `every`, or the last entry."""
+        return i % int(self.every) == 0 or i == n - 1
+
+    def to_abi(self):
+        return _abi.InterpolateParams(float(self.depth_tolerance))
+
+
 def jittered_camera(camera, jx, jy, time_start):
     """A copy of the rayn_camera `camera` (an _abi.Camera) offset by (jx, jy) pixels of ITS resolution: the centre ray of its pixel
     (x, y) goes through what `camera` sees at the pixel coordinates (x + 0.5 + jx, y + 0.5 + jy).  With the basis u, v, w the camera has
