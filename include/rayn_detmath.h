@@ -13,9 +13,20 @@
  * v_fma_f64) - half the binary64 instructions of the mul + add form r1 used, which matters on the GPU
  * (k_shade_setup spends about a third of its cycles here).  The same source
  * compiled by g++ (oracle) and by hipcc for gfx950 (kernels) therefore yields bit-identical floats.
- * Internally everything is evaluated in double with truncation error < 1e-15, so the float result
- * is the correctly rounded one except in ~1e-8 of cases — i.e. it agrees with a good libm (glibc's
- * sinf/expf/powf are themselves double-evaluated) essentially everywhere.
+ * Internally everything is evaluated in binary64 and converted once to float.  HOW CLOSE the binary64 value is to the true one is
+ * measured, not assumed (tests/test_detmath.py against mpmath at 320 bits, tests/detmath_ref.py: every exponent field, both signs, the
+ * mantissas next to the powers of two + seeded random ones; oracle_detmath_core exports the value before the conversion).
+ * max |core - truth| / |truth| over those grids:
+ *     exp 2^-52.8   log 2^-52.1   sin 2^-51.8   cos 2^-51.8   tan 2^-51.1   atan2 2^-51.7          (all below 2^-49)
+ *     pow 2^-45.2: x^y = e^a with a = y * ln x, and the error of ln x and of the product is scaled by |a| - up to 104 before the
+ *     result leaves the floats.  Bound (4 |y ln x| + 8) 2^-53, reached to 0.78 of it.
+ * THE RULE FOR HARD POINTS: the float returned is the correctly rounded one unless the TRUE value lies within that bound (relative) of a
+ * binary32 rounding boundary, the midpoint of two consecutive floats; such a point is hard and may be one ulp off.  On the grids:
+ *     exp 3 hard of 32640, 0 off    sin, tan, log 0 hard    cos 2 hard of 32640, 0 off    atan2 33 hard of 118336, 1 off
+ *     pow 102 hard of 97800, 15 off by one ulp (bases 2^k (1 - 2^-24) and the like with y = 0.5, 1.5): pow is NOT correctly rounded
+ *     next to a tie; that is a stated limit, pinned by the test.
+ * sin, cos and tan hold this for EVERY finite float (dm_sincos_large above 2^20), |sin|, |cos| <= 1 included.  Next to a good libm
+ * (glibc's sinf / expf / powf are themselves double-evaluated) the results agree wherever that libm is correctly rounded.
  *
  * Both compilers MUST be run with -ffp-contract=off (hipcc defaults to 'fast').
  *
@@ -37,6 +48,17 @@
 #define RAYN_HD_CORE static __host__ __device__ __attribute__((noinline))
 #else
 #define RAYN_HD_CORE RAYN_HD
+#endif
+/* A rarely taken arm (dm_sincosf_large, dm_tanf_large): one float in, the results by value, behind an unlikely branch, and whether a
+ * call site inlines it is left to the compiler.  k_shade_setup runs at its register cap, and what this arm costs there is decided by what
+ * the allocator evicts around it, not by the arm's own instructions (it runs for no argument a shipped scene produces).  Measured on
+ * the c3 frame (k_shade_setup 1134 ms): this form +5 ms, the benchmark's headline inside its run-to-run spread; the same with a
+ * select per funnel shift in dm_sincos_large +8 ms; forced out of line (noinline, with or without `cold`) +23 ms; the reduction
+ * inlined in front of the shared dm_sincos_core +18 ms; the reduction alone out of line +29 ms. */
+#if defined(__HIPCC__)
+#define RAYN_HD_COLD static __host__ __device__ inline
+#else
+#define RAYN_HD_COLD inline
 #endif
 
 #ifndef RAYN_FMA_POLICY
@@ -166,13 +188,8 @@ RAYN_HD float dm_powf(float xf, float yf) {
     return (float)dm_exp_core(a);
 }
 
-/* sin and cos of a double; accurate for |x| up to ~1e6 (rayn's arguments are < 7). */
-RAYN_HD_CORE void dm_sincos_core(double x, double* sn, double* cs) {
-    const double TWO_OVER_PI = 6.36619772367581382433e-01;
-    const double PIO2_1 = 1.57079632673412561417e+00;  /* first 33 bits of pi/2 */
-    const double PIO2_1T = 6.07710050650619224932e-11; /* pi/2 - PIO2_1 */
-    double kf = __builtin_floor(x * TWO_OVER_PI + 0.5);
-    double r = (x - kf * PIO2_1) - kf * PIO2_1T; /* |r| <= ~pi/4 */
+/* sin and cos of q * pi/2 + r for a reduced argument |r| <= ~pi/4 and a quadrant q in 0..3. */
+RAYN_HD void dm_sincos_poly(double r, int q, double* sn, double* cs) {
     double z = r * r;
     /* sin r = r + r z (s1 + z(s2 + ...)), through r^17/17! */
     double ps = 1.0 / 355687428096000.0;
@@ -195,18 +212,97 @@ RAYN_HD_CORE void dm_sincos_core(double x, double* sn, double* cs) {
     pc = __builtin_fma(pc, z, DM_K(1.0 / 24.0));
     pc = __builtin_fma(pc, z, DM_K(-0.5));
     double C = 1.0 + z * pc;
-    long long k = (long long)kf;
-    int q = (int)(k & 3);
     if (q == 0) { *sn = S; *cs = C; }
     else if (q == 1) { *sn = C; *cs = -S; }
     else if (q == 2) { *sn = -S; *cs = -C; }
     else { *sn = -C; *cs = S; }
 }
 
-/* f32x4::sin_cos stand-in. */
+/* sin and cos of a double, |x| < 2^20 (rayn's arguments are < 7): k = round(x * 2/pi) stays below 2^20, so k * PIO2_1 (33 bits) is
+ * exact and r carries about 2^-53 * |x| of absolute error.  dm_sincosf / dm_tanf send larger arguments to dm_sincos_large. */
+RAYN_HD_CORE void dm_sincos_core(double x, double* sn, double* cs) {
+    const double TWO_OVER_PI = 6.36619772367581382433e-01;
+    const double PIO2_1 = 1.57079632673412561417e+00;  /* first 33 bits of pi/2 */
+    const double PIO2_1T = 6.07710050650619224932e-11; /* pi/2 - PIO2_1 */
+    double kf = __builtin_floor(x * TWO_OVER_PI + 0.5);
+    double r = (x - kf * PIO2_1) - kf * PIO2_1T; /* |r| <= ~pi/4 */
+    long long k = (long long)kf;                 /* |kf| < 2^20 */
+    dm_sincos_poly(r, (int)(k & 3), sn, cs);
+}
+
+/* sin and cos of a finite float with |x| >= 2^20: a Payne-Hanek reduction in integers.  x = +-m 2^e with the 24-bit significand m
+ * and e in -3..104.  2/pi = 0.b1 b2 b3.. in binary; the bits b_i with i <= e - 2 contribute multiples of 4 to x * 2/pi and are dropped, the
+ * 128 bits W = b_(e-1) .. b_(e+126) are kept (256 bits of 2/pi cover every e), and m * W mod 2^128 is x * 2/pi mod 4 in units of 2^-126:
+ * two quadrant bits and a 126-bit fraction, short of the true product by less than m 2^-126 < 2^-102.  The fraction is taken to the nearest
+ * quadrant (|f| <= 1/2), its leading 63 bits converted to binary64 (one rounding; the 2^-102 would only show for |f| < 2^-49, and the closest
+ * a binary32 comes to a multiple of pi/2 is about 2^-30 of a quadrant: Muller et al., Handbook of Floating-Point Arithmetic, "Range
+ * Reduction") and r = f * pi/2 formed with a two-piece pi/2 and one fused step: |r - true| < 2^-52 |r|.
+ * Integer operations, one int64 -> binary64 conversion, an exact scaling and one fma: the same bits from g++ and hipcc, and no
+ * conversion of an out-of-range value.  Reached only through dm_sincosf_large / dm_tanf_large below. */
+RAYN_HD void dm_sincos_large(float xf, double* sn, double* cs) {
+    const uint64_t TOP1 = 0xA2F9836E4E441529ULL, TOP2 = 0xFC2757D1F534DDC0ULL; /* floor(2/pi * 2^256), most significant word first */
+    const uint64_t TOP3 = 0xDB6295993C439041ULL, TOP4 = 0xFE5163ABDEBBC561ULL;
+    const double PIO2_H = 1.57079632679489655800e+00; /* pi/2 rounded to binary64 */
+    const double PIO2_L = 6.12323399573676603587e-17; /* pi/2 - PIO2_H */
+    const uint32_t u = dm_f2u(xf);
+    const uint64_t m = (uint64_t)((u & 0x007fffffu) | 0x00800000u);
+    const int g = (int)((u >> 23) & 0xffu) - 150 - 1 + 63; /* position of b_(e-1) in the string {64 zero bits, TOP1, TOP2, TOP3, TOP4}: 59..166 */
+    const int w = g >> 6, sh = g & 63;
+    const uint64_t w0 = w == 0 ? 0ULL : (w == 1 ? TOP1 : TOP2);
+    const uint64_t w1 = w == 0 ? TOP1 : (w == 1 ? TOP2 : TOP3);
+    const uint64_t w2 = w == 0 ? TOP2 : (w == 1 ? TOP3 : TOP4);
+    const uint64_t whi = (w0 << sh) | ((w1 >> 1) >> (63 - sh)); /* (w1 >> 1) >> (63 - sh): w1 >> (64 - sh), and 0 for sh = 0 */
+    const uint64_t wlo = (w1 << sh) | ((w2 >> 1) >> (63 - sh));
+    /* m * W mod 2^128 from 24 x 32 -> 56-bit partial products */
+    const uint64_t p0 = m * (wlo & 0xffffffffULL), p1 = m * (wlo >> 32);
+    uint64_t lo = p0 + (p1 << 32);
+    uint64_t hi = m * whi + (p1 >> 32) + (lo < p0 ? 1ULL : 0ULL);
+    int q = (int)(hi >> 62);
+    hi &= 0x3fffffffffffffffULL;
+    const bool up = (hi >> 61) != 0; /* fraction >= 1/2: the next quadrant, f = fraction - 1 < 0 */
+    if (up) {
+        q += 1;
+        hi = 0x4000000000000000ULL - hi - (lo != 0 ? 1ULL : 0ULL); /* 2^126 - (hi 2^64 + lo) */
+        lo = 0ULL - lo;
+    }
+    double f = 0.0; /* |fraction| as a binary64 */
+    if (hi != 0) {
+        const int lz = __builtin_clzll(hi); /* 2..63 */
+        const uint64_t t = (hi << (lz - 1)) | (lo >> (65 - lz)); /* leading 63 bits */
+        f = (double)(int64_t)t * dm_pow2i(-61 - lz);
+    } else if (lo != 0) {
+        const int lz = __builtin_clzll(lo);
+        f = (double)(int64_t)((lo << lz) >> 1) * dm_pow2i(-125 - lz);
+    }
+    double r = __builtin_fma(f, PIO2_H, f * PIO2_L);
+    if (up) r = -r;
+    double s, c;
+    dm_sincos_poly(r, q & 3, &s, &c);
+    *sn = (u >> 31) ? -s : s; /* sin is odd, cos even */
+    *cs = c;
+}
+
+/* The large-argument arm as dm_sincosf / dm_tanf reach it (RAYN_HD_COLD above): an early exit, the code for |x| < 2^20 stays as it was. */
+struct dm_sincos_pair { float sn, cs; };
+RAYN_HD_COLD dm_sincos_pair dm_sincosf_large(float xf) {
+    double s, c;
+    dm_sincos_large(xf, &s, &c);
+    dm_sincos_pair p;
+    p.sn = (float)s;
+    p.cs = (float)c;
+    return p;
+}
+RAYN_HD_COLD float dm_tanf_large(float xf) {
+    double s, c;
+    dm_sincos_large(xf, &s, &c);
+    return (float)(s / c);
+}
+
+/* f32x4::sin_cos stand-in: every finite float (|x| < 2^20: dm_sincos_core; above: dm_sincos_large). */
 RAYN_HD void dm_sincosf(float xf, float* sn, float* cs) {
     float ax = xf < 0.0f ? -xf : xf;
     if (dm_isnan(xf) || ax == dm_inff()) { *sn = dm_nanf(); *cs = dm_nanf(); return; }
+    if (__builtin_expect(ax >= 1048576.0f, 0)) { const dm_sincos_pair p = dm_sincosf_large(xf); *sn = p.sn; *cs = p.cs; return; }
     double s, c;
     dm_sincos_core((double)xf, &s, &c);
     *sn = xf == 0.0f ? xf : (float)s; /* sin(-0) = -0: the core's r + r * (z * ps) is +0 for r = -0 */
@@ -220,6 +316,7 @@ RAYN_HD float dm_sinf(float xf) { float s, c; dm_sincosf(xf, &s, &c); return s; 
 RAYN_HD float dm_tanf(float xf) {
     float ax = xf < 0.0f ? -xf : xf;
     if (dm_isnan(xf) || ax == dm_inff()) return dm_nanf();
+    if (__builtin_expect(ax >= 1048576.0f, 0)) return dm_tanf_large(xf);
     double s, c;
     dm_sincos_core((double)xf, &s, &c);
     return xf == 0.0f ? xf : (float)(s / c); /* tan(-0) = -0 (see dm_sincosf) */

@@ -968,7 +968,10 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *   rayn_hip_probe_shadow     the TracedSDF::occluded factors of HitableStore::test_occluded (src/hitable.rs:164-168, src/sdf.rs:25-57; the analytic spheres are
  *                             resolved by the shading kernel) through the PRODUCT shadow-march kernel (k_shadow1, k_shadow_bulb, the generic k_shadow) on a
  *                             synthetic job list of the n segments: 1.0 visible, 0.0 occluded;
- *   rayn_hip_probe_detmath    the pinned elementary functions (op 0 exp, 1 sin, 2 cos, 3 tan, 4 atan2(a,b), 5 pow(a,b)).
+ *   rayn_hip_probe_detmath    the pinned elementary functions as the kernels evaluate them (op 0 exp, 1 sin, 2 cos, 3 tan, 4 atan2(a,b), 5 pow(a,b),
+ *                             14 ln(a)) for ANY float argument: zero, denormals, infinities, NaN, and for sin / cos / tan every finite magnitude
+ *                             (above 2^20 through dm_sincos_large's integer reduction).  tests/test_detmath_device.py compares them with the
+ *                             oracle on every exponent field.
  *   Ops 6.. check the kernels' exact replacements of IEEE '/' and sqrt against the hardware IEEE
  *   result: 6 Newton-Raphson a/b, 7 IEEE a/b, 8 sqrt(a), 9/10/11 component x/y/z of v/|v| and
  *   12 |v| (a holds n xyz triples), 13 exhaustive sqrt sweep (out[i] = mismatch count over the

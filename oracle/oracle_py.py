@@ -240,6 +240,16 @@ def detmath(op, a, b=None, fma=False):
     return out
 
 
+def detmath_core(op, a, b=None, fma=False):
+    """The binary64 value the dm_* function of `op` (as detmath) hands to its final conversion to float; NaN where it answers without its core."""
+    L = lib(fma)
+    a = np.ascontiguousarray(a, np.float32)
+    b = np.ascontiguousarray(a if b is None else b, np.float32)
+    out = np.zeros(a.shape, np.float64)
+    L.oracle_detmath_core(C.c_uint32(op), _fp(a), _fp(b), out.ctypes.data_as(C.POINTER(C.c_double)), C.c_uint64(a.size))
+    return out
+
+
 # floats per lane read / written by each op of oracle_probe_shading / rayn_hip_probe_shading (op table: include/rayn_hip.h)
 SHADING_IN = (5, 2, 2, 3, 3, 2, 9, 3, 11, 5, 8, 1, 1, 8, 7)
 SHADING_OUT = (6, 2, 3, 3, 9, 1, 3, 3, 7, 4, 2, 1, 1, 1, 1)

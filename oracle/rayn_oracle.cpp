@@ -1524,6 +1524,45 @@ void oracle_detmath(uint32_t op, const float* a, const float* b, float* out, uin
         }
     }
 }
+/* The binary64 value each dm_* function hands to its final conversion to float (same ops as oracle_detmath), so that a test can measure the
+ * cores' distance from the true value instead of trusting the header's comment.  NaN where the function answers without its core
+ * (NaN / inf / zero arguments, results past the overflow / underflow thresholds, pow's libm conventions). */
+void oracle_detmath_core(uint32_t op, const float* a, const float* b, double* out, uint64_t n) {
+    const double none = (double)dm_nanf();
+    for (uint64_t i = 0; i < n; i++) {
+        const float x = a[i], y = b[i];
+        const float ax = x < 0.0f ? -x : x;
+        double r = none;
+        switch (op) {
+        case 0: if (!dm_isnan(x) && (double)x <= 89.0 && (double)x >= -104.0) r = dm_exp_core((double)x); break;
+        case 1: case 2: case 3:
+            if (!dm_isnan(x) && ax != dm_inff() && x != 0.0f) {
+                double s, c;
+                if (ax >= 1048576.0f) dm_sincos_large(x, &s, &c); else dm_sincos_core((double)x, &s, &c);
+                r = op == 1 ? s : (op == 2 ? c : s / c);
+            }
+            break;
+        case 4: { /* dm_atan2f(x = the ordinate, y = the abscissa) */
+            if (dm_isnan(x) || dm_isnan(y)) break;
+            const bool xneg = (dm_f2u(y) >> 31) != 0, yneg = (dm_f2u(x) >> 31) != 0;
+            const double dx = (double)(xneg ? -y : y), dy = (double)(yneg ? -x : x), inf = (double)dm_inff();
+            if (dx == 0.0 || dy == 0.0 || dx == inf || dy == inf) break;
+            double v = dy > dx ? 1.57079632679489655800e+00 - dm_atan_core(dx / dy) : dm_atan_core(dy / dx);
+            if (xneg) v = 3.14159265358979311600e+00 - v;
+            r = yneg ? -v : v;
+            break;
+        }
+        case 6: if (x > 0.0f && x != dm_inff()) r = dm_log_core((double)x); break;
+        default:
+            if (y != 0.0f && x != 1.0f && !dm_isnan(x) && !dm_isnan(y) && x > 0.0f && x != dm_inff()) {
+                const double e = (double)y * dm_log_core((double)x);
+                if (!dm_isnand(e) && e <= 89.0 && e >= -104.0) r = dm_exp_core(e);
+            }
+            break;
+        }
+        out[i] = r;
+    }
+}
 int oracle_fma_policy() { return RAYN_FMA_POLICY; }
 /* Counterpart of rayn_hip_probe_shading (op table, record widths and semantics: include/rayn_hip.h) through this file's OWN
  * functions, four lanes per call like the reference's packets: Camera::get_rays, the sampling maps, make_bsdf's BSDFs at a

@@ -218,3 +218,95 @@ def test_pinned_functions_are_correctly_rounded_where_binary64_decides(oracle, l
     # always by ONE ulp: glibc's sinf / cosf / tanf / atan2f are not correctly rounded, so on THIS libm a rayn build would draw equi-angular distances (src/light.rs:75-102) that differ in the last bit on
     # one call in six; what that does to a frame is oracle/SENSITIVITY.md's row A3.  Bounded only in size: a difference beyond 2 ulp would be a bug on either side.
     assert not differ.any() or _ulp_diff(lm[differ], got[differ]).max() <= 2
+
+
+# ---- every binade, against a multiprecision reference that shares nothing with the header (tests/detmath_ref.py) ----
+SWEEP_OPS = ["exp", "sin", "cos", "tan", "atan2", "pow", "log"]
+SWEEP_SEED = 7
+HARD_BOUND = 2.0 ** -49  # exp, log, sin, cos, tan, atan2: see _sweep
+_sweeps = {}
+
+
+def _sweep(name):
+    """The grid of one function, its correctly rounded results, and which points are HARD.
+
+    rayn_detmath.h evaluates every function in binary64 and converts once to float.  If the binary64 value is within a relative distance E of the true
+    value, the float can differ from the correctly rounded one only where the true value lies within E of a binary32 rounding boundary (the midpoint of two
+    consecutive floats), and then by one ulp.  A point is hard when its true value is that close; `hardness` is computed from mpmath alone.
+      exp, log, sin, cos, tan, atan2: E = 2^-49.  The cores are a reduction of a few binary64 roundings, a polynomial whose truncation is below 2^-56 and
+        at most a division, a few 2^-53 in all (test_cores_are_as_accurate_as_the_hard_bound_assumes measures 2^-51.1 .. 2^-52.8); 2^-49 leaves a factor 4.
+      pow: E = (4 |y ln x| + 8) 2^-53.  x^y = e^a with a = fl(y * L), L = dm_log_core(x) = ln x (1 + e1), |e1| <= 2.5 x 2^-53 (the roundings of 2 s p and of the two sums; measured
+        2^-52.1 on the unary grid), and the product's rounding e2, |e2| <= 2^-53: a = y ln x (1 + e1)(1 + e2), an ABSOLUTE error of at most 3.51 |y ln x| 2^-53 in the exponent, which is the
+        RELATIVE error of e^a.  dm_exp_core adds its own error on a binary64 argument (measured 2^-52.8 on floats; the reduction of a 53-bit argument costs
+        another |a| 2^-53 through a * LOG2E's k) - (4 |a| + 8) 2^-53 covers the sum.  |y ln x| reaches 104 before the result leaves the floats, so a pow
+        result carries up to 2^-44.3 of relative error: pow is NOT correctly rounded next to a tie, and this test pins where it may differ, not that it never does."""
+    if name not in _sweeps:
+        import detmath_ref as R
+        a, b = R.grid_pairs(SWEEP_SEED) if name == "atan2" else R.grid_pow(SWEEP_SEED) if name == "pow" else (R.grid_unary(SWEEP_SEED), None)
+        want, hardness = R.correctly_rounded(name, a, b), R.hardness(name, a, b)
+        if name == "pow":
+            import mpmath
+            ylnx = np.array([abs(float(mpmath.log(v))) if v is not None else 0.0 for v in R.truth(name, a, b)])  # |ln(x^y)|, from the reference alone
+            bound = (4.0 * ylnx + 8.0) * 2.0 ** -53
+        else:
+            bound = np.full(a.size, HARD_BOUND)
+        _sweeps[name] = (a, np.zeros_like(a) if b is None else b, want, hardness < bound, bound)
+    return _sweeps[name]
+
+
+def _same_bits(x, y):
+    return (x.view(np.uint32) == y.view(np.uint32)) | (np.isnan(x) & np.isnan(y))
+
+
+@pytest.mark.parametrize("fma", [False, True])
+@pytest.mark.parametrize("name", SWEEP_OPS)
+def test_pinned_functions_are_correctly_rounded_on_every_binade(oracle, name, fma):
+    """Every exponent field, both signs, the mantissas where rounding goes wrong (a power of two, one and two ulps above it, around 1.5, one and two ulps
+    below the next power) and seeded random ones - uniform draws from moderate intervals never visit most of these.  The result equals the correctly rounded
+    float bit for bit (NaN = NaN, the sign of zero compared) under both mul_add policies, except at a HARD point (_sweep), where it may be one ulp off; hard
+    points are at most 0.5 % of a grid.  sin, cos and tan run over ALL binades: the two-piece reduction of dm_sincos_core is exact only below 2^20, and until
+    dm_sincos_large existed this test failed from tan(8388610) on (|sin| > 1 from 4.1e16, inf and NaN from 5.3e18)."""
+    import detmath_ref as R
+    a, b, want, hard, _ = _sweep(name)
+    got = oracle.detmath(R.OPS[name], a, b, fma=fma)
+    off = ~_same_bits(got, want)
+    print(f"{name} (fma={fma}): {int(off.sum())} of {a.size} points differ from the correctly rounded float; {int(hard.sum())} points are hard")
+    first = np.flatnonzero(off & ~hard)[:4]
+    assert not (off & ~hard).any(), (int((off & ~hard).sum()), a[first], b[first], got[first], want[first])
+    assert hard.mean() <= 0.005, hard.mean()
+    if off.any():
+        assert not (np.isnan(got[off]) | np.isnan(want[off])).any() and _ulp_diff(got[off], want[off]).max() <= 1
+    if name in ("sin", "cos", "tan"):
+        fin = np.isfinite(a)
+        assert np.isfinite(got[fin]).all()  # (tan: no float is close enough to an odd multiple of pi / 2 to overflow)
+        if name != "tan":
+            assert (np.abs(got[fin]) <= 1.0).all()
+
+
+@pytest.mark.parametrize("name", SWEEP_OPS)
+def test_fast_functions_return_the_reference_bits_on_every_binade(oracle, name):
+    """include/rayn_detmath_fast.h (host build) on the same grids: the bits of rayn_detmath.h everywhere.  Most of a grid lies outside the fast windows by
+    design, so nothing is claimed about the fallback rate here (test_fast_functions_return_the_reference_bits does that on its own inputs)."""
+    import ctypes as C
+    import detmath_ref as R
+    a, b, _, _, _ = _sweep(name)
+    fp = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))
+    out = np.zeros_like(a)
+    st = (C.c_double * 2)()
+    oracle.lib().oracle_detmath_fast(C.c_uint32(R.OPS[name]), fp(a), fp(b), fp(out), C.c_uint64(a.size), st)
+    same = _same_bits(out, oracle.detmath(R.OPS[name], a, b))
+    assert same.all(), (int((~same).sum()), a[~same][:4], b[~same][:4])
+
+
+@pytest.mark.parametrize("name", SWEEP_OPS)
+def test_cores_are_as_accurate_as_the_hard_bound_assumes(oracle, name):
+    """Measured, not assumed: the binary64 value each dm_* function hands to its final conversion (oracle_detmath_core) against the multiprecision value,
+    max |core - truth| / |truth| over the grid, below the bound that defines a hard point.  The header's opening comment quotes these figures
+    (seed 7: exp 2^-52.8, sin 2^-51.8, cos 2^-51.8, tan 2^-51.1, atan2 2^-51.7, log 2^-52.1; pow 2^-45.2, at most 0.78 of its |y ln x| bound)."""
+    import detmath_ref as R
+    a, b, _, _, bound = _sweep(name)
+    core = oracle.detmath_core(R.OPS[name], a, b)
+    assert np.isfinite(core).sum() > a.size // 3  # the export covers the grid, not a corner of it
+    err = R.core_error(name, a, b, core)
+    print(f"{name}: max |core - truth| / |truth| = 2^{np.log2(err.max()):.2f}; largest share of the hard bound {float((err / bound).max()):.3f}")
+    assert (err < bound).all(), (float(err.max()), a[np.argmax(err / bound)], b[np.argmax(err / bound)])
