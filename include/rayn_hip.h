@@ -882,7 +882,17 @@ uint32_t rayn_tile_count(uint32_t width, uint32_t height, uint32_t tile_w, uint3
 /* timing: bracket every kernel launch with HIP events and fill rayn_stats.ms_*; count_evals: run
  * the instrumented kernel variants that count SDF distance evaluations (roofline accounting). */
 int rayn_hip_set_profiling(rayn_ctx* ctx, int timing, int count_evals);
-/* out[0] k_extend (closest-hit marches), out[1] k_shade_setup (normal estimation), out[2] k_shadow (NEE visibility) */
+/* out[0] k_extend (closest-hit marches), out[1] k_shade_setup (normal estimation), out[2] k_shadow (NEE visibility).
+ * What is counted, per ray and independent of what other lanes do (every count below is a deterministic function of the scene and the rays; the tests hold them
+ * to the CPU oracle's per-lane accounting with ==, tests/test_counters_device.py):
+ *   out[0]  every valid ray of the queue against every TracedSDF of the scene (src/hitable.rs:177-198 with the running closest hit as t_max): one evaluation
+ *           at the origin, then one per march trip of TracedSDF::hit (src/sdf.rs:59-83) up to and including the trip in which the ray stops (hit, first
+ *           distance NaN, or t > t_max), at most max_marches trips.  Analytic spheres and padding entries of the queue cost nothing.
+ *   out[1]  4 evaluations (the tetrahedral normal estimator) per valid slot whose hit object is a TracedSDF; none for padding lanes and slots on spheres.
+ *   out[2]  every PARKED shadow segment (rayn_stats.shadow_jobs) against the TracedSDFs in index order, up to and including the first that occludes it: per
+ *           TracedSDF one evaluation at the segment start, then one per trip of TracedSDF::occluded (src/sdf.rs:25-57) the segment enters - none when
+ *           max_vis_marches == 0, or once t > max_dist or the first distance was NaN.
+ * A counting context also counts in rayn_hip_probe_extend / _shadow / _shade (below): the four getters then report that probe call. */
 int rayn_hip_get_eval_counts(const rayn_ctx* ctx, uint64_t out[3]);
 /* the fold / orbit ITERATIONS those evaluations ran, same three kernels (MandelBox::dist always runs `iterations` folds, src/sdf.rs:125-141;
  * the Mandelbulb extension stops at its bailout; a sphere SDF has none): what an evaluation of the scene's own SDF costs is
@@ -891,12 +901,20 @@ int rayn_hip_get_sdf_iterations(const rayn_ctx* ctx, uint64_t out[3]);
 /* r6, same instrumented kernels: out[0] = shaded slots whose throughput was exactly (0, 0, 0) and whose NEE was therefore elided - every Le / surface / volume
  * NEE term of src/integrator.rs:70,91-92,128-129 is multiplied by that zero, so their shadow rays are never marched (k_shade_setup, exact: see the
  * kernel) - out[1] = the shadow segments those slots would have parked for TracedSDF::occluded (src/sdf.rs:25-57), out[2] = NEE samples of such
- * slots that were NOT elided because their contribution is not provably finite (then inf * 0 / NaN must keep its bits: tested and marched as ever) */
+ * slots that were NOT elided because their contribution is not provably finite (then inf * 0 / NaN must keep its bits: tested and marched as ever).
+ * The rule, per NEE sample of a VALID slot (n_lights > 0; a surface sample exists when the slot's material receives light, a volume sample when the volume
+ * scatters).  zero_w: the slot's throughput is exactly (0, 0, 0) and |vol_T| and |rho_s| are finite.  ELIDED: zero_w, and every |x_c| <= 2^60 and |pdf| >= 2^-60
+ * (surface: x = Le * f * cos * tr; volume: x_c = Le_c * tr, pdf = vpdf * lpdf, and |aux| finite too).  A sample is PARKED as a shadow job
+ * (rayn_stats.shadow_jobs) iff it is not elided, every analytic sphere's occlusion factor is 1, the scene holds a TracedSDF and - surface samples only - x is
+ * not all-zero.  out[0] counts the zero_w slots, out[1] the elided samples that would otherwise have been parked, out[2] the samples of zero_w slots that are
+ * not elided. */
 int rayn_hip_get_elision_counts(const rayn_ctx* ctx, uint64_t out[3]);
 /* r6, same instrumented kernels, single-Mandelbulb scenes only (rayn_amd/csrc/march_bulb.h; zero otherwise): the shadow-march kernel written for that SDF runs an
  * evaluation in two stages - orbit steps, then distance + one step of TracedSDF::occluded (src/sdf.rs:25-57) - each at its own occupancy.
  * out[0] / out[1] = lane slots (64 x wave executions) the orbit / epilogue stage of k_shadow_bulb offered; the lane slots USED are
- * rayn_hip_get_sdf_iterations()[2] (orbit steps) and rayn_hip_get_eval_counts()[2] (epilogues). */
+ * rayn_hip_get_sdf_iterations()[2] (orbit steps) and rayn_hip_get_eval_counts()[2] (epilogues).  Unlike every other counter these two depend on which
+ * wave wins which chunk of the job queue (they count executions of a stage per WAVE), so they differ from run to run: multiples of 64 that bound the used slots
+ * from above, and no more can be asserted of them. */
 int rayn_hip_get_stage_slots(const rayn_ctx* ctx, uint64_t out[2]);
 /* A frame's tiles are dealt to up to two workers (host thread + HIP stream + own device memory each) so that one
  * worker's HBM-bound kernels and readbacks run underneath the other's VALU-bound marches.  n_workers 1..4 (default 2).
@@ -968,6 +986,12 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *   rayn_hip_probe_shadow     the TracedSDF::occluded factors of HitableStore::test_occluded (src/hitable.rs:164-168, src/sdf.rs:25-57; the analytic spheres are
  *                             resolved by the shading kernel) through the PRODUCT shadow-march kernel (k_shadow1, k_shadow_bulb, the generic k_shadow) on a
  *                             synthetic job list of the n segments: 1.0 visible, 0.0 occluded;
+ *   COUNTING in rayn_hip_probe_extend / _shadow / _shade: while the context's count_evals is on (rayn_hip_set_profiling) these three launch the INSTRUMENTED
+ *                             instantiations of the same kernels instead (k_extend<true> / k_extend1<true, -1>; k_shadow<true> / k_shadow1<true, -1> /
+ *                             k_shadow_bulb<true, K, STEPS>; k_shade_setup<true> and the scene's shadow march), return the same outputs bit for bit, and leave
+ *                             the counters of THAT call in the context: rayn_hip_get_eval_counts / _sdf_iterations / _elision_counts / _stage_slots report it
+ *                             (the classes the call did not run are 0) until the next counted probe or frame.  With count_evals off - the default - the probes
+ *                             run the product instantiations and leave the context's counters alone.
  *   rayn_hip_probe_detmath    the pinned elementary functions as the kernels evaluate them (op 0 exp, 1 sin, 2 cos, 3 tan, 4 atan2(a,b), 5 pow(a,b),
  *                             14 ln(a)) for ANY float argument: zero, denormals, infinities, NaN, and for sin / cos / tan every finite magnitude
  *                             (above 2^20 through dm_sincos_large's integer reduction).  tests/test_detmath_device.py compares them with the

@@ -11,9 +11,24 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
+# oracle_counters::tally / the out_tally of oracle_shade_packets_counts: the PER-LANE accounting the HIP path's instrumented kernels are held to
+TALLY_KEYS = ("evals_extend", "evals_shade_setup", "evals_shadow", "iters_extend", "iters_shade_setup", "iters_shadow",
+              "zero_throughput_slots", "elided_shadow_jobs", "samples_out_of_bounds", "shadow_jobs", "sphere_blocked_samples", "jobs_first_sdf_occludes", "jobs_all_sdfs_marched")
+
+
 class Counters(C.Structure):
+    """dist_evals counts four lanes per packet call; tally (TALLY_KEYS) counts per lane: a lane is charged while it holds a ray and has not stopped."""
     _fields_ = [("paths", C.c_uint64), ("segments", C.c_uint64), ("packets", C.c_uint64),
-                ("dist_evals", C.c_uint64), ("tiles", C.c_uint64)]
+                ("dist_evals", C.c_uint64), ("tiles", C.c_uint64), ("tally", C.c_uint64 * 13)]
+
+    def lane_counts(self):
+        """The per-lane accounting of the frame as a dict over TALLY_KEYS."""
+        return {k: int(v) for k, v in zip(TALLY_KEYS, self.tally)}
+
+    def device_counts(self):
+        """What a counting HIP context reports for the same frame: (eval_counts, sdf_iterations, elision_counts, shadow_jobs)."""
+        t = [int(v) for v in self.tally]
+        return t[0:3], t[3:6], t[6:9], t[9]
 
 
 def build(force=False):
@@ -42,8 +57,10 @@ def lib(fma=False, variant=None):
     name = f"librayn_oracle_{variant}.so" if variant else ("librayn_oracle_fma.so" if fma else "librayn_oracle.so")
     if name not in _libs:
         path = os.path.join(_HERE, name)
-        if not os.path.exists(path):
-            build_variants() if variant else build()
+        if variant:
+            build_variants()  # through make every time: a variant library left from older sources lacks the entries bound below
+        elif not os.path.exists(path):
+            build()
         L = C.CDLL(path)
         fp = C.POINTER(C.c_float)
         up = C.POINTER(C.c_uint32)
@@ -62,6 +79,19 @@ def lib(fma=False, variant=None):
         L.oracle_raygen_tile.argtypes = [C.c_void_p, C.c_void_p, fp, fp, fp, fp] + [C.c_uint32] * 4 + [C.c_uint64, fp, up]
         L.oracle_shade_packets.restype = C.c_int
         L.oracle_shade_packets.argtypes = [C.c_void_p, C.c_void_p, fp, fp, C.c_uint32, C.c_uint64, up, up, fp, up, fp]
+        u64p = C.POINTER(C.c_uint64)
+        L.oracle_shade_packets_counts.restype = C.c_int
+        L.oracle_shade_packets_counts.argtypes = [C.c_void_p, C.c_void_p, fp, fp, C.c_uint32, C.c_uint64, up, up, fp, up, fp, u64p]
+        L.oracle_closest_hit_counts.restype = None
+        L.oracle_closest_hit_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, fp, fp, fp, up, up, up, C.c_uint64]
+        L.oracle_shadow_counts.restype = None
+        L.oracle_shadow_counts.argtypes = [C.c_void_p, C.c_void_p, fp, fp, fp, up, up, C.c_uint64]
+        L.oracle_set_job_sink.restype = None
+        L.oracle_set_job_sink.argtypes = [C.c_int]
+        L.oracle_take_job_sink.restype = C.c_uint64
+        L.oracle_take_job_sink.argtypes = [fp, C.c_uint64]
+        L.oracle_sdf_steps.restype = None
+        L.oracle_sdf_steps.argtypes = [C.c_void_p, fp, up, C.c_uint64]
         L.oracle_build_rd_tables.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, fp, fp]
         L.oracle_build_scramble.argtypes = [C.c_uint32, C.c_uint32, fp]
         L.oracle_build_fis_table.argtypes = [C.c_uint32, C.c_float, fp]
@@ -174,9 +204,9 @@ def trace_shade(world_desc, params, tables, tile_index, fma=False):
     return _shade_dict(pk[:n], lane_u[:n], lane_f[:n].copy(), out_u[:n], out_f[:n].copy())
 
 
-def shade_packets(world_desc, params, tables, depth, obj, valid, sample, lane_f, fma=False):
+def shade_packets(world_desc, params, tables, depth, obj, valid, sample, lane_f, fma=False, counts=False):
     """get_shading_info + Integrator::integrate on caller-built packets of one depth: obj [n], valid / sample [n, 4], lane_f [n, 4, 15] (SHADE_IN).
-    -> (status [n, 4], aov [n, 4], out_f [n, 4, 15])."""
+    -> (status [n, 4], aov [n, 4], out_f [n, 4, 15]); with counts=True a fourth item, the per-lane accounting of these packets as a dict over TALLY_KEYS."""
     L = lib(fma)
     s1, s2 = tables[0], tables[1]
     obj = np.ascontiguousarray(obj, np.uint32)
@@ -186,9 +216,12 @@ def shade_packets(world_desc, params, tables, depth, obj, valid, sample, lane_f,
     lane_u[:, :, 1] = np.asarray(sample).reshape(n, 4)
     lane_f = np.ascontiguousarray(lane_f, np.float32).reshape(n, 4, 15)
     out_u, out_f = np.zeros((n, 4, 2), np.uint32), np.zeros((n, 4, 15), np.float32)
-    rc = L.oracle_shade_packets(C.byref(world_desc), C.byref(params), _fp(s1), _fp(s2), depth, n, _up(obj), _up(lane_u), _fp(lane_f), _up(out_u), _fp(out_f))
+    tally = (C.c_uint64 * 13)()
+    rc = L.oracle_shade_packets_counts(C.byref(world_desc), C.byref(params), _fp(s1), _fp(s2), depth, n, _up(obj), _up(lane_u), _fp(lane_f), _up(out_u), _fp(out_f), tally)
     if rc != 0:
         raise ValueError(f"oracle_shade_packets failed: {rc}")
+    if counts:
+        return out_u[:, :, 0].copy(), out_u[:, :, 1].copy(), out_f, {k: int(v) for k, v in zip(TALLY_KEYS, tally)}
     return out_u[:, :, 0].copy(), out_u[:, :, 1].copy(), out_f
 
 
@@ -220,6 +253,54 @@ def closest_hit(world_desc, params, depth, org, dirs, fma=False):
     L.oracle_closest_hit(C.byref(world_desc), C.byref(params), C.c_uint32(depth), _fp(org), _fp(dirs), _fp(t), _up(obj),
                          C.c_uint64(len(org)))
     return t, obj
+
+
+def closest_hit_counts(world_desc, params, depth, org, dirs, fma=False):
+    """closest_hit + per ray the SDF evaluations of the fold over every TracedSDF and the fold / orbit steps they ran: (t, obj, evals, steps)."""
+    L = lib(fma)
+    org = np.ascontiguousarray(org, np.float32).reshape(-1, 3)
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    t = np.zeros(len(org), np.float32)
+    obj, ev, it = (np.zeros(len(org), np.uint32) for _ in range(3))
+    L.oracle_closest_hit_counts(C.byref(world_desc), C.byref(params), C.c_uint32(depth), _fp(org), _fp(dirs), _fp(t), _up(obj), _up(ev), _up(it),
+                                C.c_uint64(len(org)))
+    return t, obj, ev, it
+
+
+def shadow_counts(world_desc, params, start, end, fma=False):
+    """test_occluded + per segment what it costs as a parked shadow job: the evaluations (and their steps) of the TracedSDFs in index order, up to and
+    including the first that occludes: (visibility, evals, steps)."""
+    L = lib(fma)
+    start = np.ascontiguousarray(start, np.float32).reshape(-1, 3)
+    end = np.ascontiguousarray(end, np.float32).reshape(-1, 3)
+    out = np.zeros(len(start), np.float32)
+    ev, it = np.zeros(len(start), np.uint32), np.zeros(len(start), np.uint32)
+    L.oracle_shadow_counts(C.byref(world_desc), C.byref(params), _fp(start), _fp(end), _fp(out), _up(ev), _up(it), C.c_uint64(len(start)))
+    return out, ev, it
+
+
+def render_jobs(world_desc, params, tables, fma=False):
+    """render() on the calling thread with the job sink installed: (film, Counters, start [n, 3], end [n, 3]) - the segments of the frame's parked shadow jobs,
+    in world coordinates, in the order they were parked."""
+    L = lib(fma)
+    L.oracle_set_job_sink(1)
+    try:
+        film, ctr = render(world_desc, params, tables, threads=1, fma=fma)
+        n = int(L.oracle_take_job_sink(None, 0))
+        seg = np.zeros((n // 6, 6), np.float32)
+        L.oracle_take_job_sink(_fp(seg), n)
+    finally:
+        L.oracle_set_job_sink(0)
+    return film, ctr, seg[:, 0:3].copy(), seg[:, 3:6].copy()
+
+
+def sdf_steps(hitable, pts, fma=False):
+    """Fold / orbit steps one evaluation of the TracedSDF runs at each point."""
+    L = lib(fma)
+    pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+    out = np.zeros(len(pts), np.uint32)
+    L.oracle_sdf_steps(C.byref(hitable), _fp(pts), _up(out), C.c_uint64(len(pts)))
+    return out
 
 
 def test_occluded(world_desc, params, start, end, fma=False):

@@ -313,6 +313,33 @@ struct WShadingPoint {
 struct Counters { uint64_t paths = 0, segments = 0, packets = 0; }; /* one per worker thread */
 thread_local uint64_t tl_dist_evals = 0;
 
+/* ---- PER-LANE accounting: the reference of the HIP path's instrumented kernels (rayn_hip_get_eval_counts / _sdf_iterations / _elision_counts,
+ * rayn_stats.shadow_jobs).  Kept apart from tl_dist_evals, which counts packet calls (x 4 lanes at export).  None of it feeds back into a value the film sees.
+ * tl_steps: fold / orbit steps each lane ran in the calling thread's last SDF::dist (MandelBox: iterations; sphere: 0; Mandelbulb: the steps up to and
+ * including the bailout).  tl_last: evaluations and steps each lane was charged in the last TracedSDF::hit / occluded / get_shading_info - a lane is charged
+ * while it has not stopped; whether the lane holds a ray at all is the caller's business.  tl_tally: the running totals of a frame or of one call. */
+thread_local uint32_t tl_steps[4] = {0, 0, 0, 0};
+struct LaneTally {
+    uint32_t ev[4] = {0, 0, 0, 0}, it[4] = {0, 0, 0, 0};
+    void charge(int lanes) { for (int i = 0; i < 4; i++) if (lanes >> i & 1) { ev[i]++; it[i] += tl_steps[i]; } }
+};
+thread_local LaneTally tl_last;
+struct FrameTally {
+    uint64_t ev[3] = {0, 0, 0}, it[3] = {0, 0, 0};                  /* extend, shade setup (normals), shadow */
+    uint64_t zero_slots = 0, elided_jobs = 0, out_of_bounds = 0;     /* the elision counters, include/rayn_hip.h */
+    uint64_t jobs = 0;                                               /* parked shadow segments */
+    /* test diagnostics (no counterpart on the device): NEE samples an analytic sphere kept from being a job; jobs of a multi-SDF scene whose FIRST TracedSDF
+     * occluded (the march stopped there), and jobs marched against every TracedSDF */
+    uint64_t sphere_blocked = 0, jobs_first_sdf = 0, jobs_all_sdfs = 0;
+    void add(int cls, const LaneTally& l, int i) { ev[cls] += l.ev[i]; it[cls] += l.it[i]; }
+    void store(uint64_t out[13]) const {
+        for (int k = 0; k < 3; k++) { out[k] = ev[k]; out[3 + k] = it[k]; }
+        out[6] = zero_slots; out[7] = elided_jobs; out[8] = out_of_bounds; out[9] = jobs; out[10] = sphere_blocked; out[11] = jobs_first_sdf; out[12] = jobs_all_sdfs;
+    }
+};
+thread_local FrameTally tl_tally;
+inline void set_steps(uint32_t s) { for (int i = 0; i < 4; i++) tl_steps[i] = s; }
+
 /* ------------------------------------------------------------------ SDFs (sdfu::SDF) ------ */
 struct SDF {
     virtual ~SDF() {}
@@ -323,7 +350,7 @@ struct SDF {
 };
 struct SphereSDF : SDF { /* sdfu::Sphere (A5) */
     F4 radius;
-    F4 dist(W3 p) const override { tl_dist_evals++; return mag(p) - radius; }
+    F4 dist(W3 p) const override { tl_dist_evals++; set_steps(0); return mag(p) - radius; }
 };
 struct MandelBox : SDF { /* src/sdf.rs:104-188 */
     size_t iterations; F4 scale; W3 scale_vec;
@@ -342,7 +369,7 @@ struct MandelBox : SDF { /* src/sdf.rs:104-188 */
         p *= mul; dr *= mul;
     }
     F4 dist_with(W3 p, F4 sc) const { /* :126-140 with the scale as an argument */
-        tl_dist_evals++;
+        tl_dist_evals++; set_steps((uint32_t)iterations);
         W3 offset = p; F4 one(1.0f); F4 dr = one;
         const W3 sv = W3::broadcast(sc);
         for (size_t i = 0; i < iterations; i++) {
@@ -368,7 +395,9 @@ struct Mandelbulb : SDF {
             const float px = pp.x.v[l], py = pp.y.v[l], pz = pp.z.v[l];
             float wx = px, wy = py, wz = pz;
             float m = wx * wx + wy * wy + wz * wz, dz = 1.0f;
+            tl_steps[l] = 0;
             for (size_t i = 0; i < iterations; i++) {
+                tl_steps[l]++; /* an orbit step that runs, the bailing one included; a NaN m never bails out */
                 float m2 = m * m, m4 = m2 * m2;
                 dz = 8.0f * __builtin_sqrtf(m4 * m2 * m) * dz + 1.0f;
                 float x = wx, x2 = x * x, x4 = x2 * x2;
@@ -398,6 +427,7 @@ struct Hitable {
     virtual F4 hit(const WRay& rays, F4 t_max, const ThresholdFn& thr) const = 0;
     virtual F4 occluded(W3 start, W3 end, F4 time) const = 0;
     virtual ShadingInfo get_shading_info(const WHit& hit, const ThresholdFn& hps) const = 0;
+    virtual bool traced() const { return false; } /* accounting only: a TracedSDF, whose calls leave their per-lane charges in tl_last */
 };
 
 /* DIAGNOSTICS (tools/coherence_sim.cpp only; never set by the tests): when a sink is installed through
@@ -413,6 +443,7 @@ struct TracedSDF : Hitable {
      * Sphere's transform_seq semantics (src/sphere.rs:8-21, src/animation.rs:62-68): constant, or the closure
      * |t| center + vel * t sampled at lane 0's time.  Zero constant = the reference's behaviour (x - 0 == x). */
     V3 center{0, 0, 0}; bool animated = false; V3 center_vel{0, 0, 0};
+    bool traced() const override { return true; }
     W3 origin_at(F4 time) const {
         if (!animated) return W3::splat(center);
         float t = time.v[0];
@@ -432,6 +463,8 @@ struct TracedSDF : Hitable {
         dir = dir / max_dist;
         const float t0 = time.v[0];
         F4 dist = sdf->dist_at(start, t0);
+        LaneTally lc; lc.charge(0xF); /* one evaluation at the segment start */
+        int frozen = 0;               /* lanes a hit stopped in an earlier trip (their t no longer moves) */
         M4 nan_mask = cmp_nan(dist, dist);
         M4 gt_mask = cmp_gt(dist, max_dist);
         M4 gt_nan_mask = gt_mask | nan_mask;
@@ -443,48 +476,58 @@ struct TracedSDF : Hitable {
             if (gt_nan_mask.move_mask() == 0xF) break;
             W3 point = mul_add(dir, W3::broadcast(t), start);
             F4 d = sdf->dist_at(point, t0);
+            lc.charge(~(frozen | gt_nan_mask.move_mask()) & 0xF); /* the lanes that enter this trip */
             hit_mask = cmp_lt(abs4(d), fmax4(F4(0.0001f * cfg.detail_scale), F4(0.00001f * cfg.detail_scale) * t));
             M4 hit_gt_nan = hit_mask | gt_nan_mask;
+            frozen |= hit_gt_nan.move_mask();
             if (hit_gt_nan.move_mask() == 0xF) break;
             t = merge(hit_gt_nan, t, t + d);
         }
+        tl_last = lc;
         return merge(hit_mask & !gt_nan_mask, F4(0.0f), F4(1.0f));
     }
     F4 hit(const WRay& ray, F4 t_max, const ThresholdFn& thr) const override { /* :59-83 */
         W3 local_origin = ray.origin - origin_at(ray.time);
         const float t0 = ray.time.v[0];
         F4 dist = sdf->dist_at(local_origin, t0);
+        LaneTally lc; lc.charge(0xF); /* one evaluation at the origin */
+        int stopped = 0;              /* lanes that stopped in an earlier trip */
         F4 t = dist;
         M4 nan_mask = cmp_nan(t, t);
         for (uint32_t m = 0; m < cfg.max_marches; m++) {
             W3 point = mul_add(ray.dir, W3::broadcast(t), local_origin); /* Ray::point_at in the SDF's frame */
             F4 d = sdf->dist_at(point, t0);
+            lc.charge(~stopped & 0xF); /* up to and including the trip in which the lane stops */
             M4 hit_mask = cmp_lt(abs4(d), fmax4(F4(0.00005f * cfg.detail_scale), F4(0.05f * cfg.detail_scale) * thr(t)));
             M4 gt_mask = cmp_gt(t, t_max);
             M4 stop = hit_mask | nan_mask | gt_mask;
             t = merge(stop, t, t + d);
+            stopped |= stop.move_mask();
             if (stop.move_mask() == 0xF) break;
         }
+        tl_last = lc;
         return t;
     }
     W3 normal_at(W3 p, F4 eps, float t0) const { /* sdfu normals_fast (A5), called at src/sdf.rs:94-96 */
         F4 o(1.0f), n(-1.0f);
+        LaneTally lc; /* every evaluation of the estimator is charged to all four lanes */
+        auto dist_at = [&](W3 q, float tq) { F4 r = sdf->dist_at(q, tq); lc.charge(0xF); tl_last = lc; return r; };
 #if defined(RAYN_ORACLE_ALT_NORMALS) && RAYN_ORACLE_ALT_NORMALS == 1 /* alternative reading of A5: central differences (sdfu `normals`) */
         F4 z(0.0f);
         (void)n;
         W3 ex(eps * o, z, z), ey(z, eps * o, z), ez(z, z, eps * o);
-        W3 g(sdf->dist_at(p + ex, t0) - sdf->dist_at(p - ex, t0), sdf->dist_at(p + ey, t0) - sdf->dist_at(p - ey, t0),
-             sdf->dist_at(p + ez, t0) - sdf->dist_at(p - ez, t0));
+        W3 g(dist_at(p + ex, t0) - dist_at(p - ex, t0), dist_at(p + ey, t0) - dist_at(p - ey, t0),
+             dist_at(p + ez, t0) - dist_at(p - ez, t0));
         return normalized(g);
 #elif defined(RAYN_ORACLE_ALT_NORMALS) && RAYN_ORACLE_ALT_NORMALS == 2 /* alternative reading of A5: same estimator, other summation order */
         W3 xyy(o, n, n), yyx(n, n, o), yxy(n, o, n), xxx(o, o, o);
-        W3 g = xxx * sdf->dist_at(p + xxx * eps, t0) + xyy * sdf->dist_at(p + xyy * eps, t0) +
-               yxy * sdf->dist_at(p + yxy * eps, t0) + yyx * sdf->dist_at(p + yyx * eps, t0);
+        W3 g = xxx * dist_at(p + xxx * eps, t0) + xyy * dist_at(p + xyy * eps, t0) +
+               yxy * dist_at(p + yxy * eps, t0) + yyx * dist_at(p + yyx * eps, t0);
         return normalized(g);
 #else
         W3 xyy(o, n, n), yyx(n, n, o), yxy(n, o, n), xxx(o, o, o);
-        W3 g = xyy * sdf->dist_at(p + xyy * eps, t0) + yyx * sdf->dist_at(p + yyx * eps, t0) +
-               yxy * sdf->dist_at(p + yxy * eps, t0) + xxx * sdf->dist_at(p + xxx * eps, t0);
+        W3 g = xyy * dist_at(p + xyy * eps, t0) + yyx * dist_at(p + yyx * eps, t0) +
+               yxy * dist_at(p + yxy * eps, t0) + xxx * dist_at(p + xxx * eps, t0);
         return normalized(g);
 #endif
     }
@@ -829,13 +872,56 @@ struct World {
         has_scatter = d.has_scattering != 0; has_extinct = d.has_extinction != 0;
         rho_s = d.coeff_scattering; rho_t = d.coeff_extinction;
     }
-    /* HitableStore::test_occluded, src/hitable.rs:164-168 */
-    F4 test_occluded(W3 start, W3 end, F4 time) const {
+    uint32_t n_sdf() const { uint32_t n = 0; for (auto& h : hitables) n += h->traced(); return n; }
+    /* HitableStore::test_occluded, src/hitable.rs:164-168.  With `ot` it also reports, per lane, what a parked shadow segment costs: the product of the
+     * analytic spheres' factors, and the charges of the TracedSDFs in index order up to and including the first that occludes the lane (the reference
+     * marches them all: every factor is 0 or 1, so the product may stop). */
+    struct OccTally { F4 spheres = F4(1.0f); LaneTally sdf; uint32_t reached[4] = {0, 0, 0, 0}; /* TracedSDFs the lane was marched against */ };
+    F4 test_occluded(W3 start, W3 end, F4 time, OccTally* ot = nullptr) const {
         F4 acc(1.0f);
-        for (auto& h : hitables) acc = acc * h->occluded(start, end, time);
+        int stopped = 0;
+        for (auto& h : hitables) {
+            F4 r = h->occluded(start, end, time);
+            acc = acc * r;
+            if (!ot) continue;
+            if (!h->traced()) { ot->spheres = ot->spheres * r; continue; }
+            for (int i = 0; i < 4; i++)
+                if (!(stopped >> i & 1)) {
+                    ot->sdf.ev[i] += tl_last.ev[i]; ot->sdf.it[i] += tl_last.it[i]; ot->reached[i]++;
+                    if (r.v[i] == 0.0f) stopped |= 1 << i;
+                }
+        }
         return acc;
     }
 };
+
+/* Which NEE samples become shadow jobs, restated from the contract of rayn_hip_get_elision_counts (include/rayn_hip.h) - accounting only.
+ * zero_w: the lane holds a ray, its throughput is exactly (0, 0, 0), and |vol_T| and |rho_s| are finite.  A sample of such a lane is ELIDED when its
+ * weight is inside the bounds (the caller's in_bounds: every |x_c| <= 2^60, |pdf| >= 2^-60, and for a volume sample |aux| finite); an elided sample is
+ * never a job.  Otherwise the sample is parked iff it can matter (the caller's `matters`: a surface sample with x != 0; always for a volume sample), every
+ * analytic sphere lets it through and the scene holds a TracedSDF; only parked lanes are charged the occlusion march. */
+struct NeeLanes { bool valid[4], zero_w[4]; uint32_t n_sdf; };
+constexpr float ELIDE_MAX_X = 1152921504606846976.0f /* 2^60 */, ELIDE_MIN_PDF = 1.0f / 1152921504606846976.0f /* 2^-60 */, FINITE_MAX_F = 3.40282347e+38f;
+inline bool finite1(float x) { return __builtin_fabsf(x) <= FINITE_MAX_F; }
+/* DIAGNOSTICS (tests/test_counters.py): when a sink is installed through oracle_set_job_sink, every parked shadow job appends {start.xyz, end.xyz} in world
+ * coordinates.  Single-threaded use (render with threads = 1). */
+static std::vector<float>* g_job_sink = nullptr;
+inline void tally_nee_sample(const NeeLanes& nl, int i, bool in_bounds, bool matters, const World::OccTally& ot, const W3& start, const W3& end) {
+    if (!nl.valid[i]) return;
+    const bool elided = nl.zero_w[i] && in_bounds;
+    if (nl.zero_w[i] && !elided) tl_tally.out_of_bounds++;
+    if (!matters || nl.n_sdf == 0) return;
+    if (ot.spheres.v[i] != 1.0f) { if (!elided) tl_tally.sphere_blocked++; return; }
+    if (elided) { tl_tally.elided_jobs++; return; }
+    tl_tally.jobs++;
+    tl_tally.add(2, ot.sdf, i);
+    if (g_job_sink) {
+        const float rec[6] = {start.x.v[i], start.y.v[i], start.z.v[i], end.x.v[i], end.y.v[i], end.z.v[i]};
+        g_job_sink->insert(g_job_sink->end(), rec, rec + 6);
+    }
+    if (nl.n_sdf > 1 && ot.reached[i] == 1) tl_tally.jobs_first_sdf++;
+    if (ot.reached[i] == nl.n_sdf) tl_tally.jobs_all_sdfs++;
+}
 
 /* HitStore, src/hitable.rs:77-141 */
 struct HitStore {
@@ -850,6 +936,8 @@ void add_hits(const World& w, const WRay& ray, F4 t_max, HitStore& store, const 
     F4 closest = t_max;
     for (size_t id = 0; id < w.hitables.size(); id++) {
         F4 t = w.hitables[id]->hit(ray, closest, thr);
+        if (w.hitables[id]->traced())
+            for (int i = 0; i < 4; i++) if (ray.valid[i]) tl_tally.add(0, tl_last, i);
         for (int i = 0; i < 4; i++)
             if (t.v[i] < closest.v[i]) { closest.v[i] = t.v[i]; ids[i] = id; }
     }
@@ -862,7 +950,7 @@ enum SampleKind { S_COLOR, S_ALPHA, S_BACKGROUND, S_NORMAL };
 struct ChannelSample { uint32_t tcx, tcy; SampleKind kind; V3 v; };
 
 /* surface_sample_one_light, src/integrator.rs:207-240 */
-WSrgb surface_sample_one_light(const World& w, size_t light_idx, const F4* samples, const WShadingPoint& isect, const BSDF* bsdf) {
+WSrgb surface_sample_one_light(const World& w, size_t light_idx, const F4* samples, const WShadingPoint& isect, const BSDF* bsdf, const NeeLanes& nl) {
     W3 end_point; WSrgb li; F4 pdf;
     w.lights[light_idx].sample(samples, isect.point, &end_point, &li, &pdf);
     W3 wo = -isect.ray.dir;
@@ -870,14 +958,23 @@ WSrgb surface_sample_one_light(const World& w, size_t light_idx, const F4* sampl
     F4 dist = mag(wi);
     wi = wi / dist;
     W3 occlude_point = isect.point + isect.normal * signum4(dot(isect.normal, wi)) * isect.offset_by;
-    F4 occluded = w.test_occluded(occlude_point, end_point, isect.ray.time);
+    World::OccTally ot;
+    F4 occluded = w.test_occluded(occlude_point, end_point, isect.ray.time, &ot);
     WSrgb f = bsdf->f(wo, wi, isect.normal) * fmax4(dot(isect.normal, wi), F4(0.0f));
     F4 transmission = w.has_extinct ? exp4(F4(-w.rho_t) * dist) : F4(1.0f);
-    return li * f * transmission * occluded / pdf;
+    const WSrgb x = li * f * transmission;
+    for (int i = 0; i < 4; i++) {
+        const V3 xi = lane(x, i);
+        const bool in_bounds = __builtin_fabsf(xi.x) <= ELIDE_MAX_X && __builtin_fabsf(xi.y) <= ELIDE_MAX_X && __builtin_fabsf(xi.z) <= ELIDE_MAX_X &&
+                               __builtin_fabsf(pdf.v[i]) >= ELIDE_MIN_PDF;
+        const bool x_zero = xi.x == 0.0f && xi.y == 0.0f && xi.z == 0.0f;
+        tally_nee_sample(nl, i, in_bounds, !x_zero, ot, occlude_point, end_point);
+    }
+    return x * occluded / pdf;
 }
 /* volume_sample_one_light, src/integrator.rs:242-281 */
 WSrgb volume_sample_one_light(const World& w, size_t light_idx, const F4* light_samples, F4 volume_sample,
-                              W3 ray_o, W3 ray_d, F4 max_distance, F4 time, F4* out_t) {
+                              W3 ray_o, W3 ray_d, F4 max_distance, F4 time, F4* out_t, const NeeLanes& nl) {
     const SphereLight& light = w.lights[light_idx];
     F4 vol_sample_dist, vol_sample_pdf;
     light.sample_volume_scattering(volume_sample, ray_o, ray_d, max_distance, &vol_sample_dist, &vol_sample_pdf);
@@ -886,9 +983,21 @@ WSrgb volume_sample_one_light(const World& w, size_t light_idx, const F4* light_
     light.sample(light_samples, sampled_point, &end_point, &li, &light_pdf);
     W3 wi = end_point - sampled_point;
     F4 dist_point_to_light = mag(wi);
-    F4 occluded = w.test_occluded(sampled_point, end_point, time);
+    World::OccTally ot;
+    F4 occluded = w.test_occluded(sampled_point, end_point, time, &ot);
     F4 f = F4(1.0f) / (F4(4.0f) * F4(PI_F));
     F4 transmission = w.has_extinct ? exp4(F4(-w.rho_t) * dist_point_to_light) : F4(1.0f);
+    {
+        const F4 aux = w.has_extinct ? exp4(F4(-w.rho_t) * vol_sample_dist) : F4(1.0f); /* the transmittance to the sampled point, as integrate applies it */
+        const F4 pdf = vol_sample_pdf * light_pdf;
+        for (int i = 0; i < 4; i++) {
+            const V3 le = lane(li, i);
+            const float tr = transmission.v[i];
+            const bool in_bounds = __builtin_fabsf(le.x * tr) <= ELIDE_MAX_X && __builtin_fabsf(le.y * tr) <= ELIDE_MAX_X && __builtin_fabsf(le.z * tr) <= ELIDE_MAX_X &&
+                                   __builtin_fabsf(pdf.v[i]) >= ELIDE_MIN_PDF && finite1(aux.v[i]);
+            tally_nee_sample(nl, i, in_bounds, true, ot, sampled_point, end_point);
+        }
+    }
     *out_t = vol_sample_dist;
     return li * f * transmission * occluded / (vol_sample_pdf * light_pdf);
 }
@@ -909,13 +1018,21 @@ struct Integrator {
         F4 volume_transmission = world.has_extinct ? exp4(F4(-world.rho_t) * isect.t) : F4(1.0f);
         isect.ray.radiance += bsdf->le(wo, isect) * isect.ray.throughput * volume_transmission;
         const size_t nl = world.lights.size();
+        NeeLanes lanes; /* accounting only (tally_nee_sample) */
+        lanes.n_sdf = world.n_sdf();
+        for (int i = 0; i < 4; i++) {
+            const V3 th = lane(isect.ray.throughput, i);
+            lanes.valid[i] = isect.ray.valid[i];
+            lanes.zero_w[i] = lanes.valid[i] && th.x == 0.0f && th.y == 0.0f && th.z == 0.0f && finite1(volume_transmission.v[i]) && finite1(world.rho_s);
+            if (lanes.zero_w[i]) tl_tally.zero_slots++;
+        }
         if (bsdf->receives_light() && nl > 0) {
             F4 lts = floor4(samples_1d[0] * F4((float)nl));
             F4 correction_factor((float)nl / 4.0f);
             for (size_t i = 0; i < 4; i++) {
                 size_t light_idx = light_index(lts.v[i], nl);
                 g_sink_depth = (float)depth; g_sink_sample = (float)i;
-                WSrgb li = surface_sample_one_light(world, light_idx, &samples_2d[0 + i * 2], isect, bsdf);
+                WSrgb li = surface_sample_one_light(world, light_idx, &samples_2d[0 + i * 2], isect, bsdf, lanes);
                 isect.ray.radiance += li * isect.ray.throughput * correction_factor * volume_transmission;
             }
         }
@@ -931,7 +1048,7 @@ struct Integrator {
                     F4 t;
                     g_sink_depth = (float)depth; g_sink_sample = (float)(4 + 4 * march + i);
                     WSrgb li = volume_sample_one_light(world, light_idx, &samples_2d[8 + 8 * march + i * 2], samples_1d[1],
-                                                       isect.ray.origin, isect.ray.dir, isect.t, isect.ray.time, &t);
+                                                       isect.ray.origin, isect.ray.dir, isect.t, isect.ray.time, &t, lanes);
                     F4 transmission = world.has_extinct ? exp4(F4(-world.rho_t) * t) : F4(1.0f);
                     isect.ray.radiance += li * isect.ray.throughput * correction_factor * rho_s * transmission;
                 }
@@ -1154,6 +1271,8 @@ void integrate_tile(Tile& tile, const World& world, const Camera& camera, const 
                 WHit wh; Ray rr[4] = {hits[k].ray, hits[k + 1].ray, hits[k + 2].ray, hits[k + 3].ray};
                 wh.ray = wray_from(rr); wh.t = F4(hits[k].t, hits[k + 1].t, hits[k + 2].t, hits[k + 3].t);
                 wintersections.push_back(world.hitables[obj_id]->get_shading_info(wh, half_pixel_size_at));
+                if (world.hitables[obj_id]->traced())
+                    for (int i = 0; i < 4; i++) if (rr[i].valid) tl_tally.add(1, tl_last, i);
                 if (shade) {
                     const size_t rec = shade->pk.size() / 2; /* this packet's record */
                     shade->pk.push_back((uint32_t)depth); shade->pk.push_back((uint32_t)obj_id);
@@ -1315,7 +1434,10 @@ Config cfg_of(const rayn_frame_params& p) { return Config{p.max_marches, p.max_v
 
 extern "C" {
 
-struct oracle_counters { uint64_t paths, segments, packets, dist_evals, tiles; };
+/* dist_evals counts four lanes per packet call.  tally[13] is the per-lane accounting (FrameTally::store): [0..2] evaluations of closest hit / normals /
+ * parked shadow segments, [3..5] their fold / orbit steps, [6] zero-throughput slots, [7] elided shadow jobs, [8] samples out of bounds, [9] shadow jobs,
+ * [10..12] test diagnostics (FrameTally). */
+struct oracle_counters { uint64_t paths, segments, packets, dist_evals, tiles, tally[13]; };
 
 uint32_t oracle_sets_1d(uint32_t B, uint32_t VM) { return 1 + (B + 1) * (3 + VM); }  /* src/film.rs:431, src/integrator.rs:39-41 */
 uint32_t oracle_sets_2d(uint32_t B, uint32_t VM) { return 2 + (B + 1) * (12 + 8 * VM); } /* src/film.rs:432, src/integrator.rs:43-45 */
@@ -1348,9 +1470,12 @@ int oracle_render_frame(const rayn_world_desc* wd, const rayn_frame_params* p, c
     else { uint32_t step = p->tile_step ? p->tile_step : 1; for (uint32_t k = 0; k < tiles.size(); k++) if ((k + k / step) % step == p->tile_first) todo.push_back(k); }
     FilmOut film{out_color, out_alpha, out_background, out_normal};
     std::atomic<size_t> next{0}; std::atomic<uint64_t> evals{0}, n_paths{0}, n_segments{0}, n_packets{0};
+    std::atomic<uint64_t> tally[13];
+    for (auto& t : tally) t = 0;
     auto worker = [&]() {
         Counters ctr;
         tl_dist_evals = 0;
+        tl_tally = FrameTally();
         for (;;) {
             size_t i = next.fetch_add(1);
             if (i >= todo.size()) break;
@@ -1360,10 +1485,12 @@ int oracle_render_frame(const rayn_world_desc* wd, const rayn_frame_params* p, c
             tile_finished(tile, film, p->width, (size_t)p->samples * 4); /* disjoint pixels: no mutex needed */
         }
         evals += tl_dist_evals; n_paths += ctr.paths; n_segments += ctr.segments; n_packets += ctr.packets;
+        uint64_t mine[13]; tl_tally.store(mine);
+        for (int k = 0; k < 13; k++) tally[k] += mine[k];
     };
     if (threads <= 1) worker();
     else { std::vector<std::thread> th; for (int i = 0; i < threads; i++) th.emplace_back(worker); for (auto& t : th) t.join(); }
-    if (counters) { counters->paths = n_paths; counters->segments = n_segments; counters->packets = n_packets; counters->dist_evals = evals * 4; counters->tiles = todo.size(); }
+    if (counters) { counters->paths = n_paths; counters->segments = n_segments; counters->packets = n_packets; counters->dist_evals = evals * 4; counters->tiles = todo.size(); for (int k = 0; k < 13; k++) counters->tally[k] = tally[k]; }
     return 0;
 }
 
@@ -1432,9 +1559,17 @@ int64_t oracle_trace_shade(const rayn_world_desc* wd, const rayn_frame_params* p
  * out_f in the ShadeSink layout (tcx / tcy of lane_u are not read: lane i of a packet gets tcx = i, which maps its outputs back).  An invalid lane is
  * Ray::new_invalid with hit t 0, as process_hits pads.  Returns 0, -1 for bad parameters, -2 for an object or sample out of range, -3 when the outputs
  * of a call could not be mapped back. */
+int oracle_shade_packets_counts(const rayn_world_desc* wd, const rayn_frame_params* p, const float* s1d, const float* s2d, uint32_t depth, uint64_t n_packets,
+                                const uint32_t* obj, const uint32_t* lane_u, const float* lane_f, uint32_t* out_u, float* out_f, uint64_t* out_tally);
 int oracle_shade_packets(const rayn_world_desc* wd, const rayn_frame_params* p, const float* s1d, const float* s2d, uint32_t depth, uint64_t n_packets,
                          const uint32_t* obj, const uint32_t* lane_u, const float* lane_f, uint32_t* out_u, float* out_f) {
+    return oracle_shade_packets_counts(wd, p, s1d, s2d, depth, n_packets, obj, lane_u, lane_f, out_u, out_f, nullptr);
+}
+/* the same; out_tally[13] (may be NULL) = the per-lane accounting of these packets in the layout of oracle_counters::tally ([0] and [3], the closest hit, stay 0) */
+int oracle_shade_packets_counts(const rayn_world_desc* wd, const rayn_frame_params* p, const float* s1d, const float* s2d, uint32_t depth, uint64_t n_packets,
+                                const uint32_t* obj, const uint32_t* lane_u, const float* lane_f, uint32_t* out_u, float* out_f, uint64_t* out_tally) {
     if (!wd || !p || p->volume_marches < 2 || p->volume_marches > 4 || p->samples == 0) return -1;
+    tl_tally = FrameTally();
     World world(*wd, cfg_of(*p));
     Camera camera(wd->camera);
     Integrator integ{p->max_bounces, p->volume_marches};
@@ -1455,12 +1590,15 @@ int oracle_shade_packets(const rayn_world_desc* wd, const rayn_frame_params* p, 
         }
         WHit wh; wh.ray = wray_from(rr); wh.t = F4(t[0], t[1], t[2], t[3]);
         ShadingInfo si = world.hitables[obj[k]]->get_shading_info(wh, half_pixel_size_at);
+        if (world.hitables[obj[k]]->traced())
+            for (int i = 0; i < 4; i++) if (rr[i].valid) tl_tally.add(1, tl_last, i);
         F4 s1[3 + 4], s2[12 + 8 * 4];
         fetch_packet_samples(sets, si.sp.ray, depth, p->volume_marches, s1, s2);
         spawned.clear(); samples.clear();
         integ.integrate(world, s1, s2, depth, si.material, si.sp, spawned, samples);
         if (!shade_lanes_out(rr, spawned.data(), spawned.size(), samples.data(), samples.size(), out_u + 8 * k, out_f + 4 * SHADE_LANE_FLOATS * k)) return -3;
     }
+    if (out_tally) tl_tally.store(out_tally);
     return 0;
 }
 
@@ -1486,8 +1624,16 @@ void oracle_sdf_dist_at(const rayn_hitable* h, float t0, const float* pts, float
 }
 /* closest hit of the whole world for n rays at 'depth' (threshold closure of src/film.rs:540-551):
  * out_t, out_obj (0xFFFFFFFF = none) — HitableStore::add_hits without the bins. */
+void oracle_closest_hit_counts(const rayn_world_desc* wd, const rayn_frame_params* p, uint32_t depth, const float* org, const float* dir, float* out_t,
+                               uint32_t* out_obj, uint32_t* out_evals, uint32_t* out_steps, uint64_t n);
 void oracle_closest_hit(const rayn_world_desc* wd, const rayn_frame_params* p, uint32_t depth, const float* org,
                         const float* dir, float* out_t, uint32_t* out_obj, uint64_t n) {
+    oracle_closest_hit_counts(wd, p, depth, org, dir, out_t, out_obj, nullptr, nullptr, n);
+}
+/* the same; out_evals / out_steps (may be NULL) = per ray, the SDF evaluations of the fold over every TracedSDF of the world and the fold / orbit steps they
+ * ran.  The ray is splatted over the four lanes, so the packet's count is the ray's own (lane 0's charges). */
+void oracle_closest_hit_counts(const rayn_world_desc* wd, const rayn_frame_params* p, uint32_t depth, const float* org, const float* dir, float* out_t,
+                               uint32_t* out_obj, uint32_t* out_evals, uint32_t* out_steps, uint64_t n) {
     World w(*wd, cfg_of(*p)); Camera cam(wd->camera);
     ThresholdFn thr;
     if (depth == 0) thr = [&cam](F4 t) { return cam.half_pixel_size_at(t); };
@@ -1496,11 +1642,15 @@ void oracle_closest_hit(const rayn_world_desc* wd, const rayn_frame_params* p, u
         WRay r; r.origin = W3(F4(org[3 * i]), F4(org[3 * i + 1]), F4(org[3 * i + 2]));
         r.dir = W3(F4(dir[3 * i]), F4(dir[3 * i + 1]), F4(dir[3 * i + 2])); r.time = F4(0.0f);
         F4 closest(p->world_radius * 2.0f); uint32_t id = 0xFFFFFFFFu;
+        uint32_t ev = 0, it = 0;
         for (size_t k = 0; k < w.hitables.size(); k++) {
             F4 t = w.hitables[k]->hit(r, closest, thr);
+            if (w.hitables[k]->traced()) { ev += tl_last.ev[0]; it += tl_last.it[0]; }
             if (t.v[0] < closest.v[0]) { closest = F4(t.v[0]); id = (uint32_t)k; }
         }
         out_t[i] = closest.v[0]; out_obj[i] = id;
+        if (out_evals) out_evals[i] = ev;
+        if (out_steps) out_steps[i] = it;
     }
 }
 /* HitableStore::test_occluded for n segments */
@@ -1509,6 +1659,29 @@ void oracle_test_occluded(const rayn_world_desc* wd, const rayn_frame_params* p,
     for (uint64_t i = 0; i < n; i++)
         out[i] = w.test_occluded(W3(F4(start[3 * i]), F4(start[3 * i + 1]), F4(start[3 * i + 2])),
                                  W3(F4(end[3 * i]), F4(end[3 * i + 1]), F4(end[3 * i + 2])), F4(0.0f)).v[0];
+}
+/* the same visibility; out_evals / out_steps = per segment, what the segment costs as a parked shadow job: the evaluations (and their fold / orbit steps) of
+ * the world's TracedSDFs in index order, up to and including the first that occludes (World::test_occluded's OccTally) */
+void oracle_shadow_counts(const rayn_world_desc* wd, const rayn_frame_params* p, const float* start, const float* end, float* out, uint32_t* out_evals,
+                          uint32_t* out_steps, uint64_t n) {
+    World w(*wd, cfg_of(*p));
+    for (uint64_t i = 0; i < n; i++) {
+        World::OccTally ot;
+        out[i] = w.test_occluded(W3(F4(start[3 * i]), F4(start[3 * i + 1]), F4(start[3 * i + 2])),
+                                 W3(F4(end[3 * i]), F4(end[3 * i + 1]), F4(end[3 * i + 2])), F4(0.0f), &ot).v[0];
+        out_evals[i] = ot.sdf.ev[0]; out_steps[i] = ot.sdf.it[0];
+    }
+}
+/* fold / orbit steps one evaluation of the TracedSDF runs at each point (tl_steps of lane 0); 0 for a hitable that is no TracedSDF */
+void oracle_sdf_steps(const rayn_hitable* h, const float* pts, uint32_t* out, uint64_t n) {
+    rayn_world_desc wd; memset(&wd, 0, sizeof wd); wd.n_hitables = 1; wd.hitables[0] = *h;
+    World w(wd, Config{256, 100, 0.5f});
+    const TracedSDF* t = dynamic_cast<const TracedSDF*>(w.hitables[0].get());
+    for (uint64_t i = 0; i < n; i++) {
+        if (!t) { out[i] = 0; continue; }
+        t->sdf->dist(W3(F4(pts[3 * i]), F4(pts[3 * i + 1]), F4(pts[3 * i + 2])));
+        out[i] = tl_steps[0];
+    }
 }
 /* rayn_detmath probes so tests can compare host and device bit patterns: op 0 exp,1 sin,2 cos,3 tan,4 atan2(a,b),5 pow(a,b) */
 void oracle_detmath(uint32_t op, const float* a, const float* b, float* out, uint64_t n) {
@@ -1741,6 +1914,18 @@ int oracle_save_to_pixels(uint32_t kind, int have_color, int have_alpha, int hav
 void oracle_set_shadow_sink(int on) {
     delete g_shadow_sink;
     g_shadow_sink = on ? new std::vector<float>() : nullptr;
+}
+/* DIAGNOSTICS: install (on != 0) / remove the sink of parked shadow jobs (records of 6 floats: start, end); oracle_take_job_sink copies up to cap floats and
+ * returns the float count */
+void oracle_set_job_sink(int on) {
+    delete g_job_sink;
+    g_job_sink = on ? new std::vector<float>() : nullptr;
+}
+uint64_t oracle_take_job_sink(float* out, uint64_t cap) {
+    if (!g_job_sink) return 0;
+    const uint64_t n = g_job_sink->size();
+    if (out) memcpy(out, g_job_sink->data(), (size_t)std::min(n, cap) * 4);
+    return n;
 }
 uint64_t oracle_take_shadow_sink(float* out, uint64_t cap) {
     if (!g_shadow_sink) return 0;

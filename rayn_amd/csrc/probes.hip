@@ -36,6 +36,14 @@ static int probe_common(rayn_ctx* ctx, const rayn_frame_params* p, DScene* out_h
     if (out_hs) *out_hs = hs;
     return RAYN_OK;
 }
+// count_evals on (rayn_hip_set_profiling): what a probe's instrumented launch left in its d_ev[16], decoded into the context's counters as a frame's
+// read-back is (Counters::decode) - the four getters then report that probe call
+static int probe_counters(rayn_ctx* ctx, const unsigned long long* d_ev) {
+    unsigned long long h[16];
+    HIPCHK(hipMemcpy(h, d_ev, sizeof h, hipMemcpyDeviceToHost));
+    ctx->counters.decode(h);
+    return RAYN_OK;
+}
 int rayn_hip_probe_sdf_dist(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t hitable_index, const float* pts, float* out, uint32_t n) {
     int rc = probe_common(ctx, p);
     if (rc) return rc;
@@ -136,9 +144,11 @@ int rayn_hip_probe_extend(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t de
     Pool pool;
     memset(&pool, 0, sizeof pool);
     pool.geo0 = d_g0.as<float4>(); pool.geo1 = d_g1.as<float4>(); pool.col1 = d_c1.as<float4>();
-    K.extend(ctx->stream, false, ctx->d_scene, depth, d_q.as<uint32_t>(), npad, pool, d_obj.as<uint8_t>(), single_sdf, d_ctl.as<DCtl>(), d_ev.as<unsigned long long>(), tun);
+    const bool count = ctx->cfg->counting; // the instrumented instantiation; the context's counters then report this call
+    K.extend(ctx->stream, count, ctx->d_scene, depth, d_q.as<uint32_t>(), npad, pool, d_obj.as<uint8_t>(), single_sdf, d_ctl.as<DCtl>(), d_ev.as<unsigned long long>(), tun);
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipGetLastError());
+    if (count) { rc = probe_counters(ctx, d_ev.as<unsigned long long>()); if (rc) return rc; }
     std::vector<uint8_t> obj(npad);
     HIPCHK(hipMemcpy(g1.data(), d_g1.p, (size_t)n * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(obj.data(), d_obj.p, npad, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; i++) {
@@ -182,9 +192,11 @@ int rayn_hip_probe_shadow(rayn_ctx* ctx, const rayn_frame_params* p, const float
     Nee nee;
     memset(&nee, 0, sizeof nee);
     nee.vis = d_vis.as<uint8_t>(); nee.t0 = d_t0.as<float>(); nee.cap = n; nee.job_ref = d_ref.as<uint32_t>(); nee.job_geo = d_geo.as<float2>(); nee.jobcap = n;
-    K.shadow_march(ctx->stream, false, ctx->d_scene, nee, n, single_sdf, d_ctl.as<DCtl>(), d_ev.as<unsigned long long>(), tun);
+    const bool count = ctx->cfg->counting; // the instrumented instantiation; the context's counters then report this call
+    K.shadow_march(ctx->stream, count, ctx->d_scene, nee, n, single_sdf, d_ctl.as<DCtl>(), d_ev.as<unsigned long long>(), tun);
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipGetLastError());
+    if (count) { rc = probe_counters(ctx, d_ev.as<unsigned long long>()); if (rc) return rc; }
     std::vector<uint8_t> vis(n);
     HIPCHK(hipMemcpy(vis.data(), d_vis.p, n, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; i++) out[i] = vis[i] == 1 ? 1.0f : 0.0f;
@@ -463,10 +475,12 @@ int rayn_hip_probe_shade(rayn_ctx* ctx, const rayn_frame_params* p, const float*
     nee.x = d_x.as<float>(); nee.vtr = d_vtr.as<float>(); nee.pdf = d_pdf.as<float>(); nee.aux = d_aux.as<float>(); nee.vis = d_vis.as<uint8_t>();
     nee.vpicks = d_picks.as<unsigned long long>(); nee.T = d_T.as<float>(); nee.t0 = d_t0.as<float>(); nee.nthr = d_nthr.as<float>(); nee.flags = d_flags.as<uint8_t>();
     nee.cap = CAP; nee.job_ref = d_jref.as<uint32_t>(); nee.job_geo = d_jgeo.as<float2>(); nee.jobcap = JOBCAP;
-    K.shade(s, false, ctx->d_scene, tab, d_scr.as<float>(), depth, d_bq.as<uint32_t>(), max_slots, pool, nee, NS, hs.n_sdf > 0, single_sdf,
+    const bool count = ctx->cfg->counting; // the instrumented instantiations; the context's counters then report this call
+    K.shade(s, count, ctx->d_scene, tab, d_scr.as<float>(), depth, d_bq.as<uint32_t>(), max_slots, pool, nee, NS, hs.n_sdf > 0, single_sdf,
             d_alive.as<unsigned long long>(), d_cnt.as<uint8_t>(), d_ctl.as<DCtl>(), d_ev.as<unsigned long long>(), ShadeHooks{nullptr, nullptr, nullptr}, tun);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
+    if (count) { rc = probe_counters(ctx, d_ev.as<unsigned long long>()); if (rc) return rc; }
     HIPCHK(hipMemcpy(&hc, d_ctl.p, sizeof hc, hipMemcpyDeviceToHost));
     if ((uint64_t)hc.job_count > (uint64_t)NS * n_slots) return fail(ctx, RAYN_ERR_HIP, "internal: job_count exceeds ns * n_slots");
     if (CAP > n_slots) { // the surplus of every NEE plane: no word at a slot index in [n_slots, nee_cap) may have changed

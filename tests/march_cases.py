@@ -157,8 +157,39 @@ def oracle_test_occluded_mt(oracle, wd, p, a, b, threads=None):
     return out
 
 
+def oracle_closest_hit_counts_mt(oracle, wd, p, depth, org, d, threads=None, fma=False):
+    """oracle.closest_hit_counts over contiguous blocks of the rays on a thread pool (see oracle_closest_hit_mt): (t, obj, evals, steps) per ray."""
+    n = len(org)
+    parts = _blocks(n, 4 * (threads or cpus()))
+    t = np.empty(n, np.float32)
+    obj, ev, it = (np.empty(n, np.uint32) for _ in range(3))
+
+    def run(r):
+        lo, hi = r
+        t[lo:hi], obj[lo:hi], ev[lo:hi], it[lo:hi] = oracle.closest_hit_counts(wd, p, depth, org[lo:hi], d[lo:hi], fma=fma)
+    with ThreadPoolExecutor(threads or cpus()) as ex:
+        list(ex.map(run, parts))
+    return t, obj, ev, it
+
+
+def oracle_shadow_counts_mt(oracle, wd, p, a, b, threads=None, fma=False):
+    """oracle.shadow_counts over contiguous blocks of the segments on a thread pool: (visibility, evals, steps) per segment."""
+    n = len(a)
+    parts = _blocks(n, 4 * (threads or cpus()))
+    out = np.empty(n, np.float32)
+    ev, it = np.empty(n, np.uint32), np.empty(n, np.uint32)
+
+    def run(r):
+        lo, hi = r
+        out[lo:hi], ev[lo:hi], it[lo:hi] = oracle.shadow_counts(wd, p, a[lo:hi], b[lo:hi], fma=fma)
+    with ThreadPoolExecutor(threads or cpus()) as ex:
+        list(ex.map(run, parts))
+    return out, ev, it
+
+
 def probe_world(name, sdf_only=False, **kw):
-    """(world_desc, frame_params) of a probe scene: a rayn_amd.setup.SCENES tag or "two_sdfs" (two TracedSDFs: the generic kernels); sdf_only drops the
+    """(world_desc, frame_params) of a probe scene: a rayn_amd.setup.SCENES tag, "two_sdfs" (two further TracedSDFs: the generic kernels) or "offset_sdf" /
+    "moving_sdf" (tests/test_gpu_parity.py: a TracedSDF whose origin is a constant / a closure of time - the probes run at time 0); sdf_only drops the
     analytic spheres, as rayn_hip_probe_shadow marches the TracedSDF factors only; kw = frame parameters (march budgets)."""
     import rayn_amd as R
     from rayn_amd import params as P
@@ -167,8 +198,11 @@ def probe_world(name, sdf_only=False, **kw):
         cam, world = S.setup((64, 64), volumes=False, sdf="mandelbox")  # test_gpu_parity's "two_sdfs": a sphere SDF before the MandelBox, a second MandelBox after it
         world.hitables.insert(1, R.TracedSDF(R.SphereSDF(0.35), 1))
         world.hitables.push(R.TracedSDF(R.MandelBox(6, R.BoxFold(1.0), R.SphereFold(0.5, 1.0), -2.0), 1))
-    else:
+    elif name in S.SCENES:
         cam, world = S.SCENES[name]((64, 64))
+    else:
+        from test_gpu_parity import _custom_scene
+        cam, world = _custom_scene(name, (64, 64))
     if sdf_only:
         world.hitables[:] = [h for h in world.hitables if isinstance(h, R.TracedSDF)]
     return world.to_desc(cam), P.frame_params(64, 64, 1, 3, **kw)
@@ -187,28 +221,55 @@ def _key(kind, name, kw, seed, n, extra=()):
     return (kind, name, tuple(sorted(kw.items())), seed, n) + tuple(extra)
 
 
-def occluded_case(oracle, name, kw, seed, n):
-    """(wd, p, a, b, ref) for rayn_hip_probe_shadow on segments(n, seed) of scene `name`; the oracle runs once per (scene, params, seed, n)."""
+def occluded_case(oracle, name, kw, seed, n, fma=False):
+    """(wd, p, a, b, ref) for rayn_hip_probe_shadow on segments(n, seed) of scene `name`; the oracle runs once per (scene, params, seed, n, policy), and the
+    same call leaves the per-segment counts for occluded_counts()."""
     wd, p = probe_world(name, sdf_only=True, **kw)
     a, b = segments(n, seed)
-    key = _key("occ", name, kw, seed, n)
+    key = _key("occ", name, kw, seed, n, (bool(fma),))
     if key not in _results:
-        ref = oracle_test_occluded_mt(oracle, wd, p, a, b)
-        ref.setflags(write=False)
-        _results[key] = ref
-    return wd, p, a, b, _results[key]
+        ref, ev, it = oracle_shadow_counts_mt(oracle, wd, p, a, b, fma=fma)
+        for x in (ref, ev, it):
+            x.setflags(write=False)
+        _results[key] = (ref, ev, it)
+    return wd, p, a, b, _results[key][0]
 
 
-def closest_hit_case(oracle, name, depth, kw, seed, n):
-    """(wd, p, org, d, ref_t, ref_obj) for rayn_hip_probe_extend on rays(n, seed) of scene `name`; the oracle runs once per (scene, params, depth, seed, n)."""
+def occluded_counts(name, kw, seed, n, fma=False):
+    """(evaluations, fold / orbit steps) the instrumented shadow-march kernel must report for occluded_case(...): the sums of the oracle's per-segment counts"""
+    _, ev, it = _results[_key("occ", name, kw, seed, n, (bool(fma),))]
+    return int(ev.sum(dtype=np.uint64)), int(it.sum(dtype=np.uint64))
+
+
+def closest_hit_case(oracle, name, depth, kw, seed, n, fma=False):
+    """(wd, p, org, d, ref_t, ref_obj) for rayn_hip_probe_extend on rays(n, seed) of scene `name`; the oracle runs once per (scene, params, depth, seed, n,
+    policy), and the same call leaves the per-ray counts for closest_hit_counts()."""
     wd, p = probe_world(name, **kw)
     org, d = rays(n, seed)
-    key = _key("hit", name, kw, seed, n, (depth,))
+    key = _key("hit", name, kw, seed, n, (depth, bool(fma)))
     if key not in _results:
-        t, obj = oracle_closest_hit_mt(oracle, wd, p, depth, org, d)
-        t.setflags(write=False); obj.setflags(write=False)
-        _results[key] = (t, obj)
-    return (wd, p, org, d) + _results[key]
+        res = oracle_closest_hit_counts_mt(oracle, wd, p, depth, org, d, fma=fma)
+        for x in res:
+            x.setflags(write=False)
+        _results[key] = res
+    return (wd, p, org, d) + _results[key][:2]
+
+
+def closest_hit_counts(name, depth, kw, seed, n, fma=False):
+    """(evaluations, fold / orbit steps) the instrumented extend kernel must report for closest_hit_case(...): the sums of the oracle's per-ray counts"""
+    _, _, ev, it = _results[_key("hit", name, kw, seed, n, (depth, bool(fma)))]
+    return int(ev.sum(dtype=np.uint64)), int(it.sum(dtype=np.uint64))
+
+
+def counted(ctx, fn, *args):
+    """fn(ctx, *args) through the instrumented instantiations (rayn_hip_set_profiling's count_evals; the probes then report into the context's counters):
+    (result, eval_counts, sdf_iterations, elision_counts, stage_slots).  Counting is off again afterwards, whatever happens."""
+    ctx.set_profiling(False, True)
+    try:
+        out = fn(ctx, *args)
+        return out, ctx.eval_counts(), ctx.sdf_iterations(), ctx.elision_counts(), ctx.stage_slots()
+    finally:
+        ctx.set_profiling(False, False)
 
 
 def same_t(t, rt):

@@ -237,14 +237,20 @@ def sphere_occluded(h, a, b, t0):  # src/sphere.rs:24-46: 0 occluded, 1 not
     return np.where(valid, f32(0.0), f32(1.0)).astype(f32)
 
 
-def sdf_hit(h, o, d, t_max, thr_at, ds_, max_marches, t0):  # src/sdf.rs:59-83 (+ EXTENSION: the SDF's frame is translated by its origin)
+def sdf_hit(h, o, d, t_max, thr_at, ds_, max_marches, t0, evals=None):  # src/sdf.rs:59-83 (+ EXTENSION: the SDF's frame is translated by its origin)
+    """evals (an integer array, one entry per lane) is ADDED the SDF evaluations each lane is charged: one at the origin, then one per march trip up to and
+    including the trip in which the lane stops - a lane that is `done` rides along in the packet loop for nothing."""
     o = vsub(o, sphere_center(h, t0))
     t = mandelbox_dist(o, h, t0)
+    if evals is not None:
+        evals += 1
     nan = np.isnan(t)
     done = np.zeros(len(t), bool)
     for _ in range(max_marches):
         pt = [mul_add(d[c], t, o[c]) for c in range(3)]
         di = mandelbox_dist(pt, h, t0)
+        if evals is not None:
+            evals += ~done
         hit = np.abs(di) < smax(np.full_like(t, f32(0.00005) * f32(ds_)), (f32(f32(0.05) * f32(ds_)) * thr_at(t)).astype(f32))
         stop = hit | nan | (t > t_max)
         t = np.where(stop | done, t, (t + di).astype(f32))  # a stopped lane is idempotent in the packet loop
@@ -254,13 +260,17 @@ def sdf_hit(h, o, d, t_max, thr_at, ds_, max_marches, t0):  # src/sdf.rs:59-83 (
     return t
 
 
-def sdf_occluded(h, a, b, ds_, max_vis, t0):  # src/sdf.rs:25-57 (+ EXTENSION: both ends in the SDF's frame)
+def sdf_occluded(h, a, b, ds_, max_vis, t0, evals=None):  # src/sdf.rs:25-57 (+ EXTENSION: both ends in the SDF's frame)
+    """evals (an integer array, one entry per lane) is ADDED the SDF evaluations each lane is charged: one at the segment start, then one per trip the lane
+    enters - none once it is frozen, or while its t is past the segment or its first distance was NaN."""
     org = sphere_center(h, t0)
     a, b = vsub(a, org), vsub(b, org)
     dirv = vsub(b, a)
     max_dist = mag(dirv)
     dirv = vdiv(dirv, max_dist)
     dist = mandelbox_dist(a, h, t0)
+    if evals is not None:
+        evals += 1
     nan = np.isnan(dist)
     gt_nan = (dist > max_dist) | nan
     hit = dist < f32(0.0001)
@@ -272,6 +282,8 @@ def sdf_occluded(h, a, b, ds_, max_vis, t0):  # src/sdf.rs:25-57 (+ EXTENSION: b
             break
         pt = [mul_add(dirv[c], t, a[c]) for c in range(3)]
         di = mandelbox_dist(pt, h, t0)
+        if evals is not None:
+            evals += ~(frozen | gt_nan)
         hit_new = np.abs(di) < smax(np.full_like(t, f32(0.0001) * f32(ds_)), (f32(f32(0.00001) * f32(ds_)) * t).astype(f32))
         hit = np.where(frozen | gt_nan, hit, hit_new)
         stop = hit | gt_nan

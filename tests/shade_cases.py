@@ -164,6 +164,25 @@ def expect(case, fma=False):
     return oracle_py.shade_packets(sc["wd"], sc["p"], sc["tabs"], case["depth"], case["obj"], case["valid"], case["sample"], case["lane_f"], fma=fma)
 
 
+def expect_tally(case, fma=False, tile_to=None):
+    """The oracle's per-lane accounting of a case (dict over oracle_py.TALLY_KEYS): normal and shadow evaluations with their fold / orbit steps, the three
+    elision counters, the parked shadow jobs.  tile_to = the slot count to_pool() repeats the packets to (slot j = lane j % 4 of packet (j // 4) % n): the tally
+    of each unique packet times how often the tiling holds it."""
+    from oracle import oracle_py
+    sc = scene(case["scene"])
+    run = lambda sl: oracle_py.shade_packets(sc["wd"], sc["p"], sc["tabs"], case["depth"], case["obj"][sl], case["valid"][sl], case["sample"][sl], case["lane_f"][sl],
+                                             fma=fma, counts=True)[3]
+    n = len(case["obj"])
+    if tile_to is None:
+        return run(slice(0, n))
+    times = np.bincount(np.arange(tile_to // 4) % n, minlength=n)
+    total = dict.fromkeys(oracle_py.TALLY_KEYS, 0)
+    for k in range(n):
+        for key, v in run(slice(k, k + 1)).items():
+            total[key] += int(times[k]) * v
+    return total
+
+
 # ------------------------------------------------------------------------------------------------------------------------------ mutated cases
 
 def _take(case, idx, **change):

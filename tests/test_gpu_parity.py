@@ -427,7 +427,11 @@ def test_bulb_march_kernel_variants_are_invisible(oracle, monkeypatch):
                 ev, it, slots = ctx.eval_counts(), ctx.sdf_iterations(), ctx.stage_slots()
                 ctx.set_profiling(False, False)
                 assert film_equal_bits(out, ref)
+                # evaluations and orbit steps are the oracle's per-lane tallies exactly; the stage slots depend on which wave wins which chunk and stay bounds
+                want_ev, want_it, _, want_jobs = ctr.device_counts()
+                assert list(ev.values()) == want_ev and list(it.values()) == want_it and ctx.stats()["shadow_jobs"] == want_jobs, (ev, it, want_ev, want_it)
                 assert 0 < it["shadow"] <= slots["shadow_orbit"] and 0 < ev["shadow"] <= slots["shadow_epilogue"], (ev, it, slots)
+                assert slots["shadow_orbit"] % 64 == 0 and slots["shadow_epilogue"] % 64 == 0
         finally:
             ctx.close()
             for k in env:
@@ -474,19 +478,21 @@ def test_tile_partition_union(gpu_ctx, oracle):
 
 
 def test_instrumented_variant_matches(gpu_ctx, oracle):
-    """The eval-counting kernel variants (roofline accounting) produce the same film and a plausible count."""
+    """The eval-counting kernel variants (roofline accounting) produce the same film and the oracle's per-lane counts, exactly."""
     wd, p = case("s1", 48, 32, 1, 2)
     tabs = _tables(oracle, p)
     ref, ctr = oracle.render(wd, p, tabs)
     gpu_ctx.upload_world(wd)
     gpu_ctx.set_profiling(True, True)
     out = gpu_ctx.render_host(p, tabs)
-    ev = gpu_ctx.eval_counts()
+    ev, it = gpu_ctx.eval_counts(), gpu_ctx.sdf_iterations()
     st = gpu_ctx.stats()
     gpu_ctx.set_profiling(False, False)
     assert film_equal_bits(out, ref)
-    assert all(v > 0 for v in ev.values())
-    assert sum(ev.values()) <= ctr.dist_evals  # oracle counts all 4 lanes of every packet call
+    want_ev, want_it, _, want_jobs = ctr.device_counts()  # the oracle's per-lane tallies (tests/test_counters.py checks them on their own)
+    assert all(v > 0 for v in want_ev)
+    assert list(ev.values()) == want_ev and list(it.values()) == want_it and st["shadow_jobs"] == want_jobs, (ev, it, want_ev, want_it)
+    assert sum(ev.values()) <= ctr.dist_evals  # dist_evals counts all 4 lanes of every packet call
     assert st["ms_extend"] > 0 and st["ms_shade"] > 0 and st["ms_shadow"] > 0
 
 
@@ -623,6 +629,8 @@ def test_zero_throughput_elision_counts_and_fallback(gpu_ctx, oracle):
         out = gpu_ctx.render_host(p, tabs)
         el, st = gpu_ctx.elision_counts(), gpu_ctx.stats()
         assert film_equal_bits(out, ref) and st["segments"] == ctr.segments
+        want_el, want_jobs = ctr.device_counts()[2:]  # the oracle's restatement of the elision rule, per lane
+        assert list(el.values()) == want_el and st["shadow_jobs"] == want_jobs, (el, want_el, st["shadow_jobs"], want_jobs)
         assert 0 < el["zero_throughput_slots"] < st["segments"] and el["elided_shadow_jobs"] > 0 and el["samples_out_of_bounds"] == 0, el
         gpu_ctx.set_profiling(False, False)
         jobs_counted = st["shadow_jobs"]
@@ -642,6 +650,8 @@ def test_zero_throughput_elision_counts_and_fallback(gpu_ctx, oracle):
         assert st["segments"] == ctr.segments
         assert film_equal_bits(out, ref)  # NaNs compare equal whatever their payload (common.bits_equal), everything else bit for bit
         assert np.array_equal(np.isnan(out["color"]), np.isnan(ref["color"]))
+        want_el, want_jobs = ctr.device_counts()[2:]
+        assert list(el.values()) == want_el and st["shadow_jobs"] == want_jobs, (el, want_el, st["shadow_jobs"], want_jobs)
         assert el["samples_out_of_bounds"] > 0 and el["zero_throughput_slots"] > 0, el
     finally:
         gpu_ctx.set_profiling(False, False)

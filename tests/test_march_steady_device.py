@@ -61,6 +61,26 @@ def check_shadow(ctx, oracle, name, kw, n):
     bad = out != ref
     print(name, kw, "n", n, "mismatches", int(bad.sum()), "occluded share", 1.0 - float(ref.mean()))
     assert not bad.any(), M.describe_mismatches(bad, M._SEG_SLOTS, M.SEG_CLASSES)
+    return out
+
+
+def check_shadow_counted(ctx, oracle, name, kw, n):
+    """check_shadow + ONE launch of the instrumented instantiation on the same segments: the same visibility, and evaluations / fold or orbit steps equal to the
+    sums of the per-segment counts the oracle call of check_shadow left (march_cases.occluded_counts).  In steady state a lane holds a spare segment while its
+    current one has ended, or K - 1 further ones: an evaluation charged to a lane without a current segment, or an orbit carried into the next round and charged
+    twice, shows here and at no smaller size.  The stage slots of k_shadow_bulb depend on which wave wins which chunk: inequalities."""
+    out = check_shadow(ctx, oracle, name, kw, n)
+    wd, p, a, b, _ = M.occluded_case(oracle, name, kw, SEG_SEED, n)
+    got, ev, it, el, slots = M.counted(ctx, M.probe_shadow, p, a, b)
+    want_ev, want_it = M.occluded_counts(name, kw, SEG_SEED, n)
+    print(name, "counted: evals", ev, "iterations", it, "want", want_ev, want_it, "slots", slots)
+    assert np.array_equal(got, out)
+    assert ev == {"extend": 0, "shade_setup": 0, "shadow": want_ev} and it == {"extend": 0, "shade_setup": 0, "shadow": want_it}
+    assert not any(el.values())
+    if name == "bulb":
+        assert slots["shadow_orbit"] % 64 == 0 and slots["shadow_epilogue"] % 64 == 0 and it["shadow"] <= slots["shadow_orbit"] and ev["shadow"] <= slots["shadow_epilogue"]
+    else:
+        assert not any(slots.values())
 
 
 def check_extend(ctx, oracle, name, depth, kw, n):
@@ -71,6 +91,20 @@ def check_extend(ctx, oracle, name, depth, kw, n):
     print(name, depth, kw, "n", n, "object mismatches", int(bad_obj.sum()), "t mismatches", int(bad_t.sum()))
     assert not bad_obj.any(), "objects: " + M.describe_mismatches(bad_obj, M._RAY_SLOTS, M.RAY_CLASSES)
     assert not bad_t.any(), "t: " + M.describe_mismatches(bad_t, M._RAY_SLOTS, M.RAY_CLASSES)
+    return t, obj
+
+
+def check_extend_counted(ctx, oracle, name, depth, kw, n):
+    """check_extend + ONE launch of the instrumented instantiation on the same rays (see check_shadow_counted; the INVALID padding entries at the queue's end
+    and the NaN / far corner classes are in it)."""
+    t, obj = check_extend(ctx, oracle, name, depth, kw, n)
+    wd, p, org, d, _, _ = M.closest_hit_case(oracle, name, depth, kw, RAY_SEED, n)
+    (ct, cobj), ev, it, el, slots = M.counted(ctx, M.probe_extend, p, depth, org, d)
+    want_ev, want_it = M.closest_hit_counts(name, depth, kw, RAY_SEED, n)
+    print(name, depth, "counted: evals", ev, "iterations", it, "want", want_ev, want_it)
+    assert np.array_equal(cobj, obj) and np.array_equal(ct.view(np.uint32), t.view(np.uint32))
+    assert ev == {"extend": want_ev, "shade_setup": 0, "shadow": 0} and it == {"extend": want_it, "shade_setup": 0, "shadow": 0}
+    assert not any(el.values()) and not any(slots.values())
 
 
 # ---- a. the default context: 2 048 persistent blocks, default thresholds ----------------------------------------------------------------------
@@ -84,14 +118,14 @@ def test_limits_probe(gpu_ctx):
 @pytest.mark.parametrize("name,depth", [("s1", 0), ("s1", 2), ("s0", 0), ("bulb", 0)])
 def test_extend_steady_default(gpu_ctx, oracle, name, depth):
     """k_extend1 (MandelBox in its shipped-shape instantiation, sphere SDF, Mandelbulb) with every wave of the full grid fetching in steady state."""
-    check_extend(gpu_ctx, oracle, name, depth, {}, _n(gpu_ctx))
+    (check_extend_counted if (name, depth) == ("s1", 0) else check_extend)(gpu_ctx, oracle, name, depth, {}, _n(gpu_ctx))  # + k_extend1<true, -1> in steady state
 
 
 @pytest.mark.parametrize("name", ["s1", "s0", "bulb"])
 def test_shadow_steady_default(gpu_ctx, oracle, name):
     """k_shadow1 (MandelBox, sphere SDF) and k_shadow_bulb (three rays per lane: its threshold is 3 x ENDGAME_ENTRIES) on the full grid."""
     k = M.march_limits(gpu_ctx)[3] if name == "bulb" else 1
-    check_shadow(gpu_ctx, oracle, name, {}, _n(gpu_ctx, k))
+    (check_shadow_counted if name in ("s1", "bulb") else check_shadow)(gpu_ctx, oracle, name, {}, _n(gpu_ctx, k))  # + k_shadow1<true, -1> / k_shadow_bulb<true, K, STEPS>
 
 
 # ---- b. tuned contexts, one at a time ---------------------------------------------------------------------------------------------------------------
@@ -199,7 +233,7 @@ def test_whole_path_at_size(gpu_ctx, oracle, monkeypatch, name):
     rows = FILM_H // p.tile_h
     n_tiles = (FILM_W // p.tile_w) * rows
     subset = np.unique(np.linspace(0, n_tiles - 1, 32).astype(np.uint32))
-    ref, _ = oracle.render(wd, p, tabs, threads=M.cpus(), tile_subset=subset)
+    ref, ctr = oracle.render(wd, p, tabs, threads=M.cpus(), tile_subset=subset)
     for t in subset:
         tx, ty = int(t) // rows, int(t) % rows  # reference tile order: column-major
         sl = (slice(ty * p.tile_h, (ty + 1) * p.tile_h), slice(tx * p.tile_w, (tx + 1) * p.tile_w))
@@ -218,6 +252,18 @@ def test_whole_path_at_size(gpu_ctx, oracle, monkeypatch, name):
     assert all(v > 0 for v in ev.values())
     if name == "bulbm":
         assert 0 < it["shadow"] <= slots["shadow_orbit"] and 0 < ev["shadow"] <= slots["shadow_epilogue"], (ev, it, slots)
+    # the counters exactly, where the oracle was run: the sampled tiles alone (tiles are independent), counted, against the tallies of the same oracle call
+    gpu_ctx.set_tile_subset(subset)
+    gpu_ctx.set_profiling(False, True)
+    try:
+        gpu_ctx.render_host(p, tabs)
+        sub = (list(gpu_ctx.eval_counts().values()), list(gpu_ctx.sdf_iterations().values()), list(gpu_ctx.elision_counts().values()), gpu_ctx.stats()["shadow_jobs"])
+    finally:
+        gpu_ctx.set_profiling(False, False)
+        gpu_ctx.set_tile_subset(None)
+    print(name, "sampled tiles: counted", sub, "oracle", ctr.device_counts())
+    assert sub == ctr.device_counts()
+    assert all(0 < sub[0][k] < v for k, v in enumerate(ev.values()))
     for env in FILM_ENVS[name]:
         with tuned_ctx(monkeypatch, env) as ctx:
             ctx.upload_world(wd)

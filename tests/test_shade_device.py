@@ -34,7 +34,8 @@ def run(ctx, name, case, fma, max_extra=0, nee_extra=NEE_EXTRA, tile_to=None):
     print(f"{name} policy {fma}: n_slots {n} max_slots {n + max_extra} nee_cap {n + nee_extra} valid lanes {len(pool['P'])} shadow kernel {got['shadow_kernel']} "
           f"job_count {got['job_count']} differing words {total}")
     assert total == 0, msgs
-    assert got["shadow_jobs"] == got["job_count"] <= sc["ns"] * n
+    # the parked segments are the oracle's count exactly (its restatement of the parking rule, per lane: tests/test_counters.py)
+    assert got["shadow_jobs"] == got["job_count"] == SC.expect_tally(case, bool(fma), tile_to)["shadow_jobs"] <= sc["ns"] * n
     return got
 
 
