@@ -21,8 +21,8 @@ def frame_case(name, bounces):
     from common import case
     if name in S.SCENES:
         return case(name, FRAME_W, FRAME_H, FRAME_SAMPLES, bounces)
-    from test_gpu_parity import _custom_world
-    return _custom_world(name, (FRAME_W, FRAME_H)), P.frame_params(FRAME_W, FRAME_H, FRAME_SAMPLES, bounces)
+    from scenes import custom_world
+    return custom_world(name, (FRAME_W, FRAME_H)), P.frame_params(FRAME_W, FRAME_H, FRAME_SAMPLES, bounces)
 
 
 _frames = {}

@@ -201,8 +201,8 @@ def probe_world(name, sdf_only=False, **kw):
     elif name in S.SCENES:
         cam, world = S.SCENES[name]((64, 64))
     else:
-        from test_gpu_parity import _custom_scene
-        cam, world = _custom_scene(name, (64, 64))
+        from scenes import custom_scene
+        cam, world = custom_scene(name, (64, 64))
     if sdf_only:
         world.hitables[:] = [h for h in world.hitables if isinstance(h, R.TracedSDF)]
     return world.to_desc(cam), P.frame_params(64, 64, 1, 3, **kw)

@@ -145,6 +145,7 @@ def check_coverage(ref, has_sdf):
 
 
 # ---- scenes ------------------------------------------------------------------------------------------------------------------------------
+# Not built on scenes.scene: the resting sphere, the morphing scale and the Mandelbulb's orthographic size make other world descriptions.
 def scene(name, res, camera="pinhole", moving=False):
     """(world description, world, camera handle).  spheres: no TracedSDF - a sphere resting on a ground sphere with a smaller one resting
     against it, under the sky dome; s1: the shipped MandelBox; bulb: the Mandelbulb; multi: MandelBox + a sphere SDF; every SDF scene gets

@@ -1,9 +1,10 @@
 """Inputs shared by tests/test_temporal_resample.py (CPU) and tests/test_temporal_resample_device.py (GPU): adversarial frames and histories
-in the manner of test_temporal_device._random_inputs, but with object REGIONS instead of per-pixel random objects, a sub-two-pixel
+in the manner of temporal_cases.random_inputs, but with object REGIONS instead of per-pixel random objects, a sub-two-pixel
 reprojection and a defect density low enough that whole 4x4 footprints survive - so that the restatement sends a sizeable share of the
 pixels down each of the three arms (reset, bilinear fallback, Catmull-Rom).  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this."""
 import numpy as np
 
+import scenes
 import temporal_np as T
 
 f32 = np.float32
@@ -58,11 +59,10 @@ def adversarial_inputs(seed, cam_kind, w=W, h=H):
 
 
 def moving_world(res=(40, 24)):
-    """(world description, its hitables as temporal_np.accumulate takes them): test_temporal_device's moving scene - the fractal (object 1)
+    """(world description, its hitables as temporal_np.accumulate takes them): scenes.scene's moving s1 - the fractal (object 1)
     and one sphere are animated - with the velocities cut to a tenth, so that over the half second between the two frames object motion
     shifts the footprints by a fraction of a pixel instead of tearing them apart."""
-    from test_temporal_device import _scene
-    wd, _, _ = _scene("s1", res, moving=True)
+    wd, _, _ = scenes.scene("s1", res, moving=True)
     for i in range(wd.n_hitables):
         for c in "xyz":
             setattr(wd.hitables[i].center_vel, c, 0.1 * getattr(wd.hitables[i].center_vel, c))

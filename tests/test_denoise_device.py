@@ -10,7 +10,9 @@ import numpy as np
 import pytest
 
 import denoise_np
+import device_io as IO
 from common import case
+from denoise_cases import random_film
 from rayn_amd import image
 
 pytestmark = pytest.mark.gpu
@@ -24,19 +26,8 @@ def _scratch_bytes(w, h):
     return F.denoise_scratch_bytes(w, h)
 
 
-def _random_film(w, h, seed):
-    rng = np.random.default_rng(seed)
-    n = w * h
-    color = rng.gamma(0.6, 0.5, (n, 3)).astype(np.float32)
-    normal = rng.normal(size=(n, 3)).astype(np.float32)
-    normal /= np.maximum(np.linalg.norm(normal, axis=1, keepdims=True), 1e-6)
-    alpha = rng.choice(np.array([0.0, 0.25, 1.0, 1.0, 1.0], np.float32), n)
-    normal[alpha == 0] = 0.0  # background pixels carry no normal, as the film has them
-    return {"color": color, "alpha": alpha, "normal": normal}
-
-
 def _adversarial(w, h, seed):
-    f = _random_film(w, h, seed)
+    f = random_film(w, h, seed)
     special = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 3.0e38, -3.0e38, 1e-45, -np.nan, 1e30], np.float32)
     rng = np.random.default_rng(seed + 100)
     for key in ("color", "normal", "alpha"):
@@ -45,11 +36,6 @@ def _adversarial(w, h, seed):
         flat[idx] = np.resize(special, idx.size)
     f["normal"][rng.choice(w * h, max(1, w * h // 10), replace=False)] = 0.0  # zero normals
     return f
-
-
-def _device(film):
-    import torch
-    return {k: torch.from_numpy(np.ascontiguousarray(v, np.float32).reshape(-1)).cuda() for k, v in film.items()}
 
 
 def _run(ctx, film_d, w, h, L, sigmas, stream=None):
@@ -61,20 +47,11 @@ def _run(ctx, film_d, w, h, L, sigmas, stream=None):
         d["normal"] = film_d["normal"]
     if sigmas[2]:
         d["alpha"] = film_d["alpha"]
-    out = torch.full((w * h * 3 + 16,), 7.0, dtype=torch.float32, device="cuda")  # 16 guard floats after the image
+    full, out = IO.guarded(w * h * 3, torch.float32, 7.0, 16)  # 16 guard floats after the image
     ctx.denoise(w, h, d, out, Denoise(L, *sigmas), stream=stream)
     torch.cuda.synchronize()
-    got = out.cpu().numpy()
-    assert np.all(got[w * h * 3:] == 7.0), "the kernel wrote past the output"
-    return got[: w * h * 3].reshape(-1, 3)
-
-
-def _assert_bits_equal(got, want, what):
-    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), (what, "NaN positions differ")
-    bad = (got.view(np.uint32) != want.view(np.uint32)) & ~gn
-    assert not bad.any(), (what, int(bad.sum()), got[bad][:4], want[bad][:4])
+    IO.assert_guards(full, w * h * 3, 7.0, "the output")
+    return out.cpu().numpy().reshape(-1, 3)
 
 
 def _restated(film, w, h, L, sigmas):
@@ -83,26 +60,26 @@ def _restated(film, w, h, L, sigmas):
 
 def test_every_shape_pass_count_and_term_combination(gpu_ctx, oracle):
     for si, (w, h) in enumerate(SHAPES):
-        film = _random_film(w, h, si)
-        d = _device(film)
+        film = random_film(w, h, si)
+        d = IO.upload_film(film)
         runs = [(L, SIGMAS[(L + si) % 8]) for L in range(1, 9)] + [(3, s) for s in SIGMAS]  # steps up to 128: larger than every image
         for L, sigmas in runs:
-            _assert_bits_equal(_run(gpu_ctx, d, w, h, L, sigmas), _restated(film, w, h, L, sigmas), (w, h, L, sigmas))
+            IO.assert_bits_equal(_run(gpu_ctx, d, w, h, L, sigmas), _restated(film, w, h, L, sigmas), (w, h, L, sigmas))
 
 
 def test_adversarial_films(gpu_ctx, oracle):
     for seed, (w, h) in enumerate([(1, 1), (7, 1), (17, 13), (33, 65)]):
         film = _adversarial(w, h, seed)
-        d = _device(film)
+        d = IO.upload_film(film)
         for L, sigmas in [(1, (0.5, 0.4, 0.3)), (4, (0.5, 0.4, 0.3)), (2, (2.0 ** -30, 2.0 ** 30, 0.3)), (3, (2.0 ** 30, 0.0, 2.0 ** -30)),
                           (5, (0.0, 0.0, 0.0)), (8, (0.5, 0.0, 0.3))]:
-            _assert_bits_equal(_run(gpu_ctx, d, w, h, L, sigmas), _restated(film, w, h, L, sigmas), (w, h, L, sigmas))
+            IO.assert_bits_equal(_run(gpu_ctx, d, w, h, L, sigmas), _restated(film, w, h, L, sigmas), (w, h, L, sigmas))
     # the inputs are not modified
     film = _adversarial(33, 65, 9)
-    d = _device(film)
+    d = IO.upload_film(film)
     _run(gpu_ctx, d, 33, 65, 5, (0.5, 0.4, 0.3))
     for k, v in film.items():
-        assert np.array_equal(d[k].cpu().numpy().view(np.uint32), v.reshape(-1).view(np.uint32)), k
+        IO.assert_is_host(d[k], v, k)
 
 
 def test_oracle_and_gpu_rendered_films(gpu_ctx, oracle):
@@ -119,10 +96,10 @@ def test_oracle_and_gpu_rendered_films(gpu_ctx, oracle):
     for name, film in (("oracle", rendered), ("gpu", on_gpu)):
         film = {"color": np.asarray(film["color"], np.float32).reshape(-1, 3), "alpha": np.asarray(film["alpha"], np.float32).reshape(-1),
                 "normal": np.asarray(film["normal"], np.float32).reshape(-1, 3)}
-        d = _device(film)
+        d = IO.upload_film(film)
         for L, sigmas in [(5, (0.5, 0.4, 0.3)), (2, (1.0, 0.1, 0.0)), (3, (0.0, 0.4, 0.3))]:
             got = _run(gpu_ctx, d, 40, 24, L, sigmas)
-            _assert_bits_equal(got, _restated(film, 40, 24, L, sigmas), (name, L, sigmas))
+            IO.assert_bits_equal(got, _restated(film, 40, 24, L, sigmas), (name, L, sigmas))
             assert not np.array_equal(got, film["color"])
 
 
@@ -131,10 +108,10 @@ def test_entry_is_stream_ordered(gpu_ctx, oracle):
     import torch
     from rayn_amd import Denoise
     w, h = 640, 360
-    film = _random_film(w, h, 5)
+    film = random_film(w, h, 5)
     film["background"] = np.zeros((w * h, 3), np.float32)
     want = image.color_image(_restated(film, w, h, 3, (0.5, 0.4, 0.3)).reshape(h, w, 3), background=film["background"].reshape(h, w, 3))
-    src = _device(film)
+    src = IO.upload_film(film)
     torch.cuda.synchronize()
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
@@ -154,13 +131,13 @@ def test_entry_is_stream_ordered(gpu_ctx, oracle):
 
 def test_multi_device_context_runs_on_the_first_device(oracle):
     import rayn_amd
-    film = _random_film(33, 17, 2)
+    film = random_film(33, 17, 2)
     ctx = rayn_amd.Context([0, 0])
     try:
-        got = _run(ctx, _device(film), 33, 17, 4, (0.5, 0.4, 0.3))
+        got = _run(ctx, IO.upload_film(film), 33, 17, 4, (0.5, 0.4, 0.3))
     finally:
         ctx.close()
-    _assert_bits_equal(got, _restated(film, 33, 17, 4, (0.5, 0.4, 0.3)), "multi-device")
+    IO.assert_bits_equal(got, _restated(film, 33, 17, 4, (0.5, 0.4, 0.3)), "multi-device")
 
 
 def test_bad_arguments_return_invalid_arg_with_a_text(gpu_ctx):
@@ -168,7 +145,7 @@ def test_bad_arguments_return_invalid_arg_with_a_text(gpu_ctx):
     from rayn_amd import _lib
     L = _lib.lib()
     w, h = 5, 3
-    d = _device(_random_film(w, h, 1))
+    d = IO.upload_film(random_film(w, h, 1))
     out = torch.zeros(w * h * 3, dtype=torch.float32, device="cuda")
     need = _scratch_bytes(w, h)
     scratch = torch.zeros(need + 16, dtype=torch.uint8, device="cuda")
@@ -218,18 +195,6 @@ def _small_scene(w, h):
     return R, cam, world, R.PathTracingIntegrator(max_bounces=3, volume_marches=2), R.BlackmanHarrisFilter(1.5)
 
 
-def _png_bytes(tmp_path, img):
-    p = tmp_path / "ref.png"
-    image.save(str(p), img)
-    return p.read_bytes()
-
-
-def _host_film(film):
-    K = type(film.channel_kinds[0])
-    return {"color": film.channel(K.Color), "alpha": film.channel(K.Alpha), "background": film.channel(K.Background),
-            "normal": film.channel(K.WorldNormal)}
-
-
 def test_save_to_with_denoise(tmp_path, oracle):
     W, H = 48, 32
     R, cam, world, integ, filt = _small_scene(W, H)
@@ -237,28 +202,28 @@ def test_save_to_with_denoise(tmp_path, oracle):
     params = R.Denoise(4, 0.5, 0.4, 0.3)
     film = R.Film([K.Color, K.Alpha, K.Background, K.WorldNormal], (W, H))
     film.render_frame_into(world, cam, integ, filt, (16, 16), 2, None, 2)
-    host = _host_film(film)
+    host = IO.host_film(film)
     restated = denoise_np.atrous(host["color"], host["alpha"], host["normal"], W, H, 4, 0.5, 0.4, 0.3).reshape(H, W, 3)
-    _assert_bits_equal(film.denoised_color(params).cpu().numpy().reshape(H, W, 3), restated, "denoised_color")
+    IO.assert_bits_equal(film.denoised_color(params).cpu().numpy().reshape(H, W, 3), restated, "denoised_color")
     for transparent in (False, True):
         out = tmp_path / f"t{int(transparent)}"
         film.save_to([K.Color, K.Alpha, K.WorldNormal], str(out), "x", transparent, denoise=params)
         assert sorted(os.listdir(out)) == ["x_alpha.png", "x_color_denoised.png", "x_normal.png"]
         want = (image.color_image(restated, alpha=host["alpha"], transparent_background=True) if transparent
                 else image.color_image(restated, background=host["background"]))
-        assert (out / "x_color_denoised.png").read_bytes() == _png_bytes(tmp_path, want)
-        assert (out / "x_alpha.png").read_bytes() == _png_bytes(tmp_path, image.alpha_image(host["alpha"]))
-        assert (out / "x_normal.png").read_bytes() == _png_bytes(tmp_path, image.normal_image(host["normal"]))
+        assert (out / "x_color_denoised.png").read_bytes() == IO.png_bytes(tmp_path, want)
+        assert (out / "x_alpha.png").read_bytes() == IO.png_bytes(tmp_path, image.alpha_image(host["alpha"]))
+        assert (out / "x_normal.png").read_bytes() == IO.png_bytes(tmp_path, image.normal_image(host["normal"]))
         assert np.array_equal(film.pixels(K.Color, transparent, denoise=params), want)
     # denoise=None is save_to as before
     film.save_to([K.Color], str(tmp_path / "plain"), "x")
     assert os.listdir(tmp_path / "plain") == ["x_color.png"]
-    assert (tmp_path / "plain" / "x_color.png").read_bytes() == _png_bytes(tmp_path, image.color_image(host["color"], background=host["background"]))
+    assert (tmp_path / "plain" / "x_color.png").read_bytes() == IO.png_bytes(tmp_path, image.color_image(host["color"], background=host["background"]))
     # a guide the film lacks is switched off; a film without Color cannot be denoised
     no_normal = R.Film([K.Color, K.Alpha, K.Background], (W, H))
     no_normal.render_frame_into(world, cam, integ, filt, (16, 16), 2, None, 2)
     restated = denoise_np.atrous(no_normal.channel(K.Color), no_normal.channel(K.Alpha), None, W, H, 4, 0.5, 0.0, 0.3)
-    _assert_bits_equal(no_normal.denoised_color(params).cpu().numpy(), restated, "no WorldNormal")
+    IO.assert_bits_equal(no_normal.denoised_color(params).cpu().numpy(), restated, "no WorldNormal")
     no_color = R.Film([K.Alpha, K.WorldNormal], (W, H))
     no_color.render_frame_into(world, cam, integ, filt, (16, 16), 2, None, 2)
     with pytest.raises(ValueError, match="Color"):
@@ -283,8 +248,7 @@ def test_sequence_with_denoise_equals_the_plain_loop(tmp_path, oracle):
     loop = tmp_path / "loop"
     f32 = np.float32
     for frame in FRAMES:
-        start = f32(frame) * (f32(1.0) / f32(RATE))
-        plain.render_frame_into(world, cam, integ, filt, (16, 16), frame, (float(start), float(f32(start + f32(SHUTTER)))), 2)
+        plain.render_frame_into(world, cam, integ, filt, (16, 16), frame, IO.shutter_range(frame, RATE, SHUTTER), 2)
         plain.save_to([K.Alpha, K.WorldNormal, K.Color], str(loop), f"a_{frame:04d}", denoise=params)
     assert sorted(os.listdir(loop)) == sorted(os.listdir(seq))
     for name in os.listdir(loop):
@@ -305,8 +269,8 @@ def test_denoiser_lowers_the_error_of_the_shipped_scene_at_8_spp():
     for samples in (2, 256):
         films[samples] = R.Film([K.Color, K.Alpha, K.Background, K.WorldNormal], (W, H))
         films[samples].render_frame_into(world, cam, integ, filt, S.TILE_SIZE, 1, None, samples)
-    ref = _host_film(films[256])
-    noisy = _host_film(films[2])
+    ref = IO.host_film(films[256])
+    noisy = IO.host_film(films[2])
     sat = lambda c: np.clip(c.astype(np.float64) + noisy["background"], 0.0, 1.0)
     want = np.clip(ref["color"].astype(np.float64) + ref["background"], 0.0, 1.0)
     mse = lambda c: float(np.mean((sat(c) - want) ** 2))

@@ -13,7 +13,9 @@ import pytest
 
 import denoise_np
 import denoise_variance_np as VN
+import device_io as IO
 import progressive_np as PN
+from denoise_cases import random_film
 from rayn_amd import image
 
 pytestmark = pytest.mark.gpu
@@ -28,17 +30,6 @@ GUARD = 16
 def _params(w, h, tile):
     import rayn_amd as R
     return R.frame_params(w, h, 1, 3, tile_size=tile)
-
-
-def _random_film(w, h, seed):
-    rng = np.random.default_rng(seed)
-    n = w * h
-    color = rng.gamma(0.6, 0.5, (n, 3)).astype(np.float32)
-    normal = rng.normal(size=(n, 3)).astype(np.float32)
-    normal /= np.maximum(np.linalg.norm(normal, axis=1, keepdims=True), 1e-6)
-    alpha = rng.choice(np.array([0.0, 0.25, 1.0, 1.0, 1.0], np.float32), n)
-    normal[alpha == 0] = 0.0  # background pixels carry no normal, as the film has them
-    return {"color": color, "alpha": alpha, "normal": normal}
 
 
 def _random_state(w, h, tile, seed):
@@ -62,7 +53,7 @@ SPECIAL = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 3.0e38, -3.0e38, 1e-45, 
 
 
 def _adversarial(w, h, tile, seed):
-    film, state = _random_film(w, h, seed), _random_state(w, h, tile, seed)
+    film, state = random_film(w, h, seed), _random_state(w, h, tile, seed)
     rng = np.random.default_rng(seed + 100)
     for arr in (film["color"], film["normal"], film["alpha"], state["m2"]):
         flat = arr.reshape(-1)
@@ -72,17 +63,12 @@ def _adversarial(w, h, tile, seed):
     return film, state
 
 
-def _device(film):
-    import torch
-    return {k: torch.from_numpy(np.ascontiguousarray(v, np.float32).reshape(-1)).cuda() for k, v in film.items()}
-
-
 def _device_state(state, w, h, tile):
     import torch
     from rayn_amd import progressive as P
     raw = P.join_state(state, w, h, tile)
-    d = torch.full((raw.size + 64,), 0xA5, dtype=torch.uint8, device="cuda")
-    d[: raw.size] = torch.from_numpy(raw).cuda()
+    d, view = IO.guarded(raw.size, torch.uint8, 0xA5, 64)
+    view.copy_(torch.from_numpy(raw))
     return d
 
 
@@ -97,26 +83,14 @@ def _run(ctx, film_d, d_state, w, h, tile, L, sigmas, stream=None, variance=True
     if sigmas[2]:
         d["alpha"] = film_d["alpha"]
     n = w * h
-    out = torch.full((n * 3 + GUARD,), 7.0, dtype=torch.float32, device="cuda")  # guard floats after the image
-    var = torch.full((n + GUARD,), 7.0, dtype=torch.float32, device="cuda") if variance else None
+    full_out, out = IO.guarded(n * 3, torch.float32, 7.0, GUARD)  # guard floats after the image
+    full_var, var = IO.guarded(n, torch.float32, 7.0, GUARD) if variance else (None, None)
     ctx.denoise_variance(_params(w, h, tile), d, d_state, out, VarianceDenoise(L, *sigmas), var, stream=stream)
     torch.cuda.synchronize()
-    got = out.cpu().numpy()
-    assert np.all(got[n * 3:] == 7.0), "the kernel wrote past the colour output"
-    got_v = None
+    IO.assert_guards(full_out, n * 3, 7.0, "the colour output")
     if variance:
-        got_v = var.cpu().numpy()
-        assert np.all(got_v[n:] == 7.0), "the kernel wrote past the variance output"
-        got_v = got_v[:n]
-    return got[: n * 3].reshape(-1, 3), got_v
-
-
-def _assert_bits_equal(got, want, what):
-    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), (what, "NaN positions differ")
-    bad = (got.view(np.uint32) != want.view(np.uint32)) & ~gn
-    assert not bad.any(), (what, int(bad.sum()), got[bad][:4], want[bad][:4])
+        IO.assert_guards(full_var, n, 7.0, "the variance output")
+    return out.cpu().numpy().reshape(-1, 3), var.cpu().numpy() if variance else None
 
 
 def _restated(film, state, w, h, tile, L, sigmas):
@@ -127,42 +101,42 @@ def _check(ctx, film, state, d, d_state, w, h, tile, L, sigmas, what=None):
     what = (w, h, tile, L, sigmas) if what is None else what
     got_c, got_v = _run(ctx, d, d_state, w, h, tile, L, sigmas)
     want_c, want_v = _restated(film, state, w, h, tile, L, sigmas)
-    _assert_bits_equal(got_c, want_c, (what, "colour"))
-    _assert_bits_equal(got_v, want_v, (what, "variance"))
+    IO.assert_bits_equal(got_c, want_c, (what, "colour"))
+    IO.assert_bits_equal(got_v, want_v, (what, "variance"))
     return got_c, got_v
 
 
 def test_every_shape_tile_size_pass_count_and_term_combination(gpu_ctx, oracle):
     for si, ((w, h), tile) in enumerate(SHAPES):
-        film, state = _random_film(w, h, si), _random_state(w, h, tile, si)
-        d, d_state = _device(film), _device_state(state, w, h, tile)
+        film, state = random_film(w, h, si), _random_state(w, h, tile, si)
+        d, d_state = IO.upload_film(film), _device_state(state, w, h, tile)
         runs = [(L, SIGMAS[(L + si) % 8]) for L in range(1, 9)] + [(3, s) for s in SIGMAS]  # steps up to 128: larger than every image
         for L, sigmas in runs:
             _check(gpu_ctx, film, state, d, d_state, w, h, tile, L, sigmas)
     # without a variance buffer the colour is the same
     (w, h), tile = SHAPES[4]
-    film, state = _random_film(w, h, 4), _random_state(w, h, tile, 4)
-    got_c, none = _run(gpu_ctx, _device(film), _device_state(state, w, h, tile), w, h, tile, 4, (4.0, 0.4, 0.3), variance=False)
+    film, state = random_film(w, h, 4), _random_state(w, h, tile, 4)
+    got_c, none = _run(gpu_ctx, IO.upload_film(film), _device_state(state, w, h, tile), w, h, tile, 4, (4.0, 0.4, 0.3), variance=False)
     assert none is None
-    _assert_bits_equal(got_c, _restated(film, state, w, h, tile, 4, (4.0, 0.4, 0.3))[0], "no variance buffer")
+    IO.assert_bits_equal(got_c, _restated(film, state, w, h, tile, 4, (4.0, 0.4, 0.3))[0], "no variance buffer")
 
 
 def test_adversarial_films_and_states(gpu_ctx, oracle):
     from rayn_amd import progressive as P
     for seed, ((w, h), tile) in enumerate([((1, 1), (1, 1)), ((7, 1), (3, 1)), ((17, 13), (16, 16)), ((33, 65), (8, 8)), ((50, 37), (16, 16))]):
         film, state = _adversarial(w, h, tile, seed)
-        d, d_state = _device(film), _device_state(state, w, h, tile)
+        d, d_state = IO.upload_film(film), _device_state(state, w, h, tile)
         for L, sigmas in [(1, (4.0, 0.4, 0.3)), (4, (4.0, 0.4, 0.3)), (2, (2.0 ** -30, 2.0 ** 30, 0.3)), (3, (2.0 ** 30, 0.0, 2.0 ** -30)),
                           (5, (0.0, 0.0, 0.0)), (8, (1.0, 0.0, 0.3))]:
             _check(gpu_ctx, film, state, d, d_state, w, h, tile, L, sigmas)
     # the inputs and the state are not modified, and nothing is written past the state
     (w, h), tile = (33, 65), (8, 8)
     film, state = _adversarial(w, h, tile, 9)
-    d, d_state = _device(film), _device_state(state, w, h, tile)
+    d, d_state = IO.upload_film(film), _device_state(state, w, h, tile)
     before = d_state.cpu().numpy().copy()
     _run(gpu_ctx, d, d_state, w, h, tile, 5, (4.0, 0.4, 0.3))
     for k, v in film.items():
-        assert np.array_equal(d[k].cpu().numpy().view(np.uint32), v.reshape(-1).view(np.uint32)), k
+        IO.assert_is_host(d[k], v, k)
     assert np.array_equal(d_state.cpu().numpy(), before)
     assert np.all(before[P.state_bytes(w, h, tile):] == 0xA5)
 
@@ -183,16 +157,10 @@ def _scene(name, w=W, h=H):
     return R, cam, world, R.PathTracingIntegrator(max_bounces=BOUNCES, volume_marches=S.VOLUME_MARCHES_PER_SAMPLE), R.BlackmanHarrisFilter(1.5)
 
 
-def _host_film(film):
-    K = type(film.channel_kinds[0])
-    return {"color": film.channel(K.Color), "alpha": film.channel(K.Alpha), "background": film.channel(K.Background),
-            "normal": film.channel(K.WorldNormal)}
-
-
 def _restated_from_film(film, params):
     """the restatement fed with the film's mean film and Film._progressive_arrays()"""
     arrays, pr = film._progressive_arrays()
-    host = _host_film(film)
+    host = IO.host_film(film)
     w, h = film.res
     tile = (pr["params"].tile_w, pr["params"].tile_h)
     return VN.denoise(host["color"], host["alpha"], host["normal"], arrays["m2"], arrays["epochs"], w, h, tile, params.iterations,
@@ -207,8 +175,8 @@ def test_a_real_adaptive_render_fresh_and_resumed(tmp_path, oracle):
     for params in (R.VarianceDenoise(), R.VarianceDenoise(3, 2.0, 0.0, 0.3), R.VarianceDenoise(1, 4.0, 0.4, 0.0)):
         want_c, want_v = _restated_from_film(film, params)
         got = film.denoised_color(params).cpu().numpy()
-        _assert_bits_equal(got, want_c, ("fresh", params, "colour"))
-        _assert_bits_equal(film.denoised_variance(params), want_v.reshape(H, W), ("fresh", params, "variance"))
+        IO.assert_bits_equal(got, want_c, ("fresh", params, "colour"))
+        IO.assert_bits_equal(film.denoised_variance(params), want_v.reshape(H, W), ("fresh", params, "variance"))
         assert not np.array_equal(got, film.channel(R.ChannelKind.Color).reshape(-1, 3))
         assert np.isfinite(want_v).all()  # 48x32 in 16x16 tiles is covered and every tile has run >= 3 epochs
     # a checkpoint after 5 epochs, resumed to the end: the restored state is the state
@@ -221,14 +189,14 @@ def test_a_real_adaptive_render_fresh_and_resumed(tmp_path, oracle):
     assert np.array_equal(rep_b["tile_epochs"], rep["tile_epochs"])
     params = R.VarianceDenoise()
     want_c, want_v = _restated_from_film(b, params)
-    _assert_bits_equal(b.denoised_color(params).cpu().numpy(), want_c, "resumed colour")
-    _assert_bits_equal(b.denoised_variance(params), want_v.reshape(H, W), "resumed variance")
-    _assert_bits_equal(b.denoised_color(params).cpu().numpy(), film.denoised_color(params).cpu().numpy(), "resumed against fresh")
+    IO.assert_bits_equal(b.denoised_color(params).cpu().numpy(), want_c, "resumed colour")
+    IO.assert_bits_equal(b.denoised_variance(params), want_v.reshape(H, W), "resumed variance")
+    IO.assert_bits_equal(b.denoised_color(params).cpu().numpy(), film.denoised_color(params).cpu().numpy(), "resumed against fresh")
     # a resume that renders nothing more (the checkpoint already holds max_epochs epochs) still carries the state
     c = R.Film(KINDS(R), (W, H))
     rep_c = c.render_progressive(world, cam, integ, filt, TILE, 1, None, SAMPLES, R.Progressive(**dict(ADAPTIVE, max_epochs=5)), resume=path)
     assert rep_c["epochs"] == 5 and len(rep_c["stats"]) == 0
-    _assert_bits_equal(c.denoised_color(params).cpu().numpy(), a.denoised_color(params).cpu().numpy(), "restored only")
+    IO.assert_bits_equal(c.denoised_color(params).cpu().numpy(), a.denoised_color(params).cpu().numpy(), "restored only")
 
 
 def test_entry_is_stream_ordered(gpu_ctx, oracle):
@@ -238,11 +206,11 @@ def test_entry_is_stream_ordered(gpu_ctx, oracle):
     from rayn_amd import film as F
     from rayn_amd import progressive as P
     w, h, tile = 640, 360, (16, 16)
-    film, state = _random_film(w, h, 5), _random_state(w, h, tile, 5)
+    film, state = random_film(w, h, 5), _random_state(w, h, tile, 5)
     film["background"] = np.zeros((w * h, 3), np.float32)
     want_c, want_v = _restated(film, state, w, h, tile, 3, (4.0, 0.4, 0.3))
     want = image.color_image(want_c.reshape(h, w, 3), background=film["background"].reshape(h, w, 3))
-    src = _device(film)
+    src = IO.upload_film(film)
     src_state = torch.from_numpy(P.join_state(state, w, h, tile)).cuda()
     torch.cuda.synchronize()
     s = torch.cuda.Stream()
@@ -264,16 +232,16 @@ def test_entry_is_stream_ordered(gpu_ctx, oracle):
         host_v.copy_(var, non_blocking=True)
     s.synchronize()
     assert np.array_equal(host.numpy().reshape(h, w, 3), want)
-    _assert_bits_equal(host_v.numpy(), want_v, "variance on the side stream")
+    IO.assert_bits_equal(host_v.numpy(), want_v, "variance on the side stream")
 
 
 def test_multi_device_context_runs_on_the_first_device(oracle):
     import rayn_amd
     (w, h), tile = (33, 17), (8, 8)
-    film, state = _random_film(w, h, 2), _random_state(w, h, tile, 2)
+    film, state = random_film(w, h, 2), _random_state(w, h, tile, 2)
     ctx = rayn_amd.Context([0, 0])
     try:
-        _check(ctx, film, state, _device(film), _device_state(state, w, h, tile), w, h, tile, 4, (4.0, 0.4, 0.3), "multi-device")
+        _check(ctx, film, state, IO.upload_film(film), _device_state(state, w, h, tile), w, h, tile, 4, (4.0, 0.4, 0.3), "multi-device")
     finally:
         ctx.close()
 
@@ -285,8 +253,8 @@ def test_bad_arguments_return_invalid_arg_with_a_text(gpu_ctx):
     from rayn_amd import progressive as P
     L = _lib.lib()
     w, h, tile = 20, 12, (8, 8)
-    film, st = _random_film(w, h, 1), _random_state(w, h, tile, 1)
-    d = _device(film)
+    film, st = random_film(w, h, 1), _random_state(w, h, tile, 1)
+    d = IO.upload_film(film)
     p0 = _params(w, h, tile)
     need_state = P.state_bytes(w, h, tile)
     state = torch.zeros(need_state + 16, dtype=torch.uint8, device="cuda")
@@ -351,19 +319,13 @@ def test_bad_arguments_return_invalid_arg_with_a_text(gpu_ctx):
 
 # ---- Film.save_to / pixels / denoised_variance with a VarianceDenoise ---------------------------------------------------------------
 
-def _png_bytes(tmp_path, img):
-    p = tmp_path / "ref.png"
-    image.save(str(p), img)
-    return p.read_bytes()
-
-
 def test_save_to_with_a_variance_denoise(tmp_path, oracle):
     R, cam, world, integ, filt = _scene("s3")
     K = R.ChannelKind
     params = R.VarianceDenoise(4, 4.0, 0.4, 0.3)
     film = R.Film(KINDS(R), (W, H))
     film.render_progressive(world, cam, integ, filt, TILE, 2, None, SAMPLES, R.Progressive(min_epochs=2, max_epochs=4, adaptive=False))
-    host = _host_film(film)
+    host = IO.host_film(film)
     restated = _restated_from_film(film, params)[0].reshape(H, W, 3)
     for transparent in (False, True):
         out = tmp_path / f"t{int(transparent)}"
@@ -371,18 +333,18 @@ def test_save_to_with_a_variance_denoise(tmp_path, oracle):
         assert sorted(os.listdir(out)) == ["x_alpha.png", "x_color_denoised.png", "x_normal.png"]
         want = (image.color_image(restated, alpha=host["alpha"], transparent_background=True) if transparent
                 else image.color_image(restated, background=host["background"]))
-        assert (out / "x_color_denoised.png").read_bytes() == _png_bytes(tmp_path, want)
-        assert (out / "x_alpha.png").read_bytes() == _png_bytes(tmp_path, image.alpha_image(host["alpha"]))
+        assert (out / "x_color_denoised.png").read_bytes() == IO.png_bytes(tmp_path, want)
+        assert (out / "x_alpha.png").read_bytes() == IO.png_bytes(tmp_path, image.alpha_image(host["alpha"]))
         assert np.array_equal(film.pixels(K.Color, transparent, denoise=params), want)
     # the fixed-sigma filter still works on the same film
     fixed = denoise_np.atrous(host["color"], host["alpha"], host["normal"], W, H, 2, 0.5, 0.4, 0.3)
-    _assert_bits_equal(film.denoised_color(R.Denoise(2, 0.5, 0.4, 0.3)).cpu().numpy(), fixed, "Denoise on a progressive film")
+    IO.assert_bits_equal(film.denoised_color(R.Denoise(2, 0.5, 0.4, 0.3)).cpu().numpy(), fixed, "Denoise on a progressive film")
     # a guide the film lacks is switched off
     no_normal = R.Film([K.Color, K.Alpha, K.Background], (W, H))
     no_normal.render_progressive(world, cam, integ, filt, TILE, 2, None, SAMPLES, R.Progressive(min_epochs=2, max_epochs=2, adaptive=False))
     arrays, _ = no_normal._progressive_arrays()
     want_c, _ = VN.denoise(no_normal.channel(K.Color), no_normal.channel(K.Alpha), None, arrays["m2"], arrays["epochs"], W, H, TILE, 4, 4.0, 0.0, 0.3)
-    _assert_bits_equal(no_normal.denoised_color(params).cpu().numpy(), want_c, "no WorldNormal")
+    IO.assert_bits_equal(no_normal.denoised_color(params).cpu().numpy(), want_c, "no WorldNormal")
     # no progressive render, one that another render has replaced, one of a single epoch, a sequence, a film without Color
     plain = R.Film(KINDS(R), (W, H))
     plain.render_frame_into(world, cam, integ, filt, TILE, 2, None, 2)
@@ -422,7 +384,7 @@ def quality_figures(grid=()):
     filt = R.BlackmanHarrisFilter(S.FILTER_RADIUS)
     reference = R.Film(KINDS(R), (Wq, Hq))
     reference.render_frame_into(world, cam, integ, filt, S.TILE_SIZE, 1, None, 256)
-    ref = _host_film(reference)
+    ref = IO.host_film(reference)
     want = np.clip(ref["color"].astype(np.float64) + ref["background"], 0.0, 1.0)
     runs = {"non-adaptive": R.Progressive(min_epochs=2, max_epochs=4, adaptive=False),
             "adaptive": dataclasses.replace(R.Progressive(), max_epochs=16)}
@@ -430,7 +392,7 @@ def quality_figures(grid=()):
     for name, prog in runs.items():
         film = R.Film(KINDS(R), (Wq, Hq))
         rep = film.render_progressive(world, cam, integ, filt, S.TILE_SIZE, 1, None, 2, prog)
-        noisy = _host_film(film)
+        noisy = IO.host_film(film)
         mse = lambda c: float(np.mean((np.clip(np.asarray(c).reshape(Hq, Wq, 3).astype(np.float64) + noisy["background"], 0.0, 1.0) - want) ** 2))
         fig = {"epochs": sorted(set(rep["tile_epochs"].tolist())), "mean film": mse(noisy["color"]),
                "Denoise()": mse(film.denoised_color(R.Denoise()).cpu().numpy()),

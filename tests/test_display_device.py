@@ -10,9 +10,10 @@ import os
 import numpy as np
 import pytest
 
+import device_io as IO
 import display_np as D
+from display_cases import film as host_film
 from rayn_amd import image
-from test_display import film as host_film
 
 pytestmark = pytest.mark.gpu
 
@@ -29,55 +30,42 @@ def _display(tone, exposure, levels):
     return Display(exposure=exposure, tone=tone, bloom=Bloom(0.8, 0.6, levels) if levels else None)
 
 
-def _assert_bits_equal(got, want, what):
-    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), (what, "NaN positions differ")
-    bad = (got.view(np.uint32) != want.view(np.uint32)) & ~gn
-    assert not bad.any(), (what, int(bad.sum()), got[bad][:4], want[bad][:4])
-
-
-def _device(film):
-    import torch
-    return {k: torch.from_numpy(np.ascontiguousarray(v, np.float32).reshape(-1)).cuda() for k, v in film.items() if v is not None}
-
-
 def _run(ctx, film, w, h, display, transparent, adapt=1.0, state=None, stream=None, d=None):
     """Both entries through Context.display, every output followed by guard words.  `state`: (m, valid) before the call.  Returns the
     float plane, the image, {m, e}, the bloom plane (None without bloom) and the state afterwards."""
     import torch
     from rayn_amd.film import display_scratch_bytes, save_to_bpp
-    d = _device(film) if d is None else d
+    d = IO.upload_film(film) if d is None else d
     n = w * h
     mask = 1 | (2 if film.get("alpha") is not None else 0) | (4 if film.get("background") is not None else 0)
     bpp = save_to_bpp(0, mask, transparent)
     need = display_scratch_bytes(w, h, display.levels)
     states, outs = [], {}
     for key, dtype, count, fill in (("d", torch.float32, 3 * n, 7.0), ("image", torch.uint8, n * bpp, 0x5A)):
-        out = torch.full((count + GUARD,), fill, dtype=dtype, device="cuda")
-        meter = torch.full((2 + GUARD,), 7.0, dtype=torch.float32, device="cuda")
-        bloom = torch.full((3 * n + GUARD,), 7.0, dtype=torch.float32, device="cuda")
-        scratch = torch.full((need + 64,), 0xAB, dtype=torch.uint8, device="cuda")
-        st = torch.full((2 + GUARD,), 0x55, dtype=torch.int32, device="cuda")
+        full_out, out = IO.guarded(count, dtype, fill, GUARD)
+        full_meter, meter = IO.guarded(2, torch.float32, 7.0, GUARD)
+        full_bloom, bloom = IO.guarded(3 * n, torch.float32, 7.0, GUARD)
+        full_scratch, _ = IO.guarded(need, torch.uint8, 0xAB, 64)
+        full_st, st = IO.guarded(2, torch.int32, 0x55, GUARD)
         before = np.array([np.float32(0 if state is None else state[0]).view(np.int32), 0 if state is None else state[1]], np.int32)
-        st[:2] = torch.from_numpy(before)
-        ctx.display(display, mask, transparent, w, h, d, out, st, scratch, adapt, meter, bloom, stream)
+        st.copy_(torch.from_numpy(before))
+        # the entry is handed the whole buffers, as before: it takes their sizes from its arguments
+        ctx.display(display, mask, transparent, w, h, d, full_out, full_st, full_scratch, adapt, full_meter, full_bloom, stream)
         torch.cuda.synchronize()
-        out, meter, bloom, scratch, st = (t.cpu().numpy() for t in (out, meter, bloom, scratch, st))
-        assert np.all(out[count:] == fill) and np.all(meter[2:] == 7.0) and np.all(bloom[3 * n:] == 7.0), "a kernel wrote past an output"
-        assert np.all(scratch[need:] == 0xAB) and np.all(st[2:] == 0x55), "a kernel wrote past the scratch or the state"
-        if not display.levels:
-            assert np.all(bloom == 7.0)
+        for whole, size, word, name in ((full_out, count, fill, key), (full_meter, 2, 7.0, "meter"), (full_bloom, 3 * n if display.levels else 0, 7.0, "bloom"),
+                                        (full_scratch, need, 0xAB, "scratch"), (full_st, 2, 0x55, "state")):
+            IO.assert_guards(whole, size, word, name)
+        out, meter, bloom, st = (t.cpu().numpy() for t in (out, meter, bloom, st))
         if not display.auto:
-            assert np.array_equal(st[:2], before)  # a manual exposure leaves the state alone
-        outs[key] = out[:count]
-        states.append((st[:2].copy(), meter[:2].copy(), bloom[:3 * n].copy()))
+            assert np.array_equal(st, before)  # a manual exposure leaves the state alone
+        outs[key] = out
+        states.append((st, meter, bloom))
     for a, b in zip(states[0], states[1]):  # both entries meter, adapt and bloom alike
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
     st, meter, bloom = states[0]
     for k, v in film.items():  # the inputs are not modified
         if v is not None:
-            assert np.array_equal(d[k].cpu().numpy().view(np.uint32), np.asarray(v, np.float32).reshape(-1).view(np.uint32)), k
+            IO.assert_is_host(d[k], v, k)
     return {"d": outs["d"].reshape(n, 3), "image": outs["image"].reshape(h, w, bpp), "meter": meter,
             "bloom": bloom.reshape(n, 3) if display.levels else None, "state": (st[:1].view(np.float32)[0], int(st[1]))}
 
@@ -86,14 +74,14 @@ def _check(ctx, film, w, h, display, transparent, adapt=1.0, state=None, what=No
     got = _run(ctx, film, w, h, display, transparent, adapt, state, **kw)
     want = D.display(film["color"], w, h, display.to_abi(adapt), film.get("background"), film.get("alpha"), transparent,
                      (0.0, 0) if state is None else state)
-    _assert_bits_equal(got["d"], want["d"], (what, "float plane"))
+    IO.assert_bits_equal(got["d"], want["d"], (what, "float plane"))
     assert np.array_equal(got["image"], want["image"]), (what, "image", int((got["image"] != want["image"]).sum()))
-    _assert_bits_equal(got["meter"], [want["m"], want["e"]], (what, "m, e"))
+    IO.assert_bits_equal(got["meter"], [want["m"], want["e"]], (what, "m, e"))
     if display.levels:
-        _assert_bits_equal(got["bloom"], want["bloom"], (what, "bloom"))
+        IO.assert_bits_equal(got["bloom"], want["bloom"], (what, "bloom"))
     if display.auto:
         assert got["state"][1] == want["state"][1], what
-        _assert_bits_equal([got["state"][0]], [want["state"][0]], (what, "state"))
+        IO.assert_bits_equal([got["state"][0]], [want["state"][0]], (what, "state"))
     return got, want
 
 
@@ -120,7 +108,7 @@ def test_every_shape_against_the_restatement(gpu_ctx, oracle, shape):
 def test_every_parameter_combination_in_every_arm(gpu_ctx, oracle, arm, adversarial):
     w, h = 33, 65
     film, transparent = _film(w, h, 50 + arm, arm, adversarial)
-    d = _device(film)
+    d = IO.upload_film(film)
     for tone, exposure, levels in COMBOS:
         display = _display(tone, exposure, levels)
         _check(gpu_ctx, film, w, h, display, transparent, what=(tone, exposure, levels, arm, adversarial), d=d)
@@ -135,9 +123,9 @@ def test_identity_parameters_are_save_to(gpu_ctx, arm):
     got = _run(gpu_ctx, film, w, h, Display(exposure=0.0, tone="linear"), transparent)
     mask = 1 | (2 if film["alpha"] is not None else 0) | (4 if film["background"] is not None else 0)
     plain = torch.zeros(w * h * save_to_bpp(0, mask, transparent), dtype=torch.uint8, device="cuda")
-    gpu_ctx.save_to_pixels(0, mask, transparent, w, h, _device(film), plain)
+    gpu_ctx.save_to_pixels(0, mask, transparent, w, h, IO.upload_film(film), plain)
     assert np.array_equal(got["image"].reshape(-1), plain.cpu().numpy())
-    _assert_bits_equal(got["d"], D.input_color(film["color"], film["background"], transparent), "d has the bits of c")
+    IO.assert_bits_equal(got["d"], D.input_color(film["color"], film["background"], transparent), "d has the bits of c")
 
 
 def test_state_carries_over_two_calls(gpu_ctx, oracle):
@@ -168,7 +156,7 @@ def test_entry_is_stream_ordered(gpu_ctx, oracle):
     film, transparent = _film(w, h, 80, 1, False)
     display = _display("reinhard", "auto", 5)
     want = D.display(film["color"], w, h, display.to_abi(), film["background"])["image"]
-    src = _device(film)
+    src = IO.upload_film(film)
     torch.cuda.synchronize()
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
@@ -203,7 +191,7 @@ def test_bad_arguments_return_invalid_arg_with_a_text(gpu_ctx):
     L = _lib.lib()
     w, h = 5, 3
     film, _ = _film(w, h, 1, 0, False)
-    d = _device(film)
+    d = IO.upload_film(film)
     out8 = torch.zeros(w * h * 4, dtype=torch.uint8, device="cuda")
     outf = torch.zeros(w * h * 3, dtype=torch.float32, device="cuda")
     need = display_scratch_bytes(w, h, 3)
@@ -278,12 +266,6 @@ def _scene():
     return R, cam, world, R.PathTracingIntegrator(max_bounces=3, volume_marches=S.VOLUME_MARCHES_PER_SAMPLE), R.BlackmanHarrisFilter(S.FILTER_RADIUS), S.TILE_SIZE
 
 
-def _png_bytes(tmp_path, img):
-    p = tmp_path / "ref.png"
-    image.save(str(p), img)
-    return p.read_bytes()
-
-
 def test_film_pixels_save_to_and_save_hdr(tmp_path, oracle):
     R, cam, world, integ, filt, tile = _scene()
     K = R.ChannelKind
@@ -300,12 +282,12 @@ def test_film_pixels_save_to_and_save_hdr(tmp_path, oracle):
         alpha = film.channel(K.Alpha).reshape(-1) if transparent else None
         want = D.display(color, W, H, display.to_abi(), background, alpha, transparent)
         assert np.array_equal(film.pixels(K.Color, transparent, display=display), want["image"])
-        _assert_bits_equal(film.display_color(display, transparent_background=transparent).cpu().numpy(), want["d"], "display_color")
+        IO.assert_bits_equal(film.display_color(display, transparent_background=transparent).cpu().numpy(), want["d"], "display_color")
         assert np.array_equal(film.pixels(K.Alpha, transparent, display=display), film.pixels(K.Alpha, transparent))  # other channels ignore it
         out = tmp_path / f"{len(kinds)}{int(transparent)}"
         film.save_to([K.Color, K.Alpha], str(out), "x", transparent, display=display)
         assert sorted(os.listdir(out)) == ["x_alpha.png", "x_color_display.png"]
-        assert (out / "x_color_display.png").read_bytes() == _png_bytes(tmp_path, want["image"])
+        assert (out / "x_color_display.png").read_bytes() == IO.png_bytes(tmp_path, want["image"])
         # the exposure did something: the shipped scene's emitters are far above 1 and its mean is far below
         assert not np.array_equal(want["image"], film.pixels(K.Color, transparent))
         film.save_hdr(str(out / "x.pfm"), transparent)
@@ -337,8 +319,8 @@ def test_sequence_with_display_equals_per_frame_calls(tmp_path, oracle):
         adapts.append(1.0 if prev is None else display.adapt(float(start) - float(prev)))
         prev = start
         img = plain.pixels(K.Color, display=display, display_state=state, adapt=adapts[-1])
-        assert (seq / f"a_{frame:04d}_color_display.png").read_bytes() == _png_bytes(tmp_path, img), frame
-        assert (seq / f"a_{frame:04d}_alpha.png").read_bytes() == _png_bytes(tmp_path, plain.pixels(K.Alpha)), frame
+        assert (seq / f"a_{frame:04d}_color_display.png").read_bytes() == IO.png_bytes(tmp_path, img), frame
+        assert (seq / f"a_{frame:04d}_alpha.png").read_bytes() == IO.png_bytes(tmp_path, plain.pixels(K.Alpha)), frame
     assert adapts[0] == 1.0 and 0.0 < adapts[1] < adapts[2] < 1.0  # frames 3 -> 4 -> 6: one and two frame times
     # the suffix goes after whatever the Color file would have been called
     both = tmp_path / "both"

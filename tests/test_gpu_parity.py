@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from common import bits_equal, case, film_equal_bits, film_l2
+from scenes import custom_scene, custom_world
 
 pytestmark = pytest.mark.gpu
 L2_TOL = 1e-4  # north_star: per-pixel L2 < 1e-4 (float)
@@ -154,7 +155,7 @@ def test_mandelbox_dist_bit_exact(gpu_ctx, oracle):
 
 
 def _probe_world(name, sdf_only=False):
-    """(world_desc, frame_params) of a probe scene: a SCENES tag, or one of _custom_world's kinds; sdf_only drops the analytic spheres (rayn_hip_probe_shadow
+    """(world_desc, frame_params) of a probe scene: a SCENES tag, or one of scenes.custom_world's kinds; sdf_only drops the analytic spheres (rayn_hip_probe_shadow
     marches the TracedSDF factors of HitableStore::test_occluded - the spheres are the shading kernel's part)."""
     import rayn_amd as R
     from rayn_amd import params as P
@@ -162,7 +163,7 @@ def _probe_world(name, sdf_only=False):
     if name in S.SCENES:
         cam, world = S.SCENES[name]((64, 64))
     else:
-        cam, world = _custom_scene(name, (64, 64))
+        cam, world = custom_scene(name, (64, 64))
     if sdf_only:
         world.hitables[:] = [h for h in world.hitables if isinstance(h, R.TracedSDF)]
     return world.to_desc(cam), P.frame_params(64, 64, 1, 3)
@@ -510,98 +511,12 @@ def test_errors_instead_of_panics(gpu_ctx):
             gpu_ctx.render_host(p, [np.zeros(8, np.float32)] * 4)
 
 
-# ---- the rest of the closed set (SURVEY.md section 8 f/N4): cameras, Lambertian, Box filter, odd scenes ----
-def _custom_scene(kind, res):
-    """(camera handle, World) of one of the closed-set test scenes"""
-    import rayn_amd as R
-    from rayn_amd import setup as S
-    from rayn_amd.scene import _mul
-    cam_h, world = S.setup(res, volumes=(kind == "thinlens_volume"), sdf="mandelbox")
-    resf = (float(res[0]), float(res[1]))
-    origin = _mul(R.vec3(-0.45, 0.2, 2.0), 2.25)
-    if kind in ("thinlens", "thinlens_volume"):
-        world.cameras = R.CameraStore()
-        cam_h = world.cameras.add_camera(R.ThinLensCamera(resf, 50.0, 0.08, origin, R.vec3(0, 0, 0), R.vec3(0, 1, 0), R.vec3(0.2, 0.1, 0.9)))
-    elif kind == "ortho":
-        world.cameras = R.CameraStore()
-        cam_h = world.cameras.add_camera(R.OrthographicCamera(resf, 11.0 / 4.0, R.vec3(9.5, -3.5, 9.5), R.vec3(0.0, 0.8, 0.0), R.vec3(0, 1, 0)))
-    elif kind == "anim_pinhole":  # camera motion blur: origin and up are closures |t| base + vel*t (lane-0 time quirk)
-        world.cameras = R.CameraStore()
-        cam_h = world.cameras.add_camera(R.PinholeCamera(resf, 60.0, R.Linear(origin, R.vec3(6.0, -2.0, 1.0)), R.vec3(0, 0, 0),
-                                                         R.Linear(R.vec3(0, 1, 0), R.vec3(2.0, 0.0, 0.0))))
-    elif kind == "anim_thinlens":
-        world.cameras = R.CameraStore()
-        cam_h = world.cameras.add_camera(R.ThinLensCamera(resf, 50.0, 0.05, origin, R.Linear(R.vec3(0, 0, 0), R.vec3(1.0, 2.0, 0.0)), R.vec3(0, 1, 0),
-                                                          R.Linear(R.vec3(0.2, 0.1, 0.9), R.vec3(0.0, 0.0, -4.0))))
-    elif kind == "anim_spheres":  # closure transform_seq on Spheres: motion-blurred light proxies + a moving diffuse ball
-        for i in (2, 3, 4):
-            s = world.hitables[i]
-            s.transform_seq = R.Linear(s.transform_seq, R.vec3(3.0, -2.0, 1.5))
-        ball = world.materials.add_material(R.Lambertian(R.Srgb(0.7, 0.6, 0.5)))
-        world.hitables.push(R.Sphere(R.Linear(R.vec3(-1.6, -0.4, 1.9), R.vec3(9.0, 3.0, 0.0)), 0.3, ball))
-    elif kind == "lambertian":
-        world.materials[1] = R.Lambertian(R.Srgb(0.6, 0.3, 0.2))
-    elif kind == "no_lights":
-        world.lights = []
-    elif kind == "spheres_only":
-        del world.hitables[1]
-    elif kind == "two_sdfs":
-        # a second TracedSDF (sphere SDF) after the MandelBox + one before it: exercises the multi-SDF march paths
-        world.hitables.insert(1, R.TracedSDF(R.SphereSDF(0.35), 1))
-        world.hitables.push(R.TracedSDF(R.MandelBox(6, R.BoxFold(1.0), R.SphereFold(0.5, 1.0), -2.0), 1))
-    elif kind == "offset_sdf":  # EXTENSION: TracedSDF with a constant origin (the SDF's frame is translated)
-        world.hitables[1].transform_seq = R.vec3(0.35, -0.2, 0.15)
-    elif kind == "moving_sdf":  # EXTENSION: TracedSDF origin as the closure |t| base + vel*t (motion-blurred fractal), volume on
-        cam_h, world = S.setup(res, volumes=True, sdf="mandelbox")
-        world.hitables[1].transform_seq = R.Linear(R.vec3(0.1, 0.0, -0.05), R.vec3(-4.0, 3.0, 2.0))
-    elif kind == "moving_two_sdfs":  # both SDFs of a multi-SDF scene move differently (generic march kernels)
-        world.hitables.insert(1, R.TracedSDF(R.SphereSDF(0.35), 1, R.Linear(R.vec3(1.4, 0.9, 0.6), R.vec3(0.0, -6.0, 0.0))))
-        world.hitables[2].transform_seq = R.Linear(R.vec3(0.0, 0.0, 0.0), R.vec3(3.0, 0.0, -2.0))
-    elif kind == "moving_bulb":
-        cam_h, world = S.setup_bulb(res)
-        world.hitables[1].transform_seq = R.Linear(R.vec3(0.0, 0.05, 0.0), R.vec3(2.0, -1.0, 0.5))
-    elif kind == "morphing_box":  # EXTENSION: MandelBox scale as the closure |t| scale + scale_vel*t (single-SDF fast-path kernels), volume on
-        cam_h, world = S.setup(res, volumes=True, sdf="mandelbox")
-        world.hitables[1].sdf.scale_vel = 4.0
-    elif kind == "morphing_two_sdfs":  # ... in a multi-SDF scene (generic march kernels), together with a moving origin
-        world.hitables.push(R.TracedSDF(R.MandelBox(7, R.BoxFold(1.0), R.SphereFold(0.5, 1.0), -2.0, scale_vel=-3.0), 1,
-                                        R.Linear(R.vec3(0.3, 0.0, 0.0), R.vec3(0.0, 2.0, 0.0))))
-        world.hitables[1].sdf.scale_vel = 2.5
-    elif kind == "full_house":  # RAYN_MAX_HITABLES = 16 objects: every class of the bin histogram / scan / scatter is populated (ids 0..15)
-        mats = [world.materials.add_material(R.Lambertian(R.Srgb(0.8, 0.3, 0.2))), world.materials.add_material(R.Dielectric.new_remap(R.Srgb(0.3, 0.6, 0.3), 0.4)),
-                world.materials.add_material(R.Emissive.new_splat(R.Srgb(2.0, 1.5, 1.0)))]
-        k = 0
-        while len(world.hitables) < 16:
-            a = 0.7 * k
-            world.hitables.push(R.Sphere(R.vec3(1.9 * np.cos(a), -1.1 + 0.25 * k, 1.9 * np.sin(a)), 0.22 + 0.02 * k, mats[k % 3]))
-            k += 1
-    elif kind == "lambert_sdf_sphere":
-        world.hitables[1] = R.TracedSDF(R.SphereSDF(1.0), world.materials.add_material(R.Lambertian(R.Srgb(0.5, 0.5, 0.5))))
-    elif kind == "huge_lights":
-        # r6 (zero-throughput NEE elision, k_shade_setup): one light of absurd power and size next to an over-bright dielectric, volume on.  Close to that light
-        # pdf < 1 and x = Le * f * tr lies within a factor 1/pdf of FLT_MAX, so (x * occluded) / pdf is +inf for a VISIBLE sample and 0 for an occluded one;
-        # on a segment whose throughput is exactly 0 the reference then adds inf * 0 = NaN (src/integrator.rs:91-92) or nothing - the march outcome reaches
-        # the film, the sample fails the elision's bounds (|x| <= 2^60) and must be tested and marched like any other.
-        cam_h, world = S.setup(res, volumes=True, sdf="mandelbox")
-        world.lights[1].emission = R.Srgb(3.3e38, 1e38, 3e37)
-        world.lights[1].rad = 0.9
-        world.materials[1] = R.Dielectric.new_remap(R.Srgb(3.0, 3.0, 3.0), 0.6)
-    else:
-        raise ValueError(kind)
-    return cam_h, world
-
-
-def _custom_world(kind, res):
-    cam_h, world = _custom_scene(kind, res)
-    return world.to_desc(cam_h)
-
-
 @pytest.mark.parametrize("kind", ["thinlens", "thinlens_volume", "ortho", "anim_pinhole", "anim_thinlens", "anim_spheres", "lambertian", "no_lights", "spheres_only", "two_sdfs", "lambert_sdf_sphere",
                                   "offset_sdf", "moving_sdf", "moving_two_sdfs", "moving_bulb", "morphing_box", "morphing_two_sdfs", "full_house"])
 def test_closed_set_parity(gpu_ctx, oracle, kind):
     from rayn_amd import params as P
     w, h, samples, bounces = 40, 32, 2, 4
-    wd = _custom_world(kind, (w, h))
+    wd = custom_world(kind, (w, h))
     p = P.frame_params(w, h, samples, bounces)
     tabs = _tables(oracle, p)
     ref, ctr = oracle.render(wd, p, tabs)
@@ -637,7 +552,7 @@ def test_zero_throughput_elision_counts_and_fallback(gpu_ctx, oracle):
         out = gpu_ctx.render_host(p, tabs)  # the product kernels: same film, same job count as the instrumented ones
         assert film_equal_bits(out, ref) and gpu_ctx.stats()["shadow_jobs"] == jobs_counted
         w, h = 48, 32
-        wd = _custom_world("huge_lights", (w, h))
+        wd = custom_world("huge_lights", (w, h))
         p = P.frame_params(w, h, 4, 6)
         tabs = _tables(oracle, p)
         ref, ctr = oracle.render(wd, p, tabs)

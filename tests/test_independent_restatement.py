@@ -263,9 +263,9 @@ def test_closed_set_second_restatement(oracle, kind):
     description, not the reference."""
     import restatement_np as RN
     from rayn_amd import params as P
-    from test_gpu_parity import _custom_world
+    from scenes import custom_world
     W, H, samples, bounces = 16, 16, 1, 4
-    wd = _custom_world(kind, (W, H))
+    wd = custom_world(kind, (W, H))
     p = P.frame_params(W, H, samples, bounces, time_range=(0.1, 0.3))
     tabs = oracle.build_tables(4 * samples, bounces, p.volume_marches, p.frame, W, H)
     ref, ctr = oracle.render(wd, p, tabs)

@@ -8,33 +8,18 @@ import os
 import numpy as np
 import pytest
 
+import device_io as IO
 import interpolate_np as I
+import scenes
 import temporal_np as T
 from common import bits_equal
-from test_temporal_device import _gpu_gbuffer, _read, _render_frames, _scene
+from device_io import module_context as ctx  # noqa: F401
+from temporal_cases import SIZES, SPECIAL
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-SIZES = [(48, 32), (40, 24), (50, 37)]  # whole 256-pixel blocks; a width that is no multiple of 16; a size rayn's tile grid under-covers
 PLANE_FLOATS = {"color": 3, "alpha": 1, "background": 3, "normal": 3}
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    """A context of this module's own: the tests switch its mul_add policy and upload their worlds."""
-    import rayn_amd
-    c = rayn_amd.Context(0)
-    yield c
-    c.close()
-
-
-def _dev_key(key, n):
-    import torch
-    film = {k: torch.from_numpy(np.ascontiguousarray(v, f32).reshape(-1).copy()).cuda() for k, v in key.film.items() if v is not None}
-    g = {"records": torch.from_numpy(np.ascontiguousarray(key.rec, f32).reshape(-1).copy()).cuda(),
-         "object": torch.from_numpy(np.ascontiguousarray(key.obj, np.uint32).view(np.int32).reshape(-1).copy()).cuda()}
-    return film, g
 
 
 def _gpu_interpolate(ctx, w, h, ka, kb, rec, obj, ts, tol, guard=64, source=True):
@@ -44,35 +29,29 @@ def _gpu_interpolate(ctx, w, h, ka, kb, rec, obj, ts, tol, guard=64, source=True
     import rayn_amd as R
     n = w * h
     p = R.frame_params(w, h, 1, 1, time_range=(float(ts), float(ts) + 0.04))
-    dev = [_dev_key(k, n) for k in (ka, kb)]
-    keep = [({k: v.clone() for k, v in f.items()}, {k: v.clone() for k, v in g.items()}) for f, g in dev]
-    g = {"records": torch.from_numpy(np.ascontiguousarray(rec, f32).reshape(-1).copy()).cuda(),
-         "object": torch.from_numpy(np.ascontiguousarray(obj, np.uint32).view(np.int32).reshape(-1).copy()).cuda()}
-    gkeep = {k: v.clone() for k, v in g.items()}
-    full = {k: torch.full((c * n + guard,), 7.0, dtype=torch.float32, device="cuda") for k, c in PLANE_FLOATS.items()}
-    d_out = {k: full[k][: PLANE_FLOATS[k] * n] for k in dev[0][0]}
-    d_src = torch.full((n + guard,), -3, dtype=torch.int32, device="cuda")
+    dev = [(IO.upload_film(k.film), IO.upload_gbuffer(k.rec, k.obj)) for k in (ka, kb)]
+    g = IO.upload_gbuffer(rec, obj)
+    ins = [t for f, gk in dev + [({}, g)] for t in (*f.values(), *gk.values())]
+    keep = IO.snapshot(ins)
+    full = {k: IO.guarded(c * n, torch.float32, 7.0, guard) for k, c in PLANE_FLOATS.items()}
+    d_out = {k: full[k][1] for k in dev[0][0]}
+    full_src, d_src = IO.guarded(n, torch.int32, -3, guard)
     ctx.interpolate(p, R.Interpolate(2, tol), (dev[0][0], dev[0][1], ka.camera, ka.time), (dev[1][0], dev[1][1], kb.camera, kb.time), g, d_out,
-                    d_src[:n] if source else None)
+                    d_src if source else None)
     torch.cuda.synchronize()
     for k, c in PLANE_FLOATS.items():
-        written = c * n if k in d_out else 0
-        assert torch.all(full[k][written:] == 7.0), f"the kernel wrote past {k} or into an absent plane"
-    assert torch.all(d_src[n if source else 0:] == -3), "the kernel wrote past d_out_source or into an absent one"
-    for (f, gk), (fk, gkk) in zip(dev, keep):
-        assert all(torch.equal(f[k].view(torch.int32), fk[k].view(torch.int32)) for k in f) and all(torch.equal(gk[k].view(torch.int32), gkk[k].view(torch.int32)) for k in gk), "a key was modified"
-    assert all(torch.equal(g[k].view(torch.int32), gkeep[k].view(torch.int32)) for k in g), "the G-buffer was modified"
+        IO.assert_guards(full[k][0], c * n if k in d_out else 0, 7.0, k)
+    IO.assert_guards(full_src, n if source else 0, -3, "d_out_source")
+    IO.assert_unchanged(ins, keep, "a key or the G-buffer")
     out = {k: d_out[k].cpu().numpy().reshape(n, PLANE_FLOATS[k]) for k in d_out}
-    return out, (d_src[:n].cpu().numpy().view(np.uint32) if source else None)
+    return out, (d_src.cpu().numpy().view(np.uint32) if source else None)
 
 
 def _same(got, want, what):
     (out_g, src_g), (out_w, src_w) = got, want
-    assert sorted(out_g) == sorted(out_w), what
     if src_g is not None:
         assert np.array_equal(src_g, src_w), (what, "source", int((src_g != src_w).sum()))
-    for k in out_w:
-        assert bits_equal(out_g[k], out_w[k]), (what, k, int((out_g[k].view(np.uint32) != out_w[k].view(np.uint32)).any(axis=1).sum()))
+    IO.assert_planes_equal(out_g, out_w, what)
 
 
 def _check(ctx, w, h, ka, kb, rec, obj, ts, tol, hitables, what, **kw):
@@ -87,7 +66,7 @@ def test_kernel_on_the_exact_orthographic_cases(ctx):
     """The cases tests/test_interpolate.py writes down pixel by pixel, through the kernel: both keys, one key, tier 2, special values, the
     depth bound, ts at either key, a moving hitable, fractional positions, absent planes - and every source code occurs."""
     W, H, PIXEL = 32, 16, 0.125
-    wd, _, _ = _scene("s0", (W, H))
+    wd, _, _ = scenes.scene("s0", (W, H))
     ctx.upload_world(wd)  # no animated hitable
     seen = set()
     ka, kb, rec, obj = I.ortho_case(W, H, 2, PIXEL)
@@ -123,7 +102,7 @@ def test_kernel_on_the_exact_orthographic_cases(ctx):
         k.rec, k.obj, _ = T.ortho_plane_gbuffer(W, H, origin_x=ox, pixel=PIXEL)
     _check(ctx, W, H, ka, kb, rec, obj, 0.25, 0.05, [], "fractional")
     # a moving hitable: the world's animated fractal is object 1
-    wd, _, _ = _scene("s1", (W, H), moving=True)
+    wd, _, _ = scenes.scene("s1", (W, H), moving=True)
     ctx.upload_world(wd)
     hit = T.world_hitables(wd)
     assert hit[1][0]
@@ -165,11 +144,10 @@ def _random_case(w, h, seed, cam_kind, adversarial):
         film = {"color": rng.gamma(0.6, 0.5, (n, 3)).astype(f32), "alpha": rng.random(n).astype(f32), "background": rng.random((n, 3)).astype(f32),
                 "normal": rng.normal(size=(n, 3)).astype(f32)}
         if adversarial:
-            special = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 3.0e38, -3.0e38, 1e-45, 1e30, -1e30], f32)
             for plane in (film["color"], krec, rec):
                 flat = plane.reshape(-1)
-                idx = rng.choice(flat.size, min(flat.size // 4, 6 * special.size), replace=False)
-                flat[idx] = np.resize(special, idx.size)
+                idx = rng.choice(flat.size, min(flat.size // 4, 6 * SPECIAL.size), replace=False)
+                flat[idx] = np.resize(SPECIAL, idx.size)
         keys.append(I.Key(film, krec, kobj, c, t))
     return keys[0], keys[1], rec, obj
 
@@ -179,7 +157,7 @@ def test_kernel_matches_the_restatement_on_adversarial_inputs(ctx, cam_kind):
     """Random and adversarial keys (NaN and inf colours, positions and depths, t = +inf, misses, huge colours that overflow the sums) under
     cameras that have translated and rotated so that taps straddle every image border, for every film size, at both keys' own times and
     between them, with the depth test tight, loose and at zero."""
-    wd, _, _ = _scene("s1", (40, 24), moving=True)  # hitables 1 (the fractal) and one sphere are animated: object motion is exercised too
+    wd, _, _ = scenes.scene("s1", (40, 24), moving=True)  # hitables 1 (the fractal) and one sphere are animated: object motion is exercised too
     ctx.upload_world(wd)
     hit = T.world_hitables(wd)
     seen = set()
@@ -211,12 +189,12 @@ def test_kernel_on_rendered_keys_of_moving_scenes(ctx, fma):
     ta, ts, tb = TIMES
     seen = set()
     for name, cam, (w, h) in RENDERED:
-        wd, _, _ = _scene(name, (w, h), cam, moving=True)
+        wd, _, _ = scenes.scene(name, (w, h), cam, moving=True)
         ctx.set_fma_policy(fma)
         try:
             ps = [R.frame_params(w, h, 1, 2, frame=f, time_range=(t, t + 0.04)) for f, t in ((1, ta), (2, ts), (3, tb))]
-            films = _render_frames(ctx, wd, [ps[0], ps[2]], 2)
-            gb = [_gpu_gbuffer(ctx, p)[1:] for p in ps]
+            films = IO.render_frames(ctx, wd, [ps[0], ps[2]], 2)
+            gb = [IO.gpu_gbuffer(ctx, p)[1:] for p in ps]
         finally:
             ctx.set_fma_policy(0)
         keys = [I.Key({k: v.cpu().numpy() for k, v in film.items()}, rec, obj, wd.camera, t) for film, (rec, obj), t in zip(films, (gb[0], gb[2]), (ta, tb))]
@@ -242,7 +220,7 @@ def test_bad_arguments_are_invalid_arg_with_a_text(ctx):
     L = ctx._L
     w, h = 40, 24
     n = w * h
-    wd, _, _ = _scene("s0", (w, h))
+    wd, _, _ = scenes.scene("s0", (w, h))
     fresh = R.Context(0)
     zeros = lambda k, dt=torch.float32: torch.zeros(k, dtype=dt, device="cuda")
     vp = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
@@ -324,7 +302,7 @@ def test_bad_arguments_are_invalid_arg_with_a_text(ctx):
 def _sequence_setup(w, h):
     import rayn_amd as R
     from rayn_amd import setup as S
-    _, world, cam = _scene("s1", (w, h), moving=True)
+    _, world, cam = scenes.scene("s1", (w, h), moving=True)
     integ = R.PathTracingIntegrator(max_bounces=2, volume_marches=S.VOLUME_MARCHES_PER_SAMPLE)
     return world, cam, integ, R.BlackmanHarrisFilter(S.FILTER_RADIUS), S.TILE_SIZE
 
@@ -349,7 +327,7 @@ def test_render_sequence_with_interpolate_is_the_plain_keys_and_the_loop_of_the_
     film = R.Film(kinds, (w, h))
     stats = film.render_sequence(world, cam, integ, filt, tile, frames, 24, 1.0 / 24.0, samples, [K.Color, K.Alpha], str(tmp_path / "seq"), "a",
                                  denoise=dn, display=dp, interpolate=itp)
-    got = _read(tmp_path / "seq")
+    got = IO.read_folder(tmp_path / "seq")
     suffix = "color_interp" + ("_denoised_display" if post else "")
     assert sorted(got) == sorted(f"a_{f:04d}_{s}.png" for f in frames for s in (suffix, "alpha"))
     is_key = [itp.is_key(i, len(frames)) for i in range(len(frames))]
@@ -360,7 +338,7 @@ def test_render_sequence_with_interpolate_is_the_plain_keys_and_the_loop_of_the_
         plain = R.Film(kinds, (w, h))
         keys = [f for f, k in zip(frames, is_key) if k]
         plain.render_sequence(world, cam, integ, filt, tile, keys, 24, 1.0 / 24.0, samples, [K.Color, K.Alpha], str(tmp_path / "plain"), "a")
-        base = _read(tmp_path / "plain")
+        base = IO.read_folder(tmp_path / "plain")
         for f in keys:
             assert got[f"a_{f:04d}_color_interp.png"] == base[f"a_{f:04d}_color.png"], f
             assert got[f"a_{f:04d}_alpha.png"] == base[f"a_{f:04d}_alpha.png"], f
@@ -426,13 +404,12 @@ def test_render_sequence_without_interpolate_is_unchanged_and_bad_orders_raise(t
     film.render_sequence(world, cam, integ, filt, tile, [1, 2], 24, 1.0 / 24.0, 1, [K.Color], str(tmp_path / "none"), "a", interpolate=None)
     one = R.Film(kinds, (w, h))
     for frame in (1, 2):
-        start = f32(frame) * (f32(1.0) / f32(24))
-        one.render_frame_into(world, cam, integ, filt, tile, frame, (float(start), float(f32(start + f32(1.0 / 24.0)))), 1)
+        one.render_frame_into(world, cam, integ, filt, tile, frame, IO.shutter_range(frame), 1)
         one.save_to([K.Color], str(tmp_path / "loop"), f"a_{frame:04d}")
-    assert _read(tmp_path / "none") == _read(tmp_path / "loop")
+    assert IO.read_folder(tmp_path / "none") == IO.read_folder(tmp_path / "loop")
     # one and two frames: nothing is generated
     st = film.render_sequence(world, cam, integ, filt, tile, [3], 24, 1.0 / 24.0, 1, [K.Color], str(tmp_path / "single"), "a", interpolate=R.Interpolate(4))
-    assert sorted(_read(tmp_path / "single")) == ["a_0003_color_interp.png"] and "generated" not in st[0]
+    assert sorted(IO.read_folder(tmp_path / "single")) == ["a_0003_color_interp.png"] and "generated" not in st[0]
     with pytest.raises((ValueError, R.film.RaynHipError)):
         film.render_sequence(world, cam, integ, filt, tile, [5, 4, 1], 24, 1.0 / 24.0, 1, [K.Color], str(tmp_path / "desc"), "a", interpolate=R.Interpolate(2))
 
@@ -506,9 +483,9 @@ def test_a_generated_frame_is_closer_to_the_truth_than_the_cross_fade():
     c = R.Context(0)
     try:
         frames = IC.FRAMES
-        noisy = dict(zip(frames, _render_frames(c, wd, [ps[f] for f in frames], D.BOUNCES)))
+        noisy = dict(zip(frames, IO.render_frames(c, wd, [ps[f] for f in frames], D.BOUNCES)))
         want = {}
-        for f, film in zip(frames[1:-1], _render_frames(c, wd, [pref[f] for f in frames[1:-1]], D.BOUNCES)):
+        for f, film in zip(frames[1:-1], IO.render_frames(c, wd, [pref[f] for f in frames[1:-1]], D.BOUNCES)):
             want[f] = np.clip(film["color"].cpu().numpy().astype(np.float64).reshape(D.H, D.W, 3) + film["background"].cpu().numpy().reshape(D.H, D.W, 3), 0.0, 1.0)
         gbuf = {}
         for f in frames:

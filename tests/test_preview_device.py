@@ -9,22 +9,15 @@ import os
 import numpy as np
 import pytest
 
+import device_io as IO
 import preview_np as PN
 from common import bits_equal
+from device_io import module_context as ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 GUARD = 64
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    """A context of this module's own: the tests switch its mul_add policy."""
-    import rayn_amd
-    c = rayn_amd.Context(0)
-    yield c
-    c.close()
 
 
 def _gpu_preview(ctx, wd, p, preview, samples, scramble, optional):
@@ -34,31 +27,34 @@ def _gpu_preview(ctx, wd, p, preview, samples, scramble, optional):
     from rayn_amd import film as F
     n = p.width * p.height
     ctx.upload_world(wd)
-    d_out = {"color": torch.full((3 * n + GUARD,), 7.0, dtype=torch.float32, device="cuda"), "alpha": torch.full((n + GUARD,), 7.0, dtype=torch.float32, device="cuda"),
-             "normal": torch.full((3 * n + GUARD,), 7.0, dtype=torch.float32, device="cuda")}
-    d_ao = torch.full((n + GUARD,), 7.0, dtype=torch.float32, device="cuda") if optional else None
-    g = {"records": torch.full((4 * n + GUARD,), 7.0, dtype=torch.float32, device="cuda"), "object": torch.full((n + GUARD,), 7, dtype=torch.int32, device="cuda")} if optional else None
+    sizes = {"color": 3 * n, "alpha": n, "normal": 3 * n}
+    full = {k: IO.guarded(size, torch.float32, 7.0, GUARD) for k, size in sizes.items()}
+    if optional:
+        full.update(ao=IO.guarded(n, torch.float32, 7.0, GUARD), records=IO.guarded(4 * n, torch.float32, 7.0, GUARD), object=IO.guarded(n, torch.int32, 7, GUARD))
+    # the entry is handed the whole buffers: it takes their sizes from the frame parameters
+    d_out = {k: full[k][0] for k in sizes}
+    d_ao = full["ao"][0] if optional else None
+    g = {"records": full["records"][0], "object": full["object"][0]} if optional else None
     nb = F.preview_scratch_bytes(p.width, p.height, preview.samples)
-    d_scratch = torch.full((nb + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
+    full_scratch, d_scratch = IO.guarded(nb, torch.uint8, 0xA5, GUARD)
     d_samples = torch.from_numpy(np.ascontiguousarray(samples, f32)).cuda()
     d_scramble = None if scramble is None else torch.from_numpy(np.ascontiguousarray(scramble, f32)).cuda()
-    ctx.preview(p, preview, d_samples, d_out, d_scramble, d_ao, g, d_scratch[:nb])
+    ctx.preview(p, preview, d_samples, d_out, d_scramble, d_ao, g, d_scratch)
     torch.cuda.synchronize()
-    for name, t, size, fill in [("color", d_out["color"], 3 * n, 7.0), ("alpha", d_out["alpha"], n, 7.0), ("normal", d_out["normal"], 3 * n, 7.0), ("scratch", d_scratch, nb, 0xA5)] + \
-            ([("ao", d_ao, n, 7.0), ("records", g["records"], 4 * n, 7.0), ("object", g["object"], n, 7)] if optional else []):
-        assert torch.all(t[size:] == fill), f"the entry wrote past {name}"
-    got = {"color": d_out["color"][: 3 * n].cpu().numpy().reshape(n, 3), "alpha": d_out["alpha"][:n].cpu().numpy(), "normal": d_out["normal"][: 3 * n].cpu().numpy().reshape(n, 3),
-           "ao": None, "records": None, "object": None}
+    for k, (whole, view) in full.items():
+        IO.assert_guards(whole, view.numel(), 7 if k == "object" else 7.0, k)
+    IO.assert_guards(full_scratch, nb, 0xA5, "scratch")
+    got = {k: full[k][1].cpu().numpy() if k in full else None for k in ("color", "alpha", "normal", "ao", "records", "object")}
+    got["color"], got["normal"] = got["color"].reshape(n, 3), got["normal"].reshape(n, 3)
     if optional:
-        got.update(ao=d_ao[:n].cpu().numpy(), records=g["records"][: 4 * n].cpu().numpy().reshape(n, 4), object=g["object"][:n].cpu().numpy().view(np.uint32))
+        got["records"], got["object"] = got["records"].reshape(n, 4), got["object"].view(np.uint32)
     return got
 
 
 def _compare(got, ref, what):
     for k in ("color", "alpha", "normal", "ao", "records"):
         if got[k] is not None:
-            bad = int((np.ascontiguousarray(got[k], f32).view(np.uint32) != np.ascontiguousarray(ref[k], f32).view(np.uint32)).sum())
-            assert bits_equal(got[k], ref[k]), (what, k, bad)
+            IO.assert_bits_equal(got[k], ref[k], (what, k))
     if got["object"] is not None:
         assert np.array_equal(got["object"], ref["object"]), (what, "object")
 
@@ -153,10 +149,6 @@ def test_film_render_preview(oracle, tmp_path):
     assert not np.array_equal(film.render_preview(pv, frame=frame + 1).pixels(K.Color), out.pixels(K.Color))
 
 
-def _read(folder):
-    return {f: open(os.path.join(folder, f), "rb").read() for f in sorted(os.listdir(folder))}
-
-
 def test_render_sequence_with_preview_is_the_plain_loop_of_the_entries(tmp_path):
     """render_sequence(preview=...) over 3 frames with temporal=, denoise= and display= writes the bytes of a loop of Context.preview (into
     the temporal stage's G-buffer), temporal_accumulate, denoise, display and save_to_pixels; the other channels' files are the preview's."""
@@ -174,7 +166,7 @@ def test_render_sequence_with_preview_is_the_plain_loop_of_the_entries(tmp_path)
                                  denoise=dn, display=dsp, preview=pv, temporal=tp)
     film.render_sequence(world, cam, None, None, (16, 16), frames, 24, 1.0 / 24.0, 1, [K.Color], str(tmp_path / "bare"), "a", preview=pv)
     assert stats == [{"frame": f} for f in frames]
-    got, bare = _read(tmp_path / "seq"), _read(tmp_path / "bare")
+    got, bare = IO.read_folder(tmp_path / "seq"), IO.read_folder(tmp_path / "bare")
     suffix = "color_preview_temporal_denoised_display"
     assert sorted(got) == sorted(f"a_{f:04d}_{s}.png" for f in frames for s in (suffix, "alpha", "normal"))
     assert sorted(bare) == [f"a_{f:04d}_color_preview.png" for f in frames]
@@ -224,10 +216,9 @@ def test_render_sequence_without_preview_is_unchanged(tmp_path):
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, 24, 1.0 / 24.0, 1, [K.Color, K.Alpha], str(tmp_path / "none"), "a", preview=None)
     one = R.Film(kinds, (w, h))
     for frame in frames:
-        start = f32(frame) * (f32(1.0) / f32(24))
-        one.render_frame_into(world, cam, integ, filt, S.TILE_SIZE, frame, (float(start), float(f32(start + f32(1.0 / 24.0)))), 1)
+        one.render_frame_into(world, cam, integ, filt, S.TILE_SIZE, frame, IO.shutter_range(frame), 1)
         one.save_to([K.Color, K.Alpha], str(tmp_path / "loop"), f"a_{frame:04d}")
-    assert _read(tmp_path / "none") == _read(tmp_path / "loop")
+    assert IO.read_folder(tmp_path / "none") == IO.read_folder(tmp_path / "loop")
 
 
 def test_bad_arguments_are_invalid_arg_with_a_text(ctx):

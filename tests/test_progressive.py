@@ -5,26 +5,12 @@ import dataclasses
 import numpy as np
 import pytest
 
+import progressive_cases as PC
 import progressive_np as PN
-from common import bits_equal, case
+from common import bits_equal
+from progressive_cases import ADAPTIVE, BOUNCES, H, TILE, W, oracle_epochs
 
 F32 = np.float32
-
-# The adaptive scene of the loop tests (CPU here, GPU in test_progressive_device.py): MandelBox, part sky, part fractal.
-ADAPTIVE = dict(target_error=0.2, noise_floor=0.05, min_epochs=3, max_epochs=40, outlier_permille=100)
-W, H, TILE, SAMPLES, BOUNCES = 48, 32, (16, 16), 1, 3
-
-
-def oracle_epochs(oracle, name, frame=1, fma=False, w=W, h=H, samples=SAMPLES, bounces=BOUNCES):
-    """render_epoch(seed, tile_subset) of scene `name` through the CPU oracle, and the frame parameters"""
-    wd, p = case(name, w, h, samples, bounces, frame=frame)
-    film_tables = oracle.build_tables(4 * samples, bounces, p.volume_marches, frame, w, h, fma=fma)[2:]
-
-    def render_epoch(seed, subset):
-        rd = oracle.build_tables(4 * samples, bounces, p.volume_marches, seed, w, h, fma=fma)[:2]
-        return oracle.render(wd, p, tuple(rd) + tuple(film_tables), tile_subset=subset, fma=fma)[0]
-    return render_epoch, p
-
 
 # ---- seed --------------------------------------------------------------------------------------------------------------------------
 
@@ -74,23 +60,9 @@ def test_seed_overflow_and_too_many_sets_are_errors():
 
 # ---- the restatement on hand-made films -----------------------------------------------------------------------------------------------
 
-def _film(w, h, seed, special=False):
-    rng = np.random.default_rng(seed)
-    n = w * h
-    f = {"color": rng.gamma(0.6, 0.5, (n, 3)).astype(F32), "alpha": rng.choice(np.array([0.0, 0.25, 1.0], F32), n),
-         "background": rng.uniform(0, 1, (n, 3)).astype(F32), "normal": rng.normal(size=(n, 3)).astype(F32)}
-    if special:
-        vals = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 3.0e38, -3.0e38, 1e-45, -1e-45, 1e-39], F32)
-        for key in PN.FILM_KEYS:
-            flat = f[key].reshape(-1)
-            idx = rng.choice(flat.size, min(flat.size, 2 * vals.size), replace=False)
-            flat[idx] = np.resize(vals, idx.size)
-    return f
-
-
 def test_one_epochs_mean_film_is_the_films_bits():
     w, h = 19, 11
-    film = _film(w, h, 0, special=True)
+    film = PC.film(w, h, 0, special=True)
     film["color"][0] = -0.0
     st = PN.accumulate(PN.State(w, h, (8, 8)), film)
     covered = np.concatenate([st.pixels_of(k) for k in range(len(st.rects))])
@@ -171,10 +143,10 @@ def test_retirement_at_the_permille_boundary():
 def test_unlisted_tiles_are_left_alone():
     w, h = 40, 24
     st = PN.State(w, h, (16, 16))
-    PN.accumulate(st, _film(w, h, 2))
+    PN.accumulate(st, PC.film(w, h, 2))
     before = {k: v.copy() for k, v in st.sum.items()}
     mean_before = {k: v.copy() for k, v in st.mean.items()}
-    PN.accumulate(st, _film(w, h, 3), tiles=[1, 2])
+    PN.accumulate(st, PC.film(w, h, 3), tiles=[1, 2])
     other = np.concatenate([st.pixels_of(k) for k in (0, 3, 4, 5)])  # 40x24 in 16x16 tiles: 3 x 2 tiles
     for key in PN.FILM_KEYS:
         assert bits_equal(st.sum[key][other], before[key][other]) and bits_equal(st.mean[key][other], mean_before[key][other])
@@ -258,11 +230,6 @@ def test_progressive_parameters_are_validated():
         R.Progressive().min_epochs = 3
 
 
-def _restated_arrays(st):
-    return {"sum_color": st.sum["color"], "sum_alpha": st.sum["alpha"], "sum_background": st.sum["background"], "sum_normal": st.sum["normal"],
-            "mean_y": st.mean_y, "m2": st.m2, "epochs": st.epochs, "retired": st.retired, "outliers": st.outliers, "max_e": st.max_e}
-
-
 def test_checkpoint_round_trip_and_key_mismatches(tmp_path):
     import rayn_amd as R
     from rayn_amd import progressive as P
@@ -270,8 +237,8 @@ def test_checkpoint_round_trip_and_key_mismatches(tmp_path):
     w, h, tile = 40, 24, (16, 16)
     st = PN.State(w, h, tile)
     for i in range(3):
-        PN.accumulate(st, _film(w, h, i, special=True), tiles=None if i < 2 else [0, 3], min_epochs=2, target_error=10.0, outlier_permille=1000)
-    arrays = _restated_arrays(st)
+        PN.accumulate(st, PC.film(w, h, i, special=True), tiles=None if i < 2 else [0, 3], min_epochs=2, target_error=10.0, outlier_permille=1000)
+    arrays = PC.restated_arrays(st)
     cam, world = S.setup_s1((w, h))
     args = dict(resolution=(w, h), tile_size=tile, samples=2, max_bounces=3, volume_marches=2, frame=7, time_range=(0.25, 0.5),
                 filter=R.BlackmanHarrisFilter(1.5), world_bytes=world.to_desc(cam), progressive=R.Progressive(), fma_policy=0)

@@ -7,9 +7,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import device_io as IO
+import progressive_cases as PC
 import progressive_np as PN
 from common import bits_equal
-from test_progressive import ADAPTIVE, BOUNCES, H, SAMPLES, TILE, W, _film, _restated_arrays, oracle_epochs
+from progressive_cases import ADAPTIVE, BOUNCES, H, SAMPLES, TILE, W, oracle_epochs
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -27,21 +29,20 @@ def _dev(film, w, h, fill=None):
     import torch
     out = {}
     for key, floats in (("color", 3), ("alpha", 1), ("background", 3), ("normal", 3)):
-        t = torch.full((w * h * floats + GUARD,), 7.0, dtype=torch.float32, device="cuda")
+        out[key], view = IO.guarded(w * h * floats, torch.float32, 7.0, GUARD)  # the entries are handed the whole buffer
         if film is not None:
-            t[: w * h * floats] = torch.from_numpy(np.ascontiguousarray(film[key], F32).reshape(-1)).cuda()
+            view.copy_(torch.from_numpy(np.ascontiguousarray(film[key], F32).reshape(-1)))
         elif fill is not None:
-            t[: w * h * floats] = fill
-        out[key] = t
+            view.fill_(fill)
     return out
 
 
 def _host(d, w, h):
     out = {}
     for key, floats in (("color", 3), ("alpha", 1), ("background", 3), ("normal", 3)):
-        a = d[key].cpu().numpy()
-        assert np.all(a[w * h * floats:] == 7.0), f"the kernel wrote past the {key} plane"
-        out[key] = a[: w * h * floats].reshape(-1, 3) if floats == 3 else a[: w * h]
+        IO.assert_guards(d[key], w * h * floats, 7.0, f"the {key} plane")
+        a = d[key][: w * h * floats].cpu().numpy()
+        out[key] = a.reshape(-1, 3) if floats == 3 else a
     return out
 
 
@@ -51,9 +52,9 @@ def _assert_state(ctx, p, d_state, st, w, h, tile, what):
     torch.cuda.synchronize()
     raw = d_state.cpu().numpy()
     nbytes = P.state_bytes(w, h, tile)
-    assert np.all(raw[nbytes:] == 0xA5), (what, "the kernels wrote past the state")
+    IO.assert_guards(d_state, nbytes, 0xA5, (what, "the state"))
     got = P.split_state(raw[:nbytes], w, h, tile)
-    want = _restated_arrays(st)
+    want = PC.restated_arrays(st)
     for k in P.STATE_FIELDS:
         if np.asarray(want[k]).dtype == np.float32:
             assert bits_equal(got[k], want[k]), (what, k)
@@ -73,7 +74,7 @@ def _assert_state(ctx, p, d_state, st, w, h, tile, what):
 def _new_state(ctx, p, w, h, tile):
     import torch
     from rayn_amd import progressive as P
-    d_state = torch.full((P.state_bytes(w, h, tile) + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+    d_state, _ = IO.guarded(P.state_bytes(w, h, tile), torch.uint8, 0xA5, 64)
     ctx.progressive_reset(p, d_state)
     return d_state
 
@@ -97,7 +98,7 @@ def test_accumulate_and_compaction_match_the_restatement(gpu_ctx):
             d_mean = _dev(None, w, h, fill=5.0)
             st.mean = {k: np.full_like(v, 5.0) for k, v in st.mean.items()}  # pixels no epoch has reached keep what the caller's film held
             for epoch in range(1 + (si + sw_i) % 6):
-                film = _film(w, h, 100 * si + 10 * sw_i + epoch, special=bool((epoch + sw_i) % 2))
+                film = PC.film(w, h, 100 * si + 10 * sw_i + epoch, special=bool((epoch + sw_i) % 2))
                 if epoch % 3 == 2:  # a low-noise epoch so that some tiles do retire
                     film = {k: (np.float32(0.5) + np.float32(1e-3) * v).astype(F32) for k, v in film.items()}
                 tiles = None
@@ -132,7 +133,7 @@ def _film_state(film):
 
 def _assert_film_is_state(film, st, what):
     from rayn_amd import progressive as P
-    got, want = _film_state(film), _restated_arrays(st)
+    got, want = _film_state(film), PC.restated_arrays(st)
     for k in P.STATE_FIELDS:
         assert bits_equal(got[k], want[k]) if np.asarray(want[k]).dtype == np.float32 else np.array_equal(got[k], want[k]), (what, k)
     host = _film_host(film)
@@ -281,7 +282,7 @@ def test_accumulate_is_stream_ordered(gpu_ctx, oracle):
     import rayn_amd as R
     w, h, tile = 640, 360, (16, 16)
     p = _params(w, h, tile)
-    film = _film(w, h, 3)
+    film = PC.film(w, h, 3)
     st = PN.accumulate(PN.State(w, h, tile), film)
     src = {k: torch.from_numpy(np.ascontiguousarray(v).reshape(-1)).cuda() for k, v in film.items()}
     from rayn_amd import progressive as P
@@ -312,7 +313,7 @@ def test_bad_arguments_return_invalid_arg_with_a_text(gpu_ctx):
     p = _params(w, h, tile)
     need = P.state_bytes(w, h, tile)
     state = torch.zeros(need + 16, dtype=torch.uint8, device="cuda")
-    film, mean = _dev(_film(w, h, 0), w, h), _dev(None, w, h)
+    film, mean = _dev(PC.film(w, h, 0), w, h), _dev(None, w, h)
     ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     n_tiles = len(PN.tile_rects(w, h, *tile))

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import device_io as IO
 from common import case
 from rayn_amd import image
 
@@ -71,21 +72,15 @@ def _adversarial(h, w, seed):
     return f
 
 
-def _device_film(film):
-    import torch
-    return {k: torch.from_numpy(np.ascontiguousarray(v, np.float32).reshape(-1)).cuda() for k, v in film.items()}
-
-
 def _device_pixels(ctx, kind, film_d, mask, transparent, w, h, stream=None):
     import torch
     from rayn_amd import film as F
     bpp = F.save_to_bpp(kind, mask, transparent)
-    out = torch.full((h * w * bpp + 64,), 0xA5, dtype=torch.uint8, device="cuda")  # 64 guard bytes after the image
+    full, out = IO.guarded(h * w * bpp, torch.uint8, 0xA5, 64)  # 64 guard bytes after the image
     ctx.save_to_pixels(kind, mask, transparent, w, h, film_d, out, stream)
     torch.cuda.synchronize()
-    got = out.cpu().numpy()
-    assert np.all(got[h * w * bpp:] == 0xA5), "the kernel wrote past the image"
-    return got[: h * w * bpp].reshape(h, w, bpp)
+    IO.assert_guards(full, h * w * bpp, 0xA5, "the image")
+    return out.cpu().numpy().reshape(h, w, bpp)
 
 
 def _films(oracle):
@@ -100,7 +95,7 @@ def test_every_arm_matches_the_oracle_and_image_py(gpu_ctx, oracle):
             (1, ALL, False), (1, 2, True), (2, ALL, False), (2, 4, True), (3, ALL, False), (3, 8, False)]
     for name, film in _films(oracle):
         h, w = film["alpha"].shape
-        d = _device_film(film)
+        d = IO.upload_film(film)
         for kind, mask, transparent in arms:
             want = _oracle_pixels(oracle, kind, film, mask, transparent)
             assert want is not None
@@ -117,7 +112,7 @@ def test_every_arm_matches_the_oracle_and_image_py(gpu_ctx, oracle):
 def test_error_arms_agree_with_the_oracle(gpu_ctx, oracle):
     from rayn_amd import film as F
     film = _adversarial(4, 5, 9)
-    d = _device_film(film)
+    d = IO.upload_film(film)
     for kind in range(4):
         for mask in range(16):
             for transparent in (False, True):
@@ -209,7 +204,7 @@ def test_entry_is_stream_ordered(gpu_ctx, oracle):
     import torch
     film = _adversarial(720, 1280, 5)
     want = _oracle_pixels(oracle, 0, film, ALL, False)
-    src = _device_film(film)
+    src = IO.upload_film(film)
     torch.cuda.synchronize()
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
@@ -229,7 +224,7 @@ def test_multi_device_context_runs_on_the_first_device(oracle):
     film = _adversarial(17, 33, 2)
     ctx = rayn_amd.Context([0, 0])
     try:
-        got = _device_pixels(ctx, 0, _device_film(film), ALL, True, 33, 17)
+        got = _device_pixels(ctx, 0, IO.upload_film(film), ALL, True, 33, 17)
     finally:
         ctx.close()
     assert np.array_equal(got, _oracle_pixels(oracle, 0, film, ALL, True))
@@ -239,7 +234,7 @@ def test_bad_arguments_return_invalid_arg_with_the_reference_text(gpu_ctx):
     import torch
     from rayn_amd import _lib
     L = _lib.lib()
-    d = _device_film(_adversarial(2, 3, 1))
+    d = IO.upload_film(_adversarial(2, 3, 1))
     out = torch.zeros(64, dtype=torch.uint8, device="cuda")
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -8,102 +8,36 @@ import os
 import numpy as np
 import pytest
 
+import device_io as IO
+import scenes
+import temporal_cases as TC
 import temporal_np as T
 from common import bits_equal
+from device_io import module_context as ctx  # noqa: F401
+from temporal_cases import SIZES
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-SIZES = [(48, 32), (40, 24), (50, 37)]  # whole 16x16 blocks; a width that is no multiple of 16; a size rayn's tile grid under-covers
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    """A context of this module's own: the tests switch its mul_add policy."""
-    import rayn_amd
-    c = rayn_amd.Context(0)
-    yield c
-    c.close()
-
-
-def _scene(name, res, camera="pinhole", moving=False):
-    """(world description, world, camera handle) of a test scene: s0 sphere SDF, s1 MandelBox, bulb Mandelbulb, multi = MandelBox + sphere SDF;
-    moving: the camera's origin and `at` drift, the fractal and one light proxy sphere translate."""
-    import rayn_amd as R
-    from rayn_amd import setup as S
-    from rayn_amd.scene import Linear, OrthographicCamera, Sphere, SphereSDF, ThinLensCamera, TracedSDF
-    cam, world = S.SCENES["s1" if name == "multi" else name](res)
-    if name == "multi":
-        world.hitables.push(TracedSDF(SphereSDF(0.6), 1, R.vec3(1.4, 0.9, 0.3)))
-    c = world.cameras.get(cam)
-    rs = (float(res[0]), float(res[1]))
-    if camera == "thin":
-        world.cameras[cam] = ThinLensCamera(rs, 55.0, 0.08, c.origin, c.at, c.up, R.vec3(0.2, 0.1, 0.0))
-    elif camera == "ortho":
-        world.cameras[cam] = OrthographicCamera(rs, 3.5, c.origin, c.at, c.up)
-    if moving:
-        c = world.cameras.get(cam)
-        c.origin = Linear(c.origin, R.vec3(0.9, -0.3, 0.15))
-        c.at = Linear(c.at, R.vec3(0.1, 0.2, 0.0))
-        for h in world.hitables:
-            if isinstance(h, TracedSDF) and h.transform_seq is None:
-                h.transform_seq = Linear(R.vec3(0.0, 0.0, 0.0), R.vec3(-0.6, 0.45, 0.3))
-        k = next(i for i, h in enumerate(world.hitables) if isinstance(h, Sphere) and h.radius < 1.0)
-        world.hitables[k].transform_seq = Linear(world.hitables[k].transform_seq, R.vec3(0.5, 0.25, -0.4))
-    return world.to_desc(cam), world, cam
-
-
-def _gpu_gbuffer(ctx, p):
-    import torch
-    from rayn_amd import film as F
-    g = F.alloc_gbuffer(p.width, p.height, "cuda")
-    ctx.gbuffer(p, g)
-    torch.cuda.synchronize()
-    return g, g["records"].cpu().numpy().reshape(-1, 4), g["object"].cpu().numpy().view(np.uint32)
-
-
-def _hist_dev(prev):
-    import torch
-    return None if prev is None else torch.from_numpy(T.join_history(*prev).copy()).cuda()
-
-
-def _gpu_accumulate(ctx, p, temporal, color, normal, rec, obj, prev, prev_cam, prev_time, guard=64):
-    """The entry through Context.temporal_accumulate on host arrays: (out colour (n, 3), (A, B, N, O)); checks the guard bytes behind both outputs."""
-    import torch
-    from rayn_amd import film as F
-    n = p.width * p.height
-    film = {"color": torch.from_numpy(np.ascontiguousarray(color, f32).reshape(-1)).cuda(), "normal": torch.from_numpy(np.ascontiguousarray(normal, f32).reshape(-1)).cuda()}
-    g = {"records": torch.from_numpy(np.ascontiguousarray(rec, f32).reshape(-1)).cuda(),
-         "object": torch.from_numpy(np.ascontiguousarray(obj, np.uint32).view(np.int32).reshape(-1)).cuda()}
-    d_prev = _hist_dev(prev)
-    keep = None if d_prev is None else d_prev.clone()
-    nb = F.temporal_history_bytes(p.width, p.height)
-    d_new = torch.full((nb + guard,), 0xA5, dtype=torch.uint8, device="cuda")
-    d_out = torch.full((3 * n + guard,), 7.0, dtype=torch.float32, device="cuda")
-    ctx.temporal_accumulate(p, temporal, film, g, d_prev, prev_cam, prev_time, d_new[:nb], d_out[: 3 * n])
-    torch.cuda.synchronize()
-    assert torch.all(d_new[nb:] == 0xA5) and torch.all(d_out[3 * n:] == 7.0), "the kernel wrote past an output"
-    assert keep is None or torch.equal(keep, d_prev), "the previous history was modified"
-    for k, want in (("color", color), ("normal", normal)):
-        assert np.array_equal(film[k].cpu().numpy().view(np.uint32), np.ascontiguousarray(want, f32).reshape(-1).view(np.uint32)), k
-    assert np.array_equal(g["records"].cpu().numpy().view(np.uint32), np.ascontiguousarray(rec, f32).reshape(-1).view(np.uint32))
-    return d_out[: 3 * n].cpu().numpy().reshape(n, 3), T.split_history(d_new[:nb].cpu().numpy(), n)
+def _gpu_accumulate(ctx, p, temporal, color, normal, rec, obj, prev, prev_cam, prev_time):
+    """The plain entry through Context.temporal_accumulate on host arrays: (out colour (n, 3), (A, B, N, O)), with temporal_cases' checks"""
+    return TC.gpu_accumulate(ctx, p, temporal, color, normal, rec, obj, prev, None, prev_cam, prev_time, moments=False)[:2]
 
 
 def _same(got, want, what):
     out_g, hist_g = got
     out_w, hist_w = want
-    assert bits_equal(out_g, out_w), (what, "colour")
-    for name, a, b in zip("ABN", hist_g[:3], hist_w[:3]):
-        assert bits_equal(a, b), (what, name)
-    assert np.array_equal(hist_g[3], hist_w[3]), (what, "object")
+    IO.assert_bits_equal(out_g, out_w, (what, "colour"))
+    TC.assert_history_equal(hist_g, hist_w, what)
 
 
 # ---- 1. the G-buffer against the oracle --------------------------------------------------------------------------------------------------
 
 def _check_gbuffer(ctx, oracle, wd, p, fma, what):
     ctx.upload_world(wd)
-    _, rec, obj = _gpu_gbuffer(ctx, p)
+    _, rec, obj = IO.gpu_gbuffer(ctx, p)
     want_rec, want_obj = T.gbuffer_oracle(oracle, wd, p, fma=fma)
     assert np.array_equal(obj, want_obj), (what, int((obj != want_obj).sum()))
     assert bits_equal(rec, want_rec), (what, int((rec.view(np.uint32) != want_rec.view(np.uint32)).sum()))
@@ -122,12 +56,12 @@ def test_gbuffer_is_the_oracles_closest_hit_at_the_pixel_centres(ctx, oracle, fm
         seen = set()
         for i, (scene, camera) in enumerate([("s0", "pinhole"), ("s1", "thin"), ("bulb", "ortho"), ("multi", "pinhole"), ("s1", "ortho"), ("bulb", "thin")]):
             w, h = SIZES[i % 3]
-            wd, _, _ = _scene(scene, (w, h), camera)
+            wd, _, _ = scenes.scene(scene, (w, h), camera)
             p = R.frame_params(w, h, 2, 3)
             seen |= set(_check_gbuffer(ctx, oracle, wd, p, bool(fma), (scene, camera, w, h)).tolist())
         assert len(seen) >= 4
         # misses: without the sky dome (hitable 0 swapped for a small sphere far away) most centre rays hit nothing
-        wd, _, _ = _scene("s1", (40, 24))
+        wd, _, _ = scenes.scene("s1", (40, 24))
         wd.hitables[0].radius = 0.05
         wd.hitables[0].center.x = 50.0
         objs = _check_gbuffer(ctx, oracle, wd, R.frame_params(40, 24, 2, 3), bool(fma), "misses")
@@ -140,7 +74,7 @@ def test_gbuffer_evaluates_animated_hitables_at_time_start(ctx, oracle):
     """A moving camera, a moving fractal and a moving sphere: at time_start = 0 the oracle's probe (ray time 0) is the reference directly; at
     time_start != 0 it is the oracle on the world frozen at that time in f32 (temporal_np.frozen_world)."""
     import rayn_amd as R
-    wd, _, _ = _scene("s1", (40, 24), moving=True)
+    wd, _, _ = scenes.scene("s1", (40, 24), moving=True)
     assert sum(wd.hitables[i].animated for i in range(wd.n_hitables)) == 2 and wd.camera.animated == 3
     for time_range in ((0.0, 1.0 / 24.0), (0.375, 0.4), (-1.25, -1.0)):
         p = R.frame_params(40, 24, 2, 3, time_range=time_range)
@@ -150,7 +84,7 @@ def test_gbuffer_evaluates_animated_hitables_at_time_start(ctx, oracle):
     t, obj = oracle.closest_hit(wd, p0, 0, org, dirs)  # the unfrozen world
     want_rec, want_obj = T.gbuffer_assemble(org, dirs, t, obj)
     ctx.upload_world(wd)
-    _, rec, got_obj = _gpu_gbuffer(ctx, p0)
+    _, rec, got_obj = IO.gpu_gbuffer(ctx, p0)
     assert np.array_equal(got_obj, want_obj) and bits_equal(rec, want_rec)
 
 
@@ -159,7 +93,7 @@ def test_film_gbuffer_after_a_render(oracle):
     from rayn_amd import setup as S
     K = R.ChannelKind
     w, h = 40, 24
-    _, world, cam = _scene("s1", (w, h))
+    _, world, cam = scenes.scene("s1", (w, h))
     film = R.Film([K.Color, K.Alpha, K.Background, K.WorldNormal], (w, h))
     with pytest.raises(ValueError, match="no rendered frame"):
         film.gbuffer()
@@ -173,55 +107,19 @@ def test_film_gbuffer_after_a_render(oracle):
 
 # ---- 2. the accumulate kernel against the restatement ------------------------------------------------------------------------------------
 
-def _random_inputs(w, h, seed, cam_kind, adversarial):
-    """A current frame and a previous history around the plane z = 0 seen by two different cameras, with random objects, depths near the
-    true ones, normals near +z and history lengths 0..cap; `adversarial` scatters NaN / inf / huge values over every plane."""
-    from rayn_amd import _abi
-    rng = np.random.default_rng(seed)
-    n = w * h
-    cur = T.ortho_camera(w, h, pixel=4.0 / h)
-    prev_cam = T.ortho_camera(w, h, origin_x=float(rng.uniform(-0.6, 0.6)), pixel=4.0 / h)
-    prev_cam.origin.y = prev_cam.at.y = float(rng.uniform(-0.5, 0.5))
-    if cam_kind != _abi.CAM_ORTHOGRAPHIC:
-        for c in (cur, prev_cam):
-            c.kind, c.vfov_or_size = cam_kind, 53.0
-        prev_cam.at.x += 0.3  # a rotation as well
-        prev_cam.animated, prev_cam.origin_vel.z, prev_cam.up_vel.x = 1 | 4, 0.5, 0.2
-    # current G-buffer: the plane's points under the current pixel centres (any camera kind may be handed any positions)
-    rec, obj, normal = T.ortho_plane_gbuffer(w, h, pixel=4.0 / h)
-    rec[:, 2] = rng.normal(0.0, 0.05, n)
-    obj = rng.choice(np.array([0, 1, 1, 1, 2, 0xFFFFFFFF], np.uint32), n)
-    rec[obj == T.MISS] = (0.0, 0.0, 0.0, np.inf)
-    normal = (normal + rng.normal(0.0, 0.3, (n, 3))).astype(f32)
-    color = rng.gamma(0.6, 0.5, (n, 3)).astype(f32)
-    # previous history: depths scattered around what the projection will expect (4 for the orthographic camera), lengths 0 .. 8
-    ok, fx, fy, te = T.project(prev_cam, 0.25, [rec[:, 0], rec[:, 1], rec[:, 2]], w, h)
-    A = np.concatenate([rng.gamma(0.6, 0.5, (n, 3)), rng.choice(np.array([0.0, 1.0, 2.0, 3.5, 8.0]), n)[:, None]], axis=1).astype(f32)
-    B = np.concatenate([rng.normal(size=(n, 3)), (np.nanmedian(te[ok]) if ok.any() else 4.0) * rng.choice(np.array([1.0, 1.0, 1.02, 0.97, 1.2]), n)[:, None]], axis=1).astype(f32)
-    N = np.concatenate([np.tile([0.0, 0.0, 1.0], (n, 1)) + rng.normal(0.0, 0.3, (n, 3)), np.zeros((n, 1))], axis=1).astype(f32)
-    O = rng.choice(np.array([0, 1, 1, 1, 2, 0xFFFFFFFF], np.uint32), n)
-    if adversarial:
-        special = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 3.0e38, -3.0e38, 1e-45, 1e30, -1e30], f32)
-        for plane in (color, normal, rec, A, B, N):
-            flat = plane.reshape(-1)
-            idx = rng.choice(flat.size, min(flat.size // 4, 6 * special.size), replace=False)
-            flat[idx] = np.resize(special, idx.size)
-    return cur, prev_cam, color, normal, rec, obj, (A, B, N, O)
-
-
 @pytest.mark.parametrize("cam_kind", [0, 1, 2])
 def test_accumulate_matches_the_restatement_on_adversarial_inputs(ctx, cam_kind):
     """Random and adversarial frames and histories (NaN and inf colours, positions, depths and history lengths, t = +inf, misses) under
     cameras that have translated and rotated so that taps straddle every image border, for every film size, with max_history 1, a history at
     the cap, and each test on and off."""
     import rayn_amd as R
-    wd, _, _ = _scene("s1", (40, 24), moving=True)  # hitables 1 (the fractal) and one sphere are animated: object motion is exercised too
+    wd, _, _ = scenes.scene("s1", (40, 24), moving=True)  # hitables 1 (the fractal) and one sphere are animated: object motion is exercised too
     ctx.upload_world(wd)
     hit = T.world_hitables(wd)
     params = [R.Temporal(4, 0.05, -1.0), R.Temporal(1, 0.05, 0.9), R.Temporal(8, 0.0, 0.5), R.Temporal(3, 1e30, 1.0), R.Temporal(65536, 0.25, -1.0)]
     for si, (w, h) in enumerate(SIZES + [(1, 1), (17, 13)]):
         for adversarial in (False, True):
-            cur, prev_cam, color, normal, rec, obj, prev = _random_inputs(w, h, 10 * si + adversarial, cam_kind, adversarial)
+            cur, prev_cam, color, normal, rec, obj, prev = TC.random_inputs(w, h, 10 * si + adversarial, cam_kind, adversarial)
             p = R.frame_params(w, h, 1, 1, time_range=(0.75, 0.8))
             for tp in params[(si + adversarial) % 2::2] if w > 17 else params:
                 want = T.accumulate(w, h, color, normal, rec, obj, prev, prev_cam, 0.25, 0.75, hit, tp.max_history, tp.depth_tolerance, tp.normal_min)
@@ -239,7 +137,7 @@ def test_accumulate_on_exactly_integral_reprojections(ctx):
     """The exact orthographic case: fx and fy are integers, so one tap has weight 1 and three have weight 0 (they still count: 0 * c_tap);
     camera shifts by whole and quarter pixels across all four borders; a history that has reached the cap stays there."""
     import rayn_amd as R
-    wd, _, _ = _scene("s0", (16, 8))
+    wd, _, _ = scenes.scene("s0", (16, 8))
     ctx.upload_world(wd)
     w, h = 16, 8
     rec, obj, normal = T.ortho_plane_gbuffer(w, h)
@@ -260,32 +158,18 @@ def test_accumulate_on_exactly_integral_reprojections(ctx):
         assert set(np.unique(n1).tolist()) <= {1.0, 3.0} and ((n1 == 3.0).any() or abs(sx) >= w)
 
 
-def _render_frames(ctx, wd, ps, bounces):
-    import torch
-    import rayn_amd as R
-    ctx.upload_world(wd)
-    frames = []
-    for p in ps:
-        tabs = R.build_tables(4 * p.samples, bounces, p.volume_marches, p.frame, p.width, p.height)
-        out = R.film.alloc_device_film(p.width, p.height, "cuda")
-        ctx.render_device(p, [torch.from_numpy(t).cuda() for t in tabs], out)
-        torch.cuda.synchronize()
-        frames.append(out)
-    return frames
-
-
 def test_accumulate_on_a_rendered_sequence_with_a_moving_camera_and_a_moving_sphere(ctx):
     """Three rendered frames (GPU film, GPU G-buffer) of a scene whose camera, fractal and one sphere move: the kernel's histories and
     colours equal the restatement's, frame by frame, each fed the other's previous history."""
     import rayn_amd as R
     w, h = 40, 24
-    wd, _, _ = _scene("s1", (w, h), moving=True)
+    wd, _, _ = scenes.scene("s1", (w, h), moving=True)
     ps = [R.frame_params(w, h, 1, 2, frame=f) for f in (1, 2, 4)]
-    frames = _render_frames(ctx, wd, ps, 2)
+    frames = IO.render_frames(ctx, wd, ps, 2)
     tp = R.Temporal(8, 0.05, 0.3)
     prev, prev_time, blended = None, 0.0, 0
     for p, film in zip(ps, frames):
-        _, rec, obj = _gpu_gbuffer(ctx, p)
+        _, rec, obj = IO.gpu_gbuffer(ctx, p)
         color, normal = film["color"].cpu().numpy(), film["normal"].cpu().numpy()
         want = T.accumulate(w, h, color, normal, rec, obj, prev, wd.camera, prev_time, p.time_start, T.world_hitables(wd), tp.max_history, tp.depth_tolerance, tp.normal_min)
         got = _gpu_accumulate(ctx, p, tp, color, normal, rec, obj, prev, None if prev is None else wd.camera, prev_time)
@@ -296,10 +180,6 @@ def test_accumulate_on_a_rendered_sequence_with_a_moving_camera_and_a_moving_sph
 
 
 # ---- 3. the sequence wiring -------------------------------------------------------------------------------------------------------------
-
-def _read(folder):
-    return {f: open(os.path.join(folder, f), "rb").read() for f in sorted(os.listdir(folder))}
-
 
 @pytest.mark.parametrize("with_denoise", [False, True])
 def test_render_sequence_with_temporal_is_the_plain_loop_of_the_entries(tmp_path, with_denoise):
@@ -312,7 +192,7 @@ def test_render_sequence_with_temporal_is_the_plain_loop_of_the_entries(tmp_path
     from rayn_amd import setup as S
     K = R.ChannelKind
     w, h, frames, samples = 50, 37, [2, 3, 7], 1
-    _, world, cam = _scene("s1", (w, h), moving=True)
+    _, world, cam = scenes.scene("s1", (w, h), moving=True)
     integ = R.PathTracingIntegrator(max_bounces=2, volume_marches=S.VOLUME_MARCHES_PER_SAMPLE)
     filt = R.BlackmanHarrisFilter(S.FILTER_RADIUS)
     kinds = [K.Color, K.Alpha, K.Background, K.WorldNormal]
@@ -320,7 +200,7 @@ def test_render_sequence_with_temporal_is_the_plain_loop_of_the_entries(tmp_path
     film = R.Film(kinds, (w, h))
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, 24, 1.0 / 24.0, samples, [K.Color, K.WorldNormal], str(tmp_path / "seq"), "a",
                          denoise=dn, temporal=tp)
-    got = _read(tmp_path / "seq")
+    got = IO.read_folder(tmp_path / "seq")
     suffix = "color_temporal_denoised" if with_denoise else "color_temporal"
     assert sorted(got) == sorted(f"a_{f:04d}_{s}.png" for f in frames for s in (suffix, "normal"))
     # the loop
@@ -332,11 +212,7 @@ def test_render_sequence_with_temporal_is_the_plain_loop_of_the_entries(tmp_path
     g, acc, prev_start = F.alloc_gbuffer(w, h, "cuda"), torch.empty(w * h, 3, dtype=torch.float32, device="cuda"), None
     img = torch.empty(h * w * 3, dtype=torch.uint8, device="cuda")
     for i, frame in enumerate(frames):
-        start = f32(frame) * (f32(1.0) / f32(24))
-        p = R.frame_params(w, h, samples, 2, frame=frame, time_range=(float(start), float(f32(start + f32(1.0 / 24.0)))))
-        out = F.alloc_device_film(w, h, "cuda")
-        tabs = R.build_tables(4 * samples, 2, p.volume_marches, frame, w, h, filt)
-        ctx.render_device(p, [torch.from_numpy(t).cuda() for t in tabs], out)
+        p, out = IO.render_sequence_frame(ctx, w, h, frame, samples, 2, filt)
         ctx.gbuffer(p, g)
         ctx.temporal_accumulate(p, tp, out, g, None if i == 0 else hist[(i + 1) % 2], None if i == 0 else desc.camera, 0.0 if i == 0 else prev_start,
                                 hist[i % 2], acc)
@@ -351,7 +227,7 @@ def test_render_sequence_with_temporal_is_the_plain_loop_of_the_entries(tmp_path
     # the accumulation changed the picture, and only the Color one
     plain = R.Film(kinds, (w, h))
     plain.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, 24, 1.0 / 24.0, samples, [K.Color, K.WorldNormal], str(tmp_path / "plain"), "a", denoise=dn)
-    base = _read(tmp_path / "plain")
+    base = IO.read_folder(tmp_path / "plain")
     plain_suffix = "color_denoised" if with_denoise else "color"
     assert got[f"a_0002_{suffix}.png"] == base[f"a_0002_{plain_suffix}.png"]  # the first frame has no history
     assert got[f"a_0007_{suffix}.png"] != base[f"a_0007_{plain_suffix}.png"]
@@ -364,7 +240,7 @@ def test_render_sequence_without_temporal_is_unchanged(tmp_path):
     from rayn_amd import setup as S
     K = R.ChannelKind
     w, h, frames = 40, 24, [1, 2]
-    _, world, cam = _scene("s1", (w, h), moving=True)
+    _, world, cam = scenes.scene("s1", (w, h), moving=True)
     integ = R.PathTracingIntegrator(max_bounces=2, volume_marches=S.VOLUME_MARCHES_PER_SAMPLE)
     filt = R.BlackmanHarrisFilter(S.FILTER_RADIUS)
     kinds = [K.Color, K.Alpha, K.Background, K.WorldNormal]
@@ -373,12 +249,11 @@ def test_render_sequence_without_temporal_is_unchanged(tmp_path):
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, 24, 1.0 / 24.0, 1, [K.Alpha], str(tmp_path / "alpha"), "a", temporal=R.Temporal())
     one = R.Film(kinds, (w, h))
     for frame in frames:
-        start = f32(frame) * (f32(1.0) / f32(24))
-        one.render_frame_into(world, cam, integ, filt, S.TILE_SIZE, frame, (float(start), float(f32(start + f32(1.0 / 24.0)))), 1)
+        one.render_frame_into(world, cam, integ, filt, S.TILE_SIZE, frame, IO.shutter_range(frame), 1)
         one.save_to([K.Color, K.Alpha], str(tmp_path / "loop"), f"a_{frame:04d}")
-    want = _read(tmp_path / "loop")
-    assert _read(tmp_path / "none") == want
-    assert _read(tmp_path / "alpha") == {k: v for k, v in want.items() if k.endswith("_alpha.png")}
+    want = IO.read_folder(tmp_path / "loop")
+    assert IO.read_folder(tmp_path / "none") == want
+    assert IO.read_folder(tmp_path / "alpha") == {k: v for k, v in want.items() if k.endswith("_alpha.png")}
     no_normal = R.Film([K.Color, K.Alpha, K.Background], (w, h))
     with pytest.raises(ValueError, match="WorldNormal"):
         no_normal.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, 24, 1.0 / 24.0, 1, [K.Color], str(tmp_path / "x"), "a", temporal=R.Temporal())
@@ -396,7 +271,7 @@ def test_bad_arguments_are_invalid_arg_with_a_text(ctx):
     from rayn_amd import film as F
     L = ctx._L
     w, h, n = 40, 24, 40 * 24
-    wd, _, _ = _scene("s0", (w, h))
+    wd, _, _ = scenes.scene("s0", (w, h))
     fresh = R.Context(0)
     p = R.frame_params(w, h, 1, 1)
     vp = lambda t: C.c_void_p(t.data_ptr())
@@ -465,28 +340,8 @@ def test_temporal_accumulation_lowers_the_error_of_a_moving_camera_sequence(tmp_
     """The shipped scene at 160x96 under a camera whose origin moves, 8 frames at samples=2: the MSE of the saturated Color + Background of
     the temporally accumulated last frame against a samples=256 render of it, relative to the raw last frame's, is below 1 and reaches the
     ratio measured on the CPU path (times 1.05: the GPU path is bit-identical to it; the 5 % only absorbs a later change of defaults)."""
-    import torch
     import rayn_amd as R
-    from rayn_amd import film as F
-    D = T.DefaultsCase
-    wd, ps, pref = D.scene()
-    c = R.Context(0)
-    try:
-        frames = _render_frames(c, wd, ps + [pref], D.BOUNCES)
-        ref = frames.pop()
-        want = np.clip(ref["color"].cpu().numpy().reshape(D.H, D.W, 3).astype(np.float64) + ref["background"].cpu().numpy().reshape(D.H, D.W, 3), 0.0, 1.0)
-        hist = [torch.empty(F.temporal_history_bytes(D.W, D.H), dtype=torch.uint8, device="cuda") for _ in range(2)]
-        g, acc = F.alloc_gbuffer(D.W, D.H, "cuda"), torch.empty(D.W * D.H, 3, dtype=torch.float32, device="cuda")
-        for i, (p, film) in enumerate(zip(ps, frames)):
-            c.gbuffer(p, g)
-            c.temporal_accumulate(p, R.Temporal(), film, g, None if i == 0 else hist[(i + 1) % 2], None if i == 0 else wd.camera,
-                                  0.0 if i == 0 else ps[i - 1].time_start, hist[i % 2], acc)
-        torch.cuda.synchronize()
-        last = frames[-1]
-        bg = last["background"].cpu().numpy().reshape(D.H, D.W, 3)
-        raw, temporal = D.mse(last["color"].cpu().numpy(), bg, want), D.mse(acc.cpu().numpy(), bg, want)
-    finally:
-        c.close()
+    raw, temporal, _ = TC.defaults_case_errors(R.Temporal(), moments=False)
     print(f"MSE raw {raw:.4e}, temporal {temporal:.4e}, ratio {temporal / raw:.4f}x (CPU path: {MEASURED_RATIO}x)")
     assert temporal / raw < 1.0
     assert temporal / raw < MEASURED_RATIO * 1.05, (raw, temporal)

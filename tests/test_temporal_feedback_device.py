@@ -10,24 +10,19 @@ import os
 import numpy as np
 import pytest
 
+import device_io as IO
+import scenes
 import temporal_feedback_np as TF
 import temporal_np as T
 import temporal_variance_np as TV
-from test_temporal_feedback import H0, SIGMAS, W0, adversarial_inputs, restate
-from test_temporal_variance_device import GUARD, _dev, _dev_bytes, _moving_scene, _read
+from device_io import module_context as ctx, same_bits  # noqa: F401
+from temporal_cases import GUARD, defaults_case_errors
+from temporal_feedback_cases import H0, SIGMAS, W0, adversarial_inputs, restate
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 BETAS = (0.0, 0.5, 1.0)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import rayn_amd
-    c = rayn_amd.Context(0)
-    yield c
-    c.close()
 
 
 def _bits(a):
@@ -44,13 +39,15 @@ def _call(ctx, w, h, d, g, hist_bytes, d_mom, L, sigmas, beta):
     arena = torch.full((hb + 2 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
     d_hist = arena[GUARD: GUARD + hb]
     d_hist.copy_(torch.from_numpy(hist_bytes))
-    out = torch.full((3 * n + GUARD,), 7.0, dtype=torch.float32, device="cuda")
-    var = torch.full((n + GUARD,), 7.0, dtype=torch.float32, device="cuda")
-    ctx.denoise_temporal_variance(w, h, d, g, d_hist, d_mom, out[: 3 * n], VarianceDenoise(L, *sigmas), var[:n], feedback=beta)
+    full_out, out = IO.guarded(3 * n, torch.float32, 7.0, GUARD)
+    full_var, var = IO.guarded(n, torch.float32, 7.0, GUARD)
+    ctx.denoise_temporal_variance(w, h, d, g, d_hist, d_mom, out, VarianceDenoise(L, *sigmas), var, feedback=beta)
     torch.cuda.synchronize()
-    assert torch.all(arena[:GUARD] == 0xA5) and torch.all(arena[GUARD + hb:] == 0xA5), "a kernel wrote outside the history"
-    assert torch.all(out[3 * n:] == 7.0) and torch.all(var[n:] == 7.0), "a kernel wrote past an output"
-    return out[: 3 * n].cpu().numpy().reshape(n, 3), var[:n].cpu().numpy(), d_hist.cpu().numpy()
+    assert torch.all(arena[:GUARD] == 0xA5), "a kernel wrote in front of the history"
+    IO.assert_guards(arena, GUARD + hb, 0xA5, "history")
+    IO.assert_guards(full_out, 3 * n, 7.0, "colour")
+    IO.assert_guards(full_var, n, 7.0, "variance")
+    return out.cpu().numpy().reshape(n, 3), var.cpu().numpy(), d_hist.cpu().numpy()
 
 
 def test_history_matches_the_restatement_and_the_outputs_are_the_existing_entrys(ctx, oracle):
@@ -60,10 +57,11 @@ def test_history_matches_the_restatement_and_the_outputs_are_the_existing_entrys
     inp = adversarial_inputs(w, h, 11)
     hist_bytes = np.ascontiguousarray(inp["hist"])
     before = T.split_history(hist_bytes, n)
-    d = {"color": _dev(inp["color"]), "normal": _dev(inp["normal"]), "alpha": _dev(inp["alpha"])}
-    g = {"object": _dev(inp["obj"].view(np.int32), np.int32)}
-    d_mom = _dev_bytes(inp["mom"])
-    keep = {k: t.clone() for k, t in dict(d, object=g["object"], mom=d_mom).items()}
+    d = {"color": IO.upload(inp["color"]), "normal": IO.upload(inp["normal"]), "alpha": IO.upload(inp["alpha"])}
+    g = {"object": IO.upload(inp["obj"].view(np.int32), np.int32)}
+    d_mom = IO.upload_bytes(inp["mom"])
+    ins = dict(d, object=g["object"], mom=d_mom)
+    keep = IO.snapshot(ins)
     for sigmas in SIGMAS:
         want = {beta: restate(w, h, inp, 1, sigmas, beta)[2] for beta in BETAS}  # the write-back is pass 0's: the same for every L
         changed = (_bits(want[1.0][0]) != _bits(before[0])).any(axis=1)
@@ -73,12 +71,10 @@ def test_history_matches_the_restatement_and_the_outputs_are_the_existing_entrys
             assert np.array_equal(plain_h, hist_bytes), (L, sigmas, "a strength of 0 changed the history")
             for beta in BETAS[1:]:
                 got_c, got_v, got_h = _call(ctx, w, h, d, g, hist_bytes, d_mom, L, sigmas, beta)
-                assert np.array_equal(_bits(got_c), _bits(plain_c)) and np.array_equal(_bits(got_v), _bits(plain_v)), (L, sigmas, beta, "outputs")
+                assert same_bits(got_c, plain_c) and same_bits(got_v, plain_v), (L, sigmas, beta, "outputs")
                 for name, a, b in zip("ABNO", T.split_history(got_h, n), want[beta]):
-                    assert np.array_equal(_bits(a), _bits(b)), (L, sigmas, beta, name, int((_bits(a) != _bits(b)).sum()))
-    import torch
-    for k, t in dict(d, object=g["object"], mom=d_mom).items():
-        assert torch.equal(t.view(torch.int32), keep[k].view(torch.int32)), (k, "an input was modified")  # as bits: the inputs hold NaNs
+                    assert same_bits(a, b), (L, sigmas, beta, name, int((_bits(a) != _bits(b)).sum()))
+    IO.assert_unchanged(ins, keep, "an input")  # as bits: the inputs hold NaNs
 
 
 def test_the_new_entry_with_a_strength_of_zero_writes_nothing(ctx):
@@ -89,8 +85,8 @@ def test_the_new_entry_with_a_strength_of_zero_writes_nothing(ctx):
     n = w * h
     inp = adversarial_inputs(w, h, 12)
     vp = lambda t: C.c_void_p(t.data_ptr())
-    color, normal, alpha, obj = _dev(inp["color"]), _dev(inp["normal"]), _dev(inp["alpha"]), _dev(inp["obj"].view(np.int32), np.int32)
-    d_hist, d_mom = _dev_bytes(inp["hist"]), _dev_bytes(inp["mom"])
+    color, normal, alpha, obj = IO.upload(inp["color"]), IO.upload(inp["normal"]), IO.upload(inp["alpha"]), IO.upload(inp["obj"].view(np.int32), np.int32)
+    d_hist, d_mom = IO.upload_bytes(inp["hist"]), IO.upload_bytes(inp["mom"])
     scratch = torch.empty(F.denoise_variance_scratch_bytes(w, h), dtype=torch.uint8, device="cuda")
     res = []
     for entry, extra in ((ctx._L.rayn_hip_denoise_temporal_variance_device, ()), (ctx._L.rayn_hip_denoise_temporal_variance_feedback_device, (0.0,)),
@@ -103,7 +99,7 @@ def test_the_new_entry_with_a_strength_of_zero_writes_nothing(ctx):
         assert np.array_equal(d_hist.cpu().numpy(), inp["hist"])
         res.append((out.cpu().numpy(), var.cpu().numpy()))
     for c, v in res[1:]:
-        assert np.array_equal(_bits(c), _bits(res[0][0])) and np.array_equal(_bits(v), _bits(res[0][1]))
+        assert same_bits(c, res[0][0]) and same_bits(v, res[0][1])
 
 
 # ---- 2. a rendered sequence ------------------------------------------------------------------------------------------------------------------
@@ -122,7 +118,7 @@ def test_render_sequence_with_feedback_is_the_plain_loop_of_the_entries_and_the_
     K = R.ChannelKind
     w, h, frames, samples, bounces, beta = 48, 32, [1, 2, 3], 1, 2, 0.5
     n = w * h
-    world, cam = _moving_scene(w, h)
+    world, cam = scenes.moving_scene(w, h)
     integ = R.PathTracingIntegrator(max_bounces=bounces, volume_marches=S.VOLUME_MARCHES_PER_SAMPLE)
     filt = R.BlackmanHarrisFilter(S.FILTER_RADIUS)
     dn = R.VarianceDenoise(2, 4.0, 0.4, 0.3)
@@ -132,7 +128,7 @@ def test_render_sequence_with_feedback_is_the_plain_loop_of_the_entries_and_the_
 
     def sequence(name, temporal):
         film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, 24, 1.0 / 24.0, samples, [K.Color], str(tmp_path / name), "a", denoise=dn, temporal=temporal)
-        return _read(tmp_path / name)
+        return IO.read_folder(tmp_path / name)
 
     got = sequence("fed", R.Temporal(feedback=beta))
     names = [f"a_{f:04d}_color_temporal_denoised.png" for f in frames]
@@ -151,12 +147,9 @@ def test_render_sequence_with_feedback_is_the_plain_loop_of_the_entries_and_the_
     img = torch.empty(n * 3, dtype=torch.uint8, device="cuda")
     prev_start, prev_host, fed = None, (None, None), 0
     for i, frame in enumerate(frames):
-        start = f32(frame) * (f32(1.0) / f32(24))
-        p = R.frame_params(w, h, samples, bounces, frame=frame, time_range=(float(start), float(f32(start + f32(1.0 / 24.0)))))
         first = i == 0
         # the plain loop of the entries
-        out = F.alloc_device_film(w, h, "cuda")
-        ctx.render_device(p, [torch.from_numpy(t).cuda() for t in R.build_tables(4 * samples, bounces, p.volume_marches, frame, w, h, filt)], out)
+        p, out = IO.render_sequence_frame(ctx, w, h, frame, samples, bounces, filt)
         ctx.gbuffer(p, g)
         ctx.temporal_accumulate(p, tp, out, g, None if first else hist[(i + 1) % 2], None if first else desc.camera, 0.0 if first else prev_start,
                                 hist[i % 2], acc, None, None if first else mom[(i + 1) % 2], mom[i % 2])
@@ -175,7 +168,7 @@ def test_render_sequence_with_feedback_is_the_plain_loop_of_the_entries_and_the_
         assert open(tmp_path / "np.png", "rb").read() == got[names[i]], (frame, "the restatement on the oracle's frames")
         g_hist = T.split_history(hist[i % 2].cpu().numpy(), n)
         for name, a, b in zip("ABNO", g_hist, w_fed):
-            assert np.array_equal(_bits(a), _bits(b)), (frame, name)
+            assert same_bits(a, b), (frame, name)
         fed += int((_bits(w_fed[0]) != _bits(w_hist[0])).any(axis=1).sum())
         prev_start, prev_host = p.time_start, (w_fed, w_mom)
     assert fed > n // 2  # the write-back changed the history of the surfaces' pixels in every frame
@@ -271,33 +264,8 @@ def test_the_best_feedback_point_reaches_the_ratio_measured_on_the_cpu_path():
     with VarianceDenoise(1, 2.0, 0.4, 0.3), every frame's filter feeding the next frame's history, reaches the ratio measured on the CPU
     path (times 1.05, the project's margin for this kind of test: the GPU path is bit-identical to it).  That ratio is above the one
     without feedback: on this sequence the feedback does not pay, and nothing here claims it does."""
-    import torch
     import rayn_amd as R
-    from rayn_amd import film as F
-    from test_temporal_device import _render_frames
-    D = T.DefaultsCase
-    wd, ps, pref = D.scene()
-    dn, tp = R.VarianceDenoise(*BEST_DENOISE), R.Temporal(feedback=BEST_FEEDBACK)
-    c = R.Context(0)
-    try:
-        frames = _render_frames(c, wd, ps + [pref], D.BOUNCES)
-        ref = frames.pop()
-        want = np.clip(ref["color"].cpu().numpy().reshape(D.H, D.W, 3).astype(np.float64) + ref["background"].cpu().numpy().reshape(D.H, D.W, 3), 0.0, 1.0)
-        hist = [torch.empty(F.temporal_history_bytes(D.W, D.H), dtype=torch.uint8, device="cuda") for _ in range(2)]
-        mom = [torch.empty(F.temporal_moments_bytes(D.W, D.H), dtype=torch.uint8, device="cuda") for _ in range(2)]
-        g, acc = F.alloc_gbuffer(D.W, D.H, "cuda"), torch.empty(D.W * D.H, 3, dtype=torch.float32, device="cuda")
-        shown = torch.empty_like(acc)
-        for i, (p, film) in enumerate(zip(ps, frames)):
-            c.gbuffer(p, g)
-            c.temporal_accumulate(p, tp, film, g, None if i == 0 else hist[(i + 1) % 2], None if i == 0 else wd.camera,
-                                  0.0 if i == 0 else ps[i - 1].time_start, hist[i % 2], acc, None, None if i == 0 else mom[(i + 1) % 2], mom[i % 2])
-            c.denoise_temporal_variance(D.W, D.H, dict(film, color=acc), g, hist[i % 2], mom[i % 2], shown, dn, feedback=tp.feedback)
-        torch.cuda.synchronize()
-        last = frames[-1]
-        bg = last["background"].cpu().numpy().reshape(D.H, D.W, 3)
-        raw, both = (D.mse(x.cpu().numpy(), bg, want) for x in (last["color"], shown))
-    finally:
-        c.close()
+    raw, _, both = defaults_case_errors(R.Temporal(feedback=BEST_FEEDBACK), R.VarianceDenoise(*BEST_DENOISE), feedback=True)
     print(f"MSE raw {raw:.4e}, Temporal(feedback={BEST_FEEDBACK}) + VarianceDenoise{BEST_DENOISE} {both / raw:.4f}x (CPU path: {MEASURED_RATIO}x; "
           f"without feedback at the recommended setting: {WITHOUT_FEEDBACK}x)")
     assert both / raw < MEASURED_RATIO * 1.05, (raw, both)

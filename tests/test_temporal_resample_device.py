@@ -9,71 +9,39 @@ import os
 import numpy as np
 import pytest
 
+import device_io as IO
+import scenes
+import temporal_cases as TC
 import temporal_np as T
 import temporal_resample_cases as K
 import temporal_resample_np as TR
 from common import bits_equal
+from device_io import module_context as ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-GUARD = 64
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    """A context of this module's own: the tests switch its mul_add policy."""
-    import rayn_amd
-    c = rayn_amd.Context(0)
-    yield c
-    c.close()
-
-
-def _dev(a, dtype=f32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype).reshape(-1).copy()).cuda()
-
-
-def _dev_bytes(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).cuda()
 
 
 def _entry(ctx, p, tp, resample, color, normal, rec, obj, prev, prev_mom, prev_cam, prev_time, moments):
-    """The new entry, called directly, on host arrays: (out (n, 3), (A, B, N, O), moments (n, 2) or None); checks the guard bytes behind
-    every output and that the previous history and moments were left alone."""
-    import torch
+    """The new entry, called directly, on host arrays: (out (n, 3), (A, B, N, O), moments (n, 2) or None), with temporal_cases' checks"""
     from rayn_amd import _abi
-    from rayn_amd import film as F
-    n = p.width * p.height
-    d_c, d_n, d_r, d_o = _dev(color), _dev(normal), _dev(rec), _dev(np.asarray(obj, np.uint32).view(np.int32), np.int32)
-    d_prev = None if prev is None else _dev_bytes(T.join_history(*prev))
-    d_pm = None if prev is None or not moments else _dev_bytes(np.asarray(prev_mom, f32))
-    keep = [None if t is None else t.clone() for t in (d_prev, d_pm)]
-    hb, mb = F.temporal_history_bytes(p.width, p.height), F.temporal_moments_bytes(p.width, p.height)
-    d_new = torch.full((hb + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    d_nm = torch.full((mb + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    d_out = torch.full((3 * n + GUARD,), 7.0, dtype=torch.float32, device="cuda")
     vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     t_abi, rp = tp.to_abi(), _abi.TemporalResampleParams(resample)
-    rc = ctx._L.rayn_hip_temporal_accumulate_resample_device(
-        ctx.h, C.byref(p), C.byref(t_abi), C.byref(rp), None if prev_cam is None else C.byref(prev_cam), float(prev_time), vp(d_c), vp(d_n), vp(d_r), vp(d_o),
-        vp(d_prev), vp(d_new), hb, vp(d_pm), vp(d_nm) if moments else None, mb if moments else 0, vp(d_out), None)
-    assert rc == 0, ctx.last_error()
-    torch.cuda.synchronize()
-    assert torch.all(d_new[hb:] == 0xA5) and torch.all(d_out[3 * n:] == 7.0) and torch.all(d_nm[mb if moments else 0:] == 0xA5), "a kernel wrote past an output"
-    for t, k in zip((d_prev, d_pm), keep):
-        assert k is None or torch.equal(t, k), "a previous buffer was modified"
-    mom = d_nm[:mb].cpu().numpy().view(f32).reshape(n, 2) if moments else None
-    return d_out[: 3 * n].cpu().numpy().reshape(n, 3), T.split_history(d_new[:hb].cpu().numpy(), n), mom
+
+    def call(film, g, d_prev, d_new, d_out, d_pm, d_nm):
+        rc = ctx._L.rayn_hip_temporal_accumulate_resample_device(
+            ctx.h, C.byref(p), C.byref(t_abi), C.byref(rp), None if prev_cam is None else C.byref(prev_cam), float(prev_time), vp(film["color"]), vp(film["normal"]),
+            vp(g["records"]), vp(g["object"]), vp(d_prev), vp(d_new), d_new.numel(), vp(d_pm), vp(d_nm), 0 if d_nm is None else d_nm.numel(), vp(d_out), None)
+        assert rc == 0, ctx.last_error()
+
+    return TC.gpu_accumulate(ctx, p, tp, color, normal, rec, obj, prev, prev_mom, prev_cam, prev_time, moments, call)
 
 
 def _same(got, want, what):
     """colour, planes A, B, N and the moments bit for bit (NaN payloads aside), the objects equal"""
-    assert bits_equal(got[0], want[0]), (what, "colour")
-    for name, a, b in zip("ABN", got[1][:3], want[1][:3]):
-        assert bits_equal(a, b), (what, name)
-    assert np.array_equal(got[1][3], want[1][3]), (what, "object")
+    IO.assert_bits_equal(got[0], want[0], (what, "colour"))
+    TC.assert_history_equal(got[1], want[1], what)
     assert (got[2] is None) == (want[2] is None) and (got[2] is None or bits_equal(got[2], want[2])), (what, "moments")
 
 
@@ -112,19 +80,18 @@ def test_catmull_rom_matches_the_restatement_on_adversarial_inputs(ctx, cam_kind
 @pytest.mark.parametrize("cam_kind", [0, 1, 2])
 def test_resample_0_through_the_new_entry_is_the_two_older_entries(ctx, cam_kind):
     import rayn_amd as R
-    from test_temporal_variance_device import _accumulate
     _, hit = _upload_moving_world(ctx)
     pc, c, nr, rec, obj, prev, M = K.adversarial_inputs(5 + cam_kind, cam_kind)
     p = R.frame_params(K.W, K.H, 1, 1, time_range=(K.CUR_TIME, 0.8))
     for normal_min, moments in ((-1.0, False), (0.8, True)):
         tp = R.Temporal(8, 0.05, normal_min)
-        old = _accumulate(ctx, p, tp, c, nr, rec, obj, prev, M, pc, K.PREV_TIME, moments=moments)
+        old = TC.gpu_accumulate(ctx, p, tp, c, nr, rec, obj, prev, M, pc, K.PREV_TIME, moments=moments)
         new = _entry(ctx, p, tp, 0, c, nr, rec, obj, prev, M, pc, K.PREV_TIME, moments)
         _same(new, old, (cam_kind, moments))
         cubic = _entry(ctx, p, tp, 1, c, nr, rec, obj, prev, M, pc, K.PREV_TIME, moments)
         assert not bits_equal(cubic[0], old[0])  # and the option does something
     # Context.temporal_accumulate routes "catmull_rom" to the new entry
-    via_ctx = _accumulate(ctx, p, R.Temporal(8, 0.05, 0.8, resample="catmull_rom"), c, nr, rec, obj, prev, M, pc, K.PREV_TIME, moments=True)
+    via_ctx = TC.gpu_accumulate(ctx, p, R.Temporal(8, 0.05, 0.8, resample="catmull_rom"), c, nr, rec, obj, prev, M, pc, K.PREV_TIME, moments=True)
     _same(via_ctx, cubic, "Context.temporal_accumulate")
 
 
@@ -132,8 +99,7 @@ def test_catmull_rom_on_exactly_integral_reprojections(ctx):
     """The exact orthographic case of test_accumulate_on_exactly_integral_reprojections: camera shifts by whole and quarter pixels across
     all four borders; at whole pixels t = 0 and the footprint's weights are (-0, 1, 0, +-0)."""
     import rayn_amd as R
-    from test_temporal_device import _scene
-    wd, _, _ = _scene("s0", (16, 8))
+    wd, _, _ = scenes.scene("s0", (16, 8))
     ctx.upload_world(wd)
     w, h = 16, 8
     rec, obj, normal = T.ortho_plane_gbuffer(w, h)
@@ -157,8 +123,7 @@ def test_catmull_rom_at_the_borders_and_on_tiny_images(ctx):
     """3x2 (never the cubic arm) and 4x4 (the one footprint that fits) bit for bit, and an 8x6 image whose reprojection puts x0 - 1 < 0 on
     the left columns and x0 + 2 >= width on the right ones, y likewise."""
     import rayn_amd as R
-    from test_temporal_device import _scene
-    wd, _, _ = _scene("s0", (16, 8))
+    wd, _, _ = scenes.scene("s0", (16, 8))
     ctx.upload_world(wd)
     rng = np.random.default_rng(11)
     seen = {}
@@ -187,8 +152,7 @@ def test_catmull_rom_with_non_finite_history_inside_full_footprints(ctx):
     footprints: the clamp's handling of NaN and infinite sums and the reset behind it, bit for bit (tests/test_temporal_resample.py
     asserts on the CPU that the restatement takes each of those paths here)."""
     import rayn_amd as R
-    from test_temporal_device import _scene
-    wd, _, _ = _scene("s0", (16, 8))
+    wd, _, _ = scenes.scene("s0", (16, 8))
     ctx.upload_world(wd)
     w, h = 12, 10
     pc, c, nr, rec, obj, prev, M, _, _ = K.non_finite_history_case(w, h)
@@ -203,13 +167,12 @@ def test_catmull_rom_on_a_rendered_sequence_with_a_moving_camera_and_a_moving_sp
     """48x32, 3 frames of 4 spp (GPU film, GPU G-buffer) of a scene whose camera, fractal and one sphere move: the entry chained by hand,
     with moments, equals the restatement frame by frame, each fed the kernel's previous history and moments."""
     import rayn_amd as R
-    from test_temporal_device import _gpu_gbuffer, _render_frames, _scene
     w, h = 48, 32
-    wd, _, _ = _scene("s1", (w, h), moving=True)
+    wd, _, _ = scenes.scene("s1", (w, h), moving=True)
     ps = [R.frame_params(w, h, 1, 2, frame=f) for f in (1, 2, 4)]
-    frames = _render_frames(ctx, wd, ps, 2)
+    frames = IO.render_frames(ctx, wd, ps, 2)
     hit = T.world_hitables(wd)
-    gbufs = [_gpu_gbuffer(ctx, p)[1:] for p in ps]
+    gbufs = [IO.gpu_gbuffer(ctx, p)[1:] for p in ps]
     for tp in (R.Temporal(8, 0.05, 0.3), R.Temporal(8, 0.05, -1.0)):  # the existing test's setting (its normal test leaves few whole footprints), and without it
         prev, mom, prev_time, cubic = None, None, 0.0, 0
         for p, film, (rec, obj) in zip(ps, frames, gbufs):
@@ -238,10 +201,9 @@ def test_render_sequence_with_catmull_rom_is_the_plain_loop_of_the_entries(tmp_p
     from rayn_amd import _abi, image
     from rayn_amd import film as F
     from rayn_amd import setup as S
-    from test_temporal_device import _read, _scene
     Kd = R.ChannelKind
     w, h, frames, samples = 48, 32, [2, 3, 5], 1
-    _, world, cam = _scene("s1", (w, h), moving=True)
+    _, world, cam = scenes.scene("s1", (w, h), moving=True)
     integ = R.PathTracingIntegrator(max_bounces=2, volume_marches=S.VOLUME_MARCHES_PER_SAMPLE)
     filt = R.BlackmanHarrisFilter(S.FILTER_RADIUS)
     kinds = [Kd.Color, Kd.Alpha, Kd.Background, Kd.WorldNormal]
@@ -251,7 +213,7 @@ def test_render_sequence_with_catmull_rom_is_the_plain_loop_of_the_entries(tmp_p
     def sequence(tp, name):
         film = R.Film(kinds, (w, h))
         film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, 24, 1.0 / 24.0, samples, [Kd.Color], str(tmp_path / name), "a", denoise=dn, temporal=tp)
-        return film, _read(tmp_path / name)
+        return film, IO.read_folder(tmp_path / name)
 
     film, got = sequence(R.Temporal(resample="catmull_rom"), "cubic")
     _, default = sequence(R.Temporal(), "default")
@@ -270,11 +232,7 @@ def test_render_sequence_with_catmull_rom_is_the_plain_loop_of_the_entries(tmp_p
     vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     t_abi, rp, prev_start = R.Temporal().to_abi(), _abi.TemporalResampleParams(1), None
     for i, frame in enumerate(frames):
-        start = f32(frame) * (f32(1.0) / f32(24))
-        p = R.frame_params(w, h, samples, 2, frame=frame, time_range=(float(start), float(f32(start + f32(1.0 / 24.0)))))
-        out = F.alloc_device_film(w, h, "cuda")
-        tabs = R.build_tables(4 * samples, 2, p.volume_marches, frame, w, h, filt)
-        ctx.render_device(p, [torch.from_numpy(t).cuda() for t in tabs], out)
+        p, out = IO.render_sequence_frame(ctx, w, h, frame, samples, 2, filt)
         ctx.gbuffer(p, g)
         first = i == 0
         rc = ctx._L.rayn_hip_temporal_accumulate_resample_device(
@@ -297,10 +255,9 @@ def test_render_sequence_with_catmull_rom_denoise_and_feedback(tmp_path):
     """The option works with the other combinations too: a plain Denoise, and VarianceDenoise with feedback > 0."""
     import rayn_amd as R
     from rayn_amd import setup as S
-    from test_temporal_device import _read, _scene
     Kd = R.ChannelKind
     w, h, frames = 48, 32, [1, 2, 3]
-    _, world, cam = _scene("s1", (w, h), moving=True)
+    _, world, cam = scenes.scene("s1", (w, h), moving=True)
     integ = R.PathTracingIntegrator(max_bounces=2, volume_marches=S.VOLUME_MARCHES_PER_SAMPLE)
     filt = R.BlackmanHarrisFilter(S.FILTER_RADIUS)
     film = R.Film([Kd.Color, Kd.Alpha, Kd.Background, Kd.WorldNormal], (w, h))
@@ -309,7 +266,7 @@ def test_render_sequence_with_catmull_rom_denoise_and_feedback(tmp_path):
                          ("f_lin", R.Temporal(feedback=0.5), R.VarianceDenoise(1, 4.0, 0.4, 0.3)),
                          ("f_cub", R.Temporal(feedback=0.5, resample="catmull_rom"), R.VarianceDenoise(1, 4.0, 0.4, 0.3))):
         film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, 24, 1.0 / 24.0, 1, [Kd.Color], str(tmp_path / name), "a", denoise=dn, temporal=tp)
-        out[name] = _read(tmp_path / name)
+        out[name] = IO.read_folder(tmp_path / name)
         assert sorted(out[name]) == [f"a_{f:04d}_color_temporal_denoised.png" for f in frames]
     for lin, cub in (("d_lin", "d_cub"), ("f_lin", "f_cub")):
         assert out[lin]["a_0001_color_temporal_denoised.png"] == out[cub]["a_0001_color_temporal_denoised.png"]  # no history yet
@@ -323,10 +280,9 @@ def test_bad_arguments_are_invalid_arg_with_a_text(ctx):
     import rayn_amd as R
     from rayn_amd import _abi
     from rayn_amd import film as F
-    from test_temporal_device import _scene
     L = ctx._L
     w, h, n = 40, 24, 40 * 24
-    wd, _, _ = _scene("s0", (w, h))
+    wd, _, _ = scenes.scene("s0", (w, h))
     ctx.upload_world(wd)
     p = R.frame_params(w, h, 1, 1)
     vp = lambda t: C.c_void_p(t.data_ptr())
@@ -375,33 +331,8 @@ def test_the_best_catmull_rom_point_reaches_the_measured_ratio():
     """temporal_np.DefaultsCase (shipped scene, 160x96, moving camera, 8 frames of 8 spp, against samples=256) at the best Catmull-Rom point
     of the CPU grid reaches the ratio the CPU tool printed, times 1.05 - the margin of the three sibling tests; the GPU film is the oracle's
     bits and the kernels are the restatement's, so the GPU figure is the CPU one."""
-    import torch
     import rayn_amd as R
-    from rayn_amd import film as F
-    from test_temporal_device import _render_frames
-    D = T.DefaultsCase
-    wd, ps, pref = D.scene()
-    tp, dn = R.Temporal(max_history=BEST_MAX_HISTORY, resample="catmull_rom"), R.VarianceDenoise(*RECOMMENDED)
-    c = R.Context(0)
-    try:
-        frames = _render_frames(c, wd, ps + [pref], D.BOUNCES)
-        ref = frames.pop()
-        want = np.clip(ref["color"].cpu().numpy().reshape(D.H, D.W, 3).astype(np.float64) + ref["background"].cpu().numpy().reshape(D.H, D.W, 3), 0.0, 1.0)
-        hist = [torch.empty(F.temporal_history_bytes(D.W, D.H), dtype=torch.uint8, device="cuda") for _ in range(2)]
-        mom = [torch.empty(F.temporal_moments_bytes(D.W, D.H), dtype=torch.uint8, device="cuda") for _ in range(2)]
-        g, acc = F.alloc_gbuffer(D.W, D.H, "cuda"), torch.empty(D.W * D.H, 3, dtype=torch.float32, device="cuda")
-        shown = torch.empty_like(acc)
-        for i, (p, film) in enumerate(zip(ps, frames)):
-            c.gbuffer(p, g)
-            c.temporal_accumulate(p, tp, film, g, None if i == 0 else hist[(i + 1) % 2], None if i == 0 else wd.camera,
-                                  0.0 if i == 0 else ps[i - 1].time_start, hist[i % 2], acc, None, None if i == 0 else mom[(i + 1) % 2], mom[i % 2])
-        last = frames[-1]
-        c.denoise_temporal_variance(D.W, D.H, dict(last, color=acc), g, hist[(len(ps) - 1) % 2], mom[(len(ps) - 1) % 2], shown, dn)
-        torch.cuda.synchronize()
-        bg = last["background"].cpu().numpy().reshape(D.H, D.W, 3)
-        raw, temporal, both = (D.mse(x.cpu().numpy(), bg, want) for x in (last["color"], acc, shown))
-    finally:
-        c.close()
+    raw, temporal, both = TC.defaults_case_errors(R.Temporal(max_history=BEST_MAX_HISTORY, resample="catmull_rom"), R.VarianceDenoise(*RECOMMENDED))
     print(f"MSE raw {raw:.4e}, catmull_rom alone {temporal / raw:.4f}x (CPU path: {MEASURED_ALONE}x), + variance denoise {both / raw:.4f}x (CPU path: {MEASURED_RATIO}x)")
     assert both / raw < MEASURED_RATIO * 1.05, (raw, temporal, both)
     assert temporal / raw < MEASURED_ALONE * 1.05, (raw, temporal, both)

@@ -4,15 +4,16 @@ no low camera and an orthographic, a pinhole and an animated one, confidence off
 upscale and accumulate kernels where the definition says they agree, guard floats and untouched inputs, every INVALID_ARG text with
 nothing written, and Film.render_sequence(upscale=, temporal=, supersample=) against a step-by-step loop of Context calls."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+import device_io as IO
+import temporal_cases as TC
 import temporal_np as T
 import temporal_upscale_np as TU
-from common import bits_equal
-from test_temporal_upscale import FACTORS, SIGMAS, SIZES, sequence
+from device_io import module_context as ctx  # noqa: F401
+from temporal_upscale_cases import FACTORS, SIGMAS, SIZES, sequence
 
 pytestmark = pytest.mark.gpu
 
@@ -21,17 +22,9 @@ KEYS = (("color", 3), ("alpha", 1), ("background", 3), ("normal", 3))
 
 
 @pytest.fixture(scope="module")
-def ctx():
-    """A context of this module's own: the tests switch its mul_add policy and upload their worlds."""
-    import rayn_amd
-    c = rayn_amd.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
 def moving_world():
-    """The MandelBox scene with a moving fractal (hitable 1) and a moving sphere: the accumulate's object motion is exercised."""
+    """The MandelBox scene with a moving fractal (hitable 1) and a moving sphere: the accumulate's object motion is exercised.  Not
+    scenes.scene's moving s1: the fractal's velocity is a tenth of that one's, and the camera is left as the scene has it."""
     import rayn_amd as R
     from rayn_amd import setup as S
     from rayn_amd.scene import Linear, TracedSDF
@@ -44,15 +37,6 @@ def moving_world():
     return wd
 
 
-def _dev(a, dtype=f32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype).reshape(-1).copy()).cuda()
-
-
-def _dev_g(rec, obj):
-    return {"records": _dev(rec), "object": _dev(np.ascontiguousarray(obj, np.uint32).view(np.int32), np.int32)}
-
-
 def _gpu(ctx, w, h, up, tp, sup, film, low_g, high_g, prev, prev_cam, prev_time, low_cam, ts, guard=64):
     """The entry through Context.temporal_upscale on host arrays: (planes, weight, (A, B, N, O)).  Checks the guard floats behind every
     output and the new history, and that no input and not the previous history changed."""
@@ -61,38 +45,36 @@ def _gpu(ctx, w, h, up, tp, sup, film, low_g, high_g, prev, prev_cam, prev_time,
     from rayn_amd import film as F
     s = up.factor
     N = w * h * s * s
-    d_film = {k: _dev(film[k]) for k, _ in KEYS if k in film}
-    gl, gh = _dev_g(*low_g), _dev_g(*high_g)
-    full = {k: torch.full((c * N + guard,), 7.0, dtype=torch.float32, device="cuda") for k, c in KEYS if k in film}
-    d_out = {k: v[: v.numel() - guard] for k, v in full.items()}
-    d_wt = torch.full((N + guard,), 7.0, dtype=torch.float32, device="cuda")
+    d_film = IO.upload_film(film, [k for k, _ in KEYS])
+    gl, gh = IO.upload_gbuffer(*low_g), IO.upload_gbuffer(*high_g)
+    full = {k: IO.guarded(c * N, torch.float32, 7.0, guard) for k, c in KEYS if k in film}
+    d_out = {k: v[1] for k, v in full.items()}
+    full_wt, d_wt = IO.guarded(N, torch.float32, 7.0, guard)
     nb = F.temporal_history_bytes(w * s, h * s)
-    d_prev = None if prev is None else torch.from_numpy(T.join_history(*prev).copy()).cuda()
-    keep = None if d_prev is None else d_prev.clone()
-    d_new = torch.full((nb + guard,), 0xA5, dtype=torch.uint8, device="cuda")
+    d_prev = None if prev is None else IO.upload_bytes(T.join_history(*prev))
+    keep = IO.snapshot([d_prev])
+    full_new, d_new = IO.guarded(nb, torch.uint8, 0xA5, guard)
     p = R.frame_params(w, h, 1, 1, time_range=(float(ts), float(ts) + 0.05))
-    ctx.temporal_upscale(p, up, tp, sup, d_film, gl, gh, d_prev, prev_cam, prev_time, d_new[:nb], d_out, low_cam, d_wt[:N])
+    ctx.temporal_upscale(p, up, tp, sup, d_film, gl, gh, d_prev, prev_cam, prev_time, d_new, d_out, low_cam, d_wt)
     torch.cuda.synchronize()
-    assert all(torch.all(v[v.numel() - guard:] == 7.0) for v in full.values()) and torch.all(d_wt[N:] == 7.0), "the kernel wrote past an output"
-    assert torch.all(d_new[nb:] == 0xA5), "the kernel wrote past the new history"
-    assert keep is None or torch.equal(keep, d_prev), "the previous history was modified"
+    for k, c in KEYS:
+        if k in film:
+            IO.assert_guards(full[k][0], c * N, 7.0, k)
+    IO.assert_guards(full_wt, N, 7.0, "weight")
+    IO.assert_guards(full_new, nb, 0xA5, "new history")
+    IO.assert_unchanged([d_prev], keep, "the previous history")
     for k in d_film:
-        assert np.array_equal(d_film[k].cpu().numpy().view(np.uint32), np.ascontiguousarray(film[k], f32).reshape(-1).view(np.uint32)), k
-    for g, (rec, obj) in ((gl, low_g), (gh, high_g)):
-        assert np.array_equal(g["records"].cpu().numpy().view(np.uint32), np.ascontiguousarray(rec, f32).reshape(-1).view(np.uint32))
-        assert np.array_equal(g["object"].cpu().numpy().view(np.uint32), np.ascontiguousarray(obj, np.uint32).reshape(-1))
+        IO.assert_is_host(d_film[k], film[k], k)
+    IO.assert_gbuffer_is_host(gl, *low_g, "low G-buffer")
+    IO.assert_gbuffer_is_host(gh, *high_g, "high G-buffer")
     out = {k: d_out[k].cpu().numpy().reshape((N, c) if c == 3 else (N,)) for k, c in KEYS if k in film}
-    return out, d_wt[:N].cpu().numpy(), T.split_history(d_new[:nb].cpu().numpy(), N)
+    return out, d_wt.cpu().numpy(), T.split_history(d_new.cpu().numpy(), N)
 
 
 def _same(got, want, what):
-    assert set(got[0]) == set(want[0]), what
-    for k in want[0]:
-        assert bits_equal(got[0][k], want[0][k]), (what, k, int((got[0][k].view(np.uint32) != want[0][k].view(np.uint32)).sum()))
-    assert bits_equal(got[1], want[1]), (what, "weight")
-    for name, a, b in zip("ABN", got[2][:3], want[2][:3]):
-        assert bits_equal(a, b), (what, "history", name)
-    assert np.array_equal(got[2][3], want[2][3]), (what, "history object")
+    IO.assert_planes_equal(got[0], want[0], what)
+    IO.assert_bits_equal(got[1], want[1], (what, "weight"))
+    TC.assert_history_equal(got[2], want[2], (what, "history"))
 
 
 def _low_camera(which, w, h, s, shift, ts):
@@ -175,12 +157,12 @@ def test_without_low_camera_and_confidence_it_is_the_products_two_kernels(ctx, m
         for film, low_g, high_g, cam, ts in sequence(w, h, s, 500 + ci, adversarial):
             got = _gpu(ctx, w, h, up, tp, sup, film, low_g, high_g, prev, prev_cam, prev_time, None, ts)
             p = R.frame_params(w, h, 1, 1, time_range=(float(ts), float(ts) + 0.05))
-            d_film = {k: _dev(film[k]) for k, _ in KEYS}
-            gl, gh = _dev_g(*low_g), _dev_g(*high_g)
+            d_film = IO.upload_film(film, [k for k, _ in KEYS])
+            gl, gh = IO.upload_gbuffer(*low_g), IO.upload_gbuffer(*high_g)
             d_up = F.alloc_device_film(W, H, "cuda")
             d_wt = torch.empty(N, dtype=torch.float32, device="cuda")
             ctx.upscale(p, up, d_film, gl, gh, d_up, d_wt)
-            d_prev = None if prev is None else torch.from_numpy(T.join_history(*prev).copy()).cuda()
+            d_prev = None if prev is None else IO.upload_bytes(T.join_history(*prev))
             d_new = torch.empty(F.temporal_history_bytes(W, H), dtype=torch.uint8, device="cuda")
             d_acc = torch.empty(N * 3, dtype=torch.float32, device="cuda")
             ctx.temporal_accumulate(F._scaled_params(p, s), tp, d_up, gh, d_prev, prev_cam, prev_time, d_new, d_acc)
@@ -193,12 +175,7 @@ def test_without_low_camera_and_confidence_it_is_the_products_two_kernels(ctx, m
 
 
 def _gbuffer_host(ctx, p):
-    import torch
-    from rayn_amd import film as F
-    g = F.alloc_gbuffer(p.width, p.height, "cuda")
-    ctx.gbuffer(p, g)
-    torch.cuda.synchronize()
-    return g["records"].cpu().numpy().reshape(-1, 4), g["object"].cpu().numpy().view(np.uint32)
+    return IO.gpu_gbuffer(ctx, p)[1:]
 
 
 @pytest.mark.parametrize("scene,fma", [("s0", 0), ("ship", 1), ("s0", 1), ("ship", 0)])
@@ -341,10 +318,6 @@ def _kinds():
     return [K.Color, K.Alpha, K.Background, K.WorldNormal]
 
 
-def _read(folder):
-    return {f: open(os.path.join(folder, f), "rb").read() for f in sorted(os.listdir(folder))}
-
-
 def test_render_sequence_supersample_is_the_step_by_step_loop(tmp_path):
     """Three frames at 24 x 16, factor 2, under setup_s3 (camera origin and fractal move): the files are byte for byte those of a loop of
     upload_world(jittered), render_device, gbuffer, upload_world, gbuffer, temporal_upscale and save_to_pixels; denoise=Denoise() and
@@ -371,7 +344,7 @@ def test_render_sequence_supersample_is_the_step_by_step_loop(tmp_path):
     film.render_sequence(world, cam, integ, filt, (16, 16), frames, rate, shutter, 1, [K.Color], str(tmp_path / "seq2"), "anim", upscale=up, temporal=tp,
                          supersample=sup, denoise=dn, display=disp)
     assert [st["frame"] for st in stats] == frames and film.res == (w, h) and film.channels["color"].numel() == 3 * w * h
-    got, got2 = _read(tmp_path / "seq"), _read(tmp_path / "seq2")
+    got, got2 = IO.read_folder(tmp_path / "seq"), IO.read_folder(tmp_path / "seq2")
     assert sorted(got) == sorted(f"anim_{f:04d}_{sfx}_x2.png" for f in frames for sfx in ("color_temporal", "alpha", "background", "normal"))
     assert sorted(got2) == sorted(f"anim_{f:04d}_color_temporal_denoised_display_x2.png" for f in frames)
     # the loop
@@ -429,14 +402,13 @@ def test_render_sequence_without_jitter_and_confidence_is_the_composition(tmp_pa
                          supersample=R.Supersample(jitter=False, confidence=False))
     film.render_sequence(world, cam, integ, filt, (16, 16), frames, rate, shutter, 1, [K.Color], str(tmp_path / "jit"), "anim", upscale=up, temporal=tp,
                          supersample=R.Supersample(jitter=True, confidence=True))
-    got, jit = _read(tmp_path / "seq"), _read(tmp_path / "jit")
+    got, jit = IO.read_folder(tmp_path / "seq"), IO.read_folder(tmp_path / "jit")
     plain = R.Film(_kinds(), (w, h))
     desc = world.to_desc(cam)
     hist = [torch.empty(F.temporal_history_bytes(W, H), dtype=torch.uint8, device="cuda") for _ in range(2)]
     prev_start = None
     for i, frame in enumerate(frames):
-        start = f32(frame) * (f32(1.0) / f32(rate))
-        plain.render_frame_into(world, cam, integ, filt, (16, 16), frame, (float(start), float(f32(start + f32(shutter)))), 1)
+        plain.render_frame_into(world, cam, integ, filt, (16, 16), frame, IO.shutter_range(frame, rate, shutter), 1)
         hi = plain.upscaled(up)
         g = F.alloc_gbuffer(W, H, "cuda")
         hi.ctx.gbuffer(hi._last_params, g)

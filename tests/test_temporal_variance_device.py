@@ -11,82 +11,25 @@ import numpy as np
 import pytest
 
 import denoise_variance_np as VN
+import device_io as IO
+import scenes
+import temporal_cases as TC
 import temporal_np as T
 import temporal_variance_np as TV
 from common import bits_equal
+from device_io import module_context as ctx, same_bits  # noqa: F401
+from temporal_cases import GUARD, SPECIAL
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 W0, H0 = 37, 23  # no multiple of 16: edge blocks, and 7x7 windows that cross block and image borders
-GUARD = 64
-SPECIAL = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 3.0e38, -3.0e38, 1e-45, 1e30, -1e30], f32)
 SIGMAS = list(itertools.product((0.0, 4.0), (0.0, 0.4), (0.0, 0.3)))  # every on/off combination of luminance / normal / alpha
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    """A context of this module's own: one test switches its mul_add policy."""
-    import rayn_amd
-    c = rayn_amd.Context(0)
-    yield c
-    c.close()
-
-
-def _moving_scene(w, h):
-    """temporal_np.DefaultsCase's scene at another size: the shipped scene under a camera whose origin moves"""
-    import rayn_amd as R
-    from rayn_amd import setup as S
-    from rayn_amd.scene import Linear
-    cam, world = S.setup((w, h))
-    c = world.cameras.get(cam)
-    c.origin = Linear(c.origin, R.vec3(0.9, -0.3, 0.15))
-    return world, cam
-
-
-def _dev(a, dtype=f32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype).reshape(-1).copy()).cuda()
-
-
-def _dev_bytes(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).cuda()
-
-
-def _accumulate(ctx, p, temporal, color, normal, rec, obj, prev, prev_mom, prev_cam, prev_time, moments=True):
-    """Either accumulate entry through Context.temporal_accumulate on host arrays: (out (n, 3), (A, B, N, O), moments (n, 2) or None);
-    checks the guard bytes behind every output and that the inputs were left alone."""
-    import torch
-    from rayn_amd import film as F
-    n = p.width * p.height
-    film = {"color": _dev(color), "normal": _dev(normal)}
-    g = {"records": _dev(rec), "object": _dev(np.asarray(obj, np.uint32).view(np.int32), np.int32)}
-    d_prev = None if prev is None else _dev_bytes(T.join_history(*prev))
-    d_pm = None if prev_mom is None or not moments else _dev_bytes(np.asarray(prev_mom, f32))
-    keep = [None if t is None else t.clone() for t in (d_prev, d_pm)]
-    hb, mb = F.temporal_history_bytes(p.width, p.height), F.temporal_moments_bytes(p.width, p.height)
-    d_new = torch.full((hb + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    d_nm = torch.full((mb + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    d_out = torch.full((3 * n + GUARD,), 7.0, dtype=torch.float32, device="cuda")
-    ctx.temporal_accumulate(p, temporal, film, g, d_prev, prev_cam, prev_time, d_new[:hb], d_out[: 3 * n], None, d_pm, d_nm[:mb] if moments else None)
-    torch.cuda.synchronize()
-    assert torch.all(d_new[hb:] == 0xA5) and torch.all(d_out[3 * n:] == 7.0) and torch.all(d_nm[mb if moments else 0:] == 0xA5), "a kernel wrote past an output"
-    for t, k in zip((d_prev, d_pm), keep):
-        assert k is None or torch.equal(t.view(torch.uint8), k.view(torch.uint8)), "a previous buffer was modified"
-    assert np.array_equal(film["color"].cpu().numpy().view(np.uint32), np.ascontiguousarray(color, f32).reshape(-1).view(np.uint32))
-    mom = d_nm[:mb].cpu().numpy().view(f32).reshape(n, 2) if moments else None
-    return d_out[: 3 * n].cpu().numpy().reshape(n, 3), T.split_history(d_new[:hb].cpu().numpy(), n), mom
-
-
-def _same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
 def _adversarial_accumulate_inputs(w, h, seed, cam_kind):
     """test_temporal_device's adversarial frame + history, and previous moments with the same special values scattered over them"""
-    from test_temporal_device import _random_inputs
-    cur, prev_cam, color, normal, rec, obj, prev = _random_inputs(w, h, seed, cam_kind, True)
+    cur, prev_cam, color, normal, rec, obj, prev = TC.random_inputs(w, h, seed, cam_kind, True)
     rng = np.random.default_rng(seed + 500)
     pm = np.stack([rng.gamma(0.6, 0.5, w * h), rng.gamma(0.6, 0.8, w * h)], axis=1).astype(f32)
     flat = pm.reshape(-1)
@@ -101,21 +44,20 @@ def _adversarial_accumulate_inputs(w, h, seed, cam_kind):
 @pytest.mark.parametrize("cam_kind", [0, 2])
 def test_moments_entry_writes_the_colour_and_history_of_the_plain_entry(ctx, cam_kind):
     import rayn_amd as R
-    from test_temporal_device import _scene
-    wd, _, _ = _scene("s1", (40, 24), moving=True)
+    wd, _, _ = scenes.scene("s1", (40, 24), moving=True)
     ctx.upload_world(wd)
     for si, (w, h) in enumerate([(W0, H0), (48, 32), (1, 1)]):
         prev_cam, color, normal, rec, obj, prev, pm = _adversarial_accumulate_inputs(w, h, 20 + si, cam_kind)
         p = R.frame_params(w, h, 1, 1, time_range=(0.75, 0.8))
         for tp in (R.Temporal(4, 0.05, -1.0), R.Temporal(1, 0.05, 0.9), R.Temporal(65536, 1e30, 0.5)):
-            out_p, hist_p, _ = _accumulate(ctx, p, tp, color, normal, rec, obj, prev, pm, prev_cam, 0.25, moments=False)
-            out_m, hist_m, mom = _accumulate(ctx, p, tp, color, normal, rec, obj, prev, pm, prev_cam, 0.25)
-            assert _same_bits(out_p, out_m), (w, h, tp, "colour")
+            out_p, hist_p, _ = TC.gpu_accumulate(ctx, p, tp, color, normal, rec, obj, prev, pm, prev_cam, 0.25, moments=False)
+            out_m, hist_m, mom = TC.gpu_accumulate(ctx, p, tp, color, normal, rec, obj, prev, pm, prev_cam, 0.25)
+            assert same_bits(out_p, out_m), (w, h, tp, "colour")
             for name, a, b in zip("ABNO", hist_p, hist_m):
-                assert _same_bits(a, b), (w, h, tp, name)
-        out_p, hist_p, _ = _accumulate(ctx, p, tp, color, normal, rec, obj, None, None, None, 0.0, moments=False)
-        out_m, hist_m, mom = _accumulate(ctx, p, tp, color, normal, rec, obj, None, None, None, 0.0)
-        assert _same_bits(out_p, out_m) and all(_same_bits(a, b) for a, b in zip(hist_p, hist_m))
+                assert same_bits(a, b), (w, h, tp, name)
+        out_p, hist_p, _ = TC.gpu_accumulate(ctx, p, tp, color, normal, rec, obj, None, None, None, 0.0, moments=False)
+        out_m, hist_m, mom = TC.gpu_accumulate(ctx, p, tp, color, normal, rec, obj, None, None, None, 0.0)
+        assert same_bits(out_p, out_m) and all(same_bits(a, b) for a, b in zip(hist_p, hist_m))
 
 
 # ---- 2. the kernels against the restatement ------------------------------------------------------------------------------------------------
@@ -125,8 +67,7 @@ def test_moments_match_the_restatement_on_adversarial_inputs(ctx, cam_kind):
     """NaN / inf / 3e38 colours, histories and moments, misses, taps rejected by depth, object and normal, history lengths 0 .. 8 with a
     fractional one, cameras that have moved so that taps straddle every border; max_history 1, 4 and a large one."""
     import rayn_amd as R
-    from test_temporal_device import _scene
-    wd, _, _ = _scene("s1", (40, 24), moving=True)
+    wd, _, _ = scenes.scene("s1", (40, 24), moving=True)
     ctx.upload_world(wd)
     hit = T.world_hitables(wd)
     w, h = W0, H0
@@ -134,42 +75,16 @@ def test_moments_match_the_restatement_on_adversarial_inputs(ctx, cam_kind):
     p = R.frame_params(w, h, 1, 1, time_range=(0.75, 0.8))
     for tp in (R.Temporal(4, 0.05, -1.0), R.Temporal(1, 0.25, 0.9), R.Temporal(8, 1e30, 0.5), R.Temporal(65536, 0.25, -1.0)):
         want = TV.accumulate(w, h, color, normal, rec, obj, prev, pm, prev_cam, 0.25, 0.75, hit, tp.max_history, tp.depth_tolerance, tp.normal_min)
-        got = _accumulate(ctx, p, tp, color, normal, rec, obj, prev, pm, prev_cam, 0.25)
+        got = TC.gpu_accumulate(ctx, p, tp, color, normal, rec, obj, prev, pm, prev_cam, 0.25)
         assert bits_equal(got[0], want[0]), (tp, "colour")
         assert all(bits_equal(a, b) for a, b in zip(got[1][:3], want[1][:3])) and np.array_equal(got[1][3], want[1][3]), (tp, "history")
         assert bits_equal(got[2], want[2]), (tp, "moments", int((got[2].view(np.uint32) != want[2].view(np.uint32)).sum()))
         n1 = want[1][0][:, 3]
         assert (n1 > 1).any() or tp.max_history == 1
     want = TV.accumulate(w, h, color, normal, rec, obj, None, None, None, 0.0, 0.75, hit, 4, 0.05, -1.0)
-    got = _accumulate(ctx, p, R.Temporal(), color, normal, rec, obj, None, None, None, 0.0)
+    got = TC.gpu_accumulate(ctx, p, R.Temporal(), color, normal, rec, obj, None, None, None, 0.0)
     assert bits_equal(got[0], want[0]) and bits_equal(got[2], want[2])
     assert np.all(got[2][~np.isfinite(color).all(axis=1)] == 0.0)
-
-
-def _pack_inputs(w, h, seed):
-    """Synthetic inputs of the denoise entry: a patchwork of objects with misses, history lengths 0, 1, 3, 3.5, 4, 8 and NaN side by side,
-    special values over colour, guides and moments."""
-    rng = np.random.default_rng(seed)
-    n = w * h
-    color = rng.gamma(0.6, 0.5, (n, 3)).astype(f32)
-    normal = rng.normal(size=(n, 3)).astype(f32)
-    alpha = rng.choice(np.array([0.0, 0.25, 1.0, 1.0, 1.0], f32), n)
-    ys, xs = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
-    patch = rng.choice(np.array([0, 1, 1, 2, 0xFFFFFFFF], np.uint32), (h // 4 + 1, w // 5 + 1))
-    obj = patch[ys // 4, xs // 5].reshape(-1).copy()
-    obj[rng.choice(n, n // 20, replace=False)] = 3  # single pixels of another object inside the patches
-    n1 = rng.choice(np.array([0.0, 1.0, 1.0, 3.0, 3.5, 4.0, 8.0], f32), n)
-    if n >= 4:
-        n1[rng.choice(n, 4, replace=False)] = (np.nan, np.inf, -1.0, 0.5)
-    m1 = rng.gamma(0.6, 0.5, n).astype(f32)
-    mom = np.stack([m1, (m1 * m1 + rng.normal(0.0, 0.05, n)).astype(f32)], axis=1).astype(f32)  # m2 - m1^2 of either sign
-    for arr in (color, normal, alpha, mom):
-        flat = arr.reshape(-1)
-        idx = rng.choice(flat.size, min(flat.size, 3 * SPECIAL.size), replace=False)
-        flat[idx] = np.resize(SPECIAL, idx.size)
-    A = np.concatenate([rng.random((n, 3)).astype(f32), n1[:, None]], axis=1).astype(f32)  # the entry reads only n' of the history
-    hist = T.join_history(A, rng.random((n, 4)).astype(f32), rng.random((n, 4)).astype(f32), obj)
-    return {"color": color, "normal": normal, "alpha": alpha, "obj": obj, "n1": n1, "mom": mom, "hist": hist}
 
 
 def _denoise(ctx, w, h, inp, L, sigmas, variance=True):
@@ -177,27 +92,25 @@ def _denoise(ctx, w, h, inp, L, sigmas, variance=True):
     import torch
     from rayn_amd import VarianceDenoise
     n = w * h
-    d = {"color": _dev(inp["color"])}
-    if sigmas[1]:
-        d["normal"] = _dev(inp["normal"])
-    if sigmas[2]:
-        d["alpha"] = _dev(inp["alpha"])
-    g = {"object": _dev(inp["obj"].view(np.int32), np.int32)}
-    d_hist, d_mom = _dev_bytes(inp["hist"]), _dev_bytes(inp["mom"])
-    keep_h, keep_m = d_hist.clone(), d_mom.clone()
-    out = torch.full((3 * n + GUARD,), 7.0, dtype=torch.float32, device="cuda")
-    var = torch.full((n + GUARD,), 7.0, dtype=torch.float32, device="cuda") if variance else None
-    ctx.denoise_temporal_variance(w, h, d, g, d_hist, d_mom, out[: 3 * n], VarianceDenoise(L, *sigmas), None if var is None else var[:n])
+    d = IO.upload_film(inp, ("color",) + (("normal",) if sigmas[1] else ()) + (("alpha",) if sigmas[2] else ()))
+    g = {"object": IO.upload(inp["obj"].view(np.int32), np.int32)}
+    d_hist, d_mom = IO.upload_bytes(inp["hist"]), IO.upload_bytes(inp["mom"])
+    ins = dict(d, object=g["object"], hist=d_hist, mom=d_mom)
+    keep = IO.snapshot(ins)
+    full_out, out = IO.guarded(3 * n, torch.float32, 7.0, GUARD)
+    full_var, var = IO.guarded(n, torch.float32, 7.0, GUARD)
+    ctx.denoise_temporal_variance(w, h, d, g, d_hist, d_mom, out, VarianceDenoise(L, *sigmas), var if variance else None)
     torch.cuda.synchronize()
-    assert torch.all(out[3 * n:] == 7.0) and (var is None or torch.all(var[n:] == 7.0)), "a kernel wrote past an output"
-    assert torch.equal(keep_h, d_hist) and torch.equal(keep_m, d_mom), "an input was modified"
-    return out[: 3 * n].cpu().numpy().reshape(n, 3), None if var is None else var[:n].cpu().numpy()
+    IO.assert_guards(full_out, 3 * n, 7.0, "colour")
+    IO.assert_guards(full_var, n if variance else 0, 7.0, "variance")
+    IO.assert_unchanged(ins, keep, "an input")
+    return out.cpu().numpy().reshape(n, 3), var.cpu().numpy() if variance else None
 
 
 def test_variance_estimate_and_passes_match_the_restatement(ctx, oracle):
     """All eight term combinations at 1 and 3 passes, with and without the variance output, at 37x23 and at 1x1."""
     w, h = W0, H0
-    inp = _pack_inputs(w, h, 7)
+    inp = TC.pack_inputs(w, h, 7)
     v0, k = TV.initial_variance(w, h, inp["color"], inp["obj"], inp["n1"], inp["mom"])
     n1, guided = inp["n1"], ~np.isnan(v0)
     # the case has substance: both arms, windows cut by objects and borders, pixels that are not guided for each reason
@@ -209,8 +122,8 @@ def test_variance_estimate_and_passes_match_the_restatement(ctx, oracle):
         assert bits_equal(got_c, want_c), (L, sigmas, "colour", int((got_c.view(np.uint32) != want_c.view(np.uint32)).sum()))
         assert bits_equal(got_v, want_v) and np.array_equal(np.isnan(got_v), np.isnan(want_v)), (L, sigmas, "variance")
         got_c2, none = _denoise(ctx, w, h, inp, L, sigmas, variance=False)
-        assert none is None and _same_bits(got_c2, got_c), (L, sigmas, "without the variance output")
-    one = _pack_inputs(1, 1, 3)
+        assert none is None and same_bits(got_c2, got_c), (L, sigmas, "without the variance output")
+    one = TC.pack_inputs(1, 1, 3)
     one["color"][:], one["normal"][:], one["alpha"][:], one["obj"][:], one["mom"][:] = (0.5, 0.25, 0.75), (0.0, 0.6, 0.8), 1.0, 1, (0.5, 0.3)
     for n_hist in (1.0, 4.0):
         one["n1"][:] = n_hist
@@ -221,10 +134,6 @@ def test_variance_estimate_and_passes_match_the_restatement(ctx, oracle):
 
 
 # ---- 3. a rendered sequence ------------------------------------------------------------------------------------------------------------------
-
-def _read(folder):
-    return {f: open(os.path.join(folder, f), "rb").read() for f in sorted(os.listdir(folder))}
-
 
 @pytest.mark.parametrize("fma", [0, 1])
 def test_render_sequence_is_the_plain_loop_of_the_entries_and_the_restatement(tmp_path, oracle, fma):
@@ -239,7 +148,7 @@ def test_render_sequence_is_the_plain_loop_of_the_entries_and_the_restatement(tm
     from rayn_amd import setup as S
     K = R.ChannelKind
     w, h, frames, samples, bounces = 48, 32, [1, 2, 3, 4, 5], 1, 2
-    world, cam = _moving_scene(w, h)
+    world, cam = scenes.moving_scene(w, h)
     integ = R.PathTracingIntegrator(max_bounces=bounces, volume_marches=S.VOLUME_MARCHES_PER_SAMPLE)
     filt = R.BlackmanHarrisFilter(S.FILTER_RADIUS)
     tp, dn = R.Temporal(), R.VarianceDenoise(2, 4.0, 0.4, 0.3)
@@ -248,7 +157,7 @@ def test_render_sequence_is_the_plain_loop_of_the_entries_and_the_restatement(tm
     ctx.set_fma_policy(fma)
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, 24, 1.0 / 24.0, samples, [K.Color, K.Alpha], str(tmp_path / "seq"), "a",
                          denoise=dn, temporal=tp)
-    got = _read(tmp_path / "seq")
+    got = IO.read_folder(tmp_path / "seq")
     assert sorted(got) == sorted(f"a_{f:04d}_{s}.png" for f in frames for s in ("color_temporal_denoised", "alpha"))
     desc = world.to_desc(cam)
     ctx.upload_world(desc)
@@ -261,11 +170,7 @@ def test_render_sequence_is_the_plain_loop_of_the_entries_and_the_restatement(tm
     img = torch.empty(n * 3, dtype=torch.uint8, device="cuda")
     prev_start, prev_host, arms = None, (None, None), set()
     for i, frame in enumerate(frames):
-        start = f32(frame) * (f32(1.0) / f32(24))
-        p = R.frame_params(w, h, samples, bounces, frame=frame, time_range=(float(start), float(f32(start + f32(1.0 / 24.0)))))
-        out = F.alloc_device_film(w, h, "cuda")
-        tabs = R.build_tables(4 * samples, bounces, p.volume_marches, frame, w, h, filt)
-        ctx.render_device(p, [torch.from_numpy(t).cuda() for t in tabs], out)
+        p, out = IO.render_sequence_frame(ctx, w, h, frame, samples, bounces, filt)
         ctx.gbuffer(p, g)
         first = i == 0
         ctx.temporal_accumulate(p, tp, out, g, None if first else hist[(i + 1) % 2], None if first else desc.camera, 0.0 if first else prev_start,
@@ -292,7 +197,7 @@ def test_render_sequence_is_the_plain_loop_of_the_entries_and_the_restatement(tm
     if fma == 0:
         plain = R.Film([K.Color, K.Alpha, K.Background, K.WorldNormal], (w, h))
         plain.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames[:2], 24, 1.0 / 24.0, samples, [K.Color, K.Alpha], str(tmp_path / "plain"), "a", temporal=tp)
-        base = _read(tmp_path / "plain")
+        base = IO.read_folder(tmp_path / "plain")
         assert all(got[f"a_{f:04d}_alpha.png"] == base[f"a_{f:04d}_alpha.png"] for f in frames[:2])
         assert got["a_0002_color_temporal_denoised.png"] != base["a_0002_color_temporal.png"]
         no_alpha = R.Film([K.Color, K.Background, K.WorldNormal], (w, h))
@@ -303,7 +208,7 @@ def test_render_sequence_is_the_plain_loop_of_the_entries_and_the_restatement(tm
         assert not os.path.exists(tmp_path / "x")
         no_alpha.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames[:1], 24, 1.0 / 24.0, samples, [K.Color], str(tmp_path / "y"), "a",
                                  denoise=R.VarianceDenoise(1, 4.0, 0.4, 0.0), temporal=tp)
-        assert sorted(_read(tmp_path / "y")) == ["a_0001_color_temporal_denoised.png"]
+        assert sorted(IO.read_folder(tmp_path / "y")) == ["a_0001_color_temporal_denoised.png"]
 
 
 # ---- 4. input hygiene ------------------------------------------------------------------------------------------------------------------------
@@ -312,10 +217,9 @@ def test_bad_arguments_are_invalid_arg_with_a_text_and_leave_the_outputs_untouch
     import torch
     import rayn_amd as R
     from rayn_amd import film as F
-    from test_temporal_device import _scene
     L = ctx._L
     w, h, n = 40, 24, 40 * 24
-    wd, _, _ = _scene("s0", (w, h))
+    wd, _, _ = scenes.scene("s0", (w, h))
     ctx.upload_world(wd)
     p = R.frame_params(w, h, 1, 1)
     zero, huge = R.frame_params(0, h, 1, 1), R.frame_params(65536, 32768, 1, 1)
@@ -436,33 +340,8 @@ def test_the_recommended_setting_lowers_the_error_of_the_accumulated_sequence():
     """temporal_np.DefaultsCase (shipped scene, 160x96, moving camera, 8 frames of 8 spp, against samples=256): Temporal() followed by
     VarianceDenoise(1, 4.0, 0.4, 0.3) reaches the ratio measured on the CPU path (times 1.05, the project's margin for this kind of test:
     the GPU path is bit-identical to it), which is below Temporal() alone."""
-    import torch
     import rayn_amd as R
-    from rayn_amd import film as F
-    from test_temporal_device import _render_frames
-    D = T.DefaultsCase
-    wd, ps, pref = D.scene()
-    dn = R.VarianceDenoise(*RECOMMENDED)
-    c = R.Context(0)
-    try:
-        frames = _render_frames(c, wd, ps + [pref], D.BOUNCES)
-        ref = frames.pop()
-        want = np.clip(ref["color"].cpu().numpy().reshape(D.H, D.W, 3).astype(np.float64) + ref["background"].cpu().numpy().reshape(D.H, D.W, 3), 0.0, 1.0)
-        hist = [torch.empty(F.temporal_history_bytes(D.W, D.H), dtype=torch.uint8, device="cuda") for _ in range(2)]
-        mom = [torch.empty(F.temporal_moments_bytes(D.W, D.H), dtype=torch.uint8, device="cuda") for _ in range(2)]
-        g, acc = F.alloc_gbuffer(D.W, D.H, "cuda"), torch.empty(D.W * D.H, 3, dtype=torch.float32, device="cuda")
-        shown = torch.empty_like(acc)
-        for i, (p, film) in enumerate(zip(ps, frames)):
-            c.gbuffer(p, g)
-            c.temporal_accumulate(p, R.Temporal(), film, g, None if i == 0 else hist[(i + 1) % 2], None if i == 0 else wd.camera,
-                                  0.0 if i == 0 else ps[i - 1].time_start, hist[i % 2], acc, None, None if i == 0 else mom[(i + 1) % 2], mom[i % 2])
-        last = frames[-1]
-        c.denoise_temporal_variance(D.W, D.H, dict(last, color=acc), g, hist[(len(ps) - 1) % 2], mom[(len(ps) - 1) % 2], shown, dn)
-        torch.cuda.synchronize()
-        bg = last["background"].cpu().numpy().reshape(D.H, D.W, 3)
-        raw, temporal, both = (D.mse(x.cpu().numpy(), bg, want) for x in (last["color"], acc, shown))
-    finally:
-        c.close()
+    raw, temporal, both = TC.defaults_case_errors(R.Temporal(), R.VarianceDenoise(*RECOMMENDED))
     print(f"MSE raw {raw:.4e}, temporal {temporal / raw:.4f}x (CPU path: {MEASURED_TEMPORAL}x), temporal + variance denoise {both / raw:.4f}x (CPU path: {MEASURED_RATIO}x)")
     assert both / raw < MEASURED_RATIO * 1.05, (raw, temporal, both)
     assert both < temporal

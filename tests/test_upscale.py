@@ -6,6 +6,7 @@ resolution but the low film's hit threshold.  tests/test_upscale_device.py compa
 import numpy as np
 import pytest
 
+import scenes
 import temporal_np as T
 import upscale_np as U
 
@@ -215,18 +216,8 @@ def test_the_float64_reading_agrees():
 
 
 def _scene(name, res, camera="pinhole"):
-    """The world description of a test scene at a resolution, with the camera variants tests/test_temporal_device.py builds."""
-    import rayn_amd as R
-    from rayn_amd import setup as S
-    from rayn_amd.scene import OrthographicCamera, ThinLensCamera
-    cam, world = S.SCENES[name](res)
-    c = world.cameras.get(cam)
-    rs = (float(res[0]), float(res[1]))
-    if camera == "thin":
-        world.cameras[cam] = ThinLensCamera(rs, 55.0, 0.08, c.origin, c.at, c.up, R.vec3(0.2, 0.1, 0.0))
-    elif camera == "ortho":
-        world.cameras[cam] = OrthographicCamera(rs, 3.5, c.origin, c.at, c.up)
-    return world.to_desc(cam)
+    """The world description of a test scene at a resolution, with the camera variants of scenes.scene"""
+    return scenes.scene(name, res, camera)[0]
 
 
 @pytest.mark.parametrize("scene,camera,res,s", [("s1", "pinhole", (12, 8), 2), ("s2", "pinhole", (10, 6), 3), ("s1", "thin", (9, 7), 2),

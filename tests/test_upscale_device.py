@@ -8,9 +8,12 @@ import os
 import numpy as np
 import pytest
 
+import device_io as IO
+import scenes
 import temporal_np as T
 import upscale_np as U
 from common import bits_equal
+from device_io import module_context as ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,21 +24,6 @@ SIGMAS = [(0.02, 0.05), (0.0, 0.05), (0.02, 0.0), (0.0, 0.0)]
 KEYS = (("color", 3), ("alpha", 1), ("background", 3), ("normal", 3))
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    """A context of this module's own: the tests switch its mul_add policy."""
-    import rayn_amd
-    c = rayn_amd.Context(0)
-    yield c
-    c.close()
-
-
-def _dev_g(rec, obj):
-    import torch
-    return {"records": torch.from_numpy(np.ascontiguousarray(rec, f32).reshape(-1)).cuda(),
-            "object": torch.from_numpy(np.ascontiguousarray(obj, np.uint32).view(np.int32).reshape(-1)).cuda()}
-
-
 def _gpu_upscale(ctx, w, h, up, film, low_g, high_g, guard=64):
     """The entry through Context.upscale on host arrays: (planes dict, weight); checks the guard floats behind every output and that no
     input changed."""
@@ -43,29 +31,29 @@ def _gpu_upscale(ctx, w, h, up, film, low_g, high_g, guard=64):
     import rayn_amd as R
     s = up.factor
     N = w * h * s * s
-    d_film = {k: torch.from_numpy(np.ascontiguousarray(film[k], f32).reshape(-1)).cuda() for k, _ in KEYS if k in film}
-    gl, gh = _dev_g(*low_g), _dev_g(*high_g)
-    full = {k: torch.full((c * N + guard,), 7.0, dtype=torch.float32, device="cuda") for k, c in KEYS if k in film}
-    d_out = {k: v[: v.numel() - guard] for k, v in full.items()}
-    d_wt = torch.full((N + guard,), 7.0, dtype=torch.float32, device="cuda")
-    ctx.upscale(R.frame_params(w, h, 1, 1), up, d_film, gl, gh, d_out, d_wt[:N])
+    d_film = IO.upload_film(film, [k for k, _ in KEYS])
+    gl, gh = IO.upload_gbuffer(*low_g), IO.upload_gbuffer(*high_g)
+    full = {k: IO.guarded(c * N, torch.float32, 7.0, guard) for k, c in KEYS if k in film}
+    d_out = {k: v[1] for k, v in full.items()}
+    full_wt, d_wt = IO.guarded(N, torch.float32, 7.0, guard)
+    ctx.upscale(R.frame_params(w, h, 1, 1), up, d_film, gl, gh, d_out, d_wt)
     torch.cuda.synchronize()
-    assert all(torch.all(v[v.numel() - guard:] == 7.0) for v in full.values()) and torch.all(d_wt[N:] == 7.0), "the kernel wrote past an output"
+    for k, c in KEYS:
+        if k in film:
+            IO.assert_guards(full[k][0], c * N, 7.0, k)
+    IO.assert_guards(full_wt, N, 7.0, "weight")
     for k in d_film:
-        assert np.array_equal(d_film[k].cpu().numpy().view(np.uint32), np.ascontiguousarray(film[k], f32).reshape(-1).view(np.uint32)), k
-    for g, (rec, obj) in ((gl, low_g), (gh, high_g)):
-        assert np.array_equal(g["records"].cpu().numpy().view(np.uint32), np.ascontiguousarray(rec, f32).reshape(-1).view(np.uint32))
-        assert np.array_equal(g["object"].cpu().numpy().view(np.uint32), np.ascontiguousarray(obj, np.uint32).reshape(-1))
+        IO.assert_is_host(d_film[k], film[k], k)
+    IO.assert_gbuffer_is_host(gl, *low_g, "low G-buffer")
+    IO.assert_gbuffer_is_host(gh, *high_g, "high G-buffer")
     out = {k: d_out[k].cpu().numpy().reshape((N, c) if c == 3 else (N,)) for k, c in KEYS if k in film}
-    return out, d_wt[:N].cpu().numpy()
+    return out, d_wt.cpu().numpy()
 
 
 def _same(got, want, what):
     (out_g, wt_g), (out_w, wt_w) = got, want[:2]
-    assert set(out_g) == set(out_w), what
-    for k in out_w:
-        assert bits_equal(out_g[k], out_w[k]), (what, k, int((out_g[k].view(np.uint32) != out_w[k].view(np.uint32)).sum()))
-    assert bits_equal(wt_g, wt_w), (what, "weight")
+    IO.assert_planes_equal(out_g, out_w, what)
+    IO.assert_bits_equal(wt_g, wt_w, (what, "weight"))
 
 
 def _synthetic(w, h, s, seed, adversarial):
@@ -143,28 +131,12 @@ def test_each_sigma_in_turn_on_one_input(ctx):
 
 
 def _scene(name, res, camera):
-    import rayn_amd as R
-    from rayn_amd import setup as S
-    from rayn_amd.scene import OrthographicCamera, SphereSDF, ThinLensCamera, TracedSDF
-    cam, world = S.SCENES["s1" if name == "multi" else name](res)
-    if name == "multi":
-        world.hitables.push(TracedSDF(SphereSDF(0.6), 1, R.vec3(1.4, 0.9, 0.3)))
-    c = world.cameras.get(cam)
-    rs = (float(res[0]), float(res[1]))
-    if camera == "thin":
-        world.cameras[cam] = ThinLensCamera(rs, 55.0, 0.08, c.origin, c.at, c.up, R.vec3(0.2, 0.1, 0.0))
-    elif camera == "ortho":
-        world.cameras[cam] = OrthographicCamera(rs, 3.5, c.origin, c.at, c.up)
+    _, world, cam = scenes.scene(name, res, camera)
     return world, cam
 
 
 def _gbuffer_host(ctx, p):
-    import torch
-    from rayn_amd import film as F
-    g = F.alloc_gbuffer(p.width, p.height, "cuda")
-    ctx.gbuffer(p, g)
-    torch.cuda.synchronize()
-    return g["records"].cpu().numpy().reshape(-1, 4), g["object"].cpu().numpy().view(np.uint32)
+    return IO.gpu_gbuffer(ctx, p)[1:]
 
 
 @pytest.mark.parametrize("i,scene,camera", [(0, "s1", "pinhole"), (1, "bulb", "thin"), (2, "multi", "ortho")])
@@ -382,8 +354,7 @@ def test_render_sequence_upscale_equals_the_plain_loop(tmp_path):
     assert sorted(os.listdir(tmp_path / "seq2")) == sorted(f"anim_{f:04d}_color_denoised_display_x2.png" for f in frames)
     plain = R.Film(_kinds(), (w, h))
     for frame in frames:
-        start = f32(frame) * (f32(1.0) / f32(rate))
-        plain.render_frame_into(world, cam, integ, filt, (16, 16), frame, (float(start), float(f32(start + f32(shutter)))), 1)
+        plain.render_frame_into(world, cam, integ, filt, (16, 16), frame, IO.shutter_range(frame, rate, shutter), 1)
         hi = plain.upscaled(up)
         hi.save_to(_kinds(), str(tmp_path / "loop"), f"anim_{frame:04d}")
         hi.save_to([K.Color], str(tmp_path / "loop2"), f"anim_{frame:04d}", denoise=R.Denoise(2), display=disp)
