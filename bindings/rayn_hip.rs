@@ -481,6 +481,24 @@ extern "C" {
         d_out_source: *mut u32,
         hip_stream: *mut c_void,
     ) -> i32;
+    /// PNG encoding on the device: the bytes `d_out` / `d_scratch` of rayn_hip_png_encode_device must have for a width x height image of
+    /// `bpp` (1, 3 or 4) bytes per pixel; host only, 0 for a geometry the encoder rejects
+    pub fn rayn_png_stream_bound(width: u32, height: u32, bpp: u32) -> usize;
+    pub fn rayn_png_scratch_bytes(width: u32, height: u32, bpp: u32) -> usize;
+    /// the zlib stream of the PNG IDAT chunk of the 8-bit image `d_img` (rows top-down) behind a 16-byte header whose first word is its
+    /// length, enqueued on `hip_stream` (device pointers, `d_out` and `d_scratch` 16-byte aligned; include/rayn_hip.h has the definition)
+    pub fn rayn_hip_png_encode_device(
+        ctx: *mut RaynCtx,
+        width: u32,
+        height: u32,
+        bpp: u32,
+        d_img: *const u8,
+        d_out: *mut c_void,
+        out_bytes: usize,
+        d_scratch: *mut c_void,
+        scratch_bytes: usize,
+        hip_stream: *mut c_void,
+    ) -> i32;
 }
 
 /// Start-up layout check against the library as compiled (indices: include/rayn_hip.h, rayn_hip_sizeof).

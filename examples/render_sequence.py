@@ -5,7 +5,7 @@ written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints
     python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise [atrous|variance]] [--temporal] [--feedback B]
                                       [--resample {bilinear,catmull_rom}] [--display [--exposure auto|EV] [--tone T] [--bloom LEVELS] [--adaptation S]]
                                       [--upscale S [--temporal --supersample [--no-jitter] [--confidence | --no-confidence]]]
-                                      [--preview [K] [--ao-radius R]] [--interpolate K [--interp-tolerance D]]
+                                      [--preview [K] [--ao-radius R]] [--interpolate K [--interp-tolerance D]] [--png {host,device}]
 
 --compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
 the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
@@ -37,7 +37,11 @@ them (rayn_amd.Interpolate(K), an extension): each generated frame traces its ow
 both keys and blends the taps that show the same surface by time; --interp-tolerance D is the relative depth tolerance of a tap (default
 rayn_amd.Interpolate().depth_tolerance).  The camera's origin drifts as for --temporal, every Color file gets _interp right after _color,
 and --denoise atrous and --display work on the generated frames too; --temporal, --upscale, --preview, --denoise variance and
---compare-loop do not combine with it."""
+--compare-loop do not combine with it.
+--png device encodes every file's stream on the device (Film.render_sequence(png="device"), an extension: adaptive row filters, run-length
+and Huffman coding; the writer threads only frame it) instead of calling zlib on the host; the files keep their names and pixels, not
+their bytes, so it does not combine with --compare-loop.  The total size of the written files is printed for either encoder.
+"""
 import argparse
 import os
 import sys
@@ -113,7 +117,11 @@ def main():
                     help="render every K-th frame (2..16) and the last, and generate the frames between two rendered keys (rayn_amd.Interpolate(K))")
     ap.add_argument("--interp-tolerance", type=float, default=None, metavar="D",
                     help="relative depth tolerance of a key's tap (default rayn_amd.Interpolate().depth_tolerance); needs --interpolate")
+    ap.add_argument("--png", choices=("host", "device"), default="host",
+                    help="where the PNG streams are encoded: host (zlib in the writer threads, the default) or device (filter, run-length and Huffman kernels on the render stream)")
     args = ap.parse_args()
+    if args.png != "host" and args.compare_loop:
+        ap.error("--compare-loop compares the files byte for byte with the host encoder's: use one or the other")
     if args.interp_tolerance is not None and args.interpolate is None:
         ap.error("--interp-tolerance sets up the frame generation: add --interpolate")
     if args.interpolate is not None and not 2 <= args.interpolate <= 16:
@@ -182,12 +190,14 @@ def main():
     # warm-up: code objects, the context's first-frame arena and the writer path (not timed)
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames[:1], FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
                          os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample, preview=preview,
-                         interpolate=interpolate)
+                         interpolate=interpolate, png=args.png)
     t0 = time.perf_counter()
     stats = film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
                                  os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample, preview=preview,
-                         interpolate=interpolate)
+                         interpolate=interpolate, png=args.png)
     seq_s = time.perf_counter() - t0
+    seq_dir = os.path.join(args.out, "sequence")
+    print(f"--png {args.png}: {sum(os.path.getsize(os.path.join(seq_dir, n)) for n in os.listdir(seq_dir))} bytes in {len(os.listdir(seq_dir))} files")
     if preview is not None:  # the preview is enqueued, not waited for: there is no per-frame render time to report
         print(f"render_sequence --preview {preview}{' --temporal ' + str(temporal) if temporal else ''}{' --denoise ' + str(denoise) if denoise else ''}"
               f"{' --display ' + str(display) if display else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s")

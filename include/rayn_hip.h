@@ -855,6 +855,45 @@ int rayn_hip_interpolate_device(rayn_ctx* ctx, const rayn_frame_params* p, const
                                 float* d_out_color, float* d_out_alpha, float* d_out_background, float* d_out_normal, uint32_t* d_out_source,
                                 void* hip_stream);
 
+/* ---- PNG encoding on the device (an EXTENSION: rayn encodes on the host) -- The zlib stream of a PNG's IDAT chunk from the 8-bit image
+ * rayn_hip_save_to_pixels_device / rayn_hip_display_pixels_device write (rows top-down, bpp in {1, 3, 4} bytes per pixel), so that a
+ * sequence copies a compressed stream to the host and not the raw image.  Integer arithmetic only; tests/png_np.py restates it and the
+ * kernels agree with it byte for byte.  Any inflate accepts the stream.
+ *   Filtering.  Per row the five PNG filters None, Sub, Up, Average, Paeth (types 0..4; the row above the first is zeros, the bytes left
+ *     of the first pixel are zeros) are evaluated; the row takes the type with the smallest sum of |int8(filtered byte)|, the lowest type
+ *     on a tie.  The filtered stream R is h rows of 1 + w * bpp bytes: the type, then the filtered row.  n = h * (1 + w * bpp).
+ *   Blocks.  R is cut into blocks of 32768 bytes (the last may be shorter); every block is encoded on its own.
+ *   Tokens.  A maximal run of L equal bytes inside a block (runs never cross a block start): the first byte is a literal; of the r = L - 1
+ *     others, matches (distance 1) of length 258 while r >= 258, then one match of length r if r >= 3, else r literals.
+ *   Code.  Frequencies over the 286 literal/length symbols, end-of-block counting 1.  Code lengths are the depths of the Huffman tree built
+ *     by repeatedly merging the two smallest nodes ordered by (weight, index): a leaf's index is its symbol, internal nodes take 286, 287,
+ *     ... in creation order (the two-queue construction over the leaves sorted by (weight, symbol), a leaf before an internal node of
+ *     equal weight).  While a length exceeds 15 every non-zero frequency f becomes (f + 1) >> 1 and the tree is rebuilt.  Codes are the
+ *     canonical codes of RFC 1951 3.2.2.
+ *   A Huffman block.  A header of 1222 bits: BFINAL, BTYPE = 2, HLIT = 29, HDIST = 0, HCLEN = 15; the 19 code-length code lengths in the
+ *     RFC's order, 4 for the symbols 0..15 and 0 for 16..18 (a complete code: symbol k has the 4-bit code k); the 286 literal/length code
+ *     lengths, each as its 4-bit code; the length of the one distance code, 1 if the block has a match, else 0.  Then the tokens - a match
+ *     is its length code, its extra bits and the 1-bit distance code 0 - and end-of-block.
+ *   Stored fallback.  If that encoding, rounded up to bytes, is not shorter than len + 5 bytes the block is a stored block instead
+ *     (BTYPE = 0: one byte BFINAL, LEN, NLEN, the bytes): no block exceeds len + 5 bytes plus its alignment.
+ *   Alignment.  Every Huffman block but the final one is followed by an empty stored block: the bits 000, zero padding to the byte, 00 00
+ *     FF FF.  The final block is zero-padded.  So every block starts on a byte.
+ *   Stream.  78 01, the blocks, the big-endian Adler-32 of R.
+ *   Output.  Four little-endian words - the bytes of the zlib stream, n, the number of blocks, the number of stored blocks - then the
+ *     zlib stream from byte 16 on, contiguous; the 4-byte word holding its last byte is zero-padded and nothing behind it is written.
+ * rayn_png_stream_bound: the bytes d_out must have: 16 + 2 + n + 10 per block + 4, rounded up to 16 (a block is at most len + 5 bytes, its
+ * alignment at most 5).  rayn_png_scratch_bytes: the bytes of d_scratch (R, the blocks before their compaction, their sizes).  Both host
+ * only, needing no GPU; 0 for a geometry the encoder rejects. */
+size_t rayn_png_stream_bound(uint32_t width, uint32_t height, uint32_t bpp);
+size_t rayn_png_scratch_bytes(uint32_t width, uint32_t height, uint32_t bpp);
+/* Enqueue the encoder on 'hip_stream' (NULL = the ctx's own stream; not waited for), on the ctx's GPU (devices[0] of a multi-device ctx).
+ * DEVICE pointers: d_img width * height * bpp bytes, not modified; d_out and d_scratch 16-byte aligned, of at least the byte counts above.
+ * RAYN_ERR_INVALID_ARG with a last error text, and nothing written, for: a zero-sized image, a bpp other than 1, 3, 4, a row of more
+ * than 2^24 filtered bytes or n >= 2^31 (32-bit offsets), a NULL buffer, a misaligned or too small d_out or d_scratch, d_out == d_img and
+ * buffers that overlap. */
+int rayn_hip_png_encode_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t bpp, const uint8_t* d_img, void* d_out, size_t out_bytes,
+                               void* d_scratch, size_t scratch_bytes, void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */

@@ -396,6 +396,16 @@ inline int interpolate(rayn_ctx* ctx, const rayn_frame_params& p, float depth_to
                                        d_out_normal, d_out_source, hip_stream);
 }
 
+// Extension (include/rayn_hip.h: PNG encoding on the device): the zlib stream of the IDAT chunk of the 8-bit image d_img (res.w x res.h
+// pixels of bpp bytes, rows top-down) behind a 16-byte header whose first word is its length.  Device pointers; d_out of at least
+// png_stream_bound bytes, d_scratch of at least png_scratch_bytes, both 16-byte aligned.  Returns the entry's code.
+inline size_t png_stream_bound(Extent2u res, uint32_t bpp) { return rayn_png_stream_bound(res.w, res.h, bpp); }
+inline size_t png_scratch_bytes(Extent2u res, uint32_t bpp) { return rayn_png_scratch_bytes(res.w, res.h, bpp); }
+inline int png_encode(rayn_ctx* ctx, Extent2u res, uint32_t bpp, const uint8_t* d_img, void* d_out, size_t out_bytes, void* d_scratch,
+                      size_t scratch_bytes, void* hip_stream = nullptr) {
+    return rayn_hip_png_encode_device(ctx, res.w, res.h, bpp, d_img, d_out, out_bytes, d_scratch, scratch_bytes, hip_stream);
+}
+
 // ---- setup::setup() (src/setup.rs:46-170) with the resolution as an argument ---------------------
 namespace setup {
 constexpr float WORLD_RADIUS = 100.0f;

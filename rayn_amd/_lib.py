@@ -47,6 +47,7 @@ EXPORTS = [
     "rayn_hip_upscale_device", "rayn_hip_temporal_upscale_device",
     "rayn_preview_scratch_bytes", "rayn_hip_preview_device",
     "rayn_hip_interpolate_device",
+    "rayn_png_stream_bound", "rayn_png_scratch_bytes", "rayn_hip_png_encode_device",
 ]
 
 
@@ -144,6 +145,10 @@ def lib():
         L.rayn_hip_preview_device.argtypes = [vp, C.POINTER(_abi.FrameParams), C.POINTER(_abi.PreviewParams)] + [vp] * 9 + [C.c_size_t, vp]
         L.rayn_hip_interpolate_device.argtypes = ([vp, C.POINTER(_abi.FrameParams), C.POINTER(_abi.InterpolateParams), C.POINTER(_abi.InterpolateKey),
                                                    C.POINTER(_abi.InterpolateKey)] + [vp] * 8)
+        for fn in (L.rayn_png_stream_bound, L.rayn_png_scratch_bytes):
+            fn.restype = C.c_size_t
+            fn.argtypes = [C.c_uint32] * 3
+        L.rayn_hip_png_encode_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, vp, C.c_size_t, vp]
         L.rayn_sets_1d.restype = C.c_uint32
         L.rayn_sets_1d.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_sets_2d.restype = C.c_uint32

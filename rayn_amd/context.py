@@ -36,6 +36,17 @@ def preview_scratch_bytes(width, height, samples):
     return int(lib().rayn_preview_scratch_bytes(int(width), int(height), int(samples)))
 
 
+def png_stream_bound(width, height, bpp):
+    """rayn_png_stream_bound: the bytes Context.png_encode's output needs for a width x height image of `bpp` (1, 3 or 4) bytes per pixel:
+    the 16-byte header and the longest zlib stream the encoder can write (0 for a geometry it rejects).  Host only."""
+    return int(lib().rayn_png_stream_bound(int(width), int(height), int(bpp)))
+
+
+def png_scratch_bytes(width, height, bpp):
+    """rayn_png_scratch_bytes: bytes of device scratch the PNG encoder needs (0 for a geometry it rejects).  Host only."""
+    return int(lib().rayn_png_scratch_bytes(int(width), int(height), int(bpp)))
+
+
 def preview_tables(samples, frame, width, height):
     """The default tables of a preview of `samples` AO rays for frame `frame`: (the sample table (samples, 2) float32 - 2-D set 0 of
     build_rd_tables(samples, 0, 2, frame), so successive frames get different directions - and the per-pixel scramble of
@@ -447,6 +458,22 @@ class Context:
         ptrs = film_ptrs(d_film, FILM_KEYS, n, "d_film")
         self._chk(self._L.rayn_hip_save_to_pixels_device(self.h, int(kind), int(have_mask), int(bool(transparent_background)), int(width), int(height),
                                                          *ptrs, _ptr(d_out), stream_ptr(stream)))
+
+    def png_encode(self, width, height, bpp, d_img, d_out, d_scratch=None, stream=None):
+        """rayn_hip_png_encode_device: the zlib stream of the PNG IDAT chunk of the 8-bit image `d_img` (a uint8 CUDA tensor of width *
+        height * bpp bytes, rows top-down, as save_to_pixels and display write it) into the uint8 CUDA tensor `d_out` (at least
+        png_stream_bound(width, height, bpp) bytes, 16-byte aligned): four little-endian words - the stream's bytes, the filtered bytes,
+        the blocks, the stored blocks - then the stream (rayn_amd.image.png_from_stream frames it as a file).  d_scratch: a CUDA tensor
+        of at least png_scratch_bytes(width, height, bpp) bytes, allocated here when None.  Enqueued on the stream, not waited for; d_img
+        is not modified."""
+        import torch
+        need = int(width) * int(height) * int(bpp)
+        for t, label, n in ((d_img, "d_img", need), (d_out, "d_out", png_stream_bound(width, height, bpp))):
+            if t is None or not (t.dtype == torch.uint8 and t.is_contiguous() and t.numel() >= n):
+                raise ValueError(f"{label} must be a contiguous uint8 tensor of at least {n} bytes")
+        d_scratch, scratch_ptr, scratch_bytes = scratch(d_scratch, png_scratch_bytes(width, height, bpp), d_out.device)
+        self._chk(self._L.rayn_hip_png_encode_device(self.h, int(width), int(height), int(bpp), _ptr(d_img), _ptr(d_out), d_out.numel(), scratch_ptr,
+                                                     scratch_bytes, stream_ptr(stream)))
 
     def display_state(self):
         """A fresh state of the display transform's auto exposure: two zeroed 32-bit words {m, valid} on the context's GPU."""

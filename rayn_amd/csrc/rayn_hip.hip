@@ -29,6 +29,7 @@
 #include "post_checks.h"
 #include "preview.h"
 #include "interpolate.h"
+#include "png.h"
 #include "progressive.h"
 #include "temporal.h"
 
@@ -1186,6 +1187,16 @@ int rayn_hip_interpolate_device(rayn_ctx* ctx, const rayn_frame_params* p, const
     for (uint32_t i = 0; i < c.n_hitables; i++)
         c.hvel[i] = make_float4(w.hitables[i].center_vel.x, w.hitables[i].center_vel.y, w.hitables[i].center_vel.z, w.hitables[i].animated ? 1.0f : 0.0f);
     launch_interpolate(s, c);
+    return post_enqueued(ctx);
+}
+
+// The PNG encoder (png.hip): the 8-bit image of save_to_pixels / display_pixels -> the zlib stream of its IDAT chunk behind a 16-byte header.
+int rayn_hip_png_encode_device(rayn_ctx* ctx, uint32_t w, uint32_t h, uint32_t bpp, const uint8_t* d_img, void* d_out, size_t out_bytes, void* d_scratch,
+                               size_t scratch_bytes, void* hip_stream) {
+    const char* why = png_check_args(w, h, bpp, d_img, d_out, out_bytes, d_scratch, scratch_bytes);
+    hipStream_t s;
+    if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
+    HIPCHK(launch_png_encode(s, w, h, bpp, d_img, d_out, d_scratch));
     return post_enqueued(ctx);
 }
 

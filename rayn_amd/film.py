@@ -68,6 +68,17 @@ def _denoise_params(channel_kinds, denoise):
     return denoise.without(_have_mask(channel_kinds))
 
 
+PNG_ENCODERS = ("host", "device")
+
+
+def _check_png(png):
+    """`png` of save_to and render_sequence: "host" (zlib on the host, the files the reference's loop writes) or "device" (the stream of
+    Context.png_encode, framed on the host: smaller files of the same pixels)"""
+    if png not in PNG_ENCODERS:
+        raise ValueError(f"png must be one of {PNG_ENCODERS}, got {png!r}")
+    return png
+
+
 def _check_display(display):
     if not isinstance(display, Display):
         raise ValueError(f"display must be a Display, got {display!r}")
@@ -80,7 +91,8 @@ class SequencePlan:
     a film without WorldNormal, and None for whatever switched itself off.  variance: `denoise` was given as a VarianceDenoise.
     up_keys: the keys of the planes the upscale rebuilds (None without one).  jobs: [(kind, bytes per pixel, file suffix)] of
     every written image, the suffixes final.  preview: the Preview that takes the render's place, or None.  interpolate: the Interpolate
-    that generates the frames between the rendered keys, or None; interp_keys: the keys of the planes it generates."""
+    that generates the frames between the rendered keys, or None; interp_keys: the keys of the planes it generates.  png: "host" or
+    "device", where the files' streams are encoded."""
     denoise: object
     display: object
     upscale: object
@@ -93,6 +105,7 @@ class SequencePlan:
     preview: object = None
     interpolate: object = None
     interp_keys: object = None
+    png: str = "host"
 
     def out_res(self, res):
         """The size of the written images of a film of resolution `res`."""
@@ -101,13 +114,15 @@ class SequencePlan:
 
 
 def plan_sequence(channel_kinds, write_channels, transparent_background=False, denoise=None, display=None, upscale=None, supersample=None,
-                  temporal=None, preview=None, interpolate=None):
+                  temporal=None, preview=None, interpolate=None, png="host"):
     """The SequencePlan of render_sequence's arguments for a film of `channel_kinds`: every rule of its docstring that decides what
     runs and what the files are called, and every ValueError it raises before anything renders, in the order it raises them.  Host
     only: no context, no torch, no directory.  `interpolate` must be an Interpolate.  It raises ValueError together with `temporal`,
     with `upscale`, with `supersample` and with `preview`: none of these compositions is built.  It raises ValueError with a
     VarianceDenoise, as every sequence without `temporal` does.  It needs the film's Color channel.  It puts _interp right after
-    _color in the name of every Color image of the call, where _temporal would stand."""
+    _color in the name of every Color image of the call, where _temporal would stand.  `png` must be "host" or "device" - checked first -
+    and changes no file name."""
+    _check_png(png)
     color = ChannelKind.Color
     variance = isinstance(denoise, VarianceDenoise)
     interp_keys = None
@@ -177,7 +192,7 @@ def plan_sequence(channel_kinds, write_channels, transparent_background=False, d
     scale = "" if upscale is None else f"_x{upscale.factor}"
     jobs = [(kind, bpp, (shown_suffix if kind == color else suffix) + scale) for kind, bpp, suffix in jobs]
     return SequencePlan(denoise, display, upscale, supersample, temporal, variance, up_keys, jobs, bool(transparent_background), preview,
-                        interpolate, interp_keys)
+                        interpolate, interp_keys, png)
 
 
 class _SequencePost:
@@ -595,26 +610,37 @@ class Film:
         With `display` (a Display, an extension), the Color image goes through the HDR display transform (after the denoiser, if any;
         rayn_hip_display_pixels_device) with display_state and adapt as Context.display takes them; the other channels ignore it."""
         import torch
+        w, h = self.res
+        with torch.cuda.device(self.device):
+            out, bpp = self._pixels_device(kind, transparent_background, denoise, display, display_state, adapt)
+            return out.cpu().numpy().reshape(h, w, bpp)  # .cpu() waits for the current stream, where the kernels were enqueued
+
+    def _pixels_device(self, kind, transparent_background, denoise, display, display_state=None, adapt=1.0):
+        """pixels' image as it is enqueued on the current stream: (the uint8 device tensor, bytes per pixel).  Under torch.cuda.device."""
+        import torch
         ((kind, bpp, _),) = self._save_jobs([kind], transparent_background)
         if display is not None:
             _check_display(display)
         w, h = self.res
-        with torch.cuda.device(self.device):
-            film = self._shown_film(denoise) if kind == ChannelKind.Color else self.channels
-            out = torch.empty(h * w * bpp, dtype=torch.uint8, device=self.device)
-            if display is not None and kind == ChannelKind.Color:
-                self.ctx.display(display, self.have_mask(), transparent_background, w, h, film, out, display_state, None, adapt)
-            else:
-                self.ctx.save_to_pixels(kind, self.have_mask(), transparent_background, w, h, film, out)
-            return out.cpu().numpy().reshape(h, w, bpp)  # .cpu() waits for the current stream, where the kernels were enqueued
+        film = self._shown_film(denoise) if kind == ChannelKind.Color else self.channels
+        out = torch.empty(h * w * bpp, dtype=torch.uint8, device=self.device)
+        if display is not None and kind == ChannelKind.Color:
+            self.ctx.display(display, self.have_mask(), transparent_background, w, h, film, out, display_state, None, adapt)
+        else:
+            self.ctx.save_to_pixels(kind, self.have_mask(), transparent_background, w, h, film, out)
+        return out, bpp
 
-    def save_to(self, write_channels, output_folder, base_name, transparent_background=False, denoise=None, display=None):
+    def save_to(self, write_channels, output_folder, base_name, transparent_background=False, denoise=None, display=None, png="host"):
         """Film::save_to (src/film.rs:205-378) - the post-process after the hot path, arm by arm (on the device: pixels); the
         reference's Err(String) cases raise ValueError with the same text.  The PNGs are those of rayn_amd.image (host reference).
         With `denoise` (a Denoise or a VarianceDenoise, extensions), the Color image is made from the denoised Color and written as
         {base_name}_color_denoised.png instead of {base_name}_color.png; the other channels are unchanged.  With `display` (a Display, an
         extension) the Color image goes through the HDR display transform and its file name gets _display appended:
-        {base_name}_color_display.png, {base_name}_color_denoised_display.png."""
+        {base_name}_color_display.png, {base_name}_color_denoised_display.png.  With png="device" (an extension) the stream inside
+        every file is encoded on the device (Context.png_encode: adaptive row filters, run-length and Huffman coding) and framed by
+        image.png_from_stream: the same names and the same pixels in files of other, on rendered images smaller, bytes.  Any other value
+        than "host" and "device" raises ValueError before anything is written."""
+        _check_png(png)
         os.makedirs(output_folder, exist_ok=True)
         for kind in write_channels:
             ((kind, _, suffix),) = self._save_jobs([kind], transparent_background)  # the reference fails at the first bad channel, after writing the ones before
@@ -622,7 +648,19 @@ class Film:
                 suffix = "color_denoised"
             if display is not None and kind == ChannelKind.Color:
                 suffix += "_display"
-            image.save(os.path.join(output_folder, f"{base_name}_{suffix}.png"), self.pixels(kind, transparent_background, denoise, display))
+            path = os.path.join(output_folder, f"{base_name}_{suffix}.png")
+            if png == "host":
+                image.save(path, self.pixels(kind, transparent_background, denoise, display))
+                continue
+            import torch
+            w, h = self.res
+            with torch.cuda.device(self.device):
+                d_img, bpp = self._pixels_device(kind, transparent_background, denoise, display)
+                d_enc = torch.empty(png_stream_bound(w, h, bpp), dtype=torch.uint8, device=self.device)
+                self.ctx.png_encode(w, h, bpp, d_img, d_enc)
+                encoded = d_enc.cpu().numpy()  # waits for the current stream
+            with open(path, "wb") as f:
+                f.write(image.png_from_stream(w, h, bpp, image.png_stream_of(encoded)))
 
     def save_hdr(self, path, transparent_background=False):
         """Write the float Color channel to `path` as a little-endian PFM (image.save_pfm; rows bottom-up, like the film): Color +
@@ -747,7 +785,7 @@ class Film:
 
     def render_sequence(self, world, camera, integrator, filter, tile_size, frames, frame_rate, shutter_speed, samples, write_channels,
                         output_folder, base_name, transparent_background=False, writers=None, denoise=None, display=None, upscale=None, supersample=None, preview=None,
-                        interpolate=None, temporal=None):
+                        interpolate=None, png="host", temporal=None):
         """rayn's main loop (src/main.rs:58-96) on the GPU: for each frame of `frames`, render_frame_into at
         frame_start = frame as f32 * (1.0 / frame_rate as f32), frame_end = frame_start + shutter_speed (f32, src/main.rs:61-62), then
         save_to(write_channels, output_folder, f"{base_name}_{frame:04d}", transparent_background).  rayn writes every frame under
@@ -837,12 +875,20 @@ class Film:
         those of the plain loop.  The returned stats of a generated frame are {"frame": f, "generated": True}.  Together with
         `temporal`, `upscale`, `supersample` or `preview` it raises ValueError before anything renders: not built.  View-dependent
         shading and the shadows of moving objects are blended, not reprojected, and a generated frame averages two keys' noise
-        (DESIGN.md section 8).  interpolate=None is the path described above, unchanged."""
+        (DESIGN.md section 8).  interpolate=None is the path described above, unchanged.
+
+        With png="device" (an extension) the PNG streams are encoded on the device: after each image's post-process kernel the encoder
+        (Context.png_encode) goes on the render stream, the encoded buffer - png_stream_bound bytes, whose first word says how many
+        count - is copied into the pinned slot in place of the raw image, and the writer thread frames the stream (image.png_from_stream:
+        chunk headers and the CRC-32) and writes the file.  The encoded buffers and the encoder's scratch are allocated once and nothing
+        new synchronises.  File names do not change and the files decode to the same pixels; their bytes differ from the host
+        encoder's.  Any other value than "host" and "device" raises ValueError before anything renders.  png="host" is the path
+        described above, unchanged."""
         import concurrent.futures as cf
         import torch
         # the rules about the options alone come first and need nothing of the film, not even its channels (a bare Film.__new__ gets them)
         kinds = getattr(self, "channel_kinds", ())
-        plan = plan_sequence(kinds, write_channels, transparent_background, denoise, display, upscale, supersample, temporal, preview, interpolate)
+        plan = plan_sequence(kinds, write_channels, transparent_background, denoise, display, upscale, supersample, temporal, preview, interpolate, png)
         frames = [int(f) for f in frames]
         os.makedirs(output_folder, exist_ok=True)
         w, h = self.res
@@ -861,6 +907,12 @@ class Film:
         def write(event, img, path):
             event.synchronize()
             image.save(path, img)
+
+        def write_encoded(event, encoded, bpp, path):
+            event.synchronize()
+            data = image.png_from_stream(ow, oh, bpp, image.png_stream_of(encoded))
+            with open(path, "wb") as f:
+                f.write(data)
 
         def wait_slot(slot):
             for fut in pending[slot]:
@@ -881,7 +933,13 @@ class Film:
                 d_film = alloc_device_film(w, h, self.device)
                 d_img = [torch.empty(oh * ow * bpp, dtype=torch.uint8, device=self.device) for _, bpp, _ in plan.jobs]
                 post = _SequencePost(self, plan, desc, d_film)
-                h_img = [[torch.empty(oh * ow * bpp, dtype=torch.uint8, pin_memory=True) for _, bpp, _ in plan.jobs] for _ in range(2)]
+                on_device = plan.png == "device"
+                # what goes to the host per image: the raw image, or the encoder's output (its scratch serves every image in turn)
+                h_bytes = [png_stream_bound(ow, oh, bpp) if on_device else oh * ow * bpp for _, bpp, _ in plan.jobs]
+                h_img = [[torch.empty(n, dtype=torch.uint8, pin_memory=True) for n in h_bytes] for _ in range(2)]
+                if on_device:
+                    d_enc = [torch.empty(n, dtype=torch.uint8, device=self.device) for n in h_bytes]
+                    d_png_scratch = torch.empty(max(png_scratch_bytes(ow, oh, bpp) for _, bpp, _ in plan.jobs), dtype=torch.uint8, device=self.device)
 
                 def params_of(frame):
                     start = f32(frame) * inv_rate
@@ -916,14 +974,20 @@ class Film:
                     slot = i % 2
                     wait_slot(slot)
                     d_shown, d_base = post.enqueue(i, p, stream.cuda_stream, d_src)
-                    for (kind, _, _), d, hbuf in zip(plan.jobs, d_img, h_img[slot]):
+                    for j, ((kind, bpp, _), d, hbuf) in enumerate(zip(plan.jobs, d_img, h_img[slot])):
                         post.pixels(kind, start, d_shown if kind == ChannelKind.Color else d_base, d, stream.cuda_stream)
+                        if on_device:
+                            self.ctx.png_encode(ow, oh, bpp, d, d_enc[j], d_png_scratch, stream.cuda_stream)
+                            d = d_enc[j]
                         hbuf.copy_(d, non_blocking=True)
                     done = torch.cuda.Event()
                     done.record(stream)
                     for (_, bpp, suffix), hbuf in zip(plan.jobs, h_img[slot]):
                         path = os.path.join(output_folder, f"{base_name}_{frame:04d}_{suffix}.png")
-                        pending[slot].append(write_pool.submit(write, done, hbuf.numpy().reshape(oh, ow, bpp), path))
+                        if on_device:
+                            pending[slot].append(write_pool.submit(write_encoded, done, hbuf.numpy(), bpp, path))
+                        else:
+                            pending[slot].append(write_pool.submit(write, done, hbuf.numpy().reshape(oh, ow, bpp), path))
 
                 if itp is None:
                     for i, frame in enumerate(frames):

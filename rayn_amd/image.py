@@ -1,6 +1,7 @@
 """Film::save_to's per-pixel post-process (src/film.rs:205-378): saturate, gamma 2.2, Color+Background composite,
 Color+Alpha RGBA, normal -> RGB, y-flip, 8-bit quantise.  Host-side, after the hot path.  PNG is written with
-zlib only (the reference uses the `image` crate; the encoding is not part of the path).
+zlib only (the reference uses the `image` crate); png_from_stream frames a zlib stream made elsewhere, the device encoder's
+(Context.png_encode) included.
 
 Arithmetic follows the reference: f32 throughout, `Srgb::saturated` = x.max(0).min(1) and `gamma_corrected(2.2)` =
 x.powf(1/2.2) (src/spectrum.rs:30-40), quantisation `(v * 255.0).min(255.0).max(0.0) as u8` with Rust's f32::min/max
@@ -14,17 +15,33 @@ import numpy as np
 F32 = np.float32
 
 
+def _chunk(tag, data):
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+
+def png_from_stream(w, h, bpp, zstream):
+    """The bytes of the PNG file of a w x h image of bpp (1 grey, 3 RGB, 4 RGBA) bytes per pixel around the zlib stream of its filtered
+    rows: the signature, IHDR, one IDAT and IEND.  The CRC-32 of the chunk is computed here, on the host."""
+    ctype = {1: 0, 3: 2, 4: 6}[bpp]
+    return (b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, ctype, 0, 0, 0)) + _chunk(b"IDAT", bytes(zstream))
+            + _chunk(b"IEND", b""))
+
+
+def png_stream_of(encoded):
+    """The zlib stream inside what Context.png_encode writes (a uint8 array or bytes-like): the first little-endian word is its length,
+    the stream starts at byte 16"""
+    m = memoryview(encoded).cast("B")
+    n = int.from_bytes(m[:4], "little")
+    if n < 6 or 16 + n > len(m):
+        raise ValueError(f"not an encoded stream: length word {n} in a buffer of {len(m)} bytes")
+    return m[16:16 + n]
+
+
 def _png(path, img8):
     h, w, c = img8.shape
     raw = b"".join(b"\x00" + img8[y].tobytes() for y in range(h))
-
-    def chunk(tag, data):
-        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
-
-    ctype = {1: 0, 3: 2, 4: 6}[c]
     with open(path, "wb") as f:
-        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, ctype, 0, 0, 0)) +
-                chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+        f.write(png_from_stream(w, h, c, zlib.compress(raw, 6)))
 
 
 def _rust_min(a, b):
