@@ -1250,34 +1250,45 @@ RD float serial_sum(const float* src, uint32_t stride, uint32_t cnt) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_resolve_reg (spp <= 1024): one wave per pixel holds KPL = n_sort / 64 sort keys per lane, REGISTER-resident.  Bitonic steps whose partner lies in the same lane are compare-exchanges
-// between registers; the others exchange register r with lane ^ (jj / KPL) through a wave shuffle - no LDS round trip and no
-// barrier per step (the LDS version spent 55 x 8 dependent LDS round trips per sort at 1024 spp: 0.9 TB/s, 11 % of the HBM roof).
-// LDS only stages the sorted samples for the three serial-sum lanes.
+// What the three resolve kernels share: the sort, the Color / Background sums and the Alpha / WorldNormal pass.  A thread is t of the NT
+// threads that serve one pixel (NT = 64: the lanes of k_resolve_reg's one wave) and holds KPL keys in registers.
 // ------------------------------------------------------------------------------------------------
-RD unsigned long long shfl_xor_key(unsigned long long v, uint32_t m) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, (int)m), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), (int)m);
-    return ((unsigned long long)hi << 32) | lo;
+template <typename K>
+RD K shfl_xor_key(K v, uint32_t m) {
+    if constexpr (sizeof(K) == 8) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, (int)m), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), (int)m);
+        return ((unsigned long long)hi << 32) | lo;
+    } else return (uint32_t)__shfl_xor((int)v, (int)m);
 }
-RD uint32_t shfl_xor_key(uint32_t v, uint32_t m) { return (uint32_t)__shfl_xor((int)v, (int)m); }
 
-// ascending bitonic sort of 64 * KPL keys, element e = lane * KPL + r.  The stage (k) and the cross-lane sub-step (jj) loops
+// ascending bitonic sort of NT * KPL keys across the NT / 64 waves of a block, element e = tid * KPL + r (NT = 64: one wave, exch may be
+// null).  Sub-steps inside a thread are register compare-exchanges, sub-steps inside a wave are shuffles, and only the sub-steps whose
+// partner sits in another wave go through exch.  The stage (k) and the cross-lane sub-step (jj) loops
 // stay ROLLED (a fully unrolled u64 network at KPL = 16 was 70 KB of code and ran out of the instruction cache); only the
 // per-register work is unrolled, and selects are written so that no branch separates a shuffle from its use.
-template <typename K, uint32_t KPL>
-RD void bitonic_sort_reg(K (&key)[KPL]) {
-    const uint32_t lane = lane_id();
-    constexpr uint32_t N = 64 * KPL;
+template <typename K, uint32_t KPL, uint32_t NT>
+RD void bitonic_sort(K (&key)[KPL], K* exch /* [NT * KPL] */) {
+    const uint32_t tid = NT == 64 ? lane_id() : threadIdx.x;
+    constexpr uint32_t N = NT * KPL;
 #pragma nounroll
     for (uint32_t k = 2; k <= N; k <<= 1) {
-        const bool asc_lane = ((lane * KPL) & k) == 0; // direction of this lane's elements when k >= KPL
+        const bool asc_t = ((tid * KPL) & k) == 0; // direction of this thread's elements when k >= KPL
 #pragma nounroll
-        for (uint32_t jj = k >> 1; jj >= KPL && jj > 0; jj >>= 1) { // partner = the same register of lane ^ (jj / KPL)
-            const uint32_t lm = jj / KPL;
-            const bool keep_min = asc_lane == ((lane & lm) == 0);
+        for (uint32_t jj = k >> 1; jj >= KPL && jj > 0; jj >>= 1) {
+            const uint32_t tm = jj / KPL; // partner thread = tid ^ tm, same register
+            const bool keep_min = asc_t == ((tid & tm) == 0);
             K o[KPL];
+            if (NT > 64 && tm >= 64) { // partner in another wave: through LDS
 #pragma unroll
-            for (uint32_t r = 0; r < KPL; r++) o[r] = shfl_xor_key(key[r], lm);
+                for (uint32_t r = 0; r < KPL; r++) exch[r * NT + tid] = key[r];
+                __syncthreads();
+#pragma unroll
+                for (uint32_t r = 0; r < KPL; r++) o[r] = exch[r * NT + (tid ^ tm)];
+                __syncthreads();
+            } else {
+#pragma unroll
+                for (uint32_t r = 0; r < KPL; r++) o[r] = shfl_xor_key(key[r], tm);
+            }
 #pragma unroll
             for (uint32_t r = 0; r < KPL; r++) {
                 const bool take = (o[r] < key[r]) == keep_min; // equal keys: either copy is the same value
@@ -1285,12 +1296,12 @@ RD void bitonic_sort_reg(K (&key)[KPL]) {
             }
         }
 #pragma unroll
-        for (uint32_t jj = KPL / 2; jj > 0; jj >>= 1) { // partner in the same lane: registers r and r | jj
-            if (jj < k) {                                 // wave-uniform: this sub-step belongs to stage k
+        for (uint32_t jj = KPL / 2; jj > 0; jj >>= 1) { // partner in the same thread: registers r and r | jj
+            if (jj < k) {                                 // block-uniform: this sub-step belongs to stage k
 #pragma unroll
                 for (uint32_t r = 0; r < KPL; r++) {
                     if ((r & jj) == 0) {
-                        const bool asc = k < KPL ? (r & k) == 0 : asc_lane;
+                        const bool asc = k < KPL ? (r & k) == 0 : asc_t;
                         const K a = key[r], b = key[r | jj];
                         const bool sw = (a > b) == asc;
                         key[r] = sw ? b : a;
@@ -1300,26 +1311,6 @@ RD void bitonic_sort_reg(K (&key)[KPL]) {
             }
         }
     }
-}
-
-// keys loaded sample-major (register r of lane l = sample r * 64 + l): true when they are already in non-decreasing sample order
-RD unsigned long long shfl_key(unsigned long long v, uint32_t src) {
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, (int)src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src);
-    return ((unsigned long long)hi << 32) | lo;
-}
-RD uint32_t shfl_key(uint32_t v, uint32_t src) { return (uint32_t)__shfl((int)v, (int)src); }
-template <typename K, uint32_t KPL>
-RD bool is_sorted_reg(const K (&key)[KPL]) {
-    const uint32_t lane = lane_id();
-    bool ok = true;
-#pragma unroll
-    for (uint32_t r = 0; r < KPL; r++) {
-        // successor of sample r * 64 + lane: lane + 1 of the same register, or lane 0 of the next register (none after the last)
-        const K same = shfl_key(key[r], (lane + 1) & 63u);
-        const K wrap = r + 1 < KPL ? shfl_key(key[r + 1 < KPL ? r + 1 : r], 0u) : (K)~(K)0;
-        ok = ok && !(key[r] > (lane == 63 ? wrap : same));
-    }
-    return __ballot(!ok) == 0;
 }
 
 // serial float sum of src[lo .. hi) in index order; 128-bit LDS reads once the index is 4-aligned (one LDS instruction per four terms:
@@ -1335,6 +1326,114 @@ RD float serial_sum_range(const float* src, uint32_t lo, uint32_t hi) {
     }
     for (; e < hi; e++) a += src[e];
     return a;
+}
+
+// Color / Background of one pixel from its cnt staged samples (ch: one plane per channel in sorted order; s_flag[e]: sample e is Background;
+// nb of them are).  Background samples are emitted at depth 0 only (src/integrator.rs:151-160), i.e. they sort first: when they are
+// exactly the first nb entries of the order (split: always, unless max_bounces == 0 puts Color samples at depth 0 too) the two accumulators
+// are two plain serial sums over [0, nb) and [nb, cnt) - no per-term flag test in the issue-bound loop
+template <uint32_t N>
+RD void sum_color_background(const float (&ch)[3][N], const uint8_t* s_flag, bool split, uint32_t t, uint32_t nb, uint32_t cnt, float n, size_t fi,
+                             float* __restrict__ out_color, float* __restrict__ out_background) {
+    if (split) {
+        if (t < 6) { // threads 0..2: Color r, g, b over [nb, cnt); threads 3..5: Background over [0, nb)
+            const uint32_t c = t % 3u, isb = t / 3u;
+            const float v = serial_sum_range(ch[c], isb ? 0u : nb, isb ? nb : cnt) / n;
+            if (isb) out_background[3 * fi + c] = v; else out_color[3 * fi + c] = v;
+        }
+    } else if (t < 3) { // general order: two independent serial chains with a flag test per term (the accumulator a sample does not
+        float c = 0.0f, b = 0.0f; // belong to is simply not touched)
+        for (uint32_t e = 0; e < cnt; e++) {
+            const float v = ch[t][e];
+            if (s_flag[e]) b += v; else c += v;
+        }
+        out_color[3 * fi + t] = c / n;
+        out_background[3 * fi + t] = b / n;
+    }
+}
+
+// Alpha / WorldNormal: depth-0 packets are object-major, then queue (= sample) order: key = object:16 | sample:16, INVALID where the sample
+// hit no object; loaded sample-major (register r of thread t = sample r * NT + t, coalesced)
+template <uint32_t KPL, uint32_t NT>
+RD void aov_keys(const Pool& pool, uint32_t P0, uint32_t spp, uint32_t t, uint32_t (&k32)[KPL]) {
+#pragma unroll
+    for (uint32_t r = 0; r < KPL; r++) {
+        const uint32_t i = r * NT + t;
+        uint32_t k = INVALID;
+        if (i < spp) { const uint32_t ob = __float_as_uint(pool.aov[P0 + i].w); if (ob != OBJ_NONE) k = (ob << 16) | i; }
+        k32[r] = k;
+    }
+}
+// ... and where a pixel's normals fit in LDS together (k_resolve_reg, k_resolve_blk): stage them in key order - sorted0: the keys arrived
+// in order (the common case, one object per pixel) and are still sample-major, else they are element t * KPL + r - and sum the cnt0 of them
+template <uint32_t KPL, uint32_t NT>
+RD void aov_sums(const uint32_t (&k32)[KPL], bool sorted0, uint32_t cnt0, const Pool& pool, uint32_t P0, uint32_t t, float (&ch)[3][NT * KPL],
+                 float n, size_t fi, float* __restrict__ out_alpha, float* __restrict__ out_normal) {
+#pragma unroll
+    for (uint32_t r = 0; r < KPL; r++)
+        if (k32[r] != INVALID) {
+            const uint32_t e = sorted0 ? r * NT + t : t * KPL + r;
+            const float4 a = pool.aov[P0 + (k32[r] & 0xFFFFu)];
+            ch[0][e] = a.x; ch[1][e] = a.y; ch[2][e] = a.z;
+        }
+    __syncthreads();
+    // Alpha adds 1.0 per depth-0 surface sample: every partial sum is an integer < 2^24, so the serial sum is the count
+    if (t == 3) out_alpha[fi] = (float)cnt0 / n;
+    else if (t < 3) out_normal[3 * fi + t] = serial_sum_range(ch[t], 0u, cnt0) / n;
+}
+
+// The block kernels' "already sorted?": keys as loaded (sample-major, nokey = no sample) go to exch [NT * KPL], every thread compares its own
+// with the successors' and counts its valid ones.  meta[0] <- valid keys of the block (returned in cnt), meta[1] <- "some pair is out of
+// order"; exch is free again on return, and the first barrier also orders what the caller wrote to LDS before the call.
+template <typename K, uint32_t KPL, uint32_t NT>
+RD bool block_is_sorted(const K (&key)[KPL], K nokey, K* exch, uint32_t* meta, uint32_t& cnt) {
+    const uint32_t tid = threadIdx.x;
+    uint32_t mine = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < KPL; r++) {
+        mine += key[r] != nokey;
+        exch[r * NT + tid] = key[r];
+    }
+    if (tid < 2) meta[tid] = 0;
+    __syncthreads();
+    bool ok = true;
+#pragma unroll
+    for (uint32_t r = 0; r < KPL; r++) { // the block's last key (register KPL - 1 of thread NT - 1) has no successor
+        ok = ok && ((r + 1 == KPL && tid + 1 == NT) || !(key[r] > exch[r * NT + tid + 1]));
+    }
+    if (mine) atomicAdd(&meta[0], mine);
+    if (!ok) meta[1] = 1;
+    __syncthreads(); // also orders the LDS reads above before the exchange buffer is reused
+    cnt = meta[0];
+    return meta[1] == 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_resolve_reg (spp <= 512): one wave per pixel holds KPL = n_sort / 64 sort keys per lane, REGISTER-resident.  Bitonic steps whose partner lies in the same lane are compare-exchanges
+// between registers; the others exchange register r with lane ^ (jj / KPL) through a wave shuffle - no LDS round trip and no
+// barrier per step (the LDS version spent 55 x 8 dependent LDS round trips per sort at 1024 spp: 0.9 TB/s, 11 % of the HBM roof).
+// LDS only stages the sorted samples for the serial-sum lanes.
+// ------------------------------------------------------------------------------------------------
+template <typename K>
+RD K shfl_key(K v, uint32_t src) {
+    if constexpr (sizeof(K) == 8) {
+        const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, (int)src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src);
+        return ((unsigned long long)hi << 32) | lo;
+    } else return (uint32_t)__shfl((int)v, (int)src);
+}
+// keys loaded sample-major (register r of lane l = sample r * 64 + l): true when they are already in non-decreasing sample order
+template <typename K, uint32_t KPL>
+RD bool is_sorted_reg(const K (&key)[KPL]) {
+    const uint32_t lane = lane_id();
+    bool ok = true;
+#pragma unroll
+    for (uint32_t r = 0; r < KPL; r++) {
+        // successor of sample r * 64 + lane: lane + 1 of the same register, or lane 0 of the next register (none after the last)
+        const K same = shfl_key(key[r], (lane + 1) & 63u);
+        const K wrap = r + 1 < KPL ? shfl_key(key[r + 1 < KPL ? r + 1 : r], 0u) : (K)~(K)0;
+        ok = ok && !(key[r] > (lane == 63 ? wrap : same));
+    }
+    return __ballot(!ok) == 0;
 }
 
 template <uint32_t KPL>
@@ -1369,16 +1468,14 @@ __global__ void __launch_bounds__(64) k_resolve_reg(const DScene* __restrict__ s
         key[r] = k;
     }
     const bool sorted = is_sorted_reg<unsigned long long, KPL>(key); // sky-only pixels arrive sorted (sample-major layout)
-    if (!sorted) bitonic_sort_reg<unsigned long long, KPL>(key);   // now element lane * KPL + r
+    if (!sorted) bitonic_sort<unsigned long long, KPL, 64>(key, nullptr); // now element lane * KPL + r
     uint32_t cnt = 0, nb = 0;
 #pragma unroll
     for (uint32_t r = 0; r < KPL; r++) {
         cnt += (uint32_t)__popcll(__ballot(key[r] != NOKEY));
         nb += (uint32_t)__popcll(__ballot(key[r] != NOKEY && (((uint32_t)key[r] >> 12) & 1u)));
     }
-    // Background samples are emitted at depth 0 only, i.e. they sort first: when they are exactly the first nb entries (always, unless
-    // max_bounces == 0 puts Color samples at depth 0 too) the two accumulators are plain serial sums over [0, nb) and [nb, cnt)
-    bool prefix_ok = true;
+    bool prefix_ok = true; // the Background samples are the first nb of the order (sum_color_background)
 #pragma unroll
     for (uint32_t r = 0; r < KPL; r++) {
         if (key[r] != NOKEY) {
@@ -1392,47 +1489,17 @@ __global__ void __launch_bounds__(64) k_resolve_reg(const DScene* __restrict__ s
     }
     const bool split = __ballot(!prefix_ok) == 0;
     __syncthreads();
-    if (split) {
-        if (lane < 6) { // lanes 0..2: Color r, g, b over [nb, cnt); lanes 3..5: Background over [0, nb)
-            const uint32_t c = lane % 3u, isb = lane / 3u;
-            const float v = serial_sum_range(ch[c], isb ? 0u : nb, isb ? nb : cnt) / n;
-            if (isb) out_background[3 * fi + c] = v; else out_color[3 * fi + c] = v;
-        }
-    } else if (lane < 3) { // general order: two independent serial chains with a flag test per term (the accumulator a sample does not
-        float c = 0.0f, b = 0.0f; // belong to is simply not touched)
-        for (uint32_t e = 0; e < cnt; e++) {
-            const float v = ch[lane][e];
-            if (s_flag[e]) b += v; else c += v;
-        }
-        out_color[3 * fi + lane] = c / n;
-        out_background[3 * fi + lane] = b / n;
-    }
+    sum_color_background(ch, s_flag, split, lane, nb, cnt, n, fi, out_color, out_background);
     __syncthreads();
-    // ---- Alpha / WorldNormal: depth-0 packets are object-major, then queue (= sample) order: key = object:16 | sample:16
+    // ---- Alpha / WorldNormal
     uint32_t k32[KPL];
-#pragma unroll
-    for (uint32_t r = 0; r < KPL; r++) {
-        const uint32_t i = r * 64 + lane;
-        uint32_t k = INVALID;
-        if (i < spp) { const uint32_t ob = __float_as_uint(pool.aov[P0 + i].w); if (ob != OBJ_NONE) k = (ob << 16) | i; }
-        k32[r] = k;
-    }
-    const bool sorted0 = is_sorted_reg<uint32_t, KPL>(k32); // the common case: one object per pixel
-    if (!sorted0) bitonic_sort_reg<uint32_t, KPL>(k32);
+    aov_keys<KPL, 64>(pool, P0, spp, lane, k32);
+    const bool sorted0 = is_sorted_reg<uint32_t, KPL>(k32);
+    if (!sorted0) bitonic_sort<uint32_t, KPL, 64>(k32, nullptr);
     uint32_t cnt0 = 0;
 #pragma unroll
     for (uint32_t r = 0; r < KPL; r++) cnt0 += (uint32_t)__popcll(__ballot(k32[r] != INVALID));
-#pragma unroll
-    for (uint32_t r = 0; r < KPL; r++)
-        if (k32[r] != INVALID) {
-            const uint32_t e = sorted0 ? r * 64 + lane : lane * KPL + r;
-            const float4 a = pool.aov[P0 + (k32[r] & 0xFFFFu)];
-            ch[0][e] = a.x; ch[1][e] = a.y; ch[2][e] = a.z;
-        }
-    __syncthreads();
-    // Alpha adds 1.0 per depth-0 surface sample: every partial sum is an integer < 2^24, so the serial sum is the count
-    if (lane == 3) out_alpha[fi] = (float)cnt0 / n;
-    else if (lane < 3) out_normal[3 * fi + lane] = serial_sum_range(ch[lane], 0u, cnt0) / n;
+    aov_sums<KPL, 64>(k32, sorted0, cnt0, pool, P0, lane, ch, n, fi, out_alpha, out_normal);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1444,54 +1511,6 @@ __global__ void __launch_bounds__(64) k_resolve_reg(const DScene* __restrict__ s
 // left 2.5 (1024 spp) / 2 (4096 spp) waves per SIMD.  Half the keys per lane = ~75 VGPRs, half the chain length per lane and
 // twice the waves per pixel: 5 / 4 waves per SIMD on the same LDS.
 // ------------------------------------------------------------------------------------------------
-template <typename K, uint32_t KPL, uint32_t NT = 256>
-RD void bitonic_sort_block4(K (&key)[KPL], K* exch /* [NT * KPL] */) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    constexpr uint32_t N = NT * KPL;
-#pragma nounroll
-    for (uint32_t k = 2; k <= N; k <<= 1) {
-        const bool asc_t = ((tid * KPL) & k) == 0; // direction of this thread's elements when k >= KPL
-#pragma nounroll
-        for (uint32_t jj = k >> 1; jj >= KPL && jj > 0; jj >>= 1) {
-            const uint32_t tm = jj / KPL; // partner thread = tid ^ tm, same register
-            const bool keep_min = asc_t == ((tid & tm) == 0);
-            K o[KPL];
-            if (tm >= 64) { // partner in another wave: through LDS
-#pragma unroll
-                for (uint32_t r = 0; r < KPL; r++) exch[r * NT + tid] = key[r];
-                __syncthreads();
-#pragma unroll
-                for (uint32_t r = 0; r < KPL; r++) o[r] = exch[r * NT + (tid ^ tm)];
-                __syncthreads();
-            } else {
-#pragma unroll
-                for (uint32_t r = 0; r < KPL; r++) o[r] = shfl_xor_key(key[r], tm);
-            }
-#pragma unroll
-            for (uint32_t r = 0; r < KPL; r++) {
-                const bool take = (o[r] < key[r]) == keep_min;
-                key[r] = take ? o[r] : key[r];
-            }
-        }
-#pragma unroll
-        for (uint32_t jj = KPL / 2; jj > 0; jj >>= 1) {
-            if (jj < k) {
-#pragma unroll
-                for (uint32_t r = 0; r < KPL; r++) {
-                    if ((r & jj) == 0) {
-                        const bool asc = k < KPL ? (r & k) == 0 : asc_t;
-                        const K a = key[r], b = key[r | jj];
-                        const bool sw = (a > b) == asc;
-                        key[r] = sw ? b : a;
-                        key[r | jj] = sw ? a : b;
-                    }
-                }
-            }
-        }
-    }
-    (void)lane;
-}
-
 template <uint32_t NT, uint32_t KPL>
 __global__ void __launch_bounds__(NT) k_resolve_blk(const DScene* __restrict__ scp, const DTile* __restrict__ tiles, Pool pool,
                                                      float* __restrict__ out_color, float* __restrict__ out_alpha,
@@ -1519,7 +1538,7 @@ __global__ void __launch_bounds__(NT) k_resolve_blk(const DScene* __restrict__ s
     // a 64-bit compare and two selects.
     constexpr uint32_t NOKEY = 0xFFFFFFFFu; // keys compare UNSIGNED; depth <= 120 (validate()) puts every real key below 121 << 25 = 0xF2000000 < NOKEY (depths >= 64 do set bit 31)
     uint32_t ko[KPL];
-    uint32_t mine = 0, bgm = 0;
+    uint32_t bgm = 0;
 #pragma unroll
     for (uint32_t r = 0; r < KPL; r++) { // sample-major: register r of thread t = sample r * NT + t (coalesced)
         const uint32_t i = r * NT + tid;
@@ -1533,20 +1552,11 @@ __global__ void __launch_bounds__(NT) k_resolve_blk(const DScene* __restrict__ s
             }
         }
         ko[r] = k;
-        mine += k != NOKEY;
-        exch32[i] = k;
     }
-    if (tid < 4) s_meta[tid] = 0;
-    __syncthreads();
-    bool ok = true;
-#pragma unroll
-    for (uint32_t r = 0; r < KPL; r++) { const uint32_t i = r * NT + tid; ok = ok && (i + 1 >= n_sort || !(ko[r] > exch32[i + 1])); }
-    if (mine) atomicAdd(&s_meta[0], mine);
-    if (bgm) atomicAdd(&s_meta[2], (uint32_t)__popc(bgm));
-    if (!ok) s_meta[1] = 1;
-    __syncthreads(); // also orders the LDS reads above before the exchange buffer is reused
-    const uint32_t cnt = s_meta[0], nb = s_meta[2];
-    const bool sorted = s_meta[1] == 0;
+    if (tid < 2) s_meta[2 + tid] = 0;
+    uint32_t cnt;
+    const bool sorted = block_is_sorted<uint32_t, KPL, NT>(ko, NOKEY, exch32, s_meta, cnt);
+    if (bgm) atomicAdd(&s_meta[2], (uint32_t)__popc(bgm)); // read after the next barrier
     uint32_t rank[KPL];
 #pragma unroll
     for (uint32_t r = 0; r < KPL; r++) rank[r] = r * NT + tid; // already in order (sky-only pixels): a sample's rank is its index
@@ -1554,7 +1564,7 @@ __global__ void __launch_bounds__(NT) k_resolve_blk(const DScene* __restrict__ s
         uint32_t ks[KPL];
 #pragma unroll
         for (uint32_t r = 0; r < KPL; r++) ks[r] = ko[r];
-        bitonic_sort_block4<uint32_t, KPL, NT>(ks, exch32); // now element tid * KPL + r
+        bitonic_sort<uint32_t, KPL, NT>(ks, exch32); // now element tid * KPL + r
         __syncthreads();
 #pragma unroll
         for (uint32_t r = 0; r < KPL; r++) exch32[tid * KPL + r] = ks[r];
@@ -1568,10 +1578,8 @@ __global__ void __launch_bounds__(NT) k_resolve_blk(const DScene* __restrict__ s
         }
     }
     __syncthreads(); // every rank is known before the staging overwrites the key array
-    // Background samples are emitted at depth 0 only (src/integrator.rs:151-160), i.e. they sort first: when they are exactly the first nb
-    // entries of the order (always, unless max_bounces == 0 puts Color samples at depth 0 too) the two accumulators are two plain serial
-    // sums over [0, nb) and [nb, cnt) - no per-term flag test in the issue-bound loop
-    bool prefix_ok = true;
+    const uint32_t nb = s_meta[2];
+    bool prefix_ok = true; // the Background samples are the first nb of the order (sum_color_background)
 #pragma unroll
     for (uint32_t r = 0; r < KPL; r++) {
         if (ko[r] != NOKEY) {
@@ -1584,56 +1592,15 @@ __global__ void __launch_bounds__(NT) k_resolve_blk(const DScene* __restrict__ s
     }
     if (!prefix_ok) s_meta[3] = 1;
     __syncthreads();
-    if (s_meta[3] == 0) {
-        if (tid < 6) { // lanes 0..2: Color r, g, b over [nb, cnt); lanes 3..5: Background over [0, nb)
-            const uint32_t c = tid % 3u, isb = tid / 3u;
-            const float v = serial_sum_range(ch[c], isb ? 0u : nb, isb ? nb : cnt) / n;
-            if (isb) out_background[3 * fi + c] = v; else out_color[3 * fi + c] = v;
-        }
-    } else if (tid < 3) { // general order: two independent chains with a flag test per term (see k_resolve_reg)
-        float c = 0.0f, b = 0.0f;
-        for (uint32_t e = 0; e < cnt; e++) {
-            const float v = ch[tid][e];
-            if (s_flag[e]) b += v; else c += v;
-        }
-        out_color[3 * fi + tid] = c / n;
-        out_background[3 * fi + tid] = b / n;
-    }
+    sum_color_background(ch, s_flag, s_meta[3] == 0, tid, nb, cnt, n, fi, out_color, out_background);
     __syncthreads();
-    // ---- Alpha / WorldNormal: key = object:16 | sample:16
-    uint32_t k32[KPL];
-    mine = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < KPL; r++) {
-        const uint32_t i = r * NT + tid;
-        uint32_t k = INVALID;
-        if (i < spp) { const uint32_t ob = __float_as_uint(pool.aov[P0 + i].w); if (ob != OBJ_NONE) k = (ob << 16) | i; }
-        k32[r] = k;
-        mine += k != INVALID;
-        exch32[i] = k;
-    }
-    if (tid < 2) s_meta[tid] = 0;
+    // ---- Alpha / WorldNormal
+    uint32_t k32[KPL], cnt0;
+    aov_keys<KPL, NT>(pool, P0, spp, tid, k32);
+    const bool sorted0 = block_is_sorted<uint32_t, KPL, NT>(k32, INVALID, exch32, s_meta, cnt0);
+    if (!sorted0) bitonic_sort<uint32_t, KPL, NT>(k32, exch32);
     __syncthreads();
-    ok = true;
-#pragma unroll
-    for (uint32_t r = 0; r < KPL; r++) { const uint32_t i = r * NT + tid; ok = ok && (i + 1 >= n_sort || !(k32[r] > exch32[i + 1])); }
-    if (mine) atomicAdd(&s_meta[0], mine);
-    if (!ok) s_meta[1] = 1;
-    __syncthreads();
-    const uint32_t cnt0 = s_meta[0];
-    const bool sorted0 = s_meta[1] == 0;
-    if (!sorted0) bitonic_sort_block4<uint32_t, KPL, NT>(k32, exch32);
-    __syncthreads();
-#pragma unroll
-    for (uint32_t r = 0; r < KPL; r++)
-        if (k32[r] != INVALID) {
-            const uint32_t e = sorted0 ? r * NT + tid : tid * KPL + r;
-            const float4 a = pool.aov[P0 + (k32[r] & 0xFFFFu)];
-            ch[0][e] = a.x; ch[1][e] = a.y; ch[2][e] = a.z;
-        }
-    __syncthreads();
-    if (tid == 3) out_alpha[fi] = (float)cnt0 / n;
-    else if (tid < 3) out_normal[3 * fi + tid] = serial_sum_range(ch[tid], 0u, cnt0) / n;
+    aov_sums<KPL, NT>(k32, sorted0, cnt0, pool, P0, tid, ch, n, fi, out_alpha, out_normal);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1644,18 +1611,18 @@ __global__ void __launch_bounds__(NT) k_resolve_blk(const DScene* __restrict__ s
 // in a 2 KB bit table.  Sample index: 14 bits of the sort key.
 // ------------------------------------------------------------------------------------------------
 RD uint32_t flag_bit(const unsigned long long* bits, uint32_t e) { return (uint32_t)(bits[e >> 6] >> (e & 63u)) & 1u; }
-// serial sums of one channel in index order, colour and background kept apart by the flag table (two independent chains, see k_resolve_reg)
+// serial sums of one channel in index order, colour and background kept apart by the flag table (two independent chains, see sum_color_background)
 RD void serial_sum_split(const float* src, uint32_t stride, const unsigned long long* bits, uint32_t cnt, float& c_out, float& b_out) {
     float c = 0.0f, b = 0.0f;
     uint32_t e = 0;
     for (; e + 8 <= cnt; e += 8) {
         float v[8];
-        uint32_t f[8];
+        const uint32_t f8 = (uint32_t)(bits[e >> 6] >> (e & 63u)); // e is a multiple of 8: the eight flags sit in one word, read before the terms
 #pragma unroll
-        for (uint32_t u = 0; u < 8; u++) { v[u] = src[(e + u) * stride]; f[u] = flag_bit(bits, e + u); }
+        for (uint32_t u = 0; u < 8; u++) v[u] = src[(e + u) * stride];
 #pragma unroll
         for (uint32_t u = 0; u < 8; u++) {
-            const bool bg = f[u] != 0;
+            const bool bg = ((f8 >> u) & 1u) != 0;
             c += bg ? 0.0f : v[u];
             b += bg ? v[u] : 0.0f;
         }
@@ -1672,7 +1639,7 @@ __global__ void __launch_bounds__(1024) k_resolve_huge(const DScene* __restrict_
     constexpr uint32_t NT = 1024, KPL = 16, n_sort = NT * KPL; // 16384
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[]; // n_sort * 8 bytes
     __shared__ unsigned long long s_flags[n_sort / 64];
-    __shared__ uint32_t s_cnt;
+    __shared__ uint32_t s_meta[2]; // block_is_sorted's
     unsigned long long* exch64 = (unsigned long long*)lds_dyn;
     uint32_t* exch32 = (uint32_t*)lds_dyn;
     float2* rg = (float2*)lds_dyn;
@@ -1688,7 +1655,6 @@ __global__ void __launch_bounds__(1024) k_resolve_huge(const DScene* __restrict_
     const float n = (float)spp;
     // ---- Color / Background in (depth, slot) order
     unsigned long long key[KPL];
-    uint32_t mine = 0;
 #pragma unroll
     for (uint32_t r = 0; r < KPL; r++) { // sample-major: register r of thread t = sample r * NT + t (coalesced)
         const uint32_t i = r * NT + tid;
@@ -1699,18 +1665,10 @@ __global__ void __launch_bounds__(1024) k_resolve_huge(const DScene* __restrict_
                 k = ((unsigned long long)(info & 0x7Fu) << 47) | ((unsigned long long)pool.term_key[P0 + i] << 15) | ((info >> 7) << 14) | i;
         }
         key[r] = k;
-        mine += k != NOKEY;
-        exch64[i] = k;
     }
-    if (tid == 0) s_cnt = 0;
-    __syncthreads();
-    bool ok = true;
-#pragma unroll
-    for (uint32_t r = 0; r < KPL; r++) { const uint32_t i = r * NT + tid; ok = ok && (i + 1 >= n_sort || !(key[r] > exch64[i + 1])); }
-    if (mine) atomicAdd(&s_cnt, mine);
-    const bool sorted = __syncthreads_or(!ok) == 0; // also orders the LDS reads above before the exchange buffer is reused
-    const uint32_t cnt = s_cnt;
-    if (!sorted) bitonic_sort_block4<unsigned long long, KPL, NT>(key, exch64); // now element tid * KPL + r
+    uint32_t cnt;
+    const bool sorted = block_is_sorted<unsigned long long, KPL, NT>(key, NOKEY, exch64, s_meta, cnt);
+    if (!sorted) bitonic_sort<unsigned long long, KPL, NT>(key, exch64); // now element tid * KPL + r
     __syncthreads();
     // background flags of the sorted order (NOKEY elements sort last and are never read)
     if (sorted) {
@@ -1756,27 +1714,11 @@ __global__ void __launch_bounds__(1024) k_resolve_huge(const DScene* __restrict_
         out_background[3 * fi + 2] = b / n;
     }
     __syncthreads();
-    // ---- Alpha / WorldNormal: key = object:16 | sample:16
-    uint32_t k32[KPL];
-    mine = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < KPL; r++) {
-        const uint32_t i = r * NT + tid;
-        uint32_t k = INVALID;
-        if (i < spp) { const uint32_t ob = __float_as_uint(pool.aov[P0 + i].w); if (ob != OBJ_NONE) k = (ob << 16) | i; }
-        k32[r] = k;
-        mine += k != INVALID;
-        exch32[i] = k;
-    }
-    if (tid == 0) s_cnt = 0;
-    __syncthreads();
-    ok = true;
-#pragma unroll
-    for (uint32_t r = 0; r < KPL; r++) { const uint32_t i = r * NT + tid; ok = ok && (i + 1 >= n_sort || !(k32[r] > exch32[i + 1])); }
-    if (mine) atomicAdd(&s_cnt, mine);
-    const bool sorted0 = __syncthreads_or(!ok) == 0;
-    const uint32_t cnt0 = s_cnt;
-    if (!sorted0) bitonic_sort_block4<uint32_t, KPL, NT>(k32, exch32);
+    // ---- Alpha / WorldNormal, the normals staged in the same two rounds
+    uint32_t k32[KPL], cnt0;
+    aov_keys<KPL, NT>(pool, P0, spp, tid, k32);
+    const bool sorted0 = block_is_sorted<uint32_t, KPL, NT>(k32, INVALID, exch32, s_meta, cnt0);
+    if (!sorted0) bitonic_sort<uint32_t, KPL, NT>(k32, exch32);
     __syncthreads();
 #pragma unroll
     for (uint32_t r = 0; r < KPL; r++)
@@ -2077,23 +2019,25 @@ void launch_unpack_tiles(hipStream_t s, const DTile* tiles, uint32_t n_tiles, ui
 void launch_resolve(hipStream_t s, const DScene* sc, const DTile* tiles, uint32_t n_tiles, uint32_t max_tile_pixels, uint32_t spp, Pool pool,
                     float* out_color, float* out_alpha, float* out_background, float* out_normal, const uint32_t* base_hist, uint32_t hist_stride) {
     const dim3 grid(max_tile_pixels, n_tiles);
+#define RAYN_RESOLVE(KERNEL, NT, LDS, ...) hipLaunchKernelGGL(KERNEL, grid, dim3(NT), LDS, s, sc, tiles, pool, out_color, out_alpha, out_background, out_normal, ##__VA_ARGS__)
     if (spp <= 1024) { // register-resident sort, one wave per pixel
-        if (spp <= 64) hipLaunchKernelGGL(k_resolve_reg<1>, grid, dim3(64), 0, s, sc, tiles, pool, out_color, out_alpha, out_background, out_normal);
-        else if (spp <= 128) hipLaunchKernelGGL(k_resolve_reg<2>, grid, dim3(64), 0, s, sc, tiles, pool, out_color, out_alpha, out_background, out_normal);
-        else if (spp <= 256) hipLaunchKernelGGL(k_resolve_reg<4>, grid, dim3(64), 0, s, sc, tiles, pool, out_color, out_alpha, out_background, out_normal);
-        else if (spp <= 512) hipLaunchKernelGGL(k_resolve_reg<8>, grid, dim3(64), 0, s, sc, tiles, pool, out_color, out_alpha, out_background, out_normal);
-        else hipLaunchKernelGGL((k_resolve_blk<128, 8>), grid, dim3(128), 0, s, sc, tiles, pool, out_color, out_alpha, out_background, out_normal, base_hist, hist_stride); // two waves per pixel
+        if (spp <= 64) RAYN_RESOLVE(k_resolve_reg<1>, 64, 0);
+        else if (spp <= 128) RAYN_RESOLVE(k_resolve_reg<2>, 64, 0);
+        else if (spp <= 256) RAYN_RESOLVE(k_resolve_reg<4>, 64, 0);
+        else if (spp <= 512) RAYN_RESOLVE(k_resolve_reg<8>, 64, 0);
+        else RAYN_RESOLVE((k_resolve_blk<128, 8>), 128, 0, base_hist, hist_stride); // two waves per pixel
         return;
     }
     if (spp <= 4096) { // four / eight waves per pixel, 8 keys per lane (config 5: 4096 spp)
-        if (spp <= 2048) hipLaunchKernelGGL((k_resolve_blk<256, 8>), grid, dim3(256), 0, s, sc, tiles, pool, out_color, out_alpha, out_background, out_normal, base_hist, hist_stride);
-        else hipLaunchKernelGGL((k_resolve_blk<512, 8>), grid, dim3(512), 0, s, sc, tiles, pool, out_color, out_alpha, out_background, out_normal, base_hist, hist_stride);
+        if (spp <= 2048) RAYN_RESOLVE((k_resolve_blk<256, 8>), 256, 0, base_hist, hist_stride);
+        else RAYN_RESOLVE((k_resolve_blk<512, 8>), 512, 0, base_hist, hist_stride);
         return;
     }
     // 4096 < spp <= 16384 (the host rejects more): sixteen waves per pixel, 128 KB of dynamic LDS
     constexpr int huge_lds = 16384 * 8;
     (void)hipFuncSetAttribute((const void*)k_resolve_huge, hipFuncAttributeMaxDynamicSharedMemorySize, huge_lds); // per function AND device
-    hipLaunchKernelGGL(k_resolve_huge, grid, dim3(1024), huge_lds, s, sc, tiles, pool, out_color, out_alpha, out_background, out_normal);
+    RAYN_RESOLVE(k_resolve_huge, 1024, huge_lds);
+#undef RAYN_RESOLVE
 }
 void launch_probe_dist(hipStream_t s, const DScene* sc, uint32_t hit_index, const float* pts, float* out, uint32_t n) {
     hipLaunchKernelGGL(k_probe_dist, grid_for(n, 256), dim3(256), 0, s, sc, hit_index, pts, out, n);

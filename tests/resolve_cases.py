@@ -12,7 +12,9 @@ sign x 2^U(-12, 12) in every colour and normal channel; objects drawn from OBJEC
 
 What the shapes are for (rayn_amd/csrc/kernels.hip): launch_resolve changes kernel after 64, 128, 256, 512, 1024, 2048 and 4096 spp; k_resolve_reg<KPL>
 holds sample r * 64 + lane in register r, k_resolve_blk<NT, 8> and k_resolve_huge (NT = 1024) sample r * NT + tid: a pair of neighbouring samples can sit
-in neighbouring lanes, in lane 63 and lane 0 of the next register / wave (63|64), or in the last thread and thread 0 of the next register (NT - 1 | NT).
+in neighbouring lanes, in lane 63 and lane 0 of the next register / wave (63|64), or in the last thread and thread 0 of the next register (NT - 1 | NT).  The kernels share
+bitonic_sort, sum_color_background, aov_keys / aov_sums and block_is_sorted, so the paths that random keys do not take - the sorted shortcut, the general-order
+sums, one object per pixel, empty pixels - also run at the instantiations FAMILY_SPP leaves out (BOUNDARY_SPP).
 
 The statement of the largest case (51 pixels x 4400 spp) takes about 0.1 s on one CPU core."""
 import functools
@@ -26,6 +28,7 @@ STD_TILES = ((1, 1, 3, 2), (7, 0, 1, 5), (10, 6, 5, 4), (17, 2, 4, 5))  # x0, y0
 POOL_ORDER = (2, 0, 3, 1)
 SPP_GRID = (4, 12, 64, 68, 128, 132, 256, 260, 512, 516, 600, 1024, 1028, 1600, 2048, 2052, 2800, 4096, 4100, 4400, 16384)
 FAMILY_SPP = (256, 1024, 4096, 4400)  # reg<4>, blk<128>, blk<512>, huge
+BOUNDARY_SPP = (64, 128, 512, 2048)  # reg<1>, reg<2>, reg<8>, blk<256> at their upper launch boundary: the smallest shapes that use every register
 N_DEPTHS = 121
 OBJECTS = (0, 1, 3, 7, 0x20, 0x7F, 0x80, 0xFE)  # the default mix
 BOUNCES = 16
@@ -302,7 +305,12 @@ def builders():
         B["values_%d" % spp] = functools.partial(k_values, "values_%d" % spp, spp, s + 15)
         B["wide_grid_%d" % spp] = functools.partial(k_wide_grid, "wide_grid_%d" % spp, spp, s + 16)
         B["packed_%d" % spp] = functools.partial(k_packed, "packed_%d" % spp, spp, s + 17)
-    B["tile1024_spp4"] = functools.partial(k_tile1024, "tile1024_spp4", 77)
+    for spp in BOUNDARY_SPP:  # the non-random paths at the instantiations FAMILY_SPP leaves out
+        B["mixed0_%d" % spp] = functools.partial(k_mixed0, "mixed0_%d" % spp, spp, 9000 + spp)
+        B["sorted_sky_%d" % spp] = functools.partial(k_sorted_sky, "sorted_sky_%d" % spp, spp, 9100 + spp)
+        B["obj_one_%d" % spp] = functools.partial(k_objects, "obj_one_%d" % spp, spp, 9200 + spp, "one")
+        B["empty_%d" % spp] = functools.partial(k_empty, "empty_%d" % spp, spp, 9300 + spp)
+    B["tile1024_spp4"] =functools.partial(k_tile1024, "tile1024_spp4", 77)
     B["uncovered_256"] = functools.partial(k_random, "uncovered_256", 256, 78)
     return B
 
