@@ -96,7 +96,8 @@ struct ShadeHooks {
 
 // The persistent march kernels (k_extend / k_extend1 / k_shadow / k_shadow1 / k_shadow_bulb) hand their queue out in chunks of CHUNK entries, one atomic per
 // chunk and wave.  A chunk fetched while fewer than ENDGAME_ENTRIES entries (x K rays per lane in k_shadow_bulb) remain puts its wave into the endgame: no spare
-// rays are hoarded any more.  One definition for the kernels and for rayn_hip_probe_march_limits, from which the tests size their inputs.
+// rays are hoarded any more.  The rule itself is QueueCursor (march_queue.h); the constants are here for the kernels and for rayn_hip_probe_march_limits, from
+// which the tests size their inputs.
 constexpr uint32_t CHUNK = 256;
 constexpr uint32_t ENDGAME_ENTRIES = 256 * 32 * 64; // about one ray per resident lane of the chip
 

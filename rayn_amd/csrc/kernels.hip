@@ -26,13 +26,7 @@
 
 namespace RAYN_KNS {
 
-RD uint32_t lane_id() { return threadIdx.x & 63u; }
-// this lane's bit of a wave-uniform 64-bit mask as a predicate: the mask itself becomes the exec mask / the select's condition, no vector instruction
-RD bool lane_of(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
-// number of set bits of a 64-bit wave mask below this lane
-RD uint32_t mbcnt(uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
+#include "march_queue.h" // lane_id / lane_of / mbcnt, and what the persistent march kernels share
 
 // Per-(depth, sample) packed copy of the sample tables (see Tables in kernels.h).  One thread per record.
 __global__ void __launch_bounds__(256) k_pack_tables(Tables tab, float4* __restrict__ out, uint32_t spp, uint32_t depths, uint32_t n1, uint32_t n2) {
@@ -110,9 +104,8 @@ RD float packet_time(const DScene& sc, const uint32_t* __restrict__ q, const Poo
 
 // Persistent waves: march lengths vary 1..257 per ray, so a thread-per-ray launch idles most lanes.
 // Here every lane owns a small state machine; a lane whose ray is finished immediately takes the
-// next queue entry (wave-local chunk of 256 entries, refilled with ONE atomic per chunk), so every
-// loop iteration evaluates the SDF on (almost) all 64 lanes.  Results are written by entry/pool
-// index, so the fetch order never influences the output.
+// next queue entry (QueueCursor, march_queue.h), so every loop iteration evaluates the SDF on (almost)
+// all 64 lanes.  Results are written by entry/pool index, so the fetch order never influences the output.
 // (CHUNK and ENDGAME_ENTRIES: kernels.h, where rayn_hip_probe_march_limits reads them too)
 
 template <bool COUNT>
@@ -122,12 +115,10 @@ __global__ void __launch_bounds__(256) k_extend(const DScene* __restrict__ scp, 
     const DScene& sc = *scp;
     const uint32_t n_entries = ctl->q_groups << 6;
     uint32_t* const head = &ctl->head_extend;
-    const uint32_t lane = lane_id();
     const Thr th = make_thr(sc, depth);
     const uint32_t nh = sc.n_hitables;
     const float c0 = 0.00005f * sc.detail_scale, c1 = 0.05f * sc.detail_scale;
-    uint32_t cur = 0, end = 0; // wave-uniform chunk window
-    bool exhausted = false;
+    QueueCursor qc;
     // per-lane ray state
     bool has = false, first = false, nan = false;
     uint32_t ent = 0, P = 0, k = 0, id = OBJ_NONE, m = 0, sbits = 0;
@@ -154,42 +145,30 @@ __global__ void __launch_bounds__(256) k_extend(const DScene* __restrict__ scp, 
     bool marching = false;
     for (;;) {
         const uint64_t parked = __ballot(!marching);
-        if (parked != 0 && ((uint32_t)__popcll(parked) >= REFILL_MIN || exhausted)) {
+        if (parked != 0 && ((uint32_t)__popcll(parked) >= REFILL_MIN || qc.exhausted)) {
             if (has && !marching) { advance(); marching = has; } // epilogue of the finished march
             for (;;) { // refill idle lanes until every lane is inside a march (or the queue is empty)
                 const uint64_t need = __ballot(!has);
                 if (need == 0) break;
-                if (cur == end) {
-                    if (exhausted) break;
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(head, CHUNK);
-                    base = __builtin_amdgcn_readfirstlane(base);
-                    if (base >= n_entries) { exhausted = true; break; }
-                    cur = base;
-                    end = min(base + CHUNK, n_entries);
-                }
-                const uint32_t rank = mbcnt(need), avail = end - cur;
-                if (!has && rank < avail) {
-                    ent = cur + rank;
+                if (!qc.claim(head, n_entries)) break;
+                const QueueSlot slot = qc.fetch(need);
+                if (!has && slot.mine) {
+                    ent = slot.entry;
                     P = q[ent];
                     if (P == INVALID) ent_obj[ent] = (uint8_t)OBJ_NONE;
                     else {
-                        const float4 g0 = pool.geo0[P], g1 = pool.geo1[P];
-                        o = f3{g0.x, g0.y, g0.z};
-                        d = f3{g0.w, g1.x, g1.y};
-                        sbits = __float_as_uint(g1.w);
+                        load_ray(pool, P, &o, &d, &sbits);
                         t0 = packet_time(sc, q, pool, ent);
                         closest = sc.t_max; id = OBJ_NONE; k = 0; has = true;
                         advance();
                         marching = has;
                     }
                 }
-                cur += min((uint32_t)__popcll(need), avail);
             }
         }
         const uint64_t act = __ballot(marching);
         if (act == 0) {
-            if (__ballot(has) == 0 && exhausted) break;
+            if (__ballot(has) == 0 && qc.exhausted) break;
             continue;
         }
         // all lanes of this step evaluate the same SDF object (scenes normally hold exactly one)
@@ -214,7 +193,7 @@ __global__ void __launch_bounds__(256) k_extend(const DScene* __restrict__ scp, 
             }
         }
     }
-    if (COUNT && evals.n) { atomicAdd(evals_out, (unsigned long long)evals.n); atomicAdd(evals_out + 4, (unsigned long long)evals.it); }
+    flush_evals<COUNT>(evals, evals_out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -236,13 +215,11 @@ __global__ void __launch_bounds__(256) k_extend1(const DScene* __restrict__ scp,
     const DScene& sc = *scp;
     const uint32_t n_entries = ctl->q_groups << 6;
     uint32_t* const head = &ctl->head_extend;
-    const uint32_t lane = lane_id();
     const Thr th = make_thr(sc, depth);
     const uint32_t nh = sc.n_hitables, max_marches = sc.max_marches;
     const DHitable h = sc.h[ks]; // uniform copy
     const float c0 = 0.00005f * sc.detail_scale, c1 = 0.05f * sc.detail_scale;
-    uint32_t cur = 0, end = 0;
-    bool exhausted = false, endgame = false;
+    QueueCursor qc;
     // current ray
     uint64_t cm = 0, nm = 0, nanm = 0; // wave masks: the lanes that hold a current / a spare ray; the current ray's first distance was NaN
     uint32_t c_P = 0, c_ent = 0, c_ids = 0, e = 0; // e: evaluations of the current ray so far (marches m = e - 1)
@@ -257,45 +234,26 @@ __global__ void __launch_bounds__(256) k_extend1(const DScene* __restrict__ scp,
     float n_pre = 0.0f, n_post = 0.0f;
     for (;;) {
         const uint64_t lack = ~nm, idle = ~(cm | nm);
-        // endgame: once the queue is nearly drained no more spare rays are hoarded (a spare held by a lane that is still
-        // inside a long march would wait while other lanes idle) - idle lanes then fetch one ray at a time
-        if (!exhausted && (endgame ? idle != 0 : ((uint32_t)__popcll(lack) >= PREFETCH_MIN || (uint32_t)__popcll(idle) >= 4u))) {
+        // in the endgame (QueueCursor::endgame) no spare rays are hoarded: idle lanes fetch one ray at a time
+        if (!qc.exhausted && (qc.endgame ? idle != 0 : ((uint32_t)__popcll(lack) >= PREFETCH_MIN || (uint32_t)__popcll(idle) >= 4u))) {
             for (;;) {
-                const uint64_t need = endgame ? ~(nm | cm) : ~nm;
+                const uint64_t need = qc.endgame ? ~(nm | cm) : ~nm;
                 if (need == 0) break;
-                if (cur == end) {
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(head, CHUNK);
-                    base = __builtin_amdgcn_readfirstlane(base);
-                    if (base >= n_entries) { exhausted = true; break; }
-                    cur = base;
-                    end = min(base + CHUNK, n_entries);
-                    endgame = n_entries - base < ENDGAME_ENTRIES;
-                }
-                const uint32_t rank = mbcnt(need), avail = end - cur;
-                const uint64_t take = need & __builtin_amdgcn_ballot_w64(rank < avail);
+                if (!qc.claim(head, n_entries, ENDGAME_ENTRIES)) break;
+                const QueueSlot slot = qc.fetch(need);
+                const uint64_t take = need & __builtin_amdgcn_ballot_w64(slot.mine);
                 if (lane_of(take)) {
-                    n_ent = cur + rank;
+                    n_ent = slot.entry;
                     n_P = q[n_ent];
                     if (n_P == INVALID) ent_obj[n_ent] = (uint8_t)OBJ_NONE;
                     else {
-                        const float4 g0 = pool.geo0[n_P];
-                        const float2 g1 = *(const float2*)(&pool.geo1[n_P].x);
-                        n_o = f3{g0.x, g0.y, g0.z};
-                        n_d = f3{g0.w, g1.x, g1.y};
+                        load_ray(pool, n_P, &n_o, &n_d);
                         const float t0 = packet_time(sc, q, pool, n_ent);
                         float closest = sc.t_max;
-                        uint32_t id = OBJ_NONE;
-                        for (uint32_t k = 0; k < ks; k++) { // spheres before the SDF: the true fold
-                            float ts = sphere_hit(sc.h[k], n_o, n_d, closest, t0);
-                            if (ts < closest) { closest = ts; id = k; }
-                        }
+                        uint32_t id = OBJ_NONE, idp = OBJ_NONE;
+                        fold_spheres(sc, 0, ks, n_o, n_d, t0, closest, id); // spheres before the SDF: the true fold
                         n_pre = closest;
-                        uint32_t idp = OBJ_NONE;
-                        for (uint32_t k = ks + 1; k < nh; k++) { // spheres after it: candidates (see header)
-                            float ts = sphere_hit(sc.h[k], n_o, n_d, closest, t0);
-                            if (ts < closest) { closest = ts; idp = k; }
-                        }
+                        fold_spheres(sc, ks + 1, nh, n_o, n_d, t0, closest, idp); // spheres after it: candidates (see header)
                         n_post = closest;
                         n_ids = id | (idp << 8);
                         n_o = n_o - sphere_center(h, t0); // march in the SDF's frame (extension; zero origin in the reference)
@@ -303,7 +261,6 @@ __global__ void __launch_bounds__(256) k_extend1(const DScene* __restrict__ scp,
                     }
                 }
                 nm |= take & __builtin_amdgcn_ballot_w64(n_P != INVALID); // (a taking lane's n_P is the entry it just read)
-                cur += min((uint32_t)__popcll(need), avail);
             }
         }
         // start the spare ray; a ray's FIRST evaluation happens in the trip that promotes it, so the promotion mask is the 'first' flag (see k_shadow1)
@@ -315,7 +272,7 @@ __global__ void __launch_bounds__(256) k_extend1(const DScene* __restrict__ scp,
         }
         cm |= fm; nm &= ~fm;
         if (cm == 0) {
-            if (exhausted) break;
+            if (qc.exhausted) break;
             continue;
         }
         // TracedSDF::hit, src/sdf.rs:59-83, one evaluation per loop trip, in every lane of the product kernels (see k_shadow1)
@@ -351,7 +308,7 @@ __global__ void __launch_bounds__(256) k_extend1(const DScene* __restrict__ scp,
         cm &= ~fin;
         pt = muladd3(d, t, o); // the next trip's point (Ray::point_at); dead in a lane whose ray just ended (promotion rewrites it)
     }
-    if (COUNT && evals.n) { atomicAdd(evals_out, (unsigned long long)evals.n); atomicAdd(evals_out + 4, (unsigned long long)evals.it); }
+    flush_evals<COUNT>(evals, evals_out);
 }
 
 constexpr uint32_t QUEUE_UNROLL = 8; // groups a wave of a queue-streaming kernel has in flight per trip (r4: 4 -> 8, bin -3 %, repack -3 %)
@@ -710,12 +667,7 @@ __global__ void __launch_bounds__(256, SETUP_WAVES) k_shade_setup(const DScene* 
     // shadow jobs live IN PLACE: vis[s][slot] = 2 marks "SDF march pending" and the segment is parked at
     // job_geo[3*(s*cap + slot)..]; k_shadow_list collects the pending (sample, slot) pairs.  (A compacted job list would need
     // one atomic per wave per sample on a single counter - that alone cost 0.5 s per frame.)
-    auto park_job = [&](uint32_t s, f3 a, f3 b) {
-        const size_t idx = s * cap + j; // 24 contiguous bytes per segment (the packet time of a moving SDF is per slot: nee.t0)
-        nee.job_geo[3 * idx] = make_float2(a.x, a.y);
-        nee.job_geo[3 * idx + 1] = make_float2(a.z, b.x);
-        nee.job_geo[3 * idx + 2] = make_float2(b.y, b.z);
-    };
+    auto park_job = [&](uint32_t s, f3 a, f3 b) { store_job(nee.job_geo, s * cap + j, a, b); }; // (the packet time of a moving SDF is per slot: nee.t0)
     // analytic spheres of test_occluded (every factor is exactly 0 or 1 -> order independent)
     auto spheres_visible = [&](f3 a, f3 b) {
         f3 dir = b - a;
@@ -907,7 +859,7 @@ __global__ void __launch_bounds__(256, SETUP_WAVES) k_shade_setup(const DScene* 
     }
     const uint64_t m = __ballot(is_alive); // the group's survivors: count for the repack scan, mask for the scatter's ranks
     if (lane == 0) { alive_mask[j >> 6] = m; bgrp_cnt[j >> 6] = (uint8_t)__popcll(m); }
-    if (COUNT && evals.n) { atomicAdd(evals_out, (unsigned long long)evals.n); atomicAdd(evals_out + 4, (unsigned long long)evals.it); }
+    flush_evals<COUNT>(evals, evals_out);
     if (COUNT) { // elision accounting: [3] zero-weight slots, [7] shadow segments they would have parked, [8] their samples outside the bounds (evals_out = &evals[1])
         const uint64_t em = __ballot(zero_w);
         uint32_t nj = n_elided_jobs, no = n_oob;
@@ -982,61 +934,40 @@ __global__ void __launch_bounds__(256) k_shadow_list(Nee nee, uint32_t ns, DCtl*
     }
 }
 
-// TracedSDF::occluded (src/sdf.rs:25-57) for the pending shadow segments, persistent waves (see k_extend).
+// TracedSDF::occluded (src/sdf.rs:25-57) for the pending shadow segments, persistent waves (see k_extend; the queue: march_queue.h).
 template <bool COUNT>
 __global__ void __launch_bounds__(256) k_shadow(const DScene* __restrict__ scp, Nee nee, DCtl* __restrict__ ctl,
                                                  uint32_t REFILL_MIN, unsigned long long* __restrict__ evals_out) {
     const DScene& sc = *scp;
-    const uint32_t lane = lane_id();
     const uint32_t n_jobs = ctl->job_count, nh = sc.n_hitables;
     uint32_t* const head = &ctl->head_shadow;
     if (blockIdx.x == 0 && threadIdx.x == 0) ctl->shadow_jobs += n_jobs;
     const float c0 = 0.0001f * sc.detail_scale, c1 = 0.00001f * sc.detail_scale;
-    uint32_t cur = 0, end = 0;
-    bool exhausted = false;
-    bool has = false, first = false, nan = false;
-    uint32_t ref = 0, k = 0, m = 0;
+    QueueCursor qc;
+    bool has = false;
+    uint32_t ref = 0, k = 0, ms = 0; // ms: the march state of occluded_step
     EvalCtr evals;
     f3 start = f3{0, 0, 0}, dir = f3{0, 0, 0}, wa = f3{0, 0, 0}, wb = f3{0, 0, 0};
     float max_dist = 0.0f, t = 0.0f, jt0 = 0.0f;
     auto next_sdf = [&]() { // advance k to the next TracedSDF; none left -> the segment is visible
         while (k < nh && sc.h[k].kind == RAYN_HITABLE_SPHERE) k++;
         if (k >= nh) { nee.vis[ref] = 1; has = false; }
-        else { // the segment in this SDF's frame (TracedSDF::occluded works on start - origin, end - origin)
-            const f3 origin = sphere_center(sc.h[k], jt0);
-            start = wa - origin;
-            dir = (wb - origin) - start;
-            max_dist = mag(dir);
-            dir = div_by_mag(dir, max_dist);
-            first = true;
-        }
+        else { sdf_segment(sc.h[k], wa, wb, jt0, &start, &dir, &max_dist); ms = MS_FIRST; }
     };
     for (;;) {
         const uint64_t idle = __ballot(!has);
-        if (idle != 0 && ((uint32_t)__popcll(idle) >= REFILL_MIN) && !exhausted) {
+        if (idle != 0 && ((uint32_t)__popcll(idle) >= REFILL_MIN) && !qc.exhausted) {
             for (;;) {
                 const uint64_t need = __ballot(!has);
                 if (need == 0) break;
-                if (cur == end) {
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(head, CHUNK);
-                    base = __builtin_amdgcn_readfirstlane(base);
-                    if (base >= n_jobs) { exhausted = true; break; }
-                    cur = base;
-                    end = min(base + CHUNK, n_jobs);
-                }
-                const uint32_t rank = mbcnt(need), avail = end - cur;
-                if (!has && rank < avail) {
-                    ref = nee.job_ref[cur + rank]; // [sample][slot]
-                    const float2 j0 = nee.job_geo[3 * (size_t)ref], j1 = nee.job_geo[3 * (size_t)ref + 1], j2 = nee.job_geo[3 * (size_t)ref + 2];
-                    const float4 ja = make_float4(j0.x, j0.y, j1.x, j1.y), jb = make_float4(j2.x, j2.y, sc.anim_spheres ? nee.t0[ref % (uint32_t)nee.cap] : 0.0f, 0.0f);
-                    wa = f3{ja.x, ja.y, ja.z};
-                    wb = f3{ja.w, jb.x, jb.y};
-                    jt0 = jb.z;
+                if (!qc.claim(head, n_jobs)) break;
+                const QueueSlot slot = qc.fetch(need);
+                if (!has && slot.mine) {
+                    ref = nee.job_ref[slot.entry]; // [sample][slot]
+                    load_job(nee, sc, ref, &wa, &wb, &jt0);
                     k = 0; has = true;
                     next_sdf();
                 }
-                cur += min((uint32_t)__popcll(need), avail);
             }
         }
         const uint64_t act = __ballot(has);
@@ -1044,25 +975,14 @@ __global__ void __launch_bounds__(256) k_shadow(const DScene* __restrict__ scp, 
         const uint32_t ku = (uint32_t)__builtin_amdgcn_readlane((int)k, (int)__builtin_ctzll(act));
         const DHitable& h = sc.h[ku];
         if (has && k == ku) {
-            const f3 p = first ? start : muladd3(dir, t, start);
+            const f3 p = (ms & MS_FIRST) ? start : muladd3(dir, t, start);
             const float dist = sdf_dist<COUNT>(h, p, evals, sdf_scale(h, jt0));
-            int res = -1; // -1 keep marching, 0 occluded, 1 this SDF does not occlude
-            if (first) {
-                t = dist; nan = dist != dist; first = false; m = 0;
-                if (sc.max_vis_marches == 0) res = ((dist < 0.0001f) && !((dist > max_dist) || nan)) ? 0 : 1;
-                else if ((t > max_dist) || nan) res = 1;
-            } else {
-                if (__builtin_fabsf(dist) < fmaxs(c0, c1 * t)) res = 0;
-                else {
-                    t = t + dist; m++;
-                    if (m == sc.max_vis_marches || (t > max_dist) || nan) res = 1;
-                }
-            }
+            const int res = occluded_step(ms, t, dist, max_dist, c0, c1, sc.max_vis_marches);
             if (res == 0) has = false; // occluded: the byte keeps its 'pending' mark, which k_shade_finish reads as occluded
             else if (res == 1) { k++; next_sdf(); }
         }
     }
-    if (COUNT && evals.n) { atomicAdd(evals_out, (unsigned long long)evals.n); atomicAdd(evals_out + 4, (unsigned long long)evals.it); }
+    flush_evals<COUNT>(evals, evals_out);
 }
 
 // Fast path of k_shadow for scenes with exactly one TracedSDF: uniform SDF parameters, and a
@@ -1072,14 +992,12 @@ template <bool COUNT, int SDFK>
 __global__ void __launch_bounds__(256) k_shadow1(const DScene* __restrict__ scp, uint32_t ks, Nee nee, DCtl* __restrict__ ctl,
                                                   uint32_t PREFETCH_MIN, unsigned long long* __restrict__ evals_out) {
     const DScene& sc = *scp;
-    const uint32_t lane = lane_id();
     const uint32_t n_jobs = ctl->job_count, max_vis = sc.max_vis_marches;
     uint32_t* const head = &ctl->head_shadow;
     if (blockIdx.x == 0 && threadIdx.x == 0) ctl->shadow_jobs += n_jobs;
     const DHitable h = sc.h[ks];
     const float c0 = 0.0001f * sc.detail_scale, c1 = 0.00001f * sc.detail_scale;
-    uint32_t cur = 0, end = 0;
-    bool exhausted = false, endgame = false;
+    QueueCursor qc;
     uint64_t cm = 0, nm = 0; // wave masks: the lanes that hold a current / a spare segment
     uint32_t ref = 0, n_ref = 0, e = 0; // e: evaluations of the current segment so far (marches m = e - 1)
     EvalCtr evals;
@@ -1089,37 +1007,22 @@ __global__ void __launch_bounds__(256) k_shadow1(const DScene* __restrict__ scp,
     float c_scale = h.scale, n_scale = h.scale; // MandelBox scale at the packet time (extension)
     for (;;) {
         const uint64_t lack = ~nm, idle = ~(cm | nm);
-        // endgame: once the queue is nearly drained no more spare rays are hoarded (a spare held by a lane that is still
-        // inside a long march would wait while other lanes idle) - idle lanes then fetch one ray at a time
-        if (!exhausted && (endgame ? idle != 0 : ((uint32_t)__popcll(lack) >= PREFETCH_MIN || (uint32_t)__popcll(idle) >= 4u))) {
+        // in the endgame (QueueCursor::endgame) no spare rays are hoarded: idle lanes fetch one ray at a time
+        if (!qc.exhausted && (qc.endgame ? idle != 0 : ((uint32_t)__popcll(lack) >= PREFETCH_MIN || (uint32_t)__popcll(idle) >= 4u))) {
             for (;;) {
-                const uint64_t need = endgame ? ~(nm | cm) : ~nm;
+                const uint64_t need = qc.endgame ? ~(nm | cm) : ~nm;
                 if (need == 0) break;
-                if (cur == end) {
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(head, CHUNK);
-                    base = __builtin_amdgcn_readfirstlane(base);
-                    if (base >= n_jobs) { exhausted = true; break; }
-                    cur = base;
-                    end = min(base + CHUNK, n_jobs);
-                    endgame = n_jobs - base < ENDGAME_ENTRIES;
-                }
-                const uint32_t rank = mbcnt(need), avail = end - cur;
-                const uint64_t take = need & __builtin_amdgcn_ballot_w64(rank < avail);
+                if (!qc.claim(head, n_jobs, ENDGAME_ENTRIES)) break;
+                const QueueSlot slot = qc.fetch(need);
+                const uint64_t take = need & __builtin_amdgcn_ballot_w64(slot.mine);
                 if (lane_of(take)) {
-                    n_ref = nee.job_ref[cur + rank];
-                    const float2 j0 = nee.job_geo[3 * (size_t)n_ref], j1 = nee.job_geo[3 * (size_t)n_ref + 1], j2 = nee.job_geo[3 * (size_t)n_ref + 2];
-                    const float jt0 = sc.anim_spheres ? nee.t0[n_ref % (uint32_t)nee.cap] : 0.0f;
-                    const f3 origin = sphere_center(h, jt0); // TracedSDF origin at the packet time (extension; zero in the reference)
+                    n_ref = nee.job_ref[slot.entry];
+                    f3 a, b; float jt0;
+                    load_job(nee, sc, n_ref, &a, &b, &jt0);
                     n_scale = sdf_scale(h, jt0);
-                    n_start = f3{j0.x, j0.y, j1.x} - origin;
-                    const f3 e1 = f3{j1.y, j2.x, j2.y} - origin;
-                    n_dir = e1 - n_start;
-                    n_max = mag(n_dir);
-                    n_dir = div_by_mag(n_dir, n_max);
+                    sdf_segment(h, a, b, jt0, &n_start, &n_dir, &n_max);
                 }
                 nm |= take;
-                cur += min((uint32_t)__popcll(need), avail);
             }
         }
         // promotion of the spare segment; a segment's FIRST evaluation happens in the trip that promotes it (every lane with a
@@ -1132,7 +1035,7 @@ __global__ void __launch_bounds__(256) k_shadow1(const DScene* __restrict__ scp,
         }
         cm |= fm; nm &= ~fm;
         if (cm == 0) {
-            if (exhausted) break;
+            if (qc.exhausted) break;
             continue;
         }
         // TracedSDF::occluded, src/sdf.rs:25-57.  The product kernels evaluate in EVERY lane: a lane without a segment marches the stale point of its
@@ -1168,7 +1071,7 @@ __global__ void __launch_bounds__(256) k_shadow1(const DScene* __restrict__ scp,
         cm &= ~(occ | vis);
         pt = muladd3(dir, t, start); // the next trip's point; dead in a lane whose segment just ended (promotion rewrites it)
     }
-    if (COUNT && evals.n) { atomicAdd(evals_out, (unsigned long long)evals.n); atomicAdd(evals_out + 4, (unsigned long long)evals.it); }
+    flush_evals<COUNT>(evals, evals_out);
 }
 
 #include "march_bulb.h"
@@ -1965,16 +1868,13 @@ void launch_shadow_march(hipStream_t s, bool count, const DScene* sc, Nee nee, u
     const dim3 grid = stride_grid(max_jobs, 256, tun.persistent_blocks);
     const ShadowMarchKernel which = shadow_march_kernel(single_sdf, tun);
     if (which == SHADOW_MARCH_BULB) {
-#define RAYN_SHADOW_BULB(C, KK, SS) hipLaunchKernelGGL((k_shadow_bulb<C, KK, SS>), grid, dim3(256), 0, s, sc, (uint32_t)single_sdf, nee, ctl, tun.bulb_orbit_min, tun.bulb_prefetch_min, evals + 2)
-        if (count) { // the instrumented kernels run the SAME shape as the product ones (their stage-occupancy counters are quoted for it)
-            if (tun.bulb_rays == 2) { if (tun.bulb_steps == 2) RAYN_SHADOW_BULB(true, 2, 2); else RAYN_SHADOW_BULB(true, 2, 1); }
-            else if (tun.bulb_rays == 3) { if (tun.bulb_steps == 2) RAYN_SHADOW_BULB(true, 3, 2); else RAYN_SHADOW_BULB(true, 3, 1); }
-            else { if (tun.bulb_steps == 2) RAYN_SHADOW_BULB(true, 4, 2); else RAYN_SHADOW_BULB(true, 4, 1); }
-        }
-        else if (tun.bulb_rays == 2) { if (tun.bulb_steps == 2) RAYN_SHADOW_BULB(false, 2, 2); else RAYN_SHADOW_BULB(false, 2, 1); }
-        else if (tun.bulb_rays == 3) { if (tun.bulb_steps == 2) RAYN_SHADOW_BULB(false, 3, 2); else RAYN_SHADOW_BULB(false, 3, 1); }
-        else { if (tun.bulb_steps == 2) RAYN_SHADOW_BULB(false, 4, 2); else RAYN_SHADOW_BULB(false, 4, 1); }
-#undef RAYN_SHADOW_BULB
+        // (count, bulb_rays, bulb_steps) -> k_shadow_bulb<C, K, STEPS>, once: rays 2 / 3 / otherwise 4, steps 2 / otherwise 1.  The instrumented kernels run the
+        // SAME shape as the product ones (their stage-occupancy counters are quoted for it)
+#define RAYN_BULB(C) {{k_shadow_bulb<C, 2, 1>, k_shadow_bulb<C, 2, 2>}, {k_shadow_bulb<C, 3, 1>, k_shadow_bulb<C, 3, 2>}, {k_shadow_bulb<C, 4, 1>, k_shadow_bulb<C, 4, 2>}}
+        static constexpr decltype(&k_shadow_bulb<false, 3, 2>) bulb[2][3][2] = {RAYN_BULB(false), RAYN_BULB(true)};
+#undef RAYN_BULB
+        const auto kernel = bulb[count][tun.bulb_rays == 2 ? 0 : tun.bulb_rays == 3 ? 1 : 2][tun.bulb_steps == 2];
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, sc, (uint32_t)single_sdf, nee, ctl, tun.bulb_orbit_min, tun.bulb_prefetch_min, evals + 2);
     } else if (which == SHADOW_MARCH_SINGLE) {
 #define RAYN_SHADOW1(C, KIND) hipLaunchKernelGGL((k_shadow1<C, KIND>), grid, dim3(256), 0, s, sc, (uint32_t)single_sdf, nee, ctl, tun.prefetch_min_shadow, evals + 2)
         if (count) RAYN_SHADOW1(true, -1);

@@ -15,11 +15,9 @@
 // stages give); a refill pipelined over three rounds (6 178 ms); the same scheme for the closest-hit marches (k_extend1 stays: 1 366 vs 1 425 ms).
 #pragma once
 
-constexpr uint32_t BC_FIRST = 1u << 16, BC_NAN = 1u << 17, BC_COUNT = 0xFFFFu;        // march flags + march count of a ray
-
 // ------------------------------------------------------------------------------------------------
 // v2 (rounds): every lane owns K rays in registers; the wave works in ROUNDS of three phases
-//   A  refill    empty ray slots take the next entries of the job queue (bulk, one atomic per 256 entries)
+//   A  refill    empty ray slots take the next entries of the job queue (bulk, one atomic per chunk: QueueCursor, march_queue.h)
 //   B  orbits    the 64 K waiting points of the wave are a job list in LDS (one float4 per job: point in, |w|^2 / dz / steps out).  ANY lane
 //                runs ANY job: a lane whose orbit ends stores the result and pulls the next unstarted job (ballot + mbcnt on a wave-uniform
 //                counter), so the orbit steps run at full occupancy.  The phase does NOT wait for the slowest orbits: once every job has been started and
@@ -56,14 +54,16 @@ __global__ void __launch_bounds__(256, K == 2 ? 8 : (K == 3 ? 7 : 6)) k_shadow_b
     const DHitable h = sc.h[ks];
     const uint32_t iterations = h.iterations; // >= 1 (the host takes the generic kernels otherwise)
     const float c0 = 0.0001f * sc.detail_scale, c1 = 0.00001f * sc.detail_scale;
-    uint32_t cur = 0, end = 0;
+    // The cursor's two flags are this kernel's own variables around QueueCursor::take_chunk: with the flags inside the cursor (QueueCursor::claim) the K = 4
+    // instantiations grew by 76 to 207 instructions and from 16 to 36 bytes of spill under every form tried (DESIGN.md "Persistent march kernels")
+    QueueCursor qc;
     bool exhausted = false, endgame = false;
     EvalCtr evals;
     uint32_t n_orbit_trips = 0, n_epi_passes = 0; // COUNT builds: executions of the two stages by this wave (x 64 = lane slots offered)
     // the lane's K rays: segment start / unit direction / length in the SDF's frame, march distance, job ref, march count + flags
     f3 st[K], dr[K];
     float mx[K], t[K];
-    uint32_t ref[K], cnt[K];
+    uint32_t ref[K], cnt[K]; // cnt: the march state of occluded_step
     bool act[K];     // the slot holds a live ray
 #pragma unroll
     for (uint32_t k = 0; k < K; k++) { st[k] = dr[k] = f3{0, 0, 0}; mx[k] = t[k] = 0.0f; ref[k] = cnt[k] = 0; act[k] = false; }
@@ -87,30 +87,20 @@ __global__ void __launch_bounds__(256, K == 2 ? 8 : (K == 3 ? 7 : 6)) k_shadow_b
                 for (;;) {
                     const uint64_t need = __ballot(!act[k]);
                     if (need == 0) break;
-                    if (cur == end) {
-                        uint32_t base = 0;
-                        if (lane == 0) base = atomicAdd(head, CHUNK);
-                        base = __builtin_amdgcn_readfirstlane(base);
-                        if (base >= n_jobs) { exhausted = true; break; }
-                        cur = base;
-                        end = min(base + CHUNK, n_jobs);
-                        endgame = n_jobs - base < ENDGAME_ENTRIES * K;
+                    if (qc.cur == qc.end) {
+                        const uint32_t left = qc.take_chunk(head, n_jobs);
+                        if (left == 0) { exhausted = true; break; }
+                        endgame = left < ENDGAME_ENTRIES * K;
                     }
-                    const uint32_t rank = mbcnt(need), avail = end - cur;
-                    if (!act[k] && rank < avail) {
-                        const uint32_t n_ref = nee.job_ref[cur + rank];
-                        const float2 j0 = nee.job_geo[3 * (size_t)n_ref], j1 = nee.job_geo[3 * (size_t)n_ref + 1], j2 = nee.job_geo[3 * (size_t)n_ref + 2];
-                        const float jt0 = sc.anim_spheres ? nee.t0[n_ref % (uint32_t)nee.cap] : 0.0f;
-                        const f3 origin = sphere_center(h, jt0); // TracedSDF origin at the packet time (extension; zero in the reference)
-                        st[k] = f3{j0.x, j0.y, j1.x} - origin;
-                        const f3 e = f3{j1.y, j2.x, j2.y} - origin;
-                        const f3 d = e - st[k];
-                        mx[k] = mag(d);
-                        dr[k] = div_by_mag(d, mx[k]);
-                        ref[k] = n_ref; cnt[k] = BC_FIRST; t[k] = 0.0f; act[k] = true;
+                    const QueueSlot slot = qc.fetch(need);
+                    if (!act[k] && slot.mine) {
+                        ref[k] = nee.job_ref[slot.entry];
+                        f3 a, b; float jt0;
+                        load_job(nee, sc, ref[k], &a, &b, &jt0);
+                        sdf_segment(h, a, b, jt0, &st[k], &dr[k], &mx[k]);
+                        cnt[k] = MS_FIRST; t[k] = 0.0f; act[k] = true;
                         jobs[lane + 64u * k] = make_float4(st[k].x, st[k].y, st[k].z, __uint_as_float(BJ_POINT)); // the first evaluation is at the segment start
                     }
-                    cur += min((uint32_t)__popcll(need), avail);
                 }
             }
         }
@@ -174,19 +164,7 @@ __global__ void __launch_bounds__(256, K == 2 ? 8 : (K == 3 ? 7 : 6)) k_shadow_b
             if (act[k] && __float_as_uint(r.w) == BJ_RESULT) { // (an orbit still in flight: next round)
                 const float dist = bulb_finish_inl(r.x, r.y, logtab);
                 if (COUNT) { evals.n++; evals.it += __float_as_uint(r.z); }
-                bool nan = (cnt[k] & BC_NAN) != 0;
-                int res = -1; // -1 keep marching, 0 occluded, 1 visible
-                if (cnt[k] & BC_FIRST) {
-                    t[k] = dist; nan = dist != dist; cnt[k] = nan ? BC_NAN : 0u;
-                    if (max_vis == 0) res = ((dist < 0.0001f) && !((dist > mx[k]) || nan)) ? 0 : 1;
-                    else if ((t[k] > mx[k]) || nan) res = 1;
-                } else {
-                    if (__builtin_fabsf(dist) < fmaxs(c0, c1 * t[k])) res = 0;
-                    else {
-                        t[k] = t[k] + dist; cnt[k]++;
-                        if ((cnt[k] & BC_COUNT) == max_vis || (t[k] > mx[k]) || nan) res = 1;
-                    }
-                }
+                const int res = occluded_step(cnt[k], t[k], dist, mx[k], c0, c1, max_vis); // -1 keep marching, 0 occluded, 1 visible
                 if (res >= 0) { if (res == 1) nee.vis[ref[k]] = 1; act[k] = false; } // only VISIBLE results are written (see Nee::vis)
                 else {
                     const f3 pn = muladd3(dr[k], t[k], st[k]); // the next point of the march
@@ -199,7 +177,7 @@ __global__ void __launch_bounds__(256, K == 2 ? 8 : (K == 3 ? 7 : 6)) k_shadow_b
         if (K > 2) epilogue(K > 2 ? 2 : 0);
         if (K > 3) epilogue(K > 3 ? 3 : 0);
     }
-    if (COUNT && evals.n) { atomicAdd(evals_out, (unsigned long long)evals.n); atomicAdd(evals_out + 4, (unsigned long long)evals.it); }
+    flush_evals<COUNT>(evals, evals_out);
     if (COUNT && lane == 0) { atomicAdd(evals_out + 10, 64ull * n_orbit_trips); atomicAdd(evals_out + 11, 64ull * n_epi_passes); } // evals_out = &evals[2]: [12], [13]
 }
 

@@ -43,6 +43,8 @@
 
 namespace RAYN_KNS {
 
+#include "march_queue.h" // store_job: the segment layout the shadow kernels read
+
 // One thread per padded pixel slot, whole waves.  k0 == 0 is the first round.
 __global__ void __launch_bounds__(256) k_preview_jobs(const DScene* __restrict__ scp, uint32_t n, uint32_t npad, uint32_t k0, uint32_t kn, float radius,
                                                        float ambient, const float2* __restrict__ samples, const float* __restrict__ scramble,
@@ -115,9 +117,7 @@ __global__ void __launch_bounds__(256) k_preview_jobs(const DScene* __restrict__
             if (open && scene_has_sdf) {
                 vb = 2;
                 pend |= 1u << kk;
-                job_geo[3 * idx] = make_float2(a.x, a.y);
-                job_geo[3 * idx + 1] = make_float2(a.z, b.x);
-                job_geo[3 * idx + 2] = make_float2(b.y, b.z);
+                store_job(job_geo, idx, a, b);
             }
             vis[idx] = vb;
         }

@@ -111,3 +111,24 @@ def test_oracle_outcomes_on_the_generated_inputs(oracle, name):
         k = c == M.RAY_CLASSES.index(cls)
         assert (obj[k] == 0xFFFFFFFF).all() and (np.isnan(t[k]) | (t[k] == miss_t[0])).all(), cls
     assert M.same_t(t, t).all() and not M.same_t(t[:1000], t[1:1001]).all()
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 513])
+def test_generators_and_oracle_helpers_at_the_queue_edge_sizes(oracle, n):
+    """The sizes of test_extend_queue_edges / test_shadow_queue_edges: the generators and the cached oracle cases take them (fewer entries than oracle threads,
+    than a class period, than a chunk) and return arrays of length n that equal the plain oracle calls."""
+    a, b = M.segments(n, 31)
+    org, d = M.rays(n, 41)
+    assert a.shape == b.shape == org.shape == d.shape == (n, 3)
+    assert np.array_equal(M.seg_class(np.arange(n)), M.seg_class(np.arange(513))[:n])
+    for name in ("s1", "bulb", "two_sdfs"):
+        wd, p, ca, cb, ref = M.occluded_case(oracle, name, {}, 31, n)
+        assert ca is a and cb is b and ref.shape == (n,) and ref.dtype == np.float32
+        assert np.array_equal(ref, oracle.test_occluded(wd, p, a, b))
+        ev, it = M.occluded_counts(name, {}, 31, n)
+        assert ev >= n and it >= 0  # every segment is evaluated at least once
+    for name in ("s1", "bulb"):
+        wd, p, co, cd, t, obj = M.closest_hit_case(oracle, name, 0, {}, 41, n)
+        assert co is org and cd is d and t.shape == obj.shape == (n,)
+        rt, robj = oracle.closest_hit(wd, p, 0, org, d)
+        assert np.array_equal(obj, robj) and M.same_t(t, rt).all()

@@ -182,6 +182,32 @@ def test_generic_shadow_at_size(oracle, monkeypatch):
         check_shadow(ctx, oracle, "two_sdfs", {}, _n(ctx, 1, tuned=True))
 
 
+# ---- b2. the queue's end at a chunk boundary --------------------------------------------------------------------------------------------------------
+# Every size above puts the end of the queue deep inside a chunk.  Here: one lane; one 64-group minus / plus one entry; exactly one chunk of 256, one short and
+# one more (a second wave claims a chunk of ONE entry, every further wave of the grid finds the queue exhausted at its first claim with nothing in hand); two
+# chunks plus one.  All endgame launches (n < ENDGAME_ENTRIES): what varies is the cursor's window arithmetic, which is the same in both modes.
+EDGE_N = [1, 63, 64, 65, 255, 256, 257, 513]
+
+
+@pytest.mark.parametrize("n", EDGE_N)
+@pytest.mark.parametrize("kernel", ["k_extend1", "k_extend1_bulb", "k_extend"])
+def test_extend_queue_edges(gpu_ctx, oracle, monkeypatch, kernel, n):
+    assert M.march_limits(gpu_ctx)[0] == 256  # the sizes above are written for this CHUNK
+    if kernel == "k_extend":
+        with tuned_ctx(monkeypatch, {"RAYN_HIP_FAST_PATH": "0"}) as ctx:
+            check_extend(ctx, oracle, "s1", 0, {}, n)
+    else:
+        check_extend(gpu_ctx, oracle, "bulb" if kernel == "k_extend1_bulb" else "s1", 0, {}, n)
+
+
+@pytest.mark.parametrize("n", EDGE_N)
+@pytest.mark.parametrize("name", ["s1", "bulb", "two_sdfs"])
+def test_shadow_queue_edges(gpu_ctx, oracle, name, n):
+    """k_shadow1, k_shadow_bulb (default K and STEPS) and k_shadow (a scene of several TracedSDFs)."""
+    assert M.march_limits(gpu_ctx)[0] == 256
+    check_shadow(gpu_ctx, oracle, name, {}, n)
+
+
 # ---- c. march budgets in steady state ------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("name,budget", [("s1", 0), ("s1", 1), ("s1", 5), ("bulb", 0), ("bulb", 1), ("bulb", 5)])
