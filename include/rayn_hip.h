@@ -1068,7 +1068,7 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *   Dielectric: Sky and Emissive never scatter (receives_light is false), so those paths are never reached and are not probed.  Ops 13 and 14
  *   take t0 per lane - the packet's lane-0 time at which a closure centre (rayn_hitable.animated) is sampled; NaN is the time of a packet whose
  *   lane 0 is empty - and return RAYN_ERR_INVALID_ARG with a text when `index` is out of range or names a TracedSDF.
- *   rayn_hip_probe_queue      the queue stages of ONE depth through the PRODUCT kernels, launched as the depth loop launches them, on a caller-built ray queue
+ *   rayn_hip_probe_queue      the queue stages of ONE depth through the PRODUCT kernels and the two stage launchers the depth loop calls, on a caller-built ray queue
  *                             (no scene, no world needed): stage 0 = bin (k_group_hist, k_scan_tile, k_tile_prefix, k_bin_scatter: object-major, insertion-ordered,
  *                             x4-padded packets per tile), stage 1 = repack (k_scan_tile, k_tile_prefix, k_compact_scatter: the stable repack of the survivors).
  *     in   nclass 1..16; tile_groups[n_tiles] = 64-entry groups each tile owns in the ray queue (tiles back to back, 0 allowed); q[e] / ent_obj[e] for the

@@ -15,11 +15,11 @@ namespace rayn {
 
 struct ProfRec { int cls; hipEvent_t a, b; };
 
-struct Arena { // one device allocation carved into 256-byte aligned pieces
+struct Arena { // one device allocation carved into 256-byte aligned pieces; without memory (a dry run) it only counts
     char* base = nullptr; size_t cap = 0, off = 0;
     template <typename T> T* take(size_t n) {
         size_t bytes = (n * sizeof(T) + 255) & ~(size_t)255;
-        T* p = (T*)(base + off);
+        T* p = base ? (T*)(base + off) : nullptr;
         off += bytes;
         return p;
     }

@@ -85,6 +85,18 @@ struct DCtl {
     unsigned long long segments, shaded_slots, entries_sum, next_sum, shadow_jobs, _pad2;
 };
 
+// The per-entry, per-group and per-tile tables of one worker's queue stages.  Host side only, never a kernel argument: it names which table is which for
+// launch_bin_stage / launch_repack_stage, so that a caller cannot pass two of some twenty uint32_t* in the wrong order.
+struct QueueTables {
+    uint8_t* ent_obj;           // [ray-queue entries] hit object of every entry (the extend kernels; OBJ_NONE: miss or padding)
+    unsigned long long* alive;  // [binned groups]     survivor ballot of every binned 64-slot group (k_shade_setup)
+    uint8_t* grp_cnt; uint32_t *grp_base, *grp_tile;    // per ray-queue group: [SCAN_NC_BIN] class counts and bases, its tile
+    uint8_t* bgrp_cnt; uint32_t *bgrp_base, *bgrp_tile; // per binned group: survivor count and base, its tile
+    // per tile: first group and group count of its segment of the RAY queue (k_batch_setup, then every repack) and of the BINNED queue (every bin stage)
+    uint32_t *ray_tgb, *ray_tgc, *bin_tgb, *bin_tgc;
+    uint32_t *tile_total, *tile_valid, *tile_out_base, *tile_cls_cnt, *tile_cls_base; // per tile (the last two x SCAN_NC_BIN): scratch of the stage that runs
+};
+
 // the host brackets the three shading kernels with its profiling events through these hooks
 struct ShadeHooks {
     void* user;
@@ -156,22 +168,11 @@ struct Tables {
                        Pool pool, uint32_t* q, uint32_t n_pool, DCtl* ctl);                         \
     void launch_extend(hipStream_t s, bool count, const DScene* sc, uint32_t depth, const uint32_t* q, uint32_t max_entries, Pool pool, \
                        uint8_t* ent_obj, int single_sdf, DCtl* ctl, unsigned long long* evals, const Tuning& tun); \
-    void launch_group_hist(hipStream_t s, uint32_t nclass, const uint8_t* ent_obj, uint32_t max_entries, const DCtl* ctl, uint8_t* grp_cnt); \
-    void launch_scan_tile(hipStream_t s, uint32_t n_tiles, uint32_t nclass, uint32_t stride, uint32_t pad, const uint8_t* grp_cnt, \
-                          const uint32_t* tgb, const uint32_t* tgc, uint32_t* grp_base, uint32_t* grp_tile, uint32_t* tile_total, \
-                          uint32_t* tile_valid, uint32_t* tile_cls_cnt, const DCtl* ctl);           \
-    void launch_tile_prefix(hipStream_t s, uint32_t n_tiles, const uint32_t* tile_total, const uint32_t* tile_valid, uint32_t* tile_out_base, \
-                            uint32_t* ogb, uint32_t* ogc, DCtl* ctl, int stage, uint32_t nclass, uint32_t pad, const uint32_t* tile_cls_cnt, \
-                            uint32_t* tile_cls_base, uint32_t cap_groups, uint32_t* base_hist);     \
-    void launch_bin_scatter(hipStream_t s, uint32_t nclass, const uint32_t* q, const uint8_t* ent_obj, const uint32_t* grp_base, \
-                            const uint32_t* grp_tile, const uint32_t* tile_out_base, uint32_t max_entries, uint32_t* bq, uint32_t n_tiles, \
-                            const uint32_t* tile_cls_cnt, const uint32_t* tile_total, const uint32_t* tile_cls_base, const DCtl* ctl); \
+    void launch_bin_stage(hipStream_t s, const QueueTables& T, uint32_t nclass, uint32_t n_tiles, const uint32_t* q, uint32_t max_entries, uint32_t* bq, uint32_t cap_groups, uint32_t* base_hist_row, DCtl* ctl); \
     void launch_shade(hipStream_t s, bool count, const DScene* sc, Tables tab, const float* scramble, uint32_t depth, const uint32_t* bq, \
                       uint32_t max_slots, Pool pool, Nee nee, uint32_t ns, bool has_sdf, int single_sdf, unsigned long long* alive_mask, uint8_t* bgrp_cnt, DCtl* ctl, \
                       unsigned long long* evals, ShadeHooks hooks, const Tuning& tun);              \
-    void launch_compact_scatter(hipStream_t s, const uint32_t* bq, const unsigned long long* alive_mask, const uint32_t* grp_base, const uint32_t* grp_tile, \
-                                const uint32_t* tile_out_base, uint32_t max_slots, uint32_t* qn, uint32_t n_tiles, const uint32_t* tile_total, \
-                                const DCtl* ctl);                                                   \
+    void launch_repack_stage(hipStream_t s, const QueueTables& T, uint32_t n_tiles, const uint32_t* bq, uint32_t max_slots, uint32_t* qn, uint32_t cap_groups, DCtl* ctl); \
     void launch_unpack_tiles(hipStream_t s, const DTile* tiles, uint32_t n_tiles, uint32_t width, float* color, float* alpha, \
                              float* background, float* normal, const float* packed, size_t packed_pixels); \
     void launch_batch_setup(hipStream_t s, const DTile* tiles, uint32_t n_tiles, uint32_t* pgrp_tile, uint32_t* tgb, uint32_t* tgc); \
@@ -192,12 +193,9 @@ struct KernelSet {
     decltype(&rayn_p0::launch_pack_tables) pack_tables;
     decltype(&rayn_p0::launch_raygen) raygen;
     decltype(&rayn_p0::launch_extend) extend;
-    decltype(&rayn_p0::launch_group_hist) group_hist;
-    decltype(&rayn_p0::launch_scan_tile) scan_tile;
-    decltype(&rayn_p0::launch_tile_prefix) tile_prefix;
-    decltype(&rayn_p0::launch_bin_scatter) bin_scatter;
+    decltype(&rayn_p0::launch_bin_stage) bin_stage;
     decltype(&rayn_p0::launch_shade) shade;
-    decltype(&rayn_p0::launch_compact_scatter) compact_scatter;
+    decltype(&rayn_p0::launch_repack_stage) repack_stage;
     decltype(&rayn_p0::launch_batch_setup) batch_setup;
     decltype(&rayn_p0::launch_resolve) resolve;
     decltype(&rayn_p0::launch_probe_dist) probe_dist;
@@ -206,7 +204,7 @@ struct KernelSet {
     decltype(&rayn_p0::launch_probe_shading) probe_shading;
     decltype(&rayn_p0::launch_probe_dist_as) probe_dist_as;
 };
-#define RAYN_KERNEL_SET(NS) KernelSet{&NS::launch_pack_tables, &NS::launch_raygen, &NS::launch_extend, &NS::launch_group_hist, &NS::launch_scan_tile, &NS::launch_tile_prefix, &NS::launch_bin_scatter, &NS::launch_shade, &NS::launch_compact_scatter, &NS::launch_batch_setup, &NS::launch_resolve, &NS::launch_probe_dist, &NS::launch_shadow_march, &NS::launch_probe_detmath, &NS::launch_probe_shading, &NS::launch_probe_dist_as}
+#define RAYN_KERNEL_SET(NS) KernelSet{&NS::launch_pack_tables, &NS::launch_raygen, &NS::launch_extend, &NS::launch_bin_stage, &NS::launch_shade, &NS::launch_repack_stage, &NS::launch_batch_setup, &NS::launch_resolve, &NS::launch_probe_dist, &NS::launch_shadow_march, &NS::launch_probe_detmath, &NS::launch_probe_shading, &NS::launch_probe_dist_as}
 inline KernelSet kernel_set(int fma_policy) {
     if (fma_policy) return RAYN_KERNEL_SET(rayn_p1);
     return RAYN_KERNEL_SET(rayn_p0);

@@ -1811,7 +1811,6 @@ __global__ void __launch_bounds__(256) k_verify_short_div(float n, uint32_t lo_b
 // ---- launch wrappers (declared in kernels.h) -----------------------------------------------------
 static inline dim3 grid_for(uint32_t n, uint32_t block) { return dim3((n + block - 1) / block); }
 
-
 void launch_pack_tables(hipStream_t s, Tables tab, float4* out, uint32_t spp, uint32_t depths, uint32_t n1, uint32_t n2) {
     hipLaunchKernelGGL(k_pack_tables, grid_for(spp * depths, 256), dim3(256), 0, s, tab, out, spp, depths, n1, n2);
 }
@@ -1843,25 +1842,27 @@ void launch_extend(hipStream_t s, bool count, const DScene* sc, uint32_t depth, 
     } else if (count) hipLaunchKernelGGL(k_extend<true>, grid, dim3(256), 0, s, sc, depth, q, ctl, pool, ent_obj, tun.refill_min_extend, evals);
     else hipLaunchKernelGGL(k_extend<false>, grid, dim3(256), 0, s, sc, depth, q, ctl, pool, ent_obj, tun.refill_min_extend, evals);
 }
-void launch_group_hist(hipStream_t s, uint32_t nclass, const uint8_t* ent_obj, uint32_t max_entries, const DCtl* ctl, uint8_t* grp_cnt) {
-    hipLaunchKernelGGL(k_group_hist, stride_grid(max_entries / 16, 256, STREAM_BLOCKS), dim3(256), 0, s, nclass, ent_obj, ctl, grp_cnt);
+// The bin stage of one depth: the ray queue q -> the binned queue bq, per tile object-major, insertion-ordered, bins padded to x4 (SCAN_NC_BIN counters per
+// group).  A stage reads the tile group table of its input queue and writes that of its output queue; k_tile_prefix guards cap_groups (stage 0: bit 0).
+void launch_bin_stage(hipStream_t s, const QueueTables& T, uint32_t nclass, uint32_t n_tiles, const uint32_t* q, uint32_t max_entries, uint32_t* bq,
+                      uint32_t cap_groups, uint32_t* base_hist_row, DCtl* ctl) {
+    hipLaunchKernelGGL(k_group_hist, stride_grid(max_entries / 16, 256, STREAM_BLOCKS), dim3(256), 0, s, nclass, T.ent_obj, ctl, T.grp_cnt);
+    hipLaunchKernelGGL(k_scan_tile, dim3(n_tiles), dim3(256), 0, s, nclass, SCAN_NC_BIN, 4, T.grp_cnt, T.ray_tgb, T.ray_tgc, T.grp_base, T.grp_tile, T.tile_total,
+                       T.tile_valid, T.tile_cls_cnt, ctl);
+    hipLaunchKernelGGL(k_tile_prefix, dim3(1), dim3(1024), 0, s, n_tiles, T.tile_total, T.tile_valid, T.tile_out_base, T.bin_tgb, T.bin_tgc, ctl, 0, nclass, 4,
+                       T.tile_cls_cnt, T.tile_cls_base, cap_groups, base_hist_row);
+    hipLaunchKernelGGL(k_bin_scatter, stride_grid(max_entries, 256, STREAM_BLOCKS), dim3(256), 0, s, nclass, q, T.ent_obj, T.grp_base, T.grp_tile, T.tile_out_base, ctl, bq,
+                       n_tiles, T.tile_cls_cnt, T.tile_total, T.tile_cls_base);
 }
-void launch_scan_tile(hipStream_t s, uint32_t n_tiles, uint32_t nclass, uint32_t stride, uint32_t pad, const uint8_t* grp_cnt,
-                      const uint32_t* tgb, const uint32_t* tgc, uint32_t* grp_base, uint32_t* grp_tile, uint32_t* tile_total,
-                      uint32_t* tile_valid, uint32_t* tile_cls_cnt, const DCtl* ctl) {
-    hipLaunchKernelGGL(k_scan_tile, dim3(n_tiles), dim3(256), 0, s, nclass, stride, pad, grp_cnt, tgb, tgc, grp_base, grp_tile, tile_total, tile_valid, tile_cls_cnt, ctl);
-}
-void launch_tile_prefix(hipStream_t s, uint32_t n_tiles, const uint32_t* tile_total, const uint32_t* tile_valid, uint32_t* tile_out_base,
-                        uint32_t* ogb, uint32_t* ogc, DCtl* ctl, int stage, uint32_t nclass, uint32_t pad, const uint32_t* tile_cls_cnt,
-                        uint32_t* tile_cls_base, uint32_t cap_groups, uint32_t* base_hist) {
-    hipLaunchKernelGGL(k_tile_prefix, dim3(1), dim3(1024), 0, s, n_tiles, tile_total, tile_valid, tile_out_base, ogb, ogc, ctl, stage, nclass, pad, tile_cls_cnt,
-                       tile_cls_base, cap_groups, base_hist);
-}
-void launch_bin_scatter(hipStream_t s, uint32_t nclass, const uint32_t* q, const uint8_t* ent_obj, const uint32_t* grp_base,
-                        const uint32_t* grp_tile, const uint32_t* tile_out_base, uint32_t max_entries, uint32_t* bq, uint32_t n_tiles,
-                        const uint32_t* tile_cls_cnt, const uint32_t* tile_total, const uint32_t* tile_cls_base, const DCtl* ctl) {
-    hipLaunchKernelGGL(k_bin_scatter, stride_grid(max_entries, 256, STREAM_BLOCKS), dim3(256), 0, s, nclass, q, ent_obj, grp_base, grp_tile, tile_out_base, ctl, bq,
-                       n_tiles, tile_cls_cnt, tile_total, tile_cls_base);
+// The repack stage: the survivors (T.alive, T.bgrp_cnt: k_shade_setup) of bq -> the next ray queue qn, stable.  The same two scans with one class, one
+// counter per group and no padding (stage 1: bit 1 of the overflow word, no base_hist row).
+void launch_repack_stage(hipStream_t s, const QueueTables& T, uint32_t n_tiles, const uint32_t* bq, uint32_t max_slots, uint32_t* qn, uint32_t cap_groups, DCtl* ctl) {
+    hipLaunchKernelGGL(k_scan_tile, dim3(n_tiles), dim3(256), 0, s, 1, 1, 1, T.bgrp_cnt, T.bin_tgb, T.bin_tgc, T.bgrp_base, T.bgrp_tile, T.tile_total, T.tile_valid,
+                       T.tile_cls_cnt, ctl);
+    hipLaunchKernelGGL(k_tile_prefix, dim3(1), dim3(1024), 0, s, n_tiles, T.tile_total, T.tile_valid, T.tile_out_base, T.ray_tgb, T.ray_tgc, ctl, 1, 1, 1, T.tile_cls_cnt,
+                       T.tile_cls_base, cap_groups, nullptr);
+    hipLaunchKernelGGL(k_compact_scatter, stride_grid(max_slots, 256, STREAM_BLOCKS), dim3(256), 0, s, bq, T.alive, T.bgrp_base, T.bgrp_tile, T.tile_out_base, ctl, qn, n_tiles,
+                       T.tile_total);
 }
 // the shadow-march kernel of the scene over the job list in nee / ctl (at most max_jobs entries): k_shade's second stage, and rayn_hip_probe_shadow
 void launch_shadow_march(hipStream_t s, bool count, const DScene* sc, Nee nee, uint32_t max_jobs, int single_sdf, DCtl* ctl, unsigned long long* evals, const Tuning& tun) {
@@ -1904,11 +1905,6 @@ void launch_shade(hipStream_t s, bool count, const DScene* sc, Tables tab, const
     hooks.before(2);
     hipLaunchKernelGGL(k_shade_finish, stride_grid(max_slots, 256, STREAM_BLOCKS), dim3(256), 0, s, sc, bq, ctl, pool, nee);
     hooks.after(2);
-}
-void launch_compact_scatter(hipStream_t s, const uint32_t* bq, const unsigned long long* alive_mask, const uint32_t* grp_base, const uint32_t* grp_tile,
-                            const uint32_t* tile_out_base, uint32_t max_slots, uint32_t* qn, uint32_t n_tiles, const uint32_t* tile_total,
-                            const DCtl* ctl) {
-    hipLaunchKernelGGL(k_compact_scatter, stride_grid(max_slots, 256, STREAM_BLOCKS), dim3(256), 0, s, bq, alive_mask, grp_base, grp_tile, tile_out_base, ctl, qn, n_tiles, tile_total);
 }
 void launch_unpack_tiles(hipStream_t s, const DTile* tiles, uint32_t n_tiles, uint32_t width, float* color, float* alpha, float* background,
                          float* normal, const float* packed, size_t packed_pixels) {

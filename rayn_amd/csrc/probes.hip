@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "driver.h"
+#include "frame_layout.h"
 
 using namespace rayn;
 
@@ -17,6 +18,16 @@ struct DevBuf { // hipMalloc'ed scratch of a probe call, released on every exit 
     ~DevBuf() { if (p) (void)hipFree(p); }
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 4); }
     template <typename T> T* as() const { return (T*)p; }
+};
+struct ProbeArena : Arena { // the one device allocation of a stage probe call, released on every exit path
+    ~ProbeArena() { if (base) (void)hipFree(base); }
+    template <typename F> hipError_t alloc(F carve) { // run_worker's pattern: a dry run of `carve` sizes the allocation, then the same carve hands it out
+        Arena dry; carve(dry);
+        const hipError_t e = hipMalloc((void**)&base, dry.off);
+        if (e != hipSuccess) { base = nullptr; return e; }
+        cap = dry.off; carve(*this);
+        return hipSuccess;
+    }
 };
 } // namespace
 
@@ -42,6 +53,14 @@ static int probe_counters(rayn_ctx* ctx, const unsigned long long* d_ev) {
     unsigned long long h[16];
     HIPCHK(hipMemcpy(h, d_ev, sizeof h, hipMemcpyDeviceToHost));
     ctx->counters.decode(h);
+    return RAYN_OK;
+}
+// the first n slots of a device pool into the seven host arrays of a stage probe
+static int probe_pool_out(rayn_ctx* ctx, const Pool& pool, size_t n, float* geo0, float* geo1, float* col0, float* col1, float* aov, uint32_t* term_key, uint8_t* term_info) {
+    HIPCHK(hipMemcpy(geo0, pool.geo0, n * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(geo1, pool.geo1, n * 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(col0, pool.col0, n * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(col1, pool.col1, n * 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(aov, pool.aov, n * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(term_key, pool.term_key, n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(term_info, pool.term_info, n, hipMemcpyDeviceToHost));
     return RAYN_OK;
 }
 int rayn_hip_probe_sdf_dist(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t hitable_index, const float* pts, float* out, uint32_t n) {
@@ -254,8 +273,9 @@ int rayn_hip_probe_shading(rayn_ctx* ctx, const rayn_frame_params* p, uint32_t o
     return RAYN_OK;
 }
 // The two queue stages of one depth (bin: k_group_hist, k_scan_tile, k_tile_prefix, k_bin_scatter; repack: k_scan_tile, k_tile_prefix, k_compact_scatter) on a
-// caller-built ray queue, launched with the arguments of run_worker's depth loop.  The survivor ballots and counts k_shade_setup would write between the stages
-// are built here on the host from the binned queue as the device left it.  Both output queues hold out_slots slots (>= the input's full need, whatever the
+// caller-built ray queue: the two stage launchers run_worker's depth loop calls (launch_bin_stage, launch_repack_stage) over tables from the carve function
+// its arena is carved by.  The survivor ballots and counts k_shade_setup would write between the stages are built here on the host from the binned queue as
+// the device left it.  Both output queues hold out_slots slots (>= the input's full need, whatever the
 // cap_groups arguments say) and start filled with `sentinel`, so the overflow guard runs without an address leaving its buffer and a stray write shows.
 int rayn_hip_probe_queue(rayn_ctx* ctx, uint32_t nclass, uint32_t n_tiles, const uint32_t* tile_groups, const uint32_t* q, const uint8_t* ent_obj,
                          const uint8_t* survive, uint32_t n_refs, uint32_t cap_groups_bin, uint32_t cap_groups_repack, uint32_t max_entries,
@@ -295,15 +315,15 @@ int rayn_hip_probe_queue(rayn_ctx* ctx, uint32_t nclass, uint32_t n_tiles, const
     if (out_slots < need_groups * 64) return fail(ctx, RAYN_ERR_INVALID_ARG, "out_slots is smaller than the binned queue the input needs");
     const KernelSet K = kernel_set(ctx->cfg->fma_policy);
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t QG = groups + 1, BG = out_slots / 64 + 1, NT = n_tiles;
-    DevBuf d_q, d_obj, d_bq, d_qn, d_alive, d_grp_cnt, d_grp_base, d_grp_tile, d_bgrp_cnt, d_bgrp_base, d_bgrp_tile, d_tgbA, d_tgcA, d_tgbB, d_tgcB, d_total,
-        d_valid, d_out_base, d_cls_cnt, d_cls_base, d_hist, d_ctl;
-    HIPCHK(d_q.alloc(n_entries * 4)); HIPCHK(d_obj.alloc(n_entries)); HIPCHK(d_bq.alloc((size_t)out_slots * 4)); HIPCHK(d_qn.alloc((size_t)out_slots * 4));
-    HIPCHK(d_alive.alloc(BG * 8)); HIPCHK(d_grp_cnt.alloc(QG * SCAN_NC_BIN)); HIPCHK(d_grp_base.alloc(QG * SCAN_NC_BIN * 4)); HIPCHK(d_grp_tile.alloc(QG * 4));
-    HIPCHK(d_bgrp_cnt.alloc(BG)); HIPCHK(d_bgrp_base.alloc(BG * 4)); HIPCHK(d_bgrp_tile.alloc(BG * 4));
-    HIPCHK(d_tgbA.alloc(NT * 4)); HIPCHK(d_tgcA.alloc(NT * 4)); HIPCHK(d_tgbB.alloc(NT * 4)); HIPCHK(d_tgcB.alloc(NT * 4));
-    HIPCHK(d_total.alloc(NT * 4)); HIPCHK(d_valid.alloc(NT * 4)); HIPCHK(d_out_base.alloc(NT * 4));
-    HIPCHK(d_cls_cnt.alloc(NT * SCAN_NC_BIN * 4)); HIPCHK(d_cls_base.alloc(NT * SCAN_NC_BIN * 4)); HIPCHK(d_hist.alloc(NT * 4)); HIPCHK(d_ctl.alloc(sizeof(DCtl)));
+    const size_t BG = out_slots / 64 + 1, NT = n_tiles;
+    uint32_t *d_q, *d_bq, *d_qn, *d_hist; QueueTables T; DCtl* ctl;
+    ProbeArena arena;
+    const auto carve = [&](Arena& A) {
+        d_q = A.take<uint32_t>(n_entries); d_bq = A.take<uint32_t>(out_slots); d_qn = A.take<uint32_t>(out_slots);
+        T = carve_queue_tables(A, groups + 1, BG, NT);
+        d_hist = A.take<uint32_t>(NT); ctl = A.take<DCtl>(1);
+    };
+    HIPCHK(arena.alloc(carve));
     std::vector<uint32_t> tgb(n_tiles), fill(out_slots, sentinel);
     { uint32_t g = 0; for (uint32_t k = 0; k < n_tiles; k++) { tgb[k] = g; g += tile_groups[k]; } } // back to back, as k_batch_setup lays the tiles out
     DCtl hc;
@@ -311,33 +331,23 @@ int rayn_hip_probe_queue(rayn_ctx* ctx, uint32_t nclass, uint32_t n_tiles, const
     hc.q_groups = (uint32_t)groups; hc.q_valid = (uint32_t)ctl_io[1]; hc.b_groups = (uint32_t)ctl_io[2]; hc.b_valid = (uint32_t)ctl_io[3]; hc.overflow = (uint32_t)ctl_io[4];
     hc.segments = ctl_io[5]; hc.shaded_slots = ctl_io[6]; hc.entries_sum = ctl_io[7]; hc.next_sum = ctl_io[8];
     hc.job_count = (uint32_t)ctl_io[9]; hc.head_shadow = (uint32_t)ctl_io[10]; hc.head_extend = (uint32_t)ctl_io[11];
-    HIPCHK(hipMemcpy(d_q.p, q, n_entries * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_obj.p, ent_obj, n_entries, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_bq.p, fill.data(), (size_t)out_slots * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_qn.p, fill.data(), (size_t)out_slots * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_tgbA.p, tgb.data(), NT * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_tgcA.p, tile_groups, NT * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(d_tgbB.p, 0, NT * 4)); HIPCHK(hipMemset(d_tgcB.p, 0, NT * 4)); HIPCHK(hipMemset(d_total.p, 0, NT * 4)); HIPCHK(hipMemset(d_valid.p, 0, NT * 4));
-    HIPCHK(hipMemset(d_out_base.p, 0, NT * 4)); HIPCHK(hipMemset(d_cls_cnt.p, 0, NT * SCAN_NC_BIN * 4)); HIPCHK(hipMemset(d_cls_base.p, 0, NT * SCAN_NC_BIN * 4));
-    HIPCHK(hipMemset(d_hist.p, 0, NT * 4)); HIPCHK(hipMemcpy(d_ctl.p, &hc, sizeof hc, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(arena.base, 0, arena.cap)); // the binned queue's tile group table, the per-tile tables and the base_hist row start as zero
+    HIPCHK(hipMemcpy(d_q, q, n_entries * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(T.ent_obj, ent_obj, n_entries, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_bq, fill.data(), (size_t)out_slots * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_qn, fill.data(), (size_t)out_slots * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(T.ray_tgb, tgb.data(), NT * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(T.ray_tgc, tile_groups, NT * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctl, &hc, sizeof hc, hipMemcpyHostToDevice));
     HIPCHK(hipDeviceSynchronize()); // the fills above ran on the null stream
     hipStream_t s = ctx->stream;
-    DCtl* ctl = d_ctl.as<DCtl>();
-    uint32_t *tgbA = d_tgbA.as<uint32_t>(), *tgcA = d_tgcA.as<uint32_t>(), *tgbB = d_tgbB.as<uint32_t>(), *tgcB = d_tgcB.as<uint32_t>();
-    uint32_t *tile_total = d_total.as<uint32_t>(), *tile_valid = d_valid.as<uint32_t>(), *tile_out_base = d_out_base.as<uint32_t>();
-    uint32_t *tile_cls_cnt = d_cls_cnt.as<uint32_t>(), *tile_cls_base = d_cls_base.as<uint32_t>();
-    // stage 0: bin
-    K.group_hist(s, nclass, d_obj.as<uint8_t>(), max_entries, ctl, d_grp_cnt.as<uint8_t>());
-    K.scan_tile(s, n_tiles, nclass, SCAN_NC_BIN, 4, d_grp_cnt.as<uint8_t>(), tgbA, tgcA, d_grp_base.as<uint32_t>(), d_grp_tile.as<uint32_t>(), tile_total, tile_valid, tile_cls_cnt, ctl);
-    K.tile_prefix(s, n_tiles, tile_total, tile_valid, tile_out_base, tgbB, tgcB, ctl, 0, nclass, 4, tile_cls_cnt, tile_cls_base, cap_groups_bin, d_hist.as<uint32_t>());
-    K.bin_scatter(s, nclass, d_q.as<uint32_t>(), d_obj.as<uint8_t>(), d_grp_base.as<uint32_t>(), d_grp_tile.as<uint32_t>(), tile_out_base, max_entries, d_bq.as<uint32_t>(), n_tiles,
-                  tile_cls_cnt, tile_total, tile_cls_base, ctl);
+    K.bin_stage(s, T, nclass, n_tiles, d_q, max_entries, d_bq, cap_groups_bin, d_hist, ctl);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     std::vector<uint32_t> tmp(n_tiles);
-    HIPCHK(hipMemcpy(&hc, d_ctl.p, sizeof hc, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_bq, d_bq.p, (size_t)out_slots * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_cls_cnt, d_cls_cnt.p, NT * SCAN_NC_BIN * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_cls_base, d_cls_base.p, NT * SCAN_NC_BIN * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(tmp.data(), d_tgbB.p, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k] = tmp[k];
-    HIPCHK(hipMemcpy(tmp.data(), d_tgcB.p, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k + 1] = tmp[k];
-    HIPCHK(hipMemcpy(tmp.data(), d_hist.p, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k + 4] = tmp[k];
+    HIPCHK(hipMemcpy(&hc, ctl, sizeof hc, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_bq, d_bq, (size_t)out_slots * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_cls_cnt, T.tile_cls_cnt, NT * SCAN_NC_BIN * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_cls_base, T.tile_cls_base, NT * SCAN_NC_BIN * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tmp.data(), T.bin_tgb, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k] = tmp[k];
+    HIPCHK(hipMemcpy(tmp.data(), T.bin_tgc, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k + 1] = tmp[k];
+    HIPCHK(hipMemcpy(tmp.data(), d_hist, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k + 4] = tmp[k];
     if ((size_t)hc.b_groups * 64 > out_slots) return fail(ctx, RAYN_ERR_HIP, "internal: the bin stage reports a binned queue larger than the input's full need");
     // what k_shade_setup would leave: one survivor ballot and one survivor count per binned group
     std::vector<unsigned long long> alive(BG, 0ull);
@@ -350,18 +360,14 @@ int rayn_hip_probe_queue(rayn_ctx* ctx, uint32_t nclass, uint32_t n_tiles, const
         }
         alive[g] = m; bcnt[g] = (uint8_t)__builtin_popcountll(m);
     }
-    HIPCHK(hipMemcpy(d_alive.p, alive.data(), BG * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_bgrp_cnt.p, bcnt.data(), BG, hipMemcpyHostToDevice));
-    // stage 1: repack
-    K.scan_tile(s, n_tiles, 1, 1, 1, d_bgrp_cnt.as<uint8_t>(), tgbB, tgcB, d_bgrp_base.as<uint32_t>(), d_bgrp_tile.as<uint32_t>(), tile_total, tile_valid, tile_cls_cnt, ctl);
-    K.tile_prefix(s, n_tiles, tile_total, tile_valid, tile_out_base, tgbA, tgcA, ctl, 1, 1, 1, tile_cls_cnt, tile_cls_base, cap_groups_repack, nullptr);
-    K.compact_scatter(s, d_bq.as<uint32_t>(), d_alive.as<unsigned long long>(), d_bgrp_base.as<uint32_t>(), d_bgrp_tile.as<uint32_t>(), tile_out_base, max_slots, d_qn.as<uint32_t>(),
-                      n_tiles, tile_total, ctl);
+    HIPCHK(hipMemcpy(T.alive, alive.data(), BG * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(T.bgrp_cnt, bcnt.data(), BG, hipMemcpyHostToDevice));
+    K.repack_stage(s, T, n_tiles, d_bq, max_slots, d_qn, cap_groups_repack, ctl);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(&hc, d_ctl.p, sizeof hc, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_qn, d_qn.p, (size_t)out_slots * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(tmp.data(), d_tgbA.p, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k + 2] = tmp[k];
-    HIPCHK(hipMemcpy(tmp.data(), d_tgcA.p, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k + 3] = tmp[k];
+    HIPCHK(hipMemcpy(&hc, ctl, sizeof hc, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_qn, d_qn, (size_t)out_slots * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tmp.data(), T.ray_tgb, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k + 2] = tmp[k];
+    HIPCHK(hipMemcpy(tmp.data(), T.ray_tgc, NT * 4, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < n_tiles; k++) out_tile[5 * (size_t)k + 3] = tmp[k];
     const uint64_t fin[12] = {hc.q_groups, hc.q_valid, hc.b_groups, hc.b_valid, hc.overflow, hc.segments, hc.shaded_slots, hc.entries_sum, hc.next_sum,
                               hc.job_count, hc.head_shadow, hc.head_extend};
     memcpy(ctl_io, fin, sizeof fin);
@@ -373,9 +379,9 @@ int rayn_hip_probe_shade_limits(const rayn_ctx* ctx, uint32_t* stream_blocks, ui
     *stream_blocks = STREAM_BLOCKS; *list_ids_per_block = 256 * SCAN_ITEMS; *setup_threads = SHADE_SETUP_THREADS;
     return RAYN_OK;
 }
-// The shade stage of ONE depth through launch_shade (k_shade_setup, k_shadow_list, the scene's shadow-march kernel, k_shade_finish), launched with the
-// arguments of run_worker's depth loop, on a caller-built binned queue and pool.  The probe owns every device buffer: the pool, the NEE records, the
-// survivor ballots and the control block; what the kernels must not read before they write it starts as the worst stale value (header: rayn_hip.h).
+// The shade stage of ONE depth through launch_shade (k_shade_setup, k_shadow_list, the scene's shadow-march kernel, k_shade_finish) on a caller-built binned
+// queue and pool; the pool and the NEE records come from the carve functions run_worker's arena is carved by (frame_layout.h).  The probe owns every device
+// buffer: the pool, the NEE records, the survivor ballots and the control block; what the kernels must not read before they write it starts as the worst stale value (header: rayn_hip.h).
 // Everything the kernels would index is checked here first, and so are their preconditions.
 int rayn_hip_probe_shade(rayn_ctx* ctx, const rayn_frame_params* p, const float* samples_1d, const float* samples_2d, const float* scramble, const float* fis_table,
                          uint32_t depth, uint32_t n_slots, uint32_t max_slots, uint32_t nee_cap, const uint32_t* ref, uint32_t n_pool, const float* geo0,
@@ -392,10 +398,8 @@ int rayn_hip_probe_shade(rayn_ctx* ctx, const rayn_frame_params* p, const float*
     if (depth > p->max_bounces) return fail(ctx, RAYN_ERR_INVALID_ARG, "depth above max_bounces (the packed sample records end there)");
     if (n_pool == 0 || n_pool > (1u << 27) || max_slots > (1u << 27)) return fail(ctx, RAYN_ERR_INVALID_ARG, "probe size out of range");
     const rayn_world_desc& w = ctx->cfg->world;
-    const uint32_t NS = 4 + (w.has_scattering ? 4 * p->volume_marches : 0); // NEE samples per shading point, as render_device counts them
-    // 32-bit [sample][slot] ids, and k_shadow_list's grid-stride counter must not wrap (run_worker's check, on the probe's strides)
-    const uint64_t id_limit = ((uint64_t)1 << 32) - ((uint64_t)1 << 26);
-    if ((uint64_t)NS * nee_cap > id_limit || (uint64_t)NS * max_slots > id_limit)
+    const uint32_t NS = nee_samples(w.has_scattering, p->volume_marches);
+    if (!queue_ids_fit(NS, nee_cap) || !queue_ids_fit(NS, max_slots)) // run_worker's check, on the probe's strides
         return fail(ctx, RAYN_ERR_INVALID_ARG, "ns * nee_cap or ns * max_slots does not fit the 32-bit [sample][slot] ids");
     const uint32_t spp = p->samples * 4;
     const uint64_t n_pixels = (uint64_t)p->width * p->height;
@@ -430,58 +434,48 @@ int rayn_hip_probe_shade(rayn_ctx* ctx, const rayn_frame_params* p, const float*
     const int single_sdf = scene_march_kernels(ctx, hs, *p, &tun);
     const KernelSet K = kernel_set(ctx->cfg->fma_policy);
     const size_t n1 = (size_t)spp * rayn_sets_1d(p->max_bounces, p->volume_marches), n2 = (size_t)spp * 2 * rayn_sets_2d(p->max_bounces, p->volume_marches);
-    const uint32_t rec_stride = (8 + hs.n2) / 4, rec_depths = p->max_bounces + 1;
-    const size_t rec_n = (size_t)rec_depths * spp * rec_stride;
-    const size_t CAP = nee_cap, JOBCAP = (size_t)NS * CAP, NV = NS - 4 + 1, G = n_slots / 64, NP = n_pool;
-    DevBuf d_s1, d_s2, d_scr, d_fis, d_rec, d_bq, d_g0, d_g1, d_c0, d_c1, d_aov, d_key, d_info, d_alive, d_cnt, d_ctl, d_ev;
-    DevBuf d_x, d_vtr, d_pdf, d_aux, d_vis, d_picks, d_T, d_t0, d_nthr, d_flags, d_jref, d_jgeo;
-#define OOMCHK(expr) do { if ((expr) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAYN_ERR_OOM, "hipMalloc of the shade probe's buffers failed"); } } while (0)
-    OOMCHK(d_s1.alloc(n1 * 4)); OOMCHK(d_s2.alloc(n2 * 4)); OOMCHK(d_scr.alloc(n_pixels * 4)); OOMCHK(d_fis.alloc(RAYN_FIS_TABLE_SIZE * 4)); OOMCHK(d_rec.alloc(rec_n * 16));
-    OOMCHK(d_bq.alloc((size_t)n_slots * 4)); OOMCHK(d_g0.alloc(NP * 16)); OOMCHK(d_g1.alloc(NP * 16)); OOMCHK(d_c0.alloc(NP * 16)); OOMCHK(d_c1.alloc(NP * 16));
-    OOMCHK(d_aov.alloc(NP * 16)); OOMCHK(d_key.alloc(NP * 4)); OOMCHK(d_info.alloc(NP)); OOMCHK(d_alive.alloc(G * 8)); OOMCHK(d_cnt.alloc(G));
-    OOMCHK(d_ctl.alloc(sizeof(DCtl))); OOMCHK(d_ev.alloc(128));
-    OOMCHK(d_x.alloc(12 * CAP * 4)); OOMCHK(d_vtr.alloc(NV * CAP * 4)); OOMCHK(d_pdf.alloc(NS * CAP * 4)); OOMCHK(d_aux.alloc(NV * CAP * 4)); OOMCHK(d_vis.alloc(NS * CAP));
-    OOMCHK(d_picks.alloc(CAP * 8)); OOMCHK(d_T.alloc(CAP * 4)); OOMCHK(d_t0.alloc(CAP * 4)); OOMCHK(d_nthr.alloc(3 * CAP * 4)); OOMCHK(d_flags.alloc(CAP));
-    OOMCHK(d_jref.alloc(JOBCAP * 4)); OOMCHK(d_jgeo.alloc(3 * JOBCAP * 8));
-#undef OOMCHK
+    const RecordLayout rec(hs.n2, p->max_bounces);
+    const size_t CAP = nee_cap, NV = NS - 4 + 1, G = n_slots / 64, NP = n_pool;
+    float *d_s1, *d_s2, *d_scr, *d_fis; float4* d_rec; uint32_t* d_bq; Pool pool; Nee nee; unsigned long long *d_alive, *d_ev; uint8_t* d_cnt; DCtl* d_ctl;
+    ProbeArena arena;
+    const auto carve = [&](Arena& A) {
+        d_s1 = A.take<float>(n1); d_s2 = A.take<float>(n2); d_scr = A.take<float>(n_pixels); d_fis = A.take<float>(RAYN_FIS_TABLE_SIZE);
+        d_rec = A.take<float4>(rec.count(spp)); d_bq = A.take<uint32_t>(n_slots);
+        pool = carve_pool(A, NP); nee = carve_nee(A, NS, CAP);
+        d_alive = A.take<unsigned long long>(G); d_cnt = A.take<uint8_t>(G); d_ctl = A.take<DCtl>(1); d_ev = A.take<unsigned long long>(16);
+    };
+    if (arena.alloc(carve) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAYN_ERR_OOM, "hipMalloc of the shade probe's buffers failed"); }
     // the float planes of the NEE records, in the order the guard below walks them
-    struct Plane { DevBuf* b; size_t planes; } fplanes[] = {{&d_x, 12}, {&d_vtr, NV}, {&d_pdf, NS}, {&d_aux, NV}, {&d_T, 1}, {&d_t0, 1}, {&d_nthr, 3}};
+    const struct Plane { float* p; size_t planes; } fplanes[] = {{nee.x, 12}, {nee.vtr, NV}, {nee.pdf, NS}, {nee.aux, NV}, {nee.T, 1}, {nee.t0, 1}, {nee.nthr, 3}};
     hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpy(d_s1.p, samples_1d, n1 * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_s2.p, samples_2d, n2 * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_scr.p, scramble, n_pixels * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_fis.p, fis_table, RAYN_FIS_TABLE_SIZE * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_bq.p, ref, (size_t)n_slots * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_g0.p, geo0, NP * 16, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_g1.p, geo1, NP * 16, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_c0.p, col0, NP * 16, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_c1.p, col1, NP * 16, hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetD32((hipDeviceptr_t)d_aov.p, (int)sentinel, NP * 4)); HIPCHK(hipMemsetD32((hipDeviceptr_t)d_key.p, (int)sentinel, NP));
-    HIPCHK(hipMemset(d_info.p, (int)TERM_NONE, NP));
-    for (const Plane& pl : fplanes) HIPCHK(hipMemsetD32((hipDeviceptr_t)pl.b->p, (int)sentinel, pl.planes * CAP));
-    HIPCHK(hipMemset(d_vis.p, 2, NS * CAP)); // "march pending" everywhere: a (sample, slot) the setup forgets becomes a job and an occluded sample
-    HIPCHK(hipMemset(d_picks.p, 0xFF, CAP * 8)); HIPCHK(hipMemset(d_flags.p, 0xFF, CAP));
-    HIPCHK(hipMemset(d_jref.p, 0xFF, JOBCAP * 4)); HIPCHK(hipMemset(d_jgeo.p, 0, 3 * JOBCAP * 8));
-    HIPCHK(hipMemset(d_alive.p, 0xA5, G * 8)); HIPCHK(hipMemset(d_cnt.p, 0xA5, G)); HIPCHK(hipMemset(d_ev.p, 0, 128));
+    HIPCHK(hipMemcpy(d_s1, samples_1d, n1 * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_s2, samples_2d, n2 * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_scr, scramble, n_pixels * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_fis, fis_table, RAYN_FIS_TABLE_SIZE * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_bq, ref, (size_t)n_slots * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(pool.geo0, geo0, NP * 16, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(pool.geo1, geo1, NP * 16, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(pool.col0, col0, NP * 16, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(pool.col1, col1, NP * 16, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetD32((hipDeviceptr_t)pool.aov, (int)sentinel, NP * 4)); HIPCHK(hipMemsetD32((hipDeviceptr_t)pool.term_key, (int)sentinel, NP));
+    HIPCHK(hipMemset(pool.term_info, (int)TERM_NONE, NP));
+    for (const Plane& pl : fplanes) HIPCHK(hipMemsetD32((hipDeviceptr_t)pl.p, (int)sentinel, pl.planes * CAP));
+    HIPCHK(hipMemset(nee.vis, 2, NS * CAP)); // "march pending" everywhere: a (sample, slot) the setup forgets becomes a job and an occluded sample
+    HIPCHK(hipMemset(nee.vpicks, 0xFF, CAP * 8)); HIPCHK(hipMemset(nee.flags, 0xFF, CAP));
+    HIPCHK(hipMemset(nee.job_ref, 0xFF, nee.jobcap * 4)); HIPCHK(hipMemset(nee.job_geo, 0, 3 * nee.jobcap * 8));
+    HIPCHK(hipMemset(d_alive, 0xA5, G * 8)); HIPCHK(hipMemset(d_cnt, 0xA5, G)); HIPCHK(hipMemset(d_ev, 0, 128));
     DCtl hc;
     memset(&hc, 0, sizeof hc);
     hc.b_groups = (uint32_t)G;
     for (uint32_t k = 0; k < n_slots; k++) hc.b_valid += ref[k] != INVALID;
-    HIPCHK(hipMemcpy(d_ctl.p, &hc, sizeof hc, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_ctl, &hc, sizeof hc, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(ctx->d_scene, &hs, sizeof hs, hipMemcpyHostToDevice));
     HIPCHK(hipDeviceSynchronize()); // the fills above ran on the null stream
-    const Tables tab{d_s1.as<float>(), d_s2.as<float>(), d_fis.as<float>(), d_rec.as<float4>(), rec_stride};
-    K.pack_tables(s, tab, d_rec.as<float4>(), spp, rec_depths, hs.n1, hs.n2);
-    Pool pool;
-    pool.geo0 = d_g0.as<float4>(); pool.geo1 = d_g1.as<float4>(); pool.col0 = d_c0.as<float4>(); pool.col1 = d_c1.as<float4>(); pool.aov = d_aov.as<float4>();
-    pool.term_key = d_key.as<uint32_t>(); pool.term_info = d_info.as<uint8_t>();
-    Nee nee;
-    nee.x = d_x.as<float>(); nee.vtr = d_vtr.as<float>(); nee.pdf = d_pdf.as<float>(); nee.aux = d_aux.as<float>(); nee.vis = d_vis.as<uint8_t>();
-    nee.vpicks = d_picks.as<unsigned long long>(); nee.T = d_T.as<float>(); nee.t0 = d_t0.as<float>(); nee.nthr = d_nthr.as<float>(); nee.flags = d_flags.as<uint8_t>();
-    nee.cap = CAP; nee.job_ref = d_jref.as<uint32_t>(); nee.job_geo = d_jgeo.as<float2>(); nee.jobcap = JOBCAP;
+    const Tables tab{d_s1, d_s2, d_fis, d_rec, rec.stride};
+    K.pack_tables(s, tab, d_rec, spp, rec.depths, hs.n1, hs.n2);
     const bool count = ctx->cfg->counting; // the instrumented instantiations; the context's counters then report this call
-    K.shade(s, count, ctx->d_scene, tab, d_scr.as<float>(), depth, d_bq.as<uint32_t>(), max_slots, pool, nee, NS, hs.n_sdf > 0, single_sdf,
-            d_alive.as<unsigned long long>(), d_cnt.as<uint8_t>(), d_ctl.as<DCtl>(), d_ev.as<unsigned long long>(), ShadeHooks{nullptr, nullptr, nullptr}, tun);
+    K.shade(s, count, ctx->d_scene, tab, d_scr, depth, d_bq, max_slots, pool, nee, NS, hs.n_sdf > 0, single_sdf, d_alive, d_cnt, d_ctl, d_ev,
+            ShadeHooks{nullptr, nullptr, nullptr}, tun);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
-    if (count) { rc = probe_counters(ctx, d_ev.as<unsigned long long>()); if (rc) return rc; }
-    HIPCHK(hipMemcpy(&hc, d_ctl.p, sizeof hc, hipMemcpyDeviceToHost));
+    if (count) { rc = probe_counters(ctx, d_ev); if (rc) return rc; }
+    HIPCHK(hipMemcpy(&hc, d_ctl, sizeof hc, hipMemcpyDeviceToHost));
     if ((uint64_t)hc.job_count > (uint64_t)NS * n_slots) return fail(ctx, RAYN_ERR_HIP, "internal: job_count exceeds ns * n_slots");
     if (CAP > n_slots) { // the surplus of every NEE plane: no word at a slot index in [n_slots, nee_cap) may have changed
         const size_t extra = CAP - n_slots;
@@ -489,24 +483,21 @@ int rayn_hip_probe_shade(rayn_ctx* ctx, const rayn_frame_params* p, const float*
         std::vector<uint8_t> bytes(extra);
         for (const Plane& pl : fplanes)
             for (size_t k = 0; k < pl.planes; k++) {
-                HIPCHK(hipMemcpy(words.data(), (const uint32_t*)pl.b->p + k * CAP + n_slots, extra * 4, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(words.data(), pl.p + k * CAP + n_slots, extra * 4, hipMemcpyDeviceToHost));
                 for (uint32_t v : words) if (v != sentinel) return fail(ctx, RAYN_ERR_HIP, "internal: a float plane of the NEE records was written at a slot index in [n_slots, nee_cap)");
             }
         for (size_t k = 0; k < NS; k++) {
-            HIPCHK(hipMemcpy(bytes.data(), (const uint8_t*)d_vis.p + k * CAP + n_slots, extra, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(bytes.data(), nee.vis + k * CAP + n_slots, extra, hipMemcpyDeviceToHost));
             for (uint8_t v : bytes) if (v != 2) return fail(ctx, RAYN_ERR_HIP, "internal: the visibility plane was written at a slot index in [n_slots, nee_cap)");
         }
-        HIPCHK(hipMemcpy(bytes.data(), (const uint8_t*)d_flags.p + n_slots, extra, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(bytes.data(), nee.flags + n_slots, extra, hipMemcpyDeviceToHost));
         for (uint8_t v : bytes) if (v != 0xFF) return fail(ctx, RAYN_ERR_HIP, "internal: the flag plane was written at a slot index in [n_slots, nee_cap)");
         std::vector<unsigned long long> picks(extra);
-        HIPCHK(hipMemcpy(picks.data(), (const unsigned long long*)d_picks.p + n_slots, extra * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(picks.data(), nee.vpicks + n_slots, extra * 8, hipMemcpyDeviceToHost));
         for (unsigned long long v : picks) if (v != ~0ull) return fail(ctx, RAYN_ERR_HIP, "internal: the volume picks were written at a slot index in [n_slots, nee_cap)");
     }
-    HIPCHK(hipMemcpy(out_geo0, d_g0.p, NP * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_geo1, d_g1.p, NP * 16, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_col0, d_c0.p, NP * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_col1, d_c1.p, NP * 16, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_aov, d_aov.p, NP * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_term_key, d_key.p, NP * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_term_info, d_info.p, NP, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_alive_mask, d_alive.p, G * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_bgrp_cnt, d_cnt.p, G, hipMemcpyDeviceToHost));
+    if ((rc = probe_pool_out(ctx, pool, NP, out_geo0, out_geo1, out_col0, out_col1, out_aov, out_term_key, out_term_info))) return rc;
+    HIPCHK(hipMemcpy(out_alive_mask, d_alive, G * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_bgrp_cnt, d_cnt, G, hipMemcpyDeviceToHost));
     out_jobs[0] = hc.job_count; out_jobs[1] = hc.shadow_jobs;
     // the shadow-march kernel launch_shadow_march launched, by the decision it shares with this probe (kernels.h); 0: launch_shade skips the march without a TracedSDF
     out_jobs[2] = hs.n_sdf == 0 ? 0 : (uint64_t)shadow_march_kernel(single_sdf, tun);
@@ -599,8 +590,8 @@ int rayn_hip_probe_resolve(rayn_ctx* ctx, uint32_t width, uint32_t spp, uint32_t
     return RAYN_OK;
 }
 
-// The ray-generation stage (k_pack_tables, k_batch_setup, k_raygen) through the product launchers, as run_worker and prepare_frame launch them, on caller-built
-// tables and a caller-built tile list.  The probe owns every device buffer; every output buffer starts filled with `sentinel` (term_info with its low byte)
+// The ray-generation stage (k_pack_tables, k_batch_setup, k_raygen) through the product launchers, with the pool and the record geometry of frame_layout.h, on
+// caller-built tables and a caller-built tile list.  The probe owns every device buffer; every output buffer starts filled with `sentinel` (term_info with its low byte)
 // and is `surplus` slots longer than the pool (the group tables surplus / 64 words, the tile tables 2 words, the records 64 floats), so a write beyond the
 // pool, into a padding slot or into term_key shows.  Everything the kernels would index is checked here first (rayn_hip.h lists it).
 int rayn_hip_probe_raygen(rayn_ctx* ctx, const rayn_frame_params* p, const float* samples_1d, uint64_t n_samples_1d, const float* samples_2d, uint64_t n_samples_2d,
@@ -651,44 +642,38 @@ int rayn_hip_probe_raygen(rayn_ctx* ctx, const rayn_frame_params* p, const float
     rc = build_scene(ctx, ctx->cfg->world, *p, &hs);
     if (rc) return rc;
     const KernelSet K = kernel_set(ctx->cfg->fma_policy);
-    const uint32_t rec_stride = (8 + hs.n2) / 4, rec_depths = p->max_bounces + 1;
-    const size_t rec_words = (size_t)rec_depths * spp * rec_stride * 4 + 64;
-    const size_t NP = (size_t)n_pool + surplus, NG = NP / 64, NT = (size_t)n_tiles + 2;
-    DevBuf d_s1, d_s2, d_scr, d_fis, d_rec, d_tiles, d_g0, d_g1, d_c0, d_c1, d_aov, d_key, d_info, d_q, d_pgrp, d_tgb, d_tgc, d_ctl;
-#define OOMCHK(expr) do { if ((expr) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAYN_ERR_OOM, "hipMalloc of the ray-gen probe's buffers failed"); } } while (0)
-    OOMCHK(d_s1.alloc(n1 * 4)); OOMCHK(d_s2.alloc(n2 * 4)); OOMCHK(d_scr.alloc(n_pixels * 4)); OOMCHK(d_fis.alloc(RAYN_FIS_TABLE_SIZE * 4)); OOMCHK(d_rec.alloc(rec_words * 4));
-    OOMCHK(d_tiles.alloc((size_t)n_tiles * sizeof(DTile))); OOMCHK(d_g0.alloc(NP * 16)); OOMCHK(d_g1.alloc(NP * 16)); OOMCHK(d_c0.alloc(NP * 16)); OOMCHK(d_c1.alloc(NP * 16));
-    OOMCHK(d_aov.alloc(NP * 16)); OOMCHK(d_key.alloc(NP * 4)); OOMCHK(d_info.alloc(NP)); OOMCHK(d_q.alloc(NP * 4)); OOMCHK(d_pgrp.alloc(NG * 4));
-    OOMCHK(d_tgb.alloc(NT * 4)); OOMCHK(d_tgc.alloc(NT * 4)); OOMCHK(d_ctl.alloc(sizeof(DCtl)));
-#undef OOMCHK
-    HIPCHK(hipMemcpy(d_s1.p, samples_1d, n1 * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_s2.p, samples_2d, n2 * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_scr.p, scramble, n_pixels * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_fis.p, fis_table, RAYN_FIS_TABLE_SIZE * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_tiles.p, ht.data(), (size_t)n_tiles * sizeof(DTile), hipMemcpyHostToDevice));
-    struct Fill { DevBuf* b; size_t words; } fills[] = {{&d_rec, rec_words}, {&d_g0, NP * 4}, {&d_g1, NP * 4}, {&d_c0, NP * 4}, {&d_c1, NP * 4}, {&d_aov, NP * 4}, {&d_key, NP},
-                                                        {&d_q, NP}, {&d_pgrp, NG}, {&d_tgb, NT}, {&d_tgc, NT}, {&d_ctl, sizeof(DCtl) / 4}};
-    for (const Fill& f : fills) HIPCHK(hipMemsetD32((hipDeviceptr_t)f.b->p, (int)sentinel, f.words));
-    HIPCHK(hipMemset(d_info.p, (int)(sentinel & 0xFFu), NP));
+    const RecordLayout rec(hs.n2, p->max_bounces);
+    const size_t rec_words = rec.count(spp) * 4 + 64, NP = (size_t)n_pool + surplus, NG = NP / 64, NT = (size_t)n_tiles + 2;
+    float *d_s1, *d_s2, *d_scr, *d_fis, *d_rec; DTile* d_tiles; Pool pool; uint32_t *d_q, *d_pgrp, *d_tgb, *d_tgc; DCtl* d_ctl;
+    ProbeArena arena;
+    const auto carve = [&](Arena& A) {
+        d_s1 = A.take<float>(n1); d_s2 = A.take<float>(n2); d_scr = A.take<float>(n_pixels); d_fis = A.take<float>(RAYN_FIS_TABLE_SIZE);
+        d_rec = A.take<float>(rec_words); d_tiles = A.take<DTile>(n_tiles); pool = carve_pool(A, NP);
+        d_q = A.take<uint32_t>(NP); d_pgrp = A.take<uint32_t>(NG); d_tgb = A.take<uint32_t>(NT); d_tgc = A.take<uint32_t>(NT); d_ctl = A.take<DCtl>(1);
+    };
+    if (arena.alloc(carve) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RAYN_ERR_OOM, "hipMalloc of the ray-gen probe's buffers failed"); }
+    HIPCHK(hipMemcpy(d_s1, samples_1d, n1 * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_s2, samples_2d, n2 * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_scr, scramble, n_pixels * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_fis, fis_table, RAYN_FIS_TABLE_SIZE * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_tiles, ht.data(), (size_t)n_tiles * sizeof(DTile), hipMemcpyHostToDevice));
+    const struct Fill { void* p; size_t words; } fills[] = {{d_rec, rec_words}, {pool.geo0, NP * 4}, {pool.geo1, NP * 4}, {pool.col0, NP * 4}, {pool.col1, NP * 4},
+                                                            {pool.aov, NP * 4}, {pool.term_key, NP}, {d_q, NP}, {d_pgrp, NG}, {d_tgb, NT}, {d_tgc, NT}, {d_ctl, sizeof(DCtl) / 4}};
+    for (const Fill& f : fills) HIPCHK(hipMemsetD32((hipDeviceptr_t)f.p, (int)sentinel, f.words));
+    HIPCHK(hipMemset(pool.term_info, (int)(sentinel & 0xFFu), NP));
     HIPCHK(hipMemcpy(ctx->d_scene, &hs, sizeof hs, hipMemcpyHostToDevice));
     HIPCHK(hipDeviceSynchronize()); // the fills above ran on the null stream
     hipStream_t s = ctx->stream;
-    const Tables tab{d_s1.as<float>(), d_s2.as<float>(), d_fis.as<float>(), d_rec.as<float4>(), rec_stride};
-    K.pack_tables(s, tab, d_rec.as<float4>(), spp, rec_depths, hs.n1, hs.n2);
-    Pool pool;
-    pool.geo0 = d_g0.as<float4>(); pool.geo1 = d_g1.as<float4>(); pool.col0 = d_c0.as<float4>(); pool.col1 = d_c1.as<float4>(); pool.aov = d_aov.as<float4>();
-    pool.term_key = d_key.as<uint32_t>(); pool.term_info = d_info.as<uint8_t>();
-    K.batch_setup(s, d_tiles.as<DTile>(), n_tiles, d_pgrp.as<uint32_t>(), d_tgb.as<uint32_t>(), d_tgc.as<uint32_t>());
-    K.raygen(s, ctx->d_scene, tab, d_scr.as<float>(), d_tiles.as<DTile>(), d_pgrp.as<uint32_t>(), pool, d_q.as<uint32_t>(), n_pool, d_ctl.as<DCtl>());
+    const Tables tab{d_s1, d_s2, d_fis, (float4*)d_rec, rec.stride};
+    K.pack_tables(s, tab, (float4*)d_rec, spp, rec.depths, hs.n1, hs.n2);
+    K.batch_setup(s, d_tiles, n_tiles, d_pgrp, d_tgb, d_tgc);
+    K.raygen(s, ctx->d_scene, tab, d_scr, d_tiles, d_pgrp, pool, d_q, n_pool, d_ctl);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out_geo0, d_g0.p, NP * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_geo1, d_g1.p, NP * 16, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_col0, d_c0.p, NP * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_col1, d_c1.p, NP * 16, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_aov, d_aov.p, NP * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_term_key, d_key.p, NP * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_term_info, d_info.p, NP, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_q, d_q.p, NP * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_pgrp_tile, d_pgrp.p, NG * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_tgb, d_tgb.p, NT * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_tgc, d_tgc.p, NT * 4, hipMemcpyDeviceToHost));
+    if ((rc = probe_pool_out(ctx, pool, NP, out_geo0, out_geo1, out_col0, out_col1, out_aov, out_term_key, out_term_info))) return rc;
+    HIPCHK(hipMemcpy(out_q, d_q, NP * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_pgrp_tile, d_pgrp, NG * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_tgb, d_tgb, NT * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_tgc, d_tgc, NT * 4, hipMemcpyDeviceToHost));
     static_assert(sizeof(DCtl) >= 32, "the eight 32-bit words of DCtl");
-    HIPCHK(hipMemcpy(out_ctl, d_ctl.p, 32, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_records, d_rec.p, rec_words * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_ctl, d_ctl, 32, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_records, d_rec, rec_words * 4, hipMemcpyDeviceToHost));
     return RAYN_OK;
 }
 

@@ -19,6 +19,7 @@
 #include "../../include/rayn_detmath.h"
 #include "../../include/rayn_hip.h"
 #include "driver.h"
+#include "frame_layout.h"
 #include "tiles.h"
 #include "save_to.h"
 #include "display.h"
@@ -280,49 +281,6 @@ Plan make_plan(const std::vector<BatchTile>& mine, size_t cap_paths) { // a work
     return P;
 }
 
-// ---- device memory: one arena carved for the largest batch of a plan
-struct Layout {
-    size_t CAP = 0, QCAP = 0, BCAP = 0, JOBCAP = 0;
-    Pool pool; uint32_t *q, *qn, *bq; uint8_t* ent_obj; unsigned long long* alive;
-    uint8_t* grp_cnt; uint32_t *grp_base, *grp_tile; uint8_t* bgrp_cnt; uint32_t *bgrp_base, *bgrp_tile;
-    DTile* d_all_tiles; uint32_t* pgrp_tile;
-    uint32_t *tgbA, *tgcA, *tgbB, *tgcB, *tile_total, *tile_valid, *tile_out_base, *tile_cls_cnt, *tile_cls_base;
-    uint32_t* base_hist; size_t hist_stride; // [max_bounces + 1][max_tiles]: where each tile's binned segment began at every depth (film resolve keys)
-    Nee nee;
-};
-// binned slots of a batch of CAP pool slots in max_tiles tiles (x4 bin padding + tails)
-size_t binned_cap(size_t CAP, size_t max_tiles) { return CAP + max_tiles * (SCAN_NC_BIN * 3 + 64); }
-// carves the arena for batches of <= CAP pool slots in <= max_tiles tiles of a share of total_tiles tiles (NS NEE samples per shading point); returns the bytes
-// taken.  On an Arena without memory only A.off advances: that sizes the allocation.
-size_t carve(Arena& A, size_t CAP, size_t max_tiles, size_t total_tiles, uint32_t NS, uint32_t max_bounces, Layout* L) {
-    L->CAP = CAP;
-    L->QCAP = CAP + max_tiles * 64;                      // ray queue slots (tile tails)
-    L->BCAP = binned_cap(CAP, max_tiles);
-    L->JOBCAP = (size_t)NS * L->BCAP;
-    const size_t QCAP = L->QCAP, BCAP = L->BCAP, JOBCAP = L->JOBCAP, QG = QCAP / 64 + 1, BG = BCAP / 64 + 1;
-    A.off = 0;
-    Pool& pool = L->pool;
-    pool.geo0 = A.take<float4>(CAP); pool.geo1 = A.take<float4>(CAP); pool.col0 = A.take<float4>(CAP); pool.col1 = A.take<float4>(CAP);
-    pool.aov = A.take<float4>(CAP); pool.term_key = A.take<uint32_t>(CAP); pool.term_info = A.take<uint8_t>(CAP);
-    L->q = A.take<uint32_t>(QCAP); L->qn = A.take<uint32_t>(QCAP); L->bq = A.take<uint32_t>(BCAP);
-    L->ent_obj = A.take<uint8_t>(QCAP); L->alive = A.take<unsigned long long>(BG); // survivor ballot of every binned 64-slot group
-    L->grp_cnt = A.take<uint8_t>(QG * SCAN_NC_BIN); L->grp_base = A.take<uint32_t>(QG * SCAN_NC_BIN); L->grp_tile = A.take<uint32_t>(QG);
-    L->bgrp_cnt = A.take<uint8_t>(BG); L->bgrp_base = A.take<uint32_t>(BG); L->bgrp_tile = A.take<uint32_t>(BG);
-    L->d_all_tiles = A.take<DTile>(total_tiles); L->pgrp_tile = A.take<uint32_t>(CAP / 64 + 1);
-    L->tgbA = A.take<uint32_t>(max_tiles); L->tgcA = A.take<uint32_t>(max_tiles);
-    L->tgbB = A.take<uint32_t>(max_tiles); L->tgcB = A.take<uint32_t>(max_tiles);
-    L->tile_total = A.take<uint32_t>(max_tiles); L->tile_valid = A.take<uint32_t>(max_tiles); L->tile_out_base = A.take<uint32_t>(max_tiles);
-    L->tile_cls_cnt = A.take<uint32_t>(max_tiles * SCAN_NC_BIN); L->tile_cls_base = A.take<uint32_t>(max_tiles * SCAN_NC_BIN);
-    L->hist_stride = max_tiles; L->base_hist = A.take<uint32_t>(((size_t)max_bounces + 1) * max_tiles);
-    Nee& nee = L->nee;
-    nee.cap = BCAP; nee.jobcap = JOBCAP;
-    nee.x = A.take<float>(12 * BCAP); nee.vtr = A.take<float>((NS - 4 + 1) * BCAP); nee.pdf = A.take<float>(NS * BCAP); nee.aux = A.take<float>((NS - 4 + 1) * BCAP);
-    nee.vis = A.take<uint8_t>(NS * BCAP); nee.vpicks = A.take<unsigned long long>(BCAP);
-    nee.T = A.take<float>(BCAP); nee.t0 = A.take<float>(BCAP); nee.nthr = A.take<float>(3 * BCAP); nee.flags = A.take<uint8_t>(BCAP);
-    nee.job_ref = A.take<uint32_t>(JOBCAP); nee.job_geo = A.take<float2>(3 * JOBCAP);
-    return A.off;
-}
-
 // rayn_hip_set_trace_tile, diagnostics only (synchronises): the packet order of the traced tile after the bin stage of 'depth', in HitStore::process_hits order
 int dump_trace_tile(rayn_ctx* ctx, Worker* w, const std::vector<BatchTile>& batch, const Layout& L, uint32_t depth, uint32_t width) {
     WCHK(hipStreamSynchronize(w->stream));
@@ -330,8 +288,8 @@ int dump_trace_tile(rayn_ctx* ctx, Worker* w, const std::vector<BatchTile>& batc
         if ((int)batch[i].tile_index != ctx->trace_tile) continue;
         const DTile& td = batch[i].d;
         uint32_t base = 0, total = 0;
-        WCHK(hipMemcpy(&base, L.tile_out_base + i, 4, hipMemcpyDeviceToHost));
-        WCHK(hipMemcpy(&total, L.tile_total + i, 4, hipMemcpyDeviceToHost));
+        WCHK(hipMemcpy(&base, L.qt.tile_out_base + i, 4, hipMemcpyDeviceToHost));
+        WCHK(hipMemcpy(&total, L.qt.tile_total + i, 4, hipMemcpyDeviceToHost));
         std::vector<uint32_t> hq(total);
         std::vector<float4> g1(td.n_paths), c1(td.n_paths);
         WCHK(hipMemcpy(hq.data(), L.bq + base, (size_t)total * 4, hipMemcpyDeviceToHost));
@@ -371,11 +329,8 @@ int run_worker(rayn_ctx* ctx, Worker* w, const FrameShared& F, const std::vector
     if (spp > 512 && spp <= MAX_SPP_RESOLVE_BLK && !resolve_keys_fit(max_tile_pixels, spp))
         return wfail(w, RAYN_ERR_INVALID_ARG, "tile x spp too large for the 25-bit slot offset of the film resolve's sort keys (k_resolve_blk)");
     Plan plan = make_plan(mine, F.batch_paths);
-    {   // 32-bit [sample][slot] ids: k_shadow_list's grid-stride counter advances in steps of up to 2^25 ids and must not wrap
-        const size_t BCAP = binned_cap(plan.max_pool, plan.max_tiles);
-        if (!((size_t)NS * BCAP <= ((size_t)1 << 32) - ((size_t)1 << 26) && BCAP < ((size_t)1 << 31)))
-            return wfail(w, RAYN_ERR_INVALID_ARG, "batch too large for 32-bit queue indices; lower RAYN_HIP_BATCH_PATHS");
-    }
+    if (!queue_ids_fit(NS, binned_cap(plan.max_pool, plan.max_tiles)))
+        return wfail(w, RAYN_ERR_INVALID_ARG, "batch too large for 32-bit queue indices; lower RAYN_HIP_BATCH_PATHS");
     Layout L;
     Arena dry;
     const size_t need = carve(dry, plan.max_pool, plan.max_tiles, total_tiles, NS, F.p->max_bounces, &L);
@@ -422,10 +377,10 @@ int run_worker(rayn_ctx* ctx, Worker* w, const FrameShared& F, const std::vector
         }
         w->stats.tiles += nt; w->stats.batches++;
         // upper bounds of the device-resident queue sizes of this batch (grids are sized for them)
-        const uint32_t max_entries = (uint32_t)n_pool, max_slots = (uint32_t)std::min<size_t>(L.BCAP, n_pool + (size_t)nt * (SCAN_NC_BIN * 3 + 64));
+        const uint32_t max_entries = (uint32_t)n_pool, max_slots = (uint32_t)std::min(L.BCAP, binned_cap(n_pool, nt));
         {
             Timed t(w, prof, PC_RAYGEN);
-            K.batch_setup(stream, d_tiles, nt, L.pgrp_tile, L.tgbA, L.tgcA);
+            K.batch_setup(stream, d_tiles, nt, L.pgrp_tile, L.qt.ray_tgb, L.qt.ray_tgc);
             K.raygen(stream, ctx->d_scene, tab, F.d_scr, d_tiles, L.pgrp_tile, L.pool, L.q, (uint32_t)n_pool, d_ctl);
         }
         uint32_t* qcur = L.q; uint32_t* qnext = L.qn;
@@ -437,16 +392,10 @@ int run_worker(rayn_ctx* ctx, Worker* w, const FrameShared& F, const std::vector
                 WCHK(hipStreamSynchronize(stream));
                 if (w->h_totals[1] == 0) break;
             }
-            { Timed t(w, prof, PC_EXTEND); K.extend(stream, count, ctx->d_scene, depth, qcur, max_entries, L.pool, L.ent_obj, F.single_sdf, d_ctl, w->d_evals, F.tun); }
+            { Timed t(w, prof, PC_EXTEND); K.extend(stream, count, ctx->d_scene, depth, qcur, max_entries, L.pool, L.qt.ent_obj, F.single_sdf, d_ctl, w->d_evals, F.tun); }
             w->stats.launches_extend++;
-            {
-                Timed t(w, prof, PC_BIN);
-                K.group_hist(stream, hs.n_hitables, L.ent_obj, max_entries, d_ctl, L.grp_cnt); // timed with the bin stage it feeds (r1 / r2 timed it with the extend kernel)
-                K.scan_tile(stream, nt, hs.n_hitables, SCAN_NC_BIN, 4, L.grp_cnt, L.tgbA, L.tgcA, L.grp_base, L.grp_tile, L.tile_total, L.tile_valid, L.tile_cls_cnt, d_ctl);
-                K.tile_prefix(stream, nt, L.tile_total, L.tile_valid, L.tile_out_base, L.tgbB, L.tgcB, d_ctl, 0, hs.n_hitables, 4, L.tile_cls_cnt, L.tile_cls_base,
-                              (uint32_t)(L.BCAP / 64), L.base_hist + (size_t)depth * L.hist_stride);
-                K.bin_scatter(stream, hs.n_hitables, qcur, L.ent_obj, L.grp_base, L.grp_tile, L.tile_out_base, max_entries, L.bq, nt, L.tile_cls_cnt, L.tile_total, L.tile_cls_base, d_ctl);
-            }
+            // k_group_hist is timed with the bin stage it feeds (r1 / r2 timed it with the extend kernel)
+            { Timed t(w, prof, PC_BIN); K.bin_stage(stream, L.qt, hs.n_hitables, nt, qcur, max_entries, L.bq, (uint32_t)(L.BCAP / 64), L.base_hist + (size_t)depth * L.hist_stride, d_ctl); }
             if (ctx->trace_tile >= 0 && dump_trace_tile(ctx, w, batch, L, depth, hs.width)) return w->rc;
             {
                 static const int cls[3] = {PC_SHADE, PC_SHADOW, PC_FINISH};
@@ -455,16 +404,11 @@ int run_worker(rayn_ctx* ctx, Worker* w, const FrameShared& F, const std::vector
                 hooks.user = &hst;
                 hooks.before_fn = [](void* u, int i) { HookState* h = (HookState*)u; h->cur = new Timed(h->w, h->on, cls[i]); };
                 hooks.after_fn = [](void* u, int) { HookState* h = (HookState*)u; delete h->cur; h->cur = nullptr; };
-                K.shade(stream, count, ctx->d_scene, tab, F.d_scr, depth, L.bq, max_slots, L.pool, L.nee, NS, hs.n_sdf > 0, F.single_sdf, L.alive, L.bgrp_cnt, d_ctl, w->d_evals, hooks, F.tun);
+                K.shade(stream, count, ctx->d_scene, tab, F.d_scr, depth, L.bq, max_slots, L.pool, L.nee, NS, hs.n_sdf > 0, F.single_sdf, L.qt.alive, L.qt.bgrp_cnt, d_ctl, w->d_evals, hooks, F.tun);
             }
             w->stats.launches_shade++;
             if (depth == last_depth) break; // nothing survives the last depth: no repack
-            {
-                Timed t(w, prof, PC_COMPACT);
-                K.scan_tile(stream, nt, 1, 1, 1, L.bgrp_cnt, L.tgbB, L.tgcB, L.bgrp_base, L.bgrp_tile, L.tile_total, L.tile_valid, L.tile_cls_cnt, d_ctl);
-                K.tile_prefix(stream, nt, L.tile_total, L.tile_valid, L.tile_out_base, L.tgbA, L.tgcA, d_ctl, 1, 1, 1, L.tile_cls_cnt, L.tile_cls_base, (uint32_t)(L.QCAP / 64), nullptr);
-                K.compact_scatter(stream, L.bq, L.alive, L.bgrp_base, L.bgrp_tile, L.tile_out_base, max_slots, qnext, nt, L.tile_total, d_ctl);
-            }
+            { Timed t(w, prof, PC_COMPACT); K.repack_stage(stream, L.qt, nt, L.bq, max_slots, qnext, (uint32_t)(L.QCAP / 64), d_ctl); }
             std::swap(qcur, qnext);
         }
         { Timed t(w, prof, PC_RESOLVE); K.resolve(stream, ctx->d_scene, d_tiles, nt, max_tile_pixels, spp, L.pool, F.d_color, F.d_alpha, F.d_bg, F.d_normal, L.base_hist, (uint32_t)L.hist_stride); }
@@ -563,8 +507,8 @@ int render_device(rayn_ctx* ctx, const rayn_frame_params* p, const float* d_s1, 
     if (owned.empty()) return RAYN_OK;
 
     // ---- shared, read-only state: scene, tables, packed sample records
-    const uint32_t rec_stride = (8 + hs.n2) / 4, rec_depths = p->max_bounces + 1;
-    const size_t rec_n = (size_t)rec_depths * spp * rec_stride;
+    const RecordLayout rec(hs.n2, p->max_bounces);
+    const size_t rec_n = rec.count(spp);
     if (rec_n > ctx->rec_cap) {
         if (ctx->d_rec) HIPCHK(hipFree(ctx->d_rec));
         ctx->d_rec = nullptr; ctx->rec_cap = 0;
@@ -575,10 +519,10 @@ int render_device(rayn_ctx* ctx, const rayn_frame_params* p, const float* d_s1, 
     HIPCHK(hipMemcpyAsync(ctx->d_scene, &F.hs, sizeof F.hs, hipMemcpyHostToDevice, stream));
     F.K = kernel_set(ctx->cfg->fma_policy);
     F.single_sdf = scene_march_kernels(ctx, hs, *p, &F.tun);
-    F.tab = Tables{d_s1, d_s2, d_fis, ctx->d_rec, rec_stride};
-    F.K.pack_tables(stream, F.tab, ctx->d_rec, spp, rec_depths, hs.n1, hs.n2);
+    F.tab = Tables{d_s1, d_s2, d_fis, ctx->d_rec, rec.stride};
+    F.K.pack_tables(stream, F.tab, ctx->d_rec, spp, rec.depths, hs.n1, hs.n2);
     F.d_scr = d_scr; F.d_color = out.color; F.d_alpha = out.alpha; F.d_bg = out.bg; F.d_normal = out.normal;
-    F.NS = 4 + (ctx->cfg->world.has_scattering ? 4 * p->volume_marches : 0); // NEE samples per shading point
+    F.NS = nee_samples(ctx->cfg->world.has_scattering, p->volume_marches);
     F.count = ctx->cfg->counting; F.profiling = ctx->cfg->profiling;
     // Batch size and worker count.  Bigger batches = fewer launches and tails (2^25 -> 2^27 paths: -9 % frame time), so
     // they are sized for the HBM that is actually free: at most 60 % of it across the workers (the rest stays with the
@@ -589,7 +533,7 @@ int render_device(rayn_ctx* ctx, const rayn_frame_params* p, const float* d_s1, 
         size_t free_b = 0, total_b = 0;
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
         for (const Worker& w : ctx->workers) free_b += w.arena.cap;
-        const size_t per_path = 118 + 81 + 33 * (size_t)F.NS + 8 * ((size_t)F.NS - 3); // pool + queues | NEE records: fixed part, per light sample (pdf, vis, job ref, 24-B segment), per volume sample (vtr, aux)
+        const size_t per_path = arena_bytes_per_path(F.NS);
         // entries of a multi-device context that share one GPU (repeated device ids) size their arenas concurrently from the same
         // free figure: each takes its share of the budget
         const size_t budget_paths = (size_t)(0.6 * (double)free_b / (double)std::max(ctx->budget_share, 1)) / per_path;
@@ -1091,26 +1035,33 @@ int rayn_hip_upscale_device(rayn_ctx* ctx, uint32_t width, uint32_t height, cons
     return post_enqueued(ctx);
 }
 
-// The primary-hit G-buffer (temporal.hip): one centre ray per pixel through the scene's PRODUCT extend kernel at depth 0, selected as
-// rayn_hip_probe_extend selects it.  The scene of (uploaded world, p) goes to ctx->d_scene on the stream, as a render's does (a pageable
-// source is staged before hipMemcpyAsync returns, so the stack copy may go away).
+// The primary-hit pass of rayn_hip_gbuffer_device and rayn_hip_preview_device over the scratch g: one centre ray per pixel through the scene's
+// PRODUCT extend kernel at depth 0, selected as rayn_hip_probe_extend selects it, then (P, t) records and object indices.  The scene of (uploaded
+// world, p) goes to ctx->d_scene on the stream, as a render's does (a pageable source is staged before hipMemcpyAsync returns, so the stack copy
+// may go away).  What the scene decided comes back for the kernels a caller launches afterwards.
+struct PrimaryHit { DScene hs; int single_sdf; Tuning tun; KernelSet K; };
+static int primary_hit_pass(rayn_ctx* ctx, const rayn_frame_params* p, hipStream_t s, const GbufScratch& g, void* d_out_records, uint32_t* d_out_object,
+                            PrimaryHit* out) {
+    if (int rc = build_scene(ctx, ctx->cfg->world, *p, &out->hs)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_scene, &out->hs, sizeof out->hs, hipMemcpyHostToDevice, s));
+    out->single_sdf = scene_march_kernels(ctx, out->hs, *p, &out->tun);
+    out->K = kernel_set(ctx->cfg->fma_policy);
+    if (ctx->cfg->fma_policy) rayn_p1::launch_gbuffer_rays(s, ctx->d_scene, g);
+    else rayn_p0::launch_gbuffer_rays(s, ctx->d_scene, g);
+    out->K.extend(s, false, ctx->d_scene, 0, g.q, g.npad, g.pool, g.ent_obj, out->single_sdf, g.ctl, g.evals, out->tun);
+    launch_gbuffer_finish(s, g, d_out_records, d_out_object);
+    return RAYN_OK;
+}
+
+// The primary-hit G-buffer (temporal.hip).
 int rayn_hip_gbuffer_device(rayn_ctx* ctx, const rayn_frame_params* p, void* d_out_records, uint32_t* d_out_object, void* d_scratch,
                             size_t scratch_bytes, void* hip_stream) {
     const char* why = gbuffer_check_args(p, d_out_records, d_out_object, d_scratch, scratch_bytes);
     if (!why && ctx && !ctx->cfg->have_world) why = "rayn_hip_upload_world has not been called";
     hipStream_t s;
     if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
-    DScene hs;
-    if (int rc = build_scene(ctx, ctx->cfg->world, *p, &hs)) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->d_scene, &hs, sizeof hs, hipMemcpyHostToDevice, s));
-    Tuning tun;
-    const int single_sdf = scene_march_kernels(ctx, hs, *p, &tun);
-    const KernelSet K = kernel_set(ctx->cfg->fma_policy);
-    const GbufScratch g = gbuffer_scratch(p->width, p->height, d_scratch);
-    if (ctx->cfg->fma_policy) rayn_p1::launch_gbuffer_rays(s, ctx->d_scene, g);
-    else rayn_p0::launch_gbuffer_rays(s, ctx->d_scene, g);
-    K.extend(s, false, ctx->d_scene, 0, g.q, g.npad, g.pool, g.ent_obj, single_sdf, g.ctl, g.evals, tun);
-    launch_gbuffer_finish(s, g, d_out_records, d_out_object);
+    PrimaryHit ph;
+    if (int rc = primary_hit_pass(ctx, p, s, gbuffer_scratch(p->width, p->height, d_scratch), d_out_records, d_out_object, &ph)) return rc;
     return post_enqueued(ctx);
 }
 
@@ -1124,23 +1075,15 @@ int rayn_hip_preview_device(rayn_ctx* ctx, const rayn_frame_params* p, const ray
     if (!why && ctx && !ctx->cfg->have_world) why = "rayn_hip_upload_world has not been called";
     hipStream_t s;
     if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
-    DScene hs;
-    if (int rc = build_scene(ctx, ctx->cfg->world, *p, &hs)) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->d_scene, &hs, sizeof hs, hipMemcpyHostToDevice, s));
-    Tuning tun;
-    const int single_sdf = scene_march_kernels(ctx, hs, *p, &tun);
-    const KernelSet K = kernel_set(ctx->cfg->fma_policy);
     const PreviewScratch ps = preview_scratch(p->width, p->height, pp->samples, d_scratch, d_out_records, d_out_object);
-    if (ctx->cfg->fma_policy) rayn_p1::launch_gbuffer_rays(s, ctx->d_scene, ps.g);
-    else rayn_p0::launch_gbuffer_rays(s, ctx->d_scene, ps.g);
-    K.extend(s, false, ctx->d_scene, 0, ps.g.q, ps.g.npad, ps.g.pool, ps.g.ent_obj, single_sdf, ps.g.ctl, ps.g.evals, tun);
-    launch_gbuffer_finish(s, ps.g, ps.records, ps.object);
+    PrimaryHit ph;
+    if (int rc = primary_hit_pass(ctx, p, s, ps.g, ps.records, ps.object, &ph)) return rc;
     const Nee nee = preview_nee(ps);
     for (uint32_t k0 = 0; k0 < pp->samples; k0 += ps.round) {
         const uint32_t kn = std::min(ps.round, pp->samples - k0);
         if (ctx->cfg->fma_policy) rayn_p1::launch_preview_jobs(s, ctx->d_scene, ps, k0, kn, pp->radius, pp->ambient, d_samples, d_scramble, d_out_normal);
         else rayn_p0::launch_preview_jobs(s, ctx->d_scene, ps, k0, kn, pp->radius, pp->ambient, d_samples, d_scramble, d_out_normal);
-        if (hs.n_sdf > 0) K.shadow_march(s, false, ctx->d_scene, nee, kn * ps.g.npad, single_sdf, ps.g.ctl, ps.g.evals, tun);
+        if (ph.hs.n_sdf > 0) ph.K.shadow_march(s, false, ctx->d_scene, nee, kn * ps.g.npad, ph.single_sdf, ps.g.ctl, ps.g.evals, ph.tun);
         launch_preview_resolve(s, ps, kn, pp->samples, k0 + kn >= pp->samples, d_out_color, d_out_alpha, d_out_ao);
     }
     return post_enqueued(ctx);
