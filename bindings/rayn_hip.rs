@@ -499,6 +499,35 @@ extern "C" {
         scratch_bytes: usize,
         hip_stream: *mut c_void,
     ) -> i32;
+    /// the same with LZ77 matches: rayn_hip_png_encode_device's arguments and output, `d_scratch` of rayn_png_scratch_bytes_lz77 bytes
+    pub fn rayn_png_scratch_bytes_lz77(width: u32, height: u32, bpp: u32) -> usize;
+    pub fn rayn_hip_png_encode_lz77_device(
+        ctx: *mut RaynCtx,
+        width: u32,
+        height: u32,
+        bpp: u32,
+        d_img: *const u8,
+        d_out: *mut c_void,
+        out_bytes: usize,
+        d_scratch: *mut c_void,
+        scratch_bytes: usize,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    /// its deflate stage alone on `n` bytes at `d_data` (1 <= n < 2^31; `stride`: the row candidate's distance, 0 for none): the same
+    /// header and a zlib stream; host-only byte counts of `d_out` and `d_scratch`, 0 for a rejected size
+    pub fn rayn_deflate_stream_bound(n: usize) -> usize;
+    pub fn rayn_deflate_scratch_bytes(n: usize) -> usize;
+    pub fn rayn_hip_deflate_lz77_device(
+        ctx: *mut RaynCtx,
+        d_data: *const c_void,
+        n: usize,
+        stride: u32,
+        d_out: *mut c_void,
+        out_bytes: usize,
+        d_scratch: *mut c_void,
+        scratch_bytes: usize,
+        hip_stream: *mut c_void,
+    ) -> i32;
 }
 
 /// Start-up layout check against the library as compiled (indices: include/rayn_hip.h, rayn_hip_sizeof).

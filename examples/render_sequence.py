@@ -5,7 +5,7 @@ written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints
     python examples/render_sequence.py --frames 1:49 [--out renders_seq] [--compare-loop | --denoise [atrous|variance]] [--temporal] [--feedback B]
                                       [--resample {bilinear,catmull_rom}] [--display [--exposure auto|EV] [--tone T] [--bloom LEVELS] [--adaptation S]]
                                       [--upscale S [--temporal --supersample [--no-jitter] [--confidence | --no-confidence]]]
-                                      [--preview [K] [--ao-radius R]] [--interpolate K [--interp-tolerance D]] [--png {host,device}]
+                                      [--preview [K] [--ao-radius R]] [--interpolate K [--interp-tolerance D]] [--png {host,device,device-lz77}]
 
 --compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
 the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
@@ -40,7 +40,9 @@ and --denoise atrous and --display work on the generated frames too; --temporal,
 --compare-loop do not combine with it.
 --png device encodes every file's stream on the device (Film.render_sequence(png="device"), an extension: adaptive row filters, run-length
 and Huffman coding; the writer threads only frame it) instead of calling zlib on the host; the files keep their names and pixels, not
-their bytes, so it does not combine with --compare-loop.  The total size of the written files is printed for either encoder.
+their bytes, so it does not combine with --compare-loop.  --png device-lz77 is the same with the encoder that also finds LZ77 matches
+(png="device-lz77"): about twice the encoder time, smaller Color files - much smaller with --preview - and larger masks and normals.  The
+total size of the written files is printed for every encoder.
 """
 import argparse
 import os
@@ -117,8 +119,9 @@ def main():
                     help="render every K-th frame (2..16) and the last, and generate the frames between two rendered keys (rayn_amd.Interpolate(K))")
     ap.add_argument("--interp-tolerance", type=float, default=None, metavar="D",
                     help="relative depth tolerance of a key's tap (default rayn_amd.Interpolate().depth_tolerance); needs --interpolate")
-    ap.add_argument("--png", choices=("host", "device"), default="host",
-                    help="where the PNG streams are encoded: host (zlib in the writer threads, the default) or device (filter, run-length and Huffman kernels on the render stream)")
+    ap.add_argument("--png", choices=("host", "device", "device-lz77"), default="host",
+                    help="where the PNG streams are encoded: host (zlib in the writer threads, the default), device (filter, run-length and Huffman kernels on the "
+                         "render stream) or device-lz77 (the same with LZ77 matches)")
     args = ap.parse_args()
     if args.png != "host" and args.compare_loop:
         ap.error("--compare-loop compares the files byte for byte with the host encoder's: use one or the other")

@@ -894,6 +894,44 @@ size_t rayn_png_scratch_bytes(uint32_t width, uint32_t height, uint32_t bpp);
 int rayn_hip_png_encode_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t bpp, const uint8_t* d_img, void* d_out, size_t out_bytes,
                                void* d_scratch, size_t scratch_bytes, void* hip_stream);
 
+/* ---- PNG encoding on the device, with LZ77 matches (an EXTENSION) -- A second encoder behind the same interface, whose tokens are
+ * literals and LZ77 matches at any distance inside the block.  Integer arithmetic only; tests/png_lz_np.py restates it and the kernels
+ * agree with it byte for byte.  Unchanged from rayn_hip_png_encode_device: the filtering and the filtered stream R, the 32768-byte blocks
+ * encoded each on its own, the stored fallback at >= len + 5 bytes, the alignment block behind every Huffman block but the final one,
+ * 78 01, the Adler-32, the four header words, and rayn_png_stream_bound, which bounds the output.  New, per block B[0..len), with S the
+ * row stride 1 + w * bpp:
+ *   Candidates at position i.  A distance d is a candidate only if i - d >= 0: no match reaches before the block start.  d = 1.
+ *     d = i - prev(i), where prev(i) is the largest j < i with B[j..j+3) == B[i..i+3), defined only when i + 3 <= len (exact byte
+ *     equality; there is no hash).  d = S, the row above, if S != 0.
+ *   Match length.  m(i, d) is the largest L <= min(258, len - i) with B[i-d+k] == B[i+k] for all k < L; the two ranges may overlap.
+ *   Best match.  M(i) is the maximum of m(i, d) over the candidates, D(i) the smallest d that reaches it.  A match needs M >= 3, and a
+ *     match of length 3 at D > 4096 is not taken.
+ *   Parse.  Greedy from p = 0: the match (M(p), D(p)) and p += M(p), otherwise the literal B[p] and p += 1.  No lazy evaluation.
+ *   Codes.  The literal/length code is the construction above over 286 symbols, end-of-block counting 1.  The distance code is the same
+ *     construction over the 30 distance symbols of RFC 1951 3.2.5: leaves indexed by symbol, internal nodes 30, 31, ... in creation order,
+ *     frequencies halved - independently of the other tree - while a length exceeds 15.  With fewer than two distance symbols in use
+ *     the used one gets length 1 and every other length is 0; with none in use symbol 0 gets length 1 (the one incomplete code RFC 1951
+ *     and zlib accept).
+ *   A Huffman block.  A header of 1338 bits: BFINAL, BTYPE = 2, HLIT = 29, HDIST = 29, HCLEN = 15; the 19 code-length code lengths as
+ *     above; the 286 + 30 code lengths, each as its 4-bit code.  Then the tokens - a match is its length code, its extra bits, its
+ *     distance code and its extra bits - and end-of-block.
+ * rayn_png_scratch_bytes_lz77: the bytes of d_scratch (rayn_png_scratch_bytes and 65536 per block for the match finder's sort).  Host
+ * only; 0 for a geometry the encoder rejects.  The entry takes rayn_hip_png_encode_device's arguments and rejects the same inputs. */
+size_t rayn_png_scratch_bytes_lz77(uint32_t width, uint32_t height, uint32_t bpp);
+int rayn_hip_png_encode_lz77_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t bpp, const uint8_t* d_img, void* d_out, size_t out_bytes,
+                                    void* d_scratch, size_t scratch_bytes, void* hip_stream);
+/* The deflate stage of that encoder alone, on n bytes of the caller's at d_data (a DEVICE pointer of any alignment, not modified), which
+ * take R's place; stride takes S's (0: no row candidate; any other value is a distance like S).  d_out receives the same four header
+ * words and the zlib stream of d_data: a zlib writer for device buffers.  rayn_deflate_stream_bound(n): the bytes d_out must have,
+ * 16 + 2 + n + 10 per 32768-byte block + 4, rounded up to 16; rayn_deflate_scratch_bytes(n): the bytes of d_scratch.  Both host only; 0
+ * for n == 0 and n >= 2^31.  Enqueued on 'hip_stream' like the encoder.  RAYN_ERR_INVALID_ARG with a last error text, and nothing
+ * written, for: n == 0 or n >= 2^31 (32-bit offsets), a NULL buffer, a misaligned (16 bytes) or too small d_out or d_scratch, d_out ==
+ * d_data and buffers that overlap. */
+size_t rayn_deflate_stream_bound(size_t n);
+size_t rayn_deflate_scratch_bytes(size_t n);
+int rayn_hip_deflate_lz77_device(rayn_ctx* ctx, const void* d_data, size_t n, uint32_t stride, void* d_out, size_t out_bytes, void* d_scratch,
+                                 size_t scratch_bytes, void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */

@@ -406,6 +406,21 @@ inline int png_encode(rayn_ctx* ctx, Extent2u res, uint32_t bpp, const uint8_t* 
     return rayn_hip_png_encode_device(ctx, res.w, res.h, bpp, d_img, d_out, out_bytes, d_scratch, scratch_bytes, hip_stream);
 }
 
+// The same with LZ77 matches (include/rayn_hip.h: PNG encoding on the device, with LZ77 matches): png_encode's arguments and output, d_scratch
+// of at least png_scratch_bytes_lz77.  deflate_lz77 is its deflate stage on n bytes at d_data (stride: the row candidate's distance, 0 for
+// none): the same header and a zlib stream; d_out of at least deflate_stream_bound(n) bytes, d_scratch of deflate_scratch_bytes(n).
+inline size_t png_scratch_bytes_lz77(Extent2u res, uint32_t bpp) { return rayn_png_scratch_bytes_lz77(res.w, res.h, bpp); }
+inline int png_encode_lz77(rayn_ctx* ctx, Extent2u res, uint32_t bpp, const uint8_t* d_img, void* d_out, size_t out_bytes, void* d_scratch,
+                           size_t scratch_bytes, void* hip_stream = nullptr) {
+    return rayn_hip_png_encode_lz77_device(ctx, res.w, res.h, bpp, d_img, d_out, out_bytes, d_scratch, scratch_bytes, hip_stream);
+}
+inline size_t deflate_stream_bound(size_t n) { return rayn_deflate_stream_bound(n); }
+inline size_t deflate_scratch_bytes(size_t n) { return rayn_deflate_scratch_bytes(n); }
+inline int deflate_lz77(rayn_ctx* ctx, const void* d_data, size_t n, uint32_t stride, void* d_out, size_t out_bytes, void* d_scratch,
+                        size_t scratch_bytes, void* hip_stream = nullptr) {
+    return rayn_hip_deflate_lz77_device(ctx, d_data, n, stride, d_out, out_bytes, d_scratch, scratch_bytes, hip_stream);
+}
+
 // ---- setup::setup() (src/setup.rs:46-170) with the resolution as an argument ---------------------
 namespace setup {
 constexpr float WORLD_RADIUS = 100.0f;

@@ -48,6 +48,8 @@ EXPORTS = [
     "rayn_preview_scratch_bytes", "rayn_hip_preview_device",
     "rayn_hip_interpolate_device",
     "rayn_png_stream_bound", "rayn_png_scratch_bytes", "rayn_hip_png_encode_device",
+    "rayn_png_scratch_bytes_lz77", "rayn_hip_png_encode_lz77_device",
+    "rayn_deflate_stream_bound", "rayn_deflate_scratch_bytes", "rayn_hip_deflate_lz77_device",
 ]
 
 
@@ -145,10 +147,15 @@ def lib():
         L.rayn_hip_preview_device.argtypes = [vp, C.POINTER(_abi.FrameParams), C.POINTER(_abi.PreviewParams)] + [vp] * 9 + [C.c_size_t, vp]
         L.rayn_hip_interpolate_device.argtypes = ([vp, C.POINTER(_abi.FrameParams), C.POINTER(_abi.InterpolateParams), C.POINTER(_abi.InterpolateKey),
                                                    C.POINTER(_abi.InterpolateKey)] + [vp] * 8)
-        for fn in (L.rayn_png_stream_bound, L.rayn_png_scratch_bytes):
+        for fn in (L.rayn_png_stream_bound, L.rayn_png_scratch_bytes, L.rayn_png_scratch_bytes_lz77):
             fn.restype = C.c_size_t
             fn.argtypes = [C.c_uint32] * 3
-        L.rayn_hip_png_encode_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, vp, C.c_size_t, vp]
+        for fn in (L.rayn_hip_png_encode_device, L.rayn_hip_png_encode_lz77_device):
+            fn.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, vp, C.c_size_t, vp]
+        for fn in (L.rayn_deflate_stream_bound, L.rayn_deflate_scratch_bytes):
+            fn.restype = C.c_size_t
+            fn.argtypes = [C.c_size_t]
+        L.rayn_hip_deflate_lz77_device.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, vp]
         L.rayn_sets_1d.restype = C.c_uint32
         L.rayn_sets_1d.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_sets_2d.restype = C.c_uint32

@@ -47,6 +47,22 @@ def png_scratch_bytes(width, height, bpp):
     return int(lib().rayn_png_scratch_bytes(int(width), int(height), int(bpp)))
 
 
+def png_scratch_bytes_lz77(width, height, bpp):
+    """rayn_png_scratch_bytes_lz77: bytes of device scratch Context.png_encode_lz77 needs (0 for a geometry it rejects).  Host only."""
+    return int(lib().rayn_png_scratch_bytes_lz77(int(width), int(height), int(bpp)))
+
+
+def deflate_stream_bound(n):
+    """rayn_deflate_stream_bound: the bytes Context.deflate's output needs for n input bytes: the 16-byte header and the longest zlib
+    stream it can write (0 for n == 0 and n >= 2^31).  Host only."""
+    return int(lib().rayn_deflate_stream_bound(int(n))) if 0 <= int(n) < 1 << 63 else 0
+
+
+def deflate_scratch_bytes(n):
+    """rayn_deflate_scratch_bytes: bytes of device scratch Context.deflate needs for n input bytes (0 for a size it rejects).  Host only."""
+    return int(lib().rayn_deflate_scratch_bytes(int(n))) if 0 <= int(n) < 1 << 63 else 0
+
+
 def preview_tables(samples, frame, width, height):
     """The default tables of a preview of `samples` AO rays for frame `frame`: (the sample table (samples, 2) float32 - 2-D set 0 of
     build_rd_tables(samples, 0, 2, frame), so successive frames get different directions - and the per-pixel scramble of
@@ -459,21 +475,43 @@ class Context:
         self._chk(self._L.rayn_hip_save_to_pixels_device(self.h, int(kind), int(have_mask), int(bool(transparent_background)), int(width), int(height),
                                                          *ptrs, _ptr(d_out), stream_ptr(stream)))
 
-    def png_encode(self, width, height, bpp, d_img, d_out, d_scratch=None, stream=None):
+    def png_encode_lz77(self, width, height, bpp, d_img, d_out, d_scratch=None, stream=None):
+        """rayn_hip_png_encode_lz77_device: png_encode with LZ77 matches - the same arguments, the same header words and a zlib stream of
+        the same filtered rows, smaller on smooth and flat images.  d_scratch: at least png_scratch_bytes_lz77(width, height, bpp) bytes,
+        allocated here when None."""
+        self.png_encode(width, height, bpp, d_img, d_out, d_scratch, stream, lz77=True)
+
+    def deflate(self, d_data, d_out, stride=0, d_scratch=None, stream=None):
+        """rayn_hip_deflate_lz77_device: the zlib stream of the bytes of the contiguous uint8 CUDA tensor `d_data` (1 <= bytes < 2^31)
+        into the uint8 CUDA tensor `d_out` (at least deflate_stream_bound(bytes) bytes, 16-byte aligned): the four header words of
+        png_encode - the stream's bytes, the input bytes, the blocks, the stored blocks - then the stream, which zlib.decompress takes.
+        stride: the distance of the encoder's row candidate, 0 for none.  d_scratch: at least deflate_scratch_bytes(bytes) bytes,
+        allocated here when None.  Enqueued on the stream, not waited for; d_data is not modified."""
+        import torch
+        if d_data is None or not (d_data.dtype == torch.uint8 and d_data.is_contiguous()):
+            raise ValueError("d_data must be a contiguous uint8 tensor")
+        n = d_data.numel()
+        if d_out is None or not (d_out.dtype == torch.uint8 and d_out.is_contiguous() and d_out.numel() >= deflate_stream_bound(n)):
+            raise ValueError(f"d_out must be a contiguous uint8 tensor of at least {deflate_stream_bound(n)} bytes")
+        d_scratch, scratch_ptr, scratch_bytes = scratch(d_scratch, deflate_scratch_bytes(n), d_out.device)
+        self._chk(self._L.rayn_hip_deflate_lz77_device(self.h, _ptr(d_data), n, int(stride), _ptr(d_out), d_out.numel(), scratch_ptr, scratch_bytes,
+                                                       stream_ptr(stream)))
+
+    def png_encode(self, width, height, bpp, d_img, d_out, d_scratch=None, stream=None, lz77=False):
         """rayn_hip_png_encode_device: the zlib stream of the PNG IDAT chunk of the 8-bit image `d_img` (a uint8 CUDA tensor of width *
         height * bpp bytes, rows top-down, as save_to_pixels and display write it) into the uint8 CUDA tensor `d_out` (at least
         png_stream_bound(width, height, bpp) bytes, 16-byte aligned): four little-endian words - the stream's bytes, the filtered bytes,
         the blocks, the stored blocks - then the stream (rayn_amd.image.png_from_stream frames it as a file).  d_scratch: a CUDA tensor
         of at least png_scratch_bytes(width, height, bpp) bytes, allocated here when None.  Enqueued on the stream, not waited for; d_img
-        is not modified."""
+        is not modified.  lz77: the entry of png_encode_lz77 and its scratch size instead."""
         import torch
         need = int(width) * int(height) * int(bpp)
         for t, label, n in ((d_img, "d_img", need), (d_out, "d_out", png_stream_bound(width, height, bpp))):
             if t is None or not (t.dtype == torch.uint8 and t.is_contiguous() and t.numel() >= n):
                 raise ValueError(f"{label} must be a contiguous uint8 tensor of at least {n} bytes")
-        d_scratch, scratch_ptr, scratch_bytes = scratch(d_scratch, png_scratch_bytes(width, height, bpp), d_out.device)
-        self._chk(self._L.rayn_hip_png_encode_device(self.h, int(width), int(height), int(bpp), _ptr(d_img), _ptr(d_out), d_out.numel(), scratch_ptr,
-                                                     scratch_bytes, stream_ptr(stream)))
+        d_scratch, scratch_ptr, scratch_bytes = scratch(d_scratch, (png_scratch_bytes_lz77 if lz77 else png_scratch_bytes)(width, height, bpp), d_out.device)
+        entry = self._L.rayn_hip_png_encode_lz77_device if lz77 else self._L.rayn_hip_png_encode_device
+        self._chk(entry(self.h, int(width), int(height), int(bpp), _ptr(d_img), _ptr(d_out), d_out.numel(), scratch_ptr, scratch_bytes, stream_ptr(stream)))
 
     def display_state(self):
         """A fresh state of the display transform's auto exposure: two zeroed 32-bit words {m, valid} on the context's GPU."""

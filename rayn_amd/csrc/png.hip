@@ -9,42 +9,16 @@
 // zero-initialised words.
 #include "png.h"
 
+#include "png_device.h"
 #include "post_checks.h"
 
 namespace rayn {
 
 namespace {
 
-constexpr uint32_t BT = 256u;                   // threads of k_png_block
-constexpr uint32_t SPAN = PNG_BLOCK / BT;       // consecutive bytes of the block a thread tokenises
-constexpr uint32_t LDS_WORDS = PNG_BLOCK / 4u + PNG_BLOCK / 128u; // one pad word per 32: a thread's 32 words start on bank (33 * t) % 32
-constexpr uint32_t NSYM = 286u, END_OF_BLOCK = 256u, ADLER = 65521u, HEADER_BITS = 1222u, CODES_AT = 74u, DIST_AT = 1218u;
-constexpr uint32_t NO_START = 0xFFFFFFFFu;
-
-struct PngMeta { // one per block
-    uint32_t bytes;  // of the encoded block in its slot, the alignment block included
-    uint32_t a, b;   // Adler-32 partial sums mod 65521: sum of the bytes, sum of (len - i) * byte i
-    uint32_t stored;
-};
-
-__device__ inline uint32_t byte_at(const uint32_t* sw, uint32_t i) {
-    const uint32_t wi = i >> 2;
-    return (sw[wi + (wi >> 5)] >> ((i & 3u) * 8u)) & 255u;
-}
-
-// (symbol, extra bits, extra value) of a match length 3..258, RFC 1951 3.2.5
-__device__ inline void length_code(uint32_t n, uint32_t* sym, uint32_t* xbits, uint32_t* xval) {
-    const uint32_t l = n - 3u;
-    if (n == 258u) {
-        *sym = 285u, *xbits = 0u, *xval = 0u;
-    } else if (l < 8u) {
-        *sym = 257u + l, *xbits = 0u, *xval = 0u;
-    } else {
-        const uint32_t x = 29u - (uint32_t)__clz((int)l); // floor(log2 l) - 2
-        *sym = 261u + 4u * x + ((l >> x) & 3u), *xbits = x, *xval = l & ((1u << x) - 1u);
-    }
-}
-__device__ inline uint32_t symbol_extra_bits(uint32_t s) { return s < 265u || s == 285u ? 0u : (s - 261u) >> 2; }
+constexpr uint32_t BT = PNG_BT, SPAN = PNG_SPAN, LDS_WORDS = PNG_LDS_WORDS;
+constexpr uint32_t NSYM = PNG_NSYM, END_OF_BLOCK = PNG_END_OF_BLOCK, ADLER = PNG_ADLER, HEADER_BITS = 1222u, CODES_AT = 74u, DIST_AT = 1218u;
+constexpr uint32_t NO_START = PNG_NO_START;
 
 // The tokens whose first byte lies in [lo, hi), in order: f(symbol, extra bits, extra value).  run_start: where the run holding byte lo
 // begins (<= lo); next_start: the first run start at or behind hi, the block's length when there is none.
@@ -74,58 +48,6 @@ __device__ inline void walk_tokens(const uint32_t* sw, uint32_t lo, uint32_t hi,
         }
         i = s = seg_end;
     }
-}
-
-// the bits of v (<= 32) at bit `at` of zero-initialised words others write too, in LDS or in global memory
-__device__ inline void or_bits(uint32_t* words, uint32_t at, uint32_t v) {
-    const uint64_t x = (uint64_t)v << (at & 31u);
-    uint32_t* w = words + (at >> 5);
-    if ((uint32_t)x) atomicOr(w, (uint32_t)x);
-    if ((uint32_t)(x >> 32)) atomicOr(w + 1, (uint32_t)(x >> 32));
-}
-
-// Bits from bit `at` of the slot on, least-significant first.  A word this thread fills alone is stored; the first and last words, which
-// a neighbour may share, are or-ed into the zero-initialised slot.
-struct BitWriter {
-    uint32_t* w;
-    uint64_t acc;
-    uint32_t filled;
-    bool shared;
-    __device__ BitWriter(uint32_t* words, uint32_t at) : w(words + (at >> 5)), acc(0), filled(at & 31u), shared((at & 31u) != 0u) {}
-    __device__ void put(uint32_t v, uint32_t n) { // n <= 32
-        acc |= (uint64_t)v << filled;
-        filled += n;
-        if (filled >= 32u) {
-            if (shared) {
-                if ((uint32_t)acc) atomicOr(w, (uint32_t)acc);
-                shared = false;
-            } else {
-                *w = (uint32_t)acc;
-            }
-            w++, acc >>= 32, filled -= 32u;
-        }
-    }
-    __device__ void finish() {
-        if ((uint32_t)acc) atomicOr(w, (uint32_t)acc);
-    }
-};
-
-// blockDim.x = BT: the exclusive sum of v over the threads; *total the sum.  buf: BT words of LDS.
-__device__ inline uint32_t block_exclusive_sum(uint32_t* buf, uint32_t v, uint32_t* total) {
-    const uint32_t t = threadIdx.x;
-    __syncthreads();
-    buf[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < BT; d <<= 1) {
-        const uint32_t add = t >= d ? buf[t - d] : 0u;
-        __syncthreads();
-        buf[t] += add;
-        __syncthreads();
-    }
-    const uint32_t incl = buf[t];
-    *total = buf[BT - 1u];
-    __syncthreads();
-    return incl - v;
 }
 
 __device__ inline uint32_t abs_i8(uint32_t f) {
@@ -185,12 +107,11 @@ __global__ __launch_bounds__(256) void k_png_filter(const uint8_t* __restrict__ 
 __global__ __launch_bounds__(BT) void k_png_block(const uint8_t* __restrict__ R, uint32_t n, uint32_t nblocks, PngMeta* __restrict__ meta,
                                                   uint8_t* __restrict__ slots) {
     __shared__ uint32_t sw[LDS_WORDS];
-    __shared__ uint32_t hist[NSYM], work[NSYM], tab[NSYM], clen[NSYM]; // frequencies, halved frequencies, (reversed code | length << 16), lengths
-    __shared__ uint32_t wt[NSYM];                                      // weights of the internal nodes, in creation order
-    __shared__ uint16_t sorted[NSYM], parent[2u * NSYM];
+    __shared__ uint32_t hist[NSYM];
+    __shared__ HuffmanLds<NSYM> hl;
     __shared__ uint32_t first_start[BT], last_start[BT], sums[BT];
-    __shared__ uint32_t hdr[40], count[16], next_code[16];
-    __shared__ uint32_t sh_a, sh_b, sh_bits, sh_matches, sh_leaves, sh_depth;
+    __shared__ uint32_t hdr[40];
+    __shared__ uint32_t sh_a, sh_b, sh_bits, sh_matches;
 
     const uint32_t t = threadIdx.x, blk = blockIdx.x;
     const uint32_t base = blk * PNG_BLOCK, len = min(PNG_BLOCK, n - base);
@@ -243,85 +164,14 @@ __global__ __launch_bounds__(BT) void k_png_block(const uint8_t* __restrict__ R,
     // histogram over the 286 literal/length symbols; end-of-block counts 1
     walk_tokens(sw, lo, hi, run_start, next_start, [&](uint32_t sym, uint32_t, uint32_t) { atomicAdd(&hist[sym], 1u); });
     if (t == 0u) atomicAdd(&hist[END_OF_BLOCK], 1u);
-    __syncthreads();
-    for (uint32_t s = t; s < NSYM; s += BT) work[s] = hist[s];
-
-    // code lengths: the depths of the Huffman tree; frequencies halved while a depth exceeds 15
-    for (;;) {
-        if (t == 0u) sh_leaves = sh_depth = 0u;
-        __syncthreads();
-        for (uint32_t s = t; s < NSYM; s += BT) { // rank of (weight, symbol) among the symbols in use
-            const uint32_t f = work[s];
-            if (f) {
-                uint32_t rank = 0;
-                for (uint32_t u = 0; u < NSYM; u++) {
-                    const uint32_t g = work[u];
-                    rank += (g != 0u && (g < f || (g == f && u < s))) ? 1u : 0u;
-                }
-                sorted[rank] = (uint16_t)s;
-                atomicAdd(&sh_leaves, 1u);
-            }
-        }
-        __syncthreads();
-        const uint32_t leaves = sh_leaves, root = NSYM + leaves - 2u; // >= 2 leaves: a literal and end-of-block
-        if (t == 0u) { // two queues: the sorted leaves, and the internal nodes in creation order; a leaf goes first on equal weight
-            uint32_t li = 0, ii = 0;
-            for (uint32_t k = 0; k + 1u < leaves; k++) {
-                uint32_t sum = 0;
-                for (int j = 0; j < 2; j++) {
-                    const uint32_t lw = li < leaves ? work[sorted[li]] : 0xFFFFFFFFu, iw = ii < k ? wt[ii] : 0xFFFFFFFFu;
-                    if (lw <= iw) {
-                        parent[sorted[li++]] = (uint16_t)(NSYM + k);
-                        sum += lw;
-                    } else {
-                        parent[NSYM + ii++] = (uint16_t)(NSYM + k);
-                        sum += iw;
-                    }
-                }
-                wt[k] = sum;
-            }
-        }
-        __syncthreads();
-        for (uint32_t s = t; s < NSYM; s += BT) {
-            uint32_t d = 0;
-            if (work[s])
-                for (uint32_t k = s; k != root; k = parent[k]) d++;
-            clen[s] = d;
-            if (d) atomicMax(&sh_depth, d);
-        }
-        __syncthreads();
-        if (sh_depth <= 15u) break;
-        __syncthreads(); // everyone has read sh_depth before it is reset
-        for (uint32_t s = t; s < NSYM; s += BT)
-            if (work[s]) work[s] = (work[s] + 1u) >> 1;
-    }
-
-    // canonical codes (RFC 1951 3.2.2), bit-reversed: deflate packs a Huffman code from its most significant bit
-    if (t < 16u) count[t] = 0u;
-    __syncthreads();
-    for (uint32_t s = t; s < NSYM; s += BT)
-        if (clen[s]) atomicAdd(&count[clen[s]], 1u);
-    __syncthreads();
-    if (t == 0u) {
-        uint32_t code = 0;
-        next_code[0] = 0u;
-        for (uint32_t bits = 1; bits < 16u; bits++) {
-            code = (code + (bits > 1u ? count[bits - 1u] : 0u)) << 1;
-            next_code[bits] = code;
-        }
-    }
-    __syncthreads();
+    huffman_code(hist, hl);
+    const uint32_t* tab = hl.tab;
     for (uint32_t s = t; s < NSYM; s += BT) {
-        const uint32_t l = clen[s];
-        uint32_t e = 0;
+        const uint32_t l = hl.clen[s];
         if (l) {
-            uint32_t code = next_code[l];
-            for (uint32_t u = 0; u < s; u++) code += clen[u] == l ? 1u : 0u;
-            e = (__brev(code) >> (32u - l)) | (l << 16);
             atomicAdd(&sh_bits, hist[s] * (l + symbol_extra_bits(s) + (s > END_OF_BLOCK ? 1u : 0u)));
             if (s > END_OF_BLOCK) atomicAdd(&sh_matches, hist[s]);
         }
-        tab[s] = e;
         or_bits(hdr, CODES_AT + 4u * s, __brev(l) >> 28); // the code-length code: symbol l has the 4-bit code l
     }
     __syncthreads();
@@ -330,13 +180,7 @@ __global__ __launch_bounds__(BT) void k_png_block(const uint8_t* __restrict__ R,
 
     uint32_t bytes;
     if (stored) {
-        uint8_t* out = (uint8_t*)slot;
-        if (t == 0u) {
-            out[0] = final_block ? 1u : 0u;
-            out[1] = (uint8_t)len, out[2] = (uint8_t)(len >> 8);
-            out[3] = (uint8_t)~len, out[4] = (uint8_t)(~len >> 8);
-        }
-        for (uint32_t i = t; i < len; i += BT) out[5u + i] = (uint8_t)byte_at(sw, i);
+        store_block((uint8_t*)slot, sw, len, final_block);
         bytes = len + 5u;
     } else {
         if (t == 0u) {
@@ -449,8 +293,16 @@ PngGeometry png_geometry(uint32_t w, uint32_t h, uint32_t bpp) {
     if (stride > ((uint64_t)1 << 24)) return g.why = "row longer than 2^24 bytes unsupported (32-bit filter costs)", g;
     const uint64_t n = stride * h;
     if (n >= ((uint64_t)1 << 31)) return g.why = "image larger than 2^31 filtered bytes unsupported (32-bit offsets)", g;
-    g.ok = true;
+    g = stream_geometry(n);
     g.stride = (uint32_t)stride;
+    return g;
+}
+
+PngGeometry stream_geometry(uint64_t n) {
+    PngGeometry g = {};
+    if (!n) return g.why = "empty buffer", g;
+    if (n >= ((uint64_t)1 << 31)) return g.why = "buffer of 2^31 bytes or more unsupported (32-bit offsets)", g;
+    g.ok = true;
     g.n = (uint32_t)n;
     g.blocks = (uint32_t)((n + PNG_BLOCK - 1u) / PNG_BLOCK);
     g.off_meta = align16(n);
@@ -476,20 +328,27 @@ const char* png_check_args(uint32_t w, uint32_t h, uint32_t bpp, const uint8_t* 
     return nullptr;
 }
 
+void launch_png_filter(hipStream_t s, uint32_t w, uint32_t h, uint32_t bpp, const uint8_t* d_img, uint8_t* R) {
+    k_png_filter<<<h, 256, 0, s>>>(d_img, w * bpp, bpp, R);
+}
+
+void launch_png_finish(hipStream_t s, const PngGeometry& g, void* d_out, void* d_scratch) {
+    uint8_t* sc = (uint8_t*)d_scratch;
+    const PngMeta* meta = (const PngMeta*)(sc + g.off_meta);
+    uint32_t* offsets = (uint32_t*)(sc + g.off_offsets);
+    uint32_t* totals = (uint32_t*)(sc + g.off_totals);
+    k_png_layout<<<1, BT, 0, s>>>(meta, g.blocks, g.n, offsets, totals, (uint32_t*)d_out);
+    const uint32_t max_words = (uint32_t)((g.bound - PNG_HEADER_BYTES) / 4u);
+    k_png_compact<<<(max_words + 255u) / 256u, 256, 0, s>>>(sc + g.off_slots, offsets, totals, g.blocks, max_words, (uint32_t*)d_out);
+}
+
 hipError_t launch_png_encode(hipStream_t s, uint32_t w, uint32_t h, uint32_t bpp, const uint8_t* d_img, void* d_out, void* d_scratch) {
     const PngGeometry g = png_geometry(w, h, bpp);
     uint8_t* sc = (uint8_t*)d_scratch;
-    uint8_t* R = sc;
-    PngMeta* meta = (PngMeta*)(sc + g.off_meta);
-    uint32_t* offsets = (uint32_t*)(sc + g.off_offsets);
-    uint32_t* totals = (uint32_t*)(sc + g.off_totals);
-    uint8_t* slots = sc + g.off_slots;
-    if (hipError_t e = hipMemsetAsync(slots, 0, (size_t)g.blocks * PNG_SLOT, s)) return e; // the emit ors into zeroed words
-    k_png_filter<<<h, 256, 0, s>>>(d_img, w * bpp, bpp, R);
-    k_png_block<<<g.blocks, BT, 0, s>>>(R, g.n, g.blocks, meta, slots);
-    k_png_layout<<<1, BT, 0, s>>>(meta, g.blocks, g.n, offsets, totals, (uint32_t*)d_out);
-    const uint32_t max_words = (uint32_t)((g.bound - PNG_HEADER_BYTES) / 4u);
-    k_png_compact<<<(max_words + 255u) / 256u, 256, 0, s>>>(slots, offsets, totals, g.blocks, max_words, (uint32_t*)d_out);
+    if (hipError_t e = hipMemsetAsync(sc + g.off_slots, 0, (size_t)g.blocks * PNG_SLOT, s)) return e; // the emit ors into zeroed words
+    launch_png_filter(s, w, h, bpp, d_img, sc);
+    k_png_block<<<g.blocks, BT, 0, s>>>(sc, g.n, g.blocks, (PngMeta*)(sc + g.off_meta), sc + g.off_slots);
+    launch_png_finish(s, g, d_out, d_scratch);
     return hipSuccess;
 }
 

@@ -1143,6 +1143,26 @@ int rayn_hip_png_encode_device(rayn_ctx* ctx, uint32_t w, uint32_t h, uint32_t b
     return post_enqueued(ctx);
 }
 
+// The PNG encoder with LZ77 matches (png_lz.hip): rayn_hip_png_encode_device's arguments and output, smaller streams.
+int rayn_hip_png_encode_lz77_device(rayn_ctx* ctx, uint32_t w, uint32_t h, uint32_t bpp, const uint8_t* d_img, void* d_out, size_t out_bytes,
+                                    void* d_scratch, size_t scratch_bytes, void* hip_stream) {
+    const char* why = png_lz_check_args(w, h, bpp, d_img, d_out, out_bytes, d_scratch, scratch_bytes);
+    hipStream_t s;
+    if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
+    HIPCHK(launch_png_encode_lz77(s, w, h, bpp, d_img, d_out, d_scratch));
+    return post_enqueued(ctx);
+}
+
+// Its deflate stage alone on n bytes of the caller's: a zlib stream behind the same 16-byte header.
+int rayn_hip_deflate_lz77_device(rayn_ctx* ctx, const void* d_data, size_t n, uint32_t stride, void* d_out, size_t out_bytes, void* d_scratch,
+                                 size_t scratch_bytes, void* hip_stream) {
+    const char* why = deflate_check_args(d_data, n, d_out, out_bytes, d_scratch, scratch_bytes);
+    hipStream_t s;
+    if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
+    HIPCHK(launch_deflate_lz77(s, d_data, (uint32_t)n, stride, d_out, d_scratch));
+    return post_enqueued(ctx);
+}
+
 // The temporal accumulate entries: moments == false is the plain one (the moments arguments are then not looked at); resample is step 4's
 // filter (0: the two older entries), bad_resample the resample entry's own complaint about its rp, reported after the shared checks.
 static int temporal_accumulate(rayn_ctx* ctx, const rayn_frame_params* p, const rayn_temporal_params* tp, const rayn_camera* prev_camera,

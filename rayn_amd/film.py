@@ -68,12 +68,13 @@ def _denoise_params(channel_kinds, denoise):
     return denoise.without(_have_mask(channel_kinds))
 
 
-PNG_ENCODERS = ("host", "device")
+PNG_ENCODERS = ("host", "device", "device-lz77")
 
 
 def _check_png(png):
-    """`png` of save_to and render_sequence: "host" (zlib on the host, the files the reference's loop writes) or "device" (the stream of
-    Context.png_encode, framed on the host: smaller files of the same pixels)"""
+    """`png` of save_to and render_sequence: "host" (zlib on the host, the files the reference's loop writes), "device" (the stream of
+    Context.png_encode, framed on the host: smaller files of the same pixels) or "device-lz77" (Context.png_encode_lz77: the same with
+    LZ77 matches, smaller again on smooth and flat images)"""
     if png not in PNG_ENCODERS:
         raise ValueError(f"png must be one of {PNG_ENCODERS}, got {png!r}")
     return png
@@ -91,8 +92,8 @@ class SequencePlan:
     a film without WorldNormal, and None for whatever switched itself off.  variance: `denoise` was given as a VarianceDenoise.
     up_keys: the keys of the planes the upscale rebuilds (None without one).  jobs: [(kind, bytes per pixel, file suffix)] of
     every written image, the suffixes final.  preview: the Preview that takes the render's place, or None.  interpolate: the Interpolate
-    that generates the frames between the rendered keys, or None; interp_keys: the keys of the planes it generates.  png: "host" or
-    "device", where the files' streams are encoded."""
+    that generates the frames between the rendered keys, or None; interp_keys: the keys of the planes it generates.  png: "host",
+    "device" or "device-lz77", where and how the files' streams are encoded."""
     denoise: object
     display: object
     upscale: object
@@ -120,7 +121,7 @@ def plan_sequence(channel_kinds, write_channels, transparent_background=False, d
     only: no context, no torch, no directory.  `interpolate` must be an Interpolate.  It raises ValueError together with `temporal`,
     with `upscale`, with `supersample` and with `preview`: none of these compositions is built.  It raises ValueError with a
     VarianceDenoise, as every sequence without `temporal` does.  It needs the film's Color channel.  It puts _interp right after
-    _color in the name of every Color image of the call, where _temporal would stand.  `png` must be "host" or "device" - checked first -
+    _color in the name of every Color image of the call, where _temporal would stand.  `png` must be one of PNG_ENCODERS - checked first -
     and changes no file name."""
     _check_png(png)
     color = ChannelKind.Color
@@ -638,8 +639,9 @@ class Film:
         extension) the Color image goes through the HDR display transform and its file name gets _display appended:
         {base_name}_color_display.png, {base_name}_color_denoised_display.png.  With png="device" (an extension) the stream inside
         every file is encoded on the device (Context.png_encode: adaptive row filters, run-length and Huffman coding) and framed by
-        image.png_from_stream: the same names and the same pixels in files of other, on rendered images smaller, bytes.  Any other value
-        than "host" and "device" raises ValueError before anything is written."""
+        image.png_from_stream: the same names and the same pixels in files of other, on rendered images smaller, bytes.  png="device-lz77"
+        is the same with the encoder that also finds LZ77 matches (Context.png_encode_lz77).  Any other value raises ValueError before
+        anything is written."""
         _check_png(png)
         os.makedirs(output_folder, exist_ok=True)
         for kind in write_channels:
@@ -657,7 +659,7 @@ class Film:
             with torch.cuda.device(self.device):
                 d_img, bpp = self._pixels_device(kind, transparent_background, denoise, display)
                 d_enc = torch.empty(png_stream_bound(w, h, bpp), dtype=torch.uint8, device=self.device)
-                self.ctx.png_encode(w, h, bpp, d_img, d_enc)
+                self.ctx.png_encode(w, h, bpp, d_img, d_enc, lz77=png == "device-lz77")
                 encoded = d_enc.cpu().numpy()  # waits for the current stream
             with open(path, "wb") as f:
                 f.write(image.png_from_stream(w, h, bpp, image.png_stream_of(encoded)))
@@ -882,7 +884,8 @@ class Film:
         count - is copied into the pinned slot in place of the raw image, and the writer thread frames the stream (image.png_from_stream:
         chunk headers and the CRC-32) and writes the file.  The encoded buffers and the encoder's scratch are allocated once and nothing
         new synchronises.  File names do not change and the files decode to the same pixels; their bytes differ from the host
-        encoder's.  Any other value than "host" and "device" raises ValueError before anything renders.  png="host" is the path
+        encoder's.  png="device-lz77" puts the encoder with LZ77 matches (Context.png_encode_lz77) in the same place, with
+        the same buffers and a larger scratch.  Any other value raises ValueError before anything renders.  png="host" is the path
         described above, unchanged."""
         import concurrent.futures as cf
         import torch
@@ -933,13 +936,13 @@ class Film:
                 d_film = alloc_device_film(w, h, self.device)
                 d_img = [torch.empty(oh * ow * bpp, dtype=torch.uint8, device=self.device) for _, bpp, _ in plan.jobs]
                 post = _SequencePost(self, plan, desc, d_film)
-                on_device = plan.png == "device"
+                on_device, lz77 = plan.png != "host", plan.png == "device-lz77"
                 # what goes to the host per image: the raw image, or the encoder's output (its scratch serves every image in turn)
                 h_bytes = [png_stream_bound(ow, oh, bpp) if on_device else oh * ow * bpp for _, bpp, _ in plan.jobs]
                 h_img = [[torch.empty(n, dtype=torch.uint8, pin_memory=True) for n in h_bytes] for _ in range(2)]
                 if on_device:
                     d_enc = [torch.empty(n, dtype=torch.uint8, device=self.device) for n in h_bytes]
-                    d_png_scratch = torch.empty(max(png_scratch_bytes(ow, oh, bpp) for _, bpp, _ in plan.jobs), dtype=torch.uint8, device=self.device)
+                    d_png_scratch = torch.empty(max((png_scratch_bytes_lz77 if lz77 else png_scratch_bytes)(ow, oh, bpp) for _, bpp, _ in plan.jobs), dtype=torch.uint8, device=self.device)
 
                 def params_of(frame):
                     start = f32(frame) * inv_rate
@@ -977,7 +980,7 @@ class Film:
                     for j, ((kind, bpp, _), d, hbuf) in enumerate(zip(plan.jobs, d_img, h_img[slot])):
                         post.pixels(kind, start, d_shown if kind == ChannelKind.Color else d_base, d, stream.cuda_stream)
                         if on_device:
-                            self.ctx.png_encode(ow, oh, bpp, d, d_enc[j], d_png_scratch, stream.cuda_stream)
+                            self.ctx.png_encode(ow, oh, bpp, d, d_enc[j], d_png_scratch, stream.cuda_stream, lz77)
                             d = d_enc[j]
                         hbuf.copy_(d, non_blocking=True)
                     done = torch.cuda.Event()
