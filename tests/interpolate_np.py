@@ -1,7 +1,12 @@
 """numpy restatement of the frame generation (rayn_hip_interpolate_device; the definition is in include/rayn_hip.h), binary32 operation by
 operation, written from the header text.  It reuses the projection (step 3 of the temporal accumulate), the camera constants and the f32
 helpers of tests/temporal_np.py and shares no code with rayn_amd/csrc/interpolate.hip; tests/test_interpolate_device.py compares the two
-bit for bit.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this."""
+bit for bit.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this.
+
+MUTANTS names the wrong readings of one decision each that tests/reproject_cases.py tells from the statement (interpolate(..., mutant=);
+mutant=None is the statement).  "zc_ge" (temporal_np.EQUIVALENT) is accepted and is no mutant here either: the frame generation uses the
+same projection, whose finiteness test rejects zc = 0 whatever the sign test said (the pinhole and thin-lens keys of
+reproject_cases.interpolate_from_accumulate put zc at 0 and one ulp either side of it)."""
 import numpy as np
 
 from restatement_np import f32
@@ -9,6 +14,11 @@ from temporal_np import MISS, ortho_camera, ortho_plane_gbuffer, project
 
 PLANES = (("color", 3), ("alpha", 1), ("background", 3), ("normal", 3))
 NEG_ZERO = f32(-0.0)
+MUTANTS = ("weight_ge",    # a tap of bilinear weight b == 0 is used (b >= 0)
+           "te_ge",        # orthographic: a point on a key camera's plane is accepted, through the shared projection
+           "depth_lt",     # |t_tap - te| < tol
+           "tie_takes_b")  # tier 2 with neither own pixel usable: wA > wB, so B is taken at the exact half
+EQUIVALENT = ("zc_ge",)
 
 
 class Key:
@@ -23,7 +33,7 @@ def _planes(film, n):
     return {k: np.asarray(film[k], f32).reshape(n, c) for k, c in PLANES if film.get(k) is not None}
 
 
-def _gather(key, width, height, rec, obj, ts, hitables, depth_tolerance):
+def _gather(key, width, height, rec, obj, ts, hitables, depth_tolerance, mutant=None):
     """Steps 1 and 2 for one key: (W (n,), {plane: S (n, c)})."""
     n = width * height
     film = _planes(key.film, n)
@@ -38,7 +48,7 @@ def _gather(key, width, height, rec, obj, ts, hitables, depth_tolerance):
                 m = obj == k
                 for c in range(3):
                     Pp[c] = np.where(m, (rec[:, c] - (f32(vel[c]) * dt).astype(f32)).astype(f32), Pp[c]).astype(f32)
-        ok, fx, fy, te = project(key.camera, key.time, Pp, width, height)
+        ok, fx, fy, te = project(key.camera, key.time, Pp, width, height, mutant if mutant in ("te_ge", "zc_ge") else None)
         ok = np.where(hit, ok, True)
         fx = np.where(hit, fx, xs.reshape(-1).astype(f32)).astype(f32)
         fy = np.where(hit, fy, ys.reshape(-1).astype(f32)).astype(f32)
@@ -55,8 +65,9 @@ def _gather(key, width, height, rec, obj, ts, hitables, depth_tolerance):
             b = ((wx1 if k & 1 else wx0) * (wy1 if k >> 1 else wy0)).astype(f32)
             inside = ok & (qx >= 0) & (qx < width) & (qy >= 0) & (qy < height)
             q = np.where(inside, qx + qy * width, 0)
-            use = inside & (b > 0) & (kobj[q] == obj)
-            use &= np.where(hit, np.abs((krec[q, 3] - te).astype(f32)) <= tol, True)
+            use = inside & (b >= 0 if mutant == "weight_ge" else b > 0) & (kobj[q] == obj)
+            dd = np.abs((krec[q, 3] - te).astype(f32))
+            use &= np.where(hit, dd < tol if mutant == "depth_lt" else dd <= tol, True)
             use &= np.isfinite(film["color"][q]).all(axis=1)
             W = np.where(use, (W + b).astype(f32), W).astype(f32)
             for name, v in film.items():
@@ -64,9 +75,10 @@ def _gather(key, width, height, rec, obj, ts, hitables, depth_tolerance):
     return W, S
 
 
-def interpolate(width, height, key_a, key_b, rec, obj, ts, hitables, depth_tolerance):
+def interpolate(width, height, key_a, key_b, rec, obj, ts, hitables, depth_tolerance, mutant=None):
     """One generated frame: ({plane: (n, c) array} for the planes of the keys' films, source (n,) uint32).  rec (n, 4), obj (n,): the
     frame's own G-buffer at time ts; hitables = [(animated, (vx, vy, vz))] of the world."""
+    assert mutant is None or mutant in MUTANTS + EQUIVALENT, mutant
     n = width * height
     rec, obj = np.asarray(rec, f32).reshape(n, 4), np.asarray(obj, np.uint32).reshape(n)
     fa, fb = _planes(key_a.film, n), _planes(key_b.film, n)
@@ -75,15 +87,16 @@ def interpolate(width, height, key_a, key_b, rec, obj, ts, hitables, depth_toler
         s = f32(f32(f32(ts) - f32(key_a.time)) / f32(f32(key_b.time) - f32(key_a.time)))
         wB = s
         wA = f32(f32(1.0) - s)
-        WA, SA = _gather(key_a, width, height, rec, obj, ts, hitables, depth_tolerance)
-        WB, SB = _gather(key_b, width, height, rec, obj, ts, hitables, depth_tolerance)
+        WA, SA = _gather(key_a, width, height, rec, obj, ts, hitables, depth_tolerance, mutant)
+        WB, SB = _gather(key_b, width, height, rec, obj, ts, hitables, depth_tolerance, mutant)
         validA, validB = WA > 0, WB > 0
         tier1 = validA | validB
         usableA, usableB = np.isfinite(fa["color"]).all(axis=1), np.isfinite(fb["color"]).all(axis=1)
         neither = ~usableA & ~usableB
+        a_wins = wA > wB if mutant == "tie_takes_b" else wA >= wB
         # which keys a pixel takes its value from
-        useA = np.where(tier1, validA, np.where(neither, wA >= wB, usableA))
-        useB = np.where(tier1, validB, np.where(neither, ~(wA >= wB), usableB))
+        useA = np.where(tier1, validA, np.where(neither, a_wins, usableA))
+        useB = np.where(tier1, validB, np.where(neither, ~a_wins, usableB))
         source = np.where(tier1, np.where(validA & validB, 0, np.where(validA, 1, 2)), np.where(usableA & usableB, 3, 4)).astype(np.uint32)
         out = {}
         for name in fa:

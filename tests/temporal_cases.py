@@ -47,6 +47,39 @@ def random_inputs(w, h, seed, cam_kind, adversarial):
     return cur, prev_cam, color, normal, rec, obj, (A, B, N, O)
 
 
+# the Temporal parameter sets of tests/test_temporal_device.py::test_accumulate_matches_the_restatement_on_adversarial_inputs
+ADVERSARIAL_PARAMS = [(4, 0.05, -1.0), (1, 0.05, 0.9), (8, 0.0, 0.5), (3, 1e30, 1.0), (65536, 0.25, -1.0)]
+INTEGRAL_SHIFTS = ((0.0, 0.0), (3.0, 0.0), (-2.25, 0.0), (0.0, 2.0), (0.5, -1.75), (-20.0, 0.0))
+
+
+def older_accumulate_calls():
+    """The arguments of every temporal_np.accumulate call whose result tests/test_temporal_device.py compares the kernel with in
+    test_accumulate_matches_the_restatement_on_adversarial_inputs and test_accumulate_on_exactly_integral_reprojections (111 calls; the
+    calls without a history aside).  A COPY of those two tests' loops, for tests/test_reproject_cases.py to measure what their inputs can
+    see: whoever changes the loops there changes them here (both tests carry a note), and the count asserted there guards the copy."""
+    import scenes
+    wd, _, _ = scenes.scene("s1", (40, 24), moving=True)
+    hit = T.world_hitables(wd)
+    for cam_kind in (0, 1, 2):
+        for si, (w, h) in enumerate(SIZES + [(1, 1), (17, 13)]):
+            for adversarial in (False, True):
+                cur, prev_cam, color, normal, rec, obj, prev = random_inputs(w, h, 10 * si + adversarial, cam_kind, adversarial)
+                for tp in ADVERSARIAL_PARAMS[(si + adversarial) % 2::2] if w > 17 else ADVERSARIAL_PARAMS:
+                    yield (w, h, color, normal, rec, obj, prev, prev_cam, 0.25, 0.75, hit, *tp)
+    w, h = 16, 8
+    rec, obj, normal = T.ortho_plane_gbuffer(w, h)
+    rng = np.random.default_rng(3)
+    for sx, sy in INTEGRAL_SHIFTS:
+        prev_cam = T.ortho_camera(w, h, origin_x=-sx * 0.125)
+        prev_cam.origin.y = prev_cam.at.y = -sy * 0.125
+        prev_rec, _, _ = T.ortho_plane_gbuffer(w, h, origin_x=-sx * 0.125)
+        prev_rec[:, 1] -= f32(sy * 0.125)
+        A = np.concatenate([rng.random((w * h, 3)), np.full((w * h, 1), 3.0)], axis=1).astype(f32)
+        prev = (A, prev_rec, np.concatenate([normal, np.zeros((w * h, 1), f32)], axis=1), obj)
+        color = rng.random((w * h, 3)).astype(f32)
+        yield (w, h, color, normal, rec, obj, prev, prev_cam, 0.0, 0.0, [], 3, 0.05, 0.9)
+
+
 def pack_inputs(w, h, seed):
     """Synthetic inputs of the denoise entry: a patchwork of objects with misses, history lengths 0, 1, 3, 3.5, 4, 8 and NaN side by side,
     special values over colour, guides and moments."""

@@ -1,7 +1,16 @@
 """numpy restatement of the temporal accumulation (rayn_hip_temporal_accumulate_device; the definition is in include/rayn_hip.h) and of
 the G-buffer's assembly P = o + t * d, binary32 operation by operation with the f32 helpers of tests/restatement_np.py.  It shares no code
 with rayn_amd/csrc/temporal.hip; tests/test_temporal_device.py compares the two bit for bit.  TEST INFRASTRUCTURE: nothing under rayn_amd/
-imports this."""
+imports this.
+
+MUTANTS names the wrong readings of one decision each that the cases of tests/reproject_cases.py have to tell from the statement
+(project(..., mutant=) and accumulate(..., mutant=); mutant=None is the statement).  EQUIVALENT names two readings that look wrong and
+are not - no input tells them from the statement, so they are accepted by the functions (tests/test_reproject_cases.py holds every case
+to it) and kept out of MUTANTS:
+  zc_ge  perspective `zc > 0` read as `zc >= 0`.  zc = +-0 makes the divisor zc * half_w a zero, so uvx is +-inf or (0 / 0) NaN, and so
+         is fx = uvx * width - 0.5: the projection is rejected by its finiteness test whatever the sign test said.
+  w_ge   `W > 0` read as `W >= 0`.  The bilinear weights are >= 0, so W = 0 means every tap that counted had weight 0: S = 0 (or NaN),
+         h = S / W = 0 / 0 is NaN, the blend is not finite and the pixel resets exactly as it does for W <= 0."""
 import math
 
 import numpy as np
@@ -9,6 +18,21 @@ import numpy as np
 from restatement_np import PI, f32, vscale, vsub
 
 MISS = np.uint32(0xFFFFFFFF)
+MUTANTS = ("depth_lt",             # |t_tap - te| < tol
+           "normal_gt",            # dot(nrm, nrm_tap) > normal_min
+           "ntap_gt",              # n_tap > 1
+           "normal_switch_ge",     # the normal test stays on at normal_min == -1
+           "te_ge",                # orthographic: a point on the camera plane is accepted (te >= 0)
+           "fmin_is_minimum",      # n' = min(nh + 1, max_history) with a NaN nh propagating
+           "cap_after_add",        # n' = fmin(nh, max_history) + 1
+           "tap_inside_le",        # a tap counts as inside up to qx == width and qy == height (read from the clamped pixel)
+           "zero_weight_skipped",  # a tap of weight 0 does not count (k_interpolate's and k_upscale's rule)
+           "reset_keeps_length")   # n' = 1 for a colour that is not finite
+EQUIVALENT = ("zc_ge", "w_ge")
+
+
+def _known(mutant):
+    assert mutant is None or mutant in MUTANTS + EQUIVALENT, mutant
 
 
 # ---- the definition's own vector forms (NOT rayn's: no mul_add, a plain left-to-right dot) ------------------------------------------------
@@ -69,8 +93,9 @@ def join_history(A, B, N, O):
                            np.ascontiguousarray(N, f32).reshape(-1).view(np.uint8), np.ascontiguousarray(O, np.uint32).reshape(-1).view(np.uint8)])
 
 
-def project(cam, ts_prev, Pp, width, height):
+def project(cam, ts_prev, Pp, width, height, mutant=None):
     """Step 3 for the points Pp (three arrays): (ok, fx, fy, te)."""
+    _known(mutant)
     half_w, half_h, full_w, full_h = camera_constants(cam)
     ts = f32(ts_prev)
 
@@ -92,14 +117,14 @@ def project(cam, ts_prev, Pp, width, height):
             uvx = (dot(q, u) / full_w).astype(f32)
             uvy = (dot(q, v) / full_h).astype(f32)
             te = dot(q, w).astype(f32)
-            ok = te > 0
+            ok = te >= 0 if mutant == "te_ge" else te > 0
         else:
             w = nz(vsub(o, at))
             u = nz(cross(up, w))
             v = cross(w, u)
             q = vsub(Pp, o)
             zc = (-dot(q, w)).astype(f32)
-            ok = zc > 0
+            ok = zc >= 0 if mutant == "zc_ge" else zc > 0
             uvx = (((dot(q, u) / (zc * half_w).astype(f32)).astype(f32) + f32(1.0)).astype(f32) * f32(0.5)).astype(f32)
             uvy = (((dot(q, v) / (zc * half_h).astype(f32)).astype(f32) + f32(1.0)).astype(f32) * f32(0.5)).astype(f32)
             te = np.sqrt(dot(q, q)).astype(f32)
@@ -110,16 +135,17 @@ def project(cam, ts_prev, Pp, width, height):
 
 
 def accumulate(width, height, color, normal, rec, obj, prev, prev_cam, prev_time, cur_time, hitables, max_history, depth_tolerance, normal_min,
-               want_taps=False):
+               want_taps=False, mutant=None):
     """One temporal accumulate.  color / normal (n, 3), rec (n, 4), obj (n,) of the current frame; prev = the previous history as
     (A, B, N, O) or None; hitables = [(animated, (vx, vy, vz))] of the world.  Returns (out colour (n, 3), (A', B', N', O')) and, with
     want_taps, also the per-pixel summed tap weight W (0 where the pixel reset before its taps)."""
+    _known(mutant)
     n = width * height
     color, normal = np.asarray(color, f32).reshape(n, 3), np.asarray(normal, f32).reshape(n, 3)
     rec, obj = np.asarray(rec, f32).reshape(n, 4), np.asarray(obj, np.uint32).reshape(n)
     cfin = np.isfinite(color).all(axis=1)
     out = color.copy()
-    nn = np.where(cfin, f32(1.0), f32(0.0)).astype(f32)
+    nn = np.where(cfin, f32(1.0), f32(1.0 if mutant == "reset_keeps_length" else 0.0)).astype(f32)
     Wsum = np.zeros(n, f32)
     go = cfin & (obj != MISS)
     if prev is not None and go.any():
@@ -133,7 +159,7 @@ def accumulate(width, height, color, normal, rec, obj, prev, prev_cam, prev_time
                     m = obj == k
                     for c in range(3):
                         Pp[c] = np.where(m, (rec[:, c] - (f32(vel[c]) * dt).astype(f32)).astype(f32), Pp[c]).astype(f32)
-            ok, fx, fy, te = project(prev_cam, prev_time, Pp, width, height)
+            ok, fx, fy, te = project(prev_cam, prev_time, Pp, width, height, mutant)
             ok = ok & go
             x0f, y0f = np.floor(fx).astype(f32), np.floor(fy).astype(f32)
             wx1, wy1 = (fx - x0f).astype(f32), (fy - y0f).astype(f32)
@@ -146,20 +172,32 @@ def accumulate(width, height, color, normal, rec, obj, prev, prev_cam, prev_time
                 qx, qy = x0 + (k & 1), y0 + (k >> 1)
                 inside = ok & (qx >= 0) & (qx < width) & (qy >= 0) & (qy < height)
                 q = np.where(inside, qx + qy * width, 0)
+                if mutant == "tap_inside_le":
+                    inside = ok & (qx >= 0) & (qx <= width) & (qy >= 0) & (qy <= height)
+                    q = np.where(inside, np.minimum(qx, width - 1) + np.minimum(qy, height - 1) * width, 0)
                 a = pA[q]
-                use = inside & (a[:, 3] >= f32(1.0)) & (pO[q] == obj) & (np.abs((pB[q, 3] - te).astype(f32)) <= tol)
-                if f32(normal_min) > f32(-1.0):
+                dd = np.abs((pB[q, 3] - te).astype(f32))
+                use = inside & (a[:, 3] > f32(1.0) if mutant == "ntap_gt" else a[:, 3] >= f32(1.0)) & (pO[q] == obj)
+                use &= dd < tol if mutant == "depth_lt" else dd <= tol
+                if f32(normal_min) >= f32(-1.0) if mutant == "normal_switch_ge" else f32(normal_min) > f32(-1.0):
                     nq = pN[q]
-                    use &= dot([normal[:, 0], normal[:, 1], normal[:, 2]], [nq[:, 0], nq[:, 1], nq[:, 2]]) >= f32(normal_min)
+                    dn = dot([normal[:, 0], normal[:, 1], normal[:, 2]], [nq[:, 0], nq[:, 1], nq[:, 2]])
+                    use &= dn > f32(normal_min) if mutant == "normal_gt" else dn >= f32(normal_min)
                 w = ((wx1 if k & 1 else wx0) * (wy1 if k >> 1 else wy0)).astype(f32)
+                if mutant == "zero_weight_skipped":
+                    use &= w > 0
                 W = np.where(use, (W + w).astype(f32), W).astype(f32)
                 for c in range(3):
                     S[:, c] = np.where(use, (S[:, c] + (w * a[:, c]).astype(f32)).astype(f32), S[:, c])
                 N = np.where(use, (N + (w * a[:, 3]).astype(f32)).astype(f32), N).astype(f32)
-            have = ok & (W > 0)
+            have = ok & (W >= 0 if mutant == "w_ge" else W > 0)
             h = (S / W[:, None]).astype(f32)
             nh = (N / W).astype(f32)
             n1 = np.fmin((nh + f32(1.0)).astype(f32), f32(max_history)).astype(f32)
+            if mutant == "fmin_is_minimum":
+                n1 = np.minimum((nh + f32(1.0)).astype(f32), f32(max_history)).astype(f32)
+            elif mutant == "cap_after_add":
+                n1 = (np.fmin(nh, f32(max_history)).astype(f32) + f32(1.0)).astype(f32)
             al = (f32(1.0) / n1).astype(f32)
             b = (h + (al[:, None] * (color - h).astype(f32)).astype(f32)).astype(f32)
             take = have & np.isfinite(b).all(axis=1)

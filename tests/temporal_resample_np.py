@@ -1,7 +1,11 @@
 """numpy restatement of the temporal accumulate with a choice of the history resampling filter (rayn_hip_temporal_accumulate_resample_device;
 the definition is in include/rayn_hip.h), binary32 operation by operation.  Steps 1 - 3 and 5 and the bilinear arm are temporal_np's and
 temporal_variance_np's; the Catmull-Rom arm of step 4 is written here from the definition and shares no code with rayn_amd/csrc.
-tests/test_temporal_resample_device.py compares the kernels with it bit for bit.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this."""
+tests/test_temporal_resample_device.py compares the kernels with it bit for bit.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this.
+
+MUTANTS names wrong readings of the Catmull-Rom arm alone (accumulate(..., mutant=), without moments; mutant=None is the statement): the
+bilinear arm and steps 1 - 3 stay temporal_np's unmutated ones, which is the drift the kernel's two copies of the predicate are free to
+take.  tests/reproject_cases.py has the cases that tell each from the statement."""
 import numpy as np
 
 import temporal_np as T
@@ -10,6 +14,12 @@ import temporal_variance_np as TV
 f32 = np.float32
 MISS = T.MISS
 ARM_RESET, ARM_BILINEAR, ARM_CUBIC = 0, 1, 2
+MUTANTS = ("depth_lt",          # the footprint's copy of the predicate: |t_tap - te| < tol
+           "normal_gt",         # its dot(nrm, nrm_tap) > normal_min
+           "ntap_gt",           # its n_tap > 1
+           "footprint_le",      # x0 < 0, x0 + 2 > width (and y): a footprint one pixel over the border counts, read from the clamped pixel
+           "clamp_outer",       # the anti-ringing range over all 16 taps
+           "length_unfloored")  # nh = N / W without the fmaxf(., 1)
 
 
 def cubic_weights(t):
@@ -48,14 +58,14 @@ def clamp(v, lo, hi):
 
 
 def accumulate(width, height, color, normal, rec, obj, prev, prev_moments, prev_cam, prev_time, cur_time, hitables, max_history, depth_tolerance,
-               normal_min, resample, want_unclamped=False):
+               normal_min, resample, want_unclamped=False, mutant=None):
     """One temporal accumulate through the resample entry.  Arguments as temporal_variance_np.accumulate (prev_moments None and prev given:
     no moments, as temporal_np.accumulate), plus resample (0 bilinear, 1 Catmull-Rom) and `moments` implied by prev_moments / with_moments.
     Returns (out colour (n, 3), (A', B', N', O'), moments (n, 2) or None, arm (n,)): arm 0 the pixel reset, 1 it blended the bilinear taps,
     2 it blended the Catmull-Rom footprint.  With want_unclamped also the cubic arm's h before the anti-ringing clamp ((n, 3); NaN
     outside arm 2)."""
     return _accumulate(width, height, color, normal, rec, obj, prev, prev_moments, prev_moments is not None, prev_cam, prev_time, cur_time, hitables,
-                       max_history, depth_tolerance, normal_min, resample, want_unclamped)
+                       max_history, depth_tolerance, normal_min, resample, want_unclamped, mutant)
 
 
 def accumulate_first(width, height, color, normal, rec, obj, with_moments, max_history=4, depth_tolerance=0.05, normal_min=-1.0, resample=0):
@@ -65,8 +75,8 @@ def accumulate_first(width, height, color, normal, rec, obj, with_moments, max_h
 
 
 def _accumulate(width, height, color, normal, rec, obj, prev, prev_moments, with_moments, prev_cam, prev_time, cur_time, hitables, max_history,
-                depth_tolerance, normal_min, resample, want_unclamped):
-    assert resample in (0, 1)
+                depth_tolerance, normal_min, resample, want_unclamped, mutant=None):
+    assert resample in (0, 1) and (mutant is None or (mutant in MUTANTS and not with_moments))
     n = width * height
     # the bilinear result everywhere: steps 1 - 5 of the existing definitions
     if with_moments:
@@ -119,11 +129,16 @@ def _accumulate(width, height, color, normal, rec, obj, prev, prev_moments, with
                 qx, qy = x0 + i, y0 + j
                 counts = ok & (qx >= 0) & (qx < width) & (qy >= 0) & (qy < height)
                 q = np.where(counts, qx + qy * width, 0)
-                counts &= pA[q, 3] >= f32(1.0)
+                if mutant == "footprint_le":
+                    counts = ok & (x0 >= 0) & (x0 + 2 <= width) & (y0 >= 0) & (y0 + 2 <= height)
+                    q = np.where(counts, np.clip(qx, 0, width - 1) + np.clip(qy, 0, height - 1) * width, 0)
+                dd = np.abs((pB[q, 3] - te).astype(f32))
+                counts &= pA[q, 3] > f32(1.0) if mutant == "ntap_gt" else pA[q, 3] >= f32(1.0)
                 counts &= pO[q] == obj
-                counts &= np.abs((pB[q, 3] - te).astype(f32)) <= tol
+                counts &= dd < tol if mutant == "depth_lt" else dd <= tol
                 if f32(normal_min) > f32(-1.0):
-                    counts &= T.dot([normal[:, 0], normal[:, 1], normal[:, 2]], [pN[q, 0], pN[q, 1], pN[q, 2]]) >= f32(normal_min)
+                    dn = T.dot([normal[:, 0], normal[:, 1], normal[:, 2]], [pN[q, 0], pN[q, 1], pN[q, 2]])
+                    counts &= dn > f32(normal_min) if mutant == "normal_gt" else dn >= f32(normal_min)
                 full &= counts
                 w = (kx[i + 1] * ky[j + 1]).astype(f32)
                 W = (W + w).astype(f32)
@@ -133,11 +148,11 @@ def _accumulate(width, height, color, normal, rec, obj, prev, prev_moments, with
                 if with_moments:
                     S1 = (S1 + (w * pM[q, 0]).astype(f32)).astype(f32)
                     S2 = (S2 + (w * pM[q, 1]).astype(f32)).astype(f32)
-                if i in (0, 1) and j in (0, 1):
+                if (i in (0, 1) and j in (0, 1)) or mutant == "clamp_outer":
                     inner.append(q)
         h = (S / W[:, None]).astype(f32)
         unclamped[full] = h[full]
-        nh = fmaxf((N / W).astype(f32), f32(1.0))
+        nh = (N / W).astype(f32) if mutant == "length_unfloored" else fmaxf((N / W).astype(f32), f32(1.0))
 
         def ranged(v, plane, c):
             lo, hi = plane[inner[0], c], plane[inner[0], c]

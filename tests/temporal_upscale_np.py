@@ -3,7 +3,11 @@ upscaling's tiers on a footprint that may come from a projection through the low
 temporal accumulate at the high size with that confidence in its blend - binary32 operation by operation, tap by tap in the definition's
 order; only the pixels are vectorised.  The camera projection (step 3 of the accumulate), its constants and the history layout are
 imported from tests/temporal_np.py, expf from the oracle (denoise_np.oracle_expf); everything else is restated here.  It shares no code
-with rayn_amd/csrc/temporal_upscale.hip.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this."""
+with rayn_amd/csrc/temporal_upscale.hip.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this.
+
+MUTANTS names the wrong readings of one decision each that tests/reproject_cases.py tells from the statement (temporal_upscale(...,
+mutant=); mutant=None is the statement): the temporal predicates phase C shares with the accumulate, and the confidence rule where tier 1
+added taps and still summed to Wg == 0 - `S.W > 0` fails, tier 2 gives the value, and conf is TIER 2's largest b."""
 import numpy as np
 
 from denoise_np import oracle_expf
@@ -11,6 +15,9 @@ from temporal_np import MISS, dot, project
 
 f32 = np.float32
 PLANES = (("color", 3), ("alpha", 1), ("background", 3), ("normal", 3))
+MUTANTS = ("depth_lt", "normal_gt", "ntap_gt", "te_ge",  # temporal_np's readings, in phase C
+           "fmin_is_minimum",                            # n' = min(nh + conf, max_history) with a NaN nh propagating
+           "conf_keeps_tier1")                           # conf stays tier 1's largest b when Wg == 0 sent the pixel to tier 2
 
 
 def _origin(x0f):
@@ -38,7 +45,7 @@ def footprint(width, height, factor, high_g, low_cam, time_start):
 
 
 def temporal_upscale(film, low_g, high_g, width, height, factor, sigma_plane, sigma_position, low_cam, time_start, confidence, prev, prev_cam,
-                     prev_time, hitables, max_history, depth_tolerance, normal_min):
+                     prev_time, hitables, max_history, depth_tolerance, normal_min, mutant=None):
     """One call.  film: the low film's planes ("color" and "normal" required, "alpha" / "background" optional), pixel x + y * width;
     low_g / high_g: (records, objects) of the G-buffers; low_cam: an _abi.Camera or None; prev: the previous HIGH history as (A, B, N, O)
     or None, with prev_cam and prev_time; hitables = [(animated, (vx, vy, vz))].  Returns (planes of the high film - "color" the
@@ -46,6 +53,7 @@ def temporal_upscale(film, low_g, high_g, width, height, factor, sigma_plane, si
     1..3 per pixel, "conf", "frame_color": this frame's upscaled Color, "taps": the summed history tap weight (0 where the pixel reset
     before its taps), "n": the new history length, "projected": pixels whose footprint came from the projection, "rejected": history
     taps inside the image that failed a test}."""
+    assert mutant is None or mutant in MUTANTS, mutant
     w, h, s = int(width), int(height), int(factor)
     W, H = w * s, h * s
     n, N = w * h, W * H
@@ -114,6 +122,8 @@ def temporal_upscale(film, low_g, high_g, width, height, factor, sigma_plane, si
             frame[key] = a
         weight = np.where(t1, Wg, f32(0.0)).astype(f32)
         conf = np.where(t1, bg, np.where(t2, bb, f32(1.0))).astype(f32) if confidence else np.ones(N, f32)
+        if confidence and mutant == "conf_keeps_tier1":
+            conf = np.where(t2 & (bg > 0), bg, conf).astype(f32)
 
         # ---- C: the accumulate at the high size, conf in step 5
         c, nrm = frame["color"], frame["normal"]
@@ -133,7 +143,7 @@ def temporal_upscale(film, low_g, high_g, width, height, factor, sigma_plane, si
                     m = hobj == k
                     for a in range(3):
                         Pp[a] = np.where(m, (hrec[:, a] - (f32(vel[a]) * dt).astype(f32)).astype(f32), Pp[a]).astype(f32)
-            ok, hx, hy, te = project(prev_cam, prev_time, Pp, W, H)
+            ok, hx, hy, te = project(prev_cam, prev_time, Pp, W, H, "te_ge" if mutant == "te_ge" else None)
             ok = ok & go
             X0f, Y0f = np.floor(hx).astype(f32), np.floor(hy).astype(f32)
             vx1, vy1 = (hx - X0f).astype(f32), (hy - Y0f).astype(f32)
@@ -146,10 +156,13 @@ def temporal_upscale(film, low_g, high_g, width, height, factor, sigma_plane, si
                 inside = ok & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
                 q = np.where(inside, qx + qy * W, 0)
                 a = pA[q]
-                use = inside & (a[:, 3] >= f32(1.0)) & (pO[q] == hobj) & (np.abs((pB[q, 3] - te).astype(f32)) <= tol)
+                dd = np.abs((pB[q, 3] - te).astype(f32))
+                use = inside & (a[:, 3] > f32(1.0) if mutant == "ntap_gt" else a[:, 3] >= f32(1.0)) & (pO[q] == hobj)
+                use &= dd < tol if mutant == "depth_lt" else dd <= tol
                 if f32(normal_min) > f32(-1.0):
                     nq = pN[q]
-                    use &= dot([nrm[:, 0], nrm[:, 1], nrm[:, 2]], [nq[:, 0], nq[:, 1], nq[:, 2]]) >= f32(normal_min)
+                    dn = dot([nrm[:, 0], nrm[:, 1], nrm[:, 2]], [nq[:, 0], nq[:, 1], nq[:, 2]])
+                    use &= dn > f32(normal_min) if mutant == "normal_gt" else dn >= f32(normal_min)
                 rejected |= inside & ~use
                 wt = ((vx1 if k & 1 else vx0) * (vy1 if k >> 1 else vy0)).astype(f32)
                 Wh = np.where(use, (Wh + wt).astype(f32), Wh).astype(f32)
@@ -159,7 +172,7 @@ def temporal_upscale(film, low_g, high_g, width, height, factor, sigma_plane, si
             have = ok & (Wh > 0)
             hcol = (S / Wh[:, None]).astype(f32)
             nh = (Nh / Wh).astype(f32)
-            n1 = np.fmin((nh + conf).astype(f32), f32(max_history)).astype(f32)
+            n1 = (np.minimum if mutant == "fmin_is_minimum" else np.fmin)((nh + conf).astype(f32), f32(max_history)).astype(f32)
             al = (conf / n1).astype(f32)
             bl = (hcol + (al[:, None] * (c - hcol).astype(f32)).astype(f32)).astype(f32)
             take = have & np.isfinite(bl).all(axis=1)

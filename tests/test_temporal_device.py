@@ -112,6 +112,7 @@ def test_accumulate_matches_the_restatement_on_adversarial_inputs(ctx, cam_kind)
     """Random and adversarial frames and histories (NaN and inf colours, positions, depths and history lengths, t = +inf, misses) under
     cameras that have translated and rotated so that taps straddle every image border, for every film size, with max_history 1, a history at
     the cap, and each test on and off."""
+    # temporal_cases.older_accumulate_calls copies this loop (what these inputs can see is measured in tests/test_reproject_cases.py): change both
     import rayn_amd as R
     wd, _, _ = scenes.scene("s1", (40, 24), moving=True)  # hitables 1 (the fractal) and one sphere are animated: object motion is exercised too
     ctx.upload_world(wd)
@@ -136,6 +137,7 @@ def test_accumulate_matches_the_restatement_on_adversarial_inputs(ctx, cam_kind)
 def test_accumulate_on_exactly_integral_reprojections(ctx):
     """The exact orthographic case: fx and fy are integers, so one tap has weight 1 and three have weight 0 (they still count: 0 * c_tap);
     camera shifts by whole and quarter pixels across all four borders; a history that has reached the cap stays there."""
+    # temporal_cases.older_accumulate_calls copies this loop as well: change both
     import rayn_amd as R
     wd, _, _ = scenes.scene("s0", (16, 8))
     ctx.upload_world(wd)

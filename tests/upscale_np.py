@@ -2,21 +2,29 @@
 float32 and tap by tap in the definition's order, so that the tests can compare the kernel with it bit for bit; only the pixels are
 vectorised.  expf is the pinned dm_expf of include/rayn_detmath.h, evaluated by the oracle (denoise_np.oracle_expf).  dtype=np.float64
 reads the same formulas in float64 with numpy's exp: a cross-check of the definition, not bit-exact.  It shares no code with
-rayn_amd/csrc/upscale.hip.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this."""
+rayn_amd/csrc/upscale.hip.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this.
+
+MUTANTS names the wrong readings of one decision each that tests/reproject_cases.py tells from the statement (upscale(..., mutant=);
+mutant=None is the statement)."""
 import numpy as np
 
 from denoise_np import oracle_expf
 
 MISS = np.uint32(0xFFFFFFFF)
+MUTANTS = ("weight_ge",          # a tap of bilinear weight b == 0 is used (b >= 0)
+           "nan_weight_counts",  # a NaN guided weight is added instead of skipped
+           "tier1_any_match",    # tier 1 is taken as soon as a tap matched, even with Wg == 0 (every expf(-e) underflowed)
+           "tier2_skipped")      # a failed tier 1 falls straight to tier 3
 PLANES = (("color", 3), ("alpha", 1), ("background", 3), ("normal", 3))
 
 
-def upscale(film, low_g, high_g, width, height, factor, sigma_plane, sigma_position, dtype=np.float32, bilinear=False):
+def upscale(film, low_g, high_g, width, height, factor, sigma_plane, sigma_position, dtype=np.float32, bilinear=False, mutant=None):
     """film: {"color": (n, 3), "alpha": (n,), "background": (n, 3), "normal": (n, 3)} of the width x height low film, pixel x + y * width;
     alpha / background / normal may be absent (normal only with sigma_plane == 0).  low_g / high_g: (records (., 4), objects (.,)) of the
     G-buffers at the low and at the high resolution.  bilinear: take tier 2 (the unguided weights) for every pixel, whatever the guides
     say - the plain bilinear reading of the film.  Returns (planes dict of the high film, weight (N,), tier (N,) uint8 in 1..3, the
     largest exponent e of a tap that counted)."""
+    assert mutant is None or mutant in MUTANTS, mutant
     f = np.dtype(dtype).type
     expf = oracle_expf if f is np.float32 else np.exp
     w, h, s = int(width), int(height), int(factor)
@@ -56,7 +64,7 @@ def upscale(film, low_g, high_g, width, height, factor, sigma_plane, sigma_posit
                 inside = (qx >= 0) & (qx < w) & (qy >= 0) & (qy < h)
                 q = np.where(inside, qx + qy * w, 0)
                 b = (wx1 if k & 1 else wx0) * (wy1 if k >> 1 else wy0)
-                yield q, b, inside & (b > 0) & fin_low[q]
+                yield q, b, inside & (b >= 0 if mutant == "weight_ge" else b > 0) & fin_low[q]
 
         def add(use, g, q, Wt, St):
             Wt = np.where(use, Wt + g, Wt)
@@ -65,6 +73,7 @@ def upscale(film, low_g, high_g, width, height, factor, sigma_plane, sigma_posit
             return Wt
 
         emax = 0.0
+        matched = np.zeros(N, bool)
         Wg, Sg = sums()
         if not bilinear:
             for q, b, usable in taps():
@@ -79,15 +88,16 @@ def upscale(film, low_g, high_g, width, height, factor, sigma_plane, sigma_posit
                     dps = dot(d, d) * (inv_t * inv_t)
                     e = e + dps * ks if use_p else dps * ks
                 g = np.where(hit, b * expf(-e).astype(f), b)
-                use = match & ~np.isnan(g)
+                use = match if mutant == "nan_weight_counts" else match & ~np.isnan(g)
+                matched |= use
                 if (use & hit).any():
                     emax = max(emax, float(np.max(e[use & hit])))
                 Wg = add(use, g, q, Wg, Sg)
         Wb, Sb = sums()
         for q, b, usable in taps():
             Wb = add(usable, b, q, Wb, Sb)
-        t1 = Wg > 0
-        t2 = ~t1 & (Wb > 0)
+        t1 = matched if mutant == "tier1_any_match" else Wg > 0
+        t2 = ~t1 & (Wb > 0) & (mutant != "tier2_skipped")
         qc = np.minimum(Xi // s, w - 1) + np.minimum(Yi // s, h - 1) * w
         out = {}
         for key in val:
