@@ -11,6 +11,16 @@ def case(name, width, height, samples, bounces, **kw):
     return world.to_desc(cam), P.frame_params(width, height, samples, bounces, **kw)
 
 
+def above(v):
+    """the next float32 above v"""
+    return np.nextafter(np.float32(v), np.float32(np.inf))
+
+
+def below(v):
+    """the next float32 below v"""
+    return np.nextafter(np.float32(v), np.float32(-np.inf))
+
+
 def film_l2(a, b):
     """max over pixels of the per-pixel L2 distance over all 10 film floats (the north_star metric,
     applied to every channel)."""

@@ -5,6 +5,10 @@ float64 with numpy's exp (a cross-check of the float32 reading, not bit-exact)."
 import numpy as np
 
 H_TAPS = (1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0)
+# Wrong readings, for tests/post_edge_cases.py (mutant=None: the definition's bits).  border_le: a tap one step beyond the last row or
+# column still counts (it reads the edge pixel); nan_weight_counts: a tap whose weight is NaN is added like any other.
+# zero_weight_skipped: a tap of weight 0 is left out, where the definition adds its +0 (a sum of -0.0 becomes +0).
+MUTANTS = ("border_le", "nan_weight_counts", "zero_weight_skipped")
 
 
 def oracle_expf(x):
@@ -12,7 +16,7 @@ def oracle_expf(x):
     return oracle_py.detmath(0, np.ascontiguousarray(x, np.float32).reshape(-1)).reshape(np.shape(x))
 
 
-def atrous(color, alpha, normal, width, height, iterations, sigma_color, sigma_normal, sigma_alpha, dtype=np.float32):
+def atrous(color, alpha, normal, width, height, iterations, sigma_color, sigma_normal, sigma_alpha, dtype=np.float32, mutant=None):
     """color / normal: width * height * 3 floats, alpha: width * height floats (pixel x + y * width); a guide whose sigma is 0 is not
     read and may be None.  Returns the filtered colour, shape (width * height, 3)."""
     f = np.dtype(dtype).type
@@ -39,6 +43,8 @@ def atrous(color, alpha, normal, width, height, iterations, sigma_color, sigma_n
                         continue
                     qy, qx = ys + ky * step, xs + kx * step
                     inside = (qy >= 0) & (qy < h) & (qx >= 0) & (qx < w)
+                    if mutant == "border_le":
+                        inside = (qy >= 0) & (qy <= h) & (qx >= 0) & (qx <= w)
                     qy, qx = np.clip(qy, 0, h - 1), np.clip(qx, 0, w - 1)
                     cq = c[qy, qx]
                     ok = inside & np.isfinite(cq).all(-1)
@@ -53,7 +59,10 @@ def atrous(color, alpha, normal, width, height, iterations, sigma_color, sigma_n
                         d = a - a[qy, qx]
                         e = e + (d * d) * ka
                     wt = f(H_TAPS[ky + 2] * H_TAPS[kx + 2]) * expf(-e).astype(f)
-                    ok &= ~np.isnan(wt)
+                    if mutant != "nan_weight_counts":
+                        ok &= ~np.isnan(wt)
+                    if mutant == "zero_weight_skipped":
+                        ok &= wt != 0
                     W = np.where(ok, W + wt, W)
                     S = np.where(ok[..., None], S + wt[..., None] * cq, S)
             out = S / W[..., None]

@@ -9,10 +9,21 @@ from denoise_np import H_TAPS, oracle_expf
 from progressive_np import tile_rects
 
 LUMA = (0.2126, 0.7152, 0.0722)
+# Wrong readings, for tests/post_edge_cases.py (mutant=None: the definition's bits).  Of the initial variance - v_gt0: guided needs
+# v > 0; fnn_u32: n (n - 1) in 32 bits before the conversion.  Of the passes - border_le: a tap one step beyond the last row or column
+# still counts (it reads the edge pixel), in the 5x5 stencil and in the 3x3 pre-filter; nan_weight_counts: a tap whose weight is NaN is
+# added like any other.
+# zero_weight_skipped: a tap of weight 0 is left out, where the definition adds its +0 (a sum of -0.0 becomes +0).
+# prefilter_counts_unguided: the 3x3 pre-filter of the variance adds a neighbour that is not guided (its v is NaN) like any other.
+MUTANTS = ("v_gt0", "fnn_u32", "border_le", "nan_weight_counts", "zero_weight_skipped", "prefilter_counts_unguided")
+# n_ge1 (a tile with ONE epoch may be guided): n = 1 divides m2 by (float)0 = +0, which gives an infinity or a NaN for every m2, and a v
+# that is not finite is not guided: the reading changes no bit.  (In the accumulate kernel the same reading computes
+# e = sqrtf(m2 / 0) / ...: after one epoch m2 is +0 or NaN - d (y - mean) with mean = y - so e is NaN, in neither count: equivalent too.)
+EQUIVALENT = ("n_ge1",)
 K3 = ((1.0 / 16.0, 1.0 / 8.0, 1.0 / 16.0), (1.0 / 8.0, 1.0 / 4.0, 1.0 / 8.0), (1.0 / 16.0, 1.0 / 8.0, 1.0 / 16.0))  # [dy + 1][dx + 1]
 
 
-def initial_variance(color, m2, epochs, width, height, tile_size):
+def initial_variance(color, m2, epochs, width, height, tile_size, mutant=None):
     """v_p = m2 / (float)((uint64)n (n - 1)) in f32 for the guided pixels, NaN for the others: pixels in no tile of the reference's
     (x-major, possibly under-covering) grid, tiles with n < 2, a v that is not finite or negative, a colour with a non-finite component.
     color (n, 3), m2 (n) in film pixel order, epochs per tile in the reference's tile order."""
@@ -26,22 +37,24 @@ def initial_variance(color, m2, epochs, width, height, tile_size):
     with np.errstate(all="ignore"):
         for n, (x0, y0, x1, y1) in zip(epochs, rects):
             n = int(n)
-            if n < 2:
+            if n < (1 if mutant == "n_ge1" else 2):
                 continue
-            fnn = np.array(n * (n - 1), np.uint64).astype(np.float32)  # the C cast: one rounding
+            fnn = np.array(n * (n - 1) & (0xFFFFFFFF if mutant == "fnn_u32" else ~0), np.uint64).astype(np.float32)  # the C cast: one rounding
             v[y0:y1, x0:x1] = m2[y0:y1, x0:x1] / fnn
         v = v.reshape(-1)
-        guided = np.isfinite(v) & (v >= 0) & np.isfinite(c).all(-1)
+        guided = np.isfinite(v) & ((v > 0) if mutant == "v_gt0" else (v >= 0)) & np.isfinite(c).all(-1)
     return np.where(guided, v, np.float32(np.nan)).astype(np.float32)
 
 
-def _shift(ys, xs, dy, dx, h, w):
+def _shift(ys, xs, dy, dx, h, w, mutant=None):
     qy, qx = ys + dy, xs + dx
     inside = (qy >= 0) & (qy < h) & (qx >= 0) & (qx < w)
+    if mutant == "border_le":
+        inside = (qy >= 0) & (qy <= h) & (qx >= 0) & (qx <= w)
     return inside, np.clip(qy, 0, h - 1), np.clip(qx, 0, w - 1)
 
 
-def atrous(color, alpha, normal, v0, width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, dtype=np.float32):
+def atrous(color, alpha, normal, v0, width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, dtype=np.float32, mutant=None):
     """The passes on the initial variance v0 (n floats, NaN = not guided; initial_variance).  color / normal: width * height * 3 floats,
     alpha: width * height floats; a guide whose sigma is 0 is not read and may be None.  Returns (colour (n, 3), variance (n)); the
     variance of a pixel that is not guided is NaN."""
@@ -71,8 +84,8 @@ def atrous(color, alpha, normal, v0, width, height, iterations, sigma_luminance,
                     for dx in range(-1, 2):
                         if dx == 0 and dy == 0:
                             continue
-                        inside, qy, qx = _shift(ys, xs, dy, dx, h, w)
-                        ok = inside & guided[qy, qx]
+                        inside, qy, qx = _shift(ys, xs, dy, dx, h, w, mutant)
+                        ok = inside if mutant == "prefilter_counts_unguided" else inside & guided[qy, qx]
                         k = f(K3[dy + 1][dx + 1])
                         num = np.where(ok, num + k * v[qy, qx], num)
                         den = np.where(ok, den + k, den)
@@ -85,7 +98,7 @@ def atrous(color, alpha, normal, v0, width, height, iterations, sigma_luminance,
                 for kx in range(-2, 3):
                     if kx == 0 and ky == 0:
                         continue
-                    inside, qy, qx = _shift(ys, xs, ky * step, kx * step, h, w)
+                    inside, qy, qx = _shift(ys, xs, ky * step, kx * step, h, w, mutant)
                     ok = inside & guided[qy, qx]
                     cq, vq = c[qy, qx], v[qy, qx]
                     e = np.zeros((h, w), f)
@@ -98,7 +111,10 @@ def atrous(color, alpha, normal, v0, width, height, iterations, sigma_luminance,
                         d = a - a[qy, qx]
                         e = e + (d * d) * ka
                     wt = f(H_TAPS[ky + 2] * H_TAPS[kx + 2]) * expf(-e).astype(f)
-                    ok &= ~np.isnan(wt)
+                    if mutant != "nan_weight_counts":
+                        ok &= ~np.isnan(wt)
+                    if mutant == "zero_weight_skipped":
+                        ok &= wt != 0
                     W = np.where(ok, W + wt, W)
                     S = np.where(ok[..., None], S + wt[..., None] * cq, S)
                     V = np.where(ok, V + (wt * wt) * vq, V)
@@ -110,7 +126,8 @@ def atrous(color, alpha, normal, v0, width, height, iterations, sigma_luminance,
     return c.reshape(h * w, 3), v.reshape(h * w)
 
 
-def denoise(color, alpha, normal, m2, epochs, width, height, tile_size, iterations, sigma_luminance, sigma_normal, sigma_alpha, dtype=np.float32):
+def denoise(color, alpha, normal, m2, epochs, width, height, tile_size, iterations, sigma_luminance, sigma_normal, sigma_alpha, dtype=np.float32,
+            mutant=None):
     """The whole entry: the initial variance from the progressive state's m2 and per-tile epoch counts, then the passes."""
-    v0 = initial_variance(color, m2, epochs, width, height, tile_size)
-    return atrous(color, alpha, normal, v0, width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, dtype)
+    v0 = initial_variance(color, m2, epochs, width, height, tile_size, mutant)
+    return atrous(color, alpha, normal, v0, width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha, dtype, mutant)

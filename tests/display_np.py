@@ -8,6 +8,14 @@ import numpy as np
 from rayn_amd import image
 
 TONE_LINEAR, TONE_REINHARD, TONE_ACES = 0, 1, 2
+# Wrong readings, for tests/post_edge_cases.py (mutant=None: the definition's bits).  meter_ge0: a pixel is metered when l >= 0;
+# no_floor: the logarithm of l itself, without the 1e-4 floor; adapt_always_blend: m_prev + (m_now - m_prev) adapt whatever valid and
+# adapt are; quant_round: the 8-bit value is rounded to nearest instead of truncated;
+# bright_fin_after: the bright pass tests e c, not c, for finiteness.
+MUTANTS = ("meter_ge0", "no_floor", "adapt_always_blend", "quant_round", "bright_fin_after")
+# reinhard_ge0 (the operator is on when lx >= 0): at lx = +0 or -0.0 the scale is (1 + lx iw2) / (1 + lx) = 1 / 1 = 1.0f exactly, and
+# v * 1.0f has v's bits (a NaN's payload aside): the reading changes no bit.
+EQUIVALENT = ("reinhard_ge0",)
 
 
 def _oracle(op, x):
@@ -54,13 +62,14 @@ def input_color(color, background, transparent_background, f=np.float32):
     return c.astype(f)
 
 
-def meter(c, f=np.float32):
+def meter(c, f=np.float32, mutant=None):
     """(S, N) of the two-stage sum over the film pixels c (n, 3)."""
     n = len(c)
     with np.errstate(all="ignore"):
         l = luminance(c, f)
-        ok = np.isfinite(c).all(-1) & (l > 0)
-        v = np.where(ok, _logf(_rmax(np.where(ok, l, f(1)), f(1e-4)).astype(f), f).astype(f), f(0))
+        ok = np.isfinite(c).all(-1) & ((l >= 0) if mutant == "meter_ge0" else (l > 0))
+        floored = np.where(ok, l, f(1)) if mutant == "no_floor" else _rmax(np.where(ok, l, f(1)), f(1e-4))
+        v = np.where(ok, _logf(floored.astype(f), f).astype(f), f(0))
         nb = (n + 255) // 256
         pv, pk = np.zeros(nb * 256, f), np.zeros(nb * 256, np.uint32)
         pv[:n], pk[:n] = v, ok
@@ -75,18 +84,18 @@ def meter(c, f=np.float32):
         return halving_tree(acc_v), int(halving_tree(acc_k))
 
 
-def expose(c, p, state, f=np.float32):
+def expose(c, p, state, f=np.float32, mutant=None):
     """(e, new state (m, valid)) for the input colour c under the parameters p (a rayn_display_params) and the state before."""
     if not p.auto_exposure:
         return f(np.float32(p.exposure_scale)), state
-    S, N = meter(c, f)
+    S, N = meter(c, f, mutant)
     m_prev, valid = f(state[0]), int(state[1])
     if N == 0:
         return f(1), state
     key, adapt = f(np.float32(p.key)), f(np.float32(p.adapt))
     with np.errstate(all="ignore"):
         m_now = S / f(np.float32(N))
-        m = m_now if (valid == 0 or adapt == 1) else m_prev + (m_now - m_prev) * adapt
+        m = m_now if (valid == 0 or adapt == 1) and mutant != "adapt_always_blend" else m_prev + (m_now - m_prev) * adapt
         e = key / f(_expf(np.array([m], f), f)[0])
     return f(e), (f(m), 1)
 
@@ -129,11 +138,12 @@ def upsample(u, w, h, f):
     return wy0 * (wx0 * a + wx1 * b) + wy1 * (wx0 * c + wx1 * d)
 
 
-def bloom(c, e, width, height, levels, threshold, strength, f=np.float32):
+def bloom(c, e, width, height, levels, threshold, strength, f=np.float32, mutant=None):
     """The bloom plane B at level 0, (n, 3) in film order."""
     w, h, L = int(width), int(height), int(levels)
     with np.errstate(all="ignore"):
-        D = [_rmax(e * fin0(c) - f(np.float32(threshold)), f(0)).astype(f).reshape(h, w, 3)]
+        ec = fin0((e * c).astype(f)) if mutant == "bright_fin_after" else e * fin0(c)
+        D = [_rmax(ec - f(np.float32(threshold)), f(0)).astype(f).reshape(h, w, 3)]
         for _ in range(L):
             D.append(downsample(D[-1], f))
         U = D[L]
@@ -144,11 +154,11 @@ def bloom(c, e, width, height, levels, threshold, strength, f=np.float32):
         return (U * scale).reshape(-1, 3)
 
 
-def tone(x, kind, iw2, f=np.float32):
+def tone(x, kind, iw2, f=np.float32, mutant=None):
     with np.errstate(all="ignore"):
         if kind == TONE_REINHARD:
             lx = luminance(x, f)
-            on = np.isfinite(lx) & (lx > 0)
+            on = np.isfinite(lx) & ((lx >= 0) if mutant == "reinhard_ge0" else (lx > 0))
             s = (f(1) + lx * f(np.float32(iw2))) / (f(1) + lx)
             return np.where(on[..., None], x * s[..., None], x)
         if kind == TONE_ACES:
@@ -157,7 +167,14 @@ def tone(x, kind, iw2, f=np.float32):
         return x
 
 
-def display(color, width, height, p, background=None, alpha=None, transparent_background=False, state=(0.0, 0), dtype=np.float32):
+def _quant_round(x):
+    """the quant_round reading of image._quant"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = np.asarray(x, np.float32) * np.float32(255.0)
+        return np.floor(image._rust_max(image._rust_min(v, np.float32(255.0)), np.float32(0.0)) + np.float32(0.5)).astype(np.uint8)
+
+
+def display(color, width, height, p, background=None, alpha=None, transparent_background=False, state=(0.0, 0), dtype=np.float32, mutant=None):
     """The whole transform of a film (color / background (n, 3), alpha (n,), film order) under the rayn_display_params p.  Returns a dict:
     d (n, 3) the float plane in film order, e, m (the state's after the call; 0 with manual exposure), state (m, valid), bloom (n, 3) or
     None, and - in float32 only - image, the 8-bit image (h, w, 3 or 4), rows top-down."""
@@ -166,22 +183,23 @@ def display(color, width, height, p, background=None, alpha=None, transparent_ba
     if transparent_background and alpha is None:
         raise ValueError("Attempted to write Color channel with insufficient channels")
     c = input_color(color, background, transparent_background, f)
-    e, state = expose(c, p, state, f)
+    e, state = expose(c, p, state, f, mutant)
     with np.errstate(all="ignore"):
         x = e * c
         B = None
         if p.levels:
-            B = bloom(c, e, w, h, p.levels, p.threshold, p.strength, f)
+            B = bloom(c, e, w, h, p.levels, p.threshold, p.strength, f, mutant)
             x = x + B
-        d = tone(x, p.tone, p.iw2, f).astype(f)
+        d = tone(x, p.tone, p.iw2, f, mutant).astype(f)
     out = {"d": d, "e": e, "m": f(state[0]) if p.auto_exposure else f(0), "state": state, "bloom": B, "image": None}
     if f is np.float32:
         dd = d.reshape(h, w, 3)
+        quant = _quant_round if mutant == "quant_round" else image._quant
         if transparent_background:
-            rgb = image._quant(image.gamma_corrected(image.saturated(dd)))
-            out["image"] = np.concatenate([rgb, image._quant(np.asarray(alpha, np.float32).reshape(h, w))[..., None]], axis=-1)[::-1]
+            rgb = quant(image.gamma_corrected(image.saturated(dd)))
+            out["image"] = np.concatenate([rgb, quant(np.asarray(alpha, np.float32).reshape(h, w))[..., None]], axis=-1)[::-1]
         elif background is not None:
-            out["image"] = image._quant(image.gamma_corrected(image.saturated(dd)))[::-1]
+            out["image"] = quant(image.gamma_corrected(image.saturated(dd)))[::-1]
         else:
-            out["image"] = image._quant(image.gamma_corrected(dd))[::-1]
+            out["image"] = quant(image.gamma_corrected(dd))[::-1]
     return out

@@ -7,6 +7,18 @@ import numpy as np
 
 F32 = np.float32
 STRIDE = 65536
+# Wrong readings of the definition, for tests/post_edge_cases.py (mutant=None: the definition's bits).  e_ge: an outlier is e >= target;
+# retire_lt: outliers * 1000 < permille * pixels; epochs_gt: n > min_epochs; percent: permille read as percent; u32_products: both
+# products of the retirement rule in 32 bits; nominal_tile_pixels: tile_w * tile_h in place of the clipped tile's pixels; fnn_u32:
+# n (n - 1) in 32 bits before the conversion; compact_no_carry: the compaction forgets the chunks before (PN.compact only).
+MUTANTS = ("e_ge", "retire_lt", "epochs_gt", "percent", "u32_products", "nominal_tile_pixels", "fnn_u32", "compact_no_carry")
+# maxe_ge (max_e over e >= 0 in place of e > 0, by bit pattern as the kernel takes it) differs only for e = -0.0, whose pattern is
+# 0x80000000.  e = se / (|mean_y| + noise_floor): the divisor is |mean_y| (+0 or positive) plus a noise_floor that is >= 0 or -0.0, and
+# +0 + -0 = +0, so it is never -0 or negative; se = sqrt(m2 / fnn) is -0 only for m2 = -0.0, and m2 starts at +0 (the reset) and becomes
+# m2 + d (y - mean), a sum that is -0 only when BOTH terms are -0: by induction m2 is never -0.  A negative m2 gives a NaN.  So e is NaN,
+# +0 or positive: the reading is equivalent on every state the reset entry started.
+EQUIVALENT = ("maxe_ge",)
+CHUNK = 1024  # tiles per trip of the compaction
 FILM_KEYS = ("color", "alpha", "background", "normal")
 
 
@@ -56,26 +68,51 @@ class State:
                 "outlier_pixels": int(self.outliers.astype(np.uint64).sum())}
 
 
-def e_p(mean_y, m2, n, noise_floor):
-    """se / (|mean_y| + noise_floor) per pixel in f32; n >= 2"""
+def e_p(mean_y, m2, n, noise_floor, mutant=None):
+    """se / (|mean_y| + noise_floor) per pixel in f32; n >= 2.  n (n - 1) is an exact integer, rounded once to f32."""
+    nn = n * (n - 1)
+    if mutant == "fnn_u32":
+        nn &= 0xFFFFFFFF
     with np.errstate(all="ignore"):
-        se = np.sqrt(m2 / F32(n * (n - 1)))
+        se = np.sqrt(m2 / F32(nn))
         return (se / (np.abs(mean_y) + F32(noise_floor))).astype(F32)
 
 
-def tile_report(e, target_error):
+def tile_report(e, target_error, mutant=None):
     """(outliers, max_e) of one tile's e_p: a NaN is neither an outlier nor a maximum; both are independent of the order of e"""
     with np.errstate(invalid="ignore"):
-        outliers = int((e > F32(target_error)).sum())
+        outliers = int(((e >= F32(target_error)) if mutant == "e_ge" else (e > F32(target_error))).sum())
         pos = e[e > 0]
+        if mutant == "maxe_ge":  # the largest bit pattern, as the kernel takes the maximum
+            pos = np.ascontiguousarray(e[e >= 0]).view(np.uint32)
+            return outliers, (F32(0) if not pos.size else np.array([pos.max()], np.uint32).view(F32)[0])
     return outliers, (pos.max() if pos.size else F32(0))
 
 
-def retires(n, outliers, tile_pixels, min_epochs, outlier_permille):
-    return n >= min_epochs and outliers * 1000 <= outlier_permille * tile_pixels  # Python integers: exact
+def retires(n, outliers, tile_pixels, min_epochs, outlier_permille, mutant=None):
+    if not (n > min_epochs if mutant == "epochs_gt" else n >= min_epochs):
+        return False
+    lhs, rhs = outliers * (100 if mutant == "percent" else 1000), outlier_permille * tile_pixels  # Python integers: exact
+    if mutant == "u32_products":
+        lhs, rhs = lhs & 0xFFFFFFFF, rhs & 0xFFFFFFFF
+    return lhs < rhs if mutant == "retire_lt" else lhs <= rhs
 
 
-def accumulate(state, film, tiles=None, target_error=0.05, noise_floor=0.05, min_epochs=4, outlier_permille=50, adaptive=True):
+def compact(retired, mutant=None):
+    """(the active list, its length) as the compaction builds them, CHUNK tile records at a time, each chunk's active tiles appended behind
+    those of the chunks before; list entries it never writes are -1.  Without a mutant: flatnonzero(retired == 0) and its length."""
+    retired = np.asarray(retired)
+    out, run = np.full(len(retired), -1, np.int64), 0
+    for base in range(0, len(retired), CHUNK):
+        act = base + np.flatnonzero(retired[base:base + CHUNK] == 0)
+        if mutant == "compact_no_carry":
+            run = 0
+        out[run:run + len(act)] = act
+        run += len(act)
+    return out, run
+
+
+def accumulate(state, film, tiles=None, target_error=0.05, noise_floor=0.05, min_epochs=4, outlier_permille=50, adaptive=True, mutant=None):
     """One epoch film into the listed tiles (ascending; None = all) of the state; updates state.mean for those tiles."""
     film = flat(film)
     tiles = range(len(state.rects)) if tiles is None else [int(k) for k in tiles]
@@ -96,10 +133,11 @@ def accumulate(state, film, tiles=None, target_error=0.05, noise_floor=0.05, min
             state.mean_y[px] = mean
             state.epochs[k] = n
             if n >= 2:
-                state.outliers[k], state.max_e[k] = tile_report(e_p(state.mean_y[px], state.m2[px], n, noise_floor), target_error)
+                state.outliers[k], state.max_e[k] = tile_report(e_p(state.mean_y[px], state.m2[px], n, noise_floor, mutant), target_error, mutant)
             else:
                 state.outliers[k], state.max_e[k] = 0, F32(0)
-            if adaptive and retires(n, int(state.outliers[k]), len(px), min_epochs, outlier_permille):
+            pixels = state.tile_size[0] * state.tile_size[1] if mutant == "nominal_tile_pixels" else len(px)
+            if adaptive and retires(n, int(state.outliers[k]), pixels, min_epochs, outlier_permille, mutant):
                 state.retired[k] = 1
     return state
 

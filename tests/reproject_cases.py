@@ -11,6 +11,7 @@ TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this."""
 import numpy as np
 
 import interpolate_np as I
+from common import above, below  # noqa: F401 (the tests reach them as RC.above / RC.below)
 import temporal_np as T
 import temporal_resample_np as TR
 import temporal_upscale_np as TU
@@ -21,14 +22,6 @@ PIXEL = 0.125
 INF, NAN = f32(np.inf), f32(np.nan)
 MODULES = {"T": T, "TR": TR, "TU": TU, "U": U, "I": I}
 UNKNOWN = -1  # an outcome the case does not write down
-
-
-def above(v):
-    return np.nextafter(f32(v), INF)
-
-
-def below(v):
-    return np.nextafter(f32(v), -INF)
 
 
 class Case:

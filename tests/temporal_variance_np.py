@@ -12,6 +12,9 @@ f32 = np.float32
 MISS = T.MISS
 TEMPORAL_MIN_HISTORY = f32(4.0)  # SVGF's threshold between the spatial and the temporal estimate
 WINDOW = 3                       # the spatial estimate's window is (2 * 3 + 1)^2 at unit spacing
+# Wrong readings of the variance estimate, for tests/post_edge_cases.py (mutant=None: the definition's bits).  nprime_gt4: the temporal
+# estimate needs n' > 4; nprime_gt1: a pixel (and a tap of the window) needs n' > 1; d_ge0: d >= 0 ? d : 0, which lets d = -0.0 through.
+MUTANTS = ("nprime_gt4", "nprime_gt1", "d_ge0")
 
 
 def luminance(c):
@@ -98,7 +101,7 @@ def accumulate(width, height, color, normal, rec, obj, prev, prev_moments, prev_
     return out, hist, mom
 
 
-def initial_variance(width, height, color, obj, n_hist, moments):
+def initial_variance(width, height, color, obj, n_hist, moments, mutant=None):
     """The variance the pack kernel hands to the passes: NaN = not guided.  color (n, 3): the accumulated colour; obj (n,): the G-buffer
     objects; n_hist (n,): n' of the new history; moments (n, 2)."""
     w, h = int(width), int(height)
@@ -109,14 +112,16 @@ def initial_variance(width, height, color, obj, n_hist, moments):
     m = np.asarray(moments, f32).reshape(n, 2)
     cfin = np.isfinite(c).all(axis=1)
     with np.errstate(all="ignore"):
-        candidate = (obj != MISS) & cfin & (nh >= f32(1.0))
-        temporal = candidate & (nh >= TEMPORAL_MIN_HISTORY)
+        has = (nh > f32(1.0)) if mutant == "nprime_gt1" else (nh >= f32(1.0))
+        pos = (lambda d: d >= 0) if mutant == "d_ge0" else (lambda d: d > 0)
+        candidate = (obj != MISS) & cfin & has
+        temporal = candidate & ((nh > TEMPORAL_MIN_HISTORY) if mutant == "nprime_gt4" else (nh >= TEMPORAL_MIN_HISTORY))
         spatial = candidate & ~temporal
         d = (m[:, 1] - (m[:, 0] * m[:, 0]).astype(f32)).astype(f32)
-        vt = (np.where(d > 0, d, f32(0.0)).astype(f32) / nh).astype(f32)
+        vt = (np.where(pos(d), d, f32(0.0)).astype(f32) / nh).astype(f32)
         # the spatial estimate: 7x7 at unit spacing, raster order, centre included
         lum = luminance(c).reshape(h, w)
-        tap_ok = ((nh >= f32(1.0)) & cfin).reshape(h, w)
+        tap_ok = (has & cfin).reshape(h, w)
         o2 = obj.reshape(h, w)
         ys, xs = np.arange(h)[:, None], np.arange(w)[None, :]
         k, s1, s2 = (np.zeros((h, w), f32) for _ in range(3))
@@ -132,13 +137,13 @@ def initial_variance(width, height, color, obj, n_hist, moments):
                 s2 = np.where(counts, (s2 + (lq * lq).astype(f32)).astype(f32), s2)
         mu = (s1 / k).astype(f32)
         ds = ((s2 / k).astype(f32) - (mu * mu).astype(f32)).astype(f32)
-        vs = np.where(ds > 0, ds, f32(0.0)).astype(f32).reshape(n)
+        vs = np.where(pos(ds), ds, f32(0.0)).astype(f32).reshape(n)
         v = np.where(temporal, vt, np.where(spatial, vs, f32(np.nan))).astype(f32)
         v = np.where(np.isfinite(v), v, f32(np.nan)).astype(f32)
     return v, k.reshape(n)
 
 
-def denoise(width, height, color, alpha, normal, obj, n_hist, moments, iterations, sigma_luminance, sigma_normal, sigma_alpha):
+def denoise(width, height, color, alpha, normal, obj, n_hist, moments, iterations, sigma_luminance, sigma_normal, sigma_alpha, mutant=None):
     """The whole entry: the initial variance, then denoise_variance_np's passes.  Returns (colour (n, 3), variance (n))."""
-    v0, _ = initial_variance(width, height, color, obj, n_hist, moments)
+    v0, _ = initial_variance(width, height, color, obj, n_hist, moments, mutant)
     return V.atrous(color, alpha, normal, v0, width, height, iterations, sigma_luminance, sigma_normal, sigma_alpha)
