@@ -528,6 +528,27 @@ extern "C" {
         scratch_bytes: usize,
         hip_stream: *mut c_void,
     ) -> i32;
+    /// OpenEXR chunks on the device: the bytes `d_out` / `d_scratch` of rayn_hip_exr_encode_device must have; `layout` holds (stride,
+    /// offset, type) per channel, 3 * n_channels words on the host; host only, 0 for what the entry rejects
+    pub fn rayn_exr_stream_bound(width: u32, height: u32, n_channels: u32, layout: *const u32) -> usize;
+    pub fn rayn_exr_scratch_bytes(width: u32, height: u32, n_channels: u32, layout: *const u32, matches: u32) -> usize;
+    /// the ZIP-compressed scanline chunks of an OpenEXR file from `n_channels` planes in the film's layout (`d_planes`: device pointers in
+    /// a host array, channels in the file's order; type 0 UINT, 1 HALF, 2 FLOAT; `matches` 0 run-length blocks, 1 LZ77 blocks) behind
+    /// four words and a chunk table, enqueued on `hip_stream` (include/rayn_hip.h has the definition)
+    pub fn rayn_hip_exr_encode_device(
+        ctx: *mut RaynCtx,
+        width: u32,
+        height: u32,
+        n_channels: u32,
+        d_planes: *const *const c_void,
+        layout: *const u32,
+        matches: u32,
+        d_out: *mut c_void,
+        out_bytes: usize,
+        d_scratch: *mut c_void,
+        scratch_bytes: usize,
+        hip_stream: *mut c_void,
+    ) -> i32;
 }
 
 /// Start-up layout check against the library as compiled (indices: include/rayn_hip.h, rayn_hip_sizeof).

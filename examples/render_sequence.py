@@ -6,6 +6,7 @@ written as PNGs (Alpha, WorldNormal, Color, as rayn's main writes them).  Prints
                                       [--resample {bilinear,catmull_rom}] [--display [--exposure auto|EV] [--tone T] [--bloom LEVELS] [--adaptation S]]
                                       [--upscale S [--temporal --supersample [--no-jitter] [--confidence | --no-confidence]]]
                                       [--preview [K] [--ao-radius R]] [--interpolate K [--interp-tolerance D]] [--png {host,device,device-lz77}]
+                                      [--exr {host,device,device-lz77} [--exr-float]]
 
 --compare-loop also times the plain loop on the same frames: Film.render_frame_into, then the host post-process (the film copied to
 the host channel by channel and rayn_amd.image's numpy arms, as Film.save_to did before it ran on the device), and checks that
@@ -43,6 +44,10 @@ and Huffman coding; the writer threads only frame it) instead of calling zlib on
 their bytes, so it does not combine with --compare-loop.  --png device-lz77 is the same with the encoder that also finds LZ77 matches
 (png="device-lz77"): about twice the encoder time, smaller Color files - much smaller with --preview - and larger masks and normals.  The
 total size of the written files is printed for every encoder.
+--exr also writes one multi-channel OpenEXR file per frame (Film.render_sequence(exr=...), an extension: the written channels as HALF
+layers, FLOAT with --exr-float, ZIP-compressed scanlines): device encodes the chunks on the render stream (Context.exr_encode),
+device-lz77 the same with LZ77 matches, host calls zlib in the writer threads.  The PNGs do not change; the EXR files' total size is
+printed on its own.
 """
 import argparse
 import os
@@ -122,7 +127,13 @@ def main():
     ap.add_argument("--png", choices=("host", "device", "device-lz77"), default="host",
                     help="where the PNG streams are encoded: host (zlib in the writer threads, the default), device (filter, run-length and Huffman kernels on the "
                          "render stream) or device-lz77 (the same with LZ77 matches)")
+    ap.add_argument("--exr", choices=("host", "device", "device-lz77"), default=None,
+                    help="also write one multi-channel OpenEXR file per frame: host (zlib in the writer threads), device (the chunks encoded on the render "
+                         "stream) or device-lz77 (the same with LZ77 matches)")
+    ap.add_argument("--exr-float", action="store_true", help="write the EXR layers as FLOAT, the film's own bits (default HALF); needs --exr")
     args = ap.parse_args()
+    if args.exr_float and args.exr is None:
+        ap.error("--exr-float chooses the EXR pixel type: add --exr")
     if args.png != "host" and args.compare_loop:
         ap.error("--compare-loop compares the files byte for byte with the host encoder's: use one or the other")
     if args.interp_tolerance is not None and args.interpolate is None:
@@ -193,14 +204,17 @@ def main():
     # warm-up: code objects, the context's first-frame arena and the writer path (not timed)
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames[:1], FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
                          os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample, preview=preview,
-                         interpolate=interpolate, png=args.png)
+                         interpolate=interpolate, png=args.png, exr=args.exr, exr_half=not args.exr_float)
     t0 = time.perf_counter()
     stats = film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
                                  os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample, preview=preview,
-                         interpolate=interpolate, png=args.png)
+                         interpolate=interpolate, png=args.png, exr=args.exr, exr_half=not args.exr_float)
     seq_s = time.perf_counter() - t0
     seq_dir = os.path.join(args.out, "sequence")
-    print(f"--png {args.png}: {sum(os.path.getsize(os.path.join(seq_dir, n)) for n in os.listdir(seq_dir))} bytes in {len(os.listdir(seq_dir))} files")
+    pngs, exrs = ([n for n in os.listdir(seq_dir) if n.endswith(ext)] for ext in (".png", ".exr"))
+    print(f"--png {args.png}: {sum(os.path.getsize(os.path.join(seq_dir, n)) for n in pngs)} bytes in {len(pngs)} files")
+    if args.exr is not None:
+        print(f"--exr {args.exr}{' --exr-float' if args.exr_float else ''}: {sum(os.path.getsize(os.path.join(seq_dir, n)) for n in exrs)} bytes in {len(exrs)} files")
     if preview is not None:  # the preview is enqueued, not waited for: there is no per-frame render time to report
         print(f"render_sequence --preview {preview}{' --temporal ' + str(temporal) if temporal else ''}{' --denoise ' + str(denoise) if denoise else ''}"
               f"{' --display ' + str(display) if display else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s")

@@ -932,6 +932,45 @@ size_t rayn_deflate_scratch_bytes(size_t n);
 int rayn_hip_deflate_lz77_device(rayn_ctx* ctx, const void* d_data, size_t n, uint32_t stride, void* d_out, size_t out_bytes, void* d_scratch,
                                  size_t scratch_bytes, void* hip_stream);
 
+/* ---- OpenEXR scanline chunks with ZIP compression on the device (an EXTENSION: rayn writes no EXR) -- The chunks of a single-part
+ * scanline OpenEXR file (compression ZIP, 16 rows per chunk, lineOrder INCREASING_Y) from planes in the film's layout, so that one file
+ * per frame carries the float film.  Written from the published file layout; integer arithmetic only; tests/exr_np.py restates it and
+ * the kernels agree with it byte for byte.  Conformance with real OpenEXR readers is unpinned: no OpenEXR library was at hand.
+ *   Input.  1..16 channels, in the file's order (names ascending byte-wise: the host checks that).  Channel c of pixel p = x + y * width
+ *     (rows bottom-up, as the film stores them) is the 32-bit word plane_c[p * stride_c + offset_c]; layout holds (stride, offset, type)
+ *     per channel.  type 2 FLOAT and type 0 UINT: the word as it is, size 4.  type 1 HALF: the f32 converted to binary16, size 2.
+ *   f32 to half.  Round to nearest even; half denormals are produced; a magnitude >= 65520 becomes the infinity of its sign; the sign of
+ *     zero is kept; a magnitude <= 2^-25, f32 denormals included whatever the build's denormal mode, becomes the zero of its sign.  A
+ *     NaN becomes sign | 0x7C00 | (mantissa >> 13), with the lowest bit set when that field is 0: a signalling NaN is not quieted.
+ *   Rows.  The file's row y is the film's row height - 1 - y.  A row's bytes: for each channel in order its width values, little-endian.
+ *     S = width * (sum of the sizes) bytes, always even.
+ *   Chunks.  Chunk k covers the rows 16k .. min(16k + 16, height) - 1; RAW_k is those rows concatenated, n_k = S * rows bytes.
+ *   Pre-process.  T: the bytes of RAW_k at even indices, then those at odd indices.  P[0] = T[0], P[i] = (T[i] - T[i-1] + 128) & 255.
+ *   Deflate.  Z_k is the zlib stream of P_k in the block format above: matches == 0 the run-length blocks of
+ *     rayn_hip_png_encode_device, matches == 1 the LZ77 blocks of rayn_hip_deflate_lz77_device with the row candidate's distance S / 2.
+ *     Blocks of 32768 bytes restart at every chunk's start; the stored fallback per block, the alignment block behind every Huffman
+ *     block but the chunk's last, 78 01 and the chunk's own Adler-32 are unchanged.
+ *   Raw fallback.  If Z_k has n_k bytes or more the chunk's payload is RAW_k itself, not pre-processed; else it is Z_k.  A reader tells
+ *     the two apart by size == n_k.
+ *   Output.  Four little-endian words - the bytes of the body, the chunks, the raw chunks, the deflate blocks (32768-byte blocks over all
+ *     chunks, the raw ones included) - then one word per chunk, where it starts in the body; zeros up to a multiple of 16; then the
+ *     body, contiguous: per chunk the i32 y = 16k, the i32 payload size, the payload.  The 4-byte word holding the body's last byte is
+ *     zero-padded and nothing behind it is written.  rayn_amd.image.exr_from_chunks makes the file of it.
+ * rayn_exr_stream_bound: the bytes d_out must have, align16(16 + 4 * chunks) + align16(sum of 8 + n_k): exact, a payload never exceeds
+ * n_k.  rayn_exr_scratch_bytes: the bytes of d_scratch (P, RAW, the blocks before their compaction, their sizes; with matches == 1 65536
+ * more per block).  layout: n_channels * 3 words on the host.  Both host only; 0 for what the entry rejects. */
+size_t rayn_exr_stream_bound(uint32_t width, uint32_t height, uint32_t n_channels, const uint32_t* layout);
+size_t rayn_exr_scratch_bytes(uint32_t width, uint32_t height, uint32_t n_channels, const uint32_t* layout, uint32_t matches);
+/* Enqueue the encoder on 'hip_stream' (NULL = the ctx's own stream; not waited for), on the ctx's GPU.  d_planes: n_channels DEVICE
+ * pointers in an array on the HOST, read before the call returns, like layout; the planes are not modified.  d_out and d_scratch: DEVICE,
+ * 16-byte aligned, of at least the byte counts above.  A fixed number of launches whatever the height.  RAYN_ERR_INVALID_ARG with a last
+ * error text, and nothing written, for: a zero-sized image, 0 or more than 16 channels, a type other than 0, 1, 2, a stride of 0 or an
+ * offset >= the stride, 16 * S >= 2^31 or a bound >= 2^31 (32-bit offsets), matches > 1, a NULL buffer or plane, a misaligned or too
+ * small d_out or d_scratch, and an output or scratch that overlaps a plane or the other. */
+int rayn_hip_exr_encode_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t n_channels, const void* const* d_planes,
+                               const uint32_t* layout, uint32_t matches, void* d_out, size_t out_bytes, void* d_scratch, size_t scratch_bytes,
+                               void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */

@@ -421,6 +421,19 @@ inline int deflate_lz77(rayn_ctx* ctx, const void* d_data, size_t n, uint32_t st
     return rayn_hip_deflate_lz77_device(ctx, d_data, n, stride, d_out, out_bytes, d_scratch, scratch_bytes, hip_stream);
 }
 
+// Extension (include/rayn_hip.h: OpenEXR scanline chunks with ZIP compression on the device): the chunks of the EXR file of n_channels
+// planes in the film's layout behind four words and a chunk table.  d_planes: device pointers in a host array, in the file's channel
+// order; layout: (stride, offset, type) per channel; matches: 0 run-length blocks, 1 LZ77 blocks.  d_out of at least exr_stream_bound
+// bytes, d_scratch of at least exr_scratch_bytes, both 16-byte aligned.  Returns the entry's code.
+inline size_t exr_stream_bound(Extent2u res, uint32_t n_channels, const uint32_t* layout) { return rayn_exr_stream_bound(res.w, res.h, n_channels, layout); }
+inline size_t exr_scratch_bytes(Extent2u res, uint32_t n_channels, const uint32_t* layout, uint32_t matches) {
+    return rayn_exr_scratch_bytes(res.w, res.h, n_channels, layout, matches);
+}
+inline int exr_encode(rayn_ctx* ctx, Extent2u res, uint32_t n_channels, const void* const* d_planes, const uint32_t* layout, uint32_t matches,
+                      void* d_out, size_t out_bytes, void* d_scratch, size_t scratch_bytes, void* hip_stream = nullptr) {
+    return rayn_hip_exr_encode_device(ctx, res.w, res.h, n_channels, d_planes, layout, matches, d_out, out_bytes, d_scratch, scratch_bytes, hip_stream);
+}
+
 // ---- setup::setup() (src/setup.rs:46-170) with the resolution as an argument ---------------------
 namespace setup {
 constexpr float WORLD_RADIUS = 100.0f;

@@ -50,6 +50,7 @@ EXPORTS = [
     "rayn_png_stream_bound", "rayn_png_scratch_bytes", "rayn_hip_png_encode_device",
     "rayn_png_scratch_bytes_lz77", "rayn_hip_png_encode_lz77_device",
     "rayn_deflate_stream_bound", "rayn_deflate_scratch_bytes", "rayn_hip_deflate_lz77_device",
+    "rayn_exr_stream_bound", "rayn_exr_scratch_bytes", "rayn_hip_exr_encode_device",
 ]
 
 
@@ -156,6 +157,11 @@ def lib():
             fn.restype = C.c_size_t
             fn.argtypes = [C.c_size_t]
         L.rayn_hip_deflate_lz77_device.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, vp]
+        L.rayn_exr_stream_bound.restype = C.c_size_t
+        L.rayn_exr_stream_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, up]
+        L.rayn_exr_scratch_bytes.restype = C.c_size_t
+        L.rayn_exr_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, up, C.c_uint32]
+        L.rayn_hip_exr_encode_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp), up, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, vp]
         L.rayn_sets_1d.restype = C.c_uint32
         L.rayn_sets_1d.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_sets_2d.restype = C.c_uint32

@@ -63,6 +63,34 @@ def deflate_scratch_bytes(n):
     return int(lib().rayn_deflate_scratch_bytes(int(n))) if 0 <= int(n) < 1 << 63 else 0
 
 
+def _exr_layout(layout):
+    """(n_channels, the 3 * n_channels words of rayn_hip_exr_encode_device's layout, or None) of (stride, offset, type) triples: sizes no
+    32-bit word holds have no layout the entry accepts"""
+    flat = [int(v) for triple in layout for v in triple]
+    n = len(flat) // 3
+    if len(flat) != 3 * n or any(not 0 <= v < 1 << 32 for v in flat):
+        return n, None
+    return n, (C.c_uint32 * max(len(flat), 1))(*flat)
+
+
+def exr_stream_bound(width, height, layout):
+    """rayn_exr_stream_bound: the bytes Context.exr_encode's output needs for a width x height image of the channels `layout` ((stride,
+    offset, type) per channel): the four words, the chunk table and every chunk as raw bytes - exact, no payload is longer (0 for what
+    the entry rejects).  Host only."""
+    n, words = _exr_layout(layout)
+    if words is None or not (0 <= int(width) < 1 << 32 and 0 <= int(height) < 1 << 32):
+        return 0
+    return int(lib().rayn_exr_stream_bound(int(width), int(height), n, words))
+
+
+def exr_scratch_bytes(width, height, layout, lz77=False):
+    """rayn_exr_scratch_bytes: bytes of device scratch Context.exr_encode needs (0 for what the entry rejects).  Host only."""
+    n, words = _exr_layout(layout)
+    if words is None or not (0 <= int(width) < 1 << 32 and 0 <= int(height) < 1 << 32):
+        return 0
+    return int(lib().rayn_exr_scratch_bytes(int(width), int(height), n, words, int(bool(lz77))))
+
+
 def preview_tables(samples, frame, width, height):
     """The default tables of a preview of `samples` AO rays for frame `frame`: (the sample table (samples, 2) float32 - 2-D set 0 of
     build_rd_tables(samples, 0, 2, frame), so successive frames get different directions - and the per-pixel scramble of
@@ -512,6 +540,34 @@ class Context:
         d_scratch, scratch_ptr, scratch_bytes = scratch(d_scratch, (png_scratch_bytes_lz77 if lz77 else png_scratch_bytes)(width, height, bpp), d_out.device)
         entry = self._L.rayn_hip_png_encode_lz77_device if lz77 else self._L.rayn_hip_png_encode_device
         self._chk(entry(self.h, int(width), int(height), int(bpp), _ptr(d_img), _ptr(d_out), d_out.numel(), scratch_ptr, scratch_bytes, stream_ptr(stream)))
+
+    def exr_encode(self, width, height, channels, d_out, d_scratch=None, stream=None, lz77=False):
+        """rayn_hip_exr_encode_device: the ZIP-compressed scanline chunks of the OpenEXR file of `channels` - a list of (name, tensor,
+        stride, offset, type) in the file's order: channel `name` of pixel p (the film's layout, rows bottom-up) is the 32-bit word p *
+        stride + offset of the contiguous CUDA tensor of 4-byte elements; type 0 UINT, 1 HALF (the float32 converted), 2 FLOAT - into the
+        uint8 CUDA tensor `d_out` (at least exr_stream_bound bytes, 16-byte aligned): four little-endian words - the body's bytes, the
+        chunks, the raw chunks, the deflate blocks - the chunk table and the body (rayn_amd.image.exr_from_chunks frames it as a file).
+        lz77: the blocks of png_encode_lz77 instead of png_encode's.  d_scratch: at least exr_scratch_bytes bytes, allocated here when
+        None.  ValueError for names that are unsorted, duplicated, empty or longer than 31 bytes and for tensors too small.  Enqueued on
+        the stream, not waited for; the planes are not modified."""
+        import torch
+        from . import image
+        channels = list(channels)
+        image.check_exr_names([c[0] for c in channels])
+        width, height = int(width), int(height)
+        layout = [(int(s), int(o), int(t)) for _, _, s, o, t in channels]
+        bound = exr_stream_bound(width, height, layout)
+        for name, t, s, o, _ in channels:
+            need = (width * height - 1) * int(s) + int(o) + 1
+            if t is None or not (t.is_cuda and t.element_size() == 4 and t.is_contiguous() and t.numel() >= need):
+                raise ValueError(f"channel {name!r} must be a contiguous CUDA tensor of at least {need} 32-bit elements")
+        if d_out is None or not (d_out.dtype == torch.uint8 and d_out.is_contiguous() and d_out.numel() >= max(bound, 1)):
+            raise ValueError(f"d_out must be a contiguous uint8 tensor of at least {bound} bytes")
+        d_scratch, scratch_ptr, scratch_bytes = scratch(d_scratch, exr_scratch_bytes(width, height, layout, lz77), d_out.device)
+        n, words = _exr_layout(layout)
+        planes = (C.c_void_p * max(n, 1))(*[t.data_ptr() for _, t, _, _, _ in channels])
+        self._chk(self._L.rayn_hip_exr_encode_device(self.h, width, height, n, planes, words, int(bool(lz77)), _ptr(d_out), d_out.numel(), scratch_ptr,
+                                                     scratch_bytes, stream_ptr(stream)))
 
     def display_state(self):
         """A fresh state of the display transform's auto exposure: two zeroed 32-bit words {m, valid} on the context's GPU."""

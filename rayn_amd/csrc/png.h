@@ -19,6 +19,12 @@ struct PngMeta { // one per block
     uint32_t stored;
 };
 
+// The segmented form of the block kernels (exr.hip): R is segments of `bytes` bytes, a multiple of 16, the last one possibly shorter; each
+// is a stream of its own, cut into blocks from its own start - `blocks` of them per segment, also where the last one has fewer.
+struct PngSegments {
+    uint32_t bytes, blocks;
+};
+
 // The geometry of one call, from (w, h, bpp); ok = false for what the entry rejects (why: the reason)
 struct PngGeometry {
     bool ok;
@@ -41,6 +47,10 @@ hipError_t launch_png_encode(hipStream_t s, uint32_t w, uint32_t h, uint32_t bpp
 void launch_png_filter(hipStream_t s, uint32_t w, uint32_t h, uint32_t bpp, const uint8_t* d_img, uint8_t* R);
 void launch_png_finish(hipStream_t s, const PngGeometry& g, void* d_out, void* d_scratch);
 
+// k_png_block on the segments of R (n bytes in all, nblocks blocks over all segments): block b of segment k leaves meta[k * seg.blocks + b]
+// and that slot of `slots`
+void launch_png_block_segmented(hipStream_t s, const uint8_t* R, uint32_t n, uint32_t nblocks, PngSegments seg, PngMeta* meta, uint8_t* slots);
+
 // ---- png_lz.hip: the encoder with LZ77 matches (rayn_hip_png_encode_lz77_device, rayn_hip_deflate_lz77_device) --------------------------
 constexpr uint32_t PNG_LZ_POSITIONS = 2u * PNG_BLOCK; // bytes of scratch per block behind the slots: one array of 16-bit positions of the sort
 // scratch of n filtered bytes: the run-only encoder's, then PNG_LZ_POSITIONS per block
@@ -50,5 +60,8 @@ const char* png_lz_check_args(uint32_t w, uint32_t h, uint32_t bpp, const uint8_
 const char* deflate_check_args(const void* d_data, size_t n, const void* d_out, size_t out_bytes, const void* d_scratch, size_t scratch_bytes);
 hipError_t launch_png_encode_lz77(hipStream_t s, uint32_t w, uint32_t h, uint32_t bpp, const uint8_t* d_img, void* d_out, void* d_scratch);
 hipError_t launch_deflate_lz77(hipStream_t s, const void* d_data, uint32_t n, uint32_t stride, void* d_out, void* d_scratch);
+// k_png_lz_block on the segments of R, as launch_png_block_segmented; positions: PNG_LZ_POSITIONS bytes per block
+void launch_png_lz_block_segmented(hipStream_t s, const uint8_t* R, uint32_t n, uint32_t nblocks, PngSegments seg, uint32_t stride, PngMeta* meta,
+                                   uint8_t* slots, uint16_t* positions);
 
 } // namespace rayn

@@ -5,6 +5,8 @@
 //                  Huffman and the stored form, the block's bytes into its own slot of the scratch, its Adler-32 partial sums
 //   k_png_layout   one workgroup: the exclusive sum of the block sizes, the Adler-32, the 16-byte header
 //   k_png_compact  a thread per output word: 78 01, the blocks from their slots, the Adler-32, contiguously into the output
+// k_png_block<true> is the same kernel on segments of R that are streams of their own (the chunks of exr.hip): only where a block lies
+// and which one is final differ (block_span, png_device.h).
 // Integer arithmetic only; policy-free, built once.  Every store is a vector store; shared words are combined with integer atomicOr on
 // zero-initialised words.
 #include "png.h"
@@ -104,7 +106,8 @@ __global__ __launch_bounds__(256) void k_png_filter(const uint8_t* __restrict__ 
     }
 }
 
-__global__ __launch_bounds__(BT) void k_png_block(const uint8_t* __restrict__ R, uint32_t n, uint32_t nblocks, PngMeta* __restrict__ meta,
+template <bool SEG>
+__global__ __launch_bounds__(BT) void k_png_block(const uint8_t* __restrict__ R, uint32_t n, uint32_t nblocks, PngSegments seg, PngMeta* __restrict__ meta,
                                                   uint8_t* __restrict__ slots) {
     __shared__ uint32_t sw[LDS_WORDS];
     __shared__ uint32_t hist[NSYM];
@@ -114,8 +117,9 @@ __global__ __launch_bounds__(BT) void k_png_block(const uint8_t* __restrict__ R,
     __shared__ uint32_t sh_a, sh_b, sh_bits, sh_matches;
 
     const uint32_t t = threadIdx.x, blk = blockIdx.x;
-    const uint32_t base = blk * PNG_BLOCK, len = min(PNG_BLOCK, n - base);
-    const bool final_block = blk + 1u == nblocks;
+    const PngBlockSpan span = block_span<SEG>(blk, n, nblocks, seg);
+    const uint32_t base = span.base, len = span.len;
+    const bool final_block = span.final_block;
     uint32_t* slot = (uint32_t*)(slots + (size_t)blk * PNG_SLOT);
 
     // the block's bytes, a word at a time (R is 16-byte aligned and padded to 16: the word holding the last byte can be read whole)
@@ -342,12 +346,16 @@ void launch_png_finish(hipStream_t s, const PngGeometry& g, void* d_out, void* d
     k_png_compact<<<(max_words + 255u) / 256u, 256, 0, s>>>(sc + g.off_slots, offsets, totals, g.blocks, max_words, (uint32_t*)d_out);
 }
 
+void launch_png_block_segmented(hipStream_t s, const uint8_t* R, uint32_t n, uint32_t nblocks, PngSegments seg, PngMeta* meta, uint8_t* slots) {
+    k_png_block<true><<<nblocks, BT, 0, s>>>(R, n, nblocks, seg, meta, slots);
+}
+
 hipError_t launch_png_encode(hipStream_t s, uint32_t w, uint32_t h, uint32_t bpp, const uint8_t* d_img, void* d_out, void* d_scratch) {
     const PngGeometry g = png_geometry(w, h, bpp);
     uint8_t* sc = (uint8_t*)d_scratch;
     if (hipError_t e = hipMemsetAsync(sc + g.off_slots, 0, (size_t)g.blocks * PNG_SLOT, s)) return e; // the emit ors into zeroed words
     launch_png_filter(s, w, h, bpp, d_img, sc);
-    k_png_block<<<g.blocks, BT, 0, s>>>(sc, g.n, g.blocks, (PngMeta*)(sc + g.off_meta), sc + g.off_slots);
+    k_png_block<false><<<g.blocks, BT, 0, s>>>(sc, g.n, g.blocks, PngSegments{}, (PngMeta*)(sc + g.off_meta), sc + g.off_slots);
     launch_png_finish(s, g, d_out, d_scratch);
     return hipSuccess;
 }

@@ -17,6 +17,23 @@ constexpr uint32_t PNG_LDS_WORDS = PNG_BLOCK / 4u + PNG_BLOCK / 128u + 2u;  // o
 constexpr uint32_t PNG_NSYM = 286u, PNG_NDIST = 30u, PNG_END_OF_BLOCK = 256u, PNG_ADLER = 65521u;
 constexpr uint32_t PNG_NO_START = 0xFFFFFFFFu;
 
+// Where block blk lies in R.  SEG = false: R is one stream of n bytes, cut every PNG_BLOCK.  SEG = true: R is segments of seg.bytes
+// bytes (the last one may be shorter), every segment cut on its own into seg.blocks blocks - a stream of its own, with its own final block.
+struct PngBlockSpan {
+    uint32_t base, len;
+    bool final_block;
+};
+template <bool SEG>
+__device__ inline PngBlockSpan block_span(uint32_t blk, uint32_t n, uint32_t nblocks, PngSegments seg) {
+    if constexpr (SEG) {
+        const uint32_t first = blk / seg.blocks * seg.bytes, at = blk % seg.blocks * PNG_BLOCK, left = min(seg.bytes, n - first) - at;
+        return {first + at, min(PNG_BLOCK, left), left <= PNG_BLOCK};
+    } else {
+        const uint32_t base = blk * PNG_BLOCK;
+        return {base, min(PNG_BLOCK, n - base), blk + 1u == nblocks};
+    }
+}
+
 __device__ inline uint32_t byte_at(const uint32_t* sw, uint32_t i) {
     const uint32_t wi = i >> 2;
     return (sw[wi + (wi >> 5)] >> ((i & 3u) * 8u)) & 255u;

@@ -93,7 +93,8 @@ __device__ inline void walk_tokens(const uint32_t* sw, const uint16_t* pos, uint
     }
 }
 
-__global__ __launch_bounds__(BT) void k_png_lz_block(const uint8_t* __restrict__ R, uint32_t n, uint32_t stride, uint32_t nblocks,
+template <bool SEG>
+__global__ __launch_bounds__(BT) void k_png_lz_block(const uint8_t* __restrict__ R, uint32_t n, uint32_t stride, uint32_t nblocks, PngSegments seg,
                                                      PngMeta* __restrict__ meta, uint8_t* __restrict__ slots, uint16_t* positions) {
     __shared__ uint32_t sw[PNG_LDS_WORDS];
     __shared__ uint16_t pos[PNG_BLOCK];      // the sort's array in LDS; prev(i); then D(i) | bit 8 of the exit << 15
@@ -106,8 +107,9 @@ __global__ __launch_bounds__(BT) void k_png_lz_block(const uint8_t* __restrict__
     __shared__ uint32_t sh_a, sh_b, sh_bits;
 
     const uint32_t t = threadIdx.x, blk = blockIdx.x;
-    const uint32_t base = blk * PNG_BLOCK, len = min(PNG_BLOCK, n - base);
-    const bool final_block = blk + 1u == nblocks;
+    const PngBlockSpan span = block_span<SEG>(blk, n, nblocks, seg);
+    const uint32_t base = span.base, len = span.len;
+    const bool final_block = span.final_block;
     uint32_t* slot = (uint32_t*)(slots + (size_t)blk * PNG_SLOT);
     uint16_t* far = positions + (size_t)blk * PNG_BLOCK; // the sort's second array
     uint8_t* ex8 = (uint8_t*)ex;
@@ -299,7 +301,7 @@ const char* check_buffers(const PngGeometry& g, const void* src, size_t src_byte
 
 hipError_t launch_blocks(hipStream_t s, const PngGeometry& g, uint32_t stride, void* d_out, void* d_scratch) {
     uint8_t* sc = (uint8_t*)d_scratch;
-    k_png_lz_block<<<g.blocks, BT, 0, s>>>(sc, g.n, stride, g.blocks, (PngMeta*)(sc + g.off_meta), sc + g.off_slots, (uint16_t*)(sc + g.scratch_bytes));
+    k_png_lz_block<false><<<g.blocks, BT, 0, s>>>(sc, g.n, stride, g.blocks, PngSegments{}, (PngMeta*)(sc + g.off_meta), sc + g.off_slots, (uint16_t*)(sc + g.scratch_bytes));
     launch_png_finish(s, g, d_out, d_scratch);
     return hipSuccess;
 }
@@ -321,6 +323,11 @@ const char* deflate_check_args(const void* d_data, size_t n, const void* d_out, 
     if (!g.ok) return g.why;
     return check_buffers(g, d_data, n, d_out, out_bytes, d_scratch, scratch_bytes, "d_out smaller than rayn_deflate_stream_bound",
                          "d_scratch smaller than rayn_deflate_scratch_bytes", "d_out must not overlap d_data", "d_scratch overlaps d_data or d_out");
+}
+
+void launch_png_lz_block_segmented(hipStream_t s, const uint8_t* R, uint32_t n, uint32_t nblocks, PngSegments seg, uint32_t stride, PngMeta* meta,
+                                   uint8_t* slots, uint16_t* positions) {
+    k_png_lz_block<true><<<nblocks, BT, 0, s>>>(R, n, stride, nblocks, seg, meta, slots, positions);
 }
 
 hipError_t launch_png_encode_lz77(hipStream_t s, uint32_t w, uint32_t h, uint32_t bpp, const uint8_t* d_img, void* d_out, void* d_scratch) {

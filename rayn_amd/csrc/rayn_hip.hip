@@ -31,6 +31,7 @@
 #include "preview.h"
 #include "interpolate.h"
 #include "png.h"
+#include "exr.h"
 #include "progressive.h"
 #include "temporal.h"
 
@@ -1160,6 +1161,16 @@ int rayn_hip_deflate_lz77_device(rayn_ctx* ctx, const void* d_data, size_t n, ui
     hipStream_t s;
     if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
     HIPCHK(launch_deflate_lz77(s, d_data, (uint32_t)n, stride, d_out, d_scratch));
+    return post_enqueued(ctx);
+}
+
+// The EXR chunk encoder (exr.hip): planes in the film's layout -> the ZIP-compressed scanline chunks of an OpenEXR file behind a chunk table.
+int rayn_hip_exr_encode_device(rayn_ctx* ctx, uint32_t w, uint32_t h, uint32_t n_channels, const void* const* d_planes, const uint32_t* layout,
+                               uint32_t matches, void* d_out, size_t out_bytes, void* d_scratch, size_t scratch_bytes, void* hip_stream) {
+    const char* why = exr_check_args(w, h, n_channels, d_planes, layout, matches, d_out, out_bytes, d_scratch, scratch_bytes);
+    hipStream_t s;
+    if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
+    HIPCHK(launch_exr_encode(s, w, h, n_channels, d_planes, layout, matches, d_out, d_scratch));
     return post_enqueued(ctx);
 }
 

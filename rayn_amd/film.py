@@ -80,6 +80,60 @@ def _check_png(png):
     return png
 
 
+EXR_ENCODERS = ("host", "device", "device-lz77")
+# the layers of an EXR file: kind -> (the device film's key, the channel names of the plane's words in order)
+_EXR_LAYERS = {ChannelKind.Color: ("color", ("R", "G", "B")), ChannelKind.Alpha: ("alpha", ("A",)),
+               ChannelKind.Background: ("background", ("background.R", "background.G", "background.B")),
+               ChannelKind.WorldNormal: ("normal", ("N.X", "N.Y", "N.Z"))}
+
+
+def _check_exr(exr, allow_none=False):
+    """`exr` of save_exr and render_sequence: "host" (zlib per chunk on the host), "device" (Context.exr_encode, framed on the host) or
+    "device-lz77" (the same with LZ77 matches); render_sequence also takes None, no EXR files."""
+    if not (exr in EXR_ENCODERS or (allow_none and exr is None)):
+        raise ValueError(f"exr must be one of {EXR_ENCODERS}, got {exr!r}")
+    return exr
+
+
+def _exr_kinds(channel_kinds, channels):
+    """The kinds an EXR file holds, `channels` or every kind of the film, in the film's order; ValueError for one the film lacks, for a
+    kind named twice and for none at all"""
+    kinds = list(channel_kinds if channels is None else channels)
+    for k in kinds:
+        if k not in channel_kinds:
+            raise ValueError(f"Attempted to write {k.name} channel but it didn't exist")
+    if len(set(kinds)) != len(kinds) or not kinds:
+        raise ValueError("an EXR file holds every kind once and at least one")
+    return kinds
+
+
+def exr_channels(kinds, d_film, half=True, d_gbuffer=None):
+    """The channel list of Context.exr_encode - (name, tensor, stride, offset, type), sorted by name - of the planes of `kinds` in the
+    device film `d_film`: HALF, or FLOAT for half=False.  d_gbuffer (alloc_gbuffer's planes) adds P.X, P.Y, P.Z and Z, always FLOAT, and
+    the UINT id."""
+    t = image.EXR_HALF if half else image.EXR_FLOAT
+    out = []
+    for kind in kinds:
+        key, names = _EXR_LAYERS[kind]
+        out += [(n, d_film[key], len(names), k, t) for k, n in enumerate(names)]
+    if d_gbuffer is not None:
+        out += [(n, d_gbuffer["records"], 4, k, image.EXR_FLOAT) for k, n in enumerate(("P.X", "P.Y", "P.Z", "Z"))]
+        out.append(("id", d_gbuffer["object"], 1, 0, image.EXR_UINT))
+    return sorted(out, key=lambda c: c[0].encode())
+
+
+def exr_layout(channels):
+    return [(s, o, t) for _, _, s, o, t in channels]
+
+
+def _exr_bound(w, h, channels):
+    """exr_stream_bound of a channel list; ValueError for a film too large for one file"""
+    bound = exr_stream_bound(w, h, exr_layout(channels))
+    if not bound:
+        raise ValueError(f"a {w}x{h} EXR file of these {len(channels)} channels reaches 2^31 bytes: write fewer channels or HALF")
+    return bound
+
+
 def _check_display(display):
     if not isinstance(display, Display):
         raise ValueError(f"display must be a Display, got {display!r}")
@@ -107,6 +161,8 @@ class SequencePlan:
     interpolate: object = None
     interp_keys: object = None
     png: str = "host"
+    exr: object = None       # None, or one of EXR_ENCODERS: every frame also writes one EXR file
+    exr_kinds: object = None  # the kinds that file holds: write_channels', in the film's order
 
     def out_res(self, res):
         """The size of the written images of a film of resolution `res`."""
@@ -115,15 +171,16 @@ class SequencePlan:
 
 
 def plan_sequence(channel_kinds, write_channels, transparent_background=False, denoise=None, display=None, upscale=None, supersample=None,
-                  temporal=None, preview=None, interpolate=None, png="host"):
+                  temporal=None, preview=None, interpolate=None, png="host", exr=None):
     """The SequencePlan of render_sequence's arguments for a film of `channel_kinds`: every rule of its docstring that decides what
     runs and what the files are called, and every ValueError it raises before anything renders, in the order it raises them.  Host
     only: no context, no torch, no directory.  `interpolate` must be an Interpolate.  It raises ValueError together with `temporal`,
     with `upscale`, with `supersample` and with `preview`: none of these compositions is built.  It raises ValueError with a
     VarianceDenoise, as every sequence without `temporal` does.  It needs the film's Color channel.  It puts _interp right after
     _color in the name of every Color image of the call, where _temporal would stand.  `png` must be one of PNG_ENCODERS - checked first -
-    and changes no file name."""
+    and changes no file name.  `exr` must be None or one of EXR_ENCODERS - checked right behind it - and changes no PNG."""
     _check_png(png)
+    _check_exr(exr, allow_none=True)
     color = ChannelKind.Color
     variance = isinstance(denoise, VarianceDenoise)
     interp_keys = None
@@ -193,7 +250,7 @@ def plan_sequence(channel_kinds, write_channels, transparent_background=False, d
     scale = "" if upscale is None else f"_x{upscale.factor}"
     jobs = [(kind, bpp, (shown_suffix if kind == color else suffix) + scale) for kind, bpp, suffix in jobs]
     return SequencePlan(denoise, display, upscale, supersample, temporal, variance, up_keys, jobs, bool(transparent_background), preview,
-                        interpolate, interp_keys, png)
+                        interpolate, interp_keys, png, exr, None if exr is None else [k for k in ChannelKind if k in write_channels])
 
 
 class _SequencePost:
@@ -377,20 +434,24 @@ class Film:
         t = self.channels[_CHANNEL_KEY[kind]].cpu().numpy()
         return t.reshape(h, w, 3) if t.ndim == 2 else t.reshape(h, w)
 
+    def _gbuffer_device(self):
+        """gbuffer's device planes (alloc_gbuffer's), enqueued on the current stream.  Under torch.cuda.device."""
+        if self._last_params is None:
+            raise ValueError("the film holds no rendered frame (render_frame_into, render_sequence or render_progressive has not run)")
+        if self._gbuffer is not None and self._gbuffer[0] is self._last_params:
+            return self._gbuffer[1]
+        g = alloc_gbuffer(self.res[0], self.res[1], self.device)
+        self.ctx.gbuffer(self._last_params, g)
+        return g
+
     def gbuffer(self):
         """The primary-hit G-buffer of the last rendered frame (rayn_hip_gbuffer_device, an extension): one centre ray per pixel at the
         frame's time_start through the product closest-hit kernel.  Returns {"position": float32 (h, w, 3), "t": float32 (h, w; +inf for
         a miss), "object": uint32 (h, w; 0xFFFFFFFF for a miss)}, rows bottom-up like the film."""
         import torch
-        if self._last_params is None:
-            raise ValueError("the film holds no rendered frame (render_frame_into, render_sequence or render_progressive has not run)")
         w, h = self.res
         with torch.cuda.device(self.device):
-            if self._gbuffer is not None and self._gbuffer[0] is self._last_params:
-                g = self._gbuffer[1]
-            else:
-                g = alloc_gbuffer(w, h, self.device)
-                self.ctx.gbuffer(self._last_params, g)
+            g = self._gbuffer_device()
             rec = g["records"].cpu().numpy().reshape(h, w, 4)
             obj = g["object"].cpu().numpy().view(np.uint32).reshape(h, w)
         return {"position": rec[..., :3].copy(), "t": rec[..., 3].copy(), "object": obj}
@@ -664,6 +725,37 @@ class Film:
             with open(path, "wb") as f:
                 f.write(image.png_from_stream(w, h, bpp, image.png_stream_of(encoded)))
 
+    def save_exr(self, path, channels=None, half=True, gbuffer=False, transparent_background=False, denoise=None, exr="device"):
+        """Write the float film to `path` as ONE multi-channel OpenEXR file (an extension; scanlines, ZIP compression; include/rayn_hip.h
+        defines the chunks): the kinds `channels`, by default every kind the film holds - without Background under
+        transparent_background, the foreground alone - as the layers R G B (Color; with `denoise`, denoised_color's, as in save_to), A
+        (Alpha), background.R .G .B (kept as its own layer, not added in) and N.X .Y .Z (WorldNormal), HALF or, with half=False, FLOAT,
+        the film's own bits.  gbuffer=True adds gbuffer()'s P.X P.Y P.Z and Z, always FLOAT, and the UINT id (a miss stays 0xFFFFFFFF).
+        exr: "device" encodes the chunks on the GPU (Context.exr_encode) and frames them on the host (image.exr_from_chunks),
+        "device-lz77" the same with LZ77 matches, "host" makes the same file layout with zlib (image.save_exr_host); anything else
+        raises ValueError before anything is written.  A film whose file would reach 2^31 bytes raises ValueError too."""
+        import torch
+        _check_exr(exr)
+        if channels is None and transparent_background:
+            channels = [k for k in self.channel_kinds if k != ChannelKind.Background]
+        kinds = _exr_kinds(self.channel_kinds, channels)
+        if self.channels is None:
+            raise ValueError("the film holds no rendered frame (render_frame_into, render_sequence or render_progressive has not run)")
+        w, h = self.res
+        with torch.cuda.device(self.device):
+            film = self._shown_film(denoise) if ChannelKind.Color in kinds else self.channels
+            chans = exr_channels(kinds, film, half, self._gbuffer_device() if gbuffer else None)
+            bound = _exr_bound(w, h, chans)
+            if exr == "host":
+                image.save_exr_host(path, w, h, [(n, ty, t.reshape(-1).cpu().numpy().view(np.uint32)[o::s][:w * h]) for n, t, s, o, ty in chans])
+                return
+            d_enc = torch.empty(bound, dtype=torch.uint8, device=self.device)
+            self.ctx.exr_encode(w, h, chans, d_enc, lz77=exr == "device-lz77")
+            encoded = d_enc.cpu().numpy()  # waits for the current stream
+        data = image.exr_from_chunks(w, h, [(n, ty) for n, _, _, _, ty in chans], encoded)
+        with open(path, "wb") as f:
+            f.write(data)
+
     def save_hdr(self, path, transparent_background=False):
         """Write the float Color channel to `path` as a little-endian PFM (image.save_pfm; rows bottom-up, like the film): Color +
         Background when the film has a Background and transparent_background is false, as save_to composes them, else Color.  Host only."""
@@ -787,7 +879,7 @@ class Film:
 
     def render_sequence(self, world, camera, integrator, filter, tile_size, frames, frame_rate, shutter_speed, samples, write_channels,
                         output_folder, base_name, transparent_background=False, writers=None, denoise=None, display=None, upscale=None, supersample=None, preview=None,
-                        interpolate=None, png="host", temporal=None):
+                        interpolate=None, png="host", exr=None, exr_half=True, temporal=None):
         """rayn's main loop (src/main.rs:58-96) on the GPU: for each frame of `frames`, render_frame_into at
         frame_start = frame as f32 * (1.0 / frame_rate as f32), frame_end = frame_start + shutter_speed (f32, src/main.rs:61-62), then
         save_to(write_channels, output_folder, f"{base_name}_{frame:04d}", transparent_background).  rayn writes every frame under
@@ -886,12 +978,21 @@ class Film:
         new synchronises.  File names do not change and the files decode to the same pixels; their bytes differ from the host
         encoder's.  png="device-lz77" puts the encoder with LZ77 matches (Context.png_encode_lz77) in the same place, with
         the same buffers and a larger scratch.  Any other value raises ValueError before anything renders.  png="host" is the path
-        described above, unchanged."""
+        described above, unchanged.
+
+        With `exr` ("host", "device" or "device-lz77"; an extension) every frame ALSO writes {base_name}_{frame:04d}.exr, one multi-channel
+        OpenEXR file of the kinds in write_channels as Film.save_exr lays them out (HALF, or FLOAT with exr_half=False): Color from the
+        film the Color PNG is made from - accumulated, denoised, upscaled, generated - before any display transform, the other layers
+        from the film the other images are made from.  With "device" the chunks are encoded on the render stream behind the frame's PNG
+        work (Context.exr_encode), the encoded buffer goes into a pinned slot of its own and a writer thread frames it
+        (image.exr_from_chunks); with "host" the float planes go into pinned slots and the writer thread runs image.save_exr_host.
+        Buffers and scratch are allocated once and nothing new synchronises.  Any other value raises ValueError before anything renders;
+        exr=None leaves every file byte for byte as it is."""
         import concurrent.futures as cf
         import torch
         # the rules about the options alone come first and need nothing of the film, not even its channels (a bare Film.__new__ gets them)
         kinds = getattr(self, "channel_kinds", ())
-        plan = plan_sequence(kinds, write_channels, transparent_background, denoise, display, upscale, supersample, temporal, preview, interpolate, png)
+        plan = plan_sequence(kinds, write_channels, transparent_background, denoise, display, upscale, supersample, temporal, preview, interpolate, png, exr)
         frames = [int(f) for f in frames]
         os.makedirs(output_folder, exist_ok=True)
         w, h = self.res
@@ -914,6 +1015,16 @@ class Film:
         def write_encoded(event, encoded, bpp, path):
             event.synchronize()
             data = image.png_from_stream(ow, oh, bpp, image.png_stream_of(encoded))
+            with open(path, "wb") as f:
+                f.write(data)
+
+        def write_exr(event, held, named, path):
+            event.synchronize()
+            if plan.exr == "host":
+                planes = {k: t.numpy().reshape(-1).view(np.uint32) for k, t in held.items()}
+                image.save_exr_host(path, ow, oh, [(n, ty, a[o::s][:ow * oh]) for n, a, s, o, ty in exr_channels(plan.exr_kinds, planes, exr_half)])
+                return
+            data = image.exr_from_chunks(ow, oh, named, held.numpy())
             with open(path, "wb") as f:
                 f.write(data)
 
@@ -943,6 +1054,16 @@ class Film:
                 if on_device:
                     d_enc = [torch.empty(n, dtype=torch.uint8, device=self.device) for n in h_bytes]
                     d_png_scratch = torch.empty(max((png_scratch_bytes_lz77 if lz77 else png_scratch_bytes)(ow, oh, bpp) for _, bpp, _ in plan.jobs), dtype=torch.uint8, device=self.device)
+
+                if plan.exr is not None:
+                    exr_keys = [_EXR_LAYERS[k][0] for k in plan.exr_kinds]
+                    exr_probe = exr_channels(plan.exr_kinds, dict.fromkeys(exr_keys), exr_half)
+                    exr_named, exr_bound = [(n, ty) for n, _, _, _, ty in exr_probe], _exr_bound(ow, oh, exr_probe)
+                    h_exr = [None, None]  # per slot: the pinned planes ("host", made at the slot's first frame) or the pinned encoded buffer
+                    if plan.exr != "host":
+                        d_exr = torch.empty(exr_bound, dtype=torch.uint8, device=self.device)
+                        d_exr_scratch = torch.empty(exr_scratch_bytes(ow, oh, exr_layout(exr_probe), plan.exr == "device-lz77"), dtype=torch.uint8, device=self.device)
+                        h_exr = [torch.empty(exr_bound, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
 
                 def params_of(frame):
                     start = f32(frame) * inv_rate
@@ -983,8 +1104,21 @@ class Film:
                             self.ctx.png_encode(ow, oh, bpp, d, d_enc[j], d_png_scratch, stream.cuda_stream, lz77)
                             d = d_enc[j]
                         hbuf.copy_(d, non_blocking=True)
+                    if plan.exr is not None:  # behind the frame's PNG work, on the same stream
+                        d_src_exr = dict(d_base, color=d_shown["color"]) if "color" in exr_keys else d_base
+                        if plan.exr == "host":
+                            if h_exr[slot] is None:
+                                h_exr[slot] = {k: torch.empty(d_src_exr[k].shape, dtype=d_src_exr[k].dtype, pin_memory=True) for k in exr_keys}
+                            for k, hbuf in h_exr[slot].items():
+                                hbuf.copy_(d_src_exr[k], non_blocking=True)
+                        else:
+                            self.ctx.exr_encode(ow, oh, exr_channels(plan.exr_kinds, d_src_exr, exr_half), d_exr, d_exr_scratch, stream.cuda_stream,
+                                                plan.exr == "device-lz77")
+                            h_exr[slot].copy_(d_exr, non_blocking=True)
                     done = torch.cuda.Event()
                     done.record(stream)
+                    if plan.exr is not None:
+                        pending[slot].append(write_pool.submit(write_exr, done, h_exr[slot], exr_named, os.path.join(output_folder, f"{base_name}_{frame:04d}.exr")))
                     for (_, bpp, suffix), hbuf in zip(plan.jobs, h_img[slot]):
                         path = os.path.join(output_folder, f"{base_name}_{frame:04d}_{suffix}.png")
                         if on_device:

@@ -1,7 +1,8 @@
 """Film::save_to's per-pixel post-process (src/film.rs:205-378): saturate, gamma 2.2, Color+Background composite,
 Color+Alpha RGBA, normal -> RGB, y-flip, 8-bit quantise.  Host-side, after the hot path.  PNG is written with
 zlib only (the reference uses the `image` crate); png_from_stream frames a zlib stream made elsewhere, the device encoder's
-(Context.png_encode) included.
+(Context.png_encode) included.  The OpenEXR writer at the end of the file is an extension: exr_from_chunks frames the chunks of
+Context.exr_encode, save_exr_host makes the same file layout with zlib on the host.
 
 Arithmetic follows the reference: f32 throughout, `Srgb::saturated` = x.max(0).min(1) and `gamma_corrected(2.2)` =
 x.powf(1/2.2) (src/spectrum.rs:30-40), quantisation `(v * 255.0).min(255.0).max(0.0) as u8` with Rust's f32::min/max
@@ -133,3 +134,120 @@ def load_pfm(path):
             raise ValueError(f"{path} is not a colour PFM")
         w, h = int(dims[0]), int(dims[1])
         return np.frombuffer(f.read(12 * w * h), dtype="<f4" if scale < 0 else ">f4").astype(F32).reshape(h, w, 3)
+
+
+# ---- OpenEXR (an extension: include/rayn_hip.h, "OpenEXR scanline chunks with ZIP compression on the device") ----------------------------
+# Single-part scanline files, ZIP compression (16 rows per chunk), written from the published file layout.  Conformance with real OpenEXR
+# readers is unpinned: no OpenEXR library was at hand.
+
+EXR_UINT, EXR_HALF, EXR_FLOAT = 0, 1, 2
+EXR_ROWS = 16
+
+
+def check_exr_names(names):
+    """The channel names of an EXR file, in its order: bytes-like or str, 1..31 bytes, no NUL, strictly ascending byte-wise.  Returns them
+    as bytes; ValueError otherwise."""
+    out = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    for n in out:
+        if not 1 <= len(n) <= 31 or b"\0" in n:
+            raise ValueError(f"an EXR channel name has 1..31 bytes and no NUL, got {n!r}")
+    for a, b in zip(out, out[1:]):
+        if a == b:
+            raise ValueError(f"EXR channel {a!r} appears twice")
+        if a > b:
+            raise ValueError(f"EXR channels must be sorted by name: {a!r} stands in front of {b!r}")
+    return out
+
+
+def _exr_attr(name, kind, value):
+    return name + b"\0" + kind + b"\0" + struct.pack("<i", len(value)) + value
+
+
+def exr_header(w, h, channels):
+    """Everything of the file in front of the offset table: the magic, the version and the attributes.  channels: (name, type) in the
+    file's order, type one of EXR_UINT, EXR_HALF, EXR_FLOAT."""
+    names = check_exr_names([c[0] for c in channels])
+    if w <= 0 or h <= 0 or not names:
+        raise ValueError("an EXR file has at least one pixel and one channel")
+    for _, t in channels:
+        if t not in (EXR_UINT, EXR_HALF, EXR_FLOAT):
+            raise ValueError(f"an EXR channel type is 0 (UINT), 1 (HALF) or 2 (FLOAT), got {t!r}")
+    chlist = b"".join(n + b"\0" + struct.pack("<iB3xii", t, 0, 1, 1) for n, (_, t) in zip(names, channels)) + b"\0"
+    box = struct.pack("<iiii", 0, 0, w - 1, h - 1)
+    return (b"\x76\x2f\x31\x01" + b"\x02\x00\x00\x00"
+            + _exr_attr(b"channels", b"chlist", chlist)
+            + _exr_attr(b"compression", b"compression", b"\x03")
+            + _exr_attr(b"dataWindow", b"box2i", box)
+            + _exr_attr(b"displayWindow", b"box2i", box)
+            + _exr_attr(b"lineOrder", b"lineOrder", b"\x00")
+            + _exr_attr(b"pixelAspectRatio", b"float", struct.pack("<f", 1.0))
+            + _exr_attr(b"screenWindowCenter", b"v2f", struct.pack("<ff", 0.0, 0.0))
+            + _exr_attr(b"screenWindowWidth", b"float", struct.pack("<f", 1.0))
+            + b"\0")
+
+
+def _exr_file(w, h, channels, starts, body):
+    head = exr_header(w, h, channels)
+    at = len(head) + 8 * len(starts)
+    return head + struct.pack("<%dQ" % len(starts), *(at + s for s in starts)) + bytes(body)
+
+
+def exr_from_chunks(w, h, channels, encoded):
+    """The bytes of the EXR file of what Context.exr_encode wrote (a uint8 array or bytes-like): the header, the offset table - the
+    device's chunk starts plus the length of everything in front of the body - and the body as it is.  ValueError for a buffer that is
+    not one: a chunk count other than the height's, a body past the buffer's end, starts that do not ascend inside it."""
+    m = memoryview(encoded).cast("B")
+    chunks = -(-h // EXR_ROWS)
+    body_at = (16 + 4 * chunks + 15) // 16 * 16
+    if len(m) < body_at:
+        raise ValueError(f"not an encoded EXR body: {len(m)} bytes are less than the header and the table of {chunks} chunks")
+    body, count = struct.unpack("<II", m[:8])
+    if count != chunks or body < 10 * chunks or body_at + body > len(m):
+        raise ValueError(f"not an encoded EXR body: {count} chunks of {body} bytes in a buffer of {len(m)} bytes, {chunks} chunks expected")
+    starts = struct.unpack("<%dI" % chunks, m[16:16 + 4 * chunks])
+    if starts[0] != 0 or any(b - a < 10 for a, b in zip(starts, starts[1:] + (body,))):
+        raise ValueError("not an encoded EXR body: the chunk starts do not ascend inside it")
+    return _exr_file(w, h, channels, starts, m[body_at:body_at + body])
+
+
+def exr_row_bytes(w, h, channels):
+    """(h, S) uint8: the scanlines of the file, top-down.  channels: (name, type, words) with words the channel's h * w 32-bit words in
+    the film's order (rows bottom-up), uint32 or float32; HALF converts them as float32 with numpy's astype(float16)."""
+    parts = []
+    for _, t, words in channels:
+        a = np.ascontiguousarray(words).reshape(h, w)[::-1]
+        if a.dtype.itemsize != 4:
+            raise ValueError("an EXR channel is given as 32-bit words")
+        if t == EXR_HALF:
+            with np.errstate(over="ignore", invalid="ignore"):
+                a = a.view(np.float32).astype(np.float16)
+        parts.append(np.ascontiguousarray(a).view(np.uint8).reshape(h, -1))
+    return np.concatenate(parts, axis=1)
+
+
+def exr_preprocess(raw):
+    """The ZIP pre-process of a chunk's bytes: the even bytes, then the odd ones; then every byte but the first minus its predecessor + 128"""
+    raw = np.asarray(raw, np.uint8)
+    t = np.concatenate([raw[0::2], raw[1::2]]).astype(np.int32)
+    t[1:] = t[1:] - t[:-1] + 128
+    return t.astype(np.uint8)
+
+
+def exr_bytes_host(w, h, channels, level=6):
+    """The file exr="host" writes: the layout of exr_from_chunks with zlib.compress(P, level) per chunk and the same raw rule"""
+    rows = exr_row_bytes(w, h, channels)
+    starts, body = [], b""
+    for y in range(0, h, EXR_ROWS):
+        raw = rows[y:y + EXR_ROWS].tobytes()
+        z = zlib.compress(exr_preprocess(np.frombuffer(raw, np.uint8)).tobytes(), level)
+        payload = raw if len(z) >= len(raw) else z
+        starts.append(len(body))
+        body += struct.pack("<ii", y, len(payload)) + payload
+    return _exr_file(w, h, [(n, t) for n, t, _ in channels], starts, body)
+
+
+def save_exr_host(path, w, h, channels, level=6):
+    """Write exr_bytes_host(w, h, channels) to path"""
+    data = exr_bytes_host(w, h, channels, level)
+    with open(path, "wb") as f:
+        f.write(data)
