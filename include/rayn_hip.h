@@ -1234,6 +1234,15 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *          a padding lane while a later lane is not (lane 0 of a bin packet is always a real hit; a packet of four padding lanes is the tail of a group); a
  *          packet whose valid lanes name different objects; an object at or beyond n_hitables; a sample index at or beyond 4 * samples; a pixel index at or
  *          beyond width * height; a depth above max_bounces.  Only the pool records ref names are looked at. */
+/*   rayn_hip_probe_huffman   the Huffman construction the PNG block kernels share (huffman_code<286> of the literal/length code and huffman_code<30> of the
+ *                             distance code, "PNG encoding on the device" above) alone: one workgroup of 256 threads per count set, through the same template the
+ *                             block kernels instantiate.  n_symbols = 286 or 30; counts[n_sets][n_symbols] = the frequencies, each set summing to less than 2^32
+ *                             (the node weights are 32-bit), 1 <= n_sets <= 65536.  out_clen[n_sets][n_symbols] = the code lengths 0..15 (depths of the tree,
+ *                             frequencies halved while a depth exceeds 15; with fewer than two symbols in use the used one - symbol 0 when there is none - gets 1);
+ *                             out_tab[n_sets][n_symbols] = (the canonical code of RFC 1951 3.2.2, bit-reversed) | length << 16, 0 for an unused symbol.  The encoders
+ *                             themselves are untouched.  RAYN_ERR_INVALID_ARG with a text for anything else. */
+int rayn_hip_probe_huffman(rayn_ctx* ctx, uint32_t n_symbols, uint32_t n_sets, const uint32_t* counts,
+                           uint32_t* out_clen, uint32_t* out_tab);
 int rayn_hip_probe_shade_limits(const rayn_ctx* ctx, uint32_t* stream_blocks, uint32_t* list_ids_per_block,
                                 uint32_t* setup_threads);
 int rayn_hip_probe_shade(rayn_ctx* ctx, const rayn_frame_params* p, const float* samples_1d, const float* samples_2d,

@@ -1,5 +1,5 @@
 // probes.hip — the test probes of the C ABI (rayn_hip_probe_*): per-lane device primitives, the PRODUCT march kernels, the PRODUCT queue stages, the PRODUCT shade and ray-generation stages and the PRODUCT film resolve on caller data.
-// Test infrastructure; defines no kernels (kernels.hip holds the probe kernels).
+// Test infrastructure; the one kernel defined here is k_probe_huffman, a shell around huffman_code of png_device.h (kernels.hip holds the other probe kernels).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -9,6 +9,7 @@
 
 #include "driver.h"
 #include "frame_layout.h"
+#include "png_device.h"
 
 using namespace rayn;
 
@@ -29,6 +30,18 @@ struct ProbeArena : Arena { // the one device allocation of a stage probe call, 
         return hipSuccess;
     }
 };
+
+// One workgroup of PNG_BT threads per count set: huffman_code<N> of png_device.h as the block kernels call it - the counts in LDS, published by its first
+// barrier - and the lengths and table entries it leaves
+template <uint32_t N>
+__global__ __launch_bounds__(PNG_BT) void k_probe_huffman(const uint32_t* __restrict__ counts, uint32_t* __restrict__ clen, uint32_t* __restrict__ tab) {
+    __shared__ uint32_t hist[N];
+    __shared__ HuffmanLds<N> h;
+    const size_t at = (size_t)blockIdx.x * N;
+    for (uint32_t s = threadIdx.x; s < N; s += PNG_BT) hist[s] = counts[at + s];
+    huffman_code(hist, h);
+    for (uint32_t s = threadIdx.x; s < N; s += PNG_BT) clen[at + s] = h.clen[s], tab[at + s] = h.tab[s];
+}
 } // namespace
 
 extern "C" {
@@ -674,6 +687,31 @@ int rayn_hip_probe_raygen(rayn_ctx* ctx, const rayn_frame_params* p, const float
     static_assert(sizeof(DCtl) >= 32, "the eight 32-bit words of DCtl");
     HIPCHK(hipMemcpy(out_ctl, d_ctl, 32, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out_records, d_rec, rec_words * 4, hipMemcpyDeviceToHost));
+    return RAYN_OK;
+}
+
+// huffman_code<286> / huffman_code<30> (png_device.h) on n_sets count sets of n_symbols words each
+int rayn_hip_probe_huffman(rayn_ctx* ctx, uint32_t n_symbols, uint32_t n_sets, const uint32_t* counts, uint32_t* out_clen, uint32_t* out_tab) {
+    if (!ctx) return RAYN_ERR_INVALID_ARG;
+    if (n_symbols != PNG_NSYM && n_symbols != PNG_NDIST) return fail(ctx, RAYN_ERR_INVALID_ARG, "n_symbols must be 286 or 30");
+    if (n_sets == 0 || n_sets > (1u << 16)) return fail(ctx, RAYN_ERR_INVALID_ARG, "probe size out of range");
+    if (!counts || !out_clen || !out_tab) return fail(ctx, RAYN_ERR_INVALID_ARG, "null buffer");
+    const size_t words = (size_t)n_sets * n_symbols;
+    for (uint32_t k = 0; k < n_sets; k++) {
+        uint64_t sum = 0;
+        for (uint32_t s = 0; s < n_symbols; s++) sum += counts[(size_t)k * n_symbols + s];
+        if (sum >> 32) return fail(ctx, RAYN_ERR_INVALID_ARG, "a count set sums to 2^32 or more (32-bit node weights)");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf d_in, d_clen, d_tab;
+    HIPCHK(d_in.alloc(words * 4)); HIPCHK(d_clen.alloc(words * 4)); HIPCHK(d_tab.alloc(words * 4));
+    HIPCHK(hipMemcpy(d_in.p, counts, words * 4, hipMemcpyHostToDevice));
+    if (n_symbols == PNG_NSYM) k_probe_huffman<PNG_NSYM><<<n_sets, PNG_BT, 0, ctx->stream>>>(d_in.as<uint32_t>(), d_clen.as<uint32_t>(), d_tab.as<uint32_t>());
+    else k_probe_huffman<PNG_NDIST><<<n_sets, PNG_BT, 0, ctx->stream>>>(d_in.as<uint32_t>(), d_clen.as<uint32_t>(), d_tab.as<uint32_t>());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out_clen, d_clen.p, words * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_tab, d_tab.p, words * 4, hipMemcpyDeviceToHost));
     return RAYN_OK;
 }
 

@@ -1,7 +1,14 @@
 """The device EXR chunk encoder (include/rayn_hip.h, "OpenEXR scanline chunks with ZIP compression on the device") restated in numpy and
 plain Python: the f32 -> half conversion in integers, the scanline bytes, the ZIP pre-process, every chunk's zlib stream through
 png_np.encode_filtered / png_lz_np.encode_filtered, the raw rule, the buffer the device writes and the file made of it.
-tests/test_exr_device.py asks the kernels for exactly these bytes.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this."""
+tests/test_exr_device.py asks the kernels for exactly these bytes.
+
+`mutant` (None: the statement; the mutants of png_np and png_lz_np pass through to the chunks' streams):
+  E:raw_gt                  a chunk is raw only when its zlib stream is LONGER than its bytes (> for >=): differs at stream == n_k
+  E:raw_size_plus_header    the raw rule compares the blocks' bytes, without the stream's 6 framing bytes (78 01 and the Adler-32)
+  E:last_chunk_full_blocks  the last chunk counted with the blocks of a full chunk: the header's block count of an image whose last chunk
+                            is shorter by a block or more
+TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this."""
 import struct
 
 import numpy as np
@@ -98,24 +105,27 @@ def preprocess(raw):
     return p.astype(np.uint8)
 
 
-def encode_chunk(raw, half_row, matches):
+def encode_chunk(raw, half_row, matches, mutant=None):
     """(payload, raw?, blocks): the zlib stream of the pre-processed bytes, or the bytes themselves when it is not shorter"""
     raw = np.asarray(raw, np.uint8)
     p = preprocess(raw)
-    enc, info = Z.encode_filtered(p, half_row) if matches else P.encode_filtered(p)
+    enc, info = Z.encode_filtered(p, half_row, mutant) if matches else P.encode_filtered(p, mutant)
     z = enc[P.HEADER_BYTES:]
-    if len(z) >= len(raw):
+    size = len(z) - 6 if mutant == "E:raw_size_plus_header" else len(z)
+    if size > len(raw) if mutant == "E:raw_gt" else size >= len(raw):
         return raw.tobytes(), True, len(info)
     return z, False, len(info)
 
 
-def encode(w, h, channels, matches):
+def encode(w, h, channels, matches, mutant=None):
     """What rayn_hip_exr_encode_device writes: the four words, the chunk table, zeros to 16, the body.  info: per chunk (raw?, payload)"""
     rows = scanlines(w, h, channels)
     s = rows.shape[1]
     starts, body, info, blocks = [], b"", [], 0
     for y in range(0, h, ROWS):
-        payload, is_raw, nb = encode_chunk(rows[y:y + ROWS].reshape(-1), s // 2, matches)
+        payload, is_raw, nb = encode_chunk(rows[y:y + ROWS].reshape(-1), s // 2, matches, mutant)
+        if mutant == "E:last_chunk_full_blocks":
+            nb = -(-ROWS * s // P.BLOCK)
         starts.append(len(body))
         body += struct.pack("<ii", y, len(payload)) + payload
         info.append((is_raw, len(payload)))

@@ -1,8 +1,12 @@
 """The LZ77 device encoder's stream (include/rayn_hip.h, "PNG encoding on the device, with LZ77 matches") restated in numpy and plain
 Python on top of png_np: the same filtered stream R, blocks, stored fallback, alignment, Adler-32 and header words; per block the three
 match candidates (distance 1, the last equal trigram, the row above), the greedy parse, and a second Huffman code over the 30 distance
-symbols.  Integer arithmetic throughout; tests/test_png_lz_device.py asks the kernels for exactly these bytes.  TEST INFRASTRUCTURE:
-nothing under rayn_amd/ imports this."""
+symbols.  Integer arithmetic throughout; tests/test_png_lz_device.py asks the kernels for exactly these bytes.
+
+`mutant` (None: the statement; see png_np, whose mutants pass through to the parts shared with it - the length limit, the layout, the
+Adler-32): Z:stored_gt, png_np's P:stored_gt in this block kernel; Z:exit_bit8, the block kernel's exit - the first token start behind the
+128-byte span a token starts in, relative to the span's end, 0..257 - kept in 8 bits: a token that ends 256 or 257 bytes behind its
+span's end sends the parse 256 bytes back, into the bytes the match covers.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this."""
 import struct
 
 import numpy as np
@@ -78,7 +82,10 @@ def best_match(data, i, prev_i, stride):
     return best, dist
 
 
-def block_tokens(blk, stride=0):
+SPAN = 128              # bytes of the block a thread of the block kernel tokenises
+
+
+def block_tokens(blk, stride=0, mutant=None):
     """The tokens of one block, in order, by the greedy parse from 0: ("match", pos, M, D) if M(pos) >= 3 and not (M == 3 and D > 4096),
     else ("lit", pos, byte)"""
     blk = np.asarray(blk, np.uint8)
@@ -88,7 +95,10 @@ def block_tokens(blk, stride=0):
         m, d = best_match(data, p, prev[p], stride)
         if m >= 3 and not (m == 3 and d > FAR):
             out.append(("match", p, m, d))
+            span_end = min((p // SPAN + 1) * SPAN, n)
             p += m
+            if mutant == "Z:exit_bit8" and p - span_end >= 256:
+                p -= 256
         else:
             out.append(("lit", p, data[p]))
             p += 1
@@ -108,22 +118,22 @@ def token_frequencies(tokens):
     return f, g
 
 
-def distance_lengths(freq):
+def distance_lengths(freq, limit=15):
     """(lengths, halvings) of the distance code: png_np's construction over 30 symbols (internal nodes 30, 31, ...), halved on its own;
     with one symbol in use that one gets length 1, with none symbol 0 does - the incomplete code RFC 1951 allows"""
     if not any(freq):
         return [1] + [0] * (N_DISTANCES - 1), 0
-    return P.code_lengths(freq)
+    return P.code_lengths(freq, limit)
 
 
 # ---- blocks and the stream ------------------------------------------------------------------------------------------------------------------
 
-def huffman_block(blk, final, stride=0):
+def huffman_block(blk, final, stride=0, mutant=None):
     """The dynamic-Huffman encoding of a block, zero-padded to a byte and WITHOUT the alignment block: (bytes, bits, info)"""
-    tokens = block_tokens(blk, stride)
+    tokens = block_tokens(blk, stride, mutant)
     freq, dfreq = token_frequencies(tokens)
-    lengths, halvings = P.code_lengths(freq)
-    dlengths, dhalvings = distance_lengths(dfreq)
+    lengths, halvings = P.code_lengths(freq, P.length_limit(mutant))
+    dlengths, dhalvings = distance_lengths(dfreq, P.length_limit(mutant))
     codes, dcodes = P.canonical_codes(lengths), P.canonical_codes(dlengths)
     b = P._Bits()
     b.put(1 if final else 0, 1)
@@ -151,12 +161,12 @@ def huffman_block(blk, final, stride=0):
                             "dhalvings": dhalvings}
 
 
-def encode_block(blk, final, stride=0):
+def encode_block(blk, final, stride=0, mutant=None):
     """(bytes of the block with its alignment, stored?)"""
     blk = np.asarray(blk, np.uint8)
     n = len(blk)
-    data, bits, _ = huffman_block(blk, final, stride)
-    if len(data) >= n + 5:
+    data, bits, _ = huffman_block(blk, final, stride, mutant)
+    if len(data) > n + 5 if mutant == "Z:stored_gt" else len(data) >= n + 5:
         return struct.pack("<BHH", 1 if final else 0, n & 0xFFFF, (n & 0xFFFF) ^ 0xFFFF) + blk.tobytes(), True
     if final:
         return data, False
@@ -164,24 +174,24 @@ def encode_block(blk, final, stride=0):
     return data + b"\x00\x00\xff\xff", False
 
 
-def encode_filtered(r, stride=0):
+def encode_filtered(r, stride=0, mutant=None, block_encoder=None):
     """What rayn_hip_deflate_lz77_device writes for the bytes r with the row stride `stride` (0: no row candidate): the header words and
-    the zlib stream; info: per-block (stored?, bytes)"""
+    the zlib stream; info: per-block (stored?, bytes).  block_encoder(blk, final): as png_np.encode_filtered's."""
     r = np.asarray(r, np.uint8)
     n = len(r)
     blocks = [r[o:o + P.BLOCK] for o in range(0, n, P.BLOCK)]
     parts, info = [], []
     for k, blk in enumerate(blocks):
-        data, stored = encode_block(blk, k == len(blocks) - 1, stride)
+        data, stored = block_encoder(blk, k == len(blocks) - 1) if block_encoder else encode_block(blk, k == len(blocks) - 1, stride, mutant)
         parts.append(data)
         info.append((stored, len(data)))
-    z = b"\x78\x01" + b"".join(parts) + struct.pack(">I", P.adler32(r))
+    z = b"\x78\x01" + P.join_blocks(parts, mutant) + struct.pack(">I", P.adler32(r, mutant))
     head = struct.pack("<IIII", len(z), n, len(blocks), sum(1 for s, _ in info if s))
     return head + z, info
 
 
-def encode(img):
+def encode(img, mutant=None):
     """What rayn_hip_png_encode_lz77_device writes for an 8-bit image (h, w, bpp): the 16-byte header, then the zlib stream"""
     img = np.asarray(img, np.uint8)
     r, _ = P.filter_rows(img)
-    return encode_filtered(r, 1 + img.shape[1] * img.shape[2])[0]
+    return encode_filtered(r, 1 + img.shape[1] * img.shape[2], mutant)[0]

@@ -1,7 +1,17 @@
 """The device PNG encoder's stream (include/rayn_hip.h, "PNG encoding on the device") restated in numpy and plain Python: the adaptive row
 filter, the distance-1 run tokens, one dynamic-Huffman block per BLOCK bytes with the stored fallback, the empty stored blocks that align
 every block to a byte, the Adler-32 and the 16-byte header.  Integer arithmetic throughout; tests/test_png_device.py asks the kernels for
-exactly these bytes.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this."""
+exactly these bytes.
+
+`mutant` (None: the statement) names one deliberate departure, for tests/test_encode_edge_cases.py to show that a named case notices it and
+that the older case tables do not:
+  P:stored_gt         the stored form only when the Huffman form is LONGER (> for >=): differs where both take len + 5 bytes
+  P:limit_16          frequencies halved only while a depth exceeds 16; P:limit_14: while it exceeds 14
+  P:adler_behind_off  the layout kernel's Adler-32 B sum without the (bytes behind the block) * A term for every block that is not the first
+                      of its thread's range [t * chunk, (t + 1) * chunk), chunk = ceil(blocks / 256): the statement itself up to 256 blocks
+  P:layout_carry      the layout kernel's offsets do not advance inside a thread's range: with more than 256 blocks the blocks of a range
+                      land on one another and zeros fill what is left of the stream's length
+A mutant of another module's prefix is ignored here.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this."""
 import heapq
 import struct
 
@@ -185,11 +195,18 @@ class _Bits:
         return self.v.to_bytes((self.n + 7) // 8, "little")
 
 
-def huffman_block(blk, final):
+LAYOUT_THREADS = 256    # of the layout kernel: thread t lays out the blocks [t * chunk, (t + 1) * chunk), chunk = ceil(blocks / 256)
+
+
+def length_limit(mutant=None):
+    return {"P:limit_16": 16, "P:limit_14": 14}.get(mutant, 15)
+
+
+def huffman_block(blk, final, mutant=None):
     """The dynamic-Huffman encoding of a block, zero-padded to a byte and WITHOUT the alignment block: (bytes, bits, info)"""
     tokens = block_tokens(blk)
     freq = token_frequencies(tokens)
-    lengths, halvings = code_lengths(freq)
+    lengths, halvings = code_lengths(freq, length_limit(mutant))
     codes = canonical_codes(lengths)
     has_match = any(t[0] == "match" for t in tokens)
     b = _Bits()
@@ -216,12 +233,12 @@ def huffman_block(blk, final):
     return b.bytes(), b.n, {"tokens": tokens, "freq": freq, "lengths": lengths, "halvings": halvings, "has_match": has_match}
 
 
-def encode_block(blk, final):
+def encode_block(blk, final, mutant=None):
     """(bytes of the block with its alignment, stored?)"""
     blk = np.asarray(blk, np.uint8)
     n = len(blk)
-    data, bits, _ = huffman_block(blk, final)
-    if len(data) >= n + 5:
+    data, bits, _ = huffman_block(blk, final, mutant)
+    if len(data) > n + 5 if mutant == "P:stored_gt" else len(data) >= n + 5:
         return struct.pack("<BHH", 1 if final else 0, n, n ^ 0xFFFF) + blk.tobytes(), True
     if final:
         return data, False
@@ -229,7 +246,7 @@ def encode_block(blk, final):
     return data + b"\x00\x00\xff\xff", False
 
 
-def adler32(r):
+def adler32(r, mutant=None):
     """From the per-block sums the kernels keep: A = sum of the bytes, B = sum of (bytes that follow, the byte included) * byte"""
     r = np.asarray(r, np.uint8).astype(np.uint64)
     n = len(r)
@@ -237,29 +254,52 @@ def adler32(r):
     b = int((r * (n - np.arange(n, dtype=np.uint64))).sum() % ADLER) if n < 1 << 24 else None
     if b is None:
         raise ValueError("stream too long for this restatement")
+    if mutant == "P:adler_behind_off":
+        nblocks = -(-n // BLOCK)
+        chunk = -(-nblocks // LAYOUT_THREADS)
+        for k in range(nblocks):
+            if k % chunk:
+                b -= (n - min((k + 1) * BLOCK, n)) * int(r[k * BLOCK:(k + 1) * BLOCK].sum())
+        b %= ADLER
     return (((n + b) % ADLER) << 16) | ((1 + a) % ADLER)
 
 
-def encode_filtered(r):
-    """The header and the zlib stream of a filtered stream R; info: per-block (stored?, bytes)"""
+def join_blocks(parts, mutant=None):
+    """The encoded blocks one behind the other, as the layout kernel's offsets and the compaction place them"""
+    if mutant != "P:layout_carry":
+        return b"".join(parts)
+    chunk = -(-len(parts) // LAYOUT_THREADS)
+    out = bytearray(sum(len(d) for d in parts))
+    at = first = 0
+    for k, d in enumerate(parts):   # every block of a range at the range's first offset: a later one lies on top of an earlier one
+        if k % chunk == 0:
+            first = at
+        out[first:first + len(d)] = d
+        at += len(d)
+    return bytes(out)
+
+
+def encode_filtered(r, mutant=None, block_encoder=None):
+    """The header and the zlib stream of a filtered stream R; info: per-block (stored?, bytes).  block_encoder(blk, final): a stand-in for
+    encode_block that returns what it would - a cache, for streams of many equal blocks."""
     r = np.asarray(r, np.uint8)
     n = len(r)
     blocks = [r[o:o + BLOCK] for o in range(0, n, BLOCK)]
     parts, info = [], []
     for k, blk in enumerate(blocks):
-        data, stored = encode_block(blk, k == len(blocks) - 1)
+        data, stored = block_encoder(blk, k == len(blocks) - 1) if block_encoder else encode_block(blk, k == len(blocks) - 1, mutant)
         parts.append(data)
         info.append((stored, len(data)))
-    z = b"\x78\x01" + b"".join(parts) + struct.pack(">I", adler32(r))
+    z = b"\x78\x01" + join_blocks(parts, mutant) + struct.pack(">I", adler32(r, mutant))
     head = struct.pack("<IIII", len(z), n, len(blocks), sum(1 for s, _ in info if s))
     return head + z, info
 
 
-def encode(img):
+def encode(img, mutant=None):
     """What rayn_hip_png_encode_device writes for an 8-bit image (h, w, bpp): the 16-byte header, then the zlib stream.  The word holding
     the stream's last byte is zero-padded (see padded)."""
     r, _ = filter_rows(img)
-    return encode_filtered(r)[0]
+    return encode_filtered(r, mutant)[0]
 
 
 def padded(stream):

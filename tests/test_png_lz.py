@@ -98,9 +98,10 @@ def test_the_cases_reach_every_symbol():
 
 def test_distance_code_special_cases_and_its_halving():
     """No block here drives the 30 distance symbols past depth 15: that takes Fibonacci-like counts of 17 symbols, some 4000 matches at
-    chosen distances in one block, and no such block was constructed.  The halving is pinned on the tree function with synthetic counts;
-    on the device one builder (png_device.h) serves both codes and the run-only encoder's, whose halving tests/test_png_device.py's
-    "fibonacci" case runs."""
+    chosen distances in one block, and no such block was constructed.  The halving is pinned here on the tree function with synthetic
+    counts; on the device the distance code's own instantiation of the builder, huffman_code<30> of png_device.h, runs alone through
+    rayn_hip_probe_huffman on the count sets of tests/encode_edge_cases.py - depth 15, depth 16, three and eleven halvings, the tie
+    below, 200 seeded sets - in tests/test_encode_edges_device.py."""
     assert Z.distance_lengths([0] * 30) == ([1] + [0] * 29, 0)
     one = [0] * 30
     one[7] = 12
