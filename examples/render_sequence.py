@@ -48,6 +48,10 @@ total size of the written files is printed for every encoder.
 layers, FLOAT with --exr-float, ZIP-compressed scanlines): device encodes the chunks on the render stream (Context.exr_encode),
 device-lz77 the same with LZ77 matches, host calls zlib in the writer threads.  The PNGs do not change; the EXR files' total size is
 printed on its own.
+--jpeg [Q] also writes a baseline JPEG next to every PNG, same name, .jpg (Film.render_sequence(jpeg=rayn_amd.Jpeg(Q)), an extension: the scan
+is encoded on the render stream, quality Q, default 90, 4:2:0; --jpeg-444 keeps the chroma at full size).  --video PATH also writes one
+Motion-JPEG AVI of the frames' Color image with the same parameters (video=rayn_amd.Video(PATH)); with --no-images the video is all the
+call writes.  The .jpg files' total size and the video's are printed on their own.
 """
 import argparse
 import os
@@ -131,7 +135,20 @@ def main():
                     help="also write one multi-channel OpenEXR file per frame: host (zlib in the writer threads), device (the chunks encoded on the render "
                          "stream) or device-lz77 (the same with LZ77 matches)")
     ap.add_argument("--exr-float", action="store_true", help="write the EXR layers as FLOAT, the film's own bits (default HALF); needs --exr")
+    ap.add_argument("--jpeg", nargs="?", type=int, const=R.Jpeg().quality, default=None, metavar="Q",
+                    help="also write a baseline JPEG next to every PNG, encoded on the render stream, at quality Q (1..100, default 90); with --video alone, the video's quality")
+    ap.add_argument("--jpeg-444", action="store_true", help="keep the chroma at full size (default 4:2:0); needs --jpeg or --video")
+    ap.add_argument("--video", default=None, metavar="PATH", help="also write one Motion-JPEG AVI of the frames' Color image to PATH")
+    ap.add_argument("--no-images", action="store_true", help="write the video alone: no PNG, .jpg or EXR; needs --video")
     args = ap.parse_args()
+    if args.jpeg is not None and not 1 <= args.jpeg <= 100:
+        ap.error("--jpeg must be in 1..100")
+    if args.jpeg_444 and args.jpeg is None and args.video is None:
+        ap.error("--jpeg-444 sets up the JPEG encoder: add --jpeg or --video")
+    if args.no_images and args.video is None:
+        ap.error("--no-images leaves the video alone: add --video")
+    if args.no_images and args.compare_loop:
+        ap.error("--compare-loop compares the image files: it does not combine with --no-images")
     if args.exr_float and args.exr is None:
         ap.error("--exr-float chooses the EXR pixel type: add --exr")
     if args.png != "host" and args.compare_loop:
@@ -190,6 +207,11 @@ def main():
     interpolate = None
     if args.interpolate is not None:
         interpolate = R.Interpolate(args.interpolate, R.Interpolate().depth_tolerance if args.interp_tolerance is None else args.interp_tolerance)
+    jpeg_options = R.Jpeg(R.Jpeg().quality if args.jpeg is None else args.jpeg, "444" if args.jpeg_444 else "420")
+    jpeg = jpeg_options if args.jpeg is not None else None
+
+    def video_at(path):
+        return None if args.video is None else R.Video(path, jpeg_options, not args.no_images)
     first, end = (int(x) for x in args.frames.split(":"))
     frames = list(range(first, end))
     base = f"{SAMPLES * 4}_spp"
@@ -204,17 +226,23 @@ def main():
     # warm-up: code objects, the context's first-frame arena and the writer path (not timed)
     film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames[:1], FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
                          os.path.join(args.out, "warmup"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample, preview=preview,
-                         interpolate=interpolate, png=args.png, exr=args.exr, exr_half=not args.exr_float)
+                         interpolate=interpolate, png=args.png, exr=args.exr, exr_half=not args.exr_float, jpeg=jpeg,
+                         video=video_at(os.path.join(args.out, "warmup", os.path.basename(args.video or ""))))
     t0 = time.perf_counter()
     stats = film.render_sequence(world, cam, integ, filt, S.TILE_SIZE, frames, FRAME_RATE, SHUTTER_SPEED, SAMPLES, WRITE,
                                  os.path.join(args.out, "sequence"), base, writers=args.writers, denoise=denoise, temporal=temporal, display=display, upscale=upscale, supersample=supersample, preview=preview,
-                         interpolate=interpolate, png=args.png, exr=args.exr, exr_half=not args.exr_float)
+                         interpolate=interpolate, png=args.png, exr=args.exr, exr_half=not args.exr_float, jpeg=jpeg, video=video_at(args.video))
     seq_s = time.perf_counter() - t0
     seq_dir = os.path.join(args.out, "sequence")
     pngs, exrs = ([n for n in os.listdir(seq_dir) if n.endswith(ext)] for ext in (".png", ".exr"))
     print(f"--png {args.png}: {sum(os.path.getsize(os.path.join(seq_dir, n)) for n in pngs)} bytes in {len(pngs)} files")
     if args.exr is not None:
         print(f"--exr {args.exr}{' --exr-float' if args.exr_float else ''}: {sum(os.path.getsize(os.path.join(seq_dir, n)) for n in exrs)} bytes in {len(exrs)} files")
+    if jpeg is not None:
+        jpgs = [n for n in os.listdir(seq_dir) if n.endswith(".jpg")]
+        print(f"--jpeg {jpeg}: {sum(os.path.getsize(os.path.join(seq_dir, n)) for n in jpgs)} bytes in {len(jpgs)} files")
+    if args.video is not None:
+        print(f"--video {args.video}{' --no-images' if args.no_images else ''}: {os.path.getsize(args.video)} bytes, {len(frames)} frames of {jpeg_options}")
     if preview is not None:  # the preview is enqueued, not waited for: there is no per-frame render time to report
         print(f"render_sequence --preview {preview}{' --temporal ' + str(temporal) if temporal else ''}{' --denoise ' + str(denoise) if denoise else ''}"
               f"{' --display ' + str(display) if display else ''}: {len(frames)} frames in {seq_s:.3f} s = {len(frames) / seq_s:.2f} frames/s")

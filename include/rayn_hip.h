@@ -971,6 +971,49 @@ int rayn_hip_exr_encode_device(rayn_ctx* ctx, uint32_t width, uint32_t height, u
                                const uint32_t* layout, uint32_t matches, void* d_out, size_t out_bytes, void* d_scratch, size_t scratch_bytes,
                                void* hip_stream);
 
+/* ---- Baseline JPEG scans on the device (an EXTENSION: rayn writes PNG only) -- The entropy-coded scan of a baseline sequential DCT JPEG
+ * (SOF0, 8 bits, JFIF) from the 8-bit image rayn_hip_save_to_pixels_device / rayn_hip_display_pixels_device write (rows top-down, bpp in
+ * {1, 3} bytes per pixel), so that a sequence can leave lossy stills and a Motion-JPEG file.  Integer arithmetic only; tests/jpeg_np.py
+ * restates it and the kernels agree with it byte for byte; libjpeg decodes the files (tests/test_jpeg.py).
+ *   Components.  bpp 1: one component, the byte is Y.  bpp 3: Y, Cb, Cr (ids 1, 2, 3).  subsampling 0 is 4:4:4 (8x8 MCU: Y Cb Cr, or Y
+ *     alone); 1 is 4:2:0 (16x16 MCU: Y00 Y01 Y10 Y11 Cb Cr, Y01 the right neighbour), bpp 3 only.  The image is padded to whole MCUs by
+ *     replicating its last column and row, before conversion and downsampling.
+ *   Colour (int32, >> arithmetic).  Y = (19595 R + 38470 G + 7471 B + 32768) >> 16; Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767)
+ *     >> 16; Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16.  4:2:0 chroma: (a + b + c + d + 2) >> 2 of the 2x2 converted values.
+ *   Transform.  s = sample - 128.  K = {4096, 4017, 3784, 3406, 2896, 2276, 1567, 799} = round(4096 cos(k pi / 16)); T[0][x] = 2896, and
+ *     for u >= 1 T[u][x] = +-K[k] with cos((2x+1) u pi / 16) = +-cos(k pi / 16).  Rows: a[y][u] = (sum_x T[u][x] s[y][x] + 1024) >> 11.
+ *     Columns: F[v][u] = sum_y T[v][y] a[y][u], the coefficient times 2^15.
+ *   Quantisation.  The base tables of ITU T.81 Annex K.1 (Y) and K.2 (Cb, Cr); scale = 5000 / quality below 50, else 200 - 2 quality;
+ *     Q = clamp((base * scale + 50) / 100, 1, 255).  m = (|F| + Q * 16384) / (Q * 32768) with F's sign: ties away from zero.  Zigzag order.
+ *   Entropy code.  The Huffman tables of Annex K.3 - K.6.  DC: the category bit_length(|d|) of the difference d to the previous block of
+ *     the component, then that many bits of d (d + 2^s - 1 when negative).  AC: the code of (run << 4) | size, then the bits; 0xF0 per 16
+ *     zeros in front of a non-zero value; 0x00 iff the block ends in zeros.  Bits most significant first; 00 behind every FF byte.
+ *   Restart intervals.  Segment k is the MCUs [k Ri, min((k + 1) Ri, total)) in raster order, not cut at row ends; predictors start at 0;
+ *     every segment is padded to a byte with 1 bits (an FF made that way is stuffed too); FF D0+(k mod 8) stands between segments k and
+ *     k + 1, nothing behind the last.
+ *   Output.  Four little-endian words - the bytes of the scan, the segments, the restart interval, the blocks - then the scan with its
+ *     markers from byte 16 on, contiguous; the 4-byte word holding its last byte is zero-padded and nothing behind it is written.
+ *     rayn_amd.image.jpeg_from_scan makes the file of it.
+ * rayn_jpeg_scan_bound: the bytes d_out must have: 16 + per segment of n MCUs 2 * ceil(n * mcu_bits / 8) + 2 per marker, rounded up to 16,
+ * where a luminance block is at most 1658 bits and a chrominance block 1660 (the tables' longest codes: csrc/jpeg.h has the derivation)
+ * and the factor 2 is the stuffing.  rayn_jpeg_scratch_bytes: the bytes of d_scratch (coefficients, block sizes, the segments before and
+ * after the stuffing).  rayn_jpeg_quant_table: the 64 scaled entries of table `which` (0 Y, 1 chroma) at `quality`, in zigzag order as a
+ * DQT segment holds them.  rayn_jpeg_huffman_table: BITS into bits[16] and the first min(n, count) HUFFVAL into vals of table `which`
+ * (0 DC Y, 1 AC Y, 2 DC chroma, 3 AC chroma: 2 * id + class); returns the count (12 or 162), -1 for a bad argument.  All host only,
+ * needing no GPU; the sizes are 0 for a geometry the encoder rejects. */
+size_t rayn_jpeg_scan_bound(uint32_t width, uint32_t height, uint32_t bpp, uint32_t subsampling, uint32_t restart_interval);
+size_t rayn_jpeg_scratch_bytes(uint32_t width, uint32_t height, uint32_t bpp, uint32_t subsampling, uint32_t restart_interval);
+int rayn_jpeg_quant_table(uint32_t quality, uint32_t which, uint8_t* out);
+int rayn_jpeg_huffman_table(uint32_t which, uint8_t* bits, uint8_t* vals, uint32_t n);
+/* Enqueue the encoder on 'hip_stream' (NULL = the ctx's own stream; not waited for), on the ctx's GPU.  DEVICE pointers: d_img width *
+ * height * bpp bytes, not modified; d_out and d_scratch 16-byte aligned, of at least the byte counts above.  Four launches and no memset,
+ * whatever the size.  RAYN_ERR_INVALID_ARG with a last error text, and nothing written, for: a zero-sized image or a side above 65535, a
+ * bpp other than 1, 3, a subsampling other than 0, 1 or 1 with bpp 1, a restart_interval outside 1..65535, a bound >= 2^31 (32-bit
+ * offsets), a quality outside 1..100, a NULL buffer, a misaligned or too small d_out or d_scratch, d_out == d_img and buffers that overlap. */
+int rayn_hip_jpeg_encode_device(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t bpp, uint32_t quality, uint32_t subsampling,
+                                uint32_t restart_interval, const uint8_t* d_img, void* d_out, size_t out_bytes, void* d_scratch,
+                                size_t scratch_bytes, void* hip_stream);
+
 /* ---- host-side table builders (the a1/a3/a4 rows of SURVEY.md section 8) ------------------ */
 /* 1 + requested_1d_sample_sets(), 2 + requested_2d_sample_sets() (src/film.rs:431-432,
  * src/integrator.rs:39-45). */

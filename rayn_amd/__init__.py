@@ -3,7 +3,7 @@ integrator hot path, behind rayn's own Film / World / Hitable / Material / Light
 
 The compute path is rayn_amd/csrc/librayn_hip.so (hand-written HIP, C ABI in include/rayn_hip.h);
 this package is the thin host mirror.  There is no CPU fallback."""
-from .film import Bloom, ChannelKind, Context, Denoise, Display, Film, Interpolate, Preview, Progressive, Supersample, Temporal, Upscale, VarianceDenoise, build_tables, progressive_seed  # noqa: F401
+from .film import Bloom, ChannelKind, Context, Denoise, Display, Film, Interpolate, Jpeg, Preview, Progressive, Supersample, Temporal, Upscale, VarianceDenoise, Video, build_tables, progressive_seed  # noqa: F401
 from .params import frame_params  # noqa: F401
 from .scene import (BlackmanHarrisFilter, BoxFilter, LanczosSincFilter, MitchellNetravaliFilter, BoxFold, CameraStore, Dielectric, Emissive, HitableStore, Lambertian, Linear,  # noqa: F401
                     MandelBox, Mandelbulb, MaterialStore, OrthographicCamera, PathTracingIntegrator, PinholeCamera, Sky, Sphere, SphereFold,

@@ -51,6 +51,7 @@ EXPORTS = [
     "rayn_png_scratch_bytes_lz77", "rayn_hip_png_encode_lz77_device",
     "rayn_deflate_stream_bound", "rayn_deflate_scratch_bytes", "rayn_hip_deflate_lz77_device",
     "rayn_exr_stream_bound", "rayn_exr_scratch_bytes", "rayn_hip_exr_encode_device",
+    "rayn_jpeg_scan_bound", "rayn_jpeg_scratch_bytes", "rayn_jpeg_quant_table", "rayn_jpeg_huffman_table", "rayn_hip_jpeg_encode_device",
 ]
 
 
@@ -162,6 +163,12 @@ def lib():
         L.rayn_exr_scratch_bytes.restype = C.c_size_t
         L.rayn_exr_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, up, C.c_uint32]
         L.rayn_hip_exr_encode_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp), up, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, vp]
+        for fn in (L.rayn_jpeg_scan_bound, L.rayn_jpeg_scratch_bytes):
+            fn.restype = C.c_size_t
+            fn.argtypes = [C.c_uint32] * 5
+        L.rayn_jpeg_quant_table.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8)]
+        L.rayn_jpeg_huffman_table.argtypes = [C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_uint32]
+        L.rayn_hip_jpeg_encode_device.argtypes = [vp] + [C.c_uint32] * 6 + [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
         L.rayn_sets_1d.restype = C.c_uint32
         L.rayn_sets_1d.argtypes = [C.c_uint32, C.c_uint32]
         L.rayn_sets_2d.restype = C.c_uint32

@@ -7,6 +7,7 @@ import numpy as np
 from . import _abi
 from . import progressive as _prog
 from ._lib import RaynHipError, lib
+from .options import JPEG_DEFAULT_RESTART
 
 
 def display_scratch_bytes(width, height, levels):
@@ -50,6 +51,43 @@ def png_scratch_bytes(width, height, bpp):
 def png_scratch_bytes_lz77(width, height, bpp):
     """rayn_png_scratch_bytes_lz77: bytes of device scratch Context.png_encode_lz77 needs (0 for a geometry it rejects).  Host only."""
     return int(lib().rayn_png_scratch_bytes_lz77(int(width), int(height), int(bpp)))
+
+
+def _jpeg_args(width, height, bpp, subsampling, restart_interval):
+    a = [int(width), int(height), int(bpp), int(subsampling), int(restart_interval)]
+    return a if all(0 <= v < 1 << 32 for v in a) else None
+
+
+def jpeg_scan_bound(width, height, bpp, subsampling, restart_interval):
+    """rayn_jpeg_scan_bound: the bytes Context.jpeg_encode's output needs: the 16-byte header and the longest scan the tables allow, byte
+    stuffing and restart markers included (0 for a geometry the encoder rejects).  Host only."""
+    a = _jpeg_args(width, height, bpp, subsampling, restart_interval)
+    return int(lib().rayn_jpeg_scan_bound(*a)) if a else 0
+
+
+def jpeg_scratch_bytes(width, height, bpp, subsampling, restart_interval):
+    """rayn_jpeg_scratch_bytes: bytes of device scratch the JPEG encoder needs (0 for a geometry it rejects).  Host only."""
+    a = _jpeg_args(width, height, bpp, subsampling, restart_interval)
+    return int(lib().rayn_jpeg_scratch_bytes(*a)) if a else 0
+
+
+def jpeg_quant_table(quality, which):
+    """rayn_jpeg_quant_table: the 64 entries of quantisation table `which` (0 luminance, 1 chrominance) at `quality`, in the zigzag order
+    of a DQT segment, as bytes.  Host only."""
+    out = (C.c_uint8 * 64)()
+    if not (0 <= int(quality) < 1 << 32 and 0 <= int(which) < 1 << 32) or lib().rayn_jpeg_quant_table(int(quality), int(which), out) != 0:
+        raise ValueError(f"no quantisation table {which!r} at quality {quality!r}: quality is 1..100, the table 0 or 1")
+    return bytes(out)
+
+
+def jpeg_huffman_table(which):
+    """rayn_jpeg_huffman_table: (BITS, HUFFVAL) of Huffman table `which` (0 DC luminance, 1 AC luminance, 2 DC chrominance, 3 AC
+    chrominance), as bytes, as a DHT segment holds them.  Host only."""
+    bits, vals = (C.c_uint8 * 16)(), (C.c_uint8 * 256)()
+    n = lib().rayn_jpeg_huffman_table(int(which), bits, vals, 256) if 0 <= int(which) < 1 << 32 else -1
+    if n < 0:
+        raise ValueError(f"no Huffman table {which!r}: 0..3")
+    return bytes(bits), bytes(vals[:n])
 
 
 def deflate_stream_bound(n):
@@ -540,6 +578,26 @@ class Context:
         d_scratch, scratch_ptr, scratch_bytes = scratch(d_scratch, (png_scratch_bytes_lz77 if lz77 else png_scratch_bytes)(width, height, bpp), d_out.device)
         entry = self._L.rayn_hip_png_encode_lz77_device if lz77 else self._L.rayn_hip_png_encode_device
         self._chk(entry(self.h, int(width), int(height), int(bpp), _ptr(d_img), _ptr(d_out), d_out.numel(), scratch_ptr, scratch_bytes, stream_ptr(stream)))
+
+    def jpeg_encode(self, width, height, bpp, d_img, d_out, quality=90, subsampling=0, restart_interval=JPEG_DEFAULT_RESTART, d_scratch=None, stream=None):
+        """rayn_hip_jpeg_encode_device: the entropy-coded scan of the baseline JPEG of the 8-bit image `d_img` (a uint8 CUDA tensor of
+        width * height * bpp bytes, bpp 1 or 3, rows top-down, as save_to_pixels and display write it) into the uint8 CUDA tensor `d_out`
+        (at least jpeg_scan_bound(width, height, bpp, subsampling, restart_interval) bytes, 16-byte aligned): four little-endian words -
+        the scan's bytes, the restart segments, the restart interval, the blocks - then the scan with its RST markers
+        (rayn_amd.image.jpeg_from_scan frames it as a file).  quality 1..100; subsampling 0 (4:4:4) or 1 (4:2:0, bpp 3 only);
+        restart_interval 1..65535 MCUs.  d_scratch: a CUDA tensor of at least jpeg_scratch_bytes(...) bytes, allocated here when None.
+        Enqueued on the stream, not waited for; d_img is not modified."""
+        import torch
+        need = int(width) * int(height) * int(bpp)
+        bound = jpeg_scan_bound(width, height, bpp, subsampling, restart_interval)
+        for t, label, n in ((d_img, "d_img", need), (d_out, "d_out", bound)):
+            if t is None or not (t.dtype == torch.uint8 and t.is_contiguous() and t.numel() >= n):
+                raise ValueError(f"{label} must be a contiguous uint8 tensor of at least {n} bytes")
+        a = [int(width), int(height), int(bpp), int(quality), int(subsampling), int(restart_interval)]
+        if not all(0 <= v < 1 << 32 for v in a):
+            raise ValueError("width, height, bpp, quality, subsampling and restart_interval are unsigned 32-bit values")
+        d_scratch, scratch_ptr, scratch_bytes = scratch(d_scratch, jpeg_scratch_bytes(width, height, bpp, subsampling, restart_interval), d_out.device)
+        self._chk(self._L.rayn_hip_jpeg_encode_device(self.h, *a, _ptr(d_img), _ptr(d_out), d_out.numel(), scratch_ptr, scratch_bytes, stream_ptr(stream)))
 
     def exr_encode(self, width, height, channels, d_out, d_scratch=None, stream=None, lz77=False):
         """rayn_hip_exr_encode_device: the ZIP-compressed scanline chunks of the OpenEXR file of `channels` - a list of (name, tensor,

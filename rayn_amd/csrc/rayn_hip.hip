@@ -30,6 +30,7 @@
 #include "post_checks.h"
 #include "preview.h"
 #include "interpolate.h"
+#include "jpeg.h"
 #include "png.h"
 #include "exr.h"
 #include "progressive.h"
@@ -1171,6 +1172,16 @@ int rayn_hip_exr_encode_device(rayn_ctx* ctx, uint32_t w, uint32_t h, uint32_t n
     hipStream_t s;
     if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
     HIPCHK(launch_exr_encode(s, w, h, n_channels, d_planes, layout, matches, d_out, d_scratch));
+    return post_enqueued(ctx);
+}
+
+// The JPEG scan encoder (jpeg.hip): the 8-bit image of save_to_pixels / display_pixels -> the entropy-coded scan behind a 16-byte header.
+int rayn_hip_jpeg_encode_device(rayn_ctx* ctx, uint32_t w, uint32_t h, uint32_t bpp, uint32_t quality, uint32_t subsampling, uint32_t restart_interval,
+                                const uint8_t* d_img, void* d_out, size_t out_bytes, void* d_scratch, size_t scratch_bytes, void* hip_stream) {
+    const char* why = jpeg_check_args(w, h, bpp, quality, subsampling, restart_interval, d_img, d_out, out_bytes, d_scratch, scratch_bytes);
+    hipStream_t s;
+    if (int rc = post_enter(ctx, why, hip_stream, &s)) return rc;
+    launch_jpeg_encode(s, jpeg_geometry(w, h, bpp, subsampling, restart_interval), quality, d_img, d_out, d_scratch);
     return post_enqueued(ctx);
 }
 

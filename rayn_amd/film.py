@@ -80,6 +80,36 @@ def _check_png(png):
     return png
 
 
+def _check_jpeg(jpeg):
+    if not isinstance(jpeg, Jpeg):
+        raise ValueError(f"jpeg must be a Jpeg, got {jpeg!r}")
+
+
+def _jpeg_jobs(jobs):
+    """`jobs` ((kind, bytes per pixel, suffix)) if every image has a JPEG form; ValueError for one with 4 bytes per pixel"""
+    for kind, bpp, _ in jobs:
+        if bpp == 4:
+            raise ValueError(f"Attempted to write the {kind.name} image with alpha as a JPEG: JPEG has no alpha (transparent_background)")
+    return jobs
+
+
+def _check_sequence_jpeg(plan, write_channels, jpeg, video):
+    """render_sequence's jpeg= and video= against its plan, before anything renders: (index of the job the video shows or None, whether
+    the call writes its image files)"""
+    if jpeg is not None:
+        _check_jpeg(jpeg)
+        _jpeg_jobs(plan.jobs)
+    if video is None:
+        return None, True
+    if not isinstance(video, Video):
+        raise ValueError(f"video must be a Video, got {video!r}")
+    shown = [j for j, (kind, _, _) in enumerate(plan.jobs) if kind == ChannelKind.Color]
+    if not shown:
+        raise ValueError("video= shows the sequence's Color image: name ChannelKind.Color in write_channels")
+    _jpeg_jobs([plan.jobs[shown[0]]])
+    return shown[0], video.images
+
+
 EXR_ENCODERS = ("host", "device", "device-lz77")
 # the layers of an EXR file: kind -> (the device film's key, the channel names of the plane's words in order)
 _EXR_LAYERS = {ChannelKind.Color: ("color", ("R", "G", "B")), ChannelKind.Alpha: ("alpha", ("A",)),
@@ -725,6 +755,30 @@ class Film:
             with open(path, "wb") as f:
                 f.write(image.png_from_stream(w, h, bpp, image.png_stream_of(encoded)))
 
+    def save_jpeg(self, write_channels, output_folder, base_name, jpeg=Jpeg(), denoise=None, display=None, transparent_background=False):
+        """save_to's images as baseline JPEG files (an extension): {base_name}_{suffix}.jpg with save_to's suffixes, the scan encoded on
+        the device (Context.jpeg_encode with the Jpeg `jpeg`) and framed by image.jpeg_from_scan.  A grey image (Alpha) has one form and
+        ignores the subsampling.  JPEG has no alpha: a kind whose image has 4 bytes per pixel - Color under transparent_background -
+        raises ValueError, like a `jpeg` that is no Jpeg and a channel save_to rejects, before anything is written."""
+        import torch
+        _check_jpeg(jpeg)
+        jobs = _jpeg_jobs(self._save_jobs(list(write_channels), transparent_background))
+        os.makedirs(output_folder, exist_ok=True)
+        w, h = self.res
+        for kind, bpp, suffix in jobs:
+            if denoise is not None and kind == ChannelKind.Color:
+                suffix = "color_denoised"
+            if display is not None and kind == ChannelKind.Color:
+                suffix += "_display"
+            sub = jpeg.mode(bpp)
+            with torch.cuda.device(self.device):
+                d_img, bpp = self._pixels_device(kind, transparent_background, denoise, display)
+                d_enc = torch.empty(jpeg_scan_bound(w, h, bpp, sub, jpeg.restart), dtype=torch.uint8, device=self.device)
+                self.ctx.jpeg_encode(w, h, bpp, d_img, d_enc, jpeg.quality, sub, jpeg.restart)
+                encoded = d_enc.cpu().numpy()  # waits for the current stream
+            with open(os.path.join(output_folder, f"{base_name}_{suffix}.jpg"), "wb") as f:
+                f.write(image.jpeg_from_scan(w, h, bpp, jpeg, encoded))
+
     def save_exr(self, path, channels=None, half=True, gbuffer=False, transparent_background=False, denoise=None, exr="device"):
         """Write the float film to `path` as ONE multi-channel OpenEXR file (an extension; scanlines, ZIP compression; include/rayn_hip.h
         defines the chunks): the kinds `channels`, by default every kind the film holds - without Background under
@@ -879,7 +933,7 @@ class Film:
 
     def render_sequence(self, world, camera, integrator, filter, tile_size, frames, frame_rate, shutter_speed, samples, write_channels,
                         output_folder, base_name, transparent_background=False, writers=None, denoise=None, display=None, upscale=None, supersample=None, preview=None,
-                        interpolate=None, png="host", exr=None, exr_half=True, temporal=None):
+                        interpolate=None, png="host", exr=None, exr_half=True, jpeg=None, video=None, temporal=None):
         """rayn's main loop (src/main.rs:58-96) on the GPU: for each frame of `frames`, render_frame_into at
         frame_start = frame as f32 * (1.0 / frame_rate as f32), frame_end = frame_start + shutter_speed (f32, src/main.rs:61-62), then
         save_to(write_channels, output_folder, f"{base_name}_{frame:04d}", transparent_background).  rayn writes every frame under
@@ -987,16 +1041,37 @@ class Film:
         work (Context.exr_encode), the encoded buffer goes into a pinned slot of its own and a writer thread frames it
         (image.exr_from_chunks); with "host" the float planes go into pinned slots and the writer thread runs image.save_exr_host.
         Buffers and scratch are allocated once and nothing new synchronises.  Any other value raises ValueError before anything renders;
-        exr=None leaves every file byte for byte as it is."""
+        exr=None leaves every file byte for byte as it is.
+
+        With `jpeg` (a Jpeg, an extension) every PNG of the call also gets a baseline JPEG next to it, same name, .jpg: after the image's
+        post-process kernel the encoder (Context.jpeg_encode) goes on the render stream, the encoded buffer - jpeg_scan_bound bytes -
+        goes into a pinned slot of its own and a writer thread frames the scan (image.jpeg_from_scan).  With `video` (a Video) the call
+        also writes ONE Motion-JPEG AVI (image.AviWriter, at frame_rate) of the frame's shown Color image - the image whose PNG carries
+        _color... in its name, after denoise, display, upscale, preview and interpolate - so write_channels must name Color.  Its frames
+        are byte for byte what jpeg=video.jpeg writes for that image; they reach the file in frame order through one writer thread of
+        their own, and the file is closed - and plays as far as it got - also when the call raises.  Where jpeg= and video.jpeg are equal the image is encoded once for both.  Video(images=False) is the one
+        switch that removes files: no PNG, .jpg or EXR is written, only the video.  JPEG has no alpha: under transparent_background a
+        Color image raises ValueError, like every wrong value, before anything renders.  With jpeg=None and video=None every file is
+        byte for byte as it is."""
         import concurrent.futures as cf
         import torch
         # the rules about the options alone come first and need nothing of the film, not even its channels (a bare Film.__new__ gets them)
         kinds = getattr(self, "channel_kinds", ())
         plan = plan_sequence(kinds, write_channels, transparent_background, denoise, display, upscale, supersample, temporal, preview, interpolate, png, exr)
+        video_job, images = _check_sequence_jpeg(plan, write_channels, jpeg, video)
         frames = [int(f) for f in frames]
         os.makedirs(output_folder, exist_ok=True)
         w, h = self.res
         ow, oh = plan.out_res(self.res)
+        # the JPEG encodes of a frame: [job, its Jpeg, whether a .jpg is written, whether it is the video's frame]; where jpeg= and
+        # video= agree on the options the Color image is encoded once and goes to both
+        jpeg_work = [[j, jpeg, True, False] for j in range(len(plan.jobs))] if (jpeg is not None and images) else []
+        if video is not None:
+            if jpeg_work and video.jpeg == jpeg:
+                jpeg_work[video_job][3] = True
+            else:
+                jpeg_work.append([video_job, video.jpeg, False, True])
+        avi = None
         f32 = np.float32
         inv_rate, shutter = f32(1.0) / f32(frame_rate), f32(shutter_speed)
         if plan.preview is not None and integrator is None:
@@ -1007,6 +1082,7 @@ class Film:
         stats, pending = [], [[], []]  # pending[slot]: writer futures still reading that slot's pinned images
         table_pool = cf.ThreadPoolExecutor(max_workers=1, thread_name_prefix="rayn-rd-tables")
         write_pool = cf.ThreadPoolExecutor(max_workers=n_writers, thread_name_prefix="rayn-png")
+        video_pool = cf.ThreadPoolExecutor(max_workers=1, thread_name_prefix="rayn-avi")  # one thread: the frames keep their order
 
         def write(event, img, path):
             event.synchronize()
@@ -1028,6 +1104,16 @@ class Film:
             with open(path, "wb") as f:
                 f.write(data)
 
+        def write_jpeg(event, encoded, bpp, options, path):
+            """The framed file of an encoded scan to `path`, or into the video for None"""
+            event.synchronize()
+            data = image.jpeg_from_scan(ow, oh, bpp, options, encoded)
+            if path is None:
+                avi.add(data)
+                return
+            with open(path, "wb") as f:
+                f.write(data)
+
         def wait_slot(slot):
             for fut in pending[slot]:
                 fut.result()  # re-raises a writer's exception
@@ -1036,6 +1122,8 @@ class Film:
         try:
             if not frames:
                 return stats
+            if video is not None:
+                avi = image.AviWriter(video.path, ow, oh, frame_rate)
             with torch.cuda.device(self.device):
                 stream = torch.cuda.current_stream()
                 desc = world.to_desc(camera)
@@ -1045,17 +1133,25 @@ class Film:
                 rendered = frames if itp is None else [f for i, f in enumerate(frames) if itp.is_key(i, len(frames))]
                 tables = None if plan.preview is not None else RdTablePrefetch(table_pool, rendered, spp, mb, vm, w, h, filter, self.device)
                 d_film = alloc_device_film(w, h, self.device)
-                d_img = [torch.empty(oh * ow * bpp, dtype=torch.uint8, device=self.device) for _, bpp, _ in plan.jobs]
+                # the video alone: only the image it shows is made, and nothing of the PNG path is allocated
+                d_img = [torch.empty(oh * ow * bpp if (images or j == video_job) else 0, dtype=torch.uint8, device=self.device)
+                         for j, (_, bpp, _) in enumerate(plan.jobs)]
                 post = _SequencePost(self, plan, desc, d_film)
-                on_device, lz77 = plan.png != "host", plan.png == "device-lz77"
+                on_device, lz77 = images and plan.png != "host", plan.png == "device-lz77"
                 # what goes to the host per image: the raw image, or the encoder's output (its scratch serves every image in turn)
-                h_bytes = [png_stream_bound(ow, oh, bpp) if on_device else oh * ow * bpp for _, bpp, _ in plan.jobs]
-                h_img = [[torch.empty(n, dtype=torch.uint8, pin_memory=True) for n in h_bytes] for _ in range(2)]
+                h_bytes = [0 if not images else png_stream_bound(ow, oh, bpp) if on_device else oh * ow * bpp for _, bpp, _ in plan.jobs]
+                h_img = [[torch.empty(n, dtype=torch.uint8, pin_memory=n > 0) for n in h_bytes] for _ in range(2)]
                 if on_device:
                     d_enc = [torch.empty(n, dtype=torch.uint8, device=self.device) for n in h_bytes]
                     d_png_scratch = torch.empty(max((png_scratch_bytes_lz77 if lz77 else png_scratch_bytes)(ow, oh, bpp) for _, bpp, _ in plan.jobs), dtype=torch.uint8, device=self.device)
 
-                if plan.exr is not None:
+                if jpeg_work:
+                    jpeg_geo = [(plan.jobs[j][1], o.mode(plan.jobs[j][1]), o.restart) for j, o, _, _ in jpeg_work]
+                    d_jpeg = [torch.empty(jpeg_scan_bound(ow, oh, bpp, sub, ri), dtype=torch.uint8, device=self.device) for bpp, sub, ri in jpeg_geo]
+                    h_jpeg = [[torch.empty(d.numel(), dtype=torch.uint8, pin_memory=True) for d in d_jpeg] for _ in range(2)]
+                    d_jpeg_scratch = torch.empty(max(jpeg_scratch_bytes(ow, oh, bpp, sub, ri) for bpp, sub, ri in jpeg_geo), dtype=torch.uint8, device=self.device)
+
+                if plan.exr is not None and images:
                     exr_keys = [_EXR_LAYERS[k][0] for k in plan.exr_kinds]
                     exr_probe = exr_channels(plan.exr_kinds, dict.fromkeys(exr_keys), exr_half)
                     exr_named, exr_bound = [(n, ty) for n, _, _, _, ty in exr_probe], _exr_bound(ow, oh, exr_probe)
@@ -1099,12 +1195,20 @@ class Film:
                     wait_slot(slot)
                     d_shown, d_base = post.enqueue(i, p, stream.cuda_stream, d_src)
                     for j, ((kind, bpp, _), d, hbuf) in enumerate(zip(plan.jobs, d_img, h_img[slot])):
+                        if not images and j != video_job:
+                            continue
                         post.pixels(kind, start, d_shown if kind == ChannelKind.Color else d_base, d, stream.cuda_stream)
+                        for n, (jj, o, _, _) in enumerate(jpeg_work):  # behind the image's post-process kernel, on the same stream
+                            if jj == j:
+                                self.ctx.jpeg_encode(ow, oh, bpp, d, d_jpeg[n], o.quality, o.mode(bpp), o.restart, d_jpeg_scratch, stream.cuda_stream)
+                                h_jpeg[slot][n].copy_(d_jpeg[n], non_blocking=True)
+                        if not images:
+                            continue
                         if on_device:
                             self.ctx.png_encode(ow, oh, bpp, d, d_enc[j], d_png_scratch, stream.cuda_stream, lz77)
                             d = d_enc[j]
                         hbuf.copy_(d, non_blocking=True)
-                    if plan.exr is not None:  # behind the frame's PNG work, on the same stream
+                    if plan.exr is not None and images:  # behind the frame's PNG work, on the same stream
                         d_src_exr = dict(d_base, color=d_shown["color"]) if "color" in exr_keys else d_base
                         if plan.exr == "host":
                             if h_exr[slot] is None:
@@ -1117,6 +1221,15 @@ class Film:
                             h_exr[slot].copy_(d_exr, non_blocking=True)
                     done = torch.cuda.Event()
                     done.record(stream)
+                    for n, (jj, o, to_file, to_video) in enumerate(jpeg_work):
+                        _, bpp, suffix = plan.jobs[jj]
+                        if to_file:
+                            path = os.path.join(output_folder, f"{base_name}_{frame:04d}_{suffix}.jpg")
+                            pending[slot].append(write_pool.submit(write_jpeg, done, h_jpeg[slot][n].numpy(), bpp, o, path))
+                        if to_video:
+                            pending[slot].append(video_pool.submit(write_jpeg, done, h_jpeg[slot][n].numpy(), bpp, o, None))
+                    if not images:
+                        return
                     if plan.exr is not None:
                         pending[slot].append(write_pool.submit(write_exr, done, h_exr[slot], exr_named, os.path.join(output_folder, f"{base_name}_{frame:04d}.exr")))
                     for (_, bpp, suffix), hbuf in zip(plan.jobs, h_img[slot]):
@@ -1155,4 +1268,7 @@ class Film:
         finally:
             # on success everything has been waited for already; on an error this joins the threads before it propagates
             write_pool.shutdown(wait=True, cancel_futures=True)
+            video_pool.shutdown(wait=True, cancel_futures=True)
             table_pool.shutdown(wait=True, cancel_futures=True)
+            if avi is not None:
+                avi.close()  # also after an error: what was written plays

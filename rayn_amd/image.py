@@ -251,3 +251,121 @@ def save_exr_host(path, w, h, channels, level=6):
     data = exr_bytes_host(w, h, channels, level)
     with open(path, "wb") as f:
         f.write(data)
+
+
+# ---- JPEG and Motion-JPEG (an extension: include/rayn_hip.h, "Baseline JPEG scans on the device") ----------------------------------------
+# jpeg_from_scan frames the scan of Context.jpeg_encode with the library's own tables; AviWriter puts such files into an AVI container,
+# written from its published layout.  No player was at hand: tests/avi_read.py, a reader written from the same layout, is all that pins it.
+
+def _jpeg_segment(marker, payload):
+    return bytes((0xFF, marker)) + struct.pack(">H", len(payload) + 2) + payload
+
+
+def jpeg_from_scan(w, h, bpp, jpeg, encoded):
+    """The bytes of the baseline JPEG file of a w x h image of bpp (1 grey, 3 colour) bytes per pixel around what Context.jpeg_encode wrote
+    with the parameters `jpeg` (a Jpeg; 4:2:0 holds for bpp 3 only): SOI, APP0 JFIF 1.1, DQT per table, SOF0, DHT per table, DRI, SOS,
+    the scan, EOI.  The tables are the library's (jpeg_quant_table, jpeg_huffman_table).  ValueError for a bpp without a JPEG form, a size
+    the format has no field for, and a buffer that is not what that call writes: header words that disagree with the geometry or a scan
+    past the buffer's end."""
+    from .context import jpeg_huffman_table, jpeg_quant_table
+    from .options import Jpeg
+    if not isinstance(jpeg, Jpeg):
+        raise ValueError(f"jpeg must be a Jpeg, got {jpeg!r}")
+    if bpp not in (1, 3):
+        raise ValueError(f"a JPEG holds 1 or 3 bytes per pixel, got {bpp!r} (JPEG has no alpha)")
+    if not (1 <= w <= 65535 and 1 <= h <= 65535):
+        raise ValueError(f"a JPEG has 1..65535 columns and rows, got {w}x{h}")
+    sub, n = jpeg.mode(bpp), 1 if bpp == 1 else 3
+    side = 16 if sub else 8
+    mcus = -(-w // side) * -(-h // side)
+    m = memoryview(encoded).cast("B")
+    if len(m) < 16:
+        raise ValueError(f"not an encoded scan: {len(m)} bytes are less than the header")
+    scan, segments, ri, blocks = struct.unpack("<4I", m[:16])
+    if ri != jpeg.restart or segments != -(-mcus // ri) or blocks != mcus * (1 if n == 1 else 6 if sub else 3):
+        raise ValueError(f"not the scan of a {w}x{h} image of {bpp} bytes per pixel with {jpeg}: {segments} segments at interval {ri}, {blocks} blocks")
+    if scan < segments or 16 + scan > len(m):
+        raise ValueError(f"not an encoded scan: length word {scan} in a buffer of {len(m)} bytes")
+    out = [b"\xff\xd8", _jpeg_segment(0xE0, b"JFIF\0" + bytes((1, 1, 0, 0, 1, 0, 1, 0, 0)))]
+    out += [_jpeg_segment(0xDB, bytes((t,)) + jpeg_quant_table(jpeg.quality, t)) for t in range(2 if n == 3 else 1)]
+    comps = b"".join(bytes((i + 1, 0x22 if (sub and i == 0) else 0x11, 1 if i else 0)) for i in range(n))
+    out.append(_jpeg_segment(0xC0, struct.pack(">BHHB", 8, h, w, n) + comps))
+    for which in range(4 if n == 3 else 2):  # DC 0, AC 0, DC 1, AC 1
+        bits, vals = jpeg_huffman_table(which)
+        out.append(_jpeg_segment(0xC4, bytes((((which & 1) << 4) | (which >> 1),)) + bits + vals))
+    out.append(_jpeg_segment(0xDD, struct.pack(">H", ri)))
+    out.append(_jpeg_segment(0xDA, bytes((n,)) + b"".join(bytes((i + 1, 0x11 if i else 0x00)) for i in range(n)) + bytes((0, 63, 0))))
+    return b"".join(out) + bytes(m[16:16 + scan]) + b"\xff\xd9"
+
+
+class AviWriter:
+    """A Motion-JPEG AVI file of w x h frames at `frame_rate` frames a second (a number or a Fraction; stored as rate / scale): add(jpeg
+    file bytes) per frame, in order, then close().  RIFF 'AVI ': LIST 'hdrl' (avih with the HASINDEX flag; LIST 'strl' of strh - vids /
+    MJPG - and strf, a 40-byte BITMAPINFOHEADER of 24 bits, MJPG), LIST 'movi' of 00dc chunks padded to even length, idx1 with 16 bytes
+    per frame (keyframe flag, offsets counted from the movi fourcc).  close() patches the sizes and frame counts and appends the index;
+    it is safe to call twice, and runs at the end of a `with` block whatever happened inside, so that what was written plays.  OpenDML is
+    not written: if a frame would take the file past LIMIT (2^31) bytes, add() closes the file and raises ValueError."""
+    LIMIT = 1 << 31
+    _MOVI_AT = 220  # of the movi fourcc: 12 RIFF + 12 LIST hdrl + 64 avih + 12 LIST strl + 64 strh + 48 strf + 8 LIST movi
+
+    def __init__(self, path, w, h, frame_rate):
+        import fractions
+        w, h = int(w), int(h)
+        if not (1 <= w <= 65535 and 1 <= h <= 65535):
+            raise ValueError(f"an MJPG frame has 1..65535 columns and rows, got {w}x{h}")
+        rate = fractions.Fraction(frame_rate).limit_denominator(100000)
+        if not (0 < rate and rate.numerator < 1 << 31):
+            raise ValueError(f"frame_rate must be positive, got {frame_rate!r}")
+        self.path, self.w, self.h, self.rate = path, w, h, rate
+        self.frames, self._index, self._largest, self._closed = 0, [], 0, False
+        self._f = open(path, "wb")
+        self._f.write(self._header())
+        self._pos = self._MOVI_AT + 4
+
+    def _header(self, movi_bytes=4, riff_bytes=0):
+        n, big = self.frames, self._largest
+        usec = round(1000000 / self.rate)
+        per_sec = min(int(big * self.rate) + 1, 0xFFFFFFFF) if n else 0
+        avih = struct.pack("<14I", usec, per_sec, 0, 0x10, n, 0, 1, big, self.w, self.h, 0, 0, 0, 0)
+        strh = b"vids" + b"MJPG" + struct.pack("<IHHIIIIIIII4h", 0, 0, 0, 0, self.rate.denominator, self.rate.numerator, 0, n, big, 0xFFFFFFFF, 0,
+                                               0, 0, self.w, self.h)
+        strf = struct.pack("<IiiHH4sIiiII", 40, self.w, self.h, 1, 24, b"MJPG", self.w * self.h * 3, 0, 0, 0, 0)
+        strl = b"strl" + b"strh" + struct.pack("<I", len(strh)) + strh + b"strf" + struct.pack("<I", len(strf)) + strf
+        hdrl = b"hdrl" + b"avih" + struct.pack("<I", len(avih)) + avih + b"LIST" + struct.pack("<I", len(strl)) + strl
+        head = b"RIFF" + struct.pack("<I", riff_bytes) + b"AVI " + b"LIST" + struct.pack("<I", len(hdrl)) + hdrl + b"LIST" + struct.pack("<I", movi_bytes) + b"movi"
+        assert len(head) == self._MOVI_AT + 4
+        return head
+
+    def add(self, data):
+        if self._closed:
+            raise ValueError("the AVI file is closed")
+        data = bytes(data)
+        padded = len(data) + (len(data) & 1)
+        if self._pos + 8 + padded + 8 + 16 * (self.frames + 1) > self.LIMIT:
+            self.close()
+            raise ValueError(f"frame {self.frames} would take {self.path} past {self.LIMIT} bytes: the file is closed at {self.frames} frames (no OpenDML)")
+        self._f.write(b"00dc" + struct.pack("<I", len(data)) + data + b"\0" * (padded - len(data)))
+        self._index.append((self._pos - self._MOVI_AT, len(data)))
+        self._pos += 8 + padded
+        self.frames += 1
+        self._largest = max(self._largest, len(data))
+
+    def close(self):
+        if self._closed:
+            return
+        self._closed = True
+        try:
+            idx = b"".join(b"00dc" + struct.pack("<III", 0x10, at, n) for at, n in self._index)
+            self._f.write(b"idx1" + struct.pack("<I", len(idx)) + idx)
+            total = self._pos + 8 + len(idx)
+            self._f.seek(0)
+            self._f.write(self._header(self._pos - self._MOVI_AT, total - 8))
+        finally:
+            self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -383,6 +383,48 @@ class Interpolate:
         return _abi.InterpolateParams(float(self.depth_tolerance))
 
 
+JPEG_DEFAULT_RESTART = 32
+
+
+@dataclasses.dataclass(frozen=True)
+class Jpeg:
+    """Parameters of the baseline JPEG encoder (rayn_hip_jpeg_encode_device, an extension: rayn writes PNG only; include/rayn_hip.h has
+    the definition).  quality: IJG's 1..100.  subsampling: "420" (chroma at half size; a grey image has one form and ignores it) or
+    "444".  restart: the restart interval in MCUs, 1..65535 - a format parameter: every interval is a segment the GPU encodes on its
+    own, and costs the file a 2-byte marker, its padding and a DC predictor reset (DESIGN.md section 8 has the measured table behind the
+    default)."""
+    quality: int = 90
+    subsampling: str = "420"
+    restart: int = JPEG_DEFAULT_RESTART
+
+    def __post_init__(self):
+        _int_in("Jpeg", "quality", self.quality, 1, 100)
+        if self.subsampling not in ("420", "444"):
+            raise ValueError(f"Jpeg.subsampling must be '420' or '444', got {self.subsampling!r}")
+        _int_in("Jpeg", "restart", self.restart, 1, 65535)
+
+    def mode(self, bpp):
+        """The encoder's subsampling argument for an image of bpp bytes per pixel: 1 is 4:2:0, 0 is 4:4:4 and what a grey image gets"""
+        return 1 if self.subsampling == "420" and bpp == 3 else 0
+
+
+@dataclasses.dataclass(frozen=True)
+class Video:
+    """A Motion-JPEG AVI of a sequence (render_sequence's video=, an extension): `path` of the file, `jpeg` the encoder's parameters for
+    its frames, images=False to write the video alone - no PNG, .jpg or EXR."""
+    path: str
+    jpeg: Jpeg = Jpeg()
+    images: bool = True
+
+    def __post_init__(self):
+        if not isinstance(self.path, (str, bytes)) and not hasattr(self.path, "__fspath__"):
+            raise ValueError(f"Video.path must be a path, got {self.path!r}")
+        if not isinstance(self.jpeg, Jpeg):
+            raise ValueError(f"Video.jpeg must be a Jpeg, got {self.jpeg!r}")
+        if not isinstance(self.images, bool):
+            raise ValueError(f"Video.images must be a bool, got {self.images!r}")
+
+
 def jittered_camera(camera, jx, jy, time_start):
     """A copy of the rayn_camera `camera` (an _abi.Camera) offset by (jx, jy) pixels of ITS resolution: the centre ray of its pixel
     (x, y) goes through what `camera` sees at the pixel coordinates (x + 0.5 + jx, y + 0.5 + jy).  With the basis u, v, w the camera has
