@@ -1286,6 +1286,19 @@ int64_t rayn_hip_get_trace(const rayn_ctx* ctx, uint32_t* out, uint64_t cap_reco
  *                             themselves are untouched.  RAYN_ERR_INVALID_ARG with a text for anything else. */
 int rayn_hip_probe_huffman(rayn_ctx* ctx, uint32_t n_symbols, uint32_t n_sets, const uint32_t* counts,
                            uint32_t* out_clen, uint32_t* out_tab);
+/*   rayn_hip_probe_jpeg_transform   the first kernel of "Baseline JPEG scans on the device" above alone: img[height][width][bpp] on the HOST -> out_coef[blocks][64],
+ *                             the int16 quantised coefficients in zigzag order, the blocks in the order of the scan (blocks = MCUs * 1, 3 or 6).  At most 2^20 blocks.
+ *   rayn_hip_probe_jpeg_entropy     the other three kernels - Huffman codes per restart segment, stuffing, layout, compaction - on caller coefficients
+ *                             coef[blocks][64] (HOST, the layout above) for an image of that geometry.  The probe owns the output and the scratch and fills both,
+ *                             whole, with fill_byte (0..255) before the kernels run: the encoder has no memset, and must write the same whatever they held.
+ *                             out[out_bytes >= rayn_jpeg_scan_bound] = the bound's bytes: the four header words, the scan, fill_byte behind its last word.
+ *                             Rejected with RAYN_ERR_INVALID_ARG: a DC outside [-1024, 1023] or an |AC| above 1023 - the reach of the 13-bit transform at
+ *                             Q = 1, within which a DC difference is at most category 11 and an AC size 10, the last symbols of the Annex K tables - besides
+ *                             what the entry rejects, a null buffer and more than 2^20 blocks.  RAYN_ERR_HIP with a text if a byte behind either buffer changed. */
+int rayn_hip_probe_jpeg_transform(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t bpp, uint32_t quality, uint32_t subsampling,
+                                  const uint8_t* img, int16_t* out_coef);
+int rayn_hip_probe_jpeg_entropy(rayn_ctx* ctx, uint32_t width, uint32_t height, uint32_t bpp, uint32_t subsampling, uint32_t restart_interval,
+                                const int16_t* coef, uint32_t fill_byte, uint8_t* out, size_t out_bytes);
 int rayn_hip_probe_shade_limits(const rayn_ctx* ctx, uint32_t* stream_blocks, uint32_t* list_ids_per_block,
                                 uint32_t* setup_threads);
 int rayn_hip_probe_shade(rayn_ctx* ctx, const rayn_frame_params* p, const float* samples_1d, const float* samples_2d,

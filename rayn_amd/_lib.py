@@ -34,7 +34,7 @@ EXPORTS = [
     "rayn_hip_render_frame_device", "rayn_hip_get_stats", "rayn_sets_1d", "rayn_sets_2d", "rayn_build_rd_tables",
     "rayn_build_scramble", "rayn_build_fis_table", "rayn_build_fis_table_ex", "rayn_tile_count", "rayn_hip_set_profiling", "rayn_hip_get_eval_counts",
     "rayn_hip_set_batch_paths", "rayn_hip_set_cold_bytes", "rayn_hip_set_workers", "rayn_hip_set_tile_subset", "rayn_hip_set_trace_tile", "rayn_hip_get_trace", "rayn_hip_fma_policy", "rayn_hip_set_fma_policy", "rayn_hip_sizeof", "rayn_hip_probe_sdf_dist",
-    "rayn_hip_probe_extend", "rayn_hip_probe_shadow", "rayn_hip_probe_detmath", "rayn_hip_probe_shading", "rayn_hip_probe_queue", "rayn_hip_probe_resolve", "rayn_hip_probe_march_limits", "rayn_hip_probe_shade", "rayn_hip_probe_shade_limits", "rayn_hip_probe_raygen", "rayn_hip_probe_sdf_dist_as", "rayn_hip_probe_scene_dispatch", "rayn_hip_probe_huffman", "rayn_hip_build_variant",
+    "rayn_hip_probe_extend", "rayn_hip_probe_shadow", "rayn_hip_probe_detmath", "rayn_hip_probe_shading", "rayn_hip_probe_queue", "rayn_hip_probe_resolve", "rayn_hip_probe_march_limits", "rayn_hip_probe_shade", "rayn_hip_probe_shade_limits", "rayn_hip_probe_raygen", "rayn_hip_probe_sdf_dist_as", "rayn_hip_probe_scene_dispatch", "rayn_hip_probe_huffman", "rayn_hip_probe_jpeg_transform", "rayn_hip_probe_jpeg_entropy", "rayn_hip_build_variant",
     "rayn_hip_get_entry_stats", "rayn_hip_get_sdf_iterations", "rayn_hip_get_elision_counts", "rayn_hip_get_stage_slots", "rayn_share_pixels", "rayn_hip_render_frame_packed_device", "rayn_hip_unpack_share_device",
     "rayn_save_to_bpp", "rayn_hip_save_to_pixels_device", "rayn_denoise_scratch_bytes", "rayn_hip_denoise_device",
     "rayn_progressive_seed", "rayn_progressive_state_bytes", "rayn_hip_progressive_reset_device", "rayn_hip_progressive_accumulate_device",
@@ -212,6 +212,8 @@ def lib():
         L.rayn_hip_probe_sdf_dist_as.argtypes = [vp, C.POINTER(_abi.FrameParams), C.c_uint32, C.c_int32, C.c_uint32, C.c_float, fp, fp, C.c_uint32]
         L.rayn_hip_probe_scene_dispatch.argtypes = [vp, C.POINTER(_abi.FrameParams), C.POINTER(C.c_int32)]
         L.rayn_hip_probe_huffman.argtypes = [vp, C.c_uint32, C.c_uint32, up, up, up]
+        L.rayn_hip_probe_jpeg_transform.argtypes = [vp] + [C.c_uint32] * 5 + [vp, vp]
+        L.rayn_hip_probe_jpeg_entropy.argtypes = [vp] + [C.c_uint32] * 5 + [vp, C.c_uint32, vp, C.c_size_t]
         L.rayn_hip_build_variant.restype = C.c_char_p
         L.rayn_hip_build_variant.argtypes = []
         _lib = L

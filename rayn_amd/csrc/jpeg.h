@@ -37,7 +37,12 @@ JpegGeometry jpeg_geometry(uint32_t w, uint32_t h, uint32_t bpp, uint32_t subsam
 // nullptr when the arguments are valid, else the reason (the entry's last error text).  Checks everything but ctx and the stream.
 const char* jpeg_check_args(uint32_t w, uint32_t h, uint32_t bpp, uint32_t quality, uint32_t subsampling, uint32_t restart_interval, const uint8_t* d_img,
                             const void* d_out, size_t out_bytes, const void* d_scratch, size_t scratch_bytes);
-// Enqueue the four kernels on stream s (arguments checked by jpeg_check_args)
+// The two halves of the encoder, which rayn_hip_probe_jpeg_transform and rayn_hip_probe_jpeg_entropy (probes.hip) run alone.
+// launch_jpeg_transform: k_jpeg_transform, the image -> the int16 coefficients at the start of the scratch (64 per block, zigzag, scan order).
+// launch_jpeg_entropy: the segment, layout and compaction kernels, those coefficients -> the header words and the scan in d_out.
+void launch_jpeg_transform(hipStream_t s, const JpegGeometry& g, uint32_t quality, const uint8_t* d_img, void* d_scratch);
+void launch_jpeg_entropy(hipStream_t s, const JpegGeometry& g, void* d_out, void* d_scratch);
+// Enqueue the four kernels on stream s (arguments checked by jpeg_check_args): the two launches above
 void launch_jpeg_encode(hipStream_t s, const JpegGeometry& g, uint32_t quality, const uint8_t* d_img, void* d_out, void* d_scratch);
 
 } // namespace rayn

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void k_jpeg_transform(const uint8_t* __restric
 
 __device__ inline uint32_t bit_length(uint32_t v) { return 32u - (uint32_t)__clz((int)v); } // v != 0
 
-// The codes of one block in order: f(bits, count), count <= 27, the Huffman code in front of the value bits.  pred: the DC predictor.
+// The codes of one block in order: f(bits, count), count <= 26 (a 16-bit AC code and 10 value bits), the Huffman code in front of the value bits.  pred: the DC predictor.
 template <class F>
 __device__ inline void walk_block(const int16_t* __restrict__ c, int pred, uint32_t chroma, F&& f) {
     const uint32_t* dc = d_tables.dc[chroma];
@@ -419,19 +419,29 @@ const char* jpeg_check_args(uint32_t w, uint32_t h, uint32_t bpp, uint32_t quali
     return nullptr;
 }
 
-void launch_jpeg_encode(hipStream_t s, const JpegGeometry& g, uint32_t quality, const uint8_t* d_img, void* d_out, void* d_scratch) {
+static JpegShape shape_of(const JpegGeometry& g) { return {g.width, g.height, g.bpp, g.subsampling, g.bpm, g.mcus_x, g.mcus, g.blocks, g.ri}; }
+
+void launch_jpeg_transform(hipStream_t s, const JpegGeometry& g, uint32_t quality, const uint8_t* d_img, void* d_scratch) {
+    k_jpeg_transform<<<(g.blocks + 3u) / 4u, 256, 0, s>>>(d_img, shape_of(g), quality_scale(quality), (int16_t*)d_scratch);
+}
+
+void launch_jpeg_entropy(hipStream_t s, const JpegGeometry& g, void* d_out, void* d_scratch) {
     uint8_t* sc = (uint8_t*)d_scratch;
-    int16_t* coef = (int16_t*)sc;
+    const int16_t* coef = (const int16_t*)sc;
     uint32_t* bits = (uint32_t*)(sc + g.off_bits);
     uint32_t* meta = (uint32_t*)(sc + g.off_meta);
     uint32_t* offsets = (uint32_t*)(sc + g.off_offsets);
     uint32_t* totals = (uint32_t*)(sc + g.off_totals);
-    const JpegShape sh = {g.width, g.height, g.bpp, g.subsampling, g.bpm, g.mcus_x, g.mcus, g.blocks, g.ri};
-    k_jpeg_transform<<<(g.blocks + 3u) / 4u, 256, 0, s>>>(d_img, sh, quality_scale(quality), coef);
+    const JpegShape sh = shape_of(g);
     k_jpeg_segment<<<g.segments, BT, 0, s>>>(coef, sh, bits, (uint32_t*)(sc + g.off_raw), g.raw_words, sc + g.off_slots, g.slot_bytes, meta);
     k_jpeg_layout<<<1, BT, 0, s>>>(meta, sh, g.segments, offsets, totals, (uint32_t*)d_out);
     const uint32_t max_words = (uint32_t)((g.bound - JPEG_HEADER_BYTES) / 4u);
     k_jpeg_compact<<<(max_words + 255u) / 256u, 256, 0, s>>>(sc + g.off_slots, g.slot_bytes, offsets, totals, g.segments, max_words, (uint32_t*)d_out);
+}
+
+void launch_jpeg_encode(hipStream_t s, const JpegGeometry& g, uint32_t quality, const uint8_t* d_img, void* d_out, void* d_scratch) {
+    launch_jpeg_transform(s, g, quality, d_img, d_scratch);
+    launch_jpeg_entropy(s, g, d_out, d_scratch);
 }
 
 } // namespace rayn

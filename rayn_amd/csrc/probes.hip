@@ -1,5 +1,5 @@
 // probes.hip — the test probes of the C ABI (rayn_hip_probe_*): per-lane device primitives, the PRODUCT march kernels, the PRODUCT queue stages, the PRODUCT shade and ray-generation stages and the PRODUCT film resolve on caller data.
-// Test infrastructure; the one kernel defined here is k_probe_huffman, a shell around huffman_code of png_device.h (kernels.hip holds the other probe kernels).
+// Test infrastructure; the one kernel defined here is k_probe_huffman, a shell around huffman_code of png_device.h (kernels.hip holds the other probe kernels; the JPEG probes launch jpeg.hip's own).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -9,6 +9,7 @@
 
 #include "driver.h"
 #include "frame_layout.h"
+#include "jpeg.h"
 #include "png_device.h"
 
 using namespace rayn;
@@ -712,6 +713,78 @@ int rayn_hip_probe_huffman(rayn_ctx* ctx, uint32_t n_symbols, uint32_t n_sets, c
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out_clen, d_clen.p, words * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out_tab, d_tab.p, words * 4, hipMemcpyDeviceToHost));
+    return RAYN_OK;
+}
+
+// ---- the two halves of the JPEG encoder (jpeg.hip) alone.  Both own their device buffers, with PROBE_GUARD bytes of the fill's complement behind each
+// buffer a kernel writes, looked at after the run.
+constexpr size_t PROBE_GUARD = 64;
+constexpr uint32_t PROBE_JPEG_BLOCKS = 1u << 20; // the probes' own size limit
+static int probe_guard_intact(rayn_ctx* ctx, const void* d_buf, size_t bytes, uint8_t guard, const char* what) {
+    uint8_t h[PROBE_GUARD];
+    HIPCHK(hipMemcpy(h, (const uint8_t*)d_buf + bytes, PROBE_GUARD, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < PROBE_GUARD; k++)
+        if (h[k] != guard) return fail(ctx, RAYN_ERR_HIP, std::string("a kernel wrote behind ") + what);
+    return RAYN_OK;
+}
+
+// k_jpeg_transform alone: the image -> out_coef[blocks][64], int16, zigzag, the blocks in the order of the scan
+int rayn_hip_probe_jpeg_transform(rayn_ctx* ctx, uint32_t w, uint32_t h, uint32_t bpp, uint32_t quality, uint32_t subsampling, const uint8_t* img, int16_t* out_coef) {
+    if (!ctx) return RAYN_ERR_INVALID_ARG;
+    const JpegGeometry g = jpeg_geometry(w, h, bpp, subsampling, 65535u); // the transform does not look at the restart interval
+    if (!g.ok) return fail(ctx, RAYN_ERR_INVALID_ARG, g.why);
+    if (quality < 1u || quality > 100u) return fail(ctx, RAYN_ERR_INVALID_ARG, "quality must be in 1..100");
+    if (g.blocks > PROBE_JPEG_BLOCKS) return fail(ctx, RAYN_ERR_INVALID_ARG, "probe size out of range");
+    if (!img || !out_coef) return fail(ctx, RAYN_ERR_INVALID_ARG, "null buffer");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t img_bytes = (size_t)w * h * bpp, coef_bytes = (size_t)g.blocks * 128u;
+    DevBuf d_img, d_coef;
+    HIPCHK(d_img.alloc(img_bytes)); HIPCHK(d_coef.alloc(coef_bytes + PROBE_GUARD));
+    HIPCHK(hipMemcpy(d_img.p, img, img_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_coef.p, 0xA5, coef_bytes)); HIPCHK(hipMemset(d_coef.as<uint8_t>() + coef_bytes, 0x5A, PROBE_GUARD));
+    HIPCHK(hipDeviceSynchronize()); // the fills above ran on the null stream
+    launch_jpeg_transform(ctx->stream, g, quality, d_img.as<uint8_t>(), d_coef.p);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipGetLastError());
+    if (int rc = probe_guard_intact(ctx, d_coef.p, coef_bytes, 0x5A, "the coefficients")) return rc;
+    HIPCHK(hipMemcpy(out_coef, d_coef.p, coef_bytes, hipMemcpyDeviceToHost));
+    return RAYN_OK;
+}
+
+// k_jpeg_segment, k_jpeg_layout and k_jpeg_compact on caller coefficients: coef[blocks][64] as the transform leaves them -> the first
+// rayn_jpeg_scan_bound bytes of d_out (header words, scan, and fill_byte where nothing was written).  The whole scratch and the output
+// hold fill_byte when the kernels start.  Rejected on the host: a DC outside [-1024, 1023] or an |AC| above 1023 - the reach of the 13-bit
+// transform at Q = 1 (|F| < 2^25, so |m| <= 1024 and only a DC of -1024 is met).  Inside it a DC difference stays within +-2047, category
+// 11, and an AC within size 10, the last symbols the Annex K tables have: beyond it walk_block would index past d_tables.dc or read the 0
+// of a symbol that has no code, and the scan bound would no longer hold.
+int rayn_hip_probe_jpeg_entropy(rayn_ctx* ctx, uint32_t w, uint32_t h, uint32_t bpp, uint32_t subsampling, uint32_t restart_interval, const int16_t* coef,
+                                uint32_t fill_byte, uint8_t* out, size_t out_bytes) {
+    if (!ctx) return RAYN_ERR_INVALID_ARG;
+    const JpegGeometry g = jpeg_geometry(w, h, bpp, subsampling, restart_interval);
+    if (!g.ok) return fail(ctx, RAYN_ERR_INVALID_ARG, g.why);
+    if (g.blocks > PROBE_JPEG_BLOCKS) return fail(ctx, RAYN_ERR_INVALID_ARG, "probe size out of range");
+    if (fill_byte > 255u) return fail(ctx, RAYN_ERR_INVALID_ARG, "fill_byte must be in 0..255");
+    if (!coef || !out) return fail(ctx, RAYN_ERR_INVALID_ARG, "null buffer");
+    if (out_bytes < g.bound) return fail(ctx, RAYN_ERR_INVALID_ARG, "out smaller than rayn_jpeg_scan_bound");
+    for (size_t k = 0; k < (size_t)g.blocks * 64u; k++) {
+        const int v = coef[k];
+        if ((k & 63u) == 0u ? (v < -1024 || v > 1023) : (v < -1023 || v > 1023))
+            return fail(ctx, RAYN_ERR_INVALID_ARG, "a coefficient the encoder cannot produce (DC in -1024..1023, |AC| <= 1023)");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const uint8_t guard = (uint8_t)~fill_byte;
+    DevBuf d_out, d_scr;
+    HIPCHK(d_out.alloc(g.bound + PROBE_GUARD)); HIPCHK(d_scr.alloc(g.scratch_bytes + PROBE_GUARD));
+    HIPCHK(hipMemset(d_out.p, (int)fill_byte, g.bound)); HIPCHK(hipMemset(d_out.as<uint8_t>() + g.bound, guard, PROBE_GUARD));
+    HIPCHK(hipMemset(d_scr.p, (int)fill_byte, g.scratch_bytes)); HIPCHK(hipMemset(d_scr.as<uint8_t>() + g.scratch_bytes, guard, PROBE_GUARD));
+    HIPCHK(hipMemcpy(d_scr.p, coef, (size_t)g.blocks * 128u, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize()); // the fills above ran on the null stream
+    launch_jpeg_entropy(ctx->stream, g, d_out.p, d_scr.p);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipGetLastError());
+    if (int rc = probe_guard_intact(ctx, d_out.p, g.bound, guard, "the output")) return rc;
+    if (int rc = probe_guard_intact(ctx, d_scr.p, g.scratch_bytes, guard, "the scratch")) return rc;
+    HIPCHK(hipMemcpy(out, d_out.p, g.bound, hipMemcpyDeviceToHost));
     return RAYN_OK;
 }
 

@@ -1,6 +1,6 @@
 """Named cases of the baseline JPEG encoder, each with what it must reach on the restatement (tests/jpeg_np.py): cases() builds them
 once - images, parameters, the restatement's Encoded - and asserts every case's claim.  tests/test_jpeg.py runs them on the CPU against
-libjpeg, tests/test_jpeg_device.py on the GPU against the restatement.  mutant_kills() shows that each planted mutant of jpeg_np.MUTANTS is
+libjpeg, tests/test_jpeg_device.py on the GPU against the restatement.  mutant_kills() shows that each planted mutant of MUTANTS (the first six of jpeg_np.MUTANTS) is
 told from the real thing by at least one case.  TEST INFRASTRUCTURE: nothing under rayn_amd/ imports this."""
 import functools
 
@@ -116,9 +116,11 @@ def cases():
 
 
 NAMES = [d[0] for d in _definitions()]
+# the mutants these cases are held against; tests/jpeg_edge_cases.py has the cases for the rest of jpeg_np.MUTANTS
+MUTANTS = ("row_truncates", "ties_toward_zero", "predictor_kept", "marker_unwrapped", "eob_always", "pad_zero")
 
 
 @functools.lru_cache(None)
 def mutant_kills():
     """{mutant: [names of the cases whose scan it changes]}"""
-    return {m: [n for n, c in cases().items() if c.mutant(m).scan != c.ref.scan] for m in J.MUTANTS}
+    return {m: [n for n, c in cases().items() if c.mutant(m).scan != c.ref.scan] for m in MUTANTS}

@@ -3,15 +3,29 @@ definition alone: it shares no code with the library.  Its tables do not come fr
 libjpeg wrote (Pillow, quality 50: scale 100, so the DQT segments hold the Annex K base tables, and the DHT segments the Annex K codes).
 
 encode(img, quality, subsampling, ri) returns an Encoded: the quantised coefficients in scan order, the scan with its markers, what the
-device entry writes (header words + scan, zero-padded to a word) and the file.  `mutant` plants one wrong reading of the definition
-(tests/jpeg_cases.py shows that the cases tell each from the real thing)."""
+device entry writes (header words + scan, zero-padded to a word) and the file.  It is its two halves one after the other, as the
+library's launch is: coefficients(img, quality, subsampling) and entropy(coef, comp, bpp, subsampling, ri), which takes any coefficients
+in scan order (rayn_hip_probe_jpeg_transform and rayn_hip_probe_jpeg_entropy run the same halves on the device).  `mutant` plants one
+wrong reading of the definition (tests/jpeg_cases.py and tests/jpeg_edge_cases.py show that the cases tell each from the real thing)."""
 import functools
 import io
 import struct
 
 import numpy as np
 
-MUTANTS = ("row_truncates", "ties_toward_zero", "predictor_kept", "marker_unwrapped", "eob_always", "pad_zero")
+MUTANTS = ("row_truncates", "ties_toward_zero", "predictor_kept", "marker_unwrapped", "eob_always", "pad_zero",
+           # the readings tests/jpeg_edge_cases.py tells from the definition
+           "zrl_at_most_two",            # a run of 48 or more gets two ZRL codes, and the run code what is left modulo 16
+           "tie_positive_toward_zero",   # the quantiser rounds a positive tie down
+           "ties_toward_zero_above_q1",  # the quantiser rounds ties down wherever Q > 1
+           "chroma_offset_32768",        # Cb and Cr round with + 32768 as Y does
+           "luma_truncates",             # Y without its + 32768
+           "box_truncates",              # the 4:2:0 box without its + 2
+           "pad_unstuffed",              # an FF that the padding completes gets no 00
+           "stuff_one_per_word",         # at most one 00 per four bytes of a segment
+           "y_pred_from_y00",            # 4:2:0: Y00 is predicted from the previous MCU's Y00, not its Y11
+           "first_mcu_resets_every_y",   # 4:2:0: all four Y blocks of a segment's first MCU have the predictor 0
+           "cbcr_share_predictor")       # Cb and Cr share one predictor
 
 K = [4096, 4017, 3784, 3406, 2896, 2276, 1567, 799]
 
@@ -114,7 +128,7 @@ def codes(cls, ident):
     return out
 
 
-def planes(img, subsampling):
+def planes(img, subsampling, mutant=None):
     """The component planes, padded to whole MCUs: [Y] or [Y, Cb, Cr] as int64, chroma at half size in 4:2:0"""
     img = np.asarray(img, np.uint8)
     h, w, bpp = img.shape
@@ -124,11 +138,13 @@ def planes(img, subsampling):
     if bpp == 1:
         return [img[..., 0]]
     R, G, B = img[..., 0], img[..., 1], img[..., 2]
-    out = [(19595 * R + 38470 * G + 7471 * B + 32768) >> 16, (-11059 * R - 21709 * G + 32768 * B + 8388608 + 32767) >> 16,
-           (32768 * R - 27439 * G - 5329 * B + 8388608 + 32767) >> 16]
-    assert all(0 <= p.min() and p.max() <= 255 for p in out)
+    half = 32768 if mutant == "chroma_offset_32768" else 32767
+    out = [(19595 * R + 38470 * G + 7471 * B + (0 if mutant == "luma_truncates" else 32768)) >> 16,
+           (-11059 * R - 21709 * G + 32768 * B + 8388608 + half) >> 16, (32768 * R - 27439 * G - 5329 * B + 8388608 + half) >> 16]
+    assert mutant == "chroma_offset_32768" or all(0 <= p.min() and p.max() <= 255 for p in out)
     if subsampling:
-        out[1:] = [(p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + 2) >> 2 for p in out[1:]]
+        bias = 0 if mutant == "box_truncates" else 2
+        out[1:] = [(p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + bias) >> 2 for p in out[1:]]
     return out
 
 
@@ -150,7 +166,8 @@ def transform(plane, mutant=None):
 def quantise(F, Q, mutant=None):
     """the quantised coefficients of F[..., v, u] in zigzag order: [..., 64]"""
     Q = Q.reshape(8, 8)
-    m = (np.abs(F) + Q * 16384 - (1 if mutant == "ties_toward_zero" else 0)) // (Q * 32768)
+    down = {"ties_toward_zero": 1, "tie_positive_toward_zero": F > 0, "ties_toward_zero_above_q1": Q > 1}.get(mutant, 0)
+    m = (np.abs(F) + Q * 16384 - down) // (Q * 32768)
     return (np.sign(F) * m).reshape(F.shape[:-2] + (64,))[..., ZIGZAG]
 
 
@@ -171,10 +188,11 @@ class Bits:
     """bits, most significant first, into bytes"""
 
     def __init__(self):
-        self.out, self.acc, self.n = bytearray(), 0, 0
+        self.out, self.acc, self.n, self.total, self.log = bytearray(), 0, 0, 0, []
 
     def put(self, v, n):
         assert 0 <= v < (1 << n)
+        self.total += n
         self.acc, self.n = (self.acc << n) | v, self.n + n
         while self.n >= 8:
             self.n -= 8
@@ -196,6 +214,7 @@ def encode_block(bw, c, pred, dc, ac, mutant=None):
     """one block's codes; returns (DC category, largest AC size, ZRLs written, whether an EOB was written)"""
     s, v = _value_bits(int(c[0]) - pred)
     assert s <= 11, "DC category beyond the table"
+    bw.log.append((bw.total, dc[s][1] + s))  # the kernels put a code and its value bits at once: (where, how many bits)
     bw.put(*dc[s])
     if s:
         bw.put(v, s)
@@ -205,17 +224,21 @@ def encode_block(bw, c, pred, dc, ac, mutant=None):
         if x == 0:
             run += 1
             continue
-        while run >= 16:
+        while run >= 16 and not (mutant == "zrl_at_most_two" and zrl == 2):
+            bw.log.append((bw.total, ac[0xF0][1]))
             bw.put(*ac[0xF0])
             run, zrl = run - 16, zrl + 1
+        run &= 15
         s2, v2 = _value_bits(x)
         assert s2 <= 10, "AC size beyond the table"
         big = max(big, s2)
+        bw.log.append((bw.total, ac[(run << 4) | s2][1] + s2))
         bw.put(*ac[(run << 4) | s2])
         bw.put(v2, s2)
         run = 0
     eob = run > 0 or mutant == "eob_always"
     if eob:
+        bw.log.append((bw.total, ac[0x00][1]))
         bw.put(*ac[0x00])
     return s, big, zrl, eob
 
@@ -224,34 +247,60 @@ class Encoded:
     pass
 
 
-def encode(img, quality, subsampling, ri, mutant=None):
-    img = np.asarray(img, np.uint8)
-    h, w, bpp = img.shape
-    assert 1 <= ri <= 65535
-    e = Encoded()
-    e.width, e.height, e.bpp, e.quality, e.subsampling, e.ri = w, h, bpp, quality, subsampling, ri
-    e.planes = planes(img, subsampling)
-    e.Q = [quant_table(quality, 0 if i == 0 else 1) for i in range(len(e.planes))]
-    e.F, e.S = zip(*[transform(p, mutant) for p in e.planes])
-    e.comp_coef = [quantise(F, Q, mutant) for F, Q in zip(e.F, e.Q)]
-    coef, comp = block_order(e.comp_coef, subsampling)
-    e.coef, e.block_comp = coef.astype(np.int16), comp
-    assert (e.coef == coef).all()
+def _stuff(raw, padded, mutant):
+    """The segment's bytes with 00 behind every FF; padded: the padding wrote bits into the last byte"""
+    out = bytearray()
+    for k, b in enumerate(raw):
+        out.append(b)
+        if b == 0xFF:
+            if mutant == "pad_unstuffed" and padded and k == len(raw) - 1:
+                continue
+            if mutant == "stuff_one_per_word" and 0xFF in raw[k & ~3:k]:
+                continue
+            out.append(0)
+    return bytes(out)
+
+
+def entropy(coef, comp, bpp, subsampling, ri, mutant=None, e=None):
+    """The entropy-coded half: coef (blocks, 64) in zigzag and scan order and comp (blocks,), the component of every block, to the scan.
+    Fills an Encoded: scan, header, encoded, segment_bytes (stuffed) and raw_segments (not), stats per block, and what the bit-level cases
+    are about - block_bits [(segment, first bit, bit behind the last)] and puts [(segment, bit, count)] in the segment's unstuffed bits"""
+    coef = np.asarray(coef)
+    assert coef.ndim == 2 and coef.shape[1] == 64 and len(comp) == len(coef) and 1 <= ri <= 65535
+    e = Encoded() if e is None else e
     bpm = {1: 1, 3: 6 if subsampling else 3}[bpp]
+    assert len(coef) % bpm == 0
     total = len(coef) // bpm
+    e.bpp, e.subsampling, e.ri = bpp, subsampling, ri
+    e.coef, e.block_comp = coef.astype(np.int16), np.asarray(comp)
+    assert (e.coef == coef).all()
     e.mcus, e.blocks, e.segments = total, len(coef), -(-total // ri)
-    scan, e.segment_bytes, e.stats = bytearray(), [], []
+    scan, e.segment_bytes, e.raw_segments, e.stats, e.block_bits, e.puts, e.segment_bits = bytearray(), [], [], [], [], [], []
     for k in range(e.segments):
         bw = Bits()
         if not (mutant == "predictor_kept" and k):
             pred = [0, 0, 0]
-        for b in range(k * ri * bpm, min((k + 1) * ri, total) * bpm):
-            c = int(comp[b])
-            e.stats.append(encode_block(bw, coef[b], pred[c], codes(0, 1 if c else 0), codes(1, 1 if c else 0), mutant))
-            pred[c] = int(coef[b][0])
+        first = k * ri * bpm
+        for b in range(first, min((k + 1) * ri, total) * bpm):
+            c, j, at = int(comp[b]), b % bpm, bw.total
+            p = pred[c]
+            if subsampling and c == 0:
+                if mutant == "y_pred_from_y00" and j == 0 and b - first >= bpm:
+                    p = int(coef[b - bpm][0])
+                if mutant == "first_mcu_resets_every_y" and b - first < bpm:
+                    p = 0
+            if mutant == "cbcr_share_predictor" and c:
+                p = pred[1]
+            e.stats.append(encode_block(bw, coef[b], p, codes(0, 1 if c else 0), codes(1, 1 if c else 0), mutant))
+            pred[1 if (mutant == "cbcr_share_predictor" and c) else c] = int(coef[b][0])
+            e.block_bits.append((k, at, bw.total))
+        e.puts += [(k, at, n) for at, n in bw.log]
+        e.segment_bits.append(bw.total)
         e.pad_bits = (8 - bw.n) % 8  # of the last segment, in the end
         bw.pad(ones=mutant != "pad_zero")
-        seg = bytes(bw.out).replace(b"\xff", b"\xff\x00")
+        raw = bytes(bw.out)
+        seg = _stuff(raw, e.pad_bits > 0, mutant)
+        e.raw_segments.append(raw)
         e.segment_bytes.append(seg)
         scan += seg
         if k + 1 < e.segments:
@@ -259,7 +308,29 @@ def encode(img, quality, subsampling, ri, mutant=None):
     e.scan = bytes(scan)
     e.header = (len(e.scan), e.segments, ri, e.blocks)
     e.encoded = struct.pack("<4I", *e.header) + e.scan + b"\0" * (-len(e.scan) % 4)
-    e.file = frame(w, h, bpp, quality, subsampling, ri, e.scan)
+    return e
+
+
+def coefficients(img, quality, subsampling, mutant=None, e=None):
+    """The transform half: the image to the quantised coefficients in scan order (e.coef, e.block_comp), with what led there"""
+    img = np.asarray(img, np.uint8)
+    h, w, bpp = img.shape
+    e = Encoded() if e is None else e
+    e.width, e.height, e.bpp, e.quality, e.subsampling = w, h, bpp, quality, subsampling
+    e.planes = planes(img, subsampling, mutant)
+    e.Q = [quant_table(quality, 0 if i == 0 else 1) for i in range(len(e.planes))]
+    e.F, e.S = zip(*[transform(p, mutant) for p in e.planes])
+    e.comp_coef = [quantise(F, Q, mutant) for F, Q in zip(e.F, e.Q)]
+    coef, comp = block_order(e.comp_coef, subsampling)
+    e.coef, e.block_comp = coef.astype(np.int16), comp
+    assert (e.coef == coef).all()
+    return e
+
+
+def encode(img, quality, subsampling, ri, mutant=None):
+    e = coefficients(img, quality, subsampling, mutant)
+    entropy(e.coef, e.block_comp, e.bpp, subsampling, ri, mutant, e)
+    e.file = frame(e.width, e.height, e.bpp, quality, subsampling, ri, e.scan)
     return e
 
 
